@@ -798,6 +798,38 @@ def compact_line(out, detail_file):
     return text
 
 
+DUMP_LIMIT = 64 << 20         # --dump-outputs: bytes of all .npy files together, every rank's included
+
+
+def _dump_rows(rng, n, row_bytes, budget):
+    """Rows of an [n][...] table that fit in `budget` bytes (with a float64 row index each when sampled): all of them,
+    or a fixed sample drawn from `rng`, in row order."""
+    if n * row_bytes <= budget:
+        return None
+    return np.sort(rng.choice(n, size=budget // (row_bytes + 8), replace=False))
+
+
+def dump_outputs(d, eng, rank, world, seed):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float64 .npy files -- the window table
+    (LIBD0, LIBD1, LIBD2 per window) and the per-site table (LIBD0, LIBD1, LIBD2 per row).  A table over its share of
+    DUMP_LIMIT is written as a sample of rows drawn from --seed (`<name>_rows.npy` holds their indices), so that the same
+    arguments write the same rows.  With N ranks each writes its own files, suffixed `_rank<r>`."""
+    os.makedirs(d, exist_ok=True)
+    budget = DUMP_LIMIT // world
+    sfx = "" if world == 1 else f"_rank{rank}"
+    rng = np.random.default_rng([seed, rank])
+    written = 0
+    for name, table, share in (("window_ll", eng.window_ll(0), budget // 4), ("site_ll", eng.site_ll(0), budget * 3 // 4)):
+        rows = _dump_rows(rng, table.shape[0], table[0].nbytes if table.shape[0] else 0, share)
+        if rows is not None:
+            table = table[rows]
+            np.save(os.path.join(d, f"{name}_rows{sfx}.npy"), rows.astype(np.float64))
+            written += rows.size * 8
+        np.save(os.path.join(d, f"{name}{sfx}.npy"), np.ascontiguousarray(table, dtype=np.float64))
+        written += table.nbytes
+    assert written <= budget, f"--dump-outputs wrote {written} bytes (limit {budget})"
+
+
 def write_detail(out, world):
     """Everything measured, notes included, as indented JSON under gpurun_out/ (merged back from a GPU box); the path is
     relative to the repository root."""
@@ -856,7 +888,12 @@ def main():
                     help="every step runs the SAME comparison individual again (the timed steps of round 4: the individual's images "
                          "are then reused from the step before); default: two individuals in turn, a new one per step")
     ap.add_argument("--opt", action="append", default=[], help="engine option name=value (repeatable)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-window and per-site results of the last timed step to DIR/<name>.npy (float64, "
+                         "at most 64 MB; larger tables as a fixed sample of rows drawn from --seed)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as fresh child
@@ -1051,6 +1088,8 @@ def main():
     ms_ld = [m["ld"] for m in ms_all]
     layout_timed = eng.ld_layout()
     count_unit = eng.last_count_unit()
+    if args.dump_outputs:                       # before any later leg runs the engine again
+        dump_outputs(args.dump_outputs, eng, rank, world, args.seed)
 
     if args.timed_only:
         if rank == 0:

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -220,3 +221,73 @@ def test_the_drivers_command_prints_a_line_it_can_parse():
     assert detail["value"] == pytest.approx(line["value"], rel=1e-5)
     for leg in ("engine_clock", "upload_sites", "many_comparison_individuals", "non_ld", "warm_e2e", "cold_e2e", "sparse_pileup"):
         assert detail.get(leg), leg
+
+
+class _FakeEngine:
+    """The two result calls dump_outputs makes, over tables of a given size."""
+    def __init__(self, n_windows, n_sites):
+        r = np.random.default_rng(5)
+        self.win, self.site = r.random((n_windows, 3)), r.random((n_sites, 3))
+
+    def window_ll(self, t=0):
+        return self.win.copy()
+
+    def site_ll(self, t=0):
+        return self.site.copy()
+
+
+@pytest.mark.parametrize("world", [1, 4])
+def test_dump_outputs_stays_under_its_limit_and_repeats(world, tmp_path):
+    """--dump-outputs: float64 tables, all ranks together at most DUMP_LIMIT bytes; a table too large for its share is a
+    sample of rows whose indices are written beside it, the same rows for the same --seed."""
+    import bench
+    eng = _FakeEngine(40_000, 4_000_000)
+    for run in ("a", "b"):
+        for rank in range(world):
+            bench.dump_outputs(str(tmp_path / run), eng, rank, world, 20241008)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    sfx = [""] if world == 1 else [f"_rank{r}" for r in range(world)]
+    assert files == sorted(f"{n}{s}.npy" for s in sfx for n in ("site_ll", "site_ll_rows", "window_ll"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT + 128 * len(files)
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    s = sfx[-1]
+    assert np.array_equal(np.load(tmp_path / "a" / f"window_ll{s}.npy"), eng.win)
+    rows = np.load(tmp_path / "a" / f"site_ll_rows{s}.npy").astype(np.int64)
+    assert len(rows) > 100_000 and (np.diff(rows) > 0).all() and rows[-1] < 4_000_000
+    assert np.array_equal(np.load(tmp_path / "a" / f"site_ll{s}.npy"), eng.site[rows])
+
+
+def test_small_outputs_are_dumped_whole(tmp_path):
+    import bench
+    eng = _FakeEngine(50, 5000)
+    bench.dump_outputs(str(tmp_path), eng, 0, 1, 1)
+    assert sorted(os.listdir(tmp_path)) == ["site_ll.npy", "window_ll.npy"]
+    assert np.array_equal(np.load(tmp_path / "site_ll.npy"), eng.site)
+
+
+def test_steps_below_one_are_refused():
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "0"],
+                       env=_clean_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_repeat_run_for_run(tmp_path):
+    """Two runs with the same arguments write the same outputs of their last timed step; `steps` is the number asked for."""
+    common = ["--gpus", "1", "--steps", "7", "--warmup", "2", "--sites", "300000", "--timed-only"]
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + common + ["--dump-outputs", str(tmp_path / run)],
+                           env=_clean_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    assert all(l["steps"] == 7 and l["ms_per_step"] > 0 for l in lines)
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(os.listdir(tmp_path / "b")) == ["site_ll.npy", "window_ll.npy"]
+    site_a, site_b = np.load(tmp_path / "a" / "site_ll.npy"), np.load(tmp_path / "b" / "site_ll.npy")
+    win_a, win_b = np.load(tmp_path / "a" / "window_ll.npy"), np.load(tmp_path / "b" / "window_ll.npy")
+    assert site_a.shape == (300_000, 3) and win_a.shape[1] == 3 and len(win_a) > 2000
+    assert np.array_equal(site_a, site_b, equal_nan=True)
+    assert np.allclose(win_a, win_b, rtol=1e-10, atol=0, equal_nan=True)
