@@ -7,7 +7,8 @@ configs[3]  --LD, 4M rows, 2504-individual panel, window 100   -> (a) EVERY wind
             ~70 core-seconds) from the panel rows read back from the device input, (b) the strict and the
             exponent-counting kernels agree on every window, (c) two half-chromosome shards cut at a
             window boundary reproduce the whole, (d) a second run is bit-identical, (e) alt counts of
-            sampled rows equal numpy popcounts.
+            sampled rows equal numpy popcounts, (g) 288 windows (the smallest, the largest, a random sample)
+            within the fast forms' bound of the extended-precision reference (tests/hp_ref.py).
 The synthetic data are bench.py's (same generator, same seed)."""
 import contextlib
 import os
@@ -166,6 +167,25 @@ def test_config3_chr1_2504_individuals(chr1, oracle):
     assert checked == n_win
     print(f"oracle on all {checked} windows: max rel {worst_orc:.2e}")
     rng = np.random.default_rng(5)
+
+    # (g) the extended-precision reference (tests/hp_ref.py) on 256+ windows: the 64 smallest values, the 64 largest and
+    # 160 drawn from the rest, held to the fast forms' bound against the binomial truth
+    import hp_ref as H
+    order = np.argsort(np.minimum(win[:, 0], win[:, 1]), kind="stable")
+    pick = set(order[:64].tolist()) | set(order[-64:].tolist())
+    pick |= set(rng.choice(np.setdiff1d(np.arange(n_win), sorted(pick)), size=160, replace=False).tolist())
+    assert len(pick) >= 256
+    fac = H.binomial_factors(0.02, 20)
+    B = H.fast_B("popcount", N)
+    worst_hp = 0.0
+    for w in sorted(pick):
+        a, b = int(first[w]), int(last[w]) + 1
+        alle = oracle_pool.unpack_rows(chr1["panel"][a:b].cpu().numpy().view(np.uint64), N)
+        tr = H.ld_truth(alle, nr[a:b], na[a:b], t, 100, fac)
+        assert len(tr["rows"]) == 1
+        for col, key in ((0, "ibd0"), (1, "ibd1")):
+            worst_hp = max(worst_hp, H.check(win[w:w + 1, col], tr[key], B, H.FAST_A, f"window {w} {key}"))
+    print(f"hp_ref on {len(pick)} windows: max |got - t| / (B u t + A 2^-1074) = {worst_hp:.3f} (B = {B:.1f})")
 
     # (e) alt counts
     rows = rng.integers(0, L, 200)
