@@ -209,7 +209,20 @@ struct ibdg_ctx {
 
     // run state / results
     DevBuf targets, weight, nrefpanel, af, site_ll, win_ll;
-    DevBuf row_tab;                     // [n_sites][4]: the rows' values of an --LD run over several comparison individuals (k_row_table)
+    // The site list's row table, [n_sites][4] {LIBD0, LIBD1 under genotype 0, 1, 2}: what the rows' per-site values are for any
+    // comparison individual (they differ by the genotype picked).  Made by the first --LD run that keeps per-site results and
+    // finds it stale, used by every later one: ibdg_get_site_ll expands it for the last run's individual t (k_site_expand).
+    // It depends on the site records and -A overrides (an upload of sites), the alt counts and n_ids (an upload of the panel)
+    // and the P(D|G) table (fixed per context) -- hence on up_gen.  Stream edges:
+    //   writer  stream2 of the run that makes it (k_rows_windows<ROWS_TAB> for one individual, k_row_table for several),
+    //           behind that run's recount of the alt counts when it recounts
+    //   reader  k_site_expand on the main stream, behind join_streams (the main stream waits for stream2's last event, which
+    //           comes after the writer), and the fetch behind it waits on the host for both streams: no reader outlives its call
+    //   a rebuild happens only after an upload (which waits on the host for every stream before it changes anything) or when
+    //   ensure() has replaced the buffer (which also waits for every stream first, and whose new buffer holds no table: rt_gen 0)
+    DevBuf row_tab;
+    uint64_t up_gen = 1;                // bumped by every upload of a panel or of sites (a change of layout leaves it)
+    uint64_t rt_gen = 0;                // up_gen the table in row_tab was made for (0: none)
     size_t n_targets = 0;
     bool have_results = false;
 
@@ -237,7 +250,8 @@ struct ibdg_ctx {
                            // estimate of workgroups in flight by n/4 -- 4 measured best at 500k and 4M rows)
     long opt_ring = 2;     // LDS ring slots per wave (2, 3, 4 or 8); 2 measured fastest (fewest LDS bytes)
     long opt_recbytes = 12 * 1024;   // LDS budget for one run's segment records
-    long opt_site_blocks = 4;        // 256-thread workgroups per CU of k_site inside an --LD run (0 = a thread per site)
+    long opt_site_blocks = 2;        // 256-thread workgroups per CU of the per-row kernel inside an --LD run (k_win_ibd2; 0 = its full
+                                     // grid): 2 the fastest step of 1, 2, 4 (8) in each round of profiles/r06_side_geometry.txt
     long opt_recount_blocks = 4;     // single-wave workgroups per CU of k_alt_count when it runs inside an --LD run
                                      // (0 = the full grid; 4 measured best: tools/recount_sweep.py)
     long opt_compact = 0;            // tiles the --LD kernels read: 0 = chosen per upload (the panel's own where the pileup is
@@ -476,6 +490,7 @@ int prepare_panel(ibdg_ctx *c, size_t n_rows, unsigned n_ids)
         return fail(c, "[::] ERROR in ibdg_upload_panel: n_ids must be >= 1");
     c->n_ids = n_ids;
     c->n_rows = n_rows;
+    ++c->up_gen;                        // (the alt counts and n_ids of the row table)
     c->n_chunks = (n_ids + 63) / 64;
     c->cpw = pick_cpw(c->n_chunks, c->opt_cpw);
     c->n_groups = (c->n_chunks + c->cpw - 1) / c->cpw;
@@ -1236,6 +1251,7 @@ static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *
         c->prep_dirty = false;
     }
     ++c->sites_gen;
+    ++c->up_gen;
     c->relayout_credit = 0;
     c->ibd0_runs = 0;
     c->seg_room = c->pop_lut_ok ? seg_room : 0;
@@ -1468,12 +1484,16 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
 
     const size_t lanes = (size_t)c->n_groups * c->cpw * 64;
     const bool want_ll = c->opt_site_results != 0;
-    // --LD over several comparison individuals: one table of the rows' values for all of them (they differ by the genotype
-    // picked), an individual's per-site table is put together when it is fetched (k_row_table / k_site_expand)
-    const bool row_table = want_ll && ld_mode && T > 1;
+    // --LD: the per-site values come from the site list's row table (one for every comparison individual: they differ by the
+    // genotype picked), made once per upload; an individual's per-site table is put together when it is fetched (k_site_expand)
+    const bool row_table = want_ll && ld_mode;
+    const size_t rt_cap0 = c->row_tab.cap;
     if (ensure(c, c->targets, ibdg_ctx::TG_RING * T * 4) || (want_ll && ensure(c, c->site_ll, (row_table ? 1 : T) * c->n_sites * 24)) ||
         (row_table && ensure(c, c->row_tab, c->n_sites * 32)) || ensure(c, c->win_ll, T * (size_t)c->n_win * 24))
         return 1;
+    if (c->row_tab.cap != rt_cap0)
+        c->rt_gen = 0;                  // a new buffer (grown: the capacity tells, the address may be the old one): no table in it
+    const bool rt_build = row_table && c->rt_gen != c->up_gen;
     // targets / background weights change rarely between calls (a loop over windows sizes, repeated
     // timing steps): their device copies are rebuilt only when the inputs differ
     const bool same_bg = c->prev_pu == pu_id && c->prev_has_bg == (bg_count ? 1 : 0) && c->prev_lanes == lanes &&
@@ -1692,13 +1712,14 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     sa.t32 = c->pop_lut_ok ? (const uint4 *)c->t32.p : nullptr;
     sa.n_pairs = c->n_pairs;
     sa.cov_site = (const uint32_t *)c->cov_site.p;
+    sa.rec_cov = (const uint2 *)c->rec_cov.p;
     sa.n_cov = c->n_cov;
     sa.window = c->window;
     sa.n_win = c->n_win;
     sa.ld_mode = ld_mode ? 1 : 0;
     sa.af = nullptr;
     sa.site_ll = want_ll && !row_table ? (double *)c->site_ll.p : nullptr;
-    sa.row_tab = row_table ? (double *)c->row_tab.p : nullptr;
+    sa.row_tab = nullptr;
     sa.win_ll = (double *)c->win_ll.p;
 
     if (use_pop) {
@@ -2116,9 +2137,19 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
         unsigned row_blocks = 0;
         if (shadow && c->opt_site_blocks > 0)
             row_blocks = std::max<unsigned>(1u, (unsigned)((size_t)c->n_cu * c->opt_site_blocks / T));
-        if (row_table)
-            ibdg::launch_row_table(sa, c->stream2);
-        ibdg::launch_rows_windows(sa, (unsigned)T, c->stream2, row_blocks);
+        // The site list's row table, when stale: one comparison individual's run makes it in the launch it makes anyway
+        // (its rows' values are all computed there: 32 B per row stored instead of the per-site triple's 24), a run over
+        // several with k_row_table first.  Every other --LD run takes the LIBD2 window products of the covered rows only.
+        // (stream2, behind this run's recount of the alt counts; readers: see ibdg_ctx::row_tab)
+        ibdg::RowsArgs ra = sa;
+        if (rt_build) {
+            ra.row_tab = (double *)c->row_tab.p;
+            if (T > 1) {
+                ibdg::launch_row_table(ra, c->stream2);
+                ra.row_tab = nullptr;
+            }
+        }
+        ibdg::launch_rows_windows(ra, (unsigned)T, c->stream2, row_blocks);
         HIP_TRY(c, hipEventRecord(E.s2[2], c->stream2));
         c->last_s2 = E.s2[2];
         c->s2_pending = true;
@@ -2136,6 +2167,8 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
         c->tg_main_pending[h] = true;
     }
     HIP_TRY(c, hipGetLastError());
+    if (rt_build)
+        c->rt_gen = c->up_gen;
     c->ev_head = ev_slot;
     ++c->runs_done;
     c->chain_ok = true;
@@ -2183,7 +2216,7 @@ int ibdg_get_site_ll(ibdg_ctx *c, size_t t, double *out)
     if (!c->have_results || t >= c->n_targets) return fail(c, "[::] ERROR in ibdg_get_site_ll: no results for target %zu", t);
     if (c->res_site_mode == 0) return fail(c, "[::] ERROR in ibdg_get_site_ll: the run kept no per-site results (option site_results)");
     if (c->res_site_mode == 2) {
-        // the run kept one table of the rows' values for all its comparison individuals: this one's per-site table from it
+        // the site list's row table (ibdg_ctx::row_tab): the per-site table of the last run's individual t from it
         if (t >= c->prev_targets.size()) return fail(c, "[::] ERROR in ibdg_get_site_ll: no results for target %zu", t);
         HIP_TRY(c, hipSetDevice(c->device));
         if (join_streams(c)) return 1;

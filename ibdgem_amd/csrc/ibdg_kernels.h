@@ -22,13 +22,15 @@ struct RowsArgs {
     const uint4 *t32;           // tile-transposed panel (NULL if not built) and its pairs per chunk
     uint32_t n_pairs;
     const uint32_t *cov_site;   // [n_cov] site index of each covered row
+    const uint2 *rec_cov;       // [n_cov] {row, lut byte offset} of the covered rows (k_win_ibd2)
     uint32_t n_cov;
     uint32_t window;
     uint32_t n_win;
     int ld_mode;                // 1: of the window products only LIBD2 is written
     double *af;                 // [n_sites]: written by k_site_af only (ibdg_get_site_af)
     double *site_ll;            // [T][n_sites][3], or NULL: per-site results not wanted
-    double *row_tab;            // [n_sites][4] {LIBD0, LIBD1 under genotype 0, 1, 2}: k_row_table / k_site_expand only
+    double *row_tab;            // [n_sites][4] {LIBD0, LIBD1 under genotype 0, 1, 2} of the site list: written by k_row_table and
+                                // k_rows_windows (the run that makes it), read by k_site_expand
     double *win_ll;             // [T][n_win][3]
 };
 
@@ -305,11 +307,14 @@ void launch_prep_win_bounds(const uint32_t *cov_site, uint32_t n_cov, uint32_t w
 void launch_alt_count(const uint64_t *panel, uint32_t stride, size_t n_rows, uint32_t *alt_count,
                       hipStream_t st, unsigned max_blocks = 0);
 // max_blocks: 0 = a wave per pair of consecutive windows (four waves per workgroup); otherwise at most that many workgroups per target, which
-// walk the windows grid-stride (few long-lived waves: for running beside the --LD kernel)
+// walk the windows grid-stride (few long-lived waves: for running beside the --LD kernel).  The form follows the arguments: row_tab set
+// -- the site list's row table made on the way, for ONE comparison individual (n_targets = 1) --; --LD without site_ll -- the
+// LIBD2 products of the covered rows only (k_win_ibd2) --; otherwise every value of every row (per-site triples into site_ll when set)
 void launch_rows_windows(const RowsArgs &a, unsigned n_targets, hipStream_t st, unsigned max_blocks = 0);
 // af[s] of every site (k_site_af)
 void launch_site_af(const RowsArgs &a, hipStream_t st);
-// the row table of a run over several comparison individuals, and one individual's per-site table from it
+// the row table of a site list (an --LD run over several comparison individuals makes it with this), and one individual's
+// per-site table from it
 void launch_row_table(const RowsArgs &a, hipStream_t st);
 void launch_site_expand(const RowsArgs &a, uint32_t tgt, double *out, hipStream_t st);
 int launch_ld(const LdArgs &a, unsigned n_targets, int cpw, unsigned waves, hipStream_t st);

@@ -113,19 +113,25 @@ __global__ __launch_bounds__(256) void k_alt_count_long(const uint64_t *__restri
 // A wave per (two consecutive windows, comparison individual): for each window its lanes take the rows from the window's first covered
 // row up to the next window's (rows without reads in between are printed but join no window,
 // src/ibdgem.c:657-663; the rows before the first window go with window 0, those behind the last one
-// with it), 128 rows per turn with all their gathers in flight, compute the row's three values, store
+// with it), 128 rows per turn with all their gathers in flight, compute the row's values, store
 // them when per-site results are wanted, and leave the factors -- 1.0 for a row without reads: x * 1.0
 // is x -- in the window's LDS strip of the wave, where three lanes per window multiply them up in row order (six side by side).  The per-site triple
-// is never read back (a separate product kernel re-read 24 B per row), and a run that wants window
-// results only (FULL = false in --LD mode: the host program's --summary-only) computes just the IBD2
-// pick of every row: one table look-up, nothing stored.
+// is never read back (a separate product kernel re-read 24 B per row).
+// Two forms:
+//   ROWS_FULL  every value of the row under the individual's genotype: the per-site triples (site_ll, when kept) and, in a
+//              non-LD run, the products of all three
+//   ROWS_TAB   an --LD run of one comparison individual that finds the site list's row table stale: the row table (k_row_table's
+//              values, 32 B per row) instead of the triples, and the LIBD2 products only -- the table's one build, in the launch
+//              the run makes anyway
+// An --LD run whose row table is at hand wants the LIBD2 products only: k_win_ibd2 below.
 // ---------------------------------------------------------------------------
 // One turn of a window: rows [base, base + 128) below e, two per lane, all their gathers in flight; the rows' values go to
-// site_ll (when kept) and their factors for the window products -- 1.0 for a row without reads or beyond e -- into `buf`.
+// site_ll / row_tab (when kept) and their factors for the window products -- 1.0 for a row without reads or beyond e -- into `buf`.
 #ifndef IBDG_SITE_NT
 #define IBDG_SITE_NT 1
 #endif
-template <bool FULL>
+enum { ROWS_FULL = 1, ROWS_TAB = 2 };
+template <int MODE>
 __device__ __forceinline__ void rows_turn(const RowsArgs &a, unsigned t, uint32_t tgt, size_t base, size_t e, unsigned lane,
                                           double *__restrict__ buf)
 {
@@ -147,7 +153,7 @@ __device__ __forceinline__ void rows_turn(const RowsArgs &a, unsigned t, uint32_
         p00[u] = L[0];
         p01[u] = L[1];
         p11[u] = L[2];
-        k[u] = FULL && live[u] ? a.alt_count[rc[u].x] : 0u;
+        k[u] = live[u] ? a.alt_count[rc[u].x] : 0u;
         if (a.t32) {
             // the target's alleles from the tile-transposed copy: one 8-byte word pair serves 32
             // consecutive rows (the site-major row costs two 64-byte sectors per row for two bits)
@@ -160,21 +166,19 @@ __device__ __forceinline__ void rows_turn(const RowsArgs &a, unsigned t, uint32_
             tw[u] = make_uint2((uint32_t)((r0 >> (tgt & 63)) & 1u) << (rc[u].x & 31),
                                (uint32_t)((r1 >> (tgt & 63)) & 1u) << (rc[u].x & 31));
         }
-        fo[u] = FULL && a.fo && live[u] ? a.fo[3 * (base + 64 * u + lane)] : qnan;
+        fo[u] = a.fo && live[u] ? a.fo[3 * (base + 64 * u + lane)] : qnan;
     }
     double f[2], pw1[2], pw2[2];
-    if (FULL) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            f[u] = (double)k[u] / (double)(int)(2u * a.n_ids);       // src/ibd-parse.c:98
-            pw1[u] = a.pow_tab[2 * k[u]];
-            pw2[u] = a.pow_tab[2 * k[u] + 1];
-            if (fo[u] == fo[u]) {          // not NaN: -A override (src/ibdgem.c:609-614)
-                const size_t s = base + 64 * u + lane;
-                f[u] = fo[u];
-                pw1[u] = a.fo[3 * s + 1];
-                pw2[u] = a.fo[3 * s + 2];
-            }
+    for (int u = 0; u < 2; ++u) {
+        f[u] = (double)k[u] / (double)(int)(2u * a.n_ids);       // src/ibd-parse.c:98
+        pw1[u] = a.pow_tab[2 * k[u]];
+        pw2[u] = a.pow_tab[2 * k[u] + 1];
+        if (fo[u] == fo[u]) {          // not NaN: -A override (src/ibdgem.c:609-614)
+            const size_t s = base + 64 * u + lane;
+            f[u] = fo[u];
+            pw1[u] = a.fo[3 * s + 1];
+            pw2[u] = a.fo[3 * s + 2];
         }
     }
 #pragma unroll
@@ -185,50 +189,63 @@ __device__ __forceinline__ void rows_turn(const RowsArgs &a, unsigned t, uint32_
         const double ibd2 = g == 0 ? p00[u] : (g == 1 ? p01[u] : p11[u]);
         const bool covered = rc[u].y != 0;            // table offset 0 <=> no reads
         double *o = buf + (64 * u + lane);            // value v of the row at o[128 v]: a chain's factors are neighbours
-        if (FULL) {
-            const double omf = 1 - f[u];
-            double ibd0 = 1.0;
-            if (!(p00[u] == 1 || p01[u] == 1 || p11[u] == 1)) {
-                const double t1 = pw1[u] * p00[u];
-                const double t2 = ((2 * omf) * f[u]) * p01[u];
-                const double t3 = pw2[u] * p11[u];
-                ibd0 = (t1 + t2) + t3;
-                if (ibd0 == 0.0)
-                    ibd0 = 2.2250738585072014e-308;      // DBL_MIN
-            }
-            double ibd1;
-            if (g == 0)
-                ibd1 = (f[u] * p01[u]) + (omf * p00[u]);
-            else if (g == 1)
-                ibd1 = ((0.5 * p01[u]) + ((0.5 * omf) * p00[u])) + ((0.5 * f[u]) * p11[u]);
-            else
-                ibd1 = (omf * p01[u]) + (f[u] * p11[u]);
-            if (ibd1 == 0.0)
-                ibd1 = 2.2250738585072014e-308;
-            if (live[u]) {
-                if (a.site_ll) {
-                    double *d = a.site_ll + ((size_t)t * a.n_sites + s) * 3;
-#if IBDG_SITE_NT
-                    // (written once, read by nobody on the device: past the caches, which the --LD kernel's tables and the
-                    //  targets' tile words live in)
-                    __builtin_nontemporal_store(ibd0, d);
-                    __builtin_nontemporal_store(ibd1, d + 1);
-                    __builtin_nontemporal_store(ibd2, d + 2);
-#else
-                    d[0] = ibd0;
-                    d[1] = ibd1;
-                    d[2] = ibd2;
-#endif
-                }
-            }
-            if (!a.ld_mode) {                          // (--LD: only the IBD2 products are taken from here, :752)
-                o[0] = covered ? ibd0 : 1.0;
-                o[128] = covered ? ibd1 : 1.0;
-            }
-            o[256] = covered ? ibd2 : 1.0;
-        } else {
-            o[0] = covered ? ibd2 : 1.0;
+        const double omf = 1 - f[u];
+        double ibd0 = 1.0;
+        if (!(p00[u] == 1 || p01[u] == 1 || p11[u] == 1)) {
+            const double t1 = pw1[u] * p00[u];
+            const double t2 = ((2 * omf) * f[u]) * p01[u];
+            const double t3 = pw2[u] * p11[u];
+            ibd0 = (t1 + t2) + t3;
+            if (ibd0 == 0.0)
+                ibd0 = 2.2250738585072014e-308;      // DBL_MIN
         }
+        if (MODE == ROWS_TAB) {
+            // {LIBD0, LIBD1 under genotype 0, 1, 2}: k_row_table's arithmetic, operation for operation
+            double g0 = (f[u] * p01[u]) + (omf * p00[u]);
+            double g1 = ((0.5 * p01[u]) + ((0.5 * omf) * p00[u])) + ((0.5 * f[u]) * p11[u]);
+            double g2 = (omf * p01[u]) + (f[u] * p11[u]);
+            if (g0 == 0.0) g0 = 2.2250738585072014e-308;
+            if (g1 == 0.0) g1 = 2.2250738585072014e-308;
+            if (g2 == 0.0) g2 = 2.2250738585072014e-308;
+            if (live[u]) {
+                // (read by k_site_expand only, when somebody fetches a per-site table: past the caches like the triples)
+                double *d = a.row_tab + s * 4;
+                __builtin_nontemporal_store(ibd0, d);
+                __builtin_nontemporal_store(g0, d + 1);
+                __builtin_nontemporal_store(g1, d + 2);
+                __builtin_nontemporal_store(g2, d + 3);
+            }
+            o[0] = covered ? ibd2 : 1.0;
+            continue;
+        }
+        double ibd1;
+        if (g == 0)
+            ibd1 = (f[u] * p01[u]) + (omf * p00[u]);
+        else if (g == 1)
+            ibd1 = ((0.5 * p01[u]) + ((0.5 * omf) * p00[u])) + ((0.5 * f[u]) * p11[u]);
+        else
+            ibd1 = (omf * p01[u]) + (f[u] * p11[u]);
+        if (ibd1 == 0.0)
+            ibd1 = 2.2250738585072014e-308;
+        if (live[u] && a.site_ll) {
+            double *d = a.site_ll + ((size_t)t * a.n_sites + s) * 3;
+#if IBDG_SITE_NT
+            // (written once, read by nobody on the device: past the caches, which the --LD kernel's tables and the
+            //  targets' tile words live in)
+            __builtin_nontemporal_store(ibd0, d);
+            __builtin_nontemporal_store(ibd1, d + 1);
+            __builtin_nontemporal_store(ibd2, d + 2);
+#else
+            d[0] = ibd0;
+            d[1] = ibd1;
+            d[2] = ibd2;
+#endif
+        }
+        if (!a.ld_mode) {                          // (--LD: only the IBD2 products are taken from here, :752)
+            o[0] = covered ? ibd0 : 1.0;
+            o[128] = covered ? ibd1 : 1.0;
+        }
+        o[256] = covered ? ibd2 : 1.0;
     }
 }
 
@@ -238,9 +255,10 @@ __device__ __forceinline__ void rows_turn(const RowsArgs &a, unsigned t, uint32_
 #ifndef IBDG_ROWS_WPW
 #define IBDG_ROWS_WPW 2
 #endif
-template <bool FULL>
+template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_rows_windows(RowsArgs a)
 {
+    constexpr bool FULL = MODE == ROWS_FULL;
     constexpr int NV = FULL ? 3 : 1;                 // values per row kept for the products
     constexpr int WPW = IBDG_ROWS_WPW;
     __shared__ __attribute__((aligned(16))) double strip[4][WPW][128 * NV];
@@ -270,7 +288,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int q = 0; q < WPW; ++q)            // (a window that has run out of rows gets a strip of 1.0s)
-                rows_turn<FULL>(a, t, tgt, bd[q] + off, bd[q + 1], lane, strip[wave][q]);
+                rows_turn<MODE>(a, t, tgt, bd[q] + off, bd[q + 1], lane, strip[wave][q]);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             const uint32_t n = (uint32_t)(span - off < 128 ? span - off : 128);
@@ -294,6 +312,86 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
             else if (!a.ld_mode || cc == 2)
                 o[cc] = acc;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// The LIBD2 window products of an --LD run (src/ibdgem.c:665-667, :752): all a run takes from the per-row side once the site
+// list's row table is at hand, or when it keeps no per-site results.  The covered rows only -- window w is entries
+// [w W, min((w + 1) W, n_cov)) of rec_cov; the rows without reads between them multiply by 1.0 in k_rows_windows, which changes
+// no bit -- and of every row its record, the individual's tile word and the one P(D|G) entry of its genotype.  The waves, strips
+// and row-order products of k_rows_windows.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void ibd2_turn(const RowsArgs &a, uint32_t tgt, size_t base, size_t e, unsigned lane,
+                                          double *__restrict__ buf)
+{
+    uint2 rc[2];
+    bool live[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const size_t j = base + 64 * u + lane;
+        live[u] = j < e;
+        rc[u] = live[u] ? a.rec_cov[j] : make_uint2(0, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        unsigned g;
+        if (a.t32) {
+            const uint2 *p = reinterpret_cast<const uint2 *>(
+                a.t32 + ((size_t)(tgt >> 6) * a.n_pairs + (rc[u].x >> 6)) * 64 + (tgt & 63));
+            const uint2 tw = live[u] ? p[(rc[u].x >> 5) & 1] : make_uint2(0, 0);
+            g = ((tw.x >> (rc[u].x & 31)) & 1u) + ((tw.y >> (rc[u].x & 31)) & 1u);
+        } else {
+            const uint64_t *row = a.panel + (size_t)rc[u].x * a.stride;
+            const uint64_t r0 = live[u] ? row[2 * (tgt >> 6)] : 0, r1 = live[u] ? row[2 * (tgt >> 6) + 1] : 0;
+            g = (unsigned)((r0 >> (tgt & 63)) & 1u) + (unsigned)((r1 >> (tgt & 63)) & 1u);
+        }
+        const double *L = reinterpret_cast<const double *>(reinterpret_cast<const char *>(a.lut) + rc[u].y);
+        buf[64 * u + lane] = live[u] ? L[g] : 1.0;
+    }
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_win_ibd2(RowsArgs a)
+{
+    constexpr int WPW = IBDG_ROWS_WPW;
+    __shared__ __attribute__((aligned(16))) double strip[4][WPW][128];
+    const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const unsigned t = blockIdx.y;
+    uint32_t tgt = a.targets[t];
+    IBDG_CHECK_TGT(tgt, a.n_ids, __func__);
+    const uint32_t n_groups = (a.n_win + WPW - 1) / WPW;
+    for (uint32_t g = blockIdx.x * 4 + wave; g < n_groups; g += gridDim.x * 4) {
+        const uint32_t w0 = g * WPW;
+        size_t bd[WPW + 1];                          // window w0 + q takes the entries [bd[q], bd[q + 1]) of rec_cov
+#pragma unroll
+        for (int q = 0; q <= WPW; ++q) {
+            const size_t b = (size_t)(w0 + q) * a.window;
+            bd[q] = b < a.n_cov ? b : a.n_cov;
+        }
+        const size_t span = bd[1] - bd[0];           // (every window but the last has W rows)
+        double acc = 1.0;
+        for (size_t off = 0; off < span; off += 128) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int q = 0; q < WPW; ++q)
+                ibd2_turn(a, tgt, bd[q] + off, bd[q + 1], lane, strip[wave][q]);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t n = (uint32_t)(span - off < 128 ? span - off : 128);
+            if (lane < WPW) {
+                // (behind an odd count sits a 1.0: the turn fills a strip's lanes beyond its window's rows with it)
+                const double2 *src = reinterpret_cast<const double2 *>(&strip[wave][lane][0]);
+#pragma unroll 4
+                for (uint32_t j = 0; j < (n + 1) / 2; ++j) {
+                    const double2 v = src[j];
+                    acc *= v.x;
+                    acc *= v.y;
+                }
+            }
+        }
+        if (lane < WPW && w0 + lane < a.n_win)
+            a.win_ll[((size_t)t * a.n_win + w0 + lane) * 3 + 2] = acc;
     }
 }
 
@@ -625,16 +723,21 @@ void launch_rows_windows(const RowsArgs &a, unsigned n_targets, hipStream_t st, 
 {
     if (a.n_sites == 0 || n_targets == 0)
         return;
+    // --LD without per-site triples to write and no row table to make: the LIBD2 products of the covered rows
+    const bool ibd2_only = a.ld_mode && !a.site_ll && !a.row_tab;
+    if (ibd2_only && a.n_win == 0)
+        return;
     const uint32_t n_w = a.n_win ? a.n_win : 1;
     size_t blocks = (((size_t)n_w + IBDG_ROWS_WPW - 1) / IBDG_ROWS_WPW + 3) / 4;      // a wave per group of windows
     if (max_blocks && blocks > max_blocks)
         blocks = max_blocks;
     dim3 grid((unsigned)blocks, n_targets);
-    // everything but LIBD2 of the windows unwanted (--LD, no per-site results): the one-value form
-    if (a.ld_mode && !a.site_ll)
-        hipLaunchKernelGGL(k_rows_windows<false>, grid, dim3(256), 0, st, a);
+    if (ibd2_only)
+        hipLaunchKernelGGL(k_win_ibd2, grid, dim3(256), 0, st, a);
+    else if (a.row_tab)
+        hipLaunchKernelGGL(k_rows_windows<ROWS_TAB>, grid, dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL(k_rows_windows<true>, grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_rows_windows<ROWS_FULL>, grid, dim3(256), 0, st, a);
 }
 
 int launch_ld(const LdArgs &a, unsigned n_targets, int cpw, unsigned waves, hipStream_t st)

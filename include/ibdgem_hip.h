@@ -176,7 +176,9 @@ int ibdg_run(ibdg_ctx *ctx, const uint32_t *targets, size_t n_targets, const uin
 /* AF column: alt-allele fraction per uploaded site (or the -A override): alt count / (2 n_ids), src/ibd-parse.c:98.
  * Computed by this call (it depends on the panel row only), after an ibdg_run. */
 int ibdg_get_site_af(ibdg_ctx *ctx, double *af);
-/* LIBD0, LIBD1, LIBD2 per site of target t: out[n_sites][3] (tab columns 12-14). */
+/* LIBD0, LIBD1, LIBD2 per site of target t: out[n_sites][3] (tab columns 12-14).  After an --LD run this is the table of the
+ * last run's individual t, put together when fetched from the site list's row table (made once per upload of sites or panel
+ * by the first --LD run that keeps per-site results); after a non-LD run, the run's own per-site values. */
 int ibdg_get_site_ll(ibdg_ctx *ctx, size_t t, double *out);
 /* LIBD0, LIBD1, LIBD2 per window of target t: out[n_windows][3] (summary columns 4-6). */
 int ibdg_get_window_ll(ibdg_ctx *ctx, size_t t, double *out);
@@ -244,10 +246,11 @@ int ibdg_last_count_unit(const ibdg_ctx *ctx);
  * them); "dev_inputs_ready" (0/1: ibdg_upload_sites_dev does not wait for the whole device first, see there);
  * "count_in_run" (0/1: recompute alt counts inside every ibdg_run,
  * so the timed region covers it; beside the --LD kernel the recount runs with "recount_blocks_per_cu"
- * single-wave workgroups per CU, default 4, 0 = its full grid); "site_blocks_per_cu" (default 4: workgroups per CU of the
+ * single-wave workgroups per CU, default 4, 0 = its full grid); "site_blocks_per_cu" (default 2: workgroups per CU of the
  * per-row kernel beside the exponent-counting --LD kernel, 0 = its full grid) and "rows_blocks_per_cu" (default 0 = full
  * grid: the same for a non-LD run, where it has the chip to itself); "site_results" (what ibdg_run keeps per row: 1, the default,
- * LIBD0/1/2 of every row and comparison individual for ibdg_get_site_ll; 0 nothing -- no n_targets x n_sites x 24 bytes
+ * LIBD0/1/2 of every row and comparison individual for ibdg_get_site_ll -- in --LD mode from the site list's row table, 32 bytes
+ * per row, made by the first such run on an upload; 0 nothing -- no n_targets x n_sites x 24 bytes
  * of device memory, no per-row stores, and in --LD mode only the IBD2 pick of a row is computed at all: for callers that
  * want the window table only, e.g. hundreds of comparison individuals in one call; ibdg_get_site_ll then fails.  The AF
  * column never costs a run anything: ibdg_get_site_af computes it when called); "stage_workers" (1..8, default 8: host threads of that staging team -- a caller
