@@ -209,6 +209,7 @@ struct ibdg_ctx {
 
     // run state / results
     DevBuf targets, weight, nrefpanel, af, site_ll, win_ll;
+    DevBuf llr_seg, llr_part, llr_out;  // ibdg_window_llr_sums: segments, partial sums per block of windows, the sums
     // The site list's row table, [n_sites][4] {LIBD0, LIBD1 under genotype 0, 1, 2}: what the rows' per-site values are for any
     // comparison individual (they differ by the genotype picked).  Made by the first --LD run that keeps per-site results and
     // finds it stale, used by every later one: ibdg_get_site_ll expands it for the last run's individual t (k_site_expand).
@@ -1116,7 +1117,7 @@ void ibdg_destroy(ibdg_ctx *c)
                       &c->fo, &c->targets, &c->weight, &c->nrefpanel, &c->af, &c->site_ll, &c->win_ll, &c->row_tab, &c->t32, &c->t32c, &c->seg_first,
                       &c->segs, &c->runs, &c->wconst, &c->wtarget, &c->twords, &c->wtarget_mt, &c->twords_mt, &c->vals, &c->order, &c->pow1, &c->pow2, &c->pow3, &c->partial, &c->aimg, &c->wc_slot, &c->partial_h, &c->base_w, &c->p2w, &c->p2c, &c->p2_tw, &c->p2_wt, &c->fragb,
                       &c->in_row, &c->in_ref, &c->in_alt, &c->scan_tmp, &c->info_dev, &c->wraw, &c->nck_dev, &c->powb,
-                      &c->win_first, &c->win_last})
+                      &c->win_first, &c->win_last, &c->llr_seg, &c->llr_part, &c->llr_out})
         release(*b);
     for (hipEvent_t ev : c->ev_up)
         if (ev)
@@ -2249,6 +2250,48 @@ int ibdg_get_window_ll_all(ibdg_ctx *c, double *out)
     if (!c) return 1;
     if (!c->have_results) return fail(c, "[::] ERROR in ibdg_get_window_ll_all: no results (call ibdg_run)");
     return fetch(c, out, c->win_ll.p, c->n_targets * (size_t)c->n_win * 24);
+}
+
+// Segmented sums over the window table of the last run (ibdg_llr.hip).  On the main stream behind join_streams: LIBD2 comes
+// from stream2, LIBD0/LIBD1 may come from a finalising launch still pending for the next run.  The segments go in chunks
+// whose slab of partials stays under LLR_SLAB items (one segment per chunk at least: its slab is then ~1/1500 of win_ll).
+int ibdg_window_llr_sums(ibdg_ctx *c, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out)
+{
+    if (!c) return 1;
+    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_window_llr_sums: no results (call ibdg_run)");
+    if (n_seg && (!first || !end || !out)) return fail(c, "[::] ERROR in ibdg_window_llr_sums: NULL array");
+    for (size_t s = 0; s < n_seg; ++s) {
+        if (end[s] < first[s])
+            return fail(c, "[::] ERROR in ibdg_window_llr_sums: range %zu is reversed ([%u, %u))", s, first[s], end[s]);
+        if (end[s] > c->n_win)
+            return fail(c, "[::] ERROR in ibdg_window_llr_sums: range %zu ends at %u, past the %u windows", s, end[s], c->n_win);
+    }
+    if (n_seg == 0 || c->n_targets == 0) return 0;
+    constexpr size_t LLR_SLAB = (size_t)1 << 22;
+    const size_t T = c->n_targets;
+    std::vector<uint32_t> seg(2 * n_seg);
+    uint32_t nb = 1;
+    for (size_t s = 0; s < n_seg; ++s) {
+        seg[2 * s] = first[s];
+        seg[2 * s + 1] = end[s];
+        nb = std::max<uint32_t>(nb, (uint32_t)(((uint64_t)end[s] - first[s] + ibdg::LLR_BLK - 1) / ibdg::LLR_BLK));
+    }
+    const size_t chunk = std::max<size_t>(1, std::min(n_seg, LLR_SLAB / (T * nb)));
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ensure(c, c->llr_seg, chunk * 8) || ensure(c, c->llr_part, T * chunk * nb * 32) || ensure(c, c->llr_out, T * chunk * 32))
+        return 1;
+    if (join_streams(c)) return 1;
+    for (size_t s0 = 0; s0 < n_seg; s0 += chunk) {
+        const size_t m = std::min(chunk, n_seg - s0);
+        HIP_TRY(c, hipMemcpyAsync(c->llr_seg.p, seg.data() + 2 * s0, m * 8, hipMemcpyHostToDevice, c->stream));
+        ibdg::launch_llr_sums((const double *)c->win_ll.p, c->n_win, (uint32_t)T, (const uint32_t *)c->llr_seg.p, (uint32_t)m,
+                              nb, (double *)c->llr_part.p, (double *)c->llr_out.p, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpy2DAsync(out + s0 * 4, n_seg * 32, c->llr_out.p, m * 32, m * 32, T, hipMemcpyDeviceToHost, c->stream));
+        if (s0 + m < n_seg)                              // (the next chunk reuses the device buffers)
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return quiesce(c);
 }
 
 int ibdg_get_alt_counts(ibdg_ctx *c, size_t first_row, size_t n, uint32_t *out)

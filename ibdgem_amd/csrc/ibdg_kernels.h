@@ -319,4 +319,13 @@ void launch_row_table(const RowsArgs &a, hipStream_t st);
 void launch_site_expand(const RowsArgs &a, uint32_t tgt, double *out, hipStream_t st);
 int launch_ld(const LdArgs &a, unsigned n_targets, int cpw, unsigned waves, hipStream_t st);
 
+// Segmented log-likelihood-ratio sums over the window table of a run (ibdg_llr.hip, ibdg_window_llr_sums).
+// seg[2 s], seg[2 s + 1]: window range [first, end) of segment s (end <= n_win), shared by all targets; nb: blocks of
+// LLR_BLK windows of the longest segment (>= 1); part: n_targets * n_seg * nb * 4 doubles of partial sums; out[t][s][4] =
+// {sum log2 L2' - log2 L0' (hi, lo), sum log2 L1' - log2 L0' (hi, lo)}.  Two launches on `st`, no atomics.
+constexpr uint32_t LLR_BLK = 2048;
+constexpr uint64_t LLR_MAX_BLOCKS = 8192;
+void launch_llr_sums(const double *win_ll, uint32_t n_win, uint32_t n_targets, const uint32_t *seg, uint32_t n_seg,
+                     uint32_t nb, double *part, double *out, hipStream_t st);
+
 }  // namespace ibdg

@@ -43,6 +43,7 @@ SYMBOLS = {
     "ibdg_get_site_ll": (C.c_int, [_P, C.c_size_t, _P]),
     "ibdg_get_window_ll": (C.c_int, [_P, C.c_size_t, _P]),
     "ibdg_get_window_ll_all": (C.c_int, [_P, _P]),
+    "ibdg_window_llr_sums": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
     "ibdg_run_ms": (C.c_int, [_P, C.c_uint, _P]),
@@ -260,6 +261,16 @@ class Engine:
             out = np.empty((n_targets, self.n_windows, 3), dtype=np.float64)
         assert out.dtype == np.float64 and out.size >= n_targets * self.n_windows * 3 and out.flags.c_contiguous
         self._chk(self.lib.ibdg_get_window_ll_all(self.ctx, out.ctypes.data))
+        return out
+
+    def window_llr_sums(self, first, end):
+        """Sums of log2(L2')-log2(L0') and log2(L1')-log2(L0') over the window ranges [first[s], end[s]) for every comparison
+        individual of the last run: [T][n_seg][4] = {IBD2/IBD0 hi, lo, IBD1/IBD0 hi, lo} (double-doubles)."""
+        first = np.ascontiguousarray(first, dtype=np.uint32)
+        end = np.ascontiguousarray(end, dtype=np.uint32)
+        assert first.shape == end.shape and first.ndim == 1
+        out = np.zeros((self.lib.ibdg_num_targets(self.ctx), len(first), 4), dtype=np.float64)
+        self._chk(self.lib.ibdg_window_llr_sums(self.ctx, first.ctypes.data, end.ctypes.data, len(first), out.ctypes.data))
         return out
 
     def alt_counts(self, first, n):

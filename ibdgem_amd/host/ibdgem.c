@@ -61,11 +61,15 @@ static int opt_ld = 0, opt_plan = 0, opt_summary_only = 0, opt_ref_order = 0, in
 static int has_S = 0, has_s = 0, has_B = 0, has_A = 0, has_p = 0, has_v = 0, has_D = 0;
 static int opt_threads = 0;
 static const char *cache_fn = NULL, *dump_panel_fn = NULL;
+static int opt_stats_only = 0, has_arm = 0;
+static unsigned long arm_c0, arm_c1;     /* --arm-stats: the centromeric range [c0, c1] of the run's chromosome */
 
 static struct option longopts[] = {
     {"LD", no_argument, &opt_ld, 1},
     {"plan", no_argument, &opt_plan, 1},
     {"summary-only", no_argument, &opt_summary_only, 1},
+    {"stats-only", no_argument, &opt_stats_only, 1},
+    {"arm-stats", required_argument, 0, 1006},
     {"reference-order", no_argument, &opt_ref_order, 1},
     {"rand-stream", required_argument, 0, 1000},
     {"fmt-check", required_argument, 0, 1005},
@@ -130,6 +134,12 @@ static void usage(int code)
           "                            while the .hap file is unchanged\n"
           "  --summary-only            write the *.summary.txt files only (no per-site *.tab.txt files: the\n"
           "                            per-site values are neither copied back from the device nor formatted)\n"
+          "  --arm-stats START,END     also write <out>/<pileup-name>.armstats.txt: per comparison individual the\n"
+          "                            p-arm and q-arm sums of log2(LIBD2/LIBD0) and log2(LIBD1/LIBD0) over the\n"
+          "                            summary windows, leaving out the centromeric range START..END (the\n"
+          "                            reference's bin/chrarm-stats.py; summed on the device)\n"
+          "  --stats-only              with --arm-stats: write the armstats file only (no *.tab.txt, no\n"
+          "                            *.summary.txt; the window tables stay on the device)\n"
           "  --reference-order         --LD: sum over the background panel serially in the reference's order\n"
           "                            (LIBD0/LIBD1 bit-identical to the reference; ~12x slower than the default,\n"
           "                            whose values agree to ~1e-15)\n"
@@ -1494,6 +1504,99 @@ static int write_summary_parallel(FILE *sum, sum_job proto, size_t n_win, int th
     return rc;
 }
 
+/* ---- --arm-stats: chromosome-arm sums of the window log-likelihood ratios (reference bin/chrarm-stats.py) ----------
+ * A window's terms are log2(L2') - log2(L0') and log2(L1') - log2(L0'), L' = L or 2^-1074 where L == 0, summed as
+ * double-doubles: on the device by ibdg_window_llr_sums, here for runs without one and to add the parts of a range that
+ * several devices summed, in device order.  The rounded sum then does not depend on the split. */
+static void dd_add(double x[2], double hi, double lo)
+{
+    const double s = x[0] + hi, bb = s - x[0];
+    double e = (x[0] - (s - bb)) + (hi - bb);       /* TwoSum: s + e == x[0] + hi exactly */
+    e += x[1] + lo;
+    x[0] = s + e;
+    x[1] = e - (x[0] - s);
+}
+
+static double arm_log2(double v)
+{
+    return log2(v == 0.0 ? 0x1p-1074 : v);
+}
+
+/* the sums over windows [a, b) of a window table on the host: out = {IBD2/IBD0 hi, lo, IBD1/IBD0 hi, lo} */
+static void llr_range_host(const double *win_ll, size_t a, size_t b, double out[4])
+{
+    out[0] = out[1] = out[2] = out[3] = 0.0;
+    for (size_t w = a; w < b; ++w) {
+        const double l0 = arm_log2(win_ll[3 * w]), l1 = arm_log2(win_ll[3 * w + 1]), l2 = arm_log2(win_ll[3 * w + 2]);
+        dd_add(out, l2, 0.0);
+        dd_add(out, -l0, 0.0);
+        dd_add(out + 2, l1, 0.0);
+        dd_add(out + 2, -l0, 0.0);
+    }
+}
+
+/* The arms of a site list's n windows, from the START / END each summary row prints (fmt_summary's lookup):
+ * p = [0, k), k the first window with END >= c0 (n if none), NaN when END_0 > c0 or n == 0;
+ * q = [m, n), m the first window at or after k with START >= c1, NaN when there is none.
+ * seg = {p first, p end, q first, q end}; ok[0], ok[1]: the arm has a value. */
+static void arm_segments(const uint32_t *s_row, const uint32_t *w_first, const uint32_t *w_last, size_t n, uint32_t seg[4],
+                         int ok[2])
+{
+    size_t k = 0;
+    while (k < n && rows[s_row[w_last[k]]].pos < arm_c0)
+        ++k;
+    size_t m = k;
+    while (m < n && rows[s_row[w_first[m]]].pos < arm_c1)
+        ++m;
+    ok[0] = n > 0 && rows[s_row[w_last[0]]].pos <= arm_c0;
+    ok[1] = m < n;
+    seg[0] = 0; seg[1] = (uint32_t)k;
+    seg[2] = (uint32_t)(ok[1] ? m : n); seg[3] = (uint32_t)n;
+}
+
+/* "START,END": two decimal integers, END >= START; 0 when malformed */
+static int parse_arm_range(const char *arg)
+{
+    char *e1, *e2;
+    if (!isdigit((unsigned char)arg[0]))
+        return 0;
+    errno = 0;
+    arm_c0 = strtoul(arg, &e1, 10);
+    if (errno || *e1 != ',' || !isdigit((unsigned char)e1[1]))
+        return 0;
+    arm_c1 = strtoul(e1 + 1, &e2, 10);
+    return !errno && *e2 == 0 && arm_c1 >= arm_c0;
+}
+
+/* windows of a site list: runs of `window` covered rows (:572, :657-663, :723-730); arrays of n_win + 1 entries.  The engine's
+ * definition as well (ibdg_upload_sites: n_win = ceil(covered / window); ibdg_get_windows: first / last = the covered rows
+ * w * window and min((w + 1) * window, covered) - 1): the host program cuts the --arm-stats arms from these before a run,
+ * and checks them against the engine's whenever the window tables come back (see the gather below). */
+static size_t host_windows(const uint8_t *nr, const uint8_t *na, size_t n, unsigned window, uint32_t **first, uint32_t **last,
+                           uint32_t **ncov)
+{
+    size_t covered = 0;
+    for (size_t i = 0; i < n; ++i)
+        covered += (nr[i] + na[i]) > 0;
+    const size_t n_win = (covered + window - 1) / window;
+    uint32_t *w_first = malloc((n_win + 1) * 4), *w_last = malloc((n_win + 1) * 4), *w_ncov = calloc(n_win + 1, 4);
+    if (!w_first || !w_last || !w_ncov) {
+        fprintf(stderr, "[::] ERROR: out of memory for %zu windows.\n", n_win);
+        exit(1);
+    }
+    size_t k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (nr[i] + na[i] == 0) continue;
+        const size_t w = k / window;
+        if (k % window == 0) w_first[w] = (uint32_t)i;
+        w_last[w] = (uint32_t)i;
+        w_ncov[w]++;
+        k++;
+    }
+    *first = w_first; *last = w_last; *ncov = w_ncov;
+    return n_win;
+}
+
 /* ---- one comparison spread over several GPUs (window ranges, host-side gather) ------------ */
 typedef struct {
     ibdg_ctx *eng;
@@ -1522,6 +1625,9 @@ typedef struct {
     int same_sites;                          /* the site list is the same for every comparison individual of the run */
     const uint32_t *next_targets;            /* the batch after this one (NULL: none), queued on the device while the host goes */
     size_t n_next;                           /* through this batch's tables -- window tables only (--summary-only) */
+    const uint32_t *arm_seg;                 /* --arm-stats: {p first, p end, q first, q end} in the slice's window indices, or NULL */
+    double arm[8];                           /* ... the individual's sums over them (ibdg_window_llr_sums) */
+    int stats_only;                          /* --stats-only: no window table leaves the device */
 } shard_job;
 
 /* Per device: the window table of the site list at hand (first row, last row, covered rows per window -- the same for
@@ -1539,6 +1645,8 @@ typedef struct {
     double *batch_ll;
     size_t batch_cap, batch_T;
     const uint32_t *batch_of;                /* the batch (its targets) the tables belong to; NULL: none */
+    double *arm_sums;                        /* --arm-stats: the sums of the last run's individuals, [T][2][4] */
+    size_t arm_cap;
     const uint32_t *ahead_of;                /* the batch that has been queued ahead on the device; NULL: none */
 } win_cache;
 static win_cache g_wcache[64];
@@ -1564,7 +1672,26 @@ static void *shard_run(void *arg)
                 return NULL;
         }
         wc->ahead_of = NULL;
-        if (j->next_targets || j->n_targets > 1) {
+        if (j->arm_seg) {
+            /* every individual of the run at once, before the look-ahead below replaces the run's window tables */
+            const uint32_t sf[2] = {j->arm_seg[0], j->arm_seg[2]}, se[2] = {j->arm_seg[1], j->arm_seg[3]};
+            if (wc->arm_cap < j->n_targets * 8) {
+                free(wc->arm_sums);
+                wc->arm_sums = malloc(j->n_targets * 8 * sizeof(double));
+                wc->arm_cap = wc->arm_sums ? j->n_targets * 8 : 0;
+            }
+            if (!wc->arm_sums || ibdg_num_targets(j->eng) != j->n_targets || ibdg_window_llr_sums(j->eng, sf, se, 2, wc->arm_sums))
+                return NULL;
+        }
+        if (j->stats_only) {
+            if (j->next_targets) {                                        /* the next batch runs while the host goes on */
+                if (ibdg_set_option(j->eng, "async", 1) ||
+                    ibdg_run(j->eng, j->next_targets, j->n_next, j->bg_count, j->pu_id, j->ld) ||
+                    ibdg_set_option(j->eng, "async", 0))
+                    return NULL;
+                wc->ahead_of = j->next_targets;
+            }
+        } else if (j->next_targets || j->n_targets > 1) {
             const size_t nw = ibdg_num_windows(j->eng), need = j->n_targets * (nw + 1) * 24;
             if (wc->batch_cap < need) {
                 if (wc->batch_ll)
@@ -1588,7 +1715,13 @@ static void *shard_run(void *arg)
             }
         }
     }
+    if (j->arm_seg)
+        memcpy(j->arm, wc->arm_sums + j->t_local * 8, sizeof j->arm);
     j->n_win = ibdg_num_windows(j->eng);
+    if (j->stats_only) {
+        j->failed = 0;
+        return NULL;
+    }
     j->w_first = malloc((j->n_win + 1) * 4);
     j->w_last = malloc((j->n_win + 1) * 4);
     j->w_ncov = malloc((j->n_win + 1) * 4);
@@ -2165,6 +2298,13 @@ int main(int argc, char **argv)
         case 1002: opt_threads = atoi(optarg); break;
         case 1003: cache_fn = optarg; break;
         case 1004: dump_panel_fn = optarg; break;   /* test hook: the packed rows + clean flags as a binary file */
+        case 1006:
+            if (!parse_arm_range(optarg)) {
+                fprintf(stderr, "[::] ERROR: Invalid centromeric range (--arm-stats) '%s' (must be START,END with START <= END).\n", optarg);
+                exit(1);
+            }
+            has_arm = 1;
+            break;
         case 1005: exit(fmt_check(atol(optarg)));   /* test hook: the number conversions against printf */
         case 1000:                                  /* test hook: the first N values of the read-thinning stream */
             for (long i = atol(optarg); i > 0; --i)
@@ -2190,6 +2330,10 @@ int main(int argc, char **argv)
     if (opt_min_qual < 0) { fprintf(stderr, "[::] ERROR: Invalid genotype quality minimum (-q) of %.2f (must be >= 0).\n", opt_min_qual); exit(0); }
     if (opt_window < 2) { fprintf(stderr, "[::] ERROR: Invalid window size (-w) of %d (must be >= 2).\n", opt_window); exit(0); }
     if (opt_max_cov > 127) { fprintf(stderr, "[::] ERROR: Invalid maximum estimated coverage (-M) of %u (pileup lines hold at most 127 reads).\n", opt_max_cov); exit(0); }
+    if (opt_stats_only && !has_arm) { fprintf(stderr, "[::] ERROR: --stats-only needs --arm-stats START,END.\n"); exit(1); }
+    if (opt_stats_only && opt_plan) { fprintf(stderr, "[::] ERROR: --stats-only writes a file --plan does not make; use one of them.\n"); exit(1); }
+    if (opt_stats_only)
+        opt_summary_only = 1;                 /* (what the engine does for it: no per-site values, batches queued ahead) */
 
     /* the echoed command: argv joined by single spaces, with a trailing space (:992-997) */
     size_t cmd_len = 2;
@@ -2414,6 +2558,12 @@ int main(int argc, char **argv)
     if (getenv("IBDGEM_OUT_SLOTS") && atoi(getenv("IBDGEM_OUT_SLOTS")) >= 1 && atoi(getenv("IBDGEM_OUT_SLOTS")) <= OUT_SLOTS)
         out_slots = atoi(getenv("IBDGEM_OUT_SLOTS"));
     const int out_threads_env = getenv("IBDGEM_OUT_THREADS") ? atoi(getenv("IBDGEM_OUT_THREADS")) : 0;   /* (measurement switch) */
+    const int arm_on = has_arm && !opt_plan;
+    double *arm_res = arm_on ? malloc((targets.n + 1) * 4 * sizeof(double)) : NULL;   /* per individual: p20, q20, p10, q10 */
+    if (arm_on && !arm_res)
+        DIE("[::] ERROR: out of memory.\n");
+    uint32_t *arm_wfirst = NULL, *arm_wlast = NULL;   /* engine path: the windows the arms were cut from (checked against the engine's) */
+    size_t arm_nw = 0;
     for (size_t ti = 0; ti < targets.n; ++ti) {
         const uint32_t tgt = targets.idx[ti];
         if (overlap) {
@@ -2492,32 +2642,48 @@ int main(int argc, char **argv)
         uint32_t *w_first = NULL, *w_last = NULL, *w_ncov = NULL;
         double *win_ll = NULL;
         if (no_engine) {
-            size_t covered = 0;
-            for (size_t i = 0; i < n; ++i)
-                covered += (s_nr[i] + s_na[i]) > 0;
-            n_win = (covered + opt_window - 1) / opt_window;
-            w_first = malloc((n_win + 1) * 4); w_last = malloc((n_win + 1) * 4); w_ncov = calloc(n_win + 1, 4);
-            size_t k = 0;
-            for (size_t i = 0; i < n; ++i) {
-                if (s_nr[i] + s_na[i] == 0) continue;
-                const size_t w = k / opt_window;
-                if (k % opt_window == 0) w_first[w] = (uint32_t)i;
-                w_last[w] = (uint32_t)i;
-                w_ncov[w]++;
-                k++;
-            }
+            n_win = host_windows(s_nr, s_na, n, (unsigned)opt_window, &w_first, &w_last, &w_ncov);
             if (host_math) {
                 win_ll = malloc((n_win + 1) * 24);
                 host_nonld(cand, s_cand, s_nr, s_na, n, tgt, pdg_tab, opt_threads > 0 ? opt_threads : default_threads(),
                            site_ll, w_first, w_last, n_win, win_ll);
+            }
+            if (arm_on) {
+                uint32_t seg[4];
+                int ok[2];
+                double p[4], q[4];
+                arm_segments(s_row, w_first, w_last, n_win, seg, ok);
+                llr_range_host(win_ll, seg[0], seg[1], p);
+                llr_range_host(win_ll, seg[2], seg[3], q);
+                arm_res[4 * ti] = ok[0] ? p[0] : NAN;
+                arm_res[4 * ti + 1] = ok[1] ? q[0] : NAN;
+                arm_res[4 * ti + 2] = ok[0] ? p[2] : NAN;
+                arm_res[4 * ti + 3] = ok[1] ? q[2] : NAN;
             }
         } else {
             /* one contiguous window range per GPU, evaluated concurrently, gathered in order */
             static size_t cuts[65];                    /* kept with the site list */
             shard_job jobs[64];
             pthread_t th[64];
+            /* --arm-stats: the arms of the site list in its global windows, cut into each device's window range */
+            static uint32_t arm_local[64][4], arm_wcut[65];
+            static int arm_ok[2];
             if (!same_sites)
                 window_cuts(s_nr, s_na, n, (unsigned)opt_window, n_eng, cuts);
+            if (arm_on && !same_sites) {
+                uint32_t *an, seg[4];
+                free(arm_wfirst); free(arm_wlast);
+                const size_t nw = arm_nw = host_windows(s_nr, s_na, n, (unsigned)opt_window, &arm_wfirst, &arm_wlast, &an);
+                arm_segments(s_row, arm_wfirst, arm_wlast, nw, seg, arm_ok);
+                free(an);
+                for (int d = 0; d <= n_eng; ++d)
+                    arm_wcut[d] = (uint32_t)(nw * (size_t)d / (size_t)n_eng);     /* window_cuts' windows per device */
+                for (int d = 0; d < n_eng; ++d)
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t v = seg[k] < arm_wcut[d] ? arm_wcut[d] : seg[k] > arm_wcut[d + 1] ? arm_wcut[d + 1] : seg[k];
+                        arm_local[d][k] = v - arm_wcut[d];
+                    }
+            }
             if (slice_mode && ti == 0) {
                 /* every device gets the panel rows from its first site's row to its last site's row, and its
                  * sites are numbered within that slice */
@@ -2571,6 +2737,8 @@ int main(int argc, char **argv)
                 j->bg_count = bg_count; j->pu_id = (int)pu_id; j->ld = opt_ld;
                 j->dev_idx = d; j->same_sites = batchable;
                 j->site_ll = site_ll;
+                j->arm_seg = arm_on ? arm_local[d] : NULL;
+                j->stats_only = opt_stats_only;
                 /* (no thread to be had: the shard runs here -- never exit() while other shard threads are
                  * inside the GPU runtime) */
                 th_started[d] = n_eng > 1 && pthread_create(&th[d], NULL, shard_run, j) == 0;
@@ -2588,7 +2756,24 @@ int main(int argc, char **argv)
             }
             if (shard_failed >= 0)
                 DIE("%s\n", ibdg_last_error(jobs[shard_failed].eng));
-            if (n_eng == 1 && jobs[0].a == 0) {
+            if (arm_on) {
+                /* each device's parts of the two arms, added in device order, then rounded */
+                double acc[8] = {0};
+                for (int d = 0; d < n_eng; ++d) {
+                    if (jobs[d].n_win != arm_wcut[d + 1] - arm_wcut[d])
+                        DIE("[::] ERROR: device %d holds %zu windows, not the %u of its range.\n", d, jobs[d].n_win,
+                            arm_wcut[d + 1] - arm_wcut[d]);
+                    for (int k = 0; k < 4; ++k)
+                        dd_add(acc + 2 * k, jobs[d].arm[2 * k], jobs[d].arm[2 * k + 1]);
+                }
+                arm_res[4 * ti] = arm_ok[0] ? acc[0] + acc[1] : NAN;
+                arm_res[4 * ti + 1] = arm_ok[1] ? acc[4] + acc[5] : NAN;
+                arm_res[4 * ti + 2] = arm_ok[0] ? acc[2] + acc[3] : NAN;
+                arm_res[4 * ti + 3] = arm_ok[1] ? acc[6] + acc[7] : NAN;
+            }
+            if (opt_stats_only) {
+                /* no window table left the device */
+            } else if (n_eng == 1 && jobs[0].a == 0) {
                 /* one device, the whole site list: its arrays as they are (a copy of 1.2 MB per individual otherwise) */
                 w_first = jobs[0].w_first; w_last = jobs[0].w_last; w_ncov = jobs[0].w_ncov; win_ll = jobs[0].win_ll;
             } else {
@@ -2610,10 +2795,18 @@ int main(int argc, char **argv)
             }
         }
 
+        if (arm_on && !no_engine && !opt_stats_only &&
+            (n_win != arm_nw || memcmp(w_first, arm_wfirst, n_win * 4) || memcmp(w_last, arm_wlast, n_win * 4)))
+            DIE("[::] ERROR: the engine's windows are not the ones the chromosome arms were cut from.\n");
         /* the positions a summary row names (:751-756) are the same for every individual over a common site list: looked up
          * once -- row by row they are two dependent loads into 160 MB of row records per window and individual */
         static unsigned long *sum_pos_first, *sum_pos_last;
         static size_t sum_pos_n;
+        if (opt_stats_only) {
+            free(w_first); free(w_last); free(w_ncov); free(win_ll);
+            phase("per individual: engine (upload, run, arm sums)");
+            continue;
+        }
         if (overlap && !no_engine && (ti == 0 || sum_pos_n != n_win)) {
             free(sum_pos_first); free(sum_pos_last);
             sum_pos_first = malloc((n_win + 1) * sizeof *sum_pos_first);
@@ -2681,6 +2874,36 @@ int main(int argc, char **argv)
     }
     if (overlap)
         phase("output files of the last individuals (written beside the engine's work on the ones after them)");
+    if (arm_on) {
+        /* one file for the run, written here once: the lines in comparison order, as bin/chrarm-stats.py prints them */
+        char *arm_fn;
+        const char *chrom = uchr ? uchr : pu->n_lines ? pu->chr_names[pu->lines[0].chr] : ".";
+        if (asprintf(&arm_fn, "%s/%s.armstats.txt", out_dir, opt_sq) < 0)
+            quit(1);
+        FILE *af = fopen(arm_fn, "w");
+        if (!af) {
+            fprintf(stderr, "[::] ERROR: Cannot open '%s' for writing.\n", arm_fn);
+            quit(1);
+        }
+        fprintf(af, "SAMPLE\tCHROM\tparm_IBD2/IBD0\tqarm_IBD2/IBD0\tparm_IBD1/IBD0\tqarm_IBD1/IBD0\n");
+        for (size_t ti = 0; ti < targets.n; ++ti) {
+            fprintf(af, "%s\t%s", ids.names[targets.idx[ti]], chrom);
+            for (int k = 0; k < 4; ++k) {
+                const double v = arm_res[4 * ti + k];
+                if (isnan(v))
+                    fprintf(af, "\tnan");
+                else
+                    fprintf(af, "\t%.3e", v);
+            }
+            fputc('\n', af);
+        }
+        if (fclose(af) != 0) {
+            fprintf(stderr, "[::] ERROR writing '%s'.\n", arm_fn);
+            quit(1);
+        }
+        free(arm_fn);
+        phase("arm statistics file");
+    }
 #if !defined(__SANITIZE_ADDRESS__) && !defined(__SANITIZE_THREAD__)
     if (getenv("IBDGEM_EXIT_PROBE")) {       /* measurement only (tools/warm_phases.py): what of the process's end is the mapping */
         if (packed_mapped_bytes)

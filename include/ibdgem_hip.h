@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define IBDG_ABI_VERSION 5   /* 5: ibdg_num_targets, ibdg_upload_panel_fd; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
+#define IBDG_ABI_VERSION 5   /* 5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
                               * longer what a sparse pileup gets.  3: options site_results, stage_workers; ibdg_get_site_af
                               * computes on demand; ibdg_last_run_ms out[4] is 0 */
 
@@ -186,6 +186,14 @@ int ibdg_get_window_ll(ibdg_ctx *ctx, size_t t, double *out);
  * comparison individuals takes a batch's tables off the device at once and can queue the next batch before it goes
  * through them: the host program's --summary-only loop, reference src/ibdgem.c:522 with :751-756). */
 int ibdg_get_window_ll_all(ibdg_ctx *ctx, double *out);
+/* For each comparison individual t of the last ibdg_run and each window range s = [first[s], end[s]) of its
+ * site list: the sums over the range of log2(L2') - log2(L0') and log2(L1') - log2(L0') (L' = L, or 2^-1074 where
+ * L == 0), each as a double-double: out[((t * n_seg) + s) * 4 + {0,1,2,3}] = {IBD2/IBD0 hi, lo, IBD1/IBD0 hi, lo}.
+ * The terms of the reference's bin/chrarm-stats.py, taken as differences of fp64 logs and summed on the device without
+ * copying the window tables back; a NaN window makes its sums NaN, an empty range gives 0, 0.  hi + lo rounded is the
+ * same for any split of a range into parts whose double-doubles are added in order.  Errors: no results, end[s] <
+ * first[s], end[s] > ibdg_num_windows, NULL arrays with n_seg > 0.  Returns after the sums are in host memory. */
+int ibdg_window_llr_sums(ibdg_ctx *ctx, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out);
 /* Alt-allele count of panel rows [first_row, first_row+n): out[n] (for tests). */
 int ibdg_get_alt_counts(ibdg_ctx *ctx, size_t first_row, size_t n, uint32_t *out);
 
