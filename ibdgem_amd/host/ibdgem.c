@@ -83,6 +83,7 @@ static struct option longopts[] = {
     {"indv", required_argument, 0, 'I'},
     {"pileup", required_argument, 0, 'P'},
     {"pileup-name", required_argument, 0, 'N'},
+    {"pileup-list", required_argument, 0, 1007},
     {"window-size", required_argument, 0, 'w'},
     {"allele-freqs", required_argument, 0, 'A'},
     {"sample-list", required_argument, 0, 'S'},
@@ -106,11 +107,16 @@ static void usage(int code)
     fputs("ibdgem (MI355X engine): likelihood that low-coverage reads (pileup) and a genotyped\n"
           "individual share 0, 1 or 2 chromosomes identical by descent, per SNP and per window.\n\n"
           "Usage: ibdgem [--LD] -H hap -L legend -I indv -P pileup [options]\n"
+          "       ibdgem [--LD] -H hap -L legend -I indv --pileup-list FILE [options]\n"
           "  --LD                      background-panel (linkage-aware) window likelihoods\n"
           "  -H/--hap, -L/--legend, -I/--indv FILE   IMPUTE genotype input (plain or .gz)\n"
           "  -V/--vcf FILE             VCF genotype input (plain or .gz), biallelic SNP rows with 0/1 genotypes\n"
           "  -P/--pileup FILE          samtools pileup of the unknown sample (required)\n"
           "  -N/--pileup-name STR      name of the pileup sample (default UNKWN)\n"
+          "  --pileup-list FILE        several pileups against the one panel in one run, instead of -P / -N: a line\n"
+          "                            'NAME PATH' per pileup ('#' lines skipped); every pileup gets the files and\n"
+          "                            messages `-P PATH -N NAME` would give it, in list order.  With --devices each\n"
+          "                            context holds the whole panel and takes whole pileups from the list\n"
           "  -A/--allele-freqs FILE    CHROM POS AF table overriding the panel's own frequencies\n"
           "  -S/--sample-list FILE     individuals to compare against, one per line\n"
           "  -s/--sample STR           the same, comma separated\n"
@@ -378,10 +384,13 @@ static void packed_map(void)
 }
 
 /* the packed rows for the few things the host itself reads them for (a row's alleles of the comparison individual in the
- * per-site table, -v, a run without a device): with a panel cache the file is mapped at the first such call */
+ * per-site table, -v, a run without a device): with a panel cache the file is mapped at the first such call.  Several
+ * threads get here at once (formatters, shard and output threads, the contexts of a --pileup-list): with a cache, every
+ * call goes through pthread_once, whose return orders the mapping's store before this load (`packed` is never read
+ * unsynchronised while another thread may write it). */
 static inline const uint64_t *packed_rows(void)
 {
-    if (__builtin_expect(!packed && packed_fd >= 0, 0))
+    if (packed_fd >= 0)
         pthread_once(&packed_once, packed_map);
     return packed;
 }
@@ -786,8 +795,8 @@ static inline unsigned row_allele(size_t r, unsigned indiv, unsigned hap)
  * 310 values discarded, result = r >> 1).  The stream is restated here instead of calling
  * rand(): the HIP runtime inside this process draws from libc's global generator too, which
  * would shift the sequence.  tests/test_host_cli.py checks it against libc. */
-static uint32_t grand_state[34];
-static int grand_f = 3, grand_r = 0, grand_ready = 0;
+static __thread uint32_t grand_state[34];     /* per thread: each pileup of a --pileup-list starts the stream afresh, */
+static __thread int grand_f = 3, grand_r = 0, grand_ready = 0;   /* as a process of its own would (grand_seed(1)) */
 
 static void grand_seed(uint32_t seed)
 {
@@ -1628,6 +1637,8 @@ typedef struct {
     const uint32_t *arm_seg;                 /* --arm-stats: {p first, p end, q first, q end} in the slice's window indices, or NULL */
     double arm[8];                           /* ... the individual's sums over them (ibdg_window_llr_sums) */
     int stats_only;                          /* --stats-only: no window table leaves the device */
+    FILE *err;                               /* where the pileup's messages go */
+    int reported;                            /* a failure was reported here already (not an engine error) */
 } shard_job;
 
 /* Per device: the window table of the site list at hand (first row, last row, covered rows per window -- the same for
@@ -1650,6 +1661,18 @@ typedef struct {
     const uint32_t *ahead_of;                /* the batch that has been queued ahead on the device; NULL: none */
 } win_cache;
 static win_cache g_wcache[64];
+
+/* the engine's last run must be the run of this very batch: its size says so (a diagnostic when it does not) */
+static int same_run_size(shard_job *j)
+{
+    const size_t have = ibdg_num_targets(j->eng);
+    if (have == j->n_targets)
+        return 1;
+    fprintf(j->err ? j->err : stderr, "[::] ERROR: context %d holds the results of %zu comparison individuals, not the %zu of "
+            "the batch at hand.\n", j->dev_idx, have, j->n_targets);
+    j->reported = 1;
+    return 0;
+}
 
 static void *shard_run(void *arg)
 {
@@ -1680,7 +1703,7 @@ static void *shard_run(void *arg)
                 wc->arm_sums = malloc(j->n_targets * 8 * sizeof(double));
                 wc->arm_cap = wc->arm_sums ? j->n_targets * 8 : 0;
             }
-            if (!wc->arm_sums || ibdg_num_targets(j->eng) != j->n_targets || ibdg_window_llr_sums(j->eng, sf, se, 2, wc->arm_sums))
+            if (!wc->arm_sums || !same_run_size(j) || ibdg_window_llr_sums(j->eng, sf, se, 2, wc->arm_sums))
                 return NULL;
         }
         if (j->stats_only) {
@@ -1701,7 +1724,7 @@ static void *shard_run(void *arg)
             }
             if (wc->batch_ll && !j->want_sites) {
                 /* (the copy is as large as the LAST RUN's results: it must be the run of this very batch) */
-                if (ibdg_num_targets(j->eng) != j->n_targets || ibdg_get_window_ll_all(j->eng, wc->batch_ll))        /* waits for the run */
+                if (!same_run_size(j) || ibdg_get_window_ll_all(j->eng, wc->batch_ll))        /* waits for the run */
                     return NULL;
                 wc->batch_of = j->targets;
                 wc->batch_T = j->n_targets;
@@ -1793,7 +1816,8 @@ static void window_cuts(const uint8_t *nr, const uint8_t *na, size_t n, unsigned
 
 /* IBDGEM_TIMING=1 in the environment: wall-clock seconds per phase on stderr ("## time <phase> <s>") */
 static int timing_on = -1;
-static double timing_last;
+static __thread double timing_last;             /* per thread: the pileups of a --pileup-list are read beside the device work */
+static __thread const char *timing_tag;         /* --pileup-list: the pileup the phases belong to ("## time [NAME] ...") */
 static double now_s(void)
 {
     struct timespec ts;
@@ -1833,17 +1857,20 @@ static void phase(const char *name)
     if (!timing_on)
         return;
     const double t = now_s();
-    fprintf(stderr, "## time %s %.4f\n", name, t - timing_last);
+    if (timing_tag)
+        fprintf(stderr, "## time [%s] %s %.4f\n", timing_tag, name, t - timing_last);
+    else
+        fprintf(stderr, "## time %s %.4f\n", name, t - timing_last);
     timing_last = t;
 }
 
-/* page-locked memory from the engine when asked for and available, plain memory otherwise (never freed:
- * these arrays live as long as the program) */
-static void *io_alloc(size_t bytes, int pinned)
+/* a thread's phases start here, tagged with the pileup they belong to (NULL: untagged, a single -P run) */
+static void phase_begin(const char *tag)
 {
-    void *p = pinned ? ibdg_host_alloc(bytes) : NULL;
-    return p ? p : malloc(bytes);
+    timing_last = now_s();
+    timing_tag = tag;
 }
+
 
 /* the row filter chain up to the read counts (src/ibdgem.c:589-626) for the rows [a, b) */
 typedef struct {
@@ -1986,8 +2013,9 @@ static void *upload_run(void *arg)
      * first batch on (left alone, the engine gets there by itself once its runs have added up: nine batches) */
     if (j->share_sites >= 240 && ibdg_set_option(j->eng, "compact_tiles", 1))
         return NULL;
-    /* with a panel cache the engine reads the rows from the file itself (no mapping of 2.56 GB on this side) */
-    if (packed_fd >= 0 && !packed
+    /* with a panel cache the engine reads the rows from the file itself (no mapping of 2.56 GB on this side) -- decided
+     * by packed_fd alone: `packed` may be mapped by another thread at this very moment */
+    if (packed_fd >= 0
             ? ibdg_upload_panel_fd(j->eng, packed_fd, packed_off + (uint64_t)j->r0 * row_words * 8, j->n, j->n_ids)
             : ibdg_upload_panel(j->eng, packed_rows() + j->r0 * row_words, j->n, j->n_ids))
         return NULL;
@@ -2147,16 +2175,19 @@ typedef struct {
     const unsigned long *pos_first, *pos_last;  /* shared: the windows' first / last positions of the common site list, or NULL */
     char *sum_buf;                              /* the slot's buffer for the text of a summary file (kept between individuals) */
     size_t sum_cap;
+    const char *sq;                             /* the pileup's name (-N) */
+    FILE *err;                                  /* where the pileup's messages go */
 } out_job;
 
-enum { OUT_SLOTS = 12 };
-static out_job g_outs[OUT_SLOTS];
+enum { OUT_SLOTS = 12, MAX_WORKERS = 64 };
+static out_job g_outs[MAX_WORKERS][OUT_SLOTS];  /* per worker (one per context with --pileup-list, else one) */
+static int g_n_workers = 1;
 
-/* see quit(): join the output threads; when the run is failing, empty the files nobody got to */
-static void outs_settle(int failing)
+/* join a worker's output threads; when its run is failing, empty the files nobody got to */
+static void outs_settle_one(out_job *outs, int failing)
 {
     for (int k = 0; k < OUT_SLOTS; ++k) {
-        out_job *o = &g_outs[k];
+        out_job *o = &outs[k];
         if (o->running) {
             o->running = 0;
             pthread_join(o->th, NULL);
@@ -2171,17 +2202,24 @@ static void outs_settle(int failing)
     }
 }
 
+/* see quit(): every worker's (they have all been joined by then) */
+static void outs_settle(int failing)
+{
+    for (int w = 0; w < g_n_workers; ++w)
+        outs_settle_one(g_outs[w], failing);
+}
+
 static void *output_individual(void *arg)
 {
     out_job *o = arg;
     o->failed = 1;
     FILE *tab = o->tab, *sum = o->sum;           /* opened by the main thread: a directory that cannot be written stops the run at once */
     if (opt_plan)
-        printf("## PLAN %s %s processed=%lu skipped=%lu windows=%zu cull_p=%f\n", opt_sq, o->tname, o->processed, o->skipped,
+        printf("## PLAN %s %s processed=%lu skipped=%lu windows=%zu cull_p=%f\n", o->sq, o->tname, o->processed, o->skipped,
                o->n_win, o->cull_p);
     else {
         if ((!opt_summary_only && ftruncate(fileno(tab), 0) != 0) || ftruncate(fileno(sum), 0) != 0) {
-            fprintf(stderr, "[::] ERROR in compare_impute(): Cannot empty the output files of %s.\n", o->tname);
+            fprintf(o->err, "[::] ERROR in compare_impute(): Cannot empty the output files of %s.\n", o->tname);
             return NULL;
         }
         o->pending = 0;
@@ -2209,7 +2247,7 @@ static void *output_individual(void *arg)
         proto.pre = o->pre;
         proto.pre_off = o->pre_off;
         if (write_rows_parallel(tab, proto, o->n, o->threads)) {
-            fprintf(stderr, "[::] ERROR writing the per-site rows of %s.\n", o->tname);
+            fprintf(o->err, "[::] ERROR writing the per-site rows of %s.\n", o->tname);
             return NULL;
         }
     }
@@ -2226,7 +2264,7 @@ static void *output_individual(void *arg)
         sj.s_row = o->s_row; sj.w_first = o->w_first; sj.w_last = o->w_last; sj.w_ncov = o->w_ncov; sj.win_ll = o->win_ll;
         sj.pos_first = o->pos_first; sj.pos_last = o->pos_last;
         if (write_summary_parallel(sum, sj, o->n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
-            fprintf(stderr, "[::] ERROR writing the summary rows of %s.\n", o->tname);
+            fprintf(o->err, "[::] ERROR writing the summary rows of %s.\n", o->tname);
             return NULL;
         }
     }
@@ -2249,6 +2287,737 @@ static void *output_individual(void *arg)
     return NULL;
 }
 
+/* ---- one pileup of the run: -P, or an entry of --pileup-list ----------------------------------------------------------
+ * What belongs to the pileup -- its lines, coverage histogram and cull ratio, the target-independent part of the filter
+ * chain, the site lists and output files of its comparisons -- lives in a pile_job; what belongs to the panel -- names,
+ * genotype rows, the device contexts with the panel on them, alt counts -- is set up once by main.  A list is worked
+ * through by one worker per context (one without a device); a worker reads and filters its next pileup on threads of
+ * their own while it runs the one at hand, and no further ahead.  Every pileup's messages go to a buffer of its own,
+ * printed in list order once it is done (a single -P run writes them to stderr as they come). */
+typedef struct {
+    const char *name, *path;       /* -N, -P */
+    FILE *err;
+    char *err_buf;
+    size_t err_len;
+    pileup_t *pu;
+    long pu_id;                    /* the pileup's own name in the panel: left out of its background (:501-506) */
+    unsigned long in_dist[128];
+    double mean_cov, cull_p;
+    cand_t *cand;                  /* the rows that passed the target-independent filters */
+    uint8_t *row_fate;
+    size_t n_cand;
+    int rc;                        /* 0: fine so far; 1: failed; -1: not run (an earlier entry failed) */
+    int done;
+    char **files;                  /* --pileup-list: the output files it wrote */
+    size_t n_files;
+} pile_job;
+
+static names_t g_ids;
+static idlist_t g_targets;
+static uint8_t *g_bg_count;
+static const char *g_out_dir, *g_user_cmd, *g_uchr;
+static int g_no_engine, g_host_math, g_list_mode;
+static double *g_pdg_tab;
+
+static struct {
+    pile_job *jobs;
+    size_t n;
+    size_t next_take;              /* the next entry a worker takes */
+    size_t next_print;             /* the next entry whose messages go to stderr */
+    size_t fail_at;                /* the first entry that failed (n: none) */
+    pthread_mutex_t mu;
+} g_list = {NULL, 0, 0, 0, 0, PTHREAD_MUTEX_INITIALIZER};
+
+/* host threads for one pileup's reading, filter chain and files: all of them, or with several contexts working through a list
+ * side by side each worker's share of them */
+static int g_thread_share;
+static int all_threads(void)
+{
+    return g_thread_share > 0 ? g_thread_share : opt_threads > 0 ? opt_threads : default_threads();
+}
+
+/* --pileup-list FILE: "NAME PATH" per line, '#' lines and blank lines skipped.  Refusals exit(1) with one line. */
+static void read_pileup_list(const char *fn, pile_job **out, size_t *n_out)
+{
+    FILE *f = fopen(fn, "r");
+    if (!f) {
+        fprintf(stderr, "[::] ERROR: Cannot open the pileup list '%s'.\n", fn);
+        exit(1);
+    }
+    pile_job *jobs = NULL;
+    size_t n = 0, cap = 0, ln = 0, lcap = 0;
+    size_t *line_of = NULL;
+    char *line = NULL;
+    while (getline(&line, &lcap, f) >= 0) {
+        ++ln;
+        char *p = line;
+        while (isspace((unsigned char)*p))
+            ++p;
+        if (!*p || *p == '#')
+            continue;
+        char *save = NULL, *name = strtok_r(p, " \t\r\n", &save), *path = strtok_r(NULL, " \t\r\n", &save);
+        if (!name || !path || strtok_r(NULL, " \t\r\n", &save)) {
+            fprintf(stderr, "[::] ERROR: Line %zu of the pileup list '%s' is not 'NAME PATH'.\n", ln, fn);
+            exit(1);
+        }
+        for (size_t i = 0; i < n; ++i)
+            if (strcmp(jobs[i].name, name) == 0) {
+                fprintf(stderr, "[::] ERROR: Pileup name '%s' appears twice in the pileup list '%s' (lines %zu and %zu).\n", name,
+                        fn, line_of[i], ln);
+                exit(1);
+            }
+        if (n == cap) {
+            cap = cap ? 2 * cap : 16;
+            jobs = ls_xrealloc(jobs, cap * sizeof *jobs);
+            line_of = ls_xrealloc(line_of, cap * sizeof *line_of);
+        }
+        memset(&jobs[n], 0, sizeof jobs[n]);
+        jobs[n].name = strdup(name);
+        jobs[n].path = strdup(path);
+        line_of[n++] = ln;
+    }
+    free(line);
+    free(line_of);
+    fclose(f);
+    if (n == 0) {
+        fprintf(stderr, "[::] ERROR: The pileup list '%s' names no pileup.\n", fn);
+        exit(1);
+    }
+    *out = jobs;
+    *n_out = n;
+}
+
+/* the pileup itself (src/ibdgem.c:1001-1010) */
+static void pj_read(pile_job *pj)
+{
+    pj->pu = pileup_read_mt_to(pj->path, g_uchr, all_threads(), pj->err);
+    if (!pj->pu) {
+        fprintf(pj->err, "[::] ERROR parsing Pileup data; make sure input is valid.\n");
+        pj->rc = 1;
+    }
+}
+
+/* input coverage distribution and cull ratio: find_cull_p (:83-106) */
+static void pj_depth(pile_job *pj)
+{
+    const pileup_t *pu = pj->pu;
+    unsigned long in_total = 0;
+    memset(pj->in_dist, 0, sizeof pj->in_dist);
+    for (size_t i = 0; i < pu->n_lines; ++i)
+        if (pu->lines[i].cov <= opt_max_cov) {
+            in_total += pu->lines[i].cov;
+            pj->in_dist[pu->lines[i].cov]++;
+        }
+    pj->mean_cov = (double)in_total / pu->n_lines;
+    pj->cull_p = 1;
+    if (has_D) {
+        if (opt_target_dp > pj->mean_cov)
+            fprintf(pj->err, "Observed depth is lower than target depth -D. No culling will be done.\n");
+        else
+            pj->cull_p = opt_target_dp / pj->mean_cov;
+    }
+}
+
+/* ---- target-independent part of the row filter chain (:589-626) -------------------
+ * Rows are independent here: a team of threads takes contiguous row ranges, each fills its own part
+ * of cand[] from the range's first row on, and the parts are closed up in order afterwards. */
+static void pj_filter(pile_job *pj)
+{
+    pj->pu_id = find_name(&g_ids, pj->name);
+    cand_t *cand = pj->cand = malloc((n_rows ? n_rows : 1) * sizeof *cand);
+    uint8_t *row_fate = pj->row_fate = calloc(n_rows ? n_rows : 1, 1);   /* 0 skip-before-v, 1 candidate, 2 skipped after the -v test */
+    if (!cand || !row_fate) {
+        fprintf(pj->err, "[::] ERROR: out of memory for %zu rows.\n", n_rows);
+        pj->rc = 1;
+        return;
+    }
+    size_t n_cand = 0;
+    int T = all_threads();
+    if (T > 64) T = 64;
+    if (n_rows * 64 < ls_mt_min_bytes()) T = 1;           /* small inputs (and the tests, unless they ask) on one thread */
+    filter_job fj[64];
+    pthread_t th[64];
+    for (int t = 0; t < T; ++t) {
+        filter_job *j = &fj[t];
+        j->a = n_rows * (size_t)t / (size_t)T;
+        j->b = n_rows * (size_t)(t + 1) / (size_t)T;
+        j->pu = pj->pu; j->alt_count = alt_count_h; j->n_ids = (unsigned)g_ids.n; j->in_vcf = in_vcf; j->has_p = has_p;
+        j->has_A = has_A;
+        j->cand = cand + j->a; j->row_fate = row_fate; j->n = 0;
+        if (T == 1 || pthread_create(&th[t], NULL, filter_rows, j) != 0) {
+            filter_rows(j);
+            th[t] = pthread_self();
+        }
+    }
+    for (int t = 0; t < T; ++t) {
+        if (!pthread_equal(th[t], pthread_self()))
+            pthread_join(th[t], NULL);
+        if (fj[t].cand != cand + n_cand)
+            memmove(cand + n_cand, fj[t].cand, fj[t].n * sizeof *cand);
+        n_cand += fj[t].n;
+    }
+    pj->n_cand = n_cand;
+}
+
+/* a list entry after the first: read and filtered on a thread of its own while its worker runs the entry before it */
+static void *pj_prepare(void *arg)
+{
+    pile_job *pj = arg;
+    phase_begin(pj->name);
+    pj_read(pj);
+    if (!pj->rc)
+        pj_depth(pj);
+    phase("pileup");
+    if (!pj->rc)
+        pj_filter(pj);
+    phase("row filter chain");
+    return NULL;
+}
+
+/* what a pileup holds once its files are written (a list keeps host memory to two pileups per worker) */
+static void pj_release(pile_job *pj)
+{
+    pileup_free(pj->pu);
+    free(pj->cand);
+    free(pj->row_fate);
+    pj->pu = NULL;
+    pj->cand = NULL;
+    pj->row_fate = NULL;
+}
+
+static void pj_add_file(pile_job *pj, const char *fn)
+{
+    if (!g_list_mode)
+        return;
+    pj->files = ls_xrealloc(pj->files, (pj->n_files + 1) * sizeof *pj->files);
+    pj->files[pj->n_files++] = strdup(fn);
+}
+
+/* the next entry for a worker, -1 when there is none or an entry has failed */
+static long list_take(void)
+{
+    pthread_mutex_lock(&g_list.mu);
+    long i = -1;
+    if (g_list.fail_at == g_list.n && g_list.next_take < g_list.n)
+        i = (long)g_list.next_take++;
+    pthread_mutex_unlock(&g_list.mu);
+    return i;
+}
+
+static int list_failed_before(size_t i)
+{
+    pthread_mutex_lock(&g_list.mu);
+    const int f = g_list.fail_at < i;
+    pthread_mutex_unlock(&g_list.mu);
+    return f;
+}
+
+/* an entry is done: its messages, and those of the done entries after it, go to stderr in list order (up to and including a
+ * failed entry: nothing of the entries after it is printed) */
+static void list_finish(size_t i, int rc)
+{
+    pthread_mutex_lock(&g_list.mu);
+    pile_job *pj = &g_list.jobs[i];
+    pj->rc = rc;
+    pj->done = 1;
+    if (rc > 0 && i < g_list.fail_at)
+        g_list.fail_at = i;
+    while (g_list.next_print < g_list.n && g_list.jobs[g_list.next_print].done && g_list.next_print <= g_list.fail_at) {
+        pile_job *q = &g_list.jobs[g_list.next_print++];
+        if (q->err != stderr) {
+            fclose(q->err);                               /* (its output threads have all been joined) */
+            q->err = NULL;
+            if (q->err_len)
+                fwrite(q->err_buf, 1, q->err_len, stderr);
+            fflush(stderr);
+            free(q->err_buf);
+            q->err_buf = NULL;
+        }
+    }
+    pthread_mutex_unlock(&g_list.mu);
+}
+
+/* a worker: the contexts it drives (all of them for a single -P run, one for a list), their panel uploads and its output slots */
+typedef struct {
+    ibdg_ctx *engs[64];
+    int n_eng, dev_base;
+    upload_job *ups;
+    int n_ups, ups_pending;
+    int slice_mode;
+    out_job *outs;
+    long first;                    /* its first entry, handed out before any worker starts (-1: none) */
+    int first_ready;               /* ... already read and filtered (by main) */
+    pthread_t th;
+    int started;
+} worker_t;
+
+#define PFAIL(...)                        \
+    do {                                  \
+        fprintf(err, __VA_ARGS__);        \
+        goto fail;                        \
+    } while (0)
+
+/* ---- per comparison individual (:522-773) of one pileup ------------------------------------------ */
+static int pj_run(pile_job *pj, worker_t *w)
+{
+    grand_seed(1);                  /* a fresh process's read-thinning stream (-D) */
+    if (g_list_mode)
+        timing_tag = pj->name;
+    FILE *err = pj->err;
+    const char *sq = pj->name;
+    const pileup_t *pu = pj->pu;
+    const cand_t *cand = pj->cand;
+    const uint8_t *row_fate = pj->row_fate;
+    const size_t n_cand = pj->n_cand;
+    const double cull_p = pj->cull_p;
+    const long pu_id = pj->pu_id;
+    const idlist_t targets = g_targets;
+    const int no_engine = g_no_engine, host_math = g_host_math;
+    ibdg_ctx *const *engs = w->engs;
+    const int n_eng = w->n_eng;
+    upload_job *const ups = w->ups;
+    const int slice_mode = w->slice_mode;
+    out_job *const outs = w->outs;
+    const int batchable = !no_engine && !has_v && cull_p == 1.0;
+    const char *out_dir = g_out_dir;
+    /* Round 2 page-locked the arrays that cross the engine's boundary (ibdg_host_alloc).  Measured since: locking 128 MB costs 0.1 s, giving it
+     * back at exit 0.2 s, and the copies it was meant to speed up (24 MB in, 96 MB out per comparison) run at the same
+     * 56 GB/s from ordinary memory (bench.py results_to_host) -- so they are ordinary memory now (malloc / free). */
+    uint32_t *s_row = malloc((n_cand ? n_cand : 1) * 4), *s_cand = malloc((n_cand ? n_cand : 1) * 4);
+    uint8_t *s_nr = malloc(n_cand ? n_cand : 1), *s_na = malloc(n_cand ? n_cand : 1);
+    double *s_fo = has_A ? malloc((n_cand ? n_cand : 1) * 8) : NULL;
+    /* the per-site values are only fetched for the per-site table: no 128 MB of page-locked memory for --summary-only */
+    const size_t n_site_out = opt_summary_only && !no_engine ? 1 : (n_cand ? n_cand : 1);
+    double *site_ll = malloc(n_site_out * 24);
+    if (!s_row || !s_cand || !s_nr || !s_na || !site_ll)
+        PFAIL("[::] ERROR: out of memory for %zu rows.\n", n_cand);
+    phase("result arrays");
+    uint32_t *s_row_dev = NULL;     /* slice_mode: the site list's rows counted from each device's first row */
+    /* The files of up to out_slots individuals are written beside the main thread's work on the ones after them, each from
+     * a per-row array of its own -- when the site list is the same for all of them (it is read by the writers), the rows go
+     * to files (stdout keeps its order) and there is a table to write at all. */
+    /* (--summary-only: the summary files alone, 2.5 MB each at 35 000 windows -- 1.5 ms per individual when written one
+     * after the other, most of a whole-panel job whose engine time is 0.2 ms per individual) */
+    const int overlap = !has_v && cull_p == 1.0 && !opt_plan && targets.n > 1;
+    double *site_slot[OUT_SLOTS] = {site_ll};
+    /* (--summary-only: 2.5 MB per individual instead of 330: twelve individuals at a time with four formatter threads each --
+     * 0.52 ms per individual in a run of 960 against 0.65 with six and eight, 0.90 with four, tools/many_summaries.py) */
+    int out_slots = opt_summary_only ? 12 : 4;
+    char *row_pre = NULL;                       /* columns 1-9 of every row as text, shared by all individuals' tables */
+    uint32_t *row_pre_off = NULL;                  /* (IBDGEM_OUT_SLOTS=1..12, default 4, 12 with --summary-only: for the tests and for measurements) */
+    if (getenv("IBDGEM_OUT_SLOTS") && atoi(getenv("IBDGEM_OUT_SLOTS")) >= 1 && atoi(getenv("IBDGEM_OUT_SLOTS")) <= OUT_SLOTS)
+        out_slots = atoi(getenv("IBDGEM_OUT_SLOTS"));
+    const int out_threads_env = getenv("IBDGEM_OUT_THREADS") ? atoi(getenv("IBDGEM_OUT_THREADS")) : 0;   /* (measurement switch) */
+    const int arm_on = has_arm && !opt_plan;
+    double *arm_res = arm_on ? malloc((targets.n + 1) * 4 * sizeof(double)) : NULL;   /* per individual: p20, q20, p10, q10 */
+    if (arm_on && !arm_res)
+        PFAIL("[::] ERROR: out of memory.\n");
+    uint32_t *arm_wfirst = NULL, *arm_wlast = NULL;   /* engine path: the windows the arms were cut from (checked against the engine's) */
+    size_t arm_nw = 0;
+    /* kept from one comparison individual to the next while the site list is the same for them */
+    unsigned long skipped = 0, final_total = 0, final_dist[128] = {0};
+    size_t n = 0, n_gt_failed = 0;
+    size_t cuts[65] = {0};
+    uint32_t arm_local[64][4], arm_wcut[65];
+    int arm_ok[2] = {0, 0};
+    /* the positions a summary row names (:751-756) are the same for every individual over a common site list: looked up
+     * once -- row by row they are two dependent loads into 160 MB of row records per window and individual */
+    unsigned long *sum_pos_first = NULL, *sum_pos_last = NULL;
+    size_t sum_pos_n = 0;
+    for (size_t ti = 0; ti < targets.n; ++ti) {
+        const uint32_t tgt = targets.idx[ti];
+        if (overlap) {
+            out_job *prev = &outs[ti % (size_t)out_slots]; /* the slot's previous individual: its files must be closed */
+            if (prev->running) {
+                pthread_join(prev->th, NULL);
+                prev->running = 0;
+                if (prev->failed)
+                    goto fail;
+                phase("per individual: waiting for the output files of an earlier individual");
+            }
+            if (!site_slot[ti % (size_t)out_slots]) {
+                site_slot[ti % (size_t)out_slots] = malloc(n_site_out * 24);
+                if (!site_slot[ti % (size_t)out_slots])
+                    PFAIL("[::] ERROR: out of memory for %zu rows.\n", n_cand);
+            }
+            site_ll = site_slot[ti % (size_t)out_slots];
+        }
+        const char *tname = g_ids.names[tgt];
+        fprintf(err, "Running %s-vs-%s comparison...\n", sq, tname);
+        /* Without -v and -D the site list does not depend on the comparison individual (:584, :627-628): it is
+         * built for the first one and kept -- 9 ms per individual at 4M rows, more than its engine time.  The
+         * reference's message for rows whose genotypes did not parse is repeated per individual as it prints it. */
+        const int same_sites = !has_v && cull_p == 1.0 && ti > 0;
+        if (same_sites) {
+            for (size_t r = 0; r < n_rows && n_gt_failed; ++r)
+                if (row_fate[r] == 0 && rows[r].gt_failed)
+                    fprintf(err, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[r].pos);
+        } else {
+            n_gt_failed = 0;
+            skipped = final_total = 0;
+            memset(final_dist, 0, sizeof final_dist);
+            n = 0;
+        }
+        for (size_t r = 0, ci = 0; r < n_rows && !same_sites; ++r) {
+            if (row_fate[r] == 0) {
+                if (rows[r].gt_failed) {
+                    fprintf(err, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[r].pos);
+                    n_gt_failed++;
+                }
+                skipped++;
+                continue;
+            }
+            const int is_cand = row_fate[r] == 1;
+            const size_t my = ci;
+            if (is_cand) ci++;
+            if (has_v && row_allele(r, tgt, 0) == 0 && row_allele(r, tgt, 1) == 0) { skipped++; continue; }   /* :584 */
+            if (!is_cand) { skipped++; continue; }
+            const cand_t *c = &cand[my];
+            const unsigned nr = cull(c->n_ref, cull_p), na = cull(c->n_alt, cull_p);                          /* :627-628 */
+            final_total += nr + na;
+            final_dist[nr + na]++;
+            s_row[n] = c->row; s_cand[n] = (uint32_t)my; s_nr[n] = (uint8_t)nr; s_na[n] = (uint8_t)na;
+            if (s_fo) s_fo[n] = c->f_is_override ? c->f : NAN;
+            n++;
+        }
+        const unsigned long processed = n;
+        phase("per individual: site list");
+        if (ti == 0 && overlap && !opt_summary_only && targets.n >= 3 && n > 0) {
+            /* nine of a row's fourteen columns are the same for every comparison individual: their text is made once */
+            fmt_job pp;
+            memset(&pp, 0, sizeof pp);
+            pp.cand = cand; pp.s_cand = s_cand; pp.pu = pu; pp.s_nr = s_nr; pp.s_na = s_na;
+            if (row_prefix_build(pp, n, all_threads(), &row_pre, &row_pre_off)) {
+                row_pre = NULL;
+                row_pre_off = NULL;
+            }
+            phase("columns 1-9 of every row as text, once for all individuals");
+        }
+
+        /* windows: runs of opt_window covered rows (:572, :657-663, :723-730) */
+        size_t n_win = 0;
+        uint32_t *w_first = NULL, *w_last = NULL, *w_ncov = NULL;
+        double *win_ll = NULL;
+        if (no_engine) {
+            n_win = host_windows(s_nr, s_na, n, (unsigned)opt_window, &w_first, &w_last, &w_ncov);
+            if (host_math) {
+                win_ll = malloc((n_win + 1) * 24);
+                host_nonld(cand, s_cand, s_nr, s_na, n, tgt, g_pdg_tab, all_threads(), site_ll, w_first, w_last, n_win, win_ll);
+            }
+            if (arm_on) {
+                uint32_t seg[4];
+                int ok[2];
+                double p[4], q[4];
+                arm_segments(s_row, w_first, w_last, n_win, seg, ok);
+                llr_range_host(win_ll, seg[0], seg[1], p);
+                llr_range_host(win_ll, seg[2], seg[3], q);
+                arm_res[4 * ti] = ok[0] ? p[0] : NAN;
+                arm_res[4 * ti + 1] = ok[1] ? q[0] : NAN;
+                arm_res[4 * ti + 2] = ok[0] ? p[2] : NAN;
+                arm_res[4 * ti + 3] = ok[1] ? q[2] : NAN;
+            }
+        } else {
+            /* one contiguous window range per GPU, evaluated concurrently, gathered in order */
+            shard_job jobs[64];
+            pthread_t th[64];
+            /* --arm-stats: the arms of the site list in its global windows, cut into each device's window range */
+            if (!same_sites)
+                window_cuts(s_nr, s_na, n, (unsigned)opt_window, n_eng, cuts);
+            if (arm_on && !same_sites) {
+                uint32_t *an, seg[4];
+                free(arm_wfirst); free(arm_wlast);
+                const size_t nw = arm_nw = host_windows(s_nr, s_na, n, (unsigned)opt_window, &arm_wfirst, &arm_wlast, &an);
+                arm_segments(s_row, arm_wfirst, arm_wlast, nw, seg, arm_ok);
+                free(an);
+                for (int d = 0; d <= n_eng; ++d)
+                    arm_wcut[d] = (uint32_t)(nw * (size_t)d / (size_t)n_eng);     /* window_cuts' windows per device */
+                for (int d = 0; d < n_eng; ++d)
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t v = seg[k] < arm_wcut[d] ? arm_wcut[d] : seg[k] > arm_wcut[d + 1] ? arm_wcut[d + 1] : seg[k];
+                        arm_local[d][k] = v - arm_wcut[d];
+                    }
+            }
+            if (slice_mode && ti == 0) {
+                /* every device gets the panel rows from its first site's row to its last site's row, and its
+                 * sites are numbered within that slice */
+                s_row_dev = malloc((n ? n : 1) * 4);
+                if (!s_row_dev)
+                    PFAIL("[::] ERROR: out of memory for %zu rows.\n", n);
+                for (int d = 0; d < n_eng; ++d) {
+                    const size_t a = cuts[d], b = cuts[d + 1];
+                    ups[d].r0 = a < b ? s_row[a] : 0;
+                    ups[d].n = a < b ? (size_t)s_row[b - 1] + 1 - ups[d].r0 : 0;
+                    for (size_t i = a; i < b; ++i)
+                        s_row_dev[i] = s_row[i] - (uint32_t)ups[d].r0;
+                    if (timing_on > 0)
+                        fprintf(stderr, "## panel slice of device %d: rows %zu + %zu of %zu\n", d, ups[d].r0, ups[d].n, n_rows);
+                }
+                g_n_ups = n_eng;                     /* (a single -P run: this is the main thread; quit() joins them) */
+                uploads_start(ups, n_eng);
+                g_uploads_pending = 1;
+                w->ups_pending = 1;
+            }
+            if (w->ups_pending) {
+                const int bad = uploads_join(ups, w->n_ups);
+                w->ups_pending = 0;
+                if (bad >= 0)
+                    PFAIL("%s\n", ibdg_last_error(ups[bad].eng));
+                phase("panel upload (copy, alt counts, transposition; the part not hidden behind the filter chain)");
+            }
+            if (g_list_mode && ti == 0) {
+                /* what upload_run decides for a single run's contexts (share_sites), per pileup: whether this pileup's
+                 * individuals share one site list depends on its own cull ratio, so each pileup gets the layout choice
+                 * its single run makes ("auto" otherwise) */
+                const int compact = batchable && opt_ld && !opt_ref_order && targets.n >= 240;
+                for (int d = 0; d < n_eng; ++d)
+                    if (ibdg_set_option(engs[d], "compact_tiles", compact))
+                        PFAIL("%s\n", ibdg_last_error(engs[d]));
+            }
+            int th_started[64] = {0};
+            for (int d = 0; d < n_eng; ++d) {
+                shard_job *j = &jobs[d];
+                memset(j, 0, sizeof *j);
+                j->eng = engs[d]; j->row = slice_mode ? s_row_dev : s_row; j->nr = s_nr; j->na = s_na; j->fo = s_fo;
+                j->a = cuts[d]; j->b = cuts[d + 1]; j->window = (unsigned)opt_window;
+                j->want_sites = !opt_summary_only;
+                if (batchable) {
+                    const size_t b0 = ti - ti % TARGET_BATCH;
+                    j->targets = targets.idx + b0;
+                    j->n_targets = targets.n - b0 < TARGET_BATCH ? targets.n - b0 : TARGET_BATCH;
+                    j->t_local = ti - b0;
+                    j->do_upload = ti == 0;
+                    j->do_run = ti == b0;
+                    if (b0 + TARGET_BATCH < targets.n && opt_summary_only) {
+                        j->next_targets = targets.idx + b0 + TARGET_BATCH;
+                        j->n_next = targets.n - (b0 + TARGET_BATCH) < TARGET_BATCH ? targets.n - (b0 + TARGET_BATCH) : TARGET_BATCH;
+                    }
+                } else {
+                    j->targets = &targets.idx[ti];
+                    j->n_targets = 1;
+                    j->t_local = 0;
+                    j->do_upload = j->do_run = 1;
+                }
+                j->bg_count = g_bg_count; j->pu_id = (int)pu_id; j->ld = opt_ld;
+                j->dev_idx = w->dev_base + d; j->same_sites = batchable;
+                j->site_ll = site_ll;
+                j->arm_seg = arm_on ? arm_local[d] : NULL;
+                j->stats_only = opt_stats_only;
+                j->err = err;
+                /* (no thread to be had: the shard runs here -- never exit() while other shard threads are
+                 * inside the GPU runtime) */
+                th_started[d] = n_eng > 1 && pthread_create(&th[d], NULL, shard_run, j) == 0;
+                if (!th_started[d])
+                    shard_run(j);
+            }
+            n_win = 0;
+            int shard_failed = -1;
+            for (int d = 0; d < n_eng; ++d) {
+                if (th_started[d])
+                    pthread_join(th[d], NULL);
+                if (jobs[d].failed && shard_failed < 0)
+                    shard_failed = d;
+                n_win += jobs[d].n_win;
+            }
+            if (shard_failed >= 0) {
+                if (jobs[shard_failed].reported)
+                    goto fail;
+                PFAIL("%s\n", ibdg_last_error(jobs[shard_failed].eng));
+            }
+            if (arm_on) {
+                /* each device's parts of the two arms, added in device order, then rounded */
+                double acc[8] = {0};
+                for (int d = 0; d < n_eng; ++d) {
+                    if (jobs[d].n_win != arm_wcut[d + 1] - arm_wcut[d])
+                        PFAIL("[::] ERROR: device %d holds %zu windows, not the %u of its range.\n", d, jobs[d].n_win,
+                              arm_wcut[d + 1] - arm_wcut[d]);
+                    for (int k = 0; k < 4; ++k)
+                        dd_add(acc + 2 * k, jobs[d].arm[2 * k], jobs[d].arm[2 * k + 1]);
+                }
+                arm_res[4 * ti] = arm_ok[0] ? acc[0] + acc[1] : NAN;
+                arm_res[4 * ti + 1] = arm_ok[1] ? acc[4] + acc[5] : NAN;
+                arm_res[4 * ti + 2] = arm_ok[0] ? acc[2] + acc[3] : NAN;
+                arm_res[4 * ti + 3] = arm_ok[1] ? acc[6] + acc[7] : NAN;
+            }
+            if (opt_stats_only) {
+                /* no window table left the device */
+            } else if (n_eng == 1 && jobs[0].a == 0) {
+                /* one device, the whole site list: its arrays as they are (a copy of 1.2 MB per individual otherwise) */
+                w_first = jobs[0].w_first; w_last = jobs[0].w_last; w_ncov = jobs[0].w_ncov; win_ll = jobs[0].win_ll;
+            } else {
+                w_first = malloc((n_win + 1) * 4); w_last = malloc((n_win + 1) * 4); w_ncov = malloc((n_win + 1) * 4);
+                win_ll = malloc((n_win + 1) * 24);
+                size_t wo = 0;
+                for (int d = 0; d < n_eng; ++d) {
+                    shard_job *j = &jobs[d];
+                    const uint32_t a0 = (uint32_t)j->a;
+                    for (size_t wi = 0; wi < j->n_win; ++wi) {
+                        w_first[wo + wi] = j->w_first[wi] + a0;
+                        w_last[wo + wi] = j->w_last[wi] + a0;
+                    }
+                    memcpy(w_ncov + wo, j->w_ncov, j->n_win * 4);
+                    memcpy(win_ll + 3 * wo, j->win_ll, j->n_win * 24);
+                    wo += j->n_win;
+                    free(j->w_first); free(j->w_last); free(j->w_ncov); free(j->win_ll);
+                }
+            }
+        }
+
+        if (arm_on && !no_engine && !opt_stats_only &&
+            (n_win != arm_nw || memcmp(w_first, arm_wfirst, n_win * 4) || memcmp(w_last, arm_wlast, n_win * 4)))
+            PFAIL("[::] ERROR: the engine's windows are not the ones the chromosome arms were cut from.\n");
+        if (opt_stats_only) {
+            free(w_first); free(w_last); free(w_ncov); free(win_ll);
+            phase("per individual: engine (upload, run, arm sums)");
+            continue;
+        }
+        if (overlap && !no_engine && (ti == 0 || sum_pos_n != n_win)) {
+            free(sum_pos_first); free(sum_pos_last);
+            sum_pos_first = malloc((n_win + 1) * sizeof *sum_pos_first);
+            sum_pos_last = malloc((n_win + 1) * sizeof *sum_pos_last);
+            sum_pos_n = n_win;
+            for (size_t wi = 0; wi < n_win && sum_pos_first && sum_pos_last; ++wi) {
+                sum_pos_first[wi] = rows[s_row[w_first[wi]]].pos;
+                sum_pos_last[wi] = rows[s_row[w_last[wi]]].pos;
+            }
+        }
+        phase("per individual: engine (upload, run, results)");
+        out_job *o = &outs[overlap ? ti % (size_t)out_slots : 0];
+        o->pos_first = overlap && !no_engine && sum_pos_first && sum_pos_last ? sum_pos_first : NULL;
+        o->pos_last = o->pos_first ? sum_pos_last : NULL;
+        o->out_dir = out_dir; o->user_cmd = g_user_cmd; o->in_dist = pj->in_dist; o->mean_cov = pj->mean_cov; o->cull_p = cull_p;
+        o->cand = cand; o->s_cand = s_cand; o->s_row = s_row; o->s_nr = s_nr; o->s_na = s_na; o->pu = pu;
+        o->tname = tname; o->tgt = tgt; o->n = n; o->n_win = n_win;
+        o->processed = processed; o->skipped = skipped; o->final_total = final_total;
+        memcpy(o->final_dist, final_dist, sizeof o->final_dist);
+        o->site_ll = site_ll;
+        o->pre = row_pre; o->pre_off = row_pre_off;
+        o->w_first = w_first; o->w_last = w_last; o->w_ncov = w_ncov; o->win_ll = win_ll;
+        o->sq = sq; o->err = err;
+        if (opt_plan) {
+            o->tab = o->sum = stdout;
+        } else {
+            char *tab_fn, *sum_fn;
+            if (asprintf(&tab_fn, "%s/%s.%s.tab.txt", out_dir, sq, tname) < 0 ||
+                asprintf(&sum_fn, "%s/%s.%s.summary.txt", out_dir, sq, tname) < 0)
+                goto fail;
+            /* opened here, emptied by whoever writes them: giving back the pages of an earlier run's 330 MB table takes
+             * tens of milliseconds, which belong to the individual's output job, not between two engine calls */
+            const int tab_fd = open(opt_summary_only ? "/dev/null" : tab_fn, O_WRONLY | O_CREAT, 0666);
+            const int sum_fd = open(sum_fn, O_WRONLY | O_CREAT, 0666);
+            o->tab = tab_fd >= 0 ? fdopen(tab_fd, "w") : NULL;
+            o->sum = sum_fd >= 0 ? fdopen(sum_fd, "w") : NULL;
+            o->pending = 1;
+            if (!opt_summary_only && tab_fd >= 0)
+                pj_add_file(pj, tab_fn);
+            if (sum_fd >= 0)
+                pj_add_file(pj, sum_fn);
+            if (!o->tab || !o->sum)
+                PFAIL("[::] ERROR in compare_impute(): Cannot open '%s' and/or '%s' for writing.\n", tab_fn, sum_fn);
+            free(tab_fn);
+            free(sum_fn);
+        }
+        const int threads = all_threads();
+        /* (tools/many_tables.py: files of 1 / 2 / 3 / 4 / 6 individuals at once with 8 threads each 73* / 66 / 57 / 47 / 54 ms per
+         * individual, *16 threads; 4 x 4 threads 58, 3 x 16 threads 57) */
+        o->threads = overlap && out_slots > 1 && threads > 3 ? (opt_summary_only ? (threads + 3) / 4 : threads / 2) : threads;
+        if (overlap && out_threads_env > 0)
+            o->threads = out_threads_env;
+        o->running = overlap && pthread_create(&o->th, NULL, output_individual, o) == 0;
+        if (!o->running) {
+            output_individual(o);
+            if (o->failed)
+                goto fail;
+        }
+        phase("per individual: output files");
+    }
+    for (int k = 0; k < OUT_SLOTS; ++k) {
+        if (outs[k].running) {
+            pthread_join(outs[k].th, NULL);
+            outs[k].running = 0;
+            if (outs[k].failed)
+                goto fail;
+        }
+    }
+    if (overlap)
+        phase("output files of the last individuals (written beside the engine's work on the ones after them)");
+    if (arm_on) {
+        /* one file for the run, written here once: the lines in comparison order, as bin/chrarm-stats.py prints them */
+        char *arm_fn;
+        const char *chrom = g_uchr ? g_uchr : pu->n_lines ? pu->chr_names[pu->lines[0].chr] : ".";
+        if (asprintf(&arm_fn, "%s/%s.armstats.txt", out_dir, sq) < 0)
+            goto fail;
+        FILE *af = fopen(arm_fn, "w");
+        if (!af)
+            PFAIL("[::] ERROR: Cannot open '%s' for writing.\n", arm_fn);
+        pj_add_file(pj, arm_fn);
+        fprintf(af, "SAMPLE\tCHROM\tparm_IBD2/IBD0\tqarm_IBD2/IBD0\tparm_IBD1/IBD0\tqarm_IBD1/IBD0\n");
+        for (size_t ti = 0; ti < targets.n; ++ti) {
+            fprintf(af, "%s\t%s", g_ids.names[targets.idx[ti]], chrom);
+            for (int k = 0; k < 4; ++k) {
+                const double v = arm_res[4 * ti + k];
+                if (isnan(v))
+                    fprintf(af, "\tnan");
+                else
+                    fprintf(af, "\t%.3e", v);
+            }
+            fputc('\n', af);
+        }
+        if (fclose(af) != 0)
+            PFAIL("[::] ERROR writing '%s'.\n", arm_fn);
+        free(arm_fn);
+        phase("arm statistics file");
+    }
+    if (g_list_mode) {
+        /* the next pileup's arrays take their place (a single -P run leaves them to the end of the process) */
+        for (int k = 0; k < OUT_SLOTS; ++k)
+            free(site_slot[k]);
+        free(s_row); free(s_cand); free(s_nr); free(s_na); free(s_fo); free(s_row_dev);
+        free(row_pre); free(row_pre_off); free(arm_res); free(arm_wfirst); free(arm_wlast);
+        free(sum_pos_first); free(sum_pos_last);
+    } else {
+        free(row_pre);
+        free(row_pre_off);
+    }
+    return 0;
+fail:
+    outs_settle_one(outs, 1);
+    return 1;
+}
+
+/* a worker's loop over the list: entry i runs while entry i + 1 is read and filtered beside it */
+static void *worker_main(void *arg)
+{
+    worker_t *w = arg;
+    long cur = w->first;
+    if (cur >= 0 && !w->first_ready) {
+        pj_prepare(&g_list.jobs[cur]);
+        phase_begin(NULL);
+    }
+    while (cur >= 0) {
+        pile_job *pj = &g_list.jobs[cur];
+        long nxt = -1;
+        pthread_t pt;
+        int prefetch = 0;
+        if (!pj->rc && (nxt = list_take()) >= 0)
+            prefetch = pthread_create(&pt, NULL, pj_prepare, &g_list.jobs[nxt]) == 0;
+        int rc = pj->rc;
+        if (!rc)
+            rc = list_failed_before((size_t)cur) ? -1 : pj_run(pj, w);
+        if (g_list_mode)
+            pj_release(pj);
+        list_finish((size_t)cur, rc);
+        if (nxt >= 0) {
+            if (prefetch)
+                pthread_join(pt, NULL);
+            else
+                pj_prepare(&g_list.jobs[nxt]);
+            phase_begin(NULL);
+        }
+        cur = nxt;
+    }
+    return NULL;
+}
+
 int main(int argc, char **argv)
 {
     const clock_t t_start = clock();
@@ -2262,7 +3031,8 @@ int main(int argc, char **argv)
     fmt_init();
     const char *hap_fn = NULL, *legend_fn = NULL, *indv_fn = NULL, *pu_fn = NULL, *vcf_fn = NULL;
     const char *sample_fn = NULL, *sample_csv = NULL, *bg_fn = NULL, *af_fn = NULL, *pos_fn = NULL;
-    const char *uchr = NULL, *out_dir = NULL, *devices_arg = "0";
+    const char *uchr = NULL, *out_dir = NULL, *devices_arg = "0", *list_fn = NULL;
+    int has_N = 0;
     char cwd[PATH_MAX];
     if (argc == 1)
         usage(0);
@@ -2278,7 +3048,7 @@ int main(int argc, char **argv)
         case 'I': in_impute = 1; indv_fn = optarg; break;
         case 'P': pu_fn = optarg; break;
         case 'w': opt_window = atoi(optarg); break;
-        case 'N': opt_sq = optarg; break;
+        case 'N': opt_sq = optarg; has_N = 1; break;
         case 'S': has_S = 1; sample_fn = optarg; break;
         case 's': has_s = 1; sample_csv = optarg; break;
         case 'B': has_B = 1; bg_fn = optarg; break;
@@ -2298,6 +3068,7 @@ int main(int argc, char **argv)
         case 1002: opt_threads = atoi(optarg); break;
         case 1003: cache_fn = optarg; break;
         case 1004: dump_panel_fn = optarg; break;   /* test hook: the packed rows + clean flags as a binary file */
+        case 1007: list_fn = optarg; break;         /* --pileup-list FILE: NAME PATH per pileup */
         case 1006:
             if (!parse_arm_range(optarg)) {
                 fprintf(stderr, "[::] ERROR: Invalid centromeric range (--arm-stats) '%s' (must be START,END with START <= END).\n", optarg);
@@ -2346,8 +3117,35 @@ int main(int argc, char **argv)
         strcat(user_cmd, " ");
     }
 
-    if (!pu_fn)
-        DIE("[::] ERROR parsing Pileup data; make sure input is valid.\n");
+    /* the pileups of the run: -P / -N, or the entries of --pileup-list (refused with a line of its own before anything is read) */
+    if (list_fn) {
+        if (pu_fn || has_N) {
+            fprintf(stderr, "[::] ERROR: --pileup-list names the pileups and their names; it does not go with -P or -N.\n");
+            exit(1);
+        }
+        read_pileup_list(list_fn, &g_list.jobs, &g_list.n);
+        g_list_mode = 1;
+        for (size_t i = 0; i < g_list.n; ++i) {
+            pile_job *pj = &g_list.jobs[i];
+            pj->err = open_memstream(&pj->err_buf, &pj->err_len);
+            if (!pj->err)
+                pj->err = stderr;
+        }
+    } else {
+        if (!pu_fn)
+            DIE("[::] ERROR parsing Pileup data; make sure input is valid.\n");
+        static pile_job one;
+        one.name = opt_sq;
+        one.path = pu_fn;
+        one.err = stderr;
+        g_list.jobs = &one;
+        g_list.n = 1;
+    }
+    g_list.fail_at = g_list.n;
+    g_uchr = uchr;
+    g_out_dir = out_dir;
+    g_user_cmd = user_cmd;
+    pile_job *const p0 = &g_list.jobs[0];
     /* start the device(s) now: ibdg_create takes ~0.2 s of runtime start-up that needs none of the inputs */
     static dev_job_t dev_job;
     if (!opt_plan) {
@@ -2362,9 +3160,11 @@ int main(int argc, char **argv)
             DIE("[::] ERROR: cannot start a worker thread.\n");
         g_dev_started = 1;
     }
-    pileup_t *pu = pileup_read_mt(pu_fn, uchr, opt_threads > 0 ? opt_threads : default_threads());
-    if (!pu)
-        DIE("[::] ERROR parsing Pileup data; make sure input is valid.\n");
+    pj_read(p0);
+    if (p0->rc) {
+        list_finish(0, 1);
+        quit(1);
+    }
     if (has_A && read_af_file(af_fn, uchr))
         quit(1);
     if (has_p) {
@@ -2379,7 +3179,7 @@ int main(int argc, char **argv)
     if (in_impute && (!hap_fn || !legend_fn || !indv_fn))
         DIE("[::] ERROR parsing hap/legend/indv data; make sure inputs are valid.\n");
 
-    names_t ids;
+    names_t ids = {NULL, 0};
     if (in_vcf) {
         if (read_genotypes_vcf(vcf_fn, &ids))
             quit(1);
@@ -2415,28 +3215,16 @@ int main(int argc, char **argv)
             bg_count[bg.idx[i]]++;
         }
     }
-    const long pu_id = find_name(&ids, opt_sq);            /* is the pileup's own name in the panel? (:501-506) */
+    g_ids = ids;
+    g_targets = targets;
+    g_bg_count = bg_count;
     phase("options, pileup, names");
 
     if (in_impute && read_genotypes(hap_fn, legend_fn, n_ids))
         quit(1);
     phase("genotypes (hap or cache, legend)");
 
-    /* input coverage distribution and cull ratio: find_cull_p (:83-106) */
-    unsigned long in_dist[128] = {0}, in_total = 0;
-    for (size_t i = 0; i < pu->n_lines; ++i)
-        if (pu->lines[i].cov <= opt_max_cov) {
-            in_total += pu->lines[i].cov;
-            in_dist[pu->lines[i].cov]++;
-        }
-    const double mean_cov = (double)in_total / pu->n_lines;
-    double cull_p = 1;
-    if (has_D) {
-        if (opt_target_dp > mean_cov)
-            fprintf(stderr, "Observed depth is lower than target depth -D. No culling will be done.\n");
-        else
-            cull_p = opt_target_dp / mean_cov;
-    }
+    pj_depth(p0);
 
     /* ---- engine: panel upload, alt counts back for the AF filter ---------------------- */
     ibdg_ctx *engs[64];
@@ -2454,16 +3242,21 @@ int main(int argc, char **argv)
             if (!pdg_tab || ibdg_pdg_table(opt_eps, opt_max_cov, pdg_tab))
                 DIE("[::] ERROR: cannot build the P(D|G) table.\n");
             host_math = 1;
+            g_pdg_tab = pdg_tab;
             dev_job.n = 0;
             fprintf(stderr, "No HIP device found: per-row and window likelihoods are computed on the host (non-LD runs only).\n");
         }
     }
     const int no_engine = opt_plan || host_math;
+    g_no_engine = no_engine;
+    g_host_math = host_math;
     upload_job *const ups = g_ups;
     /* the same rows for every comparison individual unless -v looks at its genotype or -D thins the
      * reads anew for each (src/ibdgem.c:584, :627-628) */
-    const int batchable = !no_engine && !has_v && cull_p == 1.0;
-    int slice_mode = 0;             /* several devices and one site list: every device holds its window range's rows only */
+    const int batchable = !no_engine && !has_v && p0->cull_p == 1.0;
+    /* several devices and one site list: every device holds its window range's rows only (a single pileup: with a list
+     * every context holds the whole panel and takes whole pileups) */
+    int slice_mode = 0;
     if (!no_engine) {
         for (int d = 0; d < dev_job.n; ++d) {
             ibdg_ctx *e = dev_job.eng[d];
@@ -2473,13 +3266,14 @@ int main(int argc, char **argv)
         }
         if (n_eng == 0)
             DIE("[::] ERROR: --devices needs at least one device index.\n");
-        slice_mode = batchable && n_eng > 1;
+        slice_mode = batchable && n_eng > 1 && !g_list_mode;
         for (int d = 0; d < n_eng; ++d) {
             memset(&ups[d], 0, sizeof ups[d]);
             ups[d].eng = engs[d]; ups[d].r0 = 0; ups[d].n = n_rows; ups[d].n_ids = n_ids;
             ups[d].ref_order = opt_ref_order; ups[d].has_B = has_B; ups[d].bg_idx = bg.idx; ups[d].bg_n = bg.n;
             ups[d].n_uploads = n_eng;
-            ups[d].share_sites = batchable && opt_ld && !opt_ref_order ? targets.n : 0;
+            /* (a list decides this per pileup, from each one's own cull ratio: pj_run) */
+            ups[d].share_sites = batchable && opt_ld && !opt_ref_order && !g_list_mode ? targets.n : 0;
         }
         if (!slice_mode) {
             /* whole panel to every device, all copies at once, under the filter chain below */
@@ -2490,420 +3284,60 @@ int main(int argc, char **argv)
     }
     if (!alt_count_h)
         DIE("[::] ERROR: no genotype rows.\n");
-    const uint32_t *alt_count = alt_count_h;
-
-    /* ---- target-independent part of the row filter chain (:589-626) -------------------
-     * Rows are independent here: a team of threads takes contiguous row ranges, each fills its own part
-     * of cand[] from the range's first row on, and the parts are closed up in order afterwards. */
-    cand_t *cand = malloc((n_rows ? n_rows : 1) * sizeof *cand);
-    uint8_t *row_fate = calloc(n_rows ? n_rows : 1, 1);   /* 0 skip-before-v, 1 candidate, 2 skipped after the -v test */
-    size_t n_cand = 0;
-    {
-        int T = opt_threads > 0 ? opt_threads : default_threads();
-        if (T > 64) T = 64;
-        if (n_rows * 64 < ls_mt_min_bytes()) T = 1;           /* small inputs (and the tests, unless they ask) on one thread */
-        filter_job fj[64];
-        pthread_t th[64];
-        for (int t = 0; t < T; ++t) {
-            filter_job *j = &fj[t];
-            j->a = n_rows * (size_t)t / (size_t)T;
-            j->b = n_rows * (size_t)(t + 1) / (size_t)T;
-            j->pu = pu; j->alt_count = alt_count; j->n_ids = n_ids; j->in_vcf = in_vcf; j->has_p = has_p; j->has_A = has_A;
-            j->cand = cand + j->a; j->row_fate = row_fate; j->n = 0;
-            if (T == 1 || pthread_create(&th[t], NULL, filter_rows, j) != 0) {
-                filter_rows(j);
-                th[t] = pthread_self();
-            }
-        }
-        for (int t = 0; t < T; ++t) {
-            if (!pthread_equal(th[t], pthread_self()))
-                pthread_join(th[t], NULL);
-            if (fj[t].cand != cand + n_cand)
-                memmove(cand + n_cand, fj[t].cand, fj[t].n * sizeof *cand);
-            n_cand += fj[t].n;
-        }
-    }
+    pj_filter(p0);
     phase("row filter chain");
 
-    /* ---- per comparison individual (:522-773) ------------------------------------------ */
-    /* the arrays that cross the engine's boundary live in page-locked memory when a device is in use
-     * (ibdg_host_alloc: copies at link speed, 45+ GB/s instead of ~17 through a staging buffer) */
-    /* Round 2 page-locked these arrays (ibdg_host_alloc).  Measured since: locking 128 MB costs 0.1 s, giving it
-     * back at exit 0.2 s, and the copies it was meant to speed up (24 MB in, 96 MB out per comparison) run at the same
-     * 56 GB/s from ordinary memory (bench.py results_to_host) -- so they are ordinary memory now. */
-    const int pin = 0;
-    uint32_t *s_row = io_alloc((n_cand ? n_cand : 1) * 4, pin), *s_cand = malloc((n_cand ? n_cand : 1) * 4);
-    uint8_t *s_nr = io_alloc(n_cand ? n_cand : 1, pin), *s_na = io_alloc(n_cand ? n_cand : 1, pin);
-    double *s_fo = has_A ? malloc((n_cand ? n_cand : 1) * 8) : NULL;
-    /* the per-site values are only fetched for the per-site table: no 128 MB of page-locked memory for --summary-only */
-    const size_t n_site_out = opt_summary_only && !no_engine ? 1 : (n_cand ? n_cand : 1);
-    double *site_ll = io_alloc(n_site_out * 24, pin);
-    if (!s_row || !s_cand || !s_nr || !s_na || !site_ll)
-        DIE("[::] ERROR: out of memory for %zu rows.\n", n_cand);
-    phase("result arrays");
-    uint32_t *s_row_dev = NULL;     /* slice_mode: the site list's rows counted from each device's first row */
-    /* The files of up to out_slots individuals are written beside the main thread's work on the ones after them, each from
-     * a per-row array of its own -- when the site list is the same for all of them (it is read by the writers), the rows go
-     * to files (stdout keeps its order) and there is a table to write at all. */
-    out_job *const outs = g_outs;
-    /* (--summary-only: the summary files alone, 2.5 MB each at 35 000 windows -- 1.5 ms per individual when written one
-     * after the other, most of a whole-panel job whose engine time is 0.2 ms per individual) */
-    const int overlap = !has_v && cull_p == 1.0 && !opt_plan && targets.n > 1;
-    double *site_slot[OUT_SLOTS] = {site_ll};
-    /* (--summary-only: 2.5 MB per individual instead of 330: twelve individuals at a time with four formatter threads each --
-     * 0.52 ms per individual in a run of 960 against 0.65 with six and eight, 0.90 with four, tools/many_summaries.py) */
-    int out_slots = opt_summary_only ? 12 : 4;
-    char *row_pre = NULL;                       /* columns 1-9 of every row as text, shared by all individuals' tables */
-    uint32_t *row_pre_off = NULL;                  /* (IBDGEM_OUT_SLOTS=1..12, default 4, 12 with --summary-only: for the tests and for measurements) */
-    if (getenv("IBDGEM_OUT_SLOTS") && atoi(getenv("IBDGEM_OUT_SLOTS")) >= 1 && atoi(getenv("IBDGEM_OUT_SLOTS")) <= OUT_SLOTS)
-        out_slots = atoi(getenv("IBDGEM_OUT_SLOTS"));
-    const int out_threads_env = getenv("IBDGEM_OUT_THREADS") ? atoi(getenv("IBDGEM_OUT_THREADS")) : 0;   /* (measurement switch) */
-    const int arm_on = has_arm && !opt_plan;
-    double *arm_res = arm_on ? malloc((targets.n + 1) * 4 * sizeof(double)) : NULL;   /* per individual: p20, q20, p10, q10 */
-    if (arm_on && !arm_res)
-        DIE("[::] ERROR: out of memory.\n");
-    uint32_t *arm_wfirst = NULL, *arm_wlast = NULL;   /* engine path: the windows the arms were cut from (checked against the engine's) */
-    size_t arm_nw = 0;
-    for (size_t ti = 0; ti < targets.n; ++ti) {
-        const uint32_t tgt = targets.idx[ti];
-        if (overlap) {
-            out_job *prev = &outs[ti % (size_t)out_slots]; /* the slot's previous individual: its files must be closed */
-            if (prev->running) {
-                pthread_join(prev->th, NULL);
-                prev->running = 0;
-                if (prev->failed)
-                    quit(1);
-                phase("per individual: waiting for the output files of an earlier individual");
-            }
-            if (!site_slot[ti % (size_t)out_slots]) {
-                site_slot[ti % (size_t)out_slots] = io_alloc(n_site_out * 24, pin);
-                if (!site_slot[ti % (size_t)out_slots])
-                    DIE("[::] ERROR: out of memory for %zu rows.\n", n_cand);
-            }
-            site_ll = site_slot[ti % (size_t)out_slots];
-        }
-        const char *tname = ids.names[tgt];
-        fprintf(stderr, "Running %s-vs-%s comparison...\n", opt_sq, tname);
-        /* Without -v and -D the site list does not depend on the comparison individual (:584, :627-628): it is
-         * built for the first one and kept -- 9 ms per individual at 4M rows, more than its engine time.  The
-         * reference's message for rows whose genotypes did not parse is repeated per individual as it prints it. */
-        static unsigned long skipped, final_total, final_dist[128];
-        static size_t n;
-        const int same_sites = !has_v && cull_p == 1.0 && ti > 0;
-        static size_t n_gt_failed;
-        if (same_sites) {
-            for (size_t r = 0; r < n_rows && n_gt_failed; ++r)
-                if (row_fate[r] == 0 && rows[r].gt_failed)
-                    fprintf(stderr, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[r].pos);
-        } else {
-            n_gt_failed = 0;
-            skipped = final_total = 0;
-            memset(final_dist, 0, sizeof final_dist);
-            n = 0;
-        }
-        for (size_t r = 0, ci = 0; r < n_rows && !same_sites; ++r) {
-            if (row_fate[r] == 0) {
-                if (rows[r].gt_failed) {
-                    fprintf(stderr, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[r].pos);
-                    n_gt_failed++;
-                }
-                skipped++;
-                continue;
-            }
-            const int is_cand = row_fate[r] == 1;
-            const size_t my = ci;
-            if (is_cand) ci++;
-            if (has_v && row_allele(r, tgt, 0) == 0 && row_allele(r, tgt, 1) == 0) { skipped++; continue; }   /* :584 */
-            if (!is_cand) { skipped++; continue; }
-            const cand_t *c = &cand[my];
-            const unsigned nr = cull(c->n_ref, cull_p), na = cull(c->n_alt, cull_p);                          /* :627-628 */
-            final_total += nr + na;
-            final_dist[nr + na]++;
-            s_row[n] = c->row; s_cand[n] = (uint32_t)my; s_nr[n] = (uint8_t)nr; s_na[n] = (uint8_t)na;
-            if (s_fo) s_fo[n] = c->f_is_override ? c->f : NAN;
-            n++;
-        }
-        const unsigned long processed = n;
-        phase("per individual: site list");
-        if (ti == 0 && overlap && !opt_summary_only && targets.n >= 3 && n > 0) {
-            /* nine of a row's fourteen columns are the same for every comparison individual: their text is made once */
-            fmt_job pp;
-            memset(&pp, 0, sizeof pp);
-            pp.cand = cand; pp.s_cand = s_cand; pp.pu = pu; pp.s_nr = s_nr; pp.s_na = s_na;
-            if (row_prefix_build(pp, n, opt_threads > 0 ? opt_threads : default_threads(), &row_pre, &row_pre_off)) {
-                row_pre = NULL;
-                row_pre_off = NULL;
-            }
-            phase("columns 1-9 of every row as text, once for all individuals");
-        }
-
-        /* windows: runs of opt_window covered rows (:572, :657-663, :723-730) */
-        size_t n_win = 0;
-        uint32_t *w_first = NULL, *w_last = NULL, *w_ncov = NULL;
-        double *win_ll = NULL;
-        if (no_engine) {
-            n_win = host_windows(s_nr, s_na, n, (unsigned)opt_window, &w_first, &w_last, &w_ncov);
-            if (host_math) {
-                win_ll = malloc((n_win + 1) * 24);
-                host_nonld(cand, s_cand, s_nr, s_na, n, tgt, pdg_tab, opt_threads > 0 ? opt_threads : default_threads(),
-                           site_ll, w_first, w_last, n_win, win_ll);
-            }
-            if (arm_on) {
-                uint32_t seg[4];
-                int ok[2];
-                double p[4], q[4];
-                arm_segments(s_row, w_first, w_last, n_win, seg, ok);
-                llr_range_host(win_ll, seg[0], seg[1], p);
-                llr_range_host(win_ll, seg[2], seg[3], q);
-                arm_res[4 * ti] = ok[0] ? p[0] : NAN;
-                arm_res[4 * ti + 1] = ok[1] ? q[0] : NAN;
-                arm_res[4 * ti + 2] = ok[0] ? p[2] : NAN;
-                arm_res[4 * ti + 3] = ok[1] ? q[2] : NAN;
-            }
-        } else {
-            /* one contiguous window range per GPU, evaluated concurrently, gathered in order */
-            static size_t cuts[65];                    /* kept with the site list */
-            shard_job jobs[64];
-            pthread_t th[64];
-            /* --arm-stats: the arms of the site list in its global windows, cut into each device's window range */
-            static uint32_t arm_local[64][4], arm_wcut[65];
-            static int arm_ok[2];
-            if (!same_sites)
-                window_cuts(s_nr, s_na, n, (unsigned)opt_window, n_eng, cuts);
-            if (arm_on && !same_sites) {
-                uint32_t *an, seg[4];
-                free(arm_wfirst); free(arm_wlast);
-                const size_t nw = arm_nw = host_windows(s_nr, s_na, n, (unsigned)opt_window, &arm_wfirst, &arm_wlast, &an);
-                arm_segments(s_row, arm_wfirst, arm_wlast, nw, seg, arm_ok);
-                free(an);
-                for (int d = 0; d <= n_eng; ++d)
-                    arm_wcut[d] = (uint32_t)(nw * (size_t)d / (size_t)n_eng);     /* window_cuts' windows per device */
-                for (int d = 0; d < n_eng; ++d)
-                    for (int k = 0; k < 4; ++k) {
-                        const uint32_t v = seg[k] < arm_wcut[d] ? arm_wcut[d] : seg[k] > arm_wcut[d + 1] ? arm_wcut[d + 1] : seg[k];
-                        arm_local[d][k] = v - arm_wcut[d];
-                    }
-            }
-            if (slice_mode && ti == 0) {
-                /* every device gets the panel rows from its first site's row to its last site's row, and its
-                 * sites are numbered within that slice */
-                s_row_dev = io_alloc((n ? n : 1) * 4, pin);
-                if (!s_row_dev)
-                    DIE("[::] ERROR: out of memory for %zu rows.\n", n);
-                for (int d = 0; d < n_eng; ++d) {
-                    const size_t a = cuts[d], b = cuts[d + 1];
-                    ups[d].r0 = a < b ? s_row[a] : 0;
-                    ups[d].n = a < b ? (size_t)s_row[b - 1] + 1 - ups[d].r0 : 0;
-                    for (size_t i = a; i < b; ++i)
-                        s_row_dev[i] = s_row[i] - (uint32_t)ups[d].r0;
-                    if (timing_on > 0)
-                        fprintf(stderr, "## panel slice of device %d: rows %zu + %zu of %zu\n", d, ups[d].r0, ups[d].n, n_rows);
-                }
-                g_n_ups = n_eng;
-                uploads_start(ups, n_eng);
-                g_uploads_pending = 1;
-            }
-            if (g_uploads_pending) {
-                const int bad = uploads_join(ups, n_eng);
-                g_uploads_pending = 0;
-                if (bad >= 0)
-                    DIE("%s\n", ibdg_last_error(engs[bad]));
-                phase("panel upload (copy, alt counts, transposition; the part not hidden behind the filter chain)");
-            }
-            int th_started[64] = {0};
-            for (int d = 0; d < n_eng; ++d) {
-                shard_job *j = &jobs[d];
-                memset(j, 0, sizeof *j);
-                j->eng = engs[d]; j->row = slice_mode ? s_row_dev : s_row; j->nr = s_nr; j->na = s_na; j->fo = s_fo;
-                j->a = cuts[d]; j->b = cuts[d + 1]; j->window = (unsigned)opt_window;
-                j->want_sites = !opt_summary_only;
-                if (batchable) {
-                    const size_t b0 = ti - ti % TARGET_BATCH;
-                    j->targets = targets.idx + b0;
-                    j->n_targets = targets.n - b0 < TARGET_BATCH ? targets.n - b0 : TARGET_BATCH;
-                    j->t_local = ti - b0;
-                    j->do_upload = ti == 0;
-                    j->do_run = ti == b0;
-                    if (b0 + TARGET_BATCH < targets.n && opt_summary_only) {
-                        j->next_targets = targets.idx + b0 + TARGET_BATCH;
-                        j->n_next = targets.n - (b0 + TARGET_BATCH) < TARGET_BATCH ? targets.n - (b0 + TARGET_BATCH) : TARGET_BATCH;
-                    }
-                } else {
-                    j->targets = &targets.idx[ti];
-                    j->n_targets = 1;
-                    j->t_local = 0;
-                    j->do_upload = j->do_run = 1;
-                }
-                j->bg_count = bg_count; j->pu_id = (int)pu_id; j->ld = opt_ld;
-                j->dev_idx = d; j->same_sites = batchable;
-                j->site_ll = site_ll;
-                j->arm_seg = arm_on ? arm_local[d] : NULL;
-                j->stats_only = opt_stats_only;
-                /* (no thread to be had: the shard runs here -- never exit() while other shard threads are
-                 * inside the GPU runtime) */
-                th_started[d] = n_eng > 1 && pthread_create(&th[d], NULL, shard_run, j) == 0;
-                if (!th_started[d])
-                    shard_run(j);
-            }
-            n_win = 0;
-            int shard_failed = -1;
-            for (int d = 0; d < n_eng; ++d) {
-                if (th_started[d])
-                    pthread_join(th[d], NULL);
-                if (jobs[d].failed && shard_failed < 0)
-                    shard_failed = d;
-                n_win += jobs[d].n_win;
-            }
-            if (shard_failed >= 0)
-                DIE("%s\n", ibdg_last_error(jobs[shard_failed].eng));
-            if (arm_on) {
-                /* each device's parts of the two arms, added in device order, then rounded */
-                double acc[8] = {0};
-                for (int d = 0; d < n_eng; ++d) {
-                    if (jobs[d].n_win != arm_wcut[d + 1] - arm_wcut[d])
-                        DIE("[::] ERROR: device %d holds %zu windows, not the %u of its range.\n", d, jobs[d].n_win,
-                            arm_wcut[d + 1] - arm_wcut[d]);
-                    for (int k = 0; k < 4; ++k)
-                        dd_add(acc + 2 * k, jobs[d].arm[2 * k], jobs[d].arm[2 * k + 1]);
-                }
-                arm_res[4 * ti] = arm_ok[0] ? acc[0] + acc[1] : NAN;
-                arm_res[4 * ti + 1] = arm_ok[1] ? acc[4] + acc[5] : NAN;
-                arm_res[4 * ti + 2] = arm_ok[0] ? acc[2] + acc[3] : NAN;
-                arm_res[4 * ti + 3] = arm_ok[1] ? acc[6] + acc[7] : NAN;
-            }
-            if (opt_stats_only) {
-                /* no window table left the device */
-            } else if (n_eng == 1 && jobs[0].a == 0) {
-                /* one device, the whole site list: its arrays as they are (a copy of 1.2 MB per individual otherwise) */
-                w_first = jobs[0].w_first; w_last = jobs[0].w_last; w_ncov = jobs[0].w_ncov; win_ll = jobs[0].win_ll;
-            } else {
-                w_first = malloc((n_win + 1) * 4); w_last = malloc((n_win + 1) * 4); w_ncov = malloc((n_win + 1) * 4);
-                win_ll = malloc((n_win + 1) * 24);
-                size_t wo = 0;
-                for (int d = 0; d < n_eng; ++d) {
-                    shard_job *j = &jobs[d];
-                    const uint32_t a0 = (uint32_t)j->a;
-                    for (size_t w = 0; w < j->n_win; ++w) {
-                        w_first[wo + w] = j->w_first[w] + a0;
-                        w_last[wo + w] = j->w_last[w] + a0;
-                    }
-                    memcpy(w_ncov + wo, j->w_ncov, j->n_win * 4);
-                    memcpy(win_ll + 3 * wo, j->win_ll, j->n_win * 24);
-                    wo += j->n_win;
-                    free(j->w_first); free(j->w_last); free(j->w_ncov); free(j->win_ll);
-                }
-            }
-        }
-
-        if (arm_on && !no_engine && !opt_stats_only &&
-            (n_win != arm_nw || memcmp(w_first, arm_wfirst, n_win * 4) || memcmp(w_last, arm_wlast, n_win * 4)))
-            DIE("[::] ERROR: the engine's windows are not the ones the chromosome arms were cut from.\n");
-        /* the positions a summary row names (:751-756) are the same for every individual over a common site list: looked up
-         * once -- row by row they are two dependent loads into 160 MB of row records per window and individual */
-        static unsigned long *sum_pos_first, *sum_pos_last;
-        static size_t sum_pos_n;
-        if (opt_stats_only) {
-            free(w_first); free(w_last); free(w_ncov); free(win_ll);
-            phase("per individual: engine (upload, run, arm sums)");
-            continue;
-        }
-        if (overlap && !no_engine && (ti == 0 || sum_pos_n != n_win)) {
-            free(sum_pos_first); free(sum_pos_last);
-            sum_pos_first = malloc((n_win + 1) * sizeof *sum_pos_first);
-            sum_pos_last = malloc((n_win + 1) * sizeof *sum_pos_last);
-            sum_pos_n = n_win;
-            for (size_t w = 0; w < n_win && sum_pos_first && sum_pos_last; ++w) {
-                sum_pos_first[w] = rows[s_row[w_first[w]]].pos;
-                sum_pos_last[w] = rows[s_row[w_last[w]]].pos;
-            }
-        }
-        phase("per individual: engine (upload, run, results)");
-        out_job *o = &outs[overlap ? ti % (size_t)out_slots : 0];
-        o->pos_first = overlap && !no_engine && sum_pos_first && sum_pos_last ? sum_pos_first : NULL;
-        o->pos_last = o->pos_first ? sum_pos_last : NULL;
-        o->out_dir = out_dir; o->user_cmd = user_cmd; o->in_dist = in_dist; o->mean_cov = mean_cov; o->cull_p = cull_p;
-        o->cand = cand; o->s_cand = s_cand; o->s_row = s_row; o->s_nr = s_nr; o->s_na = s_na; o->pu = pu;
-        o->tname = tname; o->tgt = tgt; o->n = n; o->n_win = n_win;
-        o->processed = processed; o->skipped = skipped; o->final_total = final_total;
-        memcpy(o->final_dist, final_dist, sizeof o->final_dist);
-        o->site_ll = site_ll;
-        o->pre = row_pre; o->pre_off = row_pre_off;
-        o->w_first = w_first; o->w_last = w_last; o->w_ncov = w_ncov; o->win_ll = win_ll;
-        if (opt_plan) {
-            o->tab = o->sum = stdout;
-        } else {
-            char *tab_fn, *sum_fn;
-            if (asprintf(&tab_fn, "%s/%s.%s.tab.txt", out_dir, opt_sq, tname) < 0 ||
-                asprintf(&sum_fn, "%s/%s.%s.summary.txt", out_dir, opt_sq, tname) < 0)
-                quit(1);
-            /* opened here, emptied by whoever writes them: giving back the pages of an earlier run's 330 MB table takes
-             * tens of milliseconds, which belong to the individual's output job, not between two engine calls */
-            const int tab_fd = open(opt_summary_only ? "/dev/null" : tab_fn, O_WRONLY | O_CREAT, 0666);
-            const int sum_fd = open(sum_fn, O_WRONLY | O_CREAT, 0666);
-            o->tab = tab_fd >= 0 ? fdopen(tab_fd, "w") : NULL;
-            o->sum = sum_fd >= 0 ? fdopen(sum_fd, "w") : NULL;
-            o->pending = 1;
-            if (!o->tab || !o->sum) {
-                fprintf(stderr, "[::] ERROR in compare_impute(): Cannot open '%s' and/or '%s' for writing.\n", tab_fn, sum_fn);
-                quit(1);
-            }
-            free(tab_fn);
-            free(sum_fn);
-        }
-        const int all_threads = opt_threads > 0 ? opt_threads : default_threads();
-        /* (tools/many_tables.py: files of 1 / 2 / 3 / 4 / 6 individuals at once with 8 threads each 73* / 66 / 57 / 47 / 54 ms per
-         * individual, *16 threads; 4 x 4 threads 58, 3 x 16 threads 57) */
-        o->threads = overlap && out_slots > 1 && all_threads > 3 ? (opt_summary_only ? (all_threads + 3) / 4 : all_threads / 2) : all_threads;
-        if (overlap && out_threads_env > 0)
-            o->threads = out_threads_env;
-        o->running = overlap && pthread_create(&o->th, NULL, output_individual, o) == 0;
-        if (!o->running) {
-            output_individual(o);
-            if (o->failed)
-                quit(1);
-        }
-        phase("per individual: output files");
+    /* the workers: one per context with a list, else one for all of them; the main thread is the first */
+    static worker_t workers[MAX_WORKERS];
+    const int n_workers = g_list_mode && !no_engine ? (n_eng < MAX_WORKERS ? n_eng : MAX_WORKERS) : 1;
+    for (int k = 0; k < n_workers; ++k) {
+        worker_t *w = &workers[k];
+        const int one = n_workers > 1 || g_list_mode;        /* a context of its own */
+        w->n_eng = no_engine ? 0 : one ? 1 : n_eng;
+        for (int d = 0; d < w->n_eng; ++d)
+            w->engs[d] = engs[k + d];
+        w->dev_base = k;
+        w->ups = ups + k;
+        w->n_ups = w->n_eng;
+        w->ups_pending = !no_engine && !slice_mode;
+        w->slice_mode = slice_mode;
+        w->outs = g_outs[k];
+        /* every context's first entry is its own before any worker reads ahead: a read-ahead never takes an entry while
+         * a context has none (with no more entries than contexts each entry has a context to itself) */
+        w->first = (size_t)k < g_list.n ? k : -1;
+        w->first_ready = k == 0;
     }
-    for (int k = 0; k < OUT_SLOTS; ++k) {
-        if (outs[k].running) {
-            pthread_join(outs[k].th, NULL);
-            outs[k].running = 0;
-            if (outs[k].failed)
-                quit(1);
-        }
+    g_list.next_take = (size_t)n_workers < g_list.n ? (size_t)n_workers : g_list.n;
+    g_n_workers = n_workers;
+    if (n_workers > 1) {
+        /* the contexts share the host's threads: each worker reads, filters and writes with its part of them */
+        const int total = opt_threads > 0 ? opt_threads : default_threads();
+        g_thread_share = total / n_workers > 1 ? total / n_workers : 1;
     }
-    if (overlap)
-        phase("output files of the last individuals (written beside the engine's work on the ones after them)");
-    if (arm_on) {
-        /* one file for the run, written here once: the lines in comparison order, as bin/chrarm-stats.py prints them */
-        char *arm_fn;
-        const char *chrom = uchr ? uchr : pu->n_lines ? pu->chr_names[pu->lines[0].chr] : ".";
-        if (asprintf(&arm_fn, "%s/%s.armstats.txt", out_dir, opt_sq) < 0)
-            quit(1);
-        FILE *af = fopen(arm_fn, "w");
-        if (!af) {
-            fprintf(stderr, "[::] ERROR: Cannot open '%s' for writing.\n", arm_fn);
-            quit(1);
-        }
-        fprintf(af, "SAMPLE\tCHROM\tparm_IBD2/IBD0\tqarm_IBD2/IBD0\tparm_IBD1/IBD0\tqarm_IBD1/IBD0\n");
-        for (size_t ti = 0; ti < targets.n; ++ti) {
-            fprintf(af, "%s\t%s", ids.names[targets.idx[ti]], chrom);
-            for (int k = 0; k < 4; ++k) {
-                const double v = arm_res[4 * ti + k];
-                if (isnan(v))
-                    fprintf(af, "\tnan");
-                else
-                    fprintf(af, "\t%.3e", v);
-            }
-            fputc('\n', af);
-        }
-        if (fclose(af) != 0) {
-            fprintf(stderr, "[::] ERROR writing '%s'.\n", arm_fn);
-            quit(1);
-        }
-        free(arm_fn);
-        phase("arm statistics file");
+    for (int k = 1; k < n_workers; ++k)
+        workers[k].started = pthread_create(&workers[k].th, NULL, worker_main, &workers[k]) == 0;
+    worker_main(&workers[0]);
+    for (int k = 1; k < n_workers; ++k)
+        if (workers[k].started)
+            pthread_join(workers[k].th, NULL);
+        else
+            worker_main(&workers[k]);       /* (no thread to be had: whatever is left, here) */
+    /* every context's panel upload is joined before anything below can tear the runtime down -- a context that took no
+     * entry never joined its own -- and a failed one is reported even when its context had nothing to do */
+    int up_bad = -1;
+    if (g_uploads_pending) {
+        up_bad = uploads_join(g_ups, g_n_ups);
+        g_uploads_pending = 0;
     }
+    if (g_list.fail_at < g_list.n) {
+        /* entries after the failing one that ran on another context leave no files behind */
+        for (size_t i = g_list.fail_at + 1; i < g_list.n; ++i)
+            for (size_t f = 0; f < g_list.jobs[i].n_files; ++f)
+                unlink(g_list.jobs[i].files[f]);
+        quit(1);
+    }
+    if (up_bad >= 0)
+        DIE("%s\n", ibdg_last_error(g_ups[up_bad].eng));
 #if !defined(__SANITIZE_ADDRESS__) && !defined(__SANITIZE_THREAD__)
     if (getenv("IBDGEM_EXIT_PROBE")) {       /* measurement only (tools/warm_phases.py): what of the process's end is the mapping */
         if (packed_mapped_bytes)
@@ -2922,9 +3356,8 @@ int main(int argc, char **argv)
     for (int d = 0; d < n_eng; ++d)
         ibdg_destroy(engs[d]);
     phase("engine shutdown");
-    free(row_pre);
-    free(row_pre_off);
-    pileup_free(pu);
+    if (!g_list_mode)
+        pileup_free(p0->pu);
     fprintf(stderr, "Run time: %f minutes.\n", ((double)(clock() - t_start) / CLOCKS_PER_SEC) / 60);
     return EXIT_SUCCESS;
 }

@@ -1,5 +1,6 @@
 #include "lineio.h"
 
+#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,6 +25,11 @@ static int name_is_gz(const char *fn)
 
 line_src *ls_open(const char *fn)
 {
+    return ls_open_to(fn, stderr);
+}
+
+line_src *ls_open_to(const char *fn, FILE *err)
+{
     if (!fn)
         return NULL;
     line_src *ls = calloc(1, sizeof *ls);
@@ -36,8 +42,10 @@ line_src *ls_open(const char *fn)
     } else {
         ls->f = fopen(fn, "r");
         if (!ls->f) {
-            fprintf(stderr, "Failed to open %s.\n", fn);
-            perror("Error");
+            const int e = errno;
+            fprintf(err, "Failed to open %s.\n", fn);
+            errno = e;
+            fprintf(err, "Error: %m\n");            /* perror("Error")'s text */
         }
     }
     if (!ls->f && !ls->gz) {

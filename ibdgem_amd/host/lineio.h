@@ -9,7 +9,9 @@
 
 typedef struct line_src line_src;
 
+#include <stdio.h>
 line_src *ls_open(const char *fn);          /* NULL (and a message on stderr) on failure */
+line_src *ls_open_to(const char *fn, FILE *err);   /* the same with the message written to `err` */
 /* next line including its '\n' (if any), NUL-terminated; NULL at EOF.  The
  * pointer is valid until the next call. */
 char *ls_next(line_src *ls, size_t *len);

@@ -176,16 +176,16 @@ static void part_add_line(pu_part *t, const char *line, const char *chr, FILE *e
     t->n++;
 }
 
-static pileup_t *pileup_finish(pileup_t *pu, const char *fn)
+static pileup_t *pileup_finish(pileup_t *pu, const char *fn, FILE *err)
 {
     if (pu->n_lines == 0) {
-        fprintf(stderr, "[::] ERROR in init_Pu_chr(): Cannot parse mpileup lines from %s.\n", fn);
+        fprintf(err, "[::] ERROR in init_Pu_chr(): Cannot parse mpileup lines from %s.\n", fn);
         pileup_free(pu);
         return NULL;
     }
     for (size_t i = 0; i + 1 < pu->n_lines; ++i)
         if (pu->lines[i].pos > pu->lines[i + 1].pos) {
-            fprintf(stderr, "mpileup lines not sorted!\n");
+            fprintf(err, "mpileup lines not sorted!\n");
             pileup_free(pu);
             return NULL;
         }
@@ -194,21 +194,26 @@ static pileup_t *pileup_finish(pileup_t *pu, const char *fn)
 
 pileup_t *pileup_read(const char *fn, const char *chr)
 {
-    line_src *ls = ls_open(fn);
+    return pileup_read_to(fn, chr, stderr);
+}
+
+pileup_t *pileup_read_to(const char *fn, const char *chr, FILE *err)
+{
+    line_src *ls = ls_open_to(fn, err);
     if (!ls)
         return NULL;
     pu_part t;
     memset(&t, 0, sizeof t);
     char *line;
     while ((line = ls_next(ls, NULL)))
-        part_add_line(&t, line, chr, stderr);
+        part_add_line(&t, line, chr, err);
     ls_close(ls);
     pileup_t *pu = calloc(1, sizeof *pu);
     pu->lines = t.lines;
     pu->n_lines = t.n;
     pu->chr_names = t.chr_names;
     pu->n_chr = t.n_chr;
-    return pileup_finish(pu, fn);
+    return pileup_finish(pu, fn, err);
 }
 
 typedef struct {
@@ -246,11 +251,16 @@ static void *pu_worker(void *arg)
 
 pileup_t *pileup_read_mt(const char *fn, const char *chr, int threads)
 {
+    return pileup_read_mt_to(fn, chr, threads, stderr);
+}
+
+pileup_t *pileup_read_mt_to(const char *fn, const char *chr, int threads, FILE *err)
+{
     size_t size = 0;
     const char *base = threads > 1 ? ls_map(fn, &size) : NULL;
     if (!base || size < ls_mt_min_bytes()) {                            /* gzip, small or unmappable: line by line */
         ls_unmap(base, size);
-        return pileup_read(fn, chr);
+        return pileup_read_to(fn, chr, err);
     }
     if (threads > 64)
         threads = 64;
@@ -280,7 +290,7 @@ pileup_t *pileup_read_mt(const char *fn, const char *chr, int threads)
     for (int t = 0; t < threads; ++t) {
         pu_job *j = &jobs[t];
         if (j->msg_len)
-            fwrite(j->msg, 1, j->msg_len, stderr);
+            fwrite(j->msg, 1, j->msg_len, err);
         free(j->msg);
         /* chromosome names in order of first appearance over the whole file; lines renumbered to them */
         uint32_t map[256];
@@ -309,7 +319,7 @@ pileup_t *pileup_read_mt(const char *fn, const char *chr, int threads)
         free(j->part.lines);
     }
     ls_unmap(base, size);
-    return pileup_finish(pu, fn);
+    return pileup_finish(pu, fn, err);
 }
 
 const pu_line *pileup_find(const pileup_t *pu, unsigned long pos)

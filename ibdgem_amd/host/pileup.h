@@ -32,6 +32,10 @@ pileup_t *pileup_read(const char *fn, const char *chr);
 /* the same with the lines of a plain file parsed by `threads` threads (byte ranges cut at line starts,
  * tables and messages joined in file order: same table, same stderr text as pileup_read) */
 pileup_t *pileup_read_mt(const char *fn, const char *chr, int threads);
+/* the two with their messages written to `err` instead of stderr (the entries of a --pileup-list, printed in list order) */
+#include <stdio.h>
+pileup_t *pileup_read_to(const char *fn, const char *chr, FILE *err);
+pileup_t *pileup_read_mt_to(const char *fn, const char *chr, int threads, FILE *err);
 /* line with exactly this position, or NULL (binary search, like fetch_Pul) */
 const pu_line *pileup_find(const pileup_t *pu, unsigned long pos);
 /* count_base_from_pul: bytes equal to `base`; 0 for anything but A,C,G,T */
