@@ -25,7 +25,9 @@ copying its row list and read counts and preparing windows / segments on the dev
 (site arrays resident -> per-window results in host memory: preparation, alt-allele counts, all
 kernels, the copy back), "results_to_host" (per-site results), "warm_e2e" / "cold_e2e" (the host
 program ibdgem_amd/host/ibdgem from files to files), and "cpu_baseline" (the unmodified reference
-binary on a slice of the same data).
+binary on a slice of the same data).  Those clocks, the other steps (recount, all terms, the panel's own tiles,
+the kernel's own dispatch time) and the detail file come with `--full`; a plain run sets up, warms up, times its
+steps, writes --dump-outputs if asked and prints the line, the legs' keys in it null.
 
 The timed steps take two comparison individuals in turn (a NEW individual per step, as in the reference's loop over
 the individuals of the panel, src/ibdgem.c:522): nothing a step needs is left over from the step before it -- the
@@ -866,6 +868,11 @@ def main():
     ap.add_argument("--window", type=int, default=100)
     ap.add_argument("--target", type=int, default=7)
     ap.add_argument("--seed", type=int, default=20241008)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside `value`: the recount and all-terms steps, the "
+                         "kernel's own dispatch time, the panel's own tiles, the engine / upload / results clocks, many comparison "
+                         "individuals, thin pileups, the non-LD step, the reference on the CPU, the host program end to end; the "
+                         "detail file is written with it.  Default: set up, warm up, time the steps, print the line")
     ap.add_argument("--cpu-sample-rows", type=int, default=200_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-program clocks (warm_e2e, cold_e2e)")
@@ -964,7 +971,7 @@ def main():
         eng.set_option(k, int(v))
     eng.upload_panel_dev(panel.data_ptr(), panel.shape[0], args.ids)
     eng2 = None
-    want_second = world == 1 and not args.no_many and not args.timed_only
+    want_second = args.full and world == 1 and not args.no_many and not args.timed_only
 
     def second_context(panel_t):
         # a second context with the same panel, for engine_clock.two_contexts_alternating_ms.  Made when that leg begins, not
@@ -981,9 +988,9 @@ def main():
         e2.upload_panel_dev(panel_t.data_ptr(), panel_t.shape[0], args.ids)
         return e2
     sample_rows = min(args.cpu_sample_rows, panel.shape[0])
-    sample_words = panel[:sample_rows].cpu().numpy().view(np.uint64) if rank == 0 else None
+    sample_words = panel[:sample_rows].cpu().numpy().view(np.uint64) if rank == 0 and args.full else None
     words_all = None
-    if rank == 0 and world == 1 and not args.no_e2e:       # the whole packed panel on the host (2.56 GB) for warm_e2e
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:       # the whole packed panel on the host (2.56 GB) for warm_e2e
         words_all = np.empty((panel.shape[0], panel.shape[1]), dtype=np.uint64)
         for a in range(0, panel.shape[0], 500_000):
             words_all[a:a + 500_000] = panel[a:a + 500_000].cpu().numpy().view(np.uint64)
@@ -1088,6 +1095,7 @@ def main():
     ms_ld = [m["ld"] for m in ms_all]
     layout_timed = eng.ld_layout()
     count_unit = eng.last_count_unit()
+    ld_variant = eng.last_ld_variant()
     if args.dump_outputs:                       # before any later leg runs the engine again
         dump_outputs(args.dump_outputs, eng, rank, world, args.seed)
 
@@ -1103,246 +1111,252 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
-    # the step with the alt alleles recounted inside it (K0 in the timed region; reported beside `value`): queued
-    # back to back like the timed steps
-    eng.set_option("count_in_run", 1)
-    eng.set_option("async", 1)
-    for _ in range(10):
-        eng.run(targets, ld=True)
-    eng.sync()
-    n_rc = max(20, min(args.steps, 100))
-    t1 = time.perf_counter()
-    for _ in range(n_rc):
-        eng.run(targets, ld=True)
-    eng.sync()
-    dt_recount = (time.perf_counter() - t1) / n_rc
-    eng.set_option("async", 0)
-    alt_in_run_ms = float(np.mean([eng.run_ms(b)["alt_count"] for b in range(min(n_rc, 32))]))
-    # k_alt_count alone on the chip: recount inside non-LD runs (nothing on the main stream beside it)
-    for _ in range(6):
-        eng.run(targets, ld=False)
-    alt_ms = float(np.mean([eng.run_ms(b)["alt_count"] for b in range(5)]))
-    eng.set_option("count_in_run", 0)
-    eng.run(targets, ld=True)
-    # the dominant kernel alone: 32 more queued steps timed through the kernel's own dispatch packet
-    # (hipExtLaunchKernel start/stop events; slower per step than one event record, hence not in the
-    # timed region above)
-    ms_kernel = None
-    try:
-        eng.set_option("dispatch_events", 1)
+    # Everything from here to the result line measures something beside `value` -- the other clocks, other shapes and
+    # options, the reference on the CPU, the host program -- and runs with --full only: a plain run goes from its timed
+    # steps straight to its line.
+    dt_recount = alt_in_run_ms = alt_ms = ms_kernel = all_terms = in_place = None
+    up, engine_clock, d2h = {}, {}, None
+    non_ld = many_rank = many = sparse = win_full = None
+    if args.full:
+        # the step with the alt alleles recounted inside it (K0 in the timed region; reported beside `value`): queued
+        # back to back like the timed steps
+        eng.set_option("count_in_run", 1)
         eng.set_option("async", 1)
-        for _ in range(40):
-            step()
-        eng.sync()
-        ms_kernel = [eng.run_kernel_ms(b) for b in range(32)]
-    except ibdgem_amd.EngineError:
-        pass                                 # strict kernel: no such figure
-    eng.set_option("async", 0)
-    eng.set_option("dispatch_events", 0)
-    # the same step with every term counted in it (option ibd0_after 0: no pass over the site list is used), same tiles, same queue:
-    # what the timed steps would cost without the engine's use of what a site list's comparisons have in common
-    all_terms = None
-    if count_unit == 3:
-        eng.set_option("ibd0_after", 0)
-        eng.set_option("async", 1)
-        for _ in range(16):
-            step()
-        eng.sync()
-        n_at = max(32, min(args.steps, 200))
-        t_at = time.perf_counter()
-        for _ in range(n_at):
-            step()
-        eng.sync()
-        at_ms = (time.perf_counter() - t_at) / n_at * 1e3
-        eng.set_option("async", 0)
-        at_ld = float(np.mean([eng.run_ms(b)["ld"] for b in range(32)]))
-        all_terms = {"ms_per_step": at_ms, "ld_launch_ms": at_ld, "count_unit": eng.last_count_unit(), "steps": n_at,
-                     "sites_per_s": n_cov / (at_ms * 1e-3),
-                     "hbm_frac": algorithmic_bytes_per_site(args.ids, 1) * n_cov / (at_ld * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "note": "the timed steps' queue with option ibd0_after 0: k_ld_popcount counts the IBD0 terms of every background "
-                             "individual in every step again (ibdg_last_count_unit 2); same tiles, a new individual per step"}
-        eng.set_option("ibd0_after", next((int(kv.split("=")[1]) for kv in args.opt if kv.startswith("ibd0_after=")), 8))
-        for _ in range(2):
-            step()
-        eng.sync()
-    # the same step on the panel's own tiles (what the first 15 runs on a site list cost; the timed steps of rounds 1-3):
-    # compacted tiles forbidden, a fresh upload, queued steps after the same clock settling
-    in_place = None
-    if layout_timed == 2 and world == 1:
-        eng.set_option("compact_tiles", -1)
-        eng.set_option("ibd0_after", 0)       # (... and every run counts the IBD0 terms itself, as a site list's first runs do)
-        eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)
-        eng.set_option("async", 1)
-        t_pw = time.perf_counter()
-        while (time.perf_counter() - t_pw) * 1e3 < args.prewarm_ms:
-            for _ in range(8):
-                eng.run(targets, ld=True)
-            eng.sync()
-        n_ip = max(32, min(args.steps, 200))
-        t_ip = time.perf_counter()
-        for _ in range(n_ip):
+        for _ in range(10):
             eng.run(targets, ld=True)
         eng.sync()
-        ip_ms = (time.perf_counter() - t_ip) / n_ip * 1e3
+        n_rc = max(20, min(args.steps, 100))
+        t1 = time.perf_counter()
+        for _ in range(n_rc):
+            eng.run(targets, ld=True)
+        eng.sync()
+        dt_recount = (time.perf_counter() - t1) / n_rc
         eng.set_option("async", 0)
-        ip_ld = float(np.mean([eng.run_ms(b)["ld"] for b in range(32)]))
-        in_place = {"ms_per_step": ip_ms, "ld_launch_ms": ip_ld, "ld_layout": eng.ld_layout(), "steps": n_ip,
-                    "sites_per_s": n_cov / (ip_ms * 1e-3),
-                    "hbm_frac": algorithmic_bytes_per_site(args.ids, 1) * n_cov / (ip_ld * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        eng.set_option("compact_tiles", 0)
-        eng.set_option("ibd0_after", next((int(kv.split("=")[1]) for kv in args.opt if kv.startswith("ibd0_after=")), 8))
-        eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)
-    # the other clocks of one comparison (not `value`): upload of its rows, the survey's engine clock, results to host
-    if want_second:
-        eng2 = second_context(panel_kept)
-        del panel_kept
-        torch.cuda.empty_cache()
-    up, engine_clock, d2h = upload_and_engine_clocks(torch, eng, ibdgem_amd, n_ref, n_alt, args.window, targets, n_cov, eng2)
-    if eng2 is not None:
-        eng2.close()
-        eng2 = None
-    up["first_call_ms"] = first_upload_ms
-    # BASELINE.json configs[1]'s shape on this rank's rows (not `value`): the non-LD step (per-site values + window products)
-    non_ld = None
-    if world == 1 and not args.no_many:
-        eng.set_option("async", 1)
-        # clock settling as for the timed steps (--prewarm-ms of wall time, untimed): the legs before this one leave the
-        # GPU idle between host-side waits, and 100 steps of 0.04 ms are over before its clock is back up
-        t_pw = time.perf_counter()
-        while True:
-            for _ in range(100):
+        alt_in_run_ms = float(np.mean([eng.run_ms(b)["alt_count"] for b in range(min(n_rc, 32))]))
+        # k_alt_count alone on the chip: recount inside non-LD runs (nothing on the main stream beside it)
+        for _ in range(6):
+            eng.run(targets, ld=False)
+        alt_ms = float(np.mean([eng.run_ms(b)["alt_count"] for b in range(5)]))
+        eng.set_option("count_in_run", 0)
+        eng.run(targets, ld=True)
+        # the dominant kernel alone: 32 more queued steps timed through the kernel's own dispatch packet
+        # (hipExtLaunchKernel start/stop events; slower per step than one event record, hence not in the
+        # timed region above)
+        ms_kernel = None
+        try:
+            eng.set_option("dispatch_events", 1)
+            eng.set_option("async", 1)
+            for _ in range(40):
+                step()
+            eng.sync()
+            ms_kernel = [eng.run_kernel_ms(b) for b in range(32)]
+        except ibdgem_amd.EngineError:
+            pass                                 # strict kernel: no such figure
+        eng.set_option("async", 0)
+        eng.set_option("dispatch_events", 0)
+        # the same step with every term counted in it (option ibd0_after 0: no pass over the site list is used), same tiles, same queue:
+        # what the timed steps would cost without the engine's use of what a site list's comparisons have in common
+        all_terms = None
+        if count_unit == 3:
+            eng.set_option("ibd0_after", 0)
+            eng.set_option("async", 1)
+            for _ in range(16):
+                step()
+            eng.sync()
+            n_at = max(32, min(args.steps, 200))
+            t_at = time.perf_counter()
+            for _ in range(n_at):
+                step()
+            eng.sync()
+            at_ms = (time.perf_counter() - t_at) / n_at * 1e3
+            eng.set_option("async", 0)
+            at_ld = float(np.mean([eng.run_ms(b)["ld"] for b in range(32)]))
+            all_terms = {"ms_per_step": at_ms, "ld_launch_ms": at_ld, "count_unit": eng.last_count_unit(), "steps": n_at,
+                         "sites_per_s": n_cov / (at_ms * 1e-3),
+                         "hbm_frac": algorithmic_bytes_per_site(args.ids, 1) * n_cov / (at_ld * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                         "note": "the timed steps' queue with option ibd0_after 0: k_ld_popcount counts the IBD0 terms of every background "
+                                 "individual in every step again (ibdg_last_count_unit 2); same tiles, a new individual per step"}
+            eng.set_option("ibd0_after", next((int(kv.split("=")[1]) for kv in args.opt if kv.startswith("ibd0_after=")), 8))
+            for _ in range(2):
+                step()
+            eng.sync()
+        # the same step on the panel's own tiles (what the first 15 runs on a site list cost; the timed steps of rounds 1-3):
+        # compacted tiles forbidden, a fresh upload, queued steps after the same clock settling
+        in_place = None
+        if layout_timed == 2 and world == 1:
+            eng.set_option("compact_tiles", -1)
+            eng.set_option("ibd0_after", 0)       # (... and every run counts the IBD0 terms itself, as a site list's first runs do)
+            eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)
+            eng.set_option("async", 1)
+            t_pw = time.perf_counter()
+            while (time.perf_counter() - t_pw) * 1e3 < args.prewarm_ms:
+                for _ in range(8):
+                    eng.run(targets, ld=True)
+                eng.sync()
+            n_ip = max(32, min(args.steps, 200))
+            t_ip = time.perf_counter()
+            for _ in range(n_ip):
+                eng.run(targets, ld=True)
+            eng.sync()
+            ip_ms = (time.perf_counter() - t_ip) / n_ip * 1e3
+            eng.set_option("async", 0)
+            ip_ld = float(np.mean([eng.run_ms(b)["ld"] for b in range(32)]))
+            in_place = {"ms_per_step": ip_ms, "ld_launch_ms": ip_ld, "ld_layout": eng.ld_layout(), "steps": n_ip,
+                        "sites_per_s": n_cov / (ip_ms * 1e-3),
+                        "hbm_frac": algorithmic_bytes_per_site(args.ids, 1) * n_cov / (ip_ld * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            eng.set_option("compact_tiles", 0)
+            eng.set_option("ibd0_after", next((int(kv.split("=")[1]) for kv in args.opt if kv.startswith("ibd0_after=")), 8))
+            eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)
+        # the other clocks of one comparison (not `value`): upload of its rows, the survey's engine clock, results to host
+        if want_second:
+            eng2 = second_context(panel_kept)
+            del panel_kept
+            torch.cuda.empty_cache()
+        up, engine_clock, d2h = upload_and_engine_clocks(torch, eng, ibdgem_amd, n_ref, n_alt, args.window, targets, n_cov, eng2)
+        if eng2 is not None:
+            eng2.close()
+            eng2 = None
+        up["first_call_ms"] = first_upload_ms
+        # BASELINE.json configs[1]'s shape on this rank's rows (not `value`): the non-LD step (per-site values + window products)
+        non_ld = None
+        if world == 1 and not args.no_many:
+            eng.set_option("async", 1)
+            # clock settling as for the timed steps (--prewarm-ms of wall time, untimed): the legs before this one leave the
+            # GPU idle between host-side waits, and 100 steps of 0.04 ms are over before its clock is back up
+            t_pw = time.perf_counter()
+            while True:
+                for _ in range(100):
+                    eng.run(targets, ld=False)
+                eng.sync()
+                if (time.perf_counter() - t_pw) * 1e3 >= args.prewarm_ms:
+                    break
+            t0 = time.perf_counter()
+            for _ in range(200):
                 eng.run(targets, ld=False)
             eng.sync()
-            if (time.perf_counter() - t_pw) * 1e3 >= args.prewarm_ms:
-                break
-        t0 = time.perf_counter()
-        for _ in range(200):
-            eng.run(targets, ld=False)
-        eng.sync()
-        nl_ms = (time.perf_counter() - t0) / 200 * 1e3
-        eng.set_option("async", 0)
-        nl_k = float(np.mean([eng.run_ms(i)["rows"] for i in range(16)]))
-        nl_bytes = 4 + 0.25 + 24.24          # read counts + target alleles + three doubles (+ window results)
-        non_ld = {"ms_per_step": nl_ms, "rows_per_s": n_rows / (nl_ms * 1e-3), "k_rows_windows_ms": nl_k,
-                  "bytes_per_row": nl_bytes,
-                  "hbm_frac": nl_bytes * n_rows / (nl_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                  "kernel_hbm_frac": nl_bytes * n_rows / (nl_k * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                  "note": "non-LD comparison (per-row LIBD0/1/2 + window products, BASELINE.json configs[1] at this row count), "
-                          "queued steps, host wall clock; one kernel (k_rows_windows: a wave per pair of windows computes their rows' "
-                          "values, stores them and multiplies them up -- nothing is read back; the AF column is made by "
-                          "ibdg_get_site_af when asked for, not by the run); hbm_frac on the step clock, kernel_hbm_frac on "
-                          "the kernel's own events"}
-    # BASELINE.json configs[4]'s shape over N ranks: every rank runs ITS window range against all the comparison individuals
-    # (one ibdg_run; windows are independent, src/ibdgem.c:558-570, and so are comparison individuals, :522 -- a 2-D split
-    # would change nothing per rank); device time and wall time per rank, gathered below
-    many_rank = None
-    if world > 1 and not args.no_many:
-        many_tr = [(args.target + 5 * i) % args.ids for i in range(args.many_targets)]
-        eng.set_option("site_results", 0)
-        eng.run(many_tr, ld=True)
-        eng.sync()
-        best_dev, best_wall = None, None
-        for _ in range(3):
-            barrier()
-            tw = time.perf_counter()
+            nl_ms = (time.perf_counter() - t0) / 200 * 1e3
+            eng.set_option("async", 0)
+            nl_k = float(np.mean([eng.run_ms(i)["rows"] for i in range(16)]))
+            nl_bytes = 4 + 0.25 + 24.24          # read counts + target alleles + three doubles (+ window results)
+            non_ld = {"ms_per_step": nl_ms, "rows_per_s": n_rows / (nl_ms * 1e-3), "k_rows_windows_ms": nl_k,
+                      "bytes_per_row": nl_bytes,
+                      "hbm_frac": nl_bytes * n_rows / (nl_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                      "kernel_hbm_frac": nl_bytes * n_rows / (nl_k * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                      "note": "non-LD comparison (per-row LIBD0/1/2 + window products, BASELINE.json configs[1] at this row count), "
+                              "queued steps, host wall clock; one kernel (k_rows_windows: a wave per pair of windows computes their rows' "
+                              "values, stores them and multiplies them up -- nothing is read back; the AF column is made by "
+                              "ibdg_get_site_af when asked for, not by the run); hbm_frac on the step clock, kernel_hbm_frac on "
+                              "the kernel's own events"}
+        # BASELINE.json configs[4]'s shape over N ranks: every rank runs ITS window range against all the comparison individuals
+        # (one ibdg_run; windows are independent, src/ibdgem.c:558-570, and so are comparison individuals, :522 -- a 2-D split
+        # would change nothing per rank); device time and wall time per rank, gathered below
+        many_rank = None
+        if world > 1 and not args.no_many:
+            many_tr = [(args.target + 5 * i) % args.ids for i in range(args.many_targets)]
+            eng.set_option("site_results", 0)
             eng.run(many_tr, ld=True)
             eng.sync()
-            wall = (time.perf_counter() - tw) * 1e3
-            dev_ms = eng.last_run_ms()["total"]
-            best_dev = dev_ms if best_dev is None else min(best_dev, dev_ms)
-            best_wall = wall if best_wall is None else min(best_wall, wall)
-        eng.set_option("site_results", 1)
-        many_rank = {"comparison_individuals": len(many_tr), "device_ms": best_dev, "wall_ms": best_wall,
-                     "ld_layout": eng.ld_layout(), "windowed_sites": int(n_cov)}
-    many = None
-    if world == 1 and not args.no_many:
-        many_t = [(args.target + 5 * i) % args.ids for i in range(args.many_targets)]
-        eng.set_option("compact_tiles", -1)         # this part: the panel's own tiles, however many runs it takes (the upload before it left them)
-        eng.run(many_t, ld=True)
-        best = None
-        for _ in range(3):
+            best_dev, best_wall = None, None
+            for _ in range(3):
+                barrier()
+                tw = time.perf_counter()
+                eng.run(many_tr, ld=True)
+                eng.sync()
+                wall = (time.perf_counter() - tw) * 1e3
+                dev_ms = eng.last_run_ms()["total"]
+                best_dev = dev_ms if best_dev is None else min(best_dev, dev_ms)
+                best_wall = wall if best_wall is None else min(best_wall, wall)
+            eng.set_option("site_results", 1)
+            many_rank = {"comparison_individuals": len(many_tr), "device_ms": best_dev, "wall_ms": best_wall,
+                         "ld_layout": eng.ld_layout(), "windowed_sites": int(n_cov)}
+        many = None
+        if world == 1 and not args.no_many:
+            many_t = [(args.target + 5 * i) % args.ids for i in range(args.many_targets)]
+            eng.set_option("compact_tiles", -1)         # this part: the panel's own tiles, however many runs it takes (the upload before it left them)
             eng.run(many_t, ld=True)
-            ms = eng.last_run_ms()
-            best = ms if best is None or ms["total"] < best["total"] else best
-        T = len(many_t)
-        b_site_T = algorithmic_bytes_per_site(args.ids, T)          # N/4 + 4 + T x 24.24 B per windowed site
-        achieved_T = b_site_T * n_cov / (best["ld"] * 1e-3) / 1e9
-        # the same run with no per-row results kept (option site_results 0: the host program's --summary-only)
-        eng.set_option("site_results", 0)
-        eng.run(many_t, ld=True)
-        best0 = None
-        for _ in range(3):
+            best = None
+            for _ in range(3):
+                eng.run(many_t, ld=True)
+                ms = eng.last_run_ms()
+                best = ms if best is None or ms["total"] < best["total"] else best
+            T = len(many_t)
+            b_site_T = algorithmic_bytes_per_site(args.ids, T)          # N/4 + 4 + T x 24.24 B per windowed site
+            achieved_T = b_site_T * n_cov / (best["ld"] * 1e-3) / 1e9
+            # the same run with no per-row results kept (option site_results 0: the host program's --summary-only)
+            eng.set_option("site_results", 0)
             eng.run(many_t, ld=True)
-            ms = eng.last_run_ms()
-            best0 = ms if best0 is None or ms["total"] < best0["total"] else best0
-        eng.set_option("site_results", 1)
-        # the same run from the compacted tiles of the site list (the engine switches by itself from
-        # "compact_targets" = 256 comparison individuals; forced here): the re-layout is paid once, inside the first run
-        eng.set_option("compact_tiles", 0)
-        eng.set_option("compact_targets", 1)
-        eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)
-        eng.sync()
-        t_c = time.perf_counter()
-        eng.run(many_t, ld=True)
-        first_c_ms = (time.perf_counter() - t_c) * 1e3
-        layout_c = eng.ld_layout()
-        best_c = None
-        for _ in range(3):
+            best0 = None
+            for _ in range(3):
+                eng.run(many_t, ld=True)
+                ms = eng.last_run_ms()
+                best0 = ms if best0 is None or ms["total"] < best0["total"] else best0
+            eng.set_option("site_results", 1)
+            # the same run from the compacted tiles of the site list (the engine switches by itself from
+            # "compact_targets" = 256 comparison individuals; forced here): the re-layout is paid once, inside the first run
+            eng.set_option("compact_tiles", 0)
+            eng.set_option("compact_targets", 1)
+            eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)
+            eng.sync()
+            t_c = time.perf_counter()
             eng.run(many_t, ld=True)
-            ms = eng.last_run_ms()
-            best_c = ms if best_c is None or ms["total"] < best_c["total"] else best_c
-        eng.set_option("compact_targets", 256)
-        eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)      # back to the panel's own tiles
-        b_site_T0 = args.ids / 4.0 + 4.0 + T * 0.24                  # ... without the 24 B per row and individual
-        pmc = None
-        pdir = os.path.join(REPO, "profiles")
-        for fn in sorted(os.listdir(pdir)) if os.path.isdir(pdir) else []:
-            if fn.endswith("_mfma_pmc.json"):
-                with open(os.path.join(pdir, fn)) as fh:
-                    j = json.load(fh)
-                    k = (j.get("kernels") or j).get("ibdg::k_ld_mfma")       # (summarised or raw per-kernel averages)
-                if k:
-                    pmc = {"profile": fn, "VALUBusy_pct": k.get("VALUBusy"), "LdsUtil_pct": k.get("LdsUtil"),
-                           "MfmaUtil_pct": k.get("MfmaUtil"), "valu_instructions_per_launch": k.get("SQ_INSTS_VALU"),
-                           "lds_instructions_per_launch": k.get("SQ_INSTS_LDS")}
-        many = {"comparison_individuals": T, "run_ms": best["total"], "ms_per_individual": best["total"] / T,
-                "site_individual_pairs_per_s": n_cov * T / (best["total"] * 1e-3),
-                "ld_launches_ms": best["ld"], "rows_kernel_ms": best["rows"],
-                "roofline": {"bound": "hbm", "kernel": "k_ld_mfma (groups of 15)", "bytes_per_site": b_site_T,
-                             "sites_per_launch": n_cov, "kernel_ms": best["ld"], "achieved": achieved_T, "peak": HBM_PEAK_GBS,
-                             "unit": "GB/s", "frac": achieved_T / HBM_PEAK_GBS,
-                             "busy_shares_from_profile": pmc,
-                             "busy_shares_note": "replayed from the committed counter profile named in it, not measured by this run",
-                             "note": "bytes_per_site = N/4 + 4 + T x 24.24 (SURVEY.md s8(d): the panel row once per launch, 24 B "
-                                     "of per-row output per individual); kernel_ms = the --LD launches of the run (k_win_target_g, "
-                                     "k_win_slot_g, k_ld_mfma, k_ld_finalize for all groups) from the engine's events.  This path is "
-                                     "bound by vector-ALU issue and the LDS port in its window ends (four table products per "
-                                     "background individual, comparison individual and window), far from the HBM roofline: the "
-                                     "busy shares are those of the committed counter profile"},
-                "without_per_row_results": {"run_ms": best0["total"], "ms_per_individual": best0["total"] / T,
-                                            "bytes_per_site": b_site_T0,
-                                            "hbm_frac": b_site_T0 * n_cov / (best0["total"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                            "device_memory_for_results_bytes": int(T * eng.n_windows * 24),
-                                            "note": "option site_results 0: no T x rows x 24 B array, no per-row stores; LIBD2 of "
-                                                    "the windows from the IBD2 pick of every row (k_rows_windows<false>)"},
-                "from_compacted_tiles": {"ld_layout": layout_c, "run_ms": best_c["total"], "ms_per_individual": best_c["total"] / T,
-                                         "ld_launches_ms": best_c["ld"],
-                                         "first_run_wall_ms_with_the_relayout_inside": first_c_ms,
-                                         "relayout_pays_from_individuals": (
-                                             (first_c_ms - best_c["total"]) / max(1e-9, (best["total"] - best_c["total"]) / T)
-                                             if best["total"] > best_c["total"] else None),
-                                         "note": "rows with reads gathered back to back and transposed into tiles: 4.1 segments and 3.1 tile "
-                                                 "words per window of 100 rows instead of 4.6 and 3.6, no rows without reads streamed"},
-                "note": "one ibdg_run over that many comparison individuals against the resident panel (device time, best of 3): "
-                        "groups of 15 through k_ld_mfma -- the sums that depend on the comparison individual as integer matrix "
-                        "products (DESIGN.md s4.2); per-site values and window products of all of them included"}
-    sparse = None
-    if world == 1 and not args.no_many:
-        sparse = sparse_pileup_clocks(torch, eng, ibdgem_amd, n_ref, n_alt, args.window, args.target, many_t, args.seed)
-        eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)
-    eng.run(targets, ld=True)
-    win_full = eng.window_ll(0) if rank == 0 else None
-    ld_variant = eng.last_ld_variant()
+            first_c_ms = (time.perf_counter() - t_c) * 1e3
+            layout_c = eng.ld_layout()
+            best_c = None
+            for _ in range(3):
+                eng.run(many_t, ld=True)
+                ms = eng.last_run_ms()
+                best_c = ms if best_c is None or ms["total"] < best_c["total"] else best_c
+            eng.set_option("compact_targets", 256)
+            eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)      # back to the panel's own tiles
+            b_site_T0 = args.ids / 4.0 + 4.0 + T * 0.24                  # ... without the 24 B per row and individual
+            pmc = None
+            pdir = os.path.join(REPO, "profiles")
+            for fn in sorted(os.listdir(pdir)) if os.path.isdir(pdir) else []:
+                if fn.endswith("_mfma_pmc.json"):
+                    with open(os.path.join(pdir, fn)) as fh:
+                        j = json.load(fh)
+                        k = (j.get("kernels") or j).get("ibdg::k_ld_mfma")       # (summarised or raw per-kernel averages)
+                    if k:
+                        pmc = {"profile": fn, "VALUBusy_pct": k.get("VALUBusy"), "LdsUtil_pct": k.get("LdsUtil"),
+                               "MfmaUtil_pct": k.get("MfmaUtil"), "valu_instructions_per_launch": k.get("SQ_INSTS_VALU"),
+                               "lds_instructions_per_launch": k.get("SQ_INSTS_LDS")}
+            many = {"comparison_individuals": T, "run_ms": best["total"], "ms_per_individual": best["total"] / T,
+                    "site_individual_pairs_per_s": n_cov * T / (best["total"] * 1e-3),
+                    "ld_launches_ms": best["ld"], "rows_kernel_ms": best["rows"],
+                    "roofline": {"bound": "hbm", "kernel": "k_ld_mfma (groups of 15)", "bytes_per_site": b_site_T,
+                                 "sites_per_launch": n_cov, "kernel_ms": best["ld"], "achieved": achieved_T, "peak": HBM_PEAK_GBS,
+                                 "unit": "GB/s", "frac": achieved_T / HBM_PEAK_GBS,
+                                 "busy_shares_from_profile": pmc,
+                                 "busy_shares_note": "replayed from the committed counter profile named in it, not measured by this run",
+                                 "note": "bytes_per_site = N/4 + 4 + T x 24.24 (SURVEY.md s8(d): the panel row once per launch, 24 B "
+                                         "of per-row output per individual); kernel_ms = the --LD launches of the run (k_win_target_g, "
+                                         "k_win_slot_g, k_ld_mfma, k_ld_finalize for all groups) from the engine's events.  This path is "
+                                         "bound by vector-ALU issue and the LDS port in its window ends (four table products per "
+                                         "background individual, comparison individual and window), far from the HBM roofline: the "
+                                         "busy shares are those of the committed counter profile"},
+                    "without_per_row_results": {"run_ms": best0["total"], "ms_per_individual": best0["total"] / T,
+                                                "bytes_per_site": b_site_T0,
+                                                "hbm_frac": b_site_T0 * n_cov / (best0["total"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                                "device_memory_for_results_bytes": int(T * eng.n_windows * 24),
+                                                "note": "option site_results 0: no T x rows x 24 B array, no per-row stores; LIBD2 of "
+                                                        "the windows from the IBD2 pick of every row (k_rows_windows<false>)"},
+                    "from_compacted_tiles": {"ld_layout": layout_c, "run_ms": best_c["total"], "ms_per_individual": best_c["total"] / T,
+                                             "ld_launches_ms": best_c["ld"],
+                                             "first_run_wall_ms_with_the_relayout_inside": first_c_ms,
+                                             "relayout_pays_from_individuals": (
+                                                 (first_c_ms - best_c["total"]) / max(1e-9, (best["total"] - best_c["total"]) / T)
+                                                 if best["total"] > best_c["total"] else None),
+                                             "note": "rows with reads gathered back to back and transposed into tiles: 4.1 segments and 3.1 tile "
+                                                     "words per window of 100 rows instead of 4.6 and 3.6, no rows without reads streamed"},
+                    "note": "one ibdg_run over that many comparison individuals against the resident panel (device time, best of 3): "
+                            "groups of 15 through k_ld_mfma -- the sums that depend on the comparison individual as integer matrix "
+                            "products (DESIGN.md s4.2); per-site values and window products of all of them included"}
+        sparse = None
+        if world == 1 and not args.no_many:
+            sparse = sparse_pileup_clocks(torch, eng, ibdgem_amd, n_ref, n_alt, args.window, args.target, many_t, args.seed)
+            eng.upload_sites(np.arange(n_rows, dtype=np.uint32), n_ref, n_alt, args.window)
+        eng.run(targets, ld=True)
+        win_full = eng.window_ll(0) if rank == 0 else None
 
     tot = torch.tensor([dt, float(n_cov), float(n_rows)], dtype=torch.float64,
                        device=dev if backend == "nccl" else "cpu")
@@ -1360,7 +1374,7 @@ def main():
             "ld_launch_ms_min": float(np.min(ms_ld)),       # the fastest of those steps on the device's own clock
             "step_device_ms": float(np.mean([m["total"] for m in ms_all])),      # the engine's own events: both streams of a step
             "many_comparison_individuals": many_rank,
-            "upload_sites_ms": up["pageable_ms"], "engine_clock_ms": engine_clock["ms"],
+            "upload_sites_ms": up.get("pageable_ms"), "engine_clock_ms": engine_clock.get("ms"),
             "host_queue_ms_per_step": dt_host / args.steps * 1e3}
     per_rank = [mine]
     if use_dist:
@@ -1443,15 +1457,15 @@ def main():
             "alt_count_note": "k_alt_count alone on the chip (2.56 GB panel); inside an --LD run it is throttled to 4 single-wave "
                               "workgroups per CU so that the --LD workgroups keep their wave slots: alt_count_in_ld_run_ms",
             "alt_count_in_ld_run_ms": alt_in_run_ms,
-            "upload_sites_ms": up["pageable_ms"],
-            "upload_sites": up,
-            "engine_clock": engine_clock,
+            "upload_sites_ms": up.get("pageable_ms"),
+            "upload_sites": up or None,
+            "engine_clock": engine_clock or None,
             "results_to_host": d2h,
             "per_rank": per_rank,
             "barrier_ms": barrier_ms,
             "barrier_note": None if not use_dist else "the closing barrier of the timed region (dist.barrier + device sync) with "
                             "nothing left to wait for, best of 5: what it adds to `steps` x ms_per_step",
-            "value_with_recount": n_cov / dt_recount if world == 1 else None,
+            "value_with_recount": n_cov / dt_recount if world == 1 and dt_recount else None,
             "many_comparison_individuals": many,
             "sparse_pileup": sparse,
             "non_ld": non_ld,
@@ -1473,7 +1487,7 @@ def main():
                         "individuals in one ibdg_run (no per-row results kept: window tables only), ranks started together "
                         "(barrier), wall and device time per rank, best of 3; the job's rate = all (site, individual) pairs / the "
                         "slowest rank's wall time"}
-        if not args.no_cpu_baseline and world == 1:       # the CPU leg is timed at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:       # the CPU leg is timed at N=1 only
             s = sample_rows
             eng.upload_sites(np.arange(s, dtype=np.uint32), n_ref[:s], n_alt[:s], args.window)
             eng.run(targets, ld=True)
@@ -1498,7 +1512,8 @@ def main():
             out["cold_e2e"] = cold
             if isinstance(warm, dict) and "summary_only_s" in warm and "cpu_baseline" in out:
                 out["warm_e2e_vs_reference_end_to_end"] = (n_cov / warm["summary_only_s"]) / out["cpu_baseline"]["value"]
-        print(compact_line(out, write_detail(out, world)), flush=True)
+        # (a plain run writes no detail file: its line holds all it measured)
+        print(compact_line(out, write_detail(out, world) if args.full else None), flush=True)
     eng.close()
     if use_dist:
         dist.barrier()

@@ -4,6 +4,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -92,6 +93,24 @@ def test_result_line_is_small_and_complete(n_ranks):
     assert len(line["cpu_baseline"]["sample"]) <= 300
 
 
+def test_plain_result_line_keeps_the_contract_keys():
+    """A run without --full measures none of the legs beside `value` and writes no detail file: its line still carries
+    every key of the contract, the legs' ones null."""
+    import bench
+    out = _fat_out(1)
+    for leg in ("cpu_baseline", "warm_e2e", "cold_e2e", "sparse_pileup", "non_ld", "step_vs_reference_end_to_end",
+                "engine_clock_vs_reference_end_to_end", "ld_kernels_vs_reference_ld_stage"):
+        out.pop(leg)
+    out.update(engine_clock=None, upload_sites=None, many_comparison_individuals=None)
+    out["roofline"]["dominant_kernel_only_ms"] = None
+    line = json.loads(bench.compact_line(out, None))
+    assert CONTRACT_KEYS <= set(line) and ROOFLINE_KEYS <= set(line["roofline"])
+    assert line["detail_file"] is None and line["cpu_baseline"] is None and line["engine_sites_per_s"] is None
+    assert line["many_individuals"] is None and not any(line["parity"].values())
+    assert line["value"] == pytest.approx(out["value"], rel=1e-5) and line["ms_per_step"] == pytest.approx(out["ms_per_step"], rel=1e-5)
+    assert line["metric"] == out["metric"] and line["unit"] == "sites/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+
+
 def test_result_line_refuses_to_grow():
     import bench
     out = _fat_out(8)
@@ -127,7 +146,7 @@ def test_gpus_2_without_a_launcher_starts_two_ranks_itself():
 def test_gpus_2_self_launched_on_one_device():
     """Two self-launched ranks sharing device 0 over gloo (BENCH_FORCE_DEVICE / BENCH_BACKEND exist for this
     rehearsal only).  n_gpus, the per-rank block, and the shards add up to the one-rank run's rows."""
-    common = ["--steps", "20", "--warmup", "5", "--sites", "500000", "--no-cpu-baseline", "--no-e2e", "--many-targets", "20"]
+    common = ["--steps", "20", "--warmup", "5", "--sites", "500000", "--full", "--no-cpu-baseline", "--no-e2e", "--many-targets", "20"]
     exe = [sys.executable, os.path.join(REPO, "bench.py")]
     r1 = subprocess.run(exe + ["--gpus", "1"] + common, env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert r1.returncode == 0, r1.stderr[-2000:]
@@ -172,7 +191,8 @@ def test_one_rank_through_rccl():
     with device_id, barriers inside and after the timed region, the MAX / SUM reductions of a float64 device tensor,
     the per-rank gather, the orderly destroy) are rehearsed by ONE rank: BENCH_DIST_ONE_RANK=1, also under the
     driver's launcher (torch.distributed.run with one process), whose environment the rank must accept."""
-    common = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--sites", "500000", "--no-cpu-baseline", "--no-e2e", "--no-many"]
+    common = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--sites", "500000", "--full", "--no-cpu-baseline", "--no-e2e",
+              "--no-many"]
     bench_py = os.path.join(REPO, "bench.py")
     plain = subprocess.run([sys.executable, bench_py] + common, env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert plain.returncode == 0, plain.stderr[-2000:]
@@ -197,9 +217,9 @@ def test_one_rank_through_rccl():
 
 @pytest.mark.gpu
 def test_the_drivers_command_prints_a_line_it_can_parse():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` -- the driver's very command, every leg included -- ends with ONE line
-    of at most 4096 bytes that carries `roofline` and `cpu_baseline`, and the detail file beside it holds the rest."""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` -- the driver's command with every leg included -- ends with ONE
+    line of at most 4096 bytes that carries `roofline` and `cpu_baseline`, and the detail file beside it holds the rest."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
                        env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     assert len([l for l in r.stdout.strip().splitlines() if l.startswith("{")]) == 1
@@ -221,6 +241,32 @@ def test_the_drivers_command_prints_a_line_it_can_parse():
     assert detail["value"] == pytest.approx(line["value"], rel=1e-5)
     for leg in ("engine_clock", "upload_sites", "many_comparison_individuals", "non_ld", "warm_e2e", "cold_e2e", "sparse_pileup"):
         assert detail.get(leg), leg
+
+
+@pytest.mark.gpu
+def test_a_plain_run_measures_the_headline_alone():
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` without --full: the same workload and timed steps, ONE line with the
+    contract's keys and the roofline of those steps, none of the other legs, no detail file -- and at most 30 s of the
+    process's wall clock outside its warm-up and timed steps."""
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                       env=_clean_env(), capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and len(lines[0].encode()) <= 4096
+    line = json.loads(lines[0])
+    assert CONTRACT_KEYS <= set(line) and ROOFLINE_KEYS <= set(line["roofline"])
+    assert line["metric"] == "SNP-sites/sec in --LD mode, chr1, 2504-indiv panel" and line["unit"] == "sites/s"
+    assert line["dtype"] == "f64" and line["higher_is_better"] is True and line["clock"] == "step"
+    assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5 and line["new_individual_per_step"] is True
+    assert line["config"]["rows"] == 4_000_000 and line["config"]["n_ids"] == 2504 and line["config"]["window"] == 100
+    assert line["value"] == pytest.approx(line["config"]["windowed_sites"] / (line["ms_per_step"] * 1e-3), rel=1e-4)
+    ro = line["roofline"]
+    assert ro["kernel_ms"] == pytest.approx(line["per_rank"][0]["ld_launch_ms"], rel=1e-4) and 0.2 < ro["frac"] < 1.0
+    assert ro["dominant_kernel_only_ms"] is None and line["cpu_baseline"] is None and line["engine_sites_per_s"] is None
+    assert line["many_individuals"] is None and line["all_terms_in_every_step_ms"] is None and line["detail_file"] is None
+    assert wall - 25 * line["ms_per_step"] * 1e-3 < 30, f"{wall:.1f} s outside the steps"
 
 
 class _FakeEngine:
