@@ -56,7 +56,8 @@ struct ibdg_ctx {
         hipEvent_t k_start = nullptr, k_stop = nullptr;   // start / stop of the dominant --LD kernel's dispatch
         bool has_kernel_times = false;
         hipEvent_t s2_start = nullptr;      // stream2: before its first kernel of the run
-        hipEvent_t s2[3] = {};              // stream2: after alt-count, per-site, window-product kernels
+        hipEvent_t s2_count = nullptr;      // stream2: after the alt-count kernel
+        hipEvent_t s2_end = nullptr;        // stream2: after the per-site values and window products (one kernel)
         hipEvent_t prep = nullptr;          // main stream: the target operands of the matrix-core kernel are built
         hipEvent_t start = nullptr;         // start_own or the previous run's ld_end
         bool recount = false, ld = false;
@@ -107,11 +108,13 @@ struct ibdg_ctx {
     // The finalising step of the last run of single individuals (k_ld_finalize's work) when it has been left to the NEXT
     // run's k_ld_popcount launch (option "finalize_in_next"): whoever reads results or replaces inputs first makes up for
     // it with a launch of its own (flush_finalize).  The partial sums alternate between the two halves of their buffer.
-    bool fin_pending = false;
-    ibdg::PopFinalArgs fin_args;
-    unsigned fin_count = 0;
-    uint64_t fin_sites_gen = 0;
-    int part_half = 0;
+    struct PendingFin {
+        bool pending = false;
+        ibdg::PopFinalArgs args;
+        unsigned count = 0;             // comparison individuals of the launch
+        uint64_t sites_gen = 0;         // sites_gen of the run that left it
+        int half = 0;                   // the half of `partial` the next such run writes
+    } fin;
     float up_ms[3] = {0.f, 0.f, 0.f};   // copies, preparation on the device (with its host round trips), whole call
     bool up_ms_pending = false;         // the first two are still to be read from the events
 
@@ -141,7 +144,6 @@ struct ibdg_ctx {
     long opt_mfma_batch = 36;               // groups of 15 per launch of the matrix-core kernel (540 individuals)
     size_t dev_mem_bytes = 0;               // the device's memory (hipMemGetInfo at ibdg_create)
     uint64_t ibd0_runs = 0, ibd0_bg_gen = 0;
-    int wt_ibd1 = -1;                       // form of the images in wtarget / twords
     DevBuf fragb;                           // [n_segs][3][6 words]: the IBD1 form's fragments that do not depend on the individual (k_frag_base)
     uint64_t fb_gen = 0;                    // sites_gen they were made for
     hipEvent_t ev_fb = nullptr;
@@ -171,41 +173,46 @@ struct ibdg_ctx {
     // `targets` buffers (the kernels of earlier runs may still read the others), and the weights / background sizes that follow
     // from them are made on the device (k_target_weights) from the run's background multiplicities `base_w`; `nrefpanel` is a
     // ring as well -- a finalising step left to the next run reads its own run's entry.
-    static constexpr int TG_SLOTS = 4;
-    uint32_t *tg_stage[TG_SLOTS] = {};
-    size_t tg_stage_cap = 0;            // comparison individuals a slot holds
-    hipEvent_t tg_stage_ev[TG_SLOTS] = {};
-    bool tg_stage_busy[TG_SLOTS] = {};
-    int tg_slot = 0;
+    // `ring` and its functions (ring_prepare, ring_settle, ring_slot, ring_mark_readers) own all of it and its stream edges:
+    // runs of up to AHEAD_MAX_T individuals keep SLOTS copies of it, so that the NEXT run's can be made (on stream3) while the
+    // runs before still read theirs; larger runs use the buffers whole (slot 0), on the main stream.
     // (round 5, later: a RING of four instead of two halves -- the preparation of run i + 1 then waits for the end of run i - 3,
     // not of run i - 1, so it is long done when the --LD kernel of run i ends even on an eighth of a chromosome, where a step is
     // 70 us and the chain "wait, copy, weights, images, record" on stream3 takes 40: profiles/r05_shard_steps.txt)
-    static constexpr int TG_RING = 4;
-    int tg_cur = 0;                    // the slot of `targets` / `weight` / the images the current comparison individuals sit in
-    hipEvent_t tg_s2[TG_RING] = {};     // stream2's last kernel that read that slot
-    bool tg_s2_pending[TG_RING] = {};
-    hipEvent_t tg_main[TG_RING] = {};   // end of the last run on the main stream that read that slot
-    bool tg_main_pending[TG_RING] = {};
-    hipEvent_t tg_ready = nullptr;      // stream3: the current comparison individuals' data are complete
-    hipEvent_t ev_s3sync = nullptr;     // main stream: the prepared sites stream3's kernels read are complete
-    uint64_t s3_gen = 0;                // sites_gen stream3 has been ordered behind
-    int nref_slot = 0;                  // `nrefpanel` is a ring of its own, twice as long: a finalising step left to the next run reads
-    static constexpr int NREF_SLOTS = 2 * TG_RING;   // its own run's entry one run later than anything else of that run is read
-    static constexpr size_t AHEAD_MAX_T = 64;   // runs of up to that many individuals prepare ahead (two halves of every buffer)
+    struct Ring {
+        static constexpr int SLOTS = 4;             // of `targets`, `weight`, wtarget / twords
+        static constexpr int NREF_SLOTS = 2 * SLOTS;   // `nrefpanel`, twice as long: a finalising step left to the next run
+                                                        // reads its own run's entry one run later than anything else of that run
+        static constexpr size_t AHEAD_MAX_T = 64;   // runs of up to that many individuals prepare ahead
+        static constexpr int STAGE_SLOTS = 4;       // page-locked staging of the indices
+        uint32_t *stage[STAGE_SLOTS] = {};
+        size_t stage_cap = 0;                       // comparison individuals a staging slot holds
+        hipEvent_t stage_ev[STAGE_SLOTS] = {};
+        int stage_next = 0;
+        int cur = 0;                                // the slot the current comparison individuals sit in
+        int nref = 0;                               // ... and their slot of `nrefpanel`
+        hipEvent_t main_read[SLOTS] = {}, s2_read[SLOTS] = {};   // the last reader of a slot: main stream, stream2
+        bool main_pending[SLOTS] = {}, s2_pending[SLOTS] = {};
+        hipEvent_t ready = nullptr;                 // the current comparison individuals' data are complete (where made)
+        bool unsettled = false;                     // stream3 holds a preparation the other streams do not wait for yet
+        hipEvent_t ev_s3sync = nullptr;             // main stream: the prepared sites stream3's kernels read are complete
+        uint64_t s3_gen = 0;                        // sites_gen stream3 has been ordered behind
+    } ring;
     long opt_prep_ahead = 1;
     long opt_end_in_dispatch = 1;    // the end event of a run of single individuals rides in its --LD kernel's dispatch packet (0: an event packet behind it): -7 us of a 91 us step on an eighth of a chromosome, profiles/r05_shard_steps.txt
     int base_sum = 0;                   // sum of base_w
-    int wt_slot = -1;                   // the slot the images in wtarget / twords were made in
-    bool s3_unsettled = false;          // stream3 holds a preparation the other streams have not been made to wait for yet (an
-                                        // ibdg_run that failed half way): the next run settles it before anything else
     // the per-target LDS images of k_win_target (segment records with the target's tile words, window constants) depend
     // on the prepared sites and the targets only: a further run over the same sites and targets reuses them
     uint64_t sites_gen = 0;            // bumped by every upload of sites and every change of layout
     uint64_t relayout_credit = 0;      // what the runs on this upload would have saved on the compacted tiles so far, in
                                        // comparison individuals of the matrix-core kernel (see ibdg_run)
-    int wt_mx = -1;                    // ... and the form of the records (option mx_counts)
-    uint64_t wt_gen = 0;               // sites_gen the images in wtarget / twords were made for
-    uint32_t wt_first = 0, wt_count = 0;   // ... for comparison individuals [wt_first, wt_first + wt_count) of prev_targets
+    struct ImgKey {                    // what the images in wtarget / twords were made for: sites_gen (0: nothing), comparison
+        uint64_t gen;                  // individuals [first, first + count) of prev_targets, the form of the records (option
+        uint32_t first, count;         // mx_counts, IBD1) and the ring slot
+        int mx, ibd1, slot;
+        bool operator==(const ImgKey &o) const
+        { return gen == o.gen && first == o.first && count == o.count && mx == o.mx && ibd1 == o.ibd1 && slot == o.slot; }
+    } wt_key = {0, 0, 0, -1, -1, -1};
 
     // run state / results
     DevBuf targets, weight, nrefpanel, af, site_ll, win_ll;
@@ -313,9 +320,9 @@ int fail(ibdg_ctx *c, const char *fmt, ...)
 // The finalising launch a run left to its successor, when no successor took it
 int flush_finalize(ibdg_ctx *c)
 {
-    if (c->fin_pending) {
-        c->fin_pending = false;
-        ibdg::launch_ld_finalize(c->fin_args, c->fin_count, c->stream, ibdg::KernelEvents());
+    if (c->fin.pending) {
+        c->fin.pending = false;
+        ibdg::launch_ld_finalize(c->fin.args, c->fin.count, c->stream, ibdg::KernelEvents());
         HIP_TRY(c, hipGetLastError());
     }
     return 0;
@@ -1060,12 +1067,12 @@ ibdg_ctx *ibdg_create(int device, double epsilon, unsigned max_cov)
             return bail("hipStreamCreate", e);
         if ((e = hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, hi)) != hipSuccess)
             return bail("hipStreamCreate", e);
-        if ((e = hipEventCreateWithFlags(&c->tg_ready, hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&c->ev_s3sync, hipEventDisableTiming)) != hipSuccess)
+        if ((e = hipEventCreateWithFlags(&c->ring.ready, hipEventDisableTiming)) != hipSuccess ||
+            (e = hipEventCreateWithFlags(&c->ring.ev_s3sync, hipEventDisableTiming)) != hipSuccess)
             return bail("hipEventCreate", e);
     }
     for (auto &E : c->evs) {
-        for (hipEvent_t *ev : {&E.start_own, &E.ld_end, &E.k_start, &E.k_stop, &E.s2_start, &E.s2[0], &E.s2[1], &E.s2[2], &E.prep})
+        for (hipEvent_t *ev : {&E.start_own, &E.ld_end, &E.k_start, &E.k_stop, &E.s2_start, &E.s2_count, &E.s2_end, &E.prep})
             if ((e = hipEventCreate(ev)) != hipSuccess) return bail("hipEventCreate", e);
     }
     for (hipEvent_t &ev : c->ev_up)
@@ -1135,16 +1142,16 @@ void ibdg_destroy(ibdg_ctx *c)
     if (c->info_h)
         (void)hipHostFree(c->info_h);
     for (auto &E : c->evs)
-        for (hipEvent_t ev : {E.start_own, E.ld_end, E.k_start, E.k_stop, E.s2_start, E.s2[0], E.s2[1], E.s2[2], E.prep})
+        for (hipEvent_t ev : {E.start_own, E.ld_end, E.k_start, E.k_stop, E.s2_start, E.s2_count, E.s2_end, E.prep})
             if (ev)
                 (void)hipEventDestroy(ev);
-    for (int i = 0; i < ibdg_ctx::TG_SLOTS; ++i) {
-        if (c->tg_stage[i])
-            (void)hipHostFree(c->tg_stage[i]);
-        if (c->tg_stage_ev[i])
-            (void)hipEventDestroy(c->tg_stage_ev[i]);
+    for (int i = 0; i < ibdg_ctx::Ring::STAGE_SLOTS; ++i) {
+        if (c->ring.stage[i])
+            (void)hipHostFree(c->ring.stage[i]);
+        if (c->ring.stage_ev[i])
+            (void)hipEventDestroy(c->ring.stage_ev[i]);
     }
-    for (hipEvent_t ev : {c->tg_ready, c->ev_s3sync, c->ev_fb})
+    for (hipEvent_t ev : {c->ring.ready, c->ring.ev_s3sync, c->ev_fb})
         if (ev)
             (void)hipEventDestroy(ev);
     if (c->stream3)
@@ -1470,6 +1477,631 @@ int ibdg_get_windows(ibdg_ctx *c, uint32_t *first, uint32_t *last, uint32_t *n_c
     return 0;
 }
 
+}  // extern "C"
+
+namespace {        // ibdg_run's stages
+
+using Ring = ibdg_ctx::Ring;
+
+// slot i of a buffer cut into n equal slots, each a multiple of `align` bytes (the per-individual ring, ibdg_ctx::Ring)
+template <class P>
+P *ring_slot(const DevBuf &b, int i, int n, size_t align = sizeof(P))
+{
+    return (P *)((char *)b.p + (size_t)i * (b.cap / n / align * align));
+}
+
+// The other streams join stream3's preparation of the run's individuals: once, before the first thing that reads it, or at
+// the next run's entry when a run failed after it had queued its preparation.
+int ring_settle(ibdg_ctx *c)
+{
+    Ring &R = c->ring;
+    if (!R.unsettled) return 0;
+    R.unsettled = false;
+    HIP_TRY(c, hipEventRecord(R.ready, c->stream3));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, R.ready, 0));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream2, R.ready, 0));
+    return 0;
+}
+
+// New comparison individuals into the next slot of the ring (slot 0 for more than AHEAD_MAX_T of them): their indices and
+// k_target_weights' weights / background sizes, on stream3 in a queue of runs (ring_settle hands them over), else the main stream.
+int ring_prepare(ibdg_ctx *c, const uint32_t *targets, size_t T, size_t lanes)
+{
+    Ring &R = c->ring;
+    const bool ahead = T <= Ring::AHEAD_MAX_T;
+    if (ensure(c, c->weight, (ahead ? Ring::SLOTS : 1) * T * lanes * 8) || ensure(c, c->nrefpanel, Ring::NREF_SLOTS * T * 8))       // (per slot: T background sizes, T individuals)
+        return 1;
+    // more than a few individuals: a page-locked slot for the indices (so that the copy is a queued one), grown when a run
+    // brings more of them; up to IBDG_TG_INLINE of them travel in the weights kernel's arguments instead
+    const bool inline_tg = T <= IBDG_TG_INLINE;
+    int st = -1;
+    if (!inline_tg) {
+        if (R.stage_cap < T) {
+            if (quiesce(c)) return 1;
+            const size_t cap = std::max<size_t>(64, T);
+            for (int i = 0; i < Ring::STAGE_SLOTS; ++i) {
+                if (R.stage[i])
+                    (void)hipHostFree(R.stage[i]);
+                R.stage[i] = nullptr;
+                HIP_TRY(c, hipHostMalloc((void **)&R.stage[i], cap * 4, hipHostMallocDefault));
+                if (!R.stage_ev[i])
+                    HIP_TRY(c, hipEventCreateWithFlags(&R.stage_ev[i], hipEventDisableTiming));
+            }
+            R.stage_cap = cap;
+        }
+        st = R.stage_next;
+        R.stage_next = (st + 1) % Ring::STAGE_SLOTS;
+        HIP_TRY(c, hipEventSynchronize(R.stage_ev[st]));      // (its copy was queued STAGE_SLOTS runs ago; never recorded: no wait)
+        std::copy(targets, targets + T, R.stage[st]);
+    }
+    const bool on_s3 = ahead && c->opt_prep_ahead && c->opt_async;
+    const hipStream_t ps = on_s3 ? c->stream3 : c->stream;
+    if (on_s3)
+        R.unsettled = true;
+    // whoever still reads the ring slot this run's data go to (ring_mark_readers): the run four new individuals back, long
+    // done (on the main stream the readers there are ahead of the preparation anyway)
+    const int rs = ahead ? (R.cur + 1) % Ring::SLOTS : 0;
+    for (int h = ahead ? rs : 0; h <= (ahead ? rs : Ring::SLOTS - 1); ++h) {
+        if (R.main_pending[h] && on_s3)
+            HIP_TRY(c, hipStreamWaitEvent(ps, R.main_read[h], 0));
+        if (R.s2_pending[h])
+            HIP_TRY(c, hipStreamWaitEvent(ps, R.s2_read[h], 0));
+        R.main_pending[h] = R.s2_pending[h] = false;
+    }
+    R.cur = rs;
+    R.nref = (R.nref + 1) % Ring::NREF_SLOTS;
+    uint32_t *d_tg = ring_slot<uint32_t>(c->targets, R.cur, Ring::SLOTS);
+    if (!inline_tg) {
+        HIP_TRY(c, hipMemcpyAsync(d_tg, R.stage[st], T * 4, hipMemcpyHostToDevice, ps));
+        HIP_TRY(c, hipEventRecord(R.stage_ev[st], ps));
+    }
+    ibdg::launch_target_weights((const double *)c->base_w.p, d_tg, inline_tg ? targets : nullptr, (uint32_t)T, (uint32_t)lanes,
+                                c->base_sum, ring_slot<double>(c->weight, R.cur, Ring::SLOTS),
+                                ring_slot<int>(c->nrefpanel, R.nref, Ring::NREF_SLOTS), ps);
+    if (!on_s3) {
+        // prepared on the main stream (more than AHEAD_MAX_T individuals, "prep_ahead" 0, no queue): the second stream reads
+        // the individuals' indices too (k_rows_windows, k_row_table) and, in a queue of runs, starts behind the PREVIOUS
+        // run's end only -- it must not overtake this copy / kernel
+        HIP_TRY(c, hipEventRecord(R.ready, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream2, R.ready, 0));
+    }
+    c->prev_targets.assign(targets, targets + T);
+    c->wt_key.gen = 0;         // the images in wtarget / twords are another individual's
+    return 0;
+}
+
+// Who reads this run's slot -- every slot where the run used the buffers whole: the end of its launches on the main stream
+// and stream2's last kernel (null: stream2 was not used).  ring_prepare waits for them before it writes the slot again.
+void ring_mark_readers(ibdg_ctx *c, size_t T, hipEvent_t main_end, hipEvent_t s2_end)
+{
+    Ring &R = c->ring;
+    const bool ahead = T <= Ring::AHEAD_MAX_T;
+    for (int h = ahead ? R.cur : 0; h <= (ahead ? R.cur : Ring::SLOTS - 1); ++h) {
+        R.main_read[h] = main_end; R.main_pending[h] = true;
+        if (s2_end) { R.s2_read[h] = s2_end; R.s2_pending[h] = true; }
+    }
+}
+
+// background multiplicity per individual without any comparison individual's own exclusion; the -N sample contributes
+// nothing (src/ibdgem.c:714, :742-750).  Rare (once per program run): a host wait is fine here.
+int set_background(ibdg_ctx *c, const uint8_t *bg_count, int pu_id, size_t lanes)
+{
+    std::vector<double> wb(lanes, 0.0);
+    int sum = 0;
+    for (unsigned n = 0; n < c->n_ids; ++n) {
+        const unsigned k = bg_count ? bg_count[n] : 1u;
+        if ((int)n != pu_id && k != 0) {
+            wb[n] = (double)k;
+            sum += (int)k;
+        }
+    }
+    if (ensure(c, c->base_w, lanes * 8)) return 1;
+    HIP_TRY(c, hipMemcpyAsync(c->base_w.p, wb.data(), lanes * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));          // the host vector goes out of scope
+    c->chain_ok = false;
+    ++c->bg_gen;
+    c->base_sum = sum;
+    c->prev_pu = pu_id; c->prev_has_bg = bg_count ? 1 : 0; c->prev_lanes = lanes;
+    c->prev_bg.assign(bg_count, bg_count + (bg_count ? c->n_ids : 0));
+    return 0;
+}
+
+// Comparison individuals over one site list (the site list belongs to the pileup, not to the comparison individual:
+// src/ibdgem.c:522 loops the individuals over the same rows): the compacted tiles' one-off gather is paid back by the fewer
+// segments every later run counts.  The runs on an upload add up -- one run of 256 individuals, nine batches of 30, or
+// sixteen runs of one individual through the counting kernel all reach the point where the re-layout has paid for itself
+// (a rent-or-buy rule: never more than twice the cost of having known the number of runs beforehand).
+// (a group of the matrix-core kernel costs the same whether it holds 3 or IBDG_TG individuals)
+// (round 5: on the site list's rows back to back -- no padding, no rows without reads -- the counting kernel with its sums
+// on the matrix cores takes 0.548 ms where the panel's own tiles take 0.606 and round 4's window-aligned tiles took
+// 0.58-0.59, profiles/r05_layouts.txt: a single run saves 0.058 ms of the 1.3 ms the gather and the new segments
+// cost, i.e. 22 runs pay for them -- an individual counts as 12; with (mask, count) pairs, option mx_counts 0, as 16)
+// (a group of the matrix-core kernel saves 0.085 ms of 2.2 on the rows back to back -- 8.90 against 8.57 ms per 60 individuals,
+// `many_comparison_individuals` of the bench's detail file, since the launch's groups share the tile words through an
+// XCD's L2 --, i.e. fifteen groups pay for the re-layout: a group counts as 20; 45 earlier in round 5, when a group saved
+// 0.18 ms, 15 until round 5)
+int relayout_when_paid(ibdg_ctx *c, size_t T)
+{
+    if (!(c->pop_lut_ok && c->pop_sites_ok && !c->compact && c->opt_compact == 0 && c->opt_variant != 1 &&
+          c->opt_variant != 3 && c->pop_dense_enough))
+        return 0;
+    const bool to_mfma = c->opt_mfma_targets && c->tab_in_lds && T >= (size_t)c->opt_mfma_min;
+    c->relayout_credit += to_mfma ? (uint64_t)((T + IBDG_TG - 1) / IBDG_TG) * 20u : (uint64_t)T * (c->opt_mx_counts ? 12u : 16u);
+    if (c->relayout_credit >= (uint64_t)std::max<long>(1, c->opt_compact_targets)) {
+        if (quiesce(c)) return 1;
+        if (build_segments(c, true)) return 1;
+        if (!c->pop_sites_ok && build_segments(c, false)) return 1;     // (cannot happen: it applied a moment ago)
+    }
+    return 0;
+}
+
+// What a run does, decided on the host after the relayout and before its first launch (plan_run)
+struct RunPlan {
+    size_t T = 0, lanes = 0;
+    bool ld = false, use_pop = false;   // --LD; through the exponent-counting kernels (else the strict ones)
+    int variant = 0, count_unit = 0;    // what ibdg_last_ld_variant / ibdg_last_count_unit report
+    bool recount = false, rows_on_main = false, dispatch_events = false, rt_build = false;
+    // the individuals: [0, T_g) in n_gg groups of IBDG_TG through k_ld_mfma (gg_batch groups per launch), the T_cnt of
+    // [T_g, T) through the counting kernels: n_grp groups of MT in k_ld_popcount_mt, then T_one one per workgroup
+    size_t MT = 0, n_gg = 0, T_g = 0, gg_batch = 0, T_cnt = 0, n_grp = 0, T_one = 0;
+    bool mfma_wg_sum = false;
+    size_t ph_group = 0, part_bytes = 0;    // one k_ld_mfma group's partial sums; a half of `partial`
+    int mx_counts = 0;
+    long rho_shift = 0;
+    bool ibd1 = false, ibd0_pass = false, fin_in_next = false, end_in_dispatch = false;
+    bool side_fast = false;             // stream2's kernels in their fast forms (beside k_ld_mfma)
+    unsigned row_blocks = 0;            // workgroups of stream2's k_rows_windows (0: its full grid)
+};
+
+// The run's plan.  No HIP calls; the one state it changes is ibd0_runs, which counts runs across calls.
+int plan_run(ibdg_ctx *c, size_t T, size_t lanes, int ld_mode, bool row_table, RunPlan &P)
+{
+    P.T = T; P.lanes = lanes; P.ld = ld_mode != 0;
+    P.rt_build = row_table && c->rt_gen != c->up_gen;
+    if (ld_mode) {
+        const bool can = c->pop_lut_ok && c->pop_sites_ok && (c->compact ? c->t32c.p : c->t32.p);
+        if (c->opt_variant == 2 && !can)
+            return fail(c, "[::] ERROR in ibdg_run: ld_variant 2 (exponent counting) is not applicable here "
+                           "(clamped P(D|G) table, epsilon outside (0,1), max_cov > 50 or rows out of order)");
+        P.use_pop = can && c->opt_variant != 1 && c->opt_variant != 3 && (c->opt_variant == 2 || c->pop_dense_enough);
+    }
+    P.variant = ld_mode ? (P.use_pop ? 2 : (c->opt_variant == 3 ? 3 : 1)) : 0;
+    P.recount = c->opt_count_in_run || !c->counts_valid;
+    // a non-LD run is one kernel: it goes to the main stream (no second stream to start, wait for and join)
+    P.rows_on_main = !ld_mode && !P.recount;
+    P.dispatch_events = P.use_pop && c->opt_dispatch_events && c->n_win > 0;
+    if (P.use_pop) {
+        // Comparison individuals in groups of MT share one workgroup (and the counts that do not
+        // depend on them) in k_ld_popcount_mt; what is left over goes one per workgroup.
+        P.MT = (size_t)ibdg::ld_popcount_mt_width();
+        const bool mt_fits = ibdg::ld_popcount_lds_bytes(c->max_seg, c->wpg, c->ct_max + 1, c->tab_in_lds, c->seg_ring,
+                                                         1) <= 150 * 1024;
+        // Five or more comparison individuals: groups of IBDG_TG through the matrix cores (k_ld_mfma); the
+        // last group may be short, fewer than mfma_min individuals take the counting kernels below.
+        // (one group's partial sums and operands must stay modest: tiny windows over millions of rows go the old way)
+        // (a group's partial sums: 16 doubles per window and half chunk -- per group of eight half chunks where the kernel's
+        //  workgroups add their waves' sums up themselves, MfmaArgs::wg_sum)
+        P.mfma_wg_sum = c->opt_mfma_wg_sum && ibdg::ld_mfma_wg_sum(c->wpg, c->ct_max + 1, c->max_seg);
+        P.ph_group = (size_t)c->n_win * (P.mfma_wg_sum ? (size_t)((2 * c->n_chunks + 7) / 8) * 128 : (size_t)c->n_chunks * 2 * 128) + 128;
+        const size_t group_bytes = P.ph_group + (size_t)c->n_segs * 1024 + (size_t)c->n_win * 512;
+        if (c->opt_mfma_targets && c->tab_in_lds && !P.dispatch_events && T >= (size_t)c->opt_mfma_min && (c->compact ? c->n_pairs_c : c->n_pairs) < (1u << 21) && c->n_segs < (1u << 21) &&     // (32-bit byte offsets of its buffer loads)
+            group_bytes <= ((size_t)4 << 30) &&
+            ibdg::ld_mfma_lds_bytes(c->wpg, c->ct_max + 1, c->max_seg) <= 64 * 1024) {
+            P.n_gg = T / IBDG_TG + (T % IBDG_TG >= (size_t)c->opt_mfma_min);
+            P.T_g = std::min(P.n_gg * IBDG_TG, T);
+        }
+        P.T_cnt = T - P.T_g;
+        P.n_grp = (c->opt_multi_target && mt_fits && P.T_cnt >= P.MT) ? P.T_cnt / P.MT : 0;
+        P.T_one = P.T_cnt - P.n_grp * P.MT;
+        // target operands (1 KiB per segment and group) and partial sums (32 B per window, chunk and individual)
+        // exist for one batch of groups at a time: about 1 GiB of operands, eight groups at most
+        // (option "mfma_batch_groups": at most that many groups per launch, within 1/16 of the device's memory for each of
+        //  the two buffers)
+        const size_t mem_cap = std::max<size_t>((size_t)1 << 30, c->dev_mem_bytes / 16);
+        const size_t fit = std::min(c->n_segs ? mem_cap / ((size_t)c->n_segs * 1024) : P.n_gg, mem_cap / P.ph_group);
+        P.gg_batch = std::min({std::max<size_t>(fit, 1), (size_t)std::max<long>(1, c->opt_mfma_batch), P.n_gg});
+        // one comparison individual per workgroup: the counts of a haplotype word on the matrix cores where the larger
+        // records leave the run's LDS image within reach (option "mx_counts")
+        // ... and its power tables in LDS are plain doubles, rho^n as rho^n 2^(s n): s = the integer nearest to -log2 rho keeps
+        // every entry, and every product of a rho and a sigma entry whose exponents add up to a window's reads, a normal number
+        const double log2_rho = std::log2(c->eps / (1 - c->eps)), log2_sigma = std::log2(0.5 / (1 - c->eps));
+        // (8 where the table allows it: the window end then makes the exponent up with one subtraction)
+        const bool shift8 = (double)(c->ct_max + 1) * std::max(std::fabs(log2_rho + 8.0), std::fabs(log2_sigma)) <= 1000.0;
+        P.rho_shift = shift8 ? 8 : std::lround(-log2_rho);
+        const double per_read = std::max(std::fabs(log2_rho + (double)P.rho_shift), std::fabs(log2_sigma));
+        P.mx_counts = c->opt_mx_counts && P.rho_shift >= 0 && P.rho_shift <= 40 &&
+                      (!c->tab_in_lds || (double)(c->ct_max + 1) * per_read <= 1000.0) &&
+                      ibdg::ld_popcount_lds_bytes(c->max_seg, c->wpg, c->ct_max + 1, c->tab_in_lds, c->seg_ring, 2) <= 150 * 1024;
+        P.part_bytes = T * (size_t)c->n_win * c->n_chunks * 16;
+        // single individuals in the IBD1 form (counts on the matrix cores, tables in LDS): at once where the IBD0 pass exists,
+        // otherwise when the runs on this upload and background have added up
+        const bool p2_stale = c->p2_gen != c->sites_gen || c->p2_bg_gen != c->bg_gen || c->p2_mx != P.mx_counts;
+        if (P.T_one && P.mx_counts && c->tab_in_lds && c->opt_ibd0_after > 0) {
+            if (c->ibd0_bg_gen != c->bg_gen) {
+                c->ibd0_bg_gen = c->bg_gen;
+                c->ibd0_runs = 0;
+            }
+            c->ibd0_runs += P.T_one;
+            P.ibd1 = !p2_stale || (P.n_gg > 0) || c->ibd0_runs >= (uint64_t)c->opt_ibd0_after;
+        }
+        P.ibd0_pass = p2_stale && (P.n_gg > 0 || P.ibd1);
+        P.fin_in_next = c->opt_fin_next && c->opt_async && P.T_one > 0 && P.T_one == P.T_cnt && P.n_gg == 0;
+        // (option "end_in_dispatch": the run's end event is the --LD kernel's own completion signal -- no event packet
+        // of its own behind the kernel -- where that kernel is the run's last launch on the main stream)
+        P.end_in_dispatch = c->opt_end_in_dispatch && P.fin_in_next && !P.dispatch_events && P.T_one == T;
+        P.count_unit = P.T_one ? (P.mx_counts ? (P.ibd1 ? 3 : 2) : 1) : 0;
+        // k_ld_mfma (4 waves per SIMD) leaves wave slots to the second stream: its kernels run in their fast forms
+        // (also with a few individuals left to the counting kernels: T = 16 5.5 ms against 6.0; beside
+        // k_ld_popcount_mt alone it makes no difference)
+        P.side_fast = P.n_gg > 0;
+    }
+    // stream2's per-row values and window products, one launch (k_rows_windows).  Beside the exponent-counting --LD
+    // kernel, which holds every wave slot, it gets few long-lived workgroups (opt_site_blocks per CU, shared among
+    // the targets): its gathers wait on memory either way, and the --LD workgroups keep their wave slots
+    // (not when the alt counts are recounted in this run: the second stream's chain count -> rows is then the
+    // longer one of the two, and its kernels should be short; and not beside the matrix-core kernel, which leaves
+    // half of the wave slots free)
+    if (ld_mode && !P.recount && !P.side_fast && c->opt_site_blocks > 0)
+        P.row_blocks = std::max<unsigned>(1u, (unsigned)((size_t)c->n_cu * c->opt_site_blocks / T));
+    return 0;
+}
+
+// Two streams: the per-site kernel and the window products (memory-bound, few waves) run on stream2 beside the --LD
+// kernels (VALU-bound) on the main stream.  stream2 starts a run when the main stream does (a wait in stream2's queue
+// costs the main stream nothing; it also orders stream2 behind an upload of new targets); the main stream waits for
+// stream2 when somebody needs the results (join_streams), not once per run.
+// Timing: normally one event record per run on the main stream (a queued run takes the previous run's end as its start).
+// With the option "dispatch_events" the exponent-counting launches carry events in their own dispatch packets instead
+// (hipExtLaunchKernel: start of the first, stop of the last, and both of the dominant kernel -- the only way to time that
+// kernel alone from inside the process).
+// A finalising step flushed by this run (`flushed`) writes LIBD0 / LIBD1 of the rows a non-LD run's stream2 writes too: the
+// previous run's end lies before that step, so it cannot be the start stream2 waits for.  (Steady queues never flush.)
+int start_run(ibdg_ctx *c, const RunPlan &P, ibdg_ctx::EvSet &E, bool flushed)
+{
+    E.recount = P.recount; E.ld = P.ld; E.rows_on_main = P.rows_on_main; E.has_kernel_times = P.dispatch_events;
+    const bool chained = c->chain_ok && c->opt_async;
+    if (P.dispatch_events) {                       // (an --LD run: its stream2 writes no entry the step writes)
+        E.start = E.start_own;                     // filled in by the first --LD dispatch
+        if (chained)                               // stream2 keeps one run behind the main stream at most
+            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->evs[c->ev_head].ld_end, 0));
+        return 0;
+    }
+    if (chained && !flushed) {
+        E.start = c->evs[c->ev_head].ld_end;       // back-to-back runs: the previous end is this start
+    } else {
+        HIP_TRY(c, hipEventRecord(E.start_own, c->stream));
+        E.start = E.start_own;
+    }
+    if (!P.rows_on_main)
+        HIP_TRY(c, hipStreamWaitEvent(c->stream2, E.start, 0));
+    return 0;
+}
+
+ibdg::RowsArgs rows_args(const ibdg_ctx *c, int ld_mode, bool row_table)
+{
+    ibdg::RowsArgs sa{};
+    sa.panel = (const uint64_t *)c->panel.p; sa.stride = c->stride; sa.n_ids = c->n_ids;
+    sa.rec_all = (const uint2 *)c->rec_all.p; sa.n_sites = c->n_sites;
+    sa.lut = (const double *)c->lut.p; sa.alt_count = (const uint32_t *)c->alt_count.p; sa.pow_tab = (const double *)c->pow_tab.p;
+    sa.fo = c->have_fo ? (const double *)c->fo.p : nullptr;
+    sa.targets = ring_slot<const uint32_t>(c->targets, c->ring.cur, Ring::SLOTS);
+    sa.t32 = c->pop_lut_ok ? (const uint4 *)c->t32.p : nullptr; sa.n_pairs = c->n_pairs;
+    sa.cov_site = (const uint32_t *)c->cov_site.p; sa.rec_cov = (const uint2 *)c->rec_cov.p; sa.n_cov = c->n_cov;
+    sa.window = c->window; sa.n_win = c->n_win; sa.ld_mode = ld_mode ? 1 : 0;
+    sa.site_ll = c->opt_site_results && !row_table ? (double *)c->site_ll.p : nullptr;
+    sa.win_ll = (double *)c->win_ll.p;
+    return sa;
+}
+
+// The counting kernels' arguments, made once per run; the stages copy and adjust them.
+ibdg::PopArgs pop_args(const ibdg_ctx *c, const RunPlan &P)
+{
+    const Ring &R = c->ring;
+    ibdg::PopArgs pa;
+    pa.t32 = (const uint32_t *)(c->compact ? c->t32c.p : c->t32.p); pa.n_pairs = c->compact ? c->n_pairs_c : c->n_pairs;
+    pa.n_chunks = c->n_chunks;
+    pa.segs = (const ibdg::Seg *)c->segs.p; pa.n_segs = c->n_segs; pa.max_seg = c->max_seg;
+    pa.wconst = (const ibdg::WinConst *)c->wconst.p; pa.n_win = c->n_win; pa.win_per_group = c->wpg;
+    pa.run_begin = (const uint32_t *)c->runs.p; pa.n_runs = c->n_runs;
+    pa.n_cgroups = (c->n_chunks + 7) / 8;
+    pa.waves_per_group = (c->n_chunks + pa.n_cgroups - 1) / pa.n_cgroups;   // 40 chunks: 5 x 8; 9: 5 + 4; 2: 1 x 2
+    pa.rec_ready = ring_slot<const uint32_t>(c->twords, R.cur, Ring::SLOTS, 16);
+    pa.wc_ready = ring_slot<const uint32_t>(c->wtarget, R.cur, Ring::SLOTS, 16);
+    pa.pow_1me = (const ibdg::PowEntry *)c->pow1.p; pa.pow_eps = (const ibdg::PowEntry *)c->pow2.p;
+    pa.targets = ring_slot<const uint32_t>(c->targets, R.cur, Ring::SLOTS); pa.t_base = (uint32_t)P.T_g;
+    pa.weight = ring_slot<const double>(c->weight, R.cur, Ring::SLOTS); pa.lanes = (uint32_t)P.lanes;
+    pa.partial = (double *)((char *)c->partial.p + (P.fin_in_next ? (size_t)c->fin.half * P.part_bytes : 0));
+    pa.ring_slots = (uint32_t)c->seg_ring; pa.tab_len = c->ct_max + 1; pa.tab_in_lds = (uint32_t)c->tab_in_lds;
+    pa.mx_counts = (uint32_t)P.mx_counts; pa.rho_shift = (uint32_t)P.rho_shift; pa.sum_dpp = (uint32_t)c->opt_sum_dpp;
+    return pa;
+}
+
+// k_ld_mfma's arguments: the counting kernels' site list, windows, tables and individuals, and its own operands and sums
+ibdg::MfmaArgs mfma_args(const ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa)
+{
+    ibdg::MfmaArgs ma;
+    ma.t32 = pa.t32; ma.n_pairs = pa.n_pairs; ma.n_chunks = pa.n_chunks;
+    ma.segs = pa.segs; ma.n_segs = pa.n_segs; ma.max_seg = pa.max_seg;
+    ma.wconst = pa.wconst; ma.n_win = pa.n_win; ma.run_begin = pa.run_begin; ma.n_runs = pa.n_runs; ma.win_per_group = pa.win_per_group;
+    ma.pow_1me = pa.pow_1me; ma.pow_eps = pa.pow_eps; ma.pow_tau = (const ibdg::PowEntry *)c->pow3.p; ma.tab_len = pa.tab_len;
+    ma.plain_tau = c->opt_mfma_plain_tau ? 1u : 0u;
+    ma.targets = pa.targets; ma.lanes = pa.lanes; ma.base_weight = (const double *)c->base_w.p;
+    ma.p2w = (const double *)c->p2w.p; ma.p2c = (const double *)c->p2c.p;
+    ma.aimg = (uint4 *)c->aimg.p; ma.wc_slot = (uint4 *)c->wc_slot.p;
+    // one batch's partial sums: t1 [groups][windows][half chunks][16], t0 [groups][windows][half chunks], ov [groups][windows][16]
+    ma.part_t1 = (double *)c->partial_h.p; ma.wg_sum = P.mfma_wg_sum ? 1u : 0u;
+    return ma;
+}
+
+// The IBD0 terms of this site list and background, once: a pass of the counting kernel that keeps every lane's weighted
+// product (p2_out) and its sums per chunk; the images it reads are those of the run's first individual.  (A finalising
+// step left by the run before has been flushed: the pass rewrites the sums it reads.)
+int ibd0_pass(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa)
+{
+    if (ring_settle(c)) return 1;
+    if (ensure(c, c->p2w, (size_t)c->n_win * P.lanes * 8) || ensure(c, c->p2c, (size_t)c->n_win * c->n_chunks * 16) ||
+        ensure(c, c->p2_tw, (size_t)c->n_segs * ibdg::ld_popcount_rec_bytes(P.mx_counts)) ||
+        ensure(c, c->p2_wt, (size_t)c->n_win * 32))
+        return 1;
+    ibdg::PopArgs pp = pa;
+    pp.rec_ready = (const uint32_t *)c->p2_tw.p; pp.wc_ready = (const uint32_t *)c->p2_wt.p;
+    pp.weight = (const double *)c->base_w.p; pp.t_base = 0;
+    pp.partial = (double *)c->p2c.p; pp.p2_out = (double *)c->p2w.p;
+    ibdg::launch_win_target(pp, 1, c->stream);
+    if (ibdg::launch_ld_popcount(pp, 1, c->planes, c->stream))
+        return fail(c, "[::] ERROR in ibdg_run: unsupported number of weight bit-planes %d", c->planes);
+    c->p2_gen = c->sites_gen; c->p2_bg_gen = c->bg_gen; c->p2_mx = P.mx_counts;
+    return 0;
+}
+
+// groups of IBDG_TG individuals through the matrix cores (k_ld_mfma), gg_batch groups per launch
+int launch_mfma_groups(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa, ibdg_ctx::EvSet &E)
+{
+    if (ring_settle(c)) return 1;
+    ibdg::MfmaArgs ma = mfma_args(c, P, pa);
+    const int *d_nref = ring_slot<const int>(c->nrefpanel, c->ring.nref, Ring::NREF_SLOTS);
+    for (size_t g0 = 0; g0 < P.n_gg; g0 += P.gg_batch) {
+        const size_t nb = std::min(P.n_gg - g0, P.gg_batch);
+        ma.t_base = (uint32_t)(g0 * IBDG_TG);
+        ma.n_targets = (uint32_t)std::min(P.T_g - g0 * IBDG_TG, nb * IBDG_TG);
+        ibdg::launch_win_target_g(ma, (unsigned)nb, c->stream);
+        // the second stream (per-site values, window products; high priority) starts behind these
+        // two short kernels rather than beside them: it starved them (0.57 ms instead of 0.06)
+        if (g0 == 0)
+            HIP_TRY(c, hipEventRecord(E.prep, c->stream));
+        if (ibdg::launch_ld_mfma(ma, (unsigned)nb, c->stream, ibdg::KernelEvents()))
+            return fail(c, "[::] ERROR in ibdg_run: the matrix-core --LD kernel could not be launched");
+        ibdg::launch_ld_finalize_g(ma, (unsigned)nb, d_nref, (double *)c->win_ll.p, c->stream);
+    }
+    return 0;
+}
+
+// groups of MT individuals sharing a workgroup (k_ld_popcount_mt); `first` goes to the first launch and is used up
+int launch_mt_groups(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa, ibdg::KernelEvents &first,
+                     ibdg::KernelEvents dominant)
+{
+    if (ring_settle(c)) return 1;
+    ibdg::PopArgs pm = pa;
+    pm.mx_counts = 0;
+    pm.rec_ready = (const uint32_t *)c->twords_mt.p; pm.wc_ready = (const uint32_t *)c->wtarget_mt.p;
+    ibdg::launch_win_target_mt(pm, (unsigned)P.n_grp, c->stream, first);
+    first = ibdg::KernelEvents();
+    if (ibdg::launch_ld_popcount_mt(pm, (unsigned)P.n_grp, c->stream, P.T_one ? ibdg::KernelEvents() : dominant))
+        return fail(c, "[::] ERROR in ibdg_run: the multi-target --LD kernel could not be launched");
+    return 0;
+}
+
+// the single individuals [T_g + n_grp MT, T), one per workgroup (k_ld_popcount), with their images (k_win_target)
+int launch_singles(ibdg_ctx *c, const RunPlan &P, ibdg::PopArgs pa, ibdg::KernelEvents first, ibdg::KernelEvents dominant,
+                   bool same_inputs, ibdg_ctx::EvSet &E)
+{
+    Ring &R = c->ring;
+    pa.t_base = (uint32_t)(P.T_g + P.n_grp * P.MT);
+    pa.ibd1 = P.ibd1 ? 1u : 0u;
+    // (skipped when the previous run made the very same images: same prepared sites, same comparison individuals --
+    // a caller that runs a comparison again, e.g. timed steps: one launch of ~10 us less per run, which on an
+    // eighth of a chromosome is a tenth of the step)
+    const ibdg_ctx::ImgKey key = {c->sites_gen, pa.t_base, (uint32_t)P.T_one, P.mx_counts, (int)P.ibd1, R.cur};
+    const bool wt_cached = same_inputs && key == c->wt_key && !P.dispatch_events;
+    // a new individual's images: on stream3 with its weights (under the --LD kernel of the run before) unless the
+    // launch carries the run's start event (dispatch_events: that belongs on the main stream)
+    const bool wt_ahead = R.unsettled && !P.dispatch_events;
+    const hipStream_t is = wt_ahead ? c->stream3 : c->stream;
+    if (!wt_ahead && ring_settle(c)) return 1;
+    if (wt_ahead && R.s3_gen != c->sites_gen) {
+        // once per upload / change of layout: stream3's kernel reads the prepared sites (segments, window constants),
+        // whose kernels were queued on the main stream
+        HIP_TRY(c, hipEventRecord(R.ev_s3sync, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream3, R.ev_s3sync, 0));
+        R.s3_gen = c->sites_gen;
+    }
+    if (P.ibd1) {
+        if (c->fb_gen != c->sites_gen) {
+            // once per site list (and layout): the three fragments per segment an individual's images select between
+            if (ensure(c, c->fragb, (size_t)c->n_segs * 72)) return 1;
+            if (!c->ev_fb)
+                HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fb, hipEventDisableTiming));
+            ibdg::launch_frag_base(pa, (uint32_t *)c->fragb.p, is);
+            HIP_TRY(c, hipEventRecord(c->ev_fb, is));
+            HIP_TRY(c, hipStreamWaitEvent(wt_ahead ? c->stream : c->stream3, c->ev_fb, 0));   // (whichever makes the next images)
+            c->fb_gen = c->sites_gen;
+        }
+        pa.frag_base = (const uint32_t *)c->fragb.p;
+    }
+    if (!wt_cached)
+        ibdg::launch_win_target(pa, (unsigned)P.T_one, is, first);
+    if (ring_settle(c)) return 1;
+    c->wt_key = key;
+    if (P.end_in_dispatch)
+        dominant.stop = E.ld_end;
+    if (ibdg::launch_ld_popcount(pa, (unsigned)P.T_one, c->planes, c->stream, dominant))
+        return fail(c, "[::] ERROR in ibdg_run: unsupported number of weight bit-planes %d", c->planes);
+    return 0;
+}
+
+// LIBD0 / LIBD1 of the counting kernels' individuals [T_g, T) from their partial sums.  Queued runs of single individuals
+// (the timed steps of a shard, a caller's loop over the same comparison): this run's finalising step -- one wave per
+// window, 5 us, but a launch of its own with its gap and the event packet behind it: a tenth of a step on an eighth of a
+// chromosome -- is left to the NEXT run's --LD launch, whose first workgroups do it on the way (the kernel boundary between
+// the two launches is all the ordering it needs), and this run's launch does the same for its predecessor.  The partial
+// sums alternate between two halves of their buffer.
+int finalise(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa, ibdg::KernelEvents last, ibdg_ctx::EvSet &E)
+{
+    if (!P.T_cnt) return 0;
+    const int *d_nref = ring_slot<const int>(c->nrefpanel, c->ring.nref, Ring::NREF_SLOTS);
+    ibdg::PopFinalArgs fa;
+    fa.wconst = pa.wconst; fa.n_win = c->n_win; fa.n_chunks = c->n_chunks;
+    fa.n_refpanel = d_nref; fa.win_ll = (double *)c->win_ll.p;
+    fa.partial = pa.partial; fa.t_base = (uint32_t)P.T_g; fa.halves = 0;
+    if (P.ibd1) {                      // (whatever kernel made an individual's IBD1 sums)
+        fa.p2c = (const double *)c->p2c.p; fa.p2w = (const double *)c->p2w.p; fa.lanes = (uint32_t)P.lanes;
+        fa.targets = (const uint32_t *)(d_nref + P.T);      // (this run's individuals, from the longer ring: k_target_weights)
+    }
+    if (!P.fin_in_next) {
+        ibdg::launch_ld_finalize(fa, (unsigned)P.T_cnt, c->stream, last);
+        return 0;
+    }
+    c->fin = {true, fa, (unsigned)P.T_cnt, c->sites_gen, c->fin.half ^ 1};
+    if (P.dispatch_events)         // (no finalising launch to carry the run's end in its dispatch packet)
+        HIP_TRY(c, hipEventRecord(E.ld_end, c->stream));
+    return 0;
+}
+
+// the exponent-counting --LD path: k_ld_mfma groups, k_ld_popcount_mt groups, single individuals, the finalising step
+int launch_pop(ibdg_ctx *c, const RunPlan &P, ibdg_ctx::EvSet &E, bool same_inputs)
+{
+    // (the single individuals' images in ring slots like the other per-individual data)
+    const size_t img_slots = P.T <= Ring::AHEAD_MAX_T ? Ring::SLOTS : 1;
+    const size_t wt_cap0 = c->wtarget.cap, tw_cap0 = c->twords.cap;
+    if (ensure(c, c->wtarget, img_slots * P.T_one * (size_t)c->n_win * 32) ||
+        ensure(c, c->twords, img_slots * P.T_one * (size_t)c->n_segs * ibdg::ld_popcount_rec_bytes(P.mx_counts)) ||
+        ensure(c, c->wtarget_mt, P.n_grp * (size_t)c->n_win * ibdg::ld_popcount_mt_wc_bytes()) ||
+        ensure(c, c->twords_mt, P.n_grp * (size_t)c->n_segs * ibdg::ld_popcount_mt_rec_bytes()) ||
+        ensure(c, c->partial, P.T_cnt ? 2 * P.part_bytes : 0) ||
+        ensure(c, c->aimg, P.gg_batch * (size_t)c->n_segs * 1024) ||
+        ensure(c, c->wc_slot, P.gg_batch * (size_t)c->n_win * 512) ||
+        ensure(c, c->partial_h, P.gg_batch * P.ph_group))
+        return 1;
+    if (c->wtarget.cap != wt_cap0 || c->twords.cap != tw_cap0)
+        c->wt_key.gen = 0;                // new buffers: no images in them
+    ibdg::PopArgs pa = pop_args(c, P);
+    if (P.ibd0_pass && ibd0_pass(c, P, pa)) return 1;
+    if (c->fin.pending) {                 // the finalising step the run before left to this run's launch
+        pa.fin_prev = c->fin.args.partial; pa.win_ll = (double *)c->win_ll.p;
+        pa.n_refpanel = c->fin.args.n_refpanel;      // (of the run that left it: its entry of the ring)
+        pa.fin_p2c = c->fin.args.p2c; pa.fin_p2w = c->fin.args.p2w;   // (non-null: that run was of the IBD1 form)
+        pa.fin_targets = c->fin.args.targets;
+        c->fin.pending = false;
+    }
+    ibdg::KernelEvents first, dominant, last;  // all null unless dispatch_events
+    if (P.dispatch_events) {
+        first.start = E.start_own; last.stop = E.ld_end;
+        dominant.start = E.k_start; dominant.stop = E.k_stop;
+    }
+    if ((P.n_gg && launch_mfma_groups(c, P, pa, E)) || (P.n_grp && launch_mt_groups(c, P, pa, first, dominant)) ||
+        (P.T_one && launch_singles(c, P, pa, first, dominant, same_inputs, E)))
+        return 1;
+    return finalise(c, P, pa, last, E);
+}
+
+// the background list in the reference's order: ibdg_set_background_order's (checked against bg_count), or every
+// individual bg_count times in the panel's order
+int background_order(ibdg_ctx *c, const uint8_t *bg_count, std::vector<uint32_t> &order)
+{
+    if (c->bg_order.empty()) {
+        for (unsigned n = 0; n < c->n_ids; ++n)
+            for (unsigned k = bg_count ? bg_count[n] : 1u; k > 0; --k)
+                order.push_back(n);
+        return 0;
+    }
+    order = c->bg_order;
+    std::vector<unsigned> cnt(c->n_ids, 0);
+    for (uint32_t n : order) {
+        if (n >= c->n_ids)
+            return fail(c, "[::] ERROR in ibdg_run: background order names individual %u of %u", n, c->n_ids);
+        cnt[n]++;
+    }
+    for (unsigned n = 0; n < c->n_ids; ++n)
+        if (cnt[n] != (bg_count ? bg_count[n] : 1u))
+            return fail(c, "[::] ERROR in ibdg_run: background order and bg_count disagree for individual %u", n);
+    return 0;
+}
+
+// the strict --LD kernels; option ld_variant 3: per comparison individual, the per-individual products of every window,
+// then serial sums over the background list in the reference's order
+int launch_strict(ibdg_ctx *c, const RunPlan &P, const uint32_t *targets, const uint8_t *bg_count, int pu_id)
+{
+    if (ring_settle(c)) return 1;
+    ibdg::LdArgs la{};
+    la.panel = (const uint64_t *)c->panel.p; la.stride = c->stride; la.n_groups = c->n_groups;
+    la.rec_cov = (const uint2 *)c->rec_cov.p; la.n_cov = c->n_cov; la.window = c->window; la.n_win = c->n_win;
+    la.lut = (const double *)c->lut.p; la.win_ll = (double *)c->win_ll.p;
+    la.targets = ring_slot<const uint32_t>(c->targets, c->ring.cur, Ring::SLOTS);
+    la.weight = ring_slot<const double>(c->weight, c->ring.cur, Ring::SLOTS);
+    la.n_refpanel = ring_slot<const int>(c->nrefpanel, c->ring.nref, Ring::NREF_SLOTS);
+    if (c->opt_variant != 3) {
+        if (ibdg::launch_ld(la, (unsigned)P.T, c->cpw, (unsigned)c->opt_waves, c->stream))
+            return fail(c, "[::] ERROR in ibdg_run: unsupported chunks_per_wave %d", c->cpw);
+        return 0;
+    }
+    std::vector<uint32_t> order;
+    if (background_order(c, bg_count, order)) return 1;
+    if (ensure(c, c->vals, (size_t)c->n_win * P.lanes * 16) || ensure(c, c->order, order.size() * 4)) return 1;
+    HIP_TRY(c, hipMemcpyAsync(c->order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // `order` is a local
+    la.vals = (double2 *)c->vals.p;
+    ibdg::OrdArgs oa;
+    oa.vals = la.vals; oa.lanes = (uint32_t)P.lanes; oa.n_win = c->n_win; oa.pu_id = pu_id;
+    oa.order = (const uint32_t *)c->order.p; oa.n_order = (uint32_t)order.size();
+    for (size_t t = 0; t < P.T; ++t) {
+        la.t_base = (uint32_t)t;
+        if (ibdg::launch_ld(la, 1, c->cpw, (unsigned)c->opt_waves, c->stream))
+            return fail(c, "[::] ERROR in ibdg_run: unsupported chunks_per_wave %d", c->cpw);
+        oa.target = targets[t];
+        oa.win_ll = (double *)c->win_ll.p + t * (size_t)c->n_win * 3;
+        ibdg::launch_ld_ordered_sum(oa, c->stream);
+    }
+    return 0;
+}
+
+// stream2's share of the run, queued after the critical path so that the --LD launches reach the device first: the
+// recount of the alt counts, the per-row values and the window products
+int queue_stream2(ibdg_ctx *c, const RunPlan &P, const ibdg::RowsArgs &sa, ibdg_ctx::EvSet &E)
+{
+    if (P.n_gg)                        // (behind the matrix-core groups' operands, launch_mfma_groups)
+        HIP_TRY(c, hipStreamWaitEvent(c->stream2, E.prep, 0));
+    HIP_TRY(c, hipEventRecord(E.s2_start, c->stream2));
+    if (P.recount) {
+        // beside the --LD kernel: few long-lived waves (opt_recount_blocks per CU), so that the recount does not
+        // take the wave slots the --LD workgroups need -- it is bound by HBM, they by instruction issue
+        ibdg::launch_alt_count((const uint64_t *)c->panel.p, c->stride, c->n_rows, (uint32_t *)c->alt_count.p,
+                               c->stream2, P.ld ? (unsigned)(c->n_cu * c->opt_recount_blocks) : 0u);
+        c->counts_valid = true;
+        HIP_TRY(c, hipEventRecord(E.s2_count, c->stream2));
+    }
+    // The site list's row table, when stale: one comparison individual's run makes it in the launch it makes anyway
+    // (its rows' values are all computed there: 32 B per row stored instead of the per-site triple's 24), a run over
+    // several with k_row_table first.  Every other --LD run takes the LIBD2 window products of the covered rows only.
+    // (stream2, behind this run's recount of the alt counts; readers: see ibdg_ctx::row_tab)
+    ibdg::RowsArgs ra = sa;
+    if (P.rt_build) {
+        ra.row_tab = (double *)c->row_tab.p;
+        if (P.T > 1) {
+            ibdg::launch_row_table(ra, c->stream2);
+            ra.row_tab = nullptr;
+        }
+    }
+    ibdg::launch_rows_windows(ra, (unsigned)P.T, c->stream2, P.row_blocks);
+    HIP_TRY(c, hipEventRecord(E.s2_end, c->stream2));
+    c->last_s2 = E.s2_end;
+    c->s2_pending = true;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
 int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_count, int pu_id, int ld_mode)
 {
     if (!c) return 1;
@@ -1489,12 +2121,11 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     // genotype picked), made once per upload; an individual's per-site table is put together when it is fetched (k_site_expand)
     const bool row_table = want_ll && ld_mode;
     const size_t rt_cap0 = c->row_tab.cap;
-    if (ensure(c, c->targets, ibdg_ctx::TG_RING * T * 4) || (want_ll && ensure(c, c->site_ll, (row_table ? 1 : T) * c->n_sites * 24)) ||
+    if (ensure(c, c->targets, Ring::SLOTS * T * 4) || (want_ll && ensure(c, c->site_ll, (row_table ? 1 : T) * c->n_sites * 24)) ||
         (row_table && ensure(c, c->row_tab, c->n_sites * 32)) || ensure(c, c->win_ll, T * (size_t)c->n_win * 24))
         return 1;
     if (c->row_tab.cap != rt_cap0)
         c->rt_gen = 0;                  // a new buffer (grown: the capacity tells, the address may be the old one): no table in it
-    const bool rt_build = row_table && c->rt_gen != c->up_gen;
     // targets / background weights change rarely between calls (a loop over windows sizes, repeated
     // timing steps): their device copies are rebuilt only when the inputs differ
     const bool same_bg = c->prev_pu == pu_id && c->prev_has_bg == (bg_count ? 1 : 0) && c->prev_lanes == lanes &&
@@ -1503,606 +2134,28 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
                          c->base_w.p;
     const bool same_inputs = same_bg && c->prev_targets.size() == T && std::equal(targets, targets + T, c->prev_targets.begin()) &&
                              c->weight.p;
-    // a finalising step left to "the next run" is taken along only by a run of the same shape over the same background and
-    // prepared sites (it reads the windows' constants and its own run's background sizes): anything else makes up for it first
-    if (c->fin_pending && (!same_bg || c->prev_targets.size() != T || !ld_mode || c->fin_sites_gen != c->sites_gen ||
-                           !c->opt_fin_next || !c->opt_async) &&
-        flush_finalize(c))
-        return 1;
-    if (!same_bg) {
-        // background multiplicity per individual without any comparison individual's own exclusion; the -N sample
-        // contributes nothing (src/ibdgem.c:714, :742-750).  Rare (once per program run): a host wait is fine here.
-        std::vector<double> wb(lanes, 0.0);
-        int sum = 0;
-        for (unsigned n = 0; n < c->n_ids; ++n) {
-            const unsigned k = bg_count ? bg_count[n] : 1u;
-            if ((int)n != pu_id && k != 0) {
-                wb[n] = (double)k;
-                sum += (int)k;
-            }
-        }
-        if (ensure(c, c->base_w, lanes * 8))
-            return 1;
-        HIP_TRY(c, hipMemcpyAsync(c->base_w.p, wb.data(), lanes * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));          // the host vector goes out of scope
-        c->chain_ok = false;
-        ++c->bg_gen;
-        c->base_sum = sum;
-        c->prev_pu = pu_id;
-        c->prev_has_bg = bg_count ? 1 : 0;
-        c->prev_lanes = lanes;
-        if (bg_count)
-            c->prev_bg.assign(bg_count, bg_count + c->n_ids);
-        else
-            c->prev_bg.clear();
-    }
-    // Runs of a few individuals keep a ring of TG_RING copies of everything that depends on the individuals, so that the NEXT
-    // run's can be made (on stream3) while the runs before still read theirs; larger runs use the buffers whole, on the main stream.
-    if (c->s3_unsettled) {          // (left by a run that failed after it had queued its preparation)
-        HIP_TRY(c, hipEventRecord(c->tg_ready, c->stream3));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->tg_ready, 0));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->tg_ready, 0));
-        c->s3_unsettled = false;
-    }
-    const bool ahead_cap = T <= ibdg_ctx::AHEAD_MAX_T;
-    bool &need_ready = c->s3_unsettled;   // stream3 holds this run's preparation: the other streams wait for tg_ready before they read it
-    hipStream_t ps = c->stream;     // where this run's per-individual preparation is queued
-    if (!same_inputs) {
-        if (ensure(c, c->weight, (ahead_cap ? ibdg_ctx::TG_RING : 1) * T * lanes * 8) || ensure(c, c->nrefpanel, ibdg_ctx::NREF_SLOTS * T * 8))       // (per slot: T background sizes, T individuals)
-            return 1;
-        // more than a few individuals: a page-locked slot for the indices (so that the copy is a queued one), grown when a run
-        // brings more of them; up to IBDG_TG_INLINE of them travel in the weights kernel's arguments instead
-        const bool inline_tg = T <= IBDG_TG_INLINE;
-        int slot = -1;
-        if (!inline_tg) {
-            if (c->tg_stage_cap < T) {
-                if (quiesce(c)) return 1;
-                const size_t cap = std::max<size_t>(64, T);
-                for (int i = 0; i < ibdg_ctx::TG_SLOTS; ++i) {
-                    if (c->tg_stage[i])
-                        (void)hipHostFree(c->tg_stage[i]);
-                    c->tg_stage[i] = nullptr;
-                    HIP_TRY(c, hipHostMalloc((void **)&c->tg_stage[i], cap * 4, hipHostMallocDefault));
-                    if (!c->tg_stage_ev[i])
-                        HIP_TRY(c, hipEventCreateWithFlags(&c->tg_stage_ev[i], hipEventDisableTiming));
-                    c->tg_stage_busy[i] = false;
-                }
-                c->tg_stage_cap = cap;
-            }
-            slot = c->tg_slot;
-            c->tg_slot = (slot + 1) % ibdg_ctx::TG_SLOTS;
-            if (c->tg_stage_busy[slot])
-                HIP_TRY(c, hipEventSynchronize(c->tg_stage_ev[slot]));      // (its copy was queued TG_SLOTS runs ago)
-            std::copy(targets, targets + T, c->tg_stage[slot]);
-        }
-        const bool on_s3 = ahead_cap && c->opt_prep_ahead && c->opt_async;
-        const int rs = ahead_cap ? (c->tg_cur + 1) % ibdg_ctx::TG_RING : 0;
-        if (on_s3) {
-            ps = c->stream3;
-            need_ready = true;
-        }
-        // whoever still reads the ring slot this run's data go to: the run four new individuals back, long done
-        for (int h = ahead_cap ? rs : 0; h <= (ahead_cap ? rs : ibdg_ctx::TG_RING - 1); ++h) {
-            if (c->tg_main_pending[h] && ps != c->stream)
-                HIP_TRY(c, hipStreamWaitEvent(ps, c->tg_main[h], 0));
-            if (c->tg_s2_pending[h])
-                HIP_TRY(c, hipStreamWaitEvent(ps, c->tg_s2[h], 0));
-            c->tg_main_pending[h] = c->tg_s2_pending[h] = false;
-        }
-        c->tg_cur = rs;
-        c->nref_slot = (c->nref_slot + 1) % ibdg_ctx::NREF_SLOTS;
-        uint32_t *d_tg = (uint32_t *)((char *)c->targets.p + (size_t)rs * (c->targets.cap / ibdg_ctx::TG_RING / 4 * 4));
-        int *d_nref = (int *)((char *)c->nrefpanel.p + (size_t)c->nref_slot * (c->nrefpanel.cap / ibdg_ctx::NREF_SLOTS / 4 * 4));
-        double *d_w = (double *)((char *)c->weight.p + (size_t)rs * (c->weight.cap / ibdg_ctx::TG_RING / 8 * 8));
-        if (!inline_tg) {
-            HIP_TRY(c, hipMemcpyAsync(d_tg, c->tg_stage[slot], T * 4, hipMemcpyHostToDevice, ps));
-            HIP_TRY(c, hipEventRecord(c->tg_stage_ev[slot], ps));
-            c->tg_stage_busy[slot] = true;
-        }
-        ibdg::launch_target_weights((const double *)c->base_w.p, d_tg, inline_tg ? targets : nullptr, (uint32_t)T, (uint32_t)lanes,
-                                    c->base_sum, d_w, d_nref, ps);
-        if (ps == c->stream) {
-            // prepared on the main stream (more than AHEAD_MAX_T individuals, "prep_ahead" 0, no queue): the second stream reads
-            // the individuals' indices too (k_rows_windows, k_row_table) and, in a queue of runs, starts behind the PREVIOUS
-            // run's end only -- it must not overtake this copy / kernel
-            HIP_TRY(c, hipEventRecord(c->tg_ready, c->stream));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->tg_ready, 0));
-        }
-        c->prev_targets.assign(targets, targets + T);
-        c->wt_gen = 0;             // the images in wtarget / twords are another individual's
-    }
-    const uint32_t *const d_targets = (const uint32_t *)((const char *)c->targets.p + (size_t)c->tg_cur * (c->targets.cap / ibdg_ctx::TG_RING / 4 * 4));
-    const int *const d_nrefpanel = (const int *)((const char *)c->nrefpanel.p +
-                                                 (size_t)c->nref_slot * (c->nrefpanel.cap / ibdg_ctx::NREF_SLOTS / 4 * 4));
-    const double *const d_weight = (const double *)((const char *)c->weight.p + (size_t)c->tg_cur * (c->weight.cap / ibdg_ctx::TG_RING / 8 * 8));
-    // the other streams join stream3's preparation (once, before the first thing that reads it)
-    auto settle_ready = [&]() -> int {
-        if (!need_ready)
-            return 0;
-        need_ready = false;
-        HIP_TRY(c, hipEventRecord(c->tg_ready, c->stream3));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->tg_ready, 0));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->tg_ready, 0));
-        return 0;
-    };
-
-    bool use_pop = false, s2_after_prep = false, side_fast = false, end_recorded = false;
-    if (ld_mode && c->pop_lut_ok && c->pop_sites_ok && !c->compact && c->opt_compact == 0 && c->opt_variant != 1 &&
-        c->opt_variant != 3 && c->pop_dense_enough) {
-        // Comparison individuals over one site list (the site list belongs to the pileup, not to the comparison
-        // individual: src/ibdgem.c:522 loops the individuals over the same rows): the compacted tiles' one-off gather
-        // is paid back by the fewer segments every later run counts.  The runs on an upload add up -- one run of
-        // 256 individuals, nine batches of 30, or sixteen runs of one individual through the counting kernel all
-        // reach the point where the re-layout has paid for itself (a rent-or-buy rule: never more than twice the
-        // cost of having known the number of runs beforehand).
-        // (a group of the matrix-core kernel costs the same whether it holds 3 or IBDG_TG individuals)
-        // (round 5: on the site list's rows back to back -- no padding, no rows without reads -- the counting kernel with its sums
-        // on the matrix cores takes 0.548 ms where the panel's own tiles take 0.606 and round 4's window-aligned tiles took
-        // 0.58-0.59, profiles/r05_layouts.txt: a single run saves 0.058 ms of the 1.3 ms the gather and the new segments
-        // cost, i.e. 22 runs pay for them -- an individual counts as 12; with (mask, count) pairs, option mx_counts 0, as 16)
-        const bool to_mfma = c->opt_mfma_targets && c->tab_in_lds && T >= (size_t)c->opt_mfma_min;
-        // (a group of the matrix-core kernel saves 0.085 ms of 2.2 on the rows back to back -- 8.90 against 8.57 ms per 60 individuals,
-        // `many_comparison_individuals` of the bench's detail file, since the launch's groups share the tile words through an
-        // XCD's L2 --, i.e. fifteen groups pay for the re-layout: a group counts as 20; 45 earlier in round 5, when a group saved
-        // 0.18 ms, 15 until round 5)
-        c->relayout_credit += to_mfma ? (uint64_t)((T + IBDG_TG - 1) / IBDG_TG) * 20u : (uint64_t)T * (c->opt_mx_counts ? 12u : 16u);
-        if (c->relayout_credit >= (uint64_t)std::max<long>(1, c->opt_compact_targets)) {
-            if (quiesce(c)) return 1;
-            if (build_segments(c, true)) return 1;
-            if (!c->pop_sites_ok && build_segments(c, false)) return 1;     // (cannot happen: it applied a moment ago)
-        }
-    }
-    if (ld_mode) {
-        const bool can = c->pop_lut_ok && c->pop_sites_ok && (c->compact ? c->t32c.p : c->t32.p);
-        if (c->opt_variant == 2 && !can)
-            return fail(c, "[::] ERROR in ibdg_run: ld_variant 2 (exponent counting) is not applicable here "
-                           "(clamped P(D|G) table, epsilon outside (0,1), max_cov > 50 or rows out of order)");
-        use_pop = can && c->opt_variant != 1 && c->opt_variant != 3 && (c->opt_variant == 2 || c->pop_dense_enough);
-    }
-    // (a finalising step left to the next run is taken along by the counting kernel only: the strict kernels write the same
-    // win_ll entries themselves, and the stale sums must not land behind them)
-    if (c->fin_pending && !use_pop && flush_finalize(c))
-        return 1;
-    c->last_variant = ld_mode ? (use_pop ? 2 : (c->opt_variant == 3 ? 3 : 1)) : 0;
-    c->last_count_unit = 0;
-    const bool recount = c->opt_count_in_run || !c->counts_valid;
+    if (!same_bg && set_background(c, bg_count, pu_id, lanes)) return 1;
+    if (ring_settle(c) || (!same_inputs && ring_prepare(c, targets, T, lanes))) return 1;   // (settles what a failed run left)
+    if (ld_mode && relayout_when_paid(c, T)) return 1;
+    RunPlan P;
+    if (plan_run(c, T, lanes, ld_mode, row_table, P)) return 1;
+    c->last_variant = P.variant;
+    c->last_count_unit = P.count_unit;
+    // A finalising step left by the run before rides in this run's k_ld_popcount launch only where this run is of the same
+    // shape over the same background and prepared sites (it reads the windows' constants and its own run's background sizes)
+    // and no IBD0 pass rewrites its sums first; the strict and non-LD kernels write the same win_ll entries themselves, and
+    // the stale sums must not land behind them.  Otherwise it is made up for here, before the run's first launch.
+    const bool flush = c->fin.pending && (!same_bg || c->fin.sites_gen != c->sites_gen || !P.use_pop || P.ibd0_pass ||
+                                          !P.fin_in_next || c->fin.count != (unsigned)P.T_cnt || c->fin.args.t_base != (uint32_t)P.T_g);
+    if (flush && flush_finalize(c)) return 1;
     const int ev_slot = (c->ev_head + 1) % ibdg_ctx::EV_RING;      // becomes the head once the run is queued
     ibdg_ctx::EvSet &E = c->evs[ev_slot];
-    E.recount = recount;
-    E.ld = ld_mode != 0;
-    // a non-LD run is one kernel: it goes to the main stream (no second stream to start, wait for and join)
-    const bool rows_on_main = !ld_mode && !recount;
-    E.rows_on_main = rows_on_main;
-    // Two streams: the per-site kernel and the window products (memory-bound, few waves) run on
-    // stream2 beside the --LD kernels (VALU-bound) on the main stream.  stream2 starts a run when
-    // the main stream does (a wait in stream2's queue costs the main stream nothing; it also orders
-    // stream2 behind an upload of new targets); the main stream waits for stream2 when somebody
-    // needs the results (join_streams), not once per run.
-    // Timing: normally one event record per run on the main stream (below).  With the option
-    // "dispatch_events" the exponent-counting launches carry events in their own dispatch packets
-    // instead (hipExtLaunchKernel: start of the first, stop of the last, and both of the dominant
-    // kernel -- the only way to time that kernel alone from inside the process).
-    const bool dispatch_events = use_pop && c->opt_dispatch_events && c->n_win > 0;
-    E.has_kernel_times = dispatch_events;
-    if (dispatch_events) {
-        E.start = E.start_own;                     // filled in by the first --LD dispatch
-        if (c->chain_ok && c->opt_async)           // stream2 keeps one run behind the main stream at most
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->evs[c->ev_head].ld_end, 0));
-    } else {
-        if (c->chain_ok && c->opt_async) {
-            E.start = c->evs[c->ev_head].ld_end;   // back-to-back runs: the previous end is this start
-        } else {
-            HIP_TRY(c, hipEventRecord(E.start_own, c->stream));
-            E.start = E.start_own;
-        }
-        if (!rows_on_main)
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, E.start, 0));
-    }
+    if (start_run(c, P, E, flush)) return 1;
 
-    ibdg::RowsArgs sa;
-    sa.panel = (const uint64_t *)c->panel.p;
-    sa.stride = c->stride;
-    sa.n_ids = c->n_ids;
-    sa.rec_all = (const uint2 *)c->rec_all.p;
-    sa.n_sites = c->n_sites;
-    sa.lut = (const double *)c->lut.p;
-    sa.alt_count = (const uint32_t *)c->alt_count.p;
-    sa.pow_tab = (const double *)c->pow_tab.p;
-    sa.fo = c->have_fo ? (const double *)c->fo.p : nullptr;
-    sa.targets = d_targets;
-    sa.t32 = c->pop_lut_ok ? (const uint4 *)c->t32.p : nullptr;
-    sa.n_pairs = c->n_pairs;
-    sa.cov_site = (const uint32_t *)c->cov_site.p;
-    sa.rec_cov = (const uint2 *)c->rec_cov.p;
-    sa.n_cov = c->n_cov;
-    sa.window = c->window;
-    sa.n_win = c->n_win;
-    sa.ld_mode = ld_mode ? 1 : 0;
-    sa.af = nullptr;
-    sa.site_ll = want_ll && !row_table ? (double *)c->site_ll.p : nullptr;
-    sa.row_tab = nullptr;
-    sa.win_ll = (double *)c->win_ll.p;
-
-    if (use_pop) {
-        // Comparison individuals in groups of MT share one workgroup (and the counts that do not
-        // depend on them) in k_ld_popcount_mt; what is left over goes one per workgroup.
-        const size_t MT = (size_t)ibdg::ld_popcount_mt_width();
-        const bool mt_fits = ibdg::ld_popcount_lds_bytes(c->max_seg, c->wpg, c->ct_max + 1, c->tab_in_lds, c->seg_ring,
-                                                         1) <= 150 * 1024;
-        // Five or more comparison individuals: groups of IBDG_TG through the matrix cores (k_ld_mfma); the
-        // last group may be short, fewer than mfma_min individuals take the counting kernels below.
-        const size_t TGs = IBDG_TG;
-        size_t n_gg = 0, T_g = 0;
-        // (one group's partial sums and operands must stay modest: tiny windows over millions of rows go the old way)
-        // (a group's partial sums: 16 doubles per window and half chunk -- per group of eight half chunks where the kernel's
-        //  workgroups add their waves' sums up themselves, MfmaArgs::wg_sum)
-        const bool mfma_wg_sum = c->opt_mfma_wg_sum && ibdg::ld_mfma_wg_sum(c->wpg, c->ct_max + 1, c->max_seg);
-        const size_t ph_group = (size_t)c->n_win * (mfma_wg_sum ? (size_t)((2 * c->n_chunks + 7) / 8) * 128 : (size_t)c->n_chunks * 2 * 128) + 128;
-        const size_t group_bytes = ph_group + (size_t)c->n_segs * 1024 + (size_t)c->n_win * 512;
-        if (c->opt_mfma_targets && c->tab_in_lds && !dispatch_events && T >= (size_t)c->opt_mfma_min && (c->compact ? c->n_pairs_c : c->n_pairs) < (1u << 21) && c->n_segs < (1u << 21) &&     // (32-bit byte offsets of its buffer loads)
-            group_bytes <= ((size_t)4 << 30) &&
-            ibdg::ld_mfma_lds_bytes(c->wpg, c->ct_max + 1, c->max_seg) <= 64 * 1024) {
-            n_gg = T / TGs;
-            T_g = n_gg * TGs;
-            if (T - T_g >= (size_t)c->opt_mfma_min) {
-                n_gg++;
-                T_g = T;
-            }
-        }
-        const size_t T_cnt = T - T_g;      // comparison individuals of the counting kernels: [T_g, T)
-        const size_t n_grp = (c->opt_multi_target && mt_fits && T_cnt >= MT) ? T_cnt / MT : 0, T_one = T_cnt - n_grp * MT;
-        // target operands (1 KiB per segment and group) and partial sums (32 B per window, chunk and individual)
-        // exist for one batch of groups at a time: about 1 GiB of operands, eight groups at most
-        size_t gg_batch = n_gg;
-        if (n_gg) {
-            // (option "mfma_batch_groups": at most that many groups per launch, within 1/16 of the device's memory for each of
-            //  the two buffers)
-            const size_t per_group = (size_t)c->n_segs * 1024;
-            const size_t mem_cap = std::max<size_t>((size_t)1 << 30, c->dev_mem_bytes / 16);
-            size_t fit = per_group ? mem_cap / per_group : n_gg;
-            const size_t fit_p = mem_cap / ph_group;     // partial sums
-            fit = fit < fit_p ? fit : fit_p;
-            const size_t cap_g = (size_t)std::max<long>(1, c->opt_mfma_batch);
-            fit = fit < 1 ? 1 : (fit > cap_g ? cap_g : fit);
-            gg_batch = fit < n_gg ? fit : n_gg;
-        }
-        // one comparison individual per workgroup: the counts of a haplotype word on the matrix cores where the larger
-        // records leave the run's LDS image within reach (option "mx_counts")
-        // ... and its power tables in LDS are plain doubles, rho^n as rho^n 2^(s n): s = the integer nearest to -log2 rho keeps
-        // every entry, and every product of a rho and a sigma entry whose exponents add up to a window's reads, a normal number
-        const double log2_rho = std::log2(c->eps / (1 - c->eps)), log2_sigma = std::log2(0.5 / (1 - c->eps));
-        // (8 where the table allows it: the window end then makes the exponent up with one subtraction)
-        const bool shift8 = (double)(c->ct_max + 1) * std::max(std::fabs(log2_rho + 8.0), std::fabs(log2_sigma)) <= 1000.0;
-        const long rho_shift = shift8 ? 8 : std::lround(-log2_rho);
-        const double per_read = std::max(std::fabs(log2_rho + (double)rho_shift), std::fabs(log2_sigma));
-        const int mx_counts = c->opt_mx_counts && rho_shift >= 0 && rho_shift <= 40 &&
-                              (!c->tab_in_lds || (double)(c->ct_max + 1) * per_read <= 1000.0) &&
-                              ibdg::ld_popcount_lds_bytes(c->max_seg, c->wpg, c->ct_max + 1, c->tab_in_lds, c->seg_ring, 2) <= 150 * 1024;
-        const size_t part_bytes = T * (size_t)c->n_win * c->n_chunks * 16;       // the counting kernels' sums per chunk; two halves taken in turn
-        // (the single individuals' images in two halves like the other per-individual data, see above)
-        const size_t img_slots = ahead_cap ? ibdg_ctx::TG_RING : 1;
-        const size_t wt_cap0 = c->wtarget.cap, tw_cap0 = c->twords.cap;
-        if (ensure(c, c->wtarget, img_slots * T_one * (size_t)c->n_win * 32) ||
-            ensure(c, c->twords, img_slots * T_one * (size_t)c->n_segs * ibdg::ld_popcount_rec_bytes(mx_counts)) ||
-            ensure(c, c->wtarget_mt, n_grp * (size_t)c->n_win * ibdg::ld_popcount_mt_wc_bytes()) ||
-            ensure(c, c->twords_mt, n_grp * (size_t)c->n_segs * ibdg::ld_popcount_mt_rec_bytes()) ||
-            ensure(c, c->partial, T_cnt ? 2 * part_bytes : 0) ||
-            ensure(c, c->aimg, gg_batch * (size_t)c->n_segs * 1024) ||
-            ensure(c, c->wc_slot, gg_batch * (size_t)c->n_win * 512) ||
-            ensure(c, c->partial_h, gg_batch * ph_group))
-            return 1;
-        ibdg::PopArgs pa;
-        pa.t32 = (const uint32_t *)(c->compact ? c->t32c.p : c->t32.p);
-        pa.n_pairs = c->compact ? c->n_pairs_c : c->n_pairs;
-        pa.n_chunks = c->n_chunks;
-        pa.segs = (const ibdg::Seg *)c->segs.p;
-        pa.n_segs = c->n_segs;
-        pa.max_seg = c->max_seg;
-        if (c->wtarget.cap != wt_cap0 || c->twords.cap != tw_cap0)
-            c->wt_gen = 0;                    // new buffers: no images in them
-        pa.rec_ready = (const uint32_t *)((const char *)c->twords.p + (size_t)c->tg_cur * (c->twords.cap / ibdg_ctx::TG_RING / 16 * 16));
-        pa.wconst = (const ibdg::WinConst *)c->wconst.p;
-        pa.n_win = c->n_win;
-        pa.win_per_group = c->wpg;
-        pa.run_begin = (const uint32_t *)c->runs.p;
-        pa.n_runs = c->n_runs;
-        pa.n_cgroups = (c->n_chunks + 7) / 8;
-        pa.waves_per_group = (c->n_chunks + pa.n_cgroups - 1) / pa.n_cgroups;   // 40 chunks: 5 x 8; 9: 5 + 4; 2: 1 x 2
-        pa.wc_ready = (const uint32_t *)((const char *)c->wtarget.p + (size_t)c->tg_cur * (c->wtarget.cap / ibdg_ctx::TG_RING / 16 * 16));
-        pa.pow_1me = (const ibdg::PowEntry *)c->pow1.p;
-        pa.pow_eps = (const ibdg::PowEntry *)c->pow2.p;
-        pa.targets = sa.targets;
-        pa.t_base = (uint32_t)T_g;
-        pa.weight = d_weight;
-        pa.lanes = (uint32_t)lanes;
-        // Queued runs of single individuals (the timed steps of a shard, a caller's loop over the same comparison): this run's
-        // finalising step -- one wave per window, 5 us, but a launch of its own with its gap and the event packet behind it:
-        // a tenth of a step on an eighth of a chromosome -- is left to the NEXT run's --LD launch, whose first workgroups
-        // do it on the way (the kernel boundary between the two launches is all the ordering it needs), and this run's
-        // launch does the same for its predecessor.  The partial sums alternate between two halves of their buffer.
-        // The IBD0 terms of this site list and background, once: a pass of the counting kernel that keeps every lane's weighted
-        // product (p2_out) and its sums per chunk; the images it reads are those of the run's first individual.
-        const bool p2_stale = c->p2_gen != c->sites_gen || c->p2_bg_gen != c->bg_gen || c->p2_mx != mx_counts;
-        auto ibd0_pass = [&]() -> int {
-            if (c->fin_pending && flush_finalize(c))
-                return 1;
-            if (settle_ready())
-                return 1;
-            if (ensure(c, c->p2w, (size_t)c->n_win * lanes * 8) || ensure(c, c->p2c, (size_t)c->n_win * c->n_chunks * 16) ||
-                ensure(c, c->p2_tw, (size_t)c->n_segs * ibdg::ld_popcount_rec_bytes(mx_counts)) ||
-                ensure(c, c->p2_wt, (size_t)c->n_win * 32))
-                return 1;
-            ibdg::PopArgs pp = pa;
-            pp.rec_ready = (const uint32_t *)c->p2_tw.p;
-            pp.wc_ready = (const uint32_t *)c->p2_wt.p;
-            pp.weight = (const double *)c->base_w.p;
-            pp.t_base = 0;
-            pp.partial = (double *)c->p2c.p;
-            pp.p2_out = (double *)c->p2w.p;
-            pp.fin_prev = nullptr;
-            pp.ibd1 = 0;
-            pp.ring_slots = (uint32_t)c->seg_ring;
-            pp.tab_len = c->ct_max + 1;
-            pp.tab_in_lds = (uint32_t)c->tab_in_lds;
-            pp.mx_counts = (uint32_t)mx_counts;
-            pp.rho_shift = (uint32_t)rho_shift;
-            pp.sum_dpp = (uint32_t)c->opt_sum_dpp;
-            ibdg::launch_win_target(pp, 1, c->stream);
-            if (ibdg::launch_ld_popcount(pp, 1, c->planes, c->stream))
-                return fail(c, "[::] ERROR in ibdg_run: unsupported number of weight bit-planes %d", c->planes);
-            c->p2_gen = c->sites_gen;
-            c->p2_bg_gen = c->bg_gen;
-            c->p2_mx = mx_counts;
-            return 0;
-        };
-        // single individuals in the IBD1 form (counts on the matrix cores, tables in LDS): at once where the pass exists,
-        // otherwise when the runs on this upload and background have added up
-        bool ibd1 = false;
-        if (T_one && mx_counts && c->tab_in_lds && c->opt_ibd0_after > 0) {
-            if (c->ibd0_bg_gen != c->bg_gen) {
-                c->ibd0_bg_gen = c->bg_gen;
-                c->ibd0_runs = 0;
-            }
-            c->ibd0_runs += T_one;
-            ibd1 = !p2_stale || (n_gg > 0) || c->ibd0_runs >= (uint64_t)c->opt_ibd0_after;
-        }
-        if (p2_stale && (n_gg > 0 || ibd1) && ibd0_pass())
-            return 1;
-        const bool fin_in_next = c->opt_fin_next && c->opt_async && T_one > 0 && T_one == T_cnt && n_gg == 0;
-        if (c->fin_pending && (!fin_in_next || c->fin_count != (unsigned)T_cnt || c->fin_args.t_base != (uint32_t)T_g) &&
-            flush_finalize(c))
-            return 1;
-        pa.partial = (double *)((char *)c->partial.p + (fin_in_next ? (size_t)c->part_half * part_bytes : 0));
-        if (c->fin_pending) {
-            pa.fin_prev = c->fin_args.partial;
-            pa.n_refpanel = c->fin_args.n_refpanel;      // (of the run that left it: its entry of the ring)
-            pa.win_ll = (double *)c->win_ll.p;
-            pa.fin_p2c = c->fin_args.p2c;                // (non-null: that run was of the IBD1 form)
-            pa.fin_p2w = c->fin_args.p2w;
-            pa.fin_targets = c->fin_args.targets;
-            c->fin_pending = false;
-        }
-        pa.ring_slots = (uint32_t)c->seg_ring;
-        pa.tab_len = c->ct_max + 1;
-        pa.tab_in_lds = (uint32_t)c->tab_in_lds;
-        pa.mx_counts = (uint32_t)mx_counts;
-        pa.rho_shift = (uint32_t)rho_shift;
-        pa.sum_dpp = (uint32_t)c->opt_sum_dpp;
-        ibdg::KernelEvents first, dominant, last;  // all null unless dispatch_events
-        if (dispatch_events) {
-            first.start = E.start_own;
-            dominant.start = E.k_start;
-            dominant.stop = E.k_stop;
-            last.stop = E.ld_end;
-        }
-        if (n_gg) {
-            if (settle_ready()) return 1;
-            ibdg::MfmaArgs ma;
-            ma.t32 = pa.t32;
-            ma.n_pairs = pa.n_pairs;
-            ma.n_chunks = pa.n_chunks;
-            ma.segs = pa.segs;
-            ma.n_segs = pa.n_segs;
-            ma.wconst = pa.wconst;
-            ma.n_win = pa.n_win;
-            ma.run_begin = pa.run_begin;
-            ma.n_runs = pa.n_runs;
-            ma.win_per_group = pa.win_per_group;
-            ma.max_seg = pa.max_seg;
-            ma.aimg = (uint4 *)c->aimg.p;
-            ma.wc_slot = (uint4 *)c->wc_slot.p;
-            ma.pow_1me = pa.pow_1me;
-            ma.pow_eps = pa.pow_eps;
-            ma.pow_tau = (const ibdg::PowEntry *)c->pow3.p;
-            ma.tab_len = pa.tab_len;
-            ma.plain_tau = c->opt_mfma_plain_tau ? 1u : 0u;
-            ma.targets = pa.targets;
-            ma.base_weight = (const double *)c->base_w.p;
-            ma.p2w = (const double *)c->p2w.p;
-            ma.p2c = (const double *)c->p2c.p;
-            ma.lanes = (uint32_t)lanes;
-            ma.wg_sum = mfma_wg_sum ? 1u : 0u;
-            {
-                // one batch's partial sums: t1 [groups][windows][half chunks][16], t0 [groups][windows][half chunks], ov [groups][windows][16]
-                const size_t nh = (size_t)c->n_chunks * 2;
-                ma.part_t1 = (double *)c->partial_h.p;
-                (void)nh;
-            }
-            for (size_t g0 = 0; g0 < n_gg; g0 += gg_batch) {
-                const size_t nb = n_gg - g0 < gg_batch ? n_gg - g0 : gg_batch;
-                ma.t_base = (uint32_t)(g0 * TGs);
-                ma.n_targets = (uint32_t)((T_g - g0 * TGs) < nb * TGs ? (T_g - g0 * TGs) : nb * TGs);
-                ibdg::launch_win_target_g(ma, (unsigned)nb, c->stream);
-                if (g0 == 0) {
-                    // the second stream (per-site values, window products; high priority) starts behind these
-                    // two short kernels rather than beside them: it starved them (0.57 ms instead of 0.06)
-                    HIP_TRY(c, hipEventRecord(E.prep, c->stream));
-                    s2_after_prep = true;
-                }
-                if (ibdg::launch_ld_mfma(ma, (unsigned)nb, c->stream, ibdg::KernelEvents()))
-                    return fail(c, "[::] ERROR in ibdg_run: the matrix-core --LD kernel could not be launched");
-                ibdg::launch_ld_finalize_g(ma, (unsigned)nb, d_nrefpanel, (double *)c->win_ll.p, c->stream);
-            }
-        }
-        // k_ld_mfma (4 waves per SIMD) leaves wave slots to the second stream: its kernels run in their fast forms
-        // (also with a few individuals left to the counting kernels: T = 16 5.5 ms against 6.0; beside
-        // k_ld_popcount_mt alone it makes no difference)
-        side_fast = n_gg > 0;
-        if (n_grp) {
-            if (settle_ready()) return 1;
-            ibdg::PopArgs pm = pa;
-            pm.mx_counts = 0;
-            pm.rec_ready = (const uint32_t *)c->twords_mt.p;
-            pm.wc_ready = (const uint32_t *)c->wtarget_mt.p;
-            ibdg::launch_win_target_mt(pm, (unsigned)n_grp, c->stream, first);
-            first = ibdg::KernelEvents();
-            if (ibdg::launch_ld_popcount_mt(pm, (unsigned)n_grp, c->stream, T_one ? ibdg::KernelEvents() : dominant))
-                return fail(c, "[::] ERROR in ibdg_run: the multi-target --LD kernel could not be launched");
-        }
-        if (T_one) {
-            pa.t_base = (uint32_t)(T_g + n_grp * MT);
-            // (skipped when the previous run made the very same images: same prepared sites, same comparison individuals --
-            // a caller that runs a comparison again, e.g. timed steps: one launch of ~10 us less per run, which on an
-            // eighth of a chromosome is a tenth of the step)
-            const bool wt_cached = same_inputs && c->wt_gen == c->sites_gen && c->wt_first == pa.t_base &&
-                                   c->wt_count == (uint32_t)T_one && c->wt_mx == mx_counts && c->wt_slot == c->tg_cur &&
-                                   c->wt_ibd1 == (int)ibd1 && !dispatch_events;
-            pa.ibd1 = ibd1 ? 1u : 0u;
-            // a new individual's images: on stream3 with its weights (under the --LD kernel of the run before) unless the
-            // launch carries the run's start event (dispatch_events: that belongs on the main stream)
-            const bool wt_ahead = need_ready && !dispatch_events;
-            if (!wt_ahead && settle_ready()) return 1;
-            if (wt_ahead && c->s3_gen != c->sites_gen) {
-                // once per upload / change of layout: stream3's kernel reads the prepared sites (segments, window constants),
-                // whose kernels were queued on the main stream
-                HIP_TRY(c, hipEventRecord(c->ev_s3sync, c->stream));
-                HIP_TRY(c, hipStreamWaitEvent(c->stream3, c->ev_s3sync, 0));
-                c->s3_gen = c->sites_gen;
-            }
-            if (ibd1) {
-                if (c->fb_gen != c->sites_gen) {
-                    // once per site list (and layout): the three fragments per segment an individual's images select between
-                    if (ensure(c, c->fragb, (size_t)c->n_segs * 72))
-                        return 1;
-                    if (!c->ev_fb)
-                        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fb, hipEventDisableTiming));
-                    hipStream_t fs = wt_ahead ? c->stream3 : c->stream;
-                    ibdg::launch_frag_base(pa, (uint32_t *)c->fragb.p, fs);
-                    HIP_TRY(c, hipEventRecord(c->ev_fb, fs));
-                    HIP_TRY(c, hipStreamWaitEvent(fs == c->stream ? c->stream3 : c->stream, c->ev_fb, 0));   // (whichever makes the next images)
-                    c->fb_gen = c->sites_gen;
-                }
-                pa.frag_base = (const uint32_t *)c->fragb.p;
-            }
-            if (!wt_cached)
-                ibdg::launch_win_target(pa, (unsigned)T_one, wt_ahead ? c->stream3 : c->stream, first);
-            if (settle_ready()) return 1;
-            c->wt_slot = c->tg_cur;
-            c->wt_gen = c->sites_gen;
-            c->wt_first = pa.t_base;
-            c->wt_count = (uint32_t)T_one;
-            c->wt_mx = mx_counts;
-            c->wt_ibd1 = (int)ibd1;
-            c->last_count_unit = mx_counts ? (ibd1 ? 3 : 2) : 1;
-            // (option "end_in_dispatch": the run's end event is the --LD kernel's own completion signal -- no event packet
-            // of its own behind the kernel -- where that kernel is the run's last launch on the main stream)
-            if (c->opt_end_in_dispatch && fin_in_next && !dispatch_events && T_one == T) {
-                dominant.stop = E.ld_end;
-                end_recorded = true;
-            }
-            if (ibdg::launch_ld_popcount(pa, (unsigned)T_one, c->planes, c->stream, dominant))
-                return fail(c, "[::] ERROR in ibdg_run: unsupported number of weight bit-planes %d", c->planes);
-        }
-        ibdg::PopFinalArgs fa;
-        fa.wconst = pa.wconst;
-        fa.n_win = c->n_win;
-        fa.n_chunks = c->n_chunks;
-        fa.n_refpanel = d_nrefpanel;
-        fa.win_ll = (double *)c->win_ll.p;
-        if (T_cnt) {
-            fa.partial = pa.partial;
-            fa.t_base = (uint32_t)T_g;
-            fa.halves = 0;
-            if (ibd1) {                      // (whatever kernel made an individual's IBD1 sums)
-                fa.p2c = (const double *)c->p2c.p;
-                fa.p2w = (const double *)c->p2w.p;
-                fa.targets = (const uint32_t *)(d_nrefpanel + T);      // (this run's individuals, from the longer ring: k_target_weights)
-                fa.lanes = (uint32_t)lanes;
-            }
-            if (fin_in_next) {
-                c->fin_pending = true;
-                c->fin_args = fa;
-                c->fin_count = (unsigned)T_cnt;
-                c->fin_sites_gen = c->sites_gen;
-                c->part_half ^= 1;
-                if (dispatch_events)         // (no finalising launch to carry the run's end in its dispatch packet)
-                    HIP_TRY(c, hipEventRecord(E.ld_end, c->stream));
-            } else {
-                ibdg::launch_ld_finalize(fa, (unsigned)T_cnt, c->stream, last);
-            }
-        }
-    } else if (ld_mode) {
-        if (settle_ready()) return 1;
-        ibdg::LdArgs la;
-        la.panel = sa.panel;
-        la.stride = c->stride;
-        la.rec_cov = (const uint2 *)c->rec_cov.p;
-        la.n_cov = c->n_cov;
-        la.window = c->window;
-        la.n_win = c->n_win;
-        la.n_groups = c->n_groups;
-        la.lut = sa.lut;
-        la.targets = sa.targets;
-        la.weight = d_weight;
-        la.n_refpanel = d_nrefpanel;
-        la.win_ll = (double *)c->win_ll.p;
-        la.t_base = 0;
-        la.vals = nullptr;
-        if (c->opt_variant == 3) {
-            // reference order: per comparison individual, the per-individual products of every window,
-            // then serial sums over the background list in the reference's order
-            std::vector<uint32_t> order;
-            if (!c->bg_order.empty()) {
-                order = c->bg_order;               // checked against bg_count below
-                std::vector<unsigned> cnt(c->n_ids, 0);
-                for (uint32_t n : order) {
-                    if (n >= c->n_ids)
-                        return fail(c, "[::] ERROR in ibdg_run: background order names individual %u of %u", n, c->n_ids);
-                    cnt[n]++;
-                }
-                for (unsigned n = 0; n < c->n_ids; ++n)
-                    if (cnt[n] != (bg_count ? bg_count[n] : 1u))
-                        return fail(c, "[::] ERROR in ibdg_run: background order and bg_count disagree for individual %u", n);
-            } else {
-                for (unsigned n = 0; n < c->n_ids; ++n)
-                    for (unsigned k = bg_count ? bg_count[n] : 1u; k > 0; --k)
-                        order.push_back(n);
-            }
-            if (ensure(c, c->vals, (size_t)c->n_win * lanes * 16) || ensure(c, c->order, order.size() * 4))
-                return 1;
-            HIP_TRY(c, hipMemcpyAsync(c->order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));        // `order` is a local
-            la.vals = (double2 *)c->vals.p;
-            for (size_t t = 0; t < T; ++t) {
-                la.t_base = (uint32_t)t;
-                if (ibdg::launch_ld(la, 1, c->cpw, (unsigned)c->opt_waves, c->stream))
-                    return fail(c, "[::] ERROR in ibdg_run: unsupported chunks_per_wave %d", c->cpw);
-                ibdg::OrdArgs oa;
-                oa.vals = la.vals;
-                oa.lanes = (uint32_t)lanes;
-                oa.n_win = c->n_win;
-                oa.order = (const uint32_t *)c->order.p;
-                oa.n_order = (uint32_t)order.size();
-                oa.target = targets[t];
-                oa.pu_id = pu_id;
-                oa.win_ll = (double *)c->win_ll.p + t * (size_t)c->n_win * 3;
-                ibdg::launch_ld_ordered_sum(oa, c->stream);
-            }
-        } else if (ibdg::launch_ld(la, (unsigned)T, c->cpw, (unsigned)c->opt_waves, c->stream))
-            return fail(c, "[::] ERROR in ibdg_run: unsupported chunks_per_wave %d", c->cpw);
-    }
-    if (settle_ready()) return 1;
-    if (rows_on_main) {
+    const ibdg::RowsArgs sa = rows_args(c, ld_mode, row_table);
+    if (P.use_pop ? launch_pop(c, P, E, same_inputs) : ld_mode && launch_strict(c, P, targets, bg_count, pu_id)) return 1;
+    if (ring_settle(c)) return 1;
+    if (P.rows_on_main) {
         if (join_streams(c)) return 1;           // an earlier run's kernel on stream2 may still write the results
         // alone on the chip: a wave per pair of windows (the default).  A resident grid whose waves walk over several windows -- even
         // with the next window's records kept in flight -- measured slower at every size (rows_blocks_per_cu 4..28:
@@ -2112,71 +2165,16 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
             blocks = std::max<unsigned>(1u, (unsigned)((size_t)c->n_cu * c->opt_rows_blocks / T));
         ibdg::launch_rows_windows(sa, (unsigned)T, c->stream, blocks);
     }
-    if (!dispatch_events && !end_recorded)
+    if (!P.dispatch_events && !P.end_in_dispatch)
         HIP_TRY(c, hipEventRecord(E.ld_end, c->stream));
-
-    if (!rows_on_main) {
-        // stream2, queued after the critical path so that the --LD launches reach the device first
-        if (s2_after_prep)
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, E.prep, 0));
-        HIP_TRY(c, hipEventRecord(E.s2_start, c->stream2));
-        if (recount) {
-            // beside the --LD kernel: few long-lived waves (opt_recount_blocks per CU), so that the recount does not
-            // take the wave slots the --LD workgroups need -- it is bound by HBM, they by instruction issue
-            ibdg::launch_alt_count((const uint64_t *)c->panel.p, c->stride, c->n_rows, (uint32_t *)c->alt_count.p,
-                                   c->stream2, ld_mode ? (unsigned)(c->n_cu * c->opt_recount_blocks) : 0u);
-            c->counts_valid = true;
-            HIP_TRY(c, hipEventRecord(E.s2[0], c->stream2));
-        }
-        // the per-row values and the window products, one launch (k_rows_windows).  Beside the exponent-counting --LD
-        // kernel, which holds every wave slot, it gets few long-lived workgroups (opt_site_blocks per CU, shared among
-        // the targets): its gathers wait on memory either way, and the --LD workgroups keep their wave slots
-        // (not when the alt counts are recounted in this run: the second stream's chain count -> rows is then the
-        // longer one of the two, and its kernels should be short; and not beside the matrix-core kernel, which leaves
-        // half of the wave slots free)
-        const bool shadow = ld_mode && !recount && !side_fast;
-        unsigned row_blocks = 0;
-        if (shadow && c->opt_site_blocks > 0)
-            row_blocks = std::max<unsigned>(1u, (unsigned)((size_t)c->n_cu * c->opt_site_blocks / T));
-        // The site list's row table, when stale: one comparison individual's run makes it in the launch it makes anyway
-        // (its rows' values are all computed there: 32 B per row stored instead of the per-site triple's 24), a run over
-        // several with k_row_table first.  Every other --LD run takes the LIBD2 window products of the covered rows only.
-        // (stream2, behind this run's recount of the alt counts; readers: see ibdg_ctx::row_tab)
-        ibdg::RowsArgs ra = sa;
-        if (rt_build) {
-            ra.row_tab = (double *)c->row_tab.p;
-            if (T > 1) {
-                ibdg::launch_row_table(ra, c->stream2);
-                ra.row_tab = nullptr;
-            }
-        }
-        ibdg::launch_rows_windows(ra, (unsigned)T, c->stream2, row_blocks);
-        HIP_TRY(c, hipEventRecord(E.s2[2], c->stream2));
-        c->last_s2 = E.s2[2];
-        c->s2_pending = true;
-        c->tg_s2[c->tg_cur] = E.s2[2];
-        c->tg_s2_pending[c->tg_cur] = true;
-        if (!ahead_cap)
-            for (int h = 1; h < ibdg_ctx::TG_RING; ++h) {
-                c->tg_s2[h] = E.s2[2];
-                c->tg_s2_pending[h] = true;
-            }
-    }
-    // (who reads this run's slot of the per-individual buffers on the main stream)
-    for (int h = ahead_cap ? c->tg_cur : 0; h <= (ahead_cap ? c->tg_cur : ibdg_ctx::TG_RING - 1); ++h) {
-        c->tg_main[h] = E.ld_end;
-        c->tg_main_pending[h] = true;
-    }
+    if (!P.rows_on_main && queue_stream2(c, P, sa, E)) return 1;
+    ring_mark_readers(c, T, E.ld_end, P.rows_on_main ? nullptr : E.s2_end);
     HIP_TRY(c, hipGetLastError());
-    if (rt_build)
+    if (P.rt_build)
         c->rt_gen = c->up_gen;
-    c->ev_head = ev_slot;
-    ++c->runs_done;
-    c->chain_ok = true;
-    if (!c->opt_async && quiesce(c))
-        return 1;
-    c->n_targets = T;
-    c->have_results = true;
+    c->ev_head = ev_slot; ++c->runs_done; c->chain_ok = true;
+    if (!c->opt_async && quiesce(c)) return 1;
+    c->n_targets = T; c->have_results = true;
     c->res_site_mode = row_table ? 2 : (int)c->opt_site_results;
     return 0;
 }
@@ -2317,12 +2315,12 @@ int ibdg_run_ms(ibdg_ctx *c, unsigned back, float out[5])
         out[3] = 0.f;
         return 0;
     }
-    HIP_TRY(c, hipEventElapsedTime(&w, E.start, E.s2[2]));
+    HIP_TRY(c, hipEventElapsedTime(&w, E.start, E.s2_end));
     out[0] = v > w ? v : w;                  // the run ends when both streams are done
     out[3] = E.ld ? v : 0.f;
     if (E.recount)
-        HIP_TRY(c, hipEventElapsedTime(&out[1], E.s2_start, E.s2[0]));
-    HIP_TRY(c, hipEventElapsedTime(&v, E.recount ? E.s2[0] : E.s2_start, E.s2[2]));
+        HIP_TRY(c, hipEventElapsedTime(&out[1], E.s2_start, E.s2_count));
+    HIP_TRY(c, hipEventElapsedTime(&v, E.recount ? E.s2_count : E.s2_start, E.s2_end));
     out[2] = v;                              // per-row values and window products are one kernel
     return 0;
 }

@@ -1003,6 +1003,43 @@ def test_the_second_stream_never_overtakes_a_run_s_individuals():
         eng.set_option("async", 0)
 
 
+def test_a_flushed_finalising_step_is_ordered_before_the_second_stream():
+    """A queued --LD run of one individual leaves its finalising step to the next run (finalize_in_next 1).  A non-LD run
+    that recounts the alt counts (count_in_run 1) makes up for it on the main stream, while its own window products -- all
+    three columns of the same rows of the window table -- are written on the second stream: that stream must start behind
+    the step, whether the non-LD run brings the same individual or a new one (prepared on stream3).  Every run against its
+    synchronous result, bit for bit."""
+    N, L = 200, 20000
+    alle, nr, na = synth(24680, L, N)
+    people = (5, 120, 77)
+    with E.Engine() as eng:
+        eng.upload_panel(E.pack_alleles_fast(alle), N)
+        eng.upload_sites(np.arange(L), nr, na, 100)
+        want = {}
+        for t in people:
+            eng.run([t], ld=True)
+            ld = eng.window_ll(0)
+            eng.run([t], ld=False)
+            want[t] = (ld, eng.site_ll(0), eng.window_ll(0))
+        eng.set_option("async", 1)
+        eng.set_option("finalize_in_next", 1)
+        for rounds in range(6):
+            t = people[rounds % 3]
+            for other in (t, people[(rounds + 1) % 3]):         # the same individual, then a new one
+                eng.set_option("count_in_run", 0)
+                eng.run([t], ld=True)
+                eng.set_option("count_in_run", 1)
+                eng.run([other], ld=False)
+                what = f"round {rounds}, non-LD run over {'the same' if other == t else 'a new'} individual"
+                assert_bits(eng.site_ll(0), want[other][1], f"per-row values, {what}")
+                assert_bits(eng.window_ll(0), want[other][2], f"windows, {what}")
+            eng.set_option("count_in_run", 0)
+            eng.run([t], ld=True)
+            assert_bits(eng.window_ll(0), want[t][0], f"round {rounds}, --LD run after the non-LD runs")
+        eng.set_option("count_in_run", 0)
+        eng.set_option("async", 0)
+
+
 @pytest.mark.parametrize("tiles", [-1, 1])
 def test_ibd0_from_one_pass_over_the_site_list(oracle, tiles):
     """What a background individual's own genotype contributes to IBD0 (src/ibdgem.c:715, :743) does not depend on the
