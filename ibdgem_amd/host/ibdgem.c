@@ -48,6 +48,7 @@
 #include <errno.h>
 
 #include "../../include/ibdgem_hip.h"
+#include "hgpath.h"
 #include "ingest.h"
 #include "lineio.h"
 #include "pileup.h"
@@ -62,6 +63,8 @@ static int has_S = 0, has_s = 0, has_B = 0, has_A = 0, has_p = 0, has_v = 0, has
 static int opt_threads = 0;
 static const char *cache_fn = NULL, *dump_panel_fn = NULL;
 static int opt_stats_only = 0, has_arm = 0;
+static int opt_states = 0, has_pen = 0;  /* --states: the IBD-state path of every comparison (hgpath.c), --p01/--p02/--p12 its penalties */
+static double opt_p01 = HG_DEFAULT_P01, opt_p02 = HG_DEFAULT_P02, opt_p12 = HG_DEFAULT_P12;
 static unsigned long arm_c0, arm_c1;     /* --arm-stats: the centromeric range [c0, c1] of the run's chromosome */
 
 static struct option longopts[] = {
@@ -70,6 +73,10 @@ static struct option longopts[] = {
     {"summary-only", no_argument, &opt_summary_only, 1},
     {"stats-only", no_argument, &opt_stats_only, 1},
     {"arm-stats", required_argument, 0, 1006},
+    {"states", no_argument, &opt_states, 1},
+    {"p01", required_argument, 0, 1008},
+    {"p02", required_argument, 0, 1009},
+    {"p12", required_argument, 0, 1010},
     {"reference-order", no_argument, &opt_ref_order, 1},
     {"rand-stream", required_argument, 0, 1000},
     {"fmt-check", required_argument, 0, 1005},
@@ -144,8 +151,17 @@ static void usage(int code)
           "                            p-arm and q-arm sums of log2(LIBD2/LIBD0) and log2(LIBD1/LIBD0) over the\n"
           "                            summary windows, leaving out the centromeric range START..END (the\n"
           "                            reference's bin/chrarm-stats.py; summed on the device)\n"
-          "  --stats-only              with --arm-stats: write the armstats file only (no *.tab.txt, no\n"
-          "                            *.summary.txt; the window tables stay on the device)\n"
+          "  --states                  also write <out>/<pileup-name>.<individual>.hiddengem.txt: the most probable path\n"
+          "                            of IBD0/1/2 states over the individual's summary windows, what `hiddengem -s`\n"
+          "                            prints for its *.summary.txt; and <out>/<pileup-name>.ibdstates.txt: per\n"
+          "                            individual the windows in each state and their fractions, then the totals\n"
+          "                            (the reference's bin/sum-hiddengem.py).  Computed in the individual's output\n"
+          "                            job on the host, beside the device's next batch\n"
+          "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
+          "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
+          "  --stats-only              with --arm-stats and/or --states: write the armstats / ibdstates file only (no\n"
+          "                            *.tab.txt, no *.summary.txt, no *.hiddengem.txt; with --arm-stats alone the window\n"
+          "                            tables stay on the device)\n"
           "  --reference-order         --LD: sum over the background panel serially in the reference's order\n"
           "                            (LIBD0/LIBD1 bit-identical to the reference; ~12x slower than the default,\n"
           "                            whose values agree to ~1e-15)\n"
@@ -2177,6 +2193,12 @@ typedef struct {
     size_t sum_cap;
     const char *sq;                             /* the pileup's name (-N) */
     FILE *err;                                  /* where the pileup's messages go */
+    /* --states */
+    FILE *hg;                                   /* the individual's *.hiddengem.txt (NULL with --stats-only); closed by the job */
+    size_t *st_count;                           /* the individual's line of ibdstates.txt: windows in IBD0, IBD1, IBD2 */
+    hg_path hgp;                                /* the slot's path arrays and text buffer (kept between individuals) */
+    char *hg_buf;
+    size_t hg_cap;
 } out_job;
 
 enum { OUT_SLOTS = 12, MAX_WORKERS = 64 };
@@ -2198,6 +2220,8 @@ static void outs_settle_one(out_job *outs, int failing)
                 fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
             if (o->sum && ftruncate(fileno(o->sum), 0) != 0)
                 fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
+            if (o->hg && ftruncate(fileno(o->hg), 0) != 0)
+                fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
         }
     }
 }
@@ -2209,16 +2233,130 @@ static void outs_settle(int failing)
         outs_settle_one(g_outs[w], failing);
 }
 
+/* ---- --states: the individual's IBD-state path (hgpath.c), inside its output job --------------------------------------
+ * The path is the one `hiddengem -s` finds in the individual's *.summary.txt, so every likelihood enters the recurrence
+ * as that program would read it back: through the summary's own conversion (fmt_ll: "%e", "-nan") and strtod.  Taken
+ * from the doubles, not from the summary's text: the same holds where no summary is written (--stats-only).  No row of
+ * a summary this program writes is one sscanf passes over (two integers, three numbers or nan / inf, an integer). */
+static double summary_round_trip(double v)
+{
+    char t[48];
+    if (v == 0.0 && !signbit(v))
+        return 0.0;
+    fmt_ll(t, v, 0);
+    return strtod(t, NULL);
+}
+
+typedef struct {
+    const hg_path *h;
+    size_t a, b;
+    char *buf;
+    size_t len;
+} hg_fmt_job;
+
+static void *fmt_states(void *arg)
+{
+    hg_fmt_job *j = arg;
+    j->len = hg_format_rows(j->h, j->a, j->b, j->buf);
+    return NULL;
+}
+
+static int write_all(int fd, const char *buf, size_t len)
+{
+    for (size_t off = 0; off < len;) {
+        const ssize_t w = write(fd, buf + off, len - off);
+        if (w < 0) {
+            if (errno == EINTR)
+                continue;
+            return 1;
+        }
+        off += (size_t)w;
+    }
+    return 0;
+}
+
+/* the table of a solved path, its rows formatted by the job's team (three "%.5Le" per window: 20 ms of printf at
+ * 35 000 windows on one thread) */
+static int write_states_parallel(FILE *f, const hg_path *h, int threads, char **buf, size_t *cap)
+{
+    hg_fmt_job jobs[64];
+    pthread_t tid[64];
+    int started[64] = {0};
+    if (threads < 1) threads = 1;
+    if (threads > 64) threads = 64;
+    /* (IBDGEM_MT_MIN_BYTES below its default sends short tables through the team too: the tests' switch, as for the readers) */
+    const int team = h->n < (ls_mt_min_bytes() < ((size_t)1 << 20) ? 16 : 2048) ? 1 : threads;
+    if (*cap < h->n * HG_ROW_ROOM + 256) {
+        free(*buf);
+        *buf = malloc(h->n * HG_ROW_ROOM + 256);
+        *cap = *buf ? h->n * HG_ROW_ROOM + 256 : 0;
+    }
+    if (!*buf)
+        return 1;
+    for (int t = 0; t < team; ++t) {
+        jobs[t].h = h;
+        jobs[t].a = h->n * (size_t)t / (size_t)team;
+        jobs[t].b = h->n * (size_t)(t + 1) / (size_t)team;
+        jobs[t].buf = *buf + jobs[t].a * HG_ROW_ROOM;
+        jobs[t].len = 0;
+    }
+    for (int t = 0; t + 1 < team; ++t)
+        started[t] = pthread_create(&tid[t], NULL, fmt_states, &jobs[t]) == 0;
+    for (int t = 0; t < team; ++t)
+        if (!started[t])
+            fmt_states(&jobs[t]);
+    for (int t = 0; t + 1 < team; ++t)
+        if (started[t])
+            pthread_join(tid[t], NULL);
+    int rc = fputs(hg_header, f) < 0 || fflush(f) != 0;
+    const int fd = fileno(f);
+    for (int t = 0; t < team && !rc; ++t)
+        rc = write_all(fd, jobs[t].buf, jobs[t].len);
+    char *tail = *buf + h->n * HG_ROW_ROOM;
+    return rc || write_all(fd, tail, hg_format_tail(h, tail));
+}
+
+/* 0: the path is found, counted for ibdstates.txt and (o->hg) written and its file closed */
+static int states_individual(out_job *o)
+{
+    hg_path *h = &o->hgp;
+    hg_reset(h);
+    for (size_t w = 0; w < o->n_win; ++w)
+        if (hg_add(h, summary_round_trip(o->win_ll[3 * w]), summary_round_trip(o->win_ll[3 * w + 1]),
+                   summary_round_trip(o->win_ll[3 * w + 2])))
+            return 1;
+    if (hg_solve(h, opt_p01, opt_p02, opt_p12))
+        return 1;
+    memcpy(o->st_count, h->count, sizeof h->count);
+    if (!o->hg)
+        return 0;
+    int bad = write_states_parallel(o->hg, h, o->threads, &o->hg_buf, &o->hg_cap);
+    bad = fclose(o->hg) != 0 || bad;
+    o->hg = NULL;
+    return bad;
+}
+
 static void *output_individual(void *arg)
 {
     out_job *o = arg;
     o->failed = 1;
+    if (opt_stats_only) {                        /* --stats-only --states: the path's counts alone, no file of the individual's */
+        const int bad = states_individual(o);
+        if (bad)
+            fprintf(o->err, "[::] ERROR finding the IBD states of %s.\n", o->tname);
+        free(o->w_first); free(o->w_last); free(o->w_ncov); free(o->win_ll);
+        o->w_first = o->w_last = o->w_ncov = NULL;
+        o->win_ll = NULL;
+        o->failed = bad;
+        return NULL;
+    }
     FILE *tab = o->tab, *sum = o->sum;           /* opened by the main thread: a directory that cannot be written stops the run at once */
     if (opt_plan)
         printf("## PLAN %s %s processed=%lu skipped=%lu windows=%zu cull_p=%f\n", o->sq, o->tname, o->processed, o->skipped,
                o->n_win, o->cull_p);
     else {
-        if ((!opt_summary_only && ftruncate(fileno(tab), 0) != 0) || ftruncate(fileno(sum), 0) != 0) {
+        if ((!opt_summary_only && ftruncate(fileno(tab), 0) != 0) || ftruncate(fileno(sum), 0) != 0 ||
+            (o->hg && ftruncate(fileno(o->hg), 0) != 0)) {
             fprintf(o->err, "[::] ERROR in compare_impute(): Cannot empty the output files of %s.\n", o->tname);
             return NULL;
         }
@@ -2279,6 +2417,10 @@ static void *output_individual(void *arg)
     if (!opt_plan) {
         bad |= fclose(tab) != 0;
         bad |= fclose(sum) != 0;
+    }
+    if (opt_states && states_individual(o)) {
+        fprintf(o->err, "[::] ERROR writing the IBD-state path of %s.\n", o->tname);
+        bad = 1;
     }
     free(o->w_first); free(o->w_last); free(o->w_ncov); free(o->win_ll);
     o->w_first = o->w_last = o->w_ncov = NULL;
@@ -2580,6 +2722,9 @@ static int pj_run(pile_job *pj, worker_t *w)
     out_job *const outs = w->outs;
     const int batchable = !no_engine && !has_v && cull_p == 1.0;
     const char *out_dir = g_out_dir;
+    size_t *st_res = NULL;          /* --states: per individual the windows in IBD0, IBD1, IBD2; the run's ibdstates.txt */
+    FILE *st_file = NULL;
+    char *st_fn = NULL;
     /* Round 2 page-locked the arrays that cross the engine's boundary (ibdg_host_alloc).  Measured since: locking 128 MB costs 0.1 s, giving it
      * back at exit 0.2 s, and the copies it was meant to speed up (24 MB in, 96 MB out per comparison) run at the same
      * 56 GB/s from ordinary memory (bench.py results_to_host) -- so they are ordinary memory now (malloc / free). */
@@ -2609,6 +2754,19 @@ static int pj_run(pile_job *pj, worker_t *w)
         out_slots = atoi(getenv("IBDGEM_OUT_SLOTS"));
     const int out_threads_env = getenv("IBDGEM_OUT_THREADS") ? atoi(getenv("IBDGEM_OUT_THREADS")) : 0;   /* (measurement switch) */
     const int arm_on = has_arm && !opt_plan;
+    /* --stats-only keeps the window tables on the device unless the states are asked for: the path is found on the host */
+    const int tables_stay = opt_stats_only && !opt_states;
+    if (opt_states) {
+        st_res = calloc(targets.n + 1, 3 * sizeof(size_t));
+        /* opened before the run, like the individuals' files: a directory that cannot be written stops the run at once */
+        if (!st_res)
+            PFAIL("[::] ERROR: out of memory.\n");
+        if (asprintf(&st_fn, "%s/%s.ibdstates.txt", out_dir, sq) < 0)
+            goto fail;
+        if (!(st_file = fopen(st_fn, "w")))
+            PFAIL("[::] ERROR: Cannot open '%s' for writing.\n", st_fn);
+        pj_add_file(pj, st_fn);
+    }
     double *arm_res = arm_on ? malloc((targets.n + 1) * 4 * sizeof(double)) : NULL;   /* per individual: p20, q20, p10, q10 */
     if (arm_on && !arm_res)
         PFAIL("[::] ERROR: out of memory.\n");
@@ -2801,7 +2959,7 @@ static int pj_run(pile_job *pj, worker_t *w)
                 j->dev_idx = w->dev_base + d; j->same_sites = batchable;
                 j->site_ll = site_ll;
                 j->arm_seg = arm_on ? arm_local[d] : NULL;
-                j->stats_only = opt_stats_only;
+                j->stats_only = tables_stay;
                 j->err = err;
                 /* (no thread to be had: the shard runs here -- never exit() while other shard threads are
                  * inside the GPU runtime) */
@@ -2838,7 +2996,7 @@ static int pj_run(pile_job *pj, worker_t *w)
                 arm_res[4 * ti + 2] = arm_ok[0] ? acc[2] + acc[3] : NAN;
                 arm_res[4 * ti + 3] = arm_ok[1] ? acc[6] + acc[7] : NAN;
             }
-            if (opt_stats_only) {
+            if (tables_stay) {
                 /* no window table left the device */
             } else if (n_eng == 1 && jobs[0].a == 0) {
                 /* one device, the whole site list: its arrays as they are (a copy of 1.2 MB per individual otherwise) */
@@ -2862,10 +3020,10 @@ static int pj_run(pile_job *pj, worker_t *w)
             }
         }
 
-        if (arm_on && !no_engine && !opt_stats_only &&
+        if (arm_on && !no_engine && !tables_stay &&
             (n_win != arm_nw || memcmp(w_first, arm_wfirst, n_win * 4) || memcmp(w_last, arm_wlast, n_win * 4)))
             PFAIL("[::] ERROR: the engine's windows are not the ones the chromosome arms were cut from.\n");
-        if (opt_stats_only) {
+        if (tables_stay) {
             free(w_first); free(w_last); free(w_ncov); free(win_ll);
             phase("per individual: engine (upload, run, arm sums)");
             continue;
@@ -2893,8 +3051,12 @@ static int pj_run(pile_job *pj, worker_t *w)
         o->pre = row_pre; o->pre_off = row_pre_off;
         o->w_first = w_first; o->w_last = w_last; o->w_ncov = w_ncov; o->win_ll = win_ll;
         o->sq = sq; o->err = err;
+        o->hg = NULL;
+        o->st_count = st_res ? st_res + 3 * ti : NULL;
         if (opt_plan) {
             o->tab = o->sum = stdout;
+        } else if (opt_stats_only) {
+            o->tab = o->sum = NULL;               /* (--stats-only --states: the table is here for its path alone) */
         } else {
             char *tab_fn, *sum_fn;
             if (asprintf(&tab_fn, "%s/%s.%s.tab.txt", out_dir, sq, tname) < 0 ||
@@ -2915,6 +3077,17 @@ static int pj_run(pile_job *pj, worker_t *w)
                 PFAIL("[::] ERROR in compare_impute(): Cannot open '%s' and/or '%s' for writing.\n", tab_fn, sum_fn);
             free(tab_fn);
             free(sum_fn);
+            if (opt_states) {
+                char *hg_fn;
+                if (asprintf(&hg_fn, "%s/%s.%s.hiddengem.txt", out_dir, sq, tname) < 0)
+                    goto fail;
+                const int hg_fd = open(hg_fn, O_WRONLY | O_CREAT, 0666);
+                o->hg = hg_fd >= 0 ? fdopen(hg_fd, "w") : NULL;
+                if (!o->hg)
+                    PFAIL("[::] ERROR in compare_impute(): Cannot open '%s' for writing.\n", hg_fn);
+                pj_add_file(pj, hg_fn);
+                free(hg_fn);
+            }
         }
         const int threads = all_threads();
         /* (tools/many_tables.py: files of 1 / 2 / 3 / 4 / 6 individuals at once with 8 threads each 73* / 66 / 57 / 47 / 54 ms per
@@ -2967,6 +3140,25 @@ static int pj_run(pile_job *pj, worker_t *w)
         free(arm_fn);
         phase("arm statistics file");
     }
+    if (opt_states) {
+        /* one file for the run, like the arm statistics: a line per comparison individual in the order of the summaries, as
+         * bin/sum-hiddengem.py prints a row, then its totals over the pileup's individuals */
+        size_t total[3] = {0, 0, 0};
+        fprintf(st_file, "# ID\tN_SEGMENTS\tN_IBD0\tN_IBD1\tN_IBD2\tFRAC_IBD0\tFRAC_IBD1\tFRAC_IBD2\n");
+        for (size_t ti = 0; ti < targets.n; ++ti) {
+            hg_frac_row(st_file, g_ids.names[targets.idx[ti]], st_res + 3 * ti);
+            for (int k = 0; k < 3; ++k)
+                total[k] += st_res[3 * ti + k];
+        }
+        hg_frac_totals(st_file, total);
+        FILE *f = st_file;
+        st_file = NULL;
+        if (fclose(f) != 0)
+            PFAIL("[::] ERROR writing '%s'.\n", st_fn);
+        free(st_fn);
+        free(st_res);
+        phase("IBD-state fractions file");
+    }
     if (g_list_mode) {
         /* the next pileup's arrays take their place (a single -P run leaves them to the end of the process) */
         for (int k = 0; k < OUT_SLOTS; ++k)
@@ -2981,6 +3173,8 @@ static int pj_run(pile_job *pj, worker_t *w)
     return 0;
 fail:
     outs_settle_one(outs, 1);
+    if (st_file)
+        fclose(st_file);                  /* (opened empty, left empty) */
     return 1;
 }
 
@@ -3069,6 +3263,9 @@ int main(int argc, char **argv)
         case 1003: cache_fn = optarg; break;
         case 1004: dump_panel_fn = optarg; break;   /* test hook: the packed rows + clean flags as a binary file */
         case 1007: list_fn = optarg; break;         /* --pileup-list FILE: NAME PATH per pileup */
+        case 1008: opt_p01 = atof(optarg); has_pen = 1; break;
+        case 1009: opt_p02 = atof(optarg); has_pen = 1; break;
+        case 1010: opt_p12 = atof(optarg); has_pen = 1; break;
         case 1006:
             if (!parse_arm_range(optarg)) {
                 fprintf(stderr, "[::] ERROR: Invalid centromeric range (--arm-stats) '%s' (must be START,END with START <= END).\n", optarg);
@@ -3101,7 +3298,9 @@ int main(int argc, char **argv)
     if (opt_min_qual < 0) { fprintf(stderr, "[::] ERROR: Invalid genotype quality minimum (-q) of %.2f (must be >= 0).\n", opt_min_qual); exit(0); }
     if (opt_window < 2) { fprintf(stderr, "[::] ERROR: Invalid window size (-w) of %d (must be >= 2).\n", opt_window); exit(0); }
     if (opt_max_cov > 127) { fprintf(stderr, "[::] ERROR: Invalid maximum estimated coverage (-M) of %u (pileup lines hold at most 127 reads).\n", opt_max_cov); exit(0); }
-    if (opt_stats_only && !has_arm) { fprintf(stderr, "[::] ERROR: --stats-only needs --arm-stats START,END.\n"); exit(1); }
+    if (has_pen && !opt_states) { fprintf(stderr, "[::] ERROR: --p01, --p02 and --p12 are the penalties of --states.\n"); exit(1); }
+    if (opt_states && opt_plan) { fprintf(stderr, "[::] ERROR: --states writes files --plan does not make; use one of them.\n"); exit(1); }
+    if (opt_stats_only && !has_arm && !opt_states) { fprintf(stderr, "[::] ERROR: --stats-only needs --arm-stats START,END.\n"); exit(1); }
     if (opt_stats_only && opt_plan) { fprintf(stderr, "[::] ERROR: --stats-only writes a file --plan does not make; use one of them.\n"); exit(1); }
     if (opt_stats_only)
         opt_summary_only = 1;                 /* (what the engine does for it: no per-site values, batches queued ahead) */
