@@ -87,6 +87,18 @@ struct ibdg_ctx {
     DevBuf rec_all, rec_cov, cov_site, fo;
     DevBuf in_row, in_ref, in_alt;      // device copies of the caller's arrays (ibdg_upload_sites)
     DevBuf scan_tmp, info_dev, wraw, nck_dev, powb, win_first, win_last;
+    // The candidates of one pileup (-v: ibdg_upload_candidates): the rows that passed every filter that does not look at the
+    // comparison individual, kept until replaced or until a panel is uploaded.  ibdg_select_variable_sites compacts those at
+    // which an individual is not 0/0 into in_row / in_ref / in_alt (and `fo`) -- the buffers an upload from the host fills --
+    // and sel_cand, and hands them to upload_sites_core.  Stream edges: none of its own.  Writers and readers are all on the
+    // main stream (the copies of ibdg_upload_candidates, the selection kernels, stage A behind them, the copy of
+    // ibdg_get_site_candidates), every one of these calls waits on the host for all streams before it queues anything
+    // (quiesce), and what reads in_* / sel_cand later on another stream (stage B on stream2: rec_cov only) is ordered behind
+    // stage A by ev_prepA as after any upload.
+    DevBuf cand_row, cand_ref, cand_alt, cand_fo, sel_cand;
+    size_t n_cand = 0;
+    bool cand_valid = false, cand_have_rows = false, cand_have_fo = false;
+    bool sel_valid = false;             // the current site list came from ibdg_select_variable_sites (sel_cand is its map)
     ibdg::PrepInfo *info_h = nullptr;   // host-mapped mirror of the device's PrepInfo, filled in by the preparation kernels
     uint32_t prep_seq = 0;              // hand-overs so far (info_h->seq == prep_seq: the latest one has arrived)
     size_t seg_room = 0;                // segments the array was cleared for by stage A
@@ -515,6 +527,8 @@ int prepare_panel(ibdg_ctx *c, size_t n_rows, unsigned n_ids)
     c->n_sites = 0;
     c->n_cov = c->n_win = 0;
     c->sites_valid = false;
+    c->cand_valid = c->sel_valid = false;   // (the candidates name rows of the panel that goes)
+    c->n_cand = 0;
     c->n_pairs = (uint32_t)(((n_rows + 255) / 256) * 4);     // 64-row tile pairs, padded to whole 8-tile octs
     if (ensure(c, c->panel, n_rows * (size_t)c->stride * 8) || ensure(c, c->alt_count, n_rows * 4))
         return 1;
@@ -1124,7 +1138,8 @@ void ibdg_destroy(ibdg_ctx *c)
                       &c->fo, &c->targets, &c->weight, &c->nrefpanel, &c->af, &c->site_ll, &c->win_ll, &c->row_tab, &c->t32, &c->t32c, &c->seg_first,
                       &c->segs, &c->runs, &c->wconst, &c->wtarget, &c->twords, &c->wtarget_mt, &c->twords_mt, &c->vals, &c->order, &c->pow1, &c->pow2, &c->pow3, &c->partial, &c->aimg, &c->wc_slot, &c->partial_h, &c->base_w, &c->p2w, &c->p2c, &c->p2_tw, &c->p2_wt, &c->fragb,
                       &c->in_row, &c->in_ref, &c->in_alt, &c->scan_tmp, &c->info_dev, &c->wraw, &c->nck_dev, &c->powb,
-                      &c->win_first, &c->win_last, &c->llr_seg, &c->llr_part, &c->llr_out})
+                      &c->win_first, &c->win_last, &c->llr_seg, &c->llr_part, &c->llr_out, &c->cand_row, &c->cand_ref, &c->cand_alt,
+                      &c->cand_fo, &c->sel_cand})
         release(*b);
     for (hipEvent_t ev : c->ev_up)
         if (ev)
@@ -1224,9 +1239,28 @@ int ibdg_upload_panel_dev(ibdg_ctx *c, const void *dev_rows, size_t n_rows, unsi
     return copy_rows(c, dev_rows, n_rows, hipMemcpyDeviceToDevice);
 }
 
-// Everything an upload of sites does once the three input arrays are on the device.
+// The device's PrepInfo starts clean; afterwards every upload leaves it so (k_prep_scan, k_prep_mirror) -- unless it
+// stopped half way: prep_dirty
+static int clean_prep_info(ibdg_ctx *c)
+{
+    const bool fresh_info = !c->info_dev.p;
+    if (ensure(c, c->info_dev, sizeof(ibdg::PrepInfo)))
+        return 1;
+    if (fresh_info || c->prep_dirty) {
+        ibdg::PrepInfo init;
+        memset(&init, 0, sizeof init);
+        init.err_row_site = init.err_cov_site = init.first_row = 0xffffffffu;
+        HIP_TRY(c, hipMemcpyAsync(c->info_dev.p, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));          // `init` is a local
+        c->prep_dirty = false;
+    }
+    return 0;
+}
+
+// Everything an upload of sites does once the three input arrays are on the device.  fo_ready: the sites' -A triples are in
+// c->fo already (ibdg_select_variable_sites compacts the candidates' there); f_override is not looked at.
 static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *d_ref, const uint8_t *d_alt,
-                             const double *f_override, size_t n_sites, unsigned window)
+                             const double *f_override, size_t n_sites, unsigned window, bool fo_ready = false)
 {
     c->n_sites = n_sites;
     c->window = window;
@@ -1237,27 +1271,16 @@ static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *
     c->pop_sites_ok = false;
     c->win_bounds_valid = false;
     c->have_fo = false;
+    c->sel_valid = false;
     // segments of stage B: at most one per site, and in file order at most windows + tiles of the panel
     // (compacted tiles: windows + tiles of their virtual rows, at most window + 31 per window)
     const size_t n_win_max = (n_sites + window - 1) / window;
     const size_t seg_room = std::min<size_t>(n_sites, std::max<size_t>(n_win_max + (c->n_rows + 31) / 32 + 1,
                                                                       n_win_max + (n_win_max * ((size_t)window + 31) + 31) / 32 + 1));
-    const bool fresh_info = !c->info_dev.p;
     if (ensure(c, c->rec_all, n_sites * 8) || ensure(c, c->rec_cov, n_sites * 8) || ensure(c, c->cov_site, n_sites * 4) ||
-        ensure(c, c->scan_tmp, ibdg::prep_scan_blocks(std::max<size_t>(n_sites, 1)) * 4) ||
-        ensure(c, c->info_dev, sizeof(ibdg::PrepInfo)) ||
+        ensure(c, c->scan_tmp, ibdg::prep_scan_blocks(std::max<size_t>(n_sites, 1)) * 4) || clean_prep_info(c) ||
         (c->pop_lut_ok && (ensure(c, c->segs, seg_room * sizeof(ibdg::Seg)) || ensure(c, c->seg_first, seg_room * 4))))
         return 1;
-    if (fresh_info || c->prep_dirty) {
-        // the device's PrepInfo starts clean; afterwards every upload leaves it so (k_prep_mirror) -- unless it
-        // stopped half way: prep_dirty
-        ibdg::PrepInfo init;
-        memset(&init, 0, sizeof init);
-        init.err_row_site = init.err_cov_site = init.first_row = 0xffffffffu;
-        HIP_TRY(c, hipMemcpyAsync(c->info_dev.p, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));          // `init` is a local
-        c->prep_dirty = false;
-    }
     ++c->sites_gen;
     ++c->up_gen;
     c->relayout_credit = 0;
@@ -1316,7 +1339,9 @@ static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *
     c->n_win = (uint32_t)(((uint64_t)c->n_cov + window - 1) / window);
     if (build_layout(c))
         return 1;
-    if (f_override) {
+    if (fo_ready) {
+        c->have_fo = true;
+    } else if (f_override) {
         std::vector<double> fo(3 * n_sites);
         for (size_t s = 0; s < n_sites; ++s) {
             const double f = f_override[s];
@@ -1417,6 +1442,142 @@ int ibdg_upload_sites_dev(ibdg_ctx *c, const void *dev_row_index, const void *de
     if (rc == 0 && n_sites)
         HIP_TRY(c, hipEventSynchronize(c->ev_prepA));
     return upload_sites_finish(c, rc, t0);
+}
+
+// ---- -v: the site list of a comparison individual from the pileup's candidates, on the device ----
+
+int ibdg_upload_candidates(ibdg_ctx *c, const uint32_t *row_index, const uint8_t *n_ref, const uint8_t *n_alt,
+                           const double *f_override, size_t n_cand)
+{
+    if (!c) return 1;
+    if (upload_sites_check(c, n_ref, n_alt, row_index != nullptr, n_cand, 1)) return 1;
+    // what stage A checks per upload of sites, once for all the lists cut from these candidates -- and the selection kernels
+    // index the panel with these rows
+    for (size_t s = 0; s < n_cand; ++s) {
+        if (row_index && row_index[s] >= c->n_rows)
+            return fail(c, "[::] ERROR in ibdg_upload_candidates: row_index[%zu]=%u outside the panel (%zu rows)", s,
+                        row_index[s], c->n_rows);
+        if ((unsigned)n_ref[s] + n_alt[s] > c->max_cov)
+            return fail(c, "[::] ERROR in ibdg_upload_candidates: candidate %zu has n_ref+n_alt=%u > max_cov=%u", s,
+                        (unsigned)n_ref[s] + n_alt[s], c->max_cov);
+    }
+    if (quiesce(c)) return 1;
+    c->cand_valid = false;
+    if (ensure(c, c->cand_ref, n_cand) || ensure(c, c->cand_alt, n_cand) || (row_index && ensure(c, c->cand_row, n_cand * 4)))
+        return 1;
+    // the -A triples with the host's libm, once for every list cut from these candidates
+    std::vector<double> fo;
+    bool have_fo = false;
+    if (f_override) {
+        fo.resize(3 * n_cand);
+        for (size_t s = 0; s < n_cand; ++s) {
+            const double f = f_override[s];
+            fo[3 * s] = f;
+            if (f == f) {
+                fo[3 * s + 1] = libm_pow(1 - f, 2.0);
+                fo[3 * s + 2] = libm_pow(f, 2.0);
+                have_fo = true;
+            } else {
+                fo[3 * s + 1] = fo[3 * s + 2] = 0.0;
+            }
+        }
+        if (have_fo && ensure(c, c->cand_fo, fo.size() * 8)) return 1;
+    }
+    if (n_cand) {
+        if (row_index)
+            HIP_TRY(c, hipMemcpyAsync(c->cand_row.p, row_index, n_cand * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->cand_ref.p, n_ref, n_cand, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->cand_alt.p, n_alt, n_cand, hipMemcpyHostToDevice, c->stream));
+        if (have_fo)
+            HIP_TRY(c, hipMemcpyAsync(c->cand_fo.p, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));              // `fo` is a local, the arrays are the caller's
+    }
+    c->n_cand = n_cand;
+    c->cand_have_rows = row_index != nullptr;
+    c->cand_have_fo = have_fo;
+    c->cand_valid = true;
+    return 0;
+}
+
+size_t ibdg_num_candidates(const ibdg_ctx *c) { return c && c->cand_valid ? c->n_cand : 0; }
+
+int ibdg_select_variable_sites(ibdg_ctx *c, uint32_t target, unsigned window)
+{
+    if (!c) return 1;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!c->panel.p || c->n_ids == 0) return fail(c, "[::] ERROR in ibdg_select_variable_sites: no panel uploaded");
+    if (!c->cand_valid) return fail(c, "[::] ERROR in ibdg_select_variable_sites: no candidates uploaded");
+    if (target >= c->n_ids)
+        return fail(c, "[::] ERROR in ibdg_select_variable_sites: individual %u outside the panel (%u individuals)", target,
+                    c->n_ids);
+    if (window < 1) return fail(c, "[::] ERROR: Invalid window size (-w) of %u (must be >= 1).", window);
+    if (quiesce(c)) return 1;
+    const size_t n = c->n_cand;
+    if (ensure(c, c->in_ref, n) || ensure(c, c->in_alt, n) || (c->cand_have_rows && ensure(c, c->in_row, n * 4)) ||
+        ensure(c, c->sel_cand, n * 4) || (c->cand_have_fo && ensure(c, c->fo, n * 24)) ||
+        ensure(c, c->scan_tmp, ibdg::prep_scan_blocks(std::max<size_t>(n, 1)) * 4) || clean_prep_info(c))
+        return 1;
+    c->sel_valid = false;
+    c->sites_valid = false;
+    HIP_TRY(c, hipEventRecord(c->ev_up[0], c->stream));
+    size_t n_sel = 0;
+    if (n) {
+        ibdg::SelectArgs sa;
+        sa.row = c->cand_have_rows ? (const uint32_t *)c->cand_row.p : nullptr;
+        sa.n_ref = (const uint8_t *)c->cand_ref.p;
+        sa.n_alt = (const uint8_t *)c->cand_alt.p;
+        sa.fo = c->cand_have_fo ? (const double *)c->cand_fo.p : nullptr;
+        sa.n_cand = n;
+        sa.target = target;
+        sa.t32 = c->pop_lut_ok ? (const uint4 *)c->t32.p : nullptr;      // (no transposed panel with a clamped table)
+        sa.n_pairs = c->n_pairs;
+        sa.panel = (const uint64_t *)c->panel.p;
+        sa.stride = c->stride;
+        sa.out_row = (uint32_t *)c->in_row.p;
+        sa.out_ref = (uint8_t *)c->in_ref.p;
+        sa.out_alt = (uint8_t *)c->in_alt.p;
+        sa.out_cand = (uint32_t *)c->sel_cand.p;
+        sa.out_fo = (double *)c->fo.p;
+        sa.block_tmp = (uint32_t *)c->scan_tmp.p;
+        sa.info = (ibdg::PrepInfo *)c->info_dev.p;
+        sa.mirror = c->info_h;
+        sa.seq = ++c->prep_seq;
+        c->prep_dirty = true;
+        ibdg::launch_select_sites(sa, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        // the number selected comes with the scan's hand-over, like stage A's covered rows: the scatter kernel runs on while
+        // the host sizes stage A's buffers and queues it behind
+        if (wait_info(c, c->prep_seq))
+            return 1;
+        c->prep_dirty = false;
+        n_sel = c->info_h->n_cov;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_up[1], c->stream));
+    // candidates that are the panel's own rows: a selected site's candidate index is its row
+    const uint32_t *d_row = (const uint32_t *)(c->cand_have_rows ? c->in_row.p : c->sel_cand.p);
+    const int rc = upload_sites_core(c, d_row, (const uint8_t *)c->in_ref.p, (const uint8_t *)c->in_alt.p, nullptr, n_sel,
+                                     window, c->cand_have_fo && n_sel);
+    if (rc) {
+        // (rows and read counts were checked per candidate by ibdg_upload_candidates; whatever is left names a SITE of the
+        // selected list, whose candidate is that site's entry of ibdg_get_site_candidates' map)
+        c->err += " [site list of individual " + std::to_string(target) + " selected from " + std::to_string(n) +
+                  " candidates: a site number counts the selected candidates, in candidate order]";
+        return rc;
+    }
+    c->sel_valid = true;
+    return upload_sites_finish(c, 0, t0);
+}
+
+int ibdg_get_site_candidates(ibdg_ctx *c, uint32_t *out)
+{
+    if (!c) return 1;
+    if (!c->sel_valid || !c->sites_valid)
+        return fail(c, "[::] ERROR in ibdg_get_site_candidates: the current site list was not made by ibdg_select_variable_sites");
+    if (c->n_sites == 0) return 0;
+    if (!out) return fail(c, "[::] ERROR in ibdg_get_site_candidates: NULL output array");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, c->sel_cand.p, c->n_sites * 4, hipMemcpyDeviceToHost, c->stream));
+    return quiesce(c);
 }
 
 int ibdg_upload_ms(ibdg_ctx *c, float out[3])

@@ -274,6 +274,29 @@ struct PrepSegArgs {
                                 // (k_gather_transpose32) with this many virtual rows per window (>= window)
 };
 
+// In front of stage A (-v, ibdg_select_variable_sites): the candidates at which individual `target` is not 0/0, compacted in
+// candidate order into the arrays stage A reads.
+struct SelectArgs {
+    const uint32_t *row;        // device; NULL: candidate e is panel row e (out_cand then serves as the site list's row_index)
+    const uint8_t *n_ref, *n_alt;
+    const double *fo;           // NULL or [n_cand][3] {f, pow(1-f,2), pow(f,2)} (-A)
+    size_t n_cand;              // every row < the panel's rows (checked when the candidates were uploaded)
+    uint32_t target;            // < n_ids
+    const uint4 *t32;           // tile-transposed panel, or NULL: the site-major rows are read
+    uint32_t n_pairs;
+    const uint64_t *panel;
+    uint32_t stride;
+    uint32_t *out_row;
+    uint8_t *out_ref, *out_alt;
+    uint32_t *out_cand;
+    double *out_fo;
+    uint32_t *block_tmp;        // prep_scan_blocks(n_cand) words
+    PrepInfo *info;             // device: left as clean as stage A leaves it
+    PrepInfo *mirror;           // the number selected arrives as its n_cov, with seq
+    uint32_t seq;
+};
+void launch_select_sites(const SelectArgs &a, hipStream_t st);
+
 size_t prep_scan_blocks(size_t n);
 // stage A: rec_all, rec_cov, cov_site, info->{n_cov, err_*, first_row, last_row}; the mirror gets them with seq
 void launch_prep_sites(const PrepSiteArgs &a, hipStream_t st);

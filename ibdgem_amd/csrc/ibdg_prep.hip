@@ -595,9 +595,103 @@ __global__ __launch_bounds__(256) void k_prep_win_bounds(const uint32_t *__restr
     last[w] = cov_site[e - 1];
 }
 
+// ---- in front of stage A: the candidates of a pileup -> the site list of ONE comparison individual (-v) -------------
+// Candidate e is kept when the individual carries an alternate allele on either haplotype of the candidate's panel row
+// (src/ibdgem.c:584 skips the row otherwise).  The two bits come from the tile-transposed panel, where one 32-bit word
+// holds 32 consecutive rows of one haplotype of one individual ({first, second} haplotype side by side: one 8-byte load):
+// candidates in file order walk along ONE lane's words, rows / 64 units of 16 bytes in all, and 64 consecutive candidates
+// share a cache line or two -- the site-major panel would cost a line per candidate.  A context without the transposed
+// panel (a clamped P(D|G) table: strict kernel only) reads the two words of the site-major row instead.  The bit is taken
+// with 32-bit shifts (bits_below_lane's note).
+struct SelIn {
+    const uint32_t *row;            // NULL: candidate e is panel row e
+    const uint8_t *n_ref, *n_alt;
+    const double *fo;               // NULL or [n_cand][3]
+    size_t n_cand;
+    const uint2 *hap;               // tile-transposed: the individual's lane of its chunk, as uint2 {first, second} per 32 rows
+    const uint32_t *panel32;        // otherwise: the site-major panel as 32-bit words, at the individual's word of a row
+    uint32_t stride32;              // ... 32-bit words per row
+    uint32_t bit;                   // ... the individual's bit of that word
+};
+
+__device__ __forceinline__ bool sel_flag(const SelIn &in, size_t e)
+{
+    const uint32_t r = in.row ? in.row[e] : (uint32_t)e;
+    if (in.hap) {
+        // uint4 of tile pair r / 64 = 64 lanes x 2 uint2: {rows 0..31}, {rows 32..63}
+        const uint2 h = in.hap[(size_t)(r >> 6) * 128 + ((r >> 5) & 1)];
+        return (((h.x | h.y) >> (r & 31)) & 1u) != 0;
+    }
+    const uint32_t *w = in.panel32 + (size_t)r * in.stride32;
+    return (((w[0] | w[2]) >> in.bit) & 1u) != 0;         // (the second haplotype's 64-bit word follows the first's)
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void k_sel_count(SelIn in, uint32_t *__restrict__ block_cnt)
+{
+    const size_t base = (size_t)blockIdx.x * PREP_BLOCK;
+    const uint32_t tot = block_count(base, in.n_cand, [&](size_t e) { return sel_flag(in, e); });
+    if (threadIdx.x == 0)
+        block_cnt[blockIdx.x] = tot;
+}
+
+struct SelOut {
+    uint32_t *row;                  // [n_sel] (not written when the candidates are the panel's own rows: cand serves as it)
+    uint8_t *n_ref, *n_alt;
+    uint32_t *cand;                 // [n_sel] candidate index of every selected site
+    double *fo;                     // [n_sel][3] when the candidates carry overrides
+};
+
+__global__ __launch_bounds__(PREP_THREADS) void k_sel_scatter(SelIn in, const uint32_t *__restrict__ block_off, SelOut out)
+{
+    const size_t base = (size_t)blockIdx.x * PREP_BLOCK;
+    block_scatter(
+        base, in.n_cand, block_off[blockIdx.x], [&](size_t e) { return sel_flag(in, e); },
+        [&](size_t e, uint32_t k) {
+            if (in.row)
+                out.row[k] = in.row[e];
+            out.n_ref[k] = in.n_ref[e];
+            out.n_alt[k] = in.n_alt[e];
+            out.cand[k] = (uint32_t)e;
+            if (in.fo) {
+                out.fo[3 * (size_t)k] = in.fo[3 * e];
+                out.fo[3 * (size_t)k + 1] = in.fo[3 * e + 1];
+                out.fo[3 * (size_t)k + 2] = in.fo[3 * e + 2];
+            }
+        });
+}
+
 unsigned blocks_for(size_t n) { return (unsigned)((n + PREP_BLOCK - 1) / PREP_BLOCK); }
 
 }  // namespace
+
+void launch_select_sites(const SelectArgs &a, hipStream_t st)
+{
+    if (a.n_cand == 0)
+        return;
+    SelIn in;
+    in.row = a.row;
+    in.n_ref = a.n_ref;
+    in.n_alt = a.n_alt;
+    in.fo = a.fo;
+    in.n_cand = a.n_cand;
+    const uint32_t chunk = a.target >> 6, lane = a.target & 63;
+    in.hap = a.t32 ? reinterpret_cast<const uint2 *>(a.t32 + ((size_t)chunk * a.n_pairs * 64 + lane)) : nullptr;
+    in.panel32 = reinterpret_cast<const uint32_t *>(a.panel + 2 * (size_t)chunk) + (lane >> 5);
+    in.stride32 = 2 * a.stride;
+    in.bit = lane & 31;
+    SelOut out;
+    out.row = a.out_row;
+    out.n_ref = a.out_ref;
+    out.n_alt = a.out_alt;
+    out.cand = a.out_cand;
+    out.fo = a.out_fo;
+    const unsigned nb = blocks_for(a.n_cand);
+    hipLaunchKernelGGL(k_sel_count, dim3(nb), dim3(PREP_THREADS), 0, st, in, a.block_tmp);
+    // the scan hands the number selected to the host as stage A hands over its covered rows (word 0 of the mirror)
+    hipLaunchKernelGGL(k_prep_scan, dim3(1), dim3(1024), 0, st, a.block_tmp, nb, &a.info->n_cov, (WinConst *)nullptr, a.info,
+                       a.mirror, a.seq);
+    hipLaunchKernelGGL(k_sel_scatter, dim3(nb), dim3(PREP_THREADS), 0, st, in, a.block_tmp, out);
+}
 
 size_t prep_scan_blocks(size_t n) { return blocks_for(n); }
 

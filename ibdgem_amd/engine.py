@@ -30,6 +30,10 @@ SYMBOLS = {
     "ibdg_upload_panel_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_uint]),
     "ibdg_upload_sites": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
     "ibdg_upload_sites_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
+    "ibdg_upload_candidates": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t]),
+    "ibdg_num_candidates": (C.c_size_t, [_P]),
+    "ibdg_select_variable_sites": (C.c_int, [_P, C.c_uint32, C.c_uint]),
+    "ibdg_get_site_candidates": (C.c_int, [_P, _P]),
     "ibdg_upload_ms": (C.c_int, [_P, _P]),
     "ibdg_host_alloc": (_P, [C.c_size_t]),
     "ibdg_host_free": (None, [_P]),
@@ -75,8 +79,8 @@ def load_library(path=LIB_PATH):
                           "(python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback.")
     lib = C.CDLL(path)
     for name, (res, args) in SYMBOLS.items():
-        if path != LIB_PATH and not hasattr(lib, name):
-            continue                   # an older build of the ABI loaded for an A/B comparison
+        if (path != LIB_PATH or os.environ.get("IBDG_LIB")) and not hasattr(lib, name):
+            continue                   # an older build of the ABI loaded for an A/B comparison (by path or through IBDG_LIB)
         fn = getattr(lib, name)        # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -201,6 +205,31 @@ class Engine:
         fo = None if f_override is None else np.ascontiguousarray(f_override, dtype=np.float64)
         self._chk(self.lib.ibdg_upload_sites_dev(self.ctx, row_index_ptr or None, n_ref_ptr, n_alt_ptr,
                                                  None if fo is None else fo.ctypes.data, n_sites, window))
+
+    def upload_candidates(self, row_index, n_ref, n_alt, f_override=None):
+        """The rows of a pileup that passed every filter that does not depend on the comparison individual (-v); row_index
+        None: candidate s is panel row s.  Kept on the device until replaced or until a panel is uploaded."""
+        ri = None if row_index is None else np.ascontiguousarray(row_index, dtype=np.uint32)
+        nr = np.ascontiguousarray(n_ref, dtype=np.uint8)
+        na = np.ascontiguousarray(n_alt, dtype=np.uint8)
+        fo = None if f_override is None else np.ascontiguousarray(f_override, dtype=np.float64)
+        assert len(nr) == len(na) and (ri is None or len(ri) == len(nr)) and (fo is None or len(fo) == len(nr))
+        self._chk(self.lib.ibdg_upload_candidates(self.ctx, None if ri is None else ri.ctypes.data, nr.ctypes.data,
+                                                  na.ctypes.data, None if fo is None else fo.ctypes.data, len(nr)))
+
+    @property
+    def n_candidates(self):
+        return self.lib.ibdg_num_candidates(self.ctx)
+
+    def select_variable_sites(self, target, window):
+        """The current site list = the candidates at which individual `target` is not 0/0, made on the device."""
+        self._chk(self.lib.ibdg_select_variable_sites(self.ctx, int(target), int(window)))
+
+    def site_candidates(self):
+        """Candidate index of every site of a list made by select_variable_sites."""
+        out = np.empty(self.n_sites, dtype=np.uint32)
+        self._chk(self.lib.ibdg_get_site_candidates(self.ctx, out.ctypes.data))
+        return out
 
     def upload_ms(self):
         """Clocks of the last upload of sites (ms): copies, device preparation, whole call."""

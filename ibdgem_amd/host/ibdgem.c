@@ -2744,6 +2744,15 @@ static int pj_run(pile_job *pj, worker_t *w)
     /* (--summary-only: the summary files alone, 2.5 MB each at 35 000 windows -- 1.5 ms per individual when written one
      * after the other, most of a whole-panel job whose engine time is 0.2 ms per individual) */
     const int overlap = !has_v && cull_p == 1.0 && !opt_plan && targets.n > 1;
+    /* -v with one context and no -D: the rows that passed every filter but :584 are the pileup's; they go to the device once
+     * (ibdg_upload_candidates) and every individual's list is cut from them there (ibdg_select_variable_sites) -- the host
+     * walks the selected rows only: 3.5 ms per individual at 4M rows x 2504 where the scan of all rows took 58
+     * (profiles/r09_variable_sites.txt).  (IBDGEM_VARSITES=host: the host's own scan, for the tests and for measurements.) */
+    const char *vs_env = has_v ? getenv("IBDGEM_VARSITES") : NULL;
+    const int dev_v = has_v && !no_engine && n_eng == 1 && g_n_ups == 1 && cull_p == 1.0 && !(vs_env && !strcmp(vs_env, "host"));
+    uint32_t *c_row = NULL;                     /* dev_v: the candidates as the engine takes them */
+    uint8_t *c_nr = NULL, *c_na = NULL;
+    double *c_fo = NULL;
     double *site_slot[OUT_SLOTS] = {site_ll};
     /* (--summary-only: 2.5 MB per individual instead of 330: twelve individuals at a time with four formatter threads each --
      * 0.52 ms per individual in a run of 960 against 0.65 with six and eight, 0.90 with four, tools/many_summaries.py) */
@@ -2806,17 +2815,61 @@ static int pj_run(pile_job *pj, worker_t *w)
          * built for the first one and kept -- 9 ms per individual at 4M rows, more than its engine time.  The
          * reference's message for rows whose genotypes did not parse is repeated per individual as it prints it. */
         const int same_sites = !has_v && cull_p == 1.0 && ti > 0;
-        if (same_sites) {
+        if (dev_v && ti == 0) {
+            /* the candidate arrays, once per pileup: cand[] holds the rows of fate 1 in row order */
+            c_row = malloc((n_cand ? n_cand : 1) * 4);
+            c_nr = malloc(n_cand ? n_cand : 1);
+            c_na = malloc(n_cand ? n_cand : 1);
+            c_fo = has_A ? malloc((n_cand ? n_cand : 1) * 8) : NULL;
+            if (!c_row || !c_nr || !c_na || (has_A && !c_fo))
+                PFAIL("[::] ERROR: out of memory for %zu rows.\n", n_cand);
+            for (size_t i = 0; i < n_cand; ++i) {
+                c_row[i] = cand[i].row; c_nr[i] = cand[i].n_ref; c_na[i] = cand[i].n_alt;
+                if (c_fo) c_fo[i] = cand[i].f_is_override ? cand[i].f : NAN;
+            }
+            n_gt_failed = 0;
+            for (size_t r = 0; r < n_rows; ++r)
+                n_gt_failed += row_fate[r] == 0 && rows[r].gt_failed;
+            if (w->ups_pending) {                /* (the candidates name rows of the panel: it must be there) */
+                const int bad = uploads_join(ups, w->n_ups);
+                w->ups_pending = 0;
+                if (bad >= 0)
+                    PFAIL("%s\n", ibdg_last_error(ups[bad].eng));
+                phase("panel upload (copy, alt counts, transposition; the part not hidden behind the filter chain)");
+            }
+            if (ibdg_upload_candidates(engs[0], c_row, c_nr, c_na, c_fo, n_cand))
+                PFAIL("%s\n", ibdg_last_error(engs[0]));
+            phase("candidate rows of the pileup to the device");
+        }
+        if (same_sites || dev_v) {
             for (size_t r = 0; r < n_rows && n_gt_failed; ++r)
                 if (row_fate[r] == 0 && rows[r].gt_failed)
                     fprintf(err, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[r].pos);
         } else {
             n_gt_failed = 0;
+        }
+        if (!same_sites) {
             skipped = final_total = 0;
             memset(final_dist, 0, sizeof final_dist);
             n = 0;
         }
-        for (size_t r = 0, ci = 0; r < n_rows && !same_sites; ++r) {
+        if (dev_v) {
+            /* every row is either skipped or on the list (:584-626): the rows not selected are the skipped ones */
+            if (ibdg_select_variable_sites(engs[0], tgt, (unsigned)opt_window))
+                PFAIL("%s\n", ibdg_last_error(engs[0]));
+            n = ibdg_num_sites(engs[0]);
+            if (n > n_cand || ibdg_get_site_candidates(engs[0], s_cand))
+                PFAIL("%s\n", n > n_cand ? "[::] ERROR: more sites selected than candidates." : ibdg_last_error(engs[0]));
+            for (size_t i = 0; i < n; ++i) {
+                const size_t my = s_cand[i];
+                s_row[i] = c_row[my]; s_nr[i] = c_nr[my]; s_na[i] = c_na[my];
+                if (s_fo) s_fo[i] = c_fo[my];
+                final_total += (unsigned long)c_nr[my] + c_na[my];
+                final_dist[c_nr[my] + c_na[my]]++;
+            }
+            skipped = n_rows - n;
+        }
+        for (size_t r = 0, ci = 0; r < n_rows && !same_sites && !dev_v; ++r) {
             if (row_fate[r] == 0) {
                 if (rows[r].gt_failed) {
                     fprintf(err, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[r].pos);
@@ -2839,7 +2892,7 @@ static int pj_run(pile_job *pj, worker_t *w)
             n++;
         }
         const unsigned long processed = n;
-        phase("per individual: site list");
+        phase(dev_v ? "per individual: site list on the device" : "per individual: site list");
         if (ti == 0 && overlap && !opt_summary_only && targets.n >= 3 && n > 0) {
             /* nine of a row's fourteen columns are the same for every comparison individual: their text is made once */
             fmt_job pp;
@@ -2953,7 +3006,8 @@ static int pj_run(pile_job *pj, worker_t *w)
                     j->targets = &targets.idx[ti];
                     j->n_targets = 1;
                     j->t_local = 0;
-                    j->do_upload = j->do_run = 1;
+                    j->do_upload = !dev_v;       /* (dev_v: the engine holds the individual's list already) */
+                    j->do_run = 1;
                 }
                 j->bg_count = g_bg_count; j->pu_id = (int)pu_id; j->ld = opt_ld;
                 j->dev_idx = w->dev_base + d; j->same_sites = batchable;
@@ -3164,6 +3218,7 @@ static int pj_run(pile_job *pj, worker_t *w)
         for (int k = 0; k < OUT_SLOTS; ++k)
             free(site_slot[k]);
         free(s_row); free(s_cand); free(s_nr); free(s_na); free(s_fo); free(s_row_dev);
+        free(c_row); free(c_nr); free(c_na); free(c_fo);
         free(row_pre); free(row_pre_off); free(arm_res); free(arm_wfirst); free(arm_wlast);
         free(sum_pos_first); free(sum_pos_last);
     } else {

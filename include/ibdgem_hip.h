@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define IBDG_ABI_VERSION 5   /* 5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
+#define IBDG_ABI_VERSION 5   /* (still 5, additions only: ibdg_upload_candidates, ibdg_num_candidates, ibdg_select_variable_sites, ibdg_get_site_candidates -- the -v site lists made on the device.)  5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
                               * longer what a sparse pileup gets.  3: options site_results, stage_workers; ibdg_get_site_af
                               * computes on demand; ibdg_last_run_ms out[4] is 0 */
 
@@ -134,9 +134,33 @@ int ibdg_upload_sites_dev(ibdg_ctx *ctx, const void *dev_row_index, const void *
                           const void *dev_n_alt, const double *f_override, size_t n_sites,
                           unsigned window);
 
+/* -v / --variable-sites-only: the rows of a comparison depend on the comparison individual (src/ibdgem.c:584 skips a row
+ * at which it is 0/0), but the rows that passed every OTHER filter are the pileup's.  They go to the device once ...
+ *
+ * The rows of one pileup that passed every filter that does not depend on the comparison individual (what
+ * ibdg_upload_sites takes when there is no -v), kept on the device until replaced or until a panel is uploaded.  Same
+ * argument rules and errors as ibdg_upload_sites (rows outside the panel and read counts beyond max_cov are reported here,
+ * with the candidate's index); f_override may be NULL, its powers are taken with the host's libm once, here.  Does not
+ * change the current site list.  6 bytes per candidate of device memory (2 with row_index NULL), 24 more with overrides. */
+int ibdg_upload_candidates(ibdg_ctx *ctx, const uint32_t *row_index, const uint8_t *n_ref, const uint8_t *n_alt,
+                           const double *f_override, size_t n_cand);
+size_t ibdg_num_candidates(const ibdg_ctx *ctx);
+
+/* ... and this makes the current site list, as ibdg_upload_sites would, from the candidates at which individual `target`
+ * carries at least one alternate allele, in candidate order.  Everything is derived on the device (the flags from the
+ * tile-transposed panel, count / scan / scatter, then the preparation of any upload); the candidates stay.  Afterwards
+ * ibdg_num_sites / ibdg_num_windows / ibdg_get_windows / ibdg_run / ibdg_get_* behave exactly as after ibdg_upload_sites of
+ * that filtered list (an empty selection included).  Errors: no panel, no candidates, target >= n_ids, window = 0. */
+int ibdg_select_variable_sites(ibdg_ctx *ctx, uint32_t target, unsigned window);
+
+/* For each site of the current list its index into the candidates: out[ibdg_num_sites].  An error if the current list
+ * did not come from ibdg_select_variable_sites. */
+int ibdg_get_site_candidates(ibdg_ctx *ctx, uint32_t *out);
+
 /* Clocks of the last ibdg_upload_sites[_dev] (ms): out[0] host-to-device copies
  * of the arrays, out[1] preparation on the device including its two small
- * read-backs, out[2] the whole call on the host's clock. */
+ * read-backs, out[2] the whole call on the host's clock.  After ibdg_select_variable_sites out[0] is the selection
+ * (its three kernels and the hand-over of the number selected) instead of copies. */
 int ibdg_upload_ms(ibdg_ctx *ctx, float out[3]);
 
 /* Page-locked host memory for arrays handed to ibdg_upload_* / ibdg_get_*:
