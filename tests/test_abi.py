@@ -138,6 +138,30 @@ def test_ibd0_ibd1_twins_match_the_oracle_and_the_reference_grid_bitwise(oracle)
     assert lib.ibdg_pdg_ibd1(3, 0, 0.3, 0.1, 0.2, 0.3) == 1.0
 
 
+# options of ibdg_set_option that no GPU test sets, on purpose: name -> reason (two at the most)
+OPTIONS_WITHOUT_A_TEST = {}
+
+
+def test_every_option_is_set_by_a_gpu_test():
+    """include/ibdgem_hip.h promises the same results whatever an option says; that holds only for options some test sets.
+    Every name ibdg_set_option compares against must appear as a quoted string in a tests/test_gpu_*.py."""
+    import glob
+    src = open(os.path.join(REPO, "ibdgem_amd", "csrc", "ibdg_api.cpp")).read()
+    body = src[src.index("int ibdg_set_option("):]
+    body = body[:body.index("\n}\n")]
+    names = re.findall(r'!strcmp\(name, "([a-z0-9_]+)"\)', body)
+    assert len(names) >= 20 and len(set(names)) == len(names), names
+    assert "unknown option" in body                                            # (the function was read to its last line)
+    files = sorted(glob.glob(os.path.join(REPO, "tests", "test_gpu_*.py")))
+    assert len(files) >= 8
+    text = "\n".join(open(f).read() for f in files)
+    assert len(OPTIONS_WITHOUT_A_TEST) <= 2 and set(OPTIONS_WITHOUT_A_TEST) <= set(names)
+    unset = [n for n in names if f'"{n}"' not in text and f"'{n}'" not in text and n not in OPTIONS_WITHOUT_A_TEST]
+    assert not unset, f"options no GPU test sets: {unset}"
+    stale = [n for n in OPTIONS_WITHOUT_A_TEST if f'"{n}"' in text or f"'{n}'" in text]
+    assert not stale, f"listed as untested, but set by a test: {stale}"
+
+
 def test_bounded_poll_of_the_site_preparation():
     """ibdg_upload_sites waits for the device's hand-over by polling one host-mapped word; the poll ends when the word
     arrives, when the stream ends without it, when the stream fails, and -- a wedged stream -- when its wall-clock bound

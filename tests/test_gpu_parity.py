@@ -9,6 +9,9 @@ Bars (BASELINE.json north_star):
   * --LD window LIBD0/LIBD1: relative 1e-10 wherever |ref| >= 1e-290, "both
     below 1e-290" otherwise (the sum over the background is a tree on the
     GPU and a serial loop in the reference; observed differences are ~1e-15).
+
+The shapes here keep every kernel's work-distribution loop to one trip; tests/test_gpu_launch_trips.py holds the
+seconds-scale shapes at which those loops wrap (tests/test_gpu_fullsize.py the one full-size shape).
 """
 import os
 import sys
