@@ -3,6 +3,7 @@
 // the likelihood path lives here: without a HIP device every compute entry
 // point fails with an error.
 #include "../../include/ibdgem_hip.h"
+#include "ibdg_ctx.h"
 #include "ibdg_kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -33,276 +34,7 @@ double (*volatile libm_pow)(double, double) = std::pow;
 std::string g_create_error;          // of the last failed ibdg_create; contexts may be created from several threads
 std::mutex g_create_error_mu;
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
 }  // namespace
-
-struct ibdg_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;    // per-site + window-product kernels run beside the --LD kernels
-    hipStream_t stream3 = nullptr;    // what a NEW comparison individual needs before its --LD kernel (indices, weights, the
-                                      // individual's window / segment images), made under the --LD kernel of the run before
-    // Timing events of the last runs (asynchronous runs are timed after the fact).  Every event
-    // record is a barrier packet the command processor retires in ~5 us, so the main stream carries
-    // one per run (end of the --LD launches) plus a start only when the stream may have been idle.
-    static constexpr int EV_RING = 33;      // the last 32 runs can be queried
-    struct EvSet {
-        hipEvent_t start_own = nullptr;     // recorded when the previous run's end cannot serve as start
-        hipEvent_t ld_end = nullptr;        // main stream, after the last --LD launch
-        hipEvent_t k_start = nullptr, k_stop = nullptr;   // start / stop of the dominant --LD kernel's dispatch
-        bool has_kernel_times = false;
-        hipEvent_t s2_start = nullptr;      // stream2: before its first kernel of the run
-        hipEvent_t s2_count = nullptr;      // stream2: after the alt-count kernel
-        hipEvent_t s2_end = nullptr;        // stream2: after the per-site values and window products (one kernel)
-        hipEvent_t prep = nullptr;          // main stream: the target operands of the matrix-core kernel are built
-        hipEvent_t start = nullptr;         // start_own or the previous run's ld_end
-        bool recount = false, ld = false;
-        bool rows_on_main = false;          // non-LD run: the one kernel went to the main stream, stream2 was not used
-    } evs[EV_RING];
-    int ev_head = 0;
-    long runs_done = 0;
-    bool chain_ok = false;      // main stream has been busy since the head run's ld_end was queued
-    bool s2_pending = false;    // stream2 holds work the main stream has not waited for yet
-    hipEvent_t last_s2 = nullptr;
-    std::string err;
-
-    double eps = 0.02;
-    unsigned max_cov = 20;
-    std::vector<double> lut_h;
-    DevBuf lut, pow_tab;
-
-    // panel
-    DevBuf panel, alt_count;
-    size_t n_rows = 0;
-    unsigned n_ids = 0;
-    uint32_t n_chunks = 0, stride = 0, n_groups = 0;
-    int cpw = 0;
-    bool counts_valid = false;
-
-    // sites of the current comparison
-    DevBuf rec_all, rec_cov, cov_site, fo;
-    DevBuf in_row, in_ref, in_alt;      // device copies of the caller's arrays (ibdg_upload_sites)
-    DevBuf scan_tmp, info_dev, wraw, nck_dev, powb, win_first, win_last;
-    // The candidates of one pileup (-v: ibdg_upload_candidates): the rows that passed every filter that does not look at the
-    // comparison individual, kept until replaced or until a panel is uploaded.  ibdg_select_variable_sites compacts those at
-    // which an individual is not 0/0 into in_row / in_ref / in_alt (and `fo`) -- the buffers an upload from the host fills --
-    // and sel_cand, and hands them to upload_sites_core.  Stream edges: none of its own.  Writers and readers are all on the
-    // main stream (the copies of ibdg_upload_candidates, the selection kernels, stage A behind them, the copy of
-    // ibdg_get_site_candidates), every one of these calls waits on the host for all streams before it queues anything
-    // (quiesce), and what reads in_* / sel_cand later on another stream (stage B on stream2: rec_cov only) is ordered behind
-    // stage A by ev_prepA as after any upload.
-    DevBuf cand_row, cand_ref, cand_alt, cand_fo, sel_cand;
-    size_t n_cand = 0;
-    bool cand_valid = false, cand_have_rows = false, cand_have_fo = false;
-    bool sel_valid = false;             // the current site list came from ibdg_select_variable_sites (sel_cand is its map)
-    ibdg::PrepInfo *info_h = nullptr;   // host-mapped mirror of the device's PrepInfo, filled in by the preparation kernels
-    uint32_t prep_seq = 0;              // hand-overs so far (info_h->seq == prep_seq: the latest one has arrived)
-    size_t seg_room = 0;                // segments the array was cleared for by stage A
-    bool have_fo = false;
-    size_t n_sites = 0;
-    uint32_t n_cov = 0, window = 0, n_win = 0;
-    std::vector<uint32_t> win_first_h, win_last_h;   // fetched on the first ibdg_get_windows after an upload
-    bool win_bounds_valid = false;
-    bool sites_valid = false;           // an upload of sites has succeeded since the last upload of a panel
-    std::vector<uint32_t> runs_h;
-    // power tables (functions of epsilon only; grown on demand, see grow_pow_tables)
-    std::vector<ibdg::PowEntry> p1_h, p2_h, p3_h;      // rho^n, sigma^n, tau^n = (rho / sigma^2)^n (k_ld_mfma)
-    std::vector<ibdg::WinRaw> pb_h;
-    size_t tab_dev = 0;                 // entries the device copies hold
-    size_t tab_fail_from = (size_t)-1;  // first exponent whose power leaves the 32-bit exponent field
-    hipEvent_t ev_up[3] = {};           // before the host-to-device copies, after them, after the last prep kernel
-    hipEvent_t ev_prep2 = nullptr;      // stream2: the per-window constants of an upload are there
-    hipEvent_t ev_prepA = nullptr;      // main stream: the site records of an upload are there (behind k_prep_site_scatter)
-    // The finalising step of the last run of single individuals (k_ld_finalize's work) when it has been left to the NEXT
-    // run's k_ld_popcount launch (option "finalize_in_next"): whoever reads results or replaces inputs first makes up for
-    // it with a launch of its own (flush_finalize).  The partial sums alternate between the two halves of their buffer.
-    struct PendingFin {
-        bool pending = false;
-        ibdg::PopFinalArgs args;
-        unsigned count = 0;             // comparison individuals of the launch
-        uint64_t sites_gen = 0;         // sites_gen of the run that left it
-        int half = 0;                   // the half of `partial` the next such run writes
-    } fin;
-    float up_ms[3] = {0.f, 0.f, 0.f};   // copies, preparation on the device (with its host round trips), whole call
-    bool up_ms_pending = false;         // the first two are still to be read from the events
-
-    // fast --LD variant (exponent counting, ibdg_ld_popcount.hip)
-    // the compacted tiles of the current site list (k_gather_transpose32) and whether the segments,
-    // window constants and control words at hand were cut from them (true) or from the panel's own tiles (false)
-    DevBuf t32c;
-    uint32_t n_pairs_c = 0;
-    bool compact = false;
-    uint32_t first_row = 0, last_row = 0;   // panel rows of the first / last site of the upload
-    DevBuf seg_first;
-    DevBuf t32, segs, wconst, wtarget, twords, wtarget_mt, twords_mt, pow1, pow2, pow3, partial;
-    // many comparison individuals (k_ld_mfma): target operands of a batch of groups, window constants per slot,
-    // partial sums per half chunk, background multiplicities without the comparison individual's exclusion
-    DevBuf aimg, wc_slot, partial_h, base_w;
-    // ... and what does NOT depend on the comparison individuals (round 5): every background individual's weighted product of
-    // its own genotype factors per window (src/ibdgem.c:715, :743 -- the IBD0 terms) and their sums per chunk, from one pass of
-    // k_ld_popcount per site list and background (with some individual's images: the product does not look at them)
-    DevBuf p2w, p2c, p2_tw, p2_wt;
-    uint64_t p2_gen = 0, p2_bg_gen = 0;     // sites_gen / bg_gen the pass was made for
-    int p2_mx = -1;
-    uint64_t bg_gen = 1;                    // bumped whenever the background multiplicities change
-    // single comparison individuals take their IBD0 terms from that pass too once their runs on one upload and background
-    // have added up to "ibd0_after" individuals (the pass costs about one run and saves a fifth of every later one)
-    long opt_ibd0_after = 8;                // 0: never
-    long opt_mfma_wg_sum = 1;               // the matrix-core kernel's workgroups add their eight waves' sums up themselves (where LDS allows)
-    long opt_mfma_batch = 36;               // groups of 15 per launch of the matrix-core kernel (540 individuals)
-    size_t dev_mem_bytes = 0;               // the device's memory (hipMemGetInfo at ibdg_create)
-    uint64_t ibd0_runs = 0, ibd0_bg_gen = 0;
-    DevBuf fragb;                           // [n_segs][3][6 words]: the IBD1 form's fragments that do not depend on the individual (k_frag_base)
-    uint64_t fb_gen = 0;                    // sites_gen they were made for
-    hipEvent_t ev_fb = nullptr;
-    // pow1/pow2: rho^n, sigma^n as {f64 mantissa, i32 exponent}; powb: (1-eps)^n in the x87 format
-    uint32_t wpg = 0, max_seg = 0;     // most windows per workgroup run and its largest segment count
-    uint32_t n_runs = 0;               // runs of consecutive windows (DevBuf runs: n_runs+1 first windows)
-    DevBuf runs;
-    int n_cu = 256;
-    int tab_in_lds = 0;
-    int seg_ring = 4;                  // ring depth the segment control words were built for
-    uint32_t n_pairs = 0, n_segs = 0, ct_max = 0;
-    int planes = 0;
-    bool pop_lut_ok = false;     // P(D|G) table is the unclamped binomial form
-    bool pop_sites_ok = false;   // site rows strictly increasing, segments built
-    bool pop_dense_enough = true; // the site list went to the layout asked for (false: "compact_tiles" -1 on a sparse pileup)
-    std::vector<unsigned long> nck_h;
-    int last_variant = 0;
-    int last_count_unit = 0;           // 2: the last --LD run's single-individual launches counted on the matrix cores, 1: by (mask, count) pairs, 0: no such launch
-    // inputs of the previous ibdg_run whose device copies are still valid
-    std::vector<uint32_t> prev_targets;
-    std::vector<uint8_t> prev_bg;
-    int prev_pu = -2, prev_has_bg = -1;
-    size_t prev_lanes = 0;
-    // New comparison individuals reach the device without a host wait (the reference's loop hands every individual of the panel
-    // to the same rows in turn, src/ibdgem.c:522: a NEW individual per run is the normal case): their indices go through a
-    // weights kernel's arguments (a small ring of page-locked slots beyond IBDG_TG_INLINE of them) into one slot of a ring of
-    // `targets` buffers (the kernels of earlier runs may still read the others), and the weights / background sizes that follow
-    // from them are made on the device (k_target_weights) from the run's background multiplicities `base_w`; `nrefpanel` is a
-    // ring as well -- a finalising step left to the next run reads its own run's entry.
-    // `ring` and its functions (ring_prepare, ring_settle, ring_slot, ring_mark_readers) own all of it and its stream edges:
-    // runs of up to AHEAD_MAX_T individuals keep SLOTS copies of it, so that the NEXT run's can be made (on stream3) while the
-    // runs before still read theirs; larger runs use the buffers whole (slot 0), on the main stream.
-    // (round 5, later: a RING of four instead of two halves -- the preparation of run i + 1 then waits for the end of run i - 3,
-    // not of run i - 1, so it is long done when the --LD kernel of run i ends even on an eighth of a chromosome, where a step is
-    // 70 us and the chain "wait, copy, weights, images, record" on stream3 takes 40: profiles/r05_shard_steps.txt)
-    struct Ring {
-        static constexpr int SLOTS = 4;             // of `targets`, `weight`, wtarget / twords
-        static constexpr int NREF_SLOTS = 2 * SLOTS;   // `nrefpanel`, twice as long: a finalising step left to the next run
-                                                        // reads its own run's entry one run later than anything else of that run
-        static constexpr size_t AHEAD_MAX_T = 64;   // runs of up to that many individuals prepare ahead
-        static constexpr int STAGE_SLOTS = 4;       // page-locked staging of the indices
-        uint32_t *stage[STAGE_SLOTS] = {};
-        size_t stage_cap = 0;                       // comparison individuals a staging slot holds
-        hipEvent_t stage_ev[STAGE_SLOTS] = {};
-        int stage_next = 0;
-        int cur = 0;                                // the slot the current comparison individuals sit in
-        int nref = 0;                               // ... and their slot of `nrefpanel`
-        hipEvent_t main_read[SLOTS] = {}, s2_read[SLOTS] = {};   // the last reader of a slot: main stream, stream2
-        bool main_pending[SLOTS] = {}, s2_pending[SLOTS] = {};
-        hipEvent_t ready = nullptr;                 // the current comparison individuals' data are complete (where made)
-        bool unsettled = false;                     // stream3 holds a preparation the other streams do not wait for yet
-        hipEvent_t ev_s3sync = nullptr;             // main stream: the prepared sites stream3's kernels read are complete
-        uint64_t s3_gen = 0;                        // sites_gen stream3 has been ordered behind
-    } ring;
-    long opt_prep_ahead = 1;
-    long opt_end_in_dispatch = 1;    // the end event of a run of single individuals rides in its --LD kernel's dispatch packet (0: an event packet behind it): -7 us of a 91 us step on an eighth of a chromosome, profiles/r05_shard_steps.txt
-    int base_sum = 0;                   // sum of base_w
-    // the per-target LDS images of k_win_target (segment records with the target's tile words, window constants) depend
-    // on the prepared sites and the targets only: a further run over the same sites and targets reuses them
-    uint64_t sites_gen = 0;            // bumped by every upload of sites and every change of layout
-    uint64_t relayout_credit = 0;      // what the runs on this upload would have saved on the compacted tiles so far, in
-                                       // comparison individuals of the matrix-core kernel (see ibdg_run)
-    struct ImgKey {                    // what the images in wtarget / twords were made for: sites_gen (0: nothing), comparison
-        uint64_t gen;                  // individuals [first, first + count) of prev_targets, the form of the records (option
-        uint32_t first, count;         // mx_counts, IBD1) and the ring slot
-        int mx, ibd1, slot;
-        bool operator==(const ImgKey &o) const
-        { return gen == o.gen && first == o.first && count == o.count && mx == o.mx && ibd1 == o.ibd1 && slot == o.slot; }
-    } wt_key = {0, 0, 0, -1, -1, -1};
-
-    // run state / results
-    DevBuf targets, weight, nrefpanel, af, site_ll, win_ll;
-    DevBuf llr_seg, llr_part, llr_out;  // ibdg_window_llr_sums: segments, partial sums per block of windows, the sums
-    // The site list's row table, [n_sites][4] {LIBD0, LIBD1 under genotype 0, 1, 2}: what the rows' per-site values are for any
-    // comparison individual (they differ by the genotype picked).  Made by the first --LD run that keeps per-site results and
-    // finds it stale, used by every later one: ibdg_get_site_ll expands it for the last run's individual t (k_site_expand).
-    // It depends on the site records and -A overrides (an upload of sites), the alt counts and n_ids (an upload of the panel)
-    // and the P(D|G) table (fixed per context) -- hence on up_gen.  Stream edges:
-    //   writer  stream2 of the run that makes it (k_rows_windows<ROWS_TAB> for one individual, k_row_table for several),
-    //           behind that run's recount of the alt counts when it recounts
-    //   reader  k_site_expand on the main stream, behind join_streams (the main stream waits for stream2's last event, which
-    //           comes after the writer), and the fetch behind it waits on the host for both streams: no reader outlives its call
-    //   a rebuild happens only after an upload (which waits on the host for every stream before it changes anything) or when
-    //   ensure() has replaced the buffer (which also waits for every stream first, and whose new buffer holds no table: rt_gen 0)
-    DevBuf row_tab;
-    uint64_t up_gen = 1;                // bumped by every upload of a panel or of sites (a change of layout leaves it)
-    uint64_t rt_gen = 0;                // up_gen the table in row_tab was made for (0: none)
-    size_t n_targets = 0;
-    bool have_results = false;
-
-    // options
-    long opt_count_in_run = 0;
-    long opt_dispatch_events = 0;   // 1: time the --LD launches through their own dispatch packets (hipExtLaunchKernel);
-                                    // gives the dominant kernel's own duration, but costs ~10 us per run more than
-                                    // one event record (measured), so it is off unless asked for
-    long opt_async = 0;    // 1: ibdg_run returns once its kernels are queued
-    long opt_rows_blocks = 0;   // non-LD run: workgroups of k_rows_windows per CU (resident grid, each wave takes several windows); 0 = one wave per pair of windows
-    long opt_dev_inputs_ready = 0;   // 1: ibdg_upload_sites_dev trusts the caller that its arrays are complete (no device-wide wait)
-    long opt_cpw = 0;      // 0 = auto
-    long opt_waves = 8;
-    long opt_variant = 0;  // 0 auto, 1 strict products, 2 exponent counting, 3 strict products + serial sums in
-                           // the reference's order (bit-identical --LD columns)
-    std::vector<uint32_t> bg_order;   // optional: the background list in the reference's order (ibdg_set_background_order)
-    DevBuf vals, order;
-    long opt_wpg = 16;     // windows per wave in the fast kernel (upper bound unless set explicitly)
-    bool opt_wpg_fixed = false;
-    long opt_multi_target = 1;   // groups of comparison individuals share a workgroup (k_ld_popcount_mt)
-    long opt_mfma_targets = 1;   // 5 or more comparison individuals: groups of IBDG_TG through the matrix cores (k_ld_mfma)
-    long opt_mfma_plain_tau = 1; // k_ld_mfma looks tau^G up as a plain double where a window's powers allow it (same bits, half the LDS bytes)
-    long opt_mfma_min = 4;       // smallest (last) group worth a launch of its own (round 4: a group of 4 takes 2.09-2.17 ms, four single runs 2.5; a group of 3 2.14 against 1.87 for three single runs since their counts moved to the matrix cores -- 3 until then; of 2: 2.13 against 1.28)
-    long opt_guided = 4;   // shrink the runs towards the end of the grid (0 = uniform runs; n scales the
-                           // estimate of workgroups in flight by n/4 -- 4 measured best at 500k and 4M rows)
-    long opt_ring = 2;     // LDS ring slots per wave (2, 3, 4 or 8); 2 measured fastest (fewest LDS bytes)
-    long opt_recbytes = 12 * 1024;   // LDS budget for one run's segment records
-    long opt_site_blocks = 2;        // 256-thread workgroups per CU of the per-row kernel inside an --LD run (k_win_ibd2; 0 = its full
-                                     // grid): 2 the fastest step of 1, 2, 4 (8) in each round of profiles/r06_side_geometry.txt
-    long opt_recount_blocks = 4;     // single-wave workgroups per CU of k_alt_count when it runs inside an --LD run
-                                     // (0 = the full grid; 4 measured best: tools/recount_sweep.py)
-    long opt_compact = 0;            // tiles the --LD kernels read: 0 = chosen per upload (the panel's own where the pileup is
-                                     // dense, compacted where it is sparse or the rows are out of file order) and
-                                     // per run (many comparison individuals), 1 = always compacted, -1 = never
-    long opt_fin_next = 1;           // queued runs of single individuals: a run's finalising step rides in the next run's --LD launch
-    long opt_sum_dpp = 1;            // ... its wave sums by DPP moves (0: ds_swizzle, as the vector-ALU form)
-    long opt_mx_counts = 1;          // k_ld_popcount: the counts of a haplotype word by one matrix instruction (0: 12 (mask, count) pairs)
-    long opt_reserve_compact = 1;    // their buffer is allocated with the panel's (a panel's worth x 1.3 of HBM more per context)
-    long opt_compact_align = 1;      // rows a window of the compacted tiles is rounded up to: 1 = the rows back to back (no padding; a
-                                     // window straddles tiles like on the panel's own rows), 32 = every window on a tile boundary
-                                     // (round 4's layout: 28 % padding at windows of 100 rows)
-    long opt_compact_density = 4;    // compacted when fewer than 1 panel row in this many between the first and last site carries reads
-                                     // (tools/density_sweep.py: one comparison at 1 row in 3: 0.82 ms in place, 0.94 compacted; in 4: 0.76 / 0.76; in 5: 0.79 / 0.65)
-    long opt_compact_targets = 256;  // ... or when the runs on one upload add up to this many comparison individuals of the
-                                     // matrix-core kernel k_ld_mfma (the re-layout is paid once: one of them saves 0.007 ms of
-                                     // 0.185, the gather costs 1.5; an individual of the counting kernels counts as 16 with
-                                     // (mask, count) pairs -- it saves 0.04-0.09 ms of 0.77 -- and as 12 with mx_counts: 0.058 of 0.606)
-    long opt_site_results = 1;       // 1: per-site LIBD0/1/2 kept for ibdg_get_site_ll; 0: not -- no T x n_sites x 24 B of HBM,
-                                     // no per-site stores (window results only).  (The AF column is made on demand.)
-    int res_site_mode = 0;           // the mode the last run's results were produced under
-    bool prep_dirty = false;         // the device's PrepInfo may hold the leavings of an upload that did not finish
-    long opt_staged_upload = 1;      // panels of 256 MB and more from pageable memory go through the staging team
-    // page-locked staging for large panels from pageable memory (staged_upload)
-    static constexpr int STAGE_WORKERS = 8;
-    static constexpr size_t STAGE_BYTES = (size_t)8 << 20;
-    long opt_stage_workers = STAGE_WORKERS;   // host threads of the staging team (two 8 MB page-locked buffers each): a caller with
-                                              // several contexts uploading at once gives each a share of the cores
-    void *stage[2 * STAGE_WORKERS] = {};
-    hipEvent_t stage_ev[2 * STAGE_WORKERS] = {};
-};
 
 namespace {
 
@@ -344,9 +76,9 @@ int flush_finalize(ibdg_ctx *c)
 int join_streams(ibdg_ctx *c)
 {
     if (flush_finalize(c)) return 1;
-    if (c->s2_pending) {
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->last_s2, 0));
-        c->s2_pending = false;
+    if (c->tl.s2_pending) {
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->tl.last_s2, 0));
+        c->tl.s2_pending = false;
     }
     return 0;
 }
@@ -358,7 +90,7 @@ int quiesce(ibdg_ctx *c)
     if (join_streams(c)) return 1;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream3));     // (idle whenever the main stream is: every batch on it ends in an event the main stream waits for)
-    c->chain_ok = false;
+    c->tl.chain_ok = false;
     return 0;
 }
 
@@ -370,7 +102,7 @@ int ensure(ibdg_ctx *c, DevBuf &b, size_t bytes)
         return 0;
     if (b.p) {
         // queued runs ("async") may still use the buffer: wait for them rather than rely on hipFree doing so
-        if ((c->s2_pending || c->chain_ok) && quiesce(c))
+        if ((c->tl.s2_pending || c->tl.chain_ok) && quiesce(c))
             return 1;
         HIP_TRY(c, hipFree(b.p));
         b.p = nullptr;
@@ -378,15 +110,69 @@ int ensure(ibdg_ctx *c, DevBuf &b, size_t bytes)
     }
     HIP_TRY(c, hipMalloc(&b.p, bytes));
     b.cap = bytes;
+    ++b.allocs;
     return 0;
 }
 
-void release(DevBuf &b)
+// ---- what stops being valid when an input changes: each of these says all of it, and nobody else says any ----
+
+// A panel goes up: the alt counts, the results, the layout, the site list and the candidates (they name rows of the panel
+// that goes), and the device copies of targets / background weights, which were laid out for the previous panel.  The row
+// table goes with up_gen (its alt counts and n_ids).  sites_gen stays: no run is accepted before the next upload of sites
+// (sites_valid) and no background is taken for the same (prev_pu).
+void panel_replaced(ibdg_ctx *c)
 {
-    if (b.p)
-        (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
+    ++c->up_gen;
+    c->pan.counts_valid = false;
+    c->have_results = false;
+    c->lay.pop_sites_ok = false;
+    c->prev_targets.clear();
+    c->bg.prev_bg.clear();
+    c->bg.prev_pu = -2;
+    c->bg.prev_has_bg = -1;
+    c->bg.prev_lanes = 0;
+    c->sites.n_sites = 0;
+    c->sites.n_cov = c->sites.n_win = 0;
+    c->sites.sites_valid = false;
+    c->cand.valid = c->cand.sel_valid = false;
+    c->cand.n_cand = 0;
+}
+
+// A site list goes up (from the host, the device or the candidates): the results, the layout and its credit, the window
+// bounds, the -A triples, the selection map; with sites_gen the IBD0 pass, the fragment base, the images, a pending
+// finalising step's right to ride along and stream3's order behind the prepared sites; with up_gen the row table; and
+// the count of runs towards "ibd0_after".
+void sites_replaced(ibdg_ctx *c)
+{
+    ++c->sites_gen;
+    ++c->up_gen;
+    c->sites.n_cov = 0;
+    c->sites.n_win = 0;
+    c->sites.sites_valid = false;
+    c->sites.win_bounds_valid = false;
+    c->sites.have_fo = false;
+    c->cand.sel_valid = false;
+    c->have_results = false;
+    c->lay.pop_sites_ok = false;
+    c->lay.compact = false;
+    c->lay.relayout_credit = 0;
+    c->ibd0.drop();
+}
+
+// New segments, window constants and control words for the same site list (build_segments, also from
+// relayout_when_paid): everything keyed by sites_gen -- the IBD0 pass, the fragment base, the images, a pending finalising
+// step, stream3's order.  The row table does not depend on the layout (up_gen stays).
+void layout_changed(ibdg_ctx *c) { ++c->sites_gen; }
+
+// New background multiplicities: the IBD0 pass and the count towards "ibd0_after" (both keyed by bg_gen); a pending
+// finalising step is flushed by the run that brings them (ibdg_run: same_bg).
+void background_changed(ibdg_ctx *c) { ++c->bg.bg_gen; }
+
+// Other comparison individuals in the ring: the images in wtarget / twords are another individual's
+void targets_changed(ibdg_ctx *c, const uint32_t *targets, size_t T)
+{
+    c->prev_targets.assign(targets, targets + T);
+    c->img.drop();
 }
 
 // src/ibd-math.c:5-23: C(i,j) = (i*C(i-1,j-1))/j in unsigned long; 0 for j>i.
@@ -508,38 +294,24 @@ int prepare_panel(ibdg_ctx *c, size_t n_rows, unsigned n_ids)
 {
     if (n_ids == 0)
         return fail(c, "[::] ERROR in ibdg_upload_panel: n_ids must be >= 1");
-    c->n_ids = n_ids;
-    c->n_rows = n_rows;
-    ++c->up_gen;                        // (the alt counts and n_ids of the row table)
-    c->n_chunks = (n_ids + 63) / 64;
-    c->cpw = pick_cpw(c->n_chunks, c->opt_cpw);
-    c->n_groups = (c->n_chunks + c->cpw - 1) / c->cpw;
-    c->stride = 2u * c->cpw * c->n_groups;
-    c->counts_valid = false;
-    c->have_results = false;
-    c->pop_sites_ok = false;
-    // the device copies of targets / background weights were laid out for the previous panel
-    c->prev_targets.clear();
-    c->prev_bg.clear();
-    c->prev_pu = -2;
-    c->prev_has_bg = -1;
-    c->prev_lanes = 0;
-    c->n_sites = 0;
-    c->n_cov = c->n_win = 0;
-    c->sites_valid = false;
-    c->cand_valid = c->sel_valid = false;   // (the candidates name rows of the panel that goes)
-    c->n_cand = 0;
-    c->n_pairs = (uint32_t)(((n_rows + 255) / 256) * 4);     // 64-row tile pairs, padded to whole 8-tile octs
-    if (ensure(c, c->panel, n_rows * (size_t)c->stride * 8) || ensure(c, c->alt_count, n_rows * 4))
+    c->pan.n_ids = n_ids;
+    c->pan.n_rows = n_rows;
+    c->pan.n_chunks = (n_ids + 63) / 64;
+    c->pan.cpw = pick_cpw(c->pan.n_chunks, c->opt.cpw);
+    c->pan.n_groups = (c->pan.n_chunks + c->pan.cpw - 1) / c->pan.cpw;
+    c->pan.stride = 2u * c->pan.cpw * c->pan.n_groups;
+    panel_replaced(c);
+    c->pan.n_pairs = (uint32_t)(((n_rows + 255) / 256) * 4);     // 64-row tile pairs, padded to whole 8-tile octs
+    if (ensure(c, c->pan.panel, n_rows * (size_t)c->pan.stride * 8) || ensure(c, c->pan.alt_count, n_rows * 4))
         return 1;
-    if (c->pop_lut_ok && ensure(c, c->t32, (size_t)c->n_chunks * c->n_pairs * 64 * 16))
+    if (c->tab.pop_lut_ok && ensure(c, c->pan.t32, (size_t)c->pan.n_chunks * c->pan.n_pairs * 64 * 16))
         return 1;
     // ... and room for the compacted tiles of a site list on all these rows at the usual window sizes (32 ceil(W / 32) / W
     // <= 1.3: W = 100, 50, 75..., 97 and more), so that a re-layout in the middle of a series of runs does not allocate:
     // a hipMalloc of gigabytes is normally 0.2 ms but now and then 270-370 ms (after somebody's large hipFree:
     // tools/hipmalloc_in_process.py), which is 300 runs' worth.  Other windows grow it when their turn comes.
-    if (c->pop_lut_ok && c->opt_compact >= 0 && c->opt_reserve_compact &&
-        ensure(c, c->t32c, (size_t)c->n_chunks * (size_t)(c->n_pairs * 1.3 + 8) * 64 * 16))
+    if (c->tab.pop_lut_ok && c->opt.compact >= 0 && c->opt.reserve_compact &&
+        ensure(c, c->lay.t32c, (size_t)c->pan.n_chunks * (size_t)(c->pan.n_pairs * 1.3 + 8) * 64 * 16))
         return 1;
     // pow(1-f,2.0), pow(f,2.0) for every possible alt count (src/ibd-math.c:93-95 with
     // f = k/(2N), src/ibd-parse.c:98)
@@ -550,9 +322,9 @@ int prepare_panel(ibdg_ctx *c, size_t n_rows, unsigned n_ids)
         pt[2 * k] = libm_pow(1 - f, 2.0);
         pt[2 * k + 1] = libm_pow(f, 2.0);
     }
-    if (ensure(c, c->pow_tab, pt.size() * 8))
+    if (ensure(c, c->pan.pow_tab, pt.size() * 8))
         return 1;
-    HIP_TRY(c, hipMemcpyAsync(c->pow_tab.p, pt.data(), pt.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->pan.pow_tab.p, pt.data(), pt.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -583,17 +355,17 @@ void stage_worker(StageJob *j)
     for (size_t p = (size_t)j->worker; p < n_pieces; p += (size_t)j->n_workers, turn ^= 1) {
         const int b = 2 * j->worker + turn;
         const size_t r0 = p * j->rows_per_piece, nr = std::min(j->rows_per_piece, j->n_rows - r0);
-        if ((j->err = hipEventSynchronize(c->stage_ev[b])) != hipSuccess)     // the buffer's previous piece has left
+        if ((j->err = hipEventSynchronize(c->stg.stage_ev[b])) != hipSuccess)     // the buffer's previous piece has left
             return;
         if (j->src) {
-            memcpy(c->stage[b], j->src + r0 * j->rw, nr * j->rw);
+            memcpy(c->stg.stage[b], j->src + r0 * j->rw, nr * j->rw);
         } else {
             // straight from the file (the page cache) into the page-locked buffer: no mapping of the file, hence no page
             // faults here and no 2.56 GB of page-table entries to take down when the process ends
             size_t done = 0;
             const size_t want = nr * j->rw;
             while (done < want) {
-                const ssize_t k = pread(j->fd, (char *)c->stage[b] + done, want - done, (off_t)(j->off + r0 * j->rw + done));
+                const ssize_t k = pread(j->fd, (char *)c->stg.stage[b] + done, want - done, (off_t)(j->off + r0 * j->rw + done));
                 if (k <= 0) {
                     if (k < 0 && errno == EINTR)
                         continue;
@@ -603,10 +375,10 @@ void stage_worker(StageJob *j)
                 done += (size_t)k;
             }
         }
-        j->err = hipMemcpy2DAsync((char *)c->panel.p + r0 * j->dw, j->dw, c->stage[b], j->rw, j->rw, nr,
+        j->err = hipMemcpy2DAsync((char *)c->pan.panel.p + r0 * j->dw, j->dw, c->stg.stage[b], j->rw, j->rw, nr,
                                   hipMemcpyHostToDevice, c->stream);
         if (j->err == hipSuccess)
-            j->err = hipEventRecord(c->stage_ev[b], c->stream);
+            j->err = hipEventRecord(c->stg.stage_ev[b], c->stream);
         if (j->err != hipSuccess)
             return;
     }
@@ -614,14 +386,14 @@ void stage_worker(StageJob *j)
 
 int staged_upload(ibdg_ctx *c, const void *src, size_t n_rows, size_t rw, size_t dw, int fd = -1, uint64_t off = 0)
 {
-    int T = (int)std::min<unsigned>((unsigned)c->opt_stage_workers, std::max(1u, std::thread::hardware_concurrency()));
-    const size_t rows_per_piece = std::max<size_t>(1, ibdg_ctx::STAGE_BYTES / rw);
+    int T = (int)std::min<unsigned>((unsigned)c->opt.stage_workers, std::max(1u, std::thread::hardware_concurrency()));
+    const size_t rows_per_piece = std::max<size_t>(1, ibdg_ctx::Staging::BYTES / rw);
     for (int b = 0; b < 2 * T; ++b) {
-        if (!c->stage[b])
-            HIP_TRY(c, hipHostMalloc(&c->stage[b], ibdg_ctx::STAGE_BYTES, hipHostMallocDefault));
-        if (!c->stage_ev[b]) {
-            HIP_TRY(c, hipEventCreateWithFlags(&c->stage_ev[b], hipEventDisableTiming));
-            HIP_TRY(c, hipEventRecord(c->stage_ev[b], c->stream));       // "free" from the start
+        if (!c->stg.stage[b])
+            HIP_TRY(c, hipHostMalloc(&c->stg.stage[b], ibdg_ctx::Staging::BYTES, hipHostMallocDefault));
+        if (!c->stg.stage_ev[b]) {
+            HIP_TRY(c, hipEventCreateWithFlags(&c->stg.stage_ev[b], hipEventDisableTiming));
+            HIP_TRY(c, hipEventRecord(c->stg.stage_ev[b], c->stream));       // "free" from the start
         }
     }
     std::vector<StageJob> jobs((size_t)T);
@@ -662,31 +434,31 @@ bool is_plain_host_memory(const void *p)
 
 int copy_rows(ibdg_ctx *c, const void *src, size_t n_rows, hipMemcpyKind kind, int fd = -1, uint64_t off = 0)
 {
-    const size_t rw = ibdg_row_words(c->n_ids) * 8, dw = (size_t)c->stride * 8;
+    const size_t rw = ibdg_row_words(c->pan.n_ids) * 8, dw = (size_t)c->pan.stride * 8;
     if (n_rows == 0)
         return 0;
     if (rw != dw)
-        HIP_TRY(c, hipMemsetAsync(c->panel.p, 0, n_rows * dw, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->pan.panel.p, 0, n_rows * dw, c->stream));
     if (fd >= 0) {
         if (staged_upload(c, nullptr, n_rows, rw, dw, fd, off))
             return 1;
-    } else if (kind == hipMemcpyHostToDevice && n_rows * rw >= ((size_t)256 << 20) && c->opt_staged_upload &&
+    } else if (kind == hipMemcpyHostToDevice && n_rows * rw >= ((size_t)256 << 20) && c->opt.staged_upload &&
         is_plain_host_memory(src)) {
         if (staged_upload(c, src, n_rows, rw, dw))
             return 1;
     } else {
-        HIP_TRY(c, hipMemcpy2DAsync(c->panel.p, dw, src, rw, rw, n_rows, kind, c->stream));
+        HIP_TRY(c, hipMemcpy2DAsync(c->pan.panel.p, dw, src, rw, rw, n_rows, kind, c->stream));
     }
-    if (!c->opt_count_in_run) {
-        ibdg::launch_alt_count((const uint64_t *)c->panel.p, c->stride, n_rows, (uint32_t *)c->alt_count.p,
+    if (!c->opt.count_in_run) {
+        ibdg::launch_alt_count((const uint64_t *)c->pan.panel.p, c->pan.stride, n_rows, (uint32_t *)c->pan.alt_count.p,
                                c->stream);
         HIP_TRY(c, hipGetLastError());
-        c->counts_valid = true;
+        c->pan.counts_valid = true;
     }
-    if (c->pop_lut_ok) {
+    if (c->tab.pop_lut_ok) {
         // second resident layout of the same bits for the fast --LD kernel
-        ibdg::launch_transpose32((const uint64_t *)c->panel.p, c->stride, n_rows, c->n_chunks, c->n_pairs,
-                                 (uint32_t *)c->t32.p, c->stream);
+        ibdg::launch_transpose32((const uint64_t *)c->pan.panel.p, c->pan.stride, n_rows, c->pan.n_chunks, c->pan.n_pairs,
+                                 (uint32_t *)c->pan.t32.p, c->stream);
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -700,17 +472,17 @@ int copy_rows(ibdg_ctx *c, const void *src, size_t n_rows, hipMemcpyKind kind, i
 // full-length run.  A function of the window count alone.
 void make_runs(const ibdg_ctx *c, uint32_t g, std::vector<uint32_t> &runs)
 {
-    const uint32_t n_cg = (c->n_chunks + 7) / 8, wpg_waves = (c->n_chunks + n_cg - 1) / n_cg;
-    const uint32_t in_flight = std::max<uint32_t>(1, (uint32_t)(c->n_cu * (16 / wpg_waves) / n_cg) * (uint32_t)std::max<long>(1, c->opt_guided) / 4);
+    const uint32_t n_cg = (c->pan.n_chunks + 7) / 8, wpg_waves = (c->pan.n_chunks + n_cg - 1) / n_cg;
+    const uint32_t in_flight = std::max<uint32_t>(1, (uint32_t)(c->n_cu * (16 / wpg_waves) / n_cg) * (uint32_t)std::max<long>(1, c->opt.guided) / 4);
     runs.clear();
-    for (uint32_t w = 0; w < c->n_win;) {
+    for (uint32_t w = 0; w < c->sites.n_win;) {
         runs.push_back(w);
         uint32_t len = g;
-        if (c->opt_guided)
-            len = std::min(g, std::max<uint32_t>(1, (c->n_win - w + in_flight - 1) / in_flight));
-        w = std::min(w + len, c->n_win);
+        if (c->opt.guided)
+            len = std::min(g, std::max<uint32_t>(1, (c->sites.n_win - w + in_flight - 1) / in_flight));
+        w = std::min(w + len, c->sites.n_win);
     }
-    runs.push_back(c->n_win);
+    runs.push_back(c->sites.n_win);
 }
 
 // rho^n, sigma^n and (1-eps)^n for n < need, in extended precision; the bases come from the doubles
@@ -719,38 +491,38 @@ void make_runs(const ibdg_ctx *c, uint32_t g, std::vector<uint32_t> &runs)
 // the range of the 32-bit fields (the strict kernel then serves).
 bool grow_pow_tables(ibdg_ctx *c, size_t need)
 {
-    if (need > c->tab_fail_from)
+    if (need > c->tab.tab_fail_from)
         return false;
-    if (need <= c->p1_h.size())
+    if (need <= c->tab.p1_h.size())
         return true;
-    const size_t old = c->p1_h.size();
-    const size_t n = std::max(need, std::min<size_t>(old + old / 2 + 256, c->tab_fail_from));
-    const long double one_me = (long double)(double)(1 - c->eps);
-    const ME rho = me_norm((long double)c->eps / one_me, 0), sigma = me_norm(0.5L / one_me, 0);
+    const size_t old = c->tab.p1_h.size();
+    const size_t n = std::max(need, std::min<size_t>(old + old / 2 + 256, c->tab.tab_fail_from));
+    const long double one_me = (long double)(double)(1 - c->tab.eps);
+    const ME rho = me_norm((long double)c->tab.eps / one_me, 0), sigma = me_norm(0.5L / one_me, 0);
     // tau = rho / sigma^2 = 4 eps (1 - eps): the same long-double eps and 1 - eps as rho and sigma are made of
-    const ME tau = me_norm(4.0L * (long double)c->eps * one_me, 0);
-    c->p1_h.resize(n);
-    c->p2_h.resize(n);
-    c->p3_h.resize(n);
-    c->pb_h.resize(n);
+    const ME tau = me_norm(4.0L * (long double)c->tab.eps * one_me, 0);
+    c->tab.p1_h.resize(n);
+    c->tab.p2_h.resize(n);
+    c->tab.p3_h.resize(n);
+    c->tab.pb_h.resize(n);
     for (size_t k = old; k < n; ++k) {
-        const ME x = me_powl(rho, k), y = me_powl(sigma, k), z = me_pow(1 - c->eps, k), u = me_powl(tau, k);
+        const ME x = me_powl(rho, k), y = me_powl(sigma, k), z = me_pow(1 - c->tab.eps, k), u = me_powl(tau, k);
         if (x.e < -2000000000LL / 3 || y.e < -2000000000LL / 3 || z.e < -2000000000LL / 3 || u.e < -2000000000LL / 3 ||
             u.e > 2000000000LL / 3) {
-            c->tab_fail_from = k;
-            c->p1_h.resize(k);
-            c->p2_h.resize(k);
-            c->p3_h.resize(k);
-            c->pb_h.resize(k);
-            c->tab_dev = std::min(c->tab_dev, k);
+            c->tab.tab_fail_from = k;
+            c->tab.p1_h.resize(k);
+            c->tab.p2_h.resize(k);
+            c->tab.p3_h.resize(k);
+            c->tab.pb_h.resize(k);
+            c->tab.tab_dev = std::min(c->tab.tab_dev, k);
             return need <= k;
         }
-        c->p1_h[k].m = (double)x.m; c->p1_h[k].e = (int32_t)x.e; c->p1_h[k].pad = 0;
-        c->p2_h[k].m = (double)y.m; c->p2_h[k].e = (int32_t)y.e; c->p2_h[k].pad = 0;
-        c->p3_h[k].m = (double)u.m; c->p3_h[k].e = (int32_t)u.e; c->p3_h[k].pad = 0;
-        c->pb_h[k].m = (uint64_t)ldexpl(z.m, 64);        // exact: a 64-bit mantissa in [2^63, 2^64)
-        c->pb_h[k].e = (int32_t)z.e;
-        c->pb_h[k].pad = 0;
+        c->tab.p1_h[k].m = (double)x.m; c->tab.p1_h[k].e = (int32_t)x.e; c->tab.p1_h[k].pad = 0;
+        c->tab.p2_h[k].m = (double)y.m; c->tab.p2_h[k].e = (int32_t)y.e; c->tab.p2_h[k].pad = 0;
+        c->tab.p3_h[k].m = (double)u.m; c->tab.p3_h[k].e = (int32_t)u.e; c->tab.p3_h[k].pad = 0;
+        c->tab.pb_h[k].m = (uint64_t)ldexpl(z.m, 64);        // exact: a 64-bit mantissa in [2^63, 2^64)
+        c->tab.pb_h[k].e = (int32_t)z.e;
+        c->tab.pb_h[k].pad = 0;
     }
     return true;
 }
@@ -794,7 +566,7 @@ double wait_timeout_s()
 int wait_info(ibdg_ctx *c, uint32_t seq)
 {
     hipError_t last = hipSuccess;
-    const int rc = poll_seq(&c->info_h->seq, seq, wait_timeout_s(), [&]() {
+    const int rc = poll_seq(&c->sites.info_h->seq, seq, wait_timeout_s(), [&]() {
         last = hipStreamQuery(c->stream);
         return last == hipErrorNotReady ? 0 : (last == hipSuccess ? 1 : 2);
     });
@@ -813,141 +585,141 @@ int wait_info(ibdg_ctx *c, uint32_t seq)
 // count only (the run structure) and the epsilon-only power tables.
 int build_segments(ibdg_ctx *c, bool compact)
 {
-    c->pop_sites_ok = false;
-    if (!c->pop_lut_ok || c->n_cov == 0)
+    c->lay.pop_sites_ok = false;
+    if (!c->tab.pop_lut_ok || c->sites.n_cov == 0)
         return 0;
-    const ibdg::PrepInfo &I = *c->info_h;
+    const ibdg::PrepInfo &I = *c->sites.info_h;
     // virtual rows per window of the compacted layout: the window rounded up to the alignment asked for (1 = the rows back
     // to back, 32 = every window on a tile boundary)
-    const uint32_t align = (uint32_t)std::min<long>(32, std::max<long>(1, c->opt_compact_align));
-    const uint64_t win_rows = ((uint64_t)c->window + align - 1) / align * align;
-    const uint64_t vtiles = ((uint64_t)c->n_win * win_rows + 31) / 32;        // tiles of all its virtual rows
+    const uint32_t align = (uint32_t)std::min<long>(32, std::max<long>(1, c->opt.compact_align));
+    const uint64_t win_rows = ((uint64_t)c->sites.window + align - 1) / align * align;
+    const uint64_t vtiles = ((uint64_t)c->sites.n_win * win_rows + 31) / 32;        // tiles of all its virtual rows
     if (compact && win_rows >= (1ull << 31))
         return 0;
     // segments <= windows + tiles spanned when the rows are in file order (otherwise the device stops
     // writing at the capacity and the exponent-counting kernel is not used); never more than stage A cleared
-    uint64_t seg_cap = c->n_cov;
-    const uint32_t first_row = c->first_row, last_row = c->last_row;
+    uint64_t seg_cap = c->sites.n_cov;
+    const uint32_t first_row = c->sites.first_row, last_row = c->sites.last_row;
     if (compact)
-        seg_cap = std::min<uint64_t>(seg_cap, (uint64_t)c->n_win + vtiles + 1);
+        seg_cap = std::min<uint64_t>(seg_cap, (uint64_t)c->sites.n_win + vtiles + 1);
     else if (last_row >= first_row)
-        seg_cap = std::min<uint64_t>(seg_cap, (uint64_t)c->n_win + ((last_row >> 5) - (first_row >> 5)) + 1);
-    seg_cap = std::min<uint64_t>(seg_cap, c->seg_room);
+        seg_cap = std::min<uint64_t>(seg_cap, (uint64_t)c->sites.n_win + ((last_row >> 5) - (first_row >> 5)) + 1);
+    seg_cap = std::min<uint64_t>(seg_cap, c->sites.seg_room);
     if (compact) {
         // the rows with reads, gathered and transposed into tiles that start with their window
         const uint64_t pairs = (vtiles + 1) / 2;
         if (pairs >= (1ull << 31))
             return 0;
-        c->n_pairs_c = (uint32_t)((pairs + 3) & ~3ull);
-        if (ensure(c, c->t32c, (size_t)c->n_chunks * c->n_pairs_c * 64 * 16))
+        c->lay.n_pairs_c = (uint32_t)((pairs + 3) & ~3ull);
+        if (ensure(c, c->lay.t32c, (size_t)c->pan.n_chunks * c->lay.n_pairs_c * 64 * 16))
             return 1;
-        ibdg::launch_gather_transpose32((const uint64_t *)c->panel.p, c->stride, (const uint2 *)c->rec_cov.p, c->n_cov,
-                                        c->window, (uint32_t)win_rows, c->n_chunks, c->n_pairs_c, (uint32_t *)c->t32c.p, c->stream);
+        ibdg::launch_gather_transpose32((const uint64_t *)c->pan.panel.p, c->pan.stride, (const uint2 *)c->sites.rec_cov.p, c->sites.n_cov,
+                                        c->sites.window, (uint32_t)win_rows, c->pan.n_chunks, c->lay.n_pairs_c, (uint32_t *)c->lay.t32c.p, c->stream);
         HIP_TRY(c, hipGetLastError());
     }
-    if (ensure(c, c->wconst, ((size_t)c->n_win + 1) * sizeof(ibdg::WinConst)) ||
-        ensure(c, c->wraw, (size_t)c->n_win * sizeof(ibdg::WinRaw)))
+    if (ensure(c, c->lay.wconst, ((size_t)c->sites.n_win + 1) * sizeof(ibdg::WinConst)) ||
+        ensure(c, c->lay.wraw, (size_t)c->sites.n_win * sizeof(ibdg::WinRaw)))
         return 1;
-    if (!c->nck_dev.p) {
+    if (!c->tab.nck_dev.p) {
         // the coefficients normalised here (C << clz(C), 64 - clz(C)): the device multiplies them as they are
-        std::vector<ibdg::WinRaw> nn(c->nck_h.size());
+        std::vector<ibdg::WinRaw> nn(c->tab.nck_h.size());
         for (size_t i = 0; i < nn.size(); ++i) {
-            const unsigned long v = c->nck_h[i];
+            const unsigned long v = c->tab.nck_h[i];
             const int z = v ? __builtin_clzl(v) : 63;
             nn[i].m = v ? (uint64_t)v << z : (uint64_t)1 << 63;         // (0 is never looked up: r <= cov)
             nn[i].e = v ? 64 - z : 1;
             nn[i].pad = 0;
         }
-        if (ensure(c, c->nck_dev, nn.size() * sizeof(ibdg::WinRaw))) return 1;
+        if (ensure(c, c->tab.nck_dev, nn.size() * sizeof(ibdg::WinRaw))) return 1;
         // (a blocking copy, once per context: the kernel that reads the table runs on the second stream)
-        HIP_TRY(c, hipMemcpy(c->nck_dev.p, nn.data(), nn.size() * sizeof(ibdg::WinRaw), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->tab.nck_dev.p, nn.data(), nn.size() * sizeof(ibdg::WinRaw), hipMemcpyHostToDevice));
     }
     ibdg::PrepSegArgs sa;
-    sa.rec_cov = (const uint2 *)c->rec_cov.p;
-    sa.n_cov = c->n_cov;
-    sa.window = c->window;
-    sa.n_win = c->n_win;
-    sa.max_cov = c->max_cov;
-    sa.nck = (const ibdg::WinRaw *)c->nck_dev.p;
-    sa.segs = (ibdg::Seg *)c->segs.p;
-    sa.seg_first = (uint32_t *)c->seg_first.p;
+    sa.rec_cov = (const uint2 *)c->sites.rec_cov.p;
+    sa.n_cov = c->sites.n_cov;
+    sa.window = c->sites.window;
+    sa.n_win = c->sites.n_win;
+    sa.max_cov = c->tab.max_cov;
+    sa.nck = (const ibdg::WinRaw *)c->tab.nck_dev.p;
+    sa.segs = (ibdg::Seg *)c->lay.segs.p;
+    sa.seg_first = (uint32_t *)c->lay.seg_first.p;
     sa.seg_cap = (uint32_t)seg_cap;
-    sa.wconst = (ibdg::WinConst *)c->wconst.p;
-    sa.raw = (ibdg::WinRaw *)c->wraw.p;
-    sa.block_tmp = (uint32_t *)c->scan_tmp.p;
-    sa.info = (ibdg::PrepInfo *)c->info_dev.p;
-    sa.mirror = c->info_h;
+    sa.wconst = (ibdg::WinConst *)c->lay.wconst.p;
+    sa.raw = (ibdg::WinRaw *)c->lay.wraw.p;
+    sa.block_tmp = (uint32_t *)c->sites.scan_tmp.p;
+    sa.info = (ibdg::PrepInfo *)c->sites.info_dev.p;
+    sa.mirror = c->sites.info_h;
     sa.compact = compact ? (uint32_t)win_rows : 0u;
-    c->prep_dirty = true;
+    c->sites.prep_dirty = true;
     // windows per workgroup run: as many as keep the run's records within the LDS budget
-    uint32_t g = (uint32_t)std::max<long>(1, c->opt_wpg);
-    if (!c->opt_guided && !c->opt_wpg_fixed) {
+    uint32_t g = (uint32_t)std::max<long>(1, c->opt.wpg);
+    if (!c->opt.guided && !c->opt.wpg_fixed) {
         // uniform runs and few windows (a shard of a chromosome, a small region): shorter runs, so that
         // the grid still holds several rounds of workgroups for every CU
-        const uint64_t rows_of_blocks = (c->n_chunks + 7) / 8;
+        const uint64_t rows_of_blocks = (c->pan.n_chunks + 7) / 8;
         const uint64_t want_blocks = (uint64_t)c->n_cu * 2 * 5;          // CUs x resident blocks x rounds
-        const uint64_t g_fit = std::max<uint64_t>(1, (uint64_t)c->n_win * rows_of_blocks / want_blocks);
+        const uint64_t g_fit = std::max<uint64_t>(1, (uint64_t)c->sites.n_win * rows_of_blocks / want_blocks);
         if (g_fit < g)
             g = (uint32_t)g_fit;
     }
-    const uint32_t NS = (uint32_t)c->opt_ring;
+    const uint32_t NS = (uint32_t)c->opt.ring;
     for (bool first_try = true;; g = (g + 1) / 2, first_try = false) {
-        make_runs(c, g, c->runs_h);
-        c->n_runs = (uint32_t)c->runs_h.size() - 1;
-        if (ensure(c, c->runs, c->runs_h.size() * 4))
+        make_runs(c, g, c->lay.runs_h);
+        c->lay.n_runs = (uint32_t)c->lay.runs_h.size() - 1;
+        if (ensure(c, c->lay.runs, c->lay.runs_h.size() * 4))
             return 1;
         // runs_h is a member: it outlives the copy (the next wait is wait_info below)
-        HIP_TRY(c, hipMemcpyAsync(c->runs.p, c->runs_h.data(), c->runs_h.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->lay.runs.p, c->lay.runs_h.data(), c->lay.runs_h.size() * 4, hipMemcpyHostToDevice, c->stream));
         if (first_try) {
             // the run structure goes ahead of the segment kernels, whose last one makes the control words for it
             // (stream2 is idle: ibdg_upload_sites drained both streams before it began; it waits for stage A's records)
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_prepA, 0));
-            ibdg::launch_prep_segments(sa, (const uint32_t *)c->runs.p, c->n_runs, NS, c->stream, c->stream2);
+            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->sites.ev_prepA, 0));
+            ibdg::launch_prep_segments(sa, (const uint32_t *)c->lay.runs.p, c->lay.n_runs, NS, c->stream, c->stream2);
             HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipEventRecord(c->ev_prep2, c->stream2));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_prep2, 0));      // before the hand-over (ct_max) and K'
+            HIP_TRY(c, hipEventRecord(c->sites.ev_prep2, c->stream2));
+            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sites.ev_prep2, 0));      // before the hand-over (ct_max) and K'
         }
-        ibdg::launch_prep_seg_flags(sa, (const uint32_t *)c->runs.p, c->n_runs, NS, ++c->prep_seq, c->stream, !first_try);
+        ibdg::launch_prep_seg_flags(sa, (const uint32_t *)c->lay.runs.p, c->lay.n_runs, NS, ++c->sites.prep_seq, c->stream, !first_try);
         HIP_TRY(c, hipGetLastError());
-        if (wait_info(c, c->prep_seq))
+        if (wait_info(c, c->sites.prep_seq))
             return 1;
-        c->prep_dirty = false;
+        c->sites.prep_dirty = false;
         if ((!compact && I.out_of_order) || I.n_segs > seg_cap)
             return 0;                      // not in file order: the panel's own tiles do not apply
-        if ((size_t)I.max_seg * (sizeof(ibdg::Seg) + 8) <= (size_t)c->opt_recbytes || g == 1)
+        if ((size_t)I.max_seg * (sizeof(ibdg::Seg) + 8) <= (size_t)c->opt.recbytes || g == 1)
             break;
     }
     if (I.adv_overflow)
         return 0;                          // rows too far apart for the record format: strict kernel
-    c->wpg = g;
-    c->max_seg = I.max_seg;
-    c->seg_ring = (int)NS;
-    c->n_segs = I.n_segs;
-    c->ct_max = I.ct_max;
-    c->tab_in_lds = (size_t)(c->ct_max + 1) * 32 <= 24 * 1024;
-    if (ibdg::ld_popcount_lds_bytes(c->max_seg, c->wpg, c->ct_max + 1, c->tab_in_lds, c->seg_ring, 0) > 150 * 1024)
+    c->lay.wpg = g;
+    c->lay.max_seg = I.max_seg;
+    c->lay.seg_ring = (int)NS;
+    c->lay.n_segs = I.n_segs;
+    c->lay.ct_max = I.ct_max;
+    c->lay.tab_in_lds = (size_t)(c->lay.ct_max + 1) * 32 <= 24 * 1024;
+    if (ibdg::ld_popcount_lds_bytes(c->lay.max_seg, c->lay.wpg, c->lay.ct_max + 1, c->lay.tab_in_lds, c->lay.seg_ring, 0) > 150 * 1024)
         return 0;                          // a single window with thousands of tiles: strict kernel
-    if (!grow_pow_tables(c, (size_t)c->ct_max + 1))
+    if (!grow_pow_tables(c, (size_t)c->lay.ct_max + 1))
         return 0;
-    if (c->tab_dev < c->p1_h.size()) {     // new entries since the last upload
-        const size_t n = c->p1_h.size();
-        if (ensure(c, c->pow1, n * sizeof(ibdg::PowEntry)) || ensure(c, c->pow2, n * sizeof(ibdg::PowEntry)) ||
-            ensure(c, c->pow3, n * sizeof(ibdg::PowEntry)) || ensure(c, c->powb, n * sizeof(ibdg::WinRaw)))
+    if (c->tab.tab_dev < c->tab.p1_h.size()) {     // new entries since the last upload
+        const size_t n = c->tab.p1_h.size();
+        if (ensure(c, c->tab.pow1, n * sizeof(ibdg::PowEntry)) || ensure(c, c->tab.pow2, n * sizeof(ibdg::PowEntry)) ||
+            ensure(c, c->tab.pow3, n * sizeof(ibdg::PowEntry)) || ensure(c, c->tab.powb, n * sizeof(ibdg::WinRaw)))
             return 1;
-        HIP_TRY(c, hipMemcpyAsync(c->pow3.p, c->p3_h.data(), n * sizeof(ibdg::PowEntry), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->pow1.p, c->p1_h.data(), n * sizeof(ibdg::PowEntry), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->pow2.p, c->p2_h.data(), n * sizeof(ibdg::PowEntry), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->powb.p, c->pb_h.data(), n * sizeof(ibdg::WinRaw), hipMemcpyHostToDevice, c->stream));
-        c->tab_dev = n;
+        HIP_TRY(c, hipMemcpyAsync(c->tab.pow3.p, c->tab.p3_h.data(), n * sizeof(ibdg::PowEntry), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->tab.pow1.p, c->tab.p1_h.data(), n * sizeof(ibdg::PowEntry), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->tab.pow2.p, c->tab.p2_h.data(), n * sizeof(ibdg::PowEntry), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->tab.powb.p, c->tab.pb_h.data(), n * sizeof(ibdg::WinRaw), hipMemcpyHostToDevice, c->stream));
+        c->tab.tab_dev = n;
     }
     // K' = K * (1-eps)^(all reads of the window): with it a product is K' * rho^E2 * sigma^E3,
     // rho = eps/(1-eps), sigma = 1/(2(1-eps))  (E1 = reads - E2 - E3 eliminated)
-    ibdg::launch_prep_win_kp(c->n_win, (const ibdg::WinRaw *)c->wraw.p, (const ibdg::WinRaw *)c->powb.p,
-                             (ibdg::WinConst *)c->wconst.p, c->stream);
+    ibdg::launch_prep_win_kp(c->sites.n_win, (const ibdg::WinRaw *)c->lay.wraw.p, (const ibdg::WinRaw *)c->tab.powb.p,
+                             (ibdg::WinConst *)c->lay.wconst.p, c->stream);
     HIP_TRY(c, hipGetLastError());
-    c->pop_sites_ok = true;
-    c->compact = compact;
-    ++c->sites_gen;
+    c->lay.pop_sites_ok = true;
+    c->lay.compact = compact;
+    layout_changed(c);
     return 0;
 }
 
@@ -957,29 +729,29 @@ int build_segments(ibdg_ctx *c, bool compact)
 // 100 rows).  Below about one covered row in four the compacted layout is the faster one for a single run.
 bool sparse_sites(const ibdg_ctx *c)
 {
-    if (c->last_row < c->first_row)
+    if (c->sites.last_row < c->sites.first_row)
         return true;                       // not even the ends are in file order
-    const uint64_t span = (uint64_t)c->last_row - c->first_row + 1;
-    return (uint64_t)c->n_cov * (uint64_t)std::max<long>(1, c->opt_compact_density) < span;
+    const uint64_t span = (uint64_t)c->sites.last_row - c->sites.first_row + 1;
+    return (uint64_t)c->sites.n_cov * (uint64_t)std::max<long>(1, c->opt.compact_density) < span;
 }
 
 // Segments for the layout the options and the site list ask for; the compacted one also serves when the panel's own
 // tiles turn out not to apply (rows out of file order, rows too far apart for the control words).
 int build_layout(ibdg_ctx *c)
 {
-    c->pop_sites_ok = false;
-    c->compact = false;
-    c->pop_dense_enough = true;
-    if (!c->pop_lut_ok || c->n_cov == 0)
+    c->lay.pop_sites_ok = false;
+    c->lay.compact = false;
+    c->lay.pop_dense_enough = true;
+    if (!c->tab.pop_lut_ok || c->sites.n_cov == 0)
         return 0;
     const bool sparse = sparse_sites(c);
-    const bool want_compact = c->opt_compact > 0 || (c->opt_compact == 0 && sparse);
+    const bool want_compact = c->opt.compact > 0 || (c->opt.compact == 0 && sparse);
     if (build_segments(c, want_compact))
         return 1;
-    if (!c->pop_sites_ok && !want_compact && c->opt_compact == 0 && build_segments(c, true))
+    if (!c->lay.pop_sites_ok && !want_compact && c->opt.compact == 0 && build_segments(c, true))
         return 1;
-    if (c->opt_compact < 0 && sparse)
-        c->pop_dense_enough = false;       // the caller forbade the layout this pileup wants: the strict kernel is the faster one
+    if (c->opt.compact < 0 && sparse)
+        c->lay.pop_dense_enough = false;       // the caller forbade the layout this pileup wants: the strict kernel is the faster one
     return 0;
 }
 
@@ -1060,8 +832,8 @@ ibdg_ctx *ibdg_create(int device, double epsilon, unsigned max_cov)
     }
     ibdg_ctx *c = new ibdg_ctx;
     c->device = device;
-    c->eps = epsilon;
-    c->max_cov = max_cov;
+    c->tab.eps = epsilon;
+    c->tab.max_cov = max_cov;
     auto bail = [&](const char *what, hipError_t err) {
         fail(nullptr, "[::] ERROR in ibdg_create: %s: %s", what, hipGetErrorString(err));
         ibdg_destroy(c);
@@ -1085,18 +857,18 @@ ibdg_ctx *ibdg_create(int device, double epsilon, unsigned max_cov)
             (e = hipEventCreateWithFlags(&c->ring.ev_s3sync, hipEventDisableTiming)) != hipSuccess)
             return bail("hipEventCreate", e);
     }
-    for (auto &E : c->evs) {
+    for (auto &E : c->tl.evs) {
         for (hipEvent_t *ev : {&E.start_own, &E.ld_end, &E.k_start, &E.k_stop, &E.s2_start, &E.s2_count, &E.s2_end, &E.prep})
             if ((e = hipEventCreate(ev)) != hipSuccess) return bail("hipEventCreate", e);
     }
-    for (hipEvent_t &ev : c->ev_up)
+    for (hipEvent_t &ev : c->sites.ev_up)
         if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&c->ev_prep2, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&c->ev_prepA, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = hipEventCreateWithFlags(&c->sites.ev_prep2, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = hipEventCreateWithFlags(&c->sites.ev_prepA, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     // (coherent: the kernels' stores must reach the host while the stream is still busy, not at its next drain)
-    if ((e = hipHostMalloc((void **)&c->info_h, sizeof(ibdg::PrepInfo), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
+    if ((e = hipHostMalloc((void **)&c->sites.info_h, sizeof(ibdg::PrepInfo), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
         return bail("hipHostMalloc", e);
-    memset(c->info_h, 0, sizeof(ibdg::PrepInfo));
+    memset(c->sites.info_h, 0, sizeof(ibdg::PrepInfo));
     {
         int n_cu = 0;
         if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0)
@@ -1106,19 +878,19 @@ ibdg_ctx *ibdg_create(int device, double epsilon, unsigned max_cov)
             c->dev_mem_bytes = mem_total;
     }
     const size_t d = (size_t)max_cov + 1;
-    c->lut_h.resize(d * d * 3);
-    build_pdg_table(epsilon, max_cov, c->lut_h.data());
-    c->nck_h = nck_table(max_cov);
-    c->pop_lut_ok = lut_is_binomial(c->lut_h, c->nck_h, epsilon, max_cov);
-    c->planes = 1;
-    while ((1u << c->planes) <= max_cov)
-        ++c->planes;
-    if (ensure(c, c->lut, c->lut_h.size() * 8)) {
+    c->tab.lut_h.resize(d * d * 3);
+    build_pdg_table(epsilon, max_cov, c->tab.lut_h.data());
+    c->tab.nck_h = nck_table(max_cov);
+    c->tab.pop_lut_ok = lut_is_binomial(c->tab.lut_h, c->tab.nck_h, epsilon, max_cov);
+    c->lay.planes = 1;
+    while ((1u << c->lay.planes) <= max_cov)
+        ++c->lay.planes;
+    if (ensure(c, c->tab.lut, c->tab.lut_h.size() * 8)) {
         fail(nullptr, "%s", c->err.c_str());
         ibdg_destroy(c);
         return nullptr;
     }
-    if ((e = hipMemcpy(c->lut.p, c->lut_h.data(), c->lut_h.size() * 8, hipMemcpyHostToDevice)) != hipSuccess)
+    if ((e = hipMemcpy(c->tab.lut.p, c->tab.lut_h.data(), c->tab.lut_h.size() * 8, hipMemcpyHostToDevice)) != hipSuccess)
         return bail("hipMemcpy(lut)", e);
     return c;
 }
@@ -1134,29 +906,23 @@ void ibdg_destroy(ibdg_ctx *c)
         (void)hipStreamSynchronize(c->stream2);
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : {&c->lut, &c->pow_tab, &c->panel, &c->alt_count, &c->rec_all, &c->rec_cov, &c->cov_site,
-                      &c->fo, &c->targets, &c->weight, &c->nrefpanel, &c->af, &c->site_ll, &c->win_ll, &c->row_tab, &c->t32, &c->t32c, &c->seg_first,
-                      &c->segs, &c->runs, &c->wconst, &c->wtarget, &c->twords, &c->wtarget_mt, &c->twords_mt, &c->vals, &c->order, &c->pow1, &c->pow2, &c->pow3, &c->partial, &c->aimg, &c->wc_slot, &c->partial_h, &c->base_w, &c->p2w, &c->p2c, &c->p2_tw, &c->p2_wt, &c->fragb,
-                      &c->in_row, &c->in_ref, &c->in_alt, &c->scan_tmp, &c->info_dev, &c->wraw, &c->nck_dev, &c->powb,
-                      &c->win_first, &c->win_last, &c->llr_seg, &c->llr_part, &c->llr_out, &c->cand_row, &c->cand_ref, &c->cand_alt,
-                      &c->cand_fo, &c->sel_cand})
-        release(*b);
-    for (hipEvent_t ev : c->ev_up)
+    c->free_bufs();
+    for (hipEvent_t ev : c->sites.ev_up)
         if (ev)
             (void)hipEventDestroy(ev);
-    if (c->ev_prep2)
-        (void)hipEventDestroy(c->ev_prep2);
-    if (c->ev_prepA)
-        (void)hipEventDestroy(c->ev_prepA);
-    for (int b = 0; b < 2 * ibdg_ctx::STAGE_WORKERS; ++b) {
-        if (c->stage_ev[b])
-            (void)hipEventDestroy(c->stage_ev[b]);
-        if (c->stage[b])
-            (void)hipHostFree(c->stage[b]);
+    if (c->sites.ev_prep2)
+        (void)hipEventDestroy(c->sites.ev_prep2);
+    if (c->sites.ev_prepA)
+        (void)hipEventDestroy(c->sites.ev_prepA);
+    for (int b = 0; b < 2 * ibdg_ctx::Staging::WORKERS; ++b) {
+        if (c->stg.stage_ev[b])
+            (void)hipEventDestroy(c->stg.stage_ev[b]);
+        if (c->stg.stage[b])
+            (void)hipHostFree(c->stg.stage[b]);
     }
-    if (c->info_h)
-        (void)hipHostFree(c->info_h);
-    for (auto &E : c->evs)
+    if (c->sites.info_h)
+        (void)hipHostFree(c->sites.info_h);
+    for (auto &E : c->tl.evs)
         for (hipEvent_t ev : {E.start_own, E.ld_end, E.k_start, E.k_stop, E.s2_start, E.s2_count, E.s2_end, E.prep})
             if (ev)
                 (void)hipEventDestroy(ev);
@@ -1166,7 +932,7 @@ void ibdg_destroy(ibdg_ctx *c)
         if (c->ring.stage_ev[i])
             (void)hipEventDestroy(c->ring.stage_ev[i]);
     }
-    for (hipEvent_t ev : {c->ring.ready, c->ring.ev_s3sync, c->ev_fb})
+    for (hipEvent_t ev : {c->ring.ready, c->ring.ev_s3sync, c->fb.ev_fb})
         if (ev)
             (void)hipEventDestroy(ev);
     if (c->stream3)
@@ -1243,104 +1009,92 @@ int ibdg_upload_panel_dev(ibdg_ctx *c, const void *dev_rows, size_t n_rows, unsi
 // stopped half way: prep_dirty
 static int clean_prep_info(ibdg_ctx *c)
 {
-    const bool fresh_info = !c->info_dev.p;
-    if (ensure(c, c->info_dev, sizeof(ibdg::PrepInfo)))
+    const bool fresh_info = !c->sites.info_dev.p;
+    if (ensure(c, c->sites.info_dev, sizeof(ibdg::PrepInfo)))
         return 1;
-    if (fresh_info || c->prep_dirty) {
+    if (fresh_info || c->sites.prep_dirty) {
         ibdg::PrepInfo init;
         memset(&init, 0, sizeof init);
         init.err_row_site = init.err_cov_site = init.first_row = 0xffffffffu;
-        HIP_TRY(c, hipMemcpyAsync(c->info_dev.p, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->sites.info_dev.p, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));          // `init` is a local
-        c->prep_dirty = false;
+        c->sites.prep_dirty = false;
     }
     return 0;
 }
 
 // Everything an upload of sites does once the three input arrays are on the device.  fo_ready: the sites' -A triples are in
-// c->fo already (ibdg_select_variable_sites compacts the candidates' there); f_override is not looked at.
+// c->sites.fo already (ibdg_select_variable_sites compacts the candidates' there); f_override is not looked at.
 static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *d_ref, const uint8_t *d_alt,
                              const double *f_override, size_t n_sites, unsigned window, bool fo_ready = false)
 {
-    c->n_sites = n_sites;
-    c->window = window;
-    c->n_cov = 0;
-    c->n_win = 0;
-    c->sites_valid = false;
-    c->have_results = false;
-    c->pop_sites_ok = false;
-    c->win_bounds_valid = false;
-    c->have_fo = false;
-    c->sel_valid = false;
+    sites_replaced(c);
+    c->sites.n_sites = n_sites;
+    c->sites.window = window;
     // segments of stage B: at most one per site, and in file order at most windows + tiles of the panel
     // (compacted tiles: windows + tiles of their virtual rows, at most window + 31 per window)
     const size_t n_win_max = (n_sites + window - 1) / window;
-    const size_t seg_room = std::min<size_t>(n_sites, std::max<size_t>(n_win_max + (c->n_rows + 31) / 32 + 1,
+    const size_t seg_room = std::min<size_t>(n_sites, std::max<size_t>(n_win_max + (c->pan.n_rows + 31) / 32 + 1,
                                                                       n_win_max + (n_win_max * ((size_t)window + 31) + 31) / 32 + 1));
-    if (ensure(c, c->rec_all, n_sites * 8) || ensure(c, c->rec_cov, n_sites * 8) || ensure(c, c->cov_site, n_sites * 4) ||
-        ensure(c, c->scan_tmp, ibdg::prep_scan_blocks(std::max<size_t>(n_sites, 1)) * 4) || clean_prep_info(c) ||
-        (c->pop_lut_ok && (ensure(c, c->segs, seg_room * sizeof(ibdg::Seg)) || ensure(c, c->seg_first, seg_room * 4))))
+    if (ensure(c, c->sites.rec_all, n_sites * 8) || ensure(c, c->sites.rec_cov, n_sites * 8) || ensure(c, c->sites.cov_site, n_sites * 4) ||
+        ensure(c, c->sites.scan_tmp, ibdg::prep_scan_blocks(std::max<size_t>(n_sites, 1)) * 4) || clean_prep_info(c) ||
+        (c->tab.pop_lut_ok && (ensure(c, c->lay.segs, seg_room * sizeof(ibdg::Seg)) || ensure(c, c->lay.seg_first, seg_room * 4))))
         return 1;
-    ++c->sites_gen;
-    ++c->up_gen;
-    c->relayout_credit = 0;
-    c->ibd0_runs = 0;
-    c->seg_room = c->pop_lut_ok ? seg_room : 0;
-    c->compact = false;
+    c->sites.seg_room = c->tab.pop_lut_ok ? seg_room : 0;
     if (n_sites) {
-        c->prep_dirty = true;
+        c->sites.prep_dirty = true;
         ibdg::PrepSiteArgs pa;
         pa.row_index = d_row;
         pa.n_ref = d_ref;
         pa.n_alt = d_alt;
         pa.n_sites = n_sites;
-        pa.n_rows = c->n_rows;
-        pa.max_cov = c->max_cov;
-        pa.rec_all = (uint2 *)c->rec_all.p;
-        pa.rec_cov = (uint2 *)c->rec_cov.p;
-        pa.cov_site = (uint32_t *)c->cov_site.p;
-        pa.block_tmp = (uint32_t *)c->scan_tmp.p;
-        pa.info = (ibdg::PrepInfo *)c->info_dev.p;
-        pa.mirror = c->info_h;
-        pa.seq = ++c->prep_seq;
+        pa.n_rows = c->pan.n_rows;
+        pa.max_cov = c->tab.max_cov;
+        pa.rec_all = (uint2 *)c->sites.rec_all.p;
+        pa.rec_cov = (uint2 *)c->sites.rec_cov.p;
+        pa.cov_site = (uint32_t *)c->sites.cov_site.p;
+        pa.block_tmp = (uint32_t *)c->sites.scan_tmp.p;
+        pa.info = (ibdg::PrepInfo *)c->sites.info_dev.p;
+        pa.mirror = c->sites.info_h;
+        pa.seq = ++c->sites.prep_seq;
         ibdg::launch_prep_sites(pa, c->stream);
         HIP_TRY(c, hipGetLastError());
         // (the hand-over comes from the scan, BEFORE the scatter kernel: whatever reads the site records on the second
         // stream waits for this event; the main stream is ordered anyway)
-        HIP_TRY(c, hipEventRecord(c->ev_prepA, c->stream));
-        if (wait_info(c, c->prep_seq))
+        HIP_TRY(c, hipEventRecord(c->sites.ev_prepA, c->stream));
+        if (wait_info(c, c->sites.prep_seq))
             return 1;
-        c->prep_dirty = false;                  // the stage's last workgroup has left everything clean
+        c->sites.prep_dirty = false;                  // the stage's last workgroup has left everything clean
     } else {
-        c->prep_dirty = false;
-        memset(c->info_h, 0, sizeof(ibdg::PrepInfo));
-        c->info_h->err_row_site = c->info_h->err_cov_site = c->info_h->first_row = 0xffffffffu;
-        c->info_h->seq = c->prep_seq;
+        c->sites.prep_dirty = false;
+        memset(c->sites.info_h, 0, sizeof(ibdg::PrepInfo));
+        c->sites.info_h->err_row_site = c->sites.info_h->err_cov_site = c->sites.info_h->first_row = 0xffffffffu;
+        c->sites.info_h->seq = c->sites.prep_seq;
     }
-    const ibdg::PrepInfo &I = *c->info_h;
+    const ibdg::PrepInfo &I = *c->sites.info_h;
     if (I.err_row_site != 0xffffffffu || I.err_cov_site != 0xffffffffu) {
         // the first offending site in file order, its row checked before its counts (as a loop over the sites would)
-        c->n_sites = 0;
+        c->sites.n_sites = 0;
         if (I.err_row_site <= I.err_cov_site) {
             uint32_t row = 0;
             HIP_TRY(c, hipMemcpy(&row, d_row + I.err_row_site, 4, hipMemcpyDeviceToHost));
             return fail(c, "[::] ERROR in ibdg_upload_sites: row_index[%zu]=%u outside the panel (%zu rows)",
-                        (size_t)I.err_row_site, row, c->n_rows);
+                        (size_t)I.err_row_site, row, c->pan.n_rows);
         }
         uint8_t r = 0, a = 0;
         HIP_TRY(c, hipMemcpy(&r, d_ref + I.err_cov_site, 1, hipMemcpyDeviceToHost));
         HIP_TRY(c, hipMemcpy(&a, d_alt + I.err_cov_site, 1, hipMemcpyDeviceToHost));
         return fail(c, "[::] ERROR in ibdg_upload_sites: site %zu has n_ref+n_alt=%u > max_cov=%u",
-                    (size_t)I.err_cov_site, (unsigned)r + a, c->max_cov);
+                    (size_t)I.err_cov_site, (unsigned)r + a, c->tab.max_cov);
     }
-    c->n_cov = I.n_cov;
-    c->first_row = I.first_row;             // (the mirror is overwritten by stage B's hand-over)
-    c->last_row = I.last_row;
-    c->n_win = (uint32_t)(((uint64_t)c->n_cov + window - 1) / window);
+    c->sites.n_cov = I.n_cov;
+    c->sites.first_row = I.first_row;             // (the mirror is overwritten by stage B's hand-over)
+    c->sites.last_row = I.last_row;
+    c->sites.n_win = (uint32_t)(((uint64_t)c->sites.n_cov + window - 1) / window);
     if (build_layout(c))
         return 1;
     if (fo_ready) {
-        c->have_fo = true;
+        c->sites.have_fo = true;
     } else if (f_override) {
         std::vector<double> fo(3 * n_sites);
         for (size_t s = 0; s < n_sites; ++s) {
@@ -1349,14 +1103,14 @@ static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *
             if (f == f) {
                 fo[3 * s + 1] = libm_pow(1 - f, 2.0);
                 fo[3 * s + 2] = libm_pow(f, 2.0);
-                c->have_fo = true;
+                c->sites.have_fo = true;
             } else {
                 fo[3 * s + 1] = fo[3 * s + 2] = 0.0;
             }
         }
-        if (c->have_fo) {
-            if (ensure(c, c->fo, fo.size() * 8)) return 1;
-            HIP_TRY(c, hipMemcpyAsync(c->fo.p, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, c->stream));
+        if (c->sites.have_fo) {
+            if (ensure(c, c->sites.fo, fo.size() * 8)) return 1;
+            HIP_TRY(c, hipMemcpyAsync(c->sites.fo.p, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));          // `fo` is a local
         }
     }
@@ -1366,15 +1120,15 @@ static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *
 static int upload_sites_check(ibdg_ctx *c, const void *n_ref, const void *n_alt, bool have_rows, size_t n_sites,
                               unsigned window)
 {
-    if (!c->panel.p || c->n_ids == 0) return fail(c, "[::] ERROR in ibdg_upload_sites: no panel uploaded");
+    if (!c->pan.panel.p || c->pan.n_ids == 0) return fail(c, "[::] ERROR in ibdg_upload_sites: no panel uploaded");
     if (window < 1) return fail(c, "[::] ERROR: Invalid window size (-w) of %u (must be >= 1).", window);
     if (n_sites && (!n_ref || !n_alt))
         return fail(c, "[::] ERROR in ibdg_upload_sites: NULL input array");
     if (n_sites > 0xffffffffull)
         return fail(c, "[::] ERROR in ibdg_upload_sites: more than 2^32-1 rows in one call");
-    if (!have_rows && n_sites > c->n_rows)
-        return fail(c, "[::] ERROR in ibdg_upload_sites: row_index[%zu]=%zu outside the panel (%zu rows)", c->n_rows,
-                    c->n_rows, c->n_rows);
+    if (!have_rows && n_sites > c->pan.n_rows)
+        return fail(c, "[::] ERROR in ibdg_upload_sites: row_index[%zu]=%zu outside the panel (%zu rows)", c->pan.n_rows,
+                    c->pan.n_rows, c->pan.n_rows);
     return 0;
 }
 
@@ -1390,10 +1144,10 @@ static int upload_sites_finish(ibdg_ctx *c, int rc, std::chrono::steady_clock::t
 {
     if (rc)
         return rc;
-    c->sites_valid = true;
-    HIP_TRY(c, hipEventRecord(c->ev_up[2], c->stream));
-    c->up_ms_pending = true;
-    c->up_ms[2] = (float)wall_ms(t0);
+    c->sites.sites_valid = true;
+    HIP_TRY(c, hipEventRecord(c->sites.ev_up[2], c->stream));
+    c->sites.up_ms_pending = true;
+    c->sites.up_ms[2] = (float)wall_ms(t0);
     return 0;
 }
 
@@ -1404,19 +1158,19 @@ int ibdg_upload_sites(ibdg_ctx *c, const uint32_t *row_index, const uint8_t *n_r
     const auto t0 = std::chrono::steady_clock::now();
     if (upload_sites_check(c, n_ref, n_alt, row_index != nullptr, n_sites, window)) return 1;
     if (quiesce(c)) return 1;
-    if (ensure(c, c->in_ref, n_sites) || ensure(c, c->in_alt, n_sites) || (row_index && ensure(c, c->in_row, n_sites * 4)))
+    if (ensure(c, c->sites.in_ref, n_sites) || ensure(c, c->sites.in_alt, n_sites) || (row_index && ensure(c, c->sites.in_row, n_sites * 4)))
         return 1;
-    HIP_TRY(c, hipEventRecord(c->ev_up[0], c->stream));
+    HIP_TRY(c, hipEventRecord(c->sites.ev_up[0], c->stream));
     if (n_sites) {
         // 6 bytes per row (2 when the rows are the panel's own); pinned arrays (ibdg_host_alloc) go at link speed
         if (row_index)
-            HIP_TRY(c, hipMemcpyAsync(c->in_row.p, row_index, n_sites * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->in_ref.p, n_ref, n_sites, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->in_alt.p, n_alt, n_sites, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->sites.in_row.p, row_index, n_sites * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->sites.in_ref.p, n_ref, n_sites, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->sites.in_alt.p, n_alt, n_sites, hipMemcpyHostToDevice, c->stream));
     }
-    HIP_TRY(c, hipEventRecord(c->ev_up[1], c->stream));
-    return upload_sites_finish(c, upload_sites_core(c, row_index ? (const uint32_t *)c->in_row.p : nullptr,
-                                                    (const uint8_t *)c->in_ref.p, (const uint8_t *)c->in_alt.p,
+    HIP_TRY(c, hipEventRecord(c->sites.ev_up[1], c->stream));
+    return upload_sites_finish(c, upload_sites_core(c, row_index ? (const uint32_t *)c->sites.in_row.p : nullptr,
+                                                    (const uint8_t *)c->sites.in_ref.p, (const uint8_t *)c->sites.in_alt.p,
                                                     f_override, n_sites, window), t0);
 }
 
@@ -1430,17 +1184,17 @@ int ibdg_upload_sites_dev(ibdg_ctx *c, const void *dev_row_index, const void *de
     // the arrays may have been produced on another stream (e.g. torch's): make them visible first.  This waits for the
     // whole device -- other contexts' kernels included -- so a caller who knows the arrays are complete says so
     // (option "dev_inputs_ready") and its preparation can run under another context's --LD kernel.
-    if (!c->opt_dev_inputs_ready)
+    if (!c->opt.dev_inputs_ready)
         HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipEventRecord(c->ev_up[0], c->stream));
-    HIP_TRY(c, hipEventRecord(c->ev_up[1], c->stream));
+    HIP_TRY(c, hipEventRecord(c->sites.ev_up[0], c->stream));
+    HIP_TRY(c, hipEventRecord(c->sites.ev_up[1], c->stream));
     const int rc = upload_sites_core(c, (const uint32_t *)dev_row_index, (const uint8_t *)dev_n_ref,
                                      (const uint8_t *)dev_n_alt, f_override, n_sites, window);
     // the caller may free or reuse its arrays when this returns: the last kernel that reads them (k_prep_site_scatter) must
     // be done.  Where the layout's second stage was waited for it is (nothing to wait for); a clamped table, an empty
     // site list or a layout without segments leave that stage out
     if (rc == 0 && n_sites)
-        HIP_TRY(c, hipEventSynchronize(c->ev_prepA));
+        HIP_TRY(c, hipEventSynchronize(c->sites.ev_prepA));
     return upload_sites_finish(c, rc, t0);
 }
 
@@ -1454,16 +1208,16 @@ int ibdg_upload_candidates(ibdg_ctx *c, const uint32_t *row_index, const uint8_t
     // what stage A checks per upload of sites, once for all the lists cut from these candidates -- and the selection kernels
     // index the panel with these rows
     for (size_t s = 0; s < n_cand; ++s) {
-        if (row_index && row_index[s] >= c->n_rows)
+        if (row_index && row_index[s] >= c->pan.n_rows)
             return fail(c, "[::] ERROR in ibdg_upload_candidates: row_index[%zu]=%u outside the panel (%zu rows)", s,
-                        row_index[s], c->n_rows);
-        if ((unsigned)n_ref[s] + n_alt[s] > c->max_cov)
+                        row_index[s], c->pan.n_rows);
+        if ((unsigned)n_ref[s] + n_alt[s] > c->tab.max_cov)
             return fail(c, "[::] ERROR in ibdg_upload_candidates: candidate %zu has n_ref+n_alt=%u > max_cov=%u", s,
-                        (unsigned)n_ref[s] + n_alt[s], c->max_cov);
+                        (unsigned)n_ref[s] + n_alt[s], c->tab.max_cov);
     }
     if (quiesce(c)) return 1;
-    c->cand_valid = false;
-    if (ensure(c, c->cand_ref, n_cand) || ensure(c, c->cand_alt, n_cand) || (row_index && ensure(c, c->cand_row, n_cand * 4)))
+    c->cand.valid = false;
+    if (ensure(c, c->cand.ref, n_cand) || ensure(c, c->cand.alt, n_cand) || (row_index && ensure(c, c->cand.row, n_cand * 4)))
         return 1;
     // the -A triples with the host's libm, once for every list cut from these candidates
     std::vector<double> fo;
@@ -1481,82 +1235,81 @@ int ibdg_upload_candidates(ibdg_ctx *c, const uint32_t *row_index, const uint8_t
                 fo[3 * s + 1] = fo[3 * s + 2] = 0.0;
             }
         }
-        if (have_fo && ensure(c, c->cand_fo, fo.size() * 8)) return 1;
+        if (have_fo && ensure(c, c->cand.fo, fo.size() * 8)) return 1;
     }
     if (n_cand) {
         if (row_index)
-            HIP_TRY(c, hipMemcpyAsync(c->cand_row.p, row_index, n_cand * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->cand_ref.p, n_ref, n_cand, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->cand_alt.p, n_alt, n_cand, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->cand.row.p, row_index, n_cand * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->cand.ref.p, n_ref, n_cand, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->cand.alt.p, n_alt, n_cand, hipMemcpyHostToDevice, c->stream));
         if (have_fo)
-            HIP_TRY(c, hipMemcpyAsync(c->cand_fo.p, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->cand.fo.p, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));              // `fo` is a local, the arrays are the caller's
     }
-    c->n_cand = n_cand;
-    c->cand_have_rows = row_index != nullptr;
-    c->cand_have_fo = have_fo;
-    c->cand_valid = true;
+    c->cand.n_cand = n_cand;
+    c->cand.have_rows = row_index != nullptr;
+    c->cand.have_fo = have_fo;
+    c->cand.valid = true;
     return 0;
 }
 
-size_t ibdg_num_candidates(const ibdg_ctx *c) { return c && c->cand_valid ? c->n_cand : 0; }
+size_t ibdg_num_candidates(const ibdg_ctx *c) { return c && c->cand.valid ? c->cand.n_cand : 0; }
 
 int ibdg_select_variable_sites(ibdg_ctx *c, uint32_t target, unsigned window)
 {
     if (!c) return 1;
     const auto t0 = std::chrono::steady_clock::now();
-    if (!c->panel.p || c->n_ids == 0) return fail(c, "[::] ERROR in ibdg_select_variable_sites: no panel uploaded");
-    if (!c->cand_valid) return fail(c, "[::] ERROR in ibdg_select_variable_sites: no candidates uploaded");
-    if (target >= c->n_ids)
+    if (!c->pan.panel.p || c->pan.n_ids == 0) return fail(c, "[::] ERROR in ibdg_select_variable_sites: no panel uploaded");
+    if (!c->cand.valid) return fail(c, "[::] ERROR in ibdg_select_variable_sites: no candidates uploaded");
+    if (target >= c->pan.n_ids)
         return fail(c, "[::] ERROR in ibdg_select_variable_sites: individual %u outside the panel (%u individuals)", target,
-                    c->n_ids);
+                    c->pan.n_ids);
     if (window < 1) return fail(c, "[::] ERROR: Invalid window size (-w) of %u (must be >= 1).", window);
     if (quiesce(c)) return 1;
-    const size_t n = c->n_cand;
-    if (ensure(c, c->in_ref, n) || ensure(c, c->in_alt, n) || (c->cand_have_rows && ensure(c, c->in_row, n * 4)) ||
-        ensure(c, c->sel_cand, n * 4) || (c->cand_have_fo && ensure(c, c->fo, n * 24)) ||
-        ensure(c, c->scan_tmp, ibdg::prep_scan_blocks(std::max<size_t>(n, 1)) * 4) || clean_prep_info(c))
+    const size_t n = c->cand.n_cand;
+    if (ensure(c, c->sites.in_ref, n) || ensure(c, c->sites.in_alt, n) || (c->cand.have_rows && ensure(c, c->sites.in_row, n * 4)) ||
+        ensure(c, c->cand.sel_cand, n * 4) || (c->cand.have_fo && ensure(c, c->sites.fo, n * 24)) ||
+        ensure(c, c->sites.scan_tmp, ibdg::prep_scan_blocks(std::max<size_t>(n, 1)) * 4) || clean_prep_info(c))
         return 1;
-    c->sel_valid = false;
-    c->sites_valid = false;
-    HIP_TRY(c, hipEventRecord(c->ev_up[0], c->stream));
+    sites_replaced(c);                  // (the selection kernels overwrite in_* and sel_cand)
+    HIP_TRY(c, hipEventRecord(c->sites.ev_up[0], c->stream));
     size_t n_sel = 0;
     if (n) {
         ibdg::SelectArgs sa;
-        sa.row = c->cand_have_rows ? (const uint32_t *)c->cand_row.p : nullptr;
-        sa.n_ref = (const uint8_t *)c->cand_ref.p;
-        sa.n_alt = (const uint8_t *)c->cand_alt.p;
-        sa.fo = c->cand_have_fo ? (const double *)c->cand_fo.p : nullptr;
+        sa.row = c->cand.have_rows ? (const uint32_t *)c->cand.row.p : nullptr;
+        sa.n_ref = (const uint8_t *)c->cand.ref.p;
+        sa.n_alt = (const uint8_t *)c->cand.alt.p;
+        sa.fo = c->cand.have_fo ? (const double *)c->cand.fo.p : nullptr;
         sa.n_cand = n;
         sa.target = target;
-        sa.t32 = c->pop_lut_ok ? (const uint4 *)c->t32.p : nullptr;      // (no transposed panel with a clamped table)
-        sa.n_pairs = c->n_pairs;
-        sa.panel = (const uint64_t *)c->panel.p;
-        sa.stride = c->stride;
-        sa.out_row = (uint32_t *)c->in_row.p;
-        sa.out_ref = (uint8_t *)c->in_ref.p;
-        sa.out_alt = (uint8_t *)c->in_alt.p;
-        sa.out_cand = (uint32_t *)c->sel_cand.p;
-        sa.out_fo = (double *)c->fo.p;
-        sa.block_tmp = (uint32_t *)c->scan_tmp.p;
-        sa.info = (ibdg::PrepInfo *)c->info_dev.p;
-        sa.mirror = c->info_h;
-        sa.seq = ++c->prep_seq;
-        c->prep_dirty = true;
+        sa.t32 = c->tab.pop_lut_ok ? (const uint4 *)c->pan.t32.p : nullptr;      // (no transposed panel with a clamped table)
+        sa.n_pairs = c->pan.n_pairs;
+        sa.panel = (const uint64_t *)c->pan.panel.p;
+        sa.stride = c->pan.stride;
+        sa.out_row = (uint32_t *)c->sites.in_row.p;
+        sa.out_ref = (uint8_t *)c->sites.in_ref.p;
+        sa.out_alt = (uint8_t *)c->sites.in_alt.p;
+        sa.out_cand = (uint32_t *)c->cand.sel_cand.p;
+        sa.out_fo = (double *)c->sites.fo.p;
+        sa.block_tmp = (uint32_t *)c->sites.scan_tmp.p;
+        sa.info = (ibdg::PrepInfo *)c->sites.info_dev.p;
+        sa.mirror = c->sites.info_h;
+        sa.seq = ++c->sites.prep_seq;
+        c->sites.prep_dirty = true;
         ibdg::launch_select_sites(sa, c->stream);
         HIP_TRY(c, hipGetLastError());
         // the number selected comes with the scan's hand-over, like stage A's covered rows: the scatter kernel runs on while
         // the host sizes stage A's buffers and queues it behind
-        if (wait_info(c, c->prep_seq))
+        if (wait_info(c, c->sites.prep_seq))
             return 1;
-        c->prep_dirty = false;
-        n_sel = c->info_h->n_cov;
+        c->sites.prep_dirty = false;
+        n_sel = c->sites.info_h->n_cov;
     }
-    HIP_TRY(c, hipEventRecord(c->ev_up[1], c->stream));
+    HIP_TRY(c, hipEventRecord(c->sites.ev_up[1], c->stream));
     // candidates that are the panel's own rows: a selected site's candidate index is its row
-    const uint32_t *d_row = (const uint32_t *)(c->cand_have_rows ? c->in_row.p : c->sel_cand.p);
-    const int rc = upload_sites_core(c, d_row, (const uint8_t *)c->in_ref.p, (const uint8_t *)c->in_alt.p, nullptr, n_sel,
-                                     window, c->cand_have_fo && n_sel);
+    const uint32_t *d_row = (const uint32_t *)(c->cand.have_rows ? c->sites.in_row.p : c->cand.sel_cand.p);
+    const int rc = upload_sites_core(c, d_row, (const uint8_t *)c->sites.in_ref.p, (const uint8_t *)c->sites.in_alt.p, nullptr, n_sel,
+                                     window, c->cand.have_fo && n_sel);
     if (rc) {
         // (rows and read counts were checked per candidate by ibdg_upload_candidates; whatever is left names a SITE of the
         // selected list, whose candidate is that site's entry of ibdg_get_site_candidates' map)
@@ -1564,32 +1317,32 @@ int ibdg_select_variable_sites(ibdg_ctx *c, uint32_t target, unsigned window)
                   " candidates: a site number counts the selected candidates, in candidate order]";
         return rc;
     }
-    c->sel_valid = true;
+    c->cand.sel_valid = true;
     return upload_sites_finish(c, 0, t0);
 }
 
 int ibdg_get_site_candidates(ibdg_ctx *c, uint32_t *out)
 {
     if (!c) return 1;
-    if (!c->sel_valid || !c->sites_valid)
+    if (!c->cand.sel_valid || !c->sites.sites_valid)
         return fail(c, "[::] ERROR in ibdg_get_site_candidates: the current site list was not made by ibdg_select_variable_sites");
-    if (c->n_sites == 0) return 0;
+    if (c->sites.n_sites == 0) return 0;
     if (!out) return fail(c, "[::] ERROR in ibdg_get_site_candidates: NULL output array");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(out, c->sel_cand.p, c->n_sites * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, c->cand.sel_cand.p, c->sites.n_sites * 4, hipMemcpyDeviceToHost, c->stream));
     return quiesce(c);
 }
 
 int ibdg_upload_ms(ibdg_ctx *c, float out[3])
 {
     if (!c || !out) return 1;
-    if (c->up_ms_pending) {
-        HIP_TRY(c, hipEventSynchronize(c->ev_up[2]));
-        HIP_TRY(c, hipEventElapsedTime(&c->up_ms[0], c->ev_up[0], c->ev_up[1]));
-        HIP_TRY(c, hipEventElapsedTime(&c->up_ms[1], c->ev_up[1], c->ev_up[2]));
-        c->up_ms_pending = false;
+    if (c->sites.up_ms_pending) {
+        HIP_TRY(c, hipEventSynchronize(c->sites.ev_up[2]));
+        HIP_TRY(c, hipEventElapsedTime(&c->sites.up_ms[0], c->sites.ev_up[0], c->sites.ev_up[1]));
+        HIP_TRY(c, hipEventElapsedTime(&c->sites.up_ms[1], c->sites.ev_up[1], c->sites.ev_up[2]));
+        c->sites.up_ms_pending = false;
     }
-    for (int i = 0; i < 3; ++i) out[i] = c->up_ms[i];
+    for (int i = 0; i < 3; ++i) out[i] = c->sites.up_ms[i];
     return 0;
 }
 
@@ -1607,32 +1360,32 @@ void ibdg_host_free(void *p)
         (void)hipHostFree(p);
 }
 
-size_t ibdg_num_sites(const ibdg_ctx *c) { return c ? c->n_sites : 0; }
-size_t ibdg_num_windows(const ibdg_ctx *c) { return c ? c->n_win : 0; }
+size_t ibdg_num_sites(const ibdg_ctx *c) { return c ? c->sites.n_sites : 0; }
+size_t ibdg_num_windows(const ibdg_ctx *c) { return c ? c->sites.n_win : 0; }
 size_t ibdg_num_targets(const ibdg_ctx *c) { return c && c->have_results ? c->n_targets : 0; }
 
 int ibdg_get_windows(ibdg_ctx *c, uint32_t *first, uint32_t *last, uint32_t *n_covered)
 {
     if (!c) return 1;
-    if (c->n_win && (first || last) && !c->win_bounds_valid) {
+    if (c->sites.n_win && (first || last) && !c->sites.win_bounds_valid) {
         if (quiesce(c)) return 1;
-        if (ensure(c, c->win_first, (size_t)c->n_win * 4) || ensure(c, c->win_last, (size_t)c->n_win * 4))
+        if (ensure(c, c->sites.win_first, (size_t)c->sites.n_win * 4) || ensure(c, c->sites.win_last, (size_t)c->sites.n_win * 4))
             return 1;
-        ibdg::launch_prep_win_bounds((const uint32_t *)c->cov_site.p, c->n_cov, c->window, c->n_win,
-                                     (uint32_t *)c->win_first.p, (uint32_t *)c->win_last.p, c->stream);
+        ibdg::launch_prep_win_bounds((const uint32_t *)c->sites.cov_site.p, c->sites.n_cov, c->sites.window, c->sites.n_win,
+                                     (uint32_t *)c->sites.win_first.p, (uint32_t *)c->sites.win_last.p, c->stream);
         HIP_TRY(c, hipGetLastError());
-        c->win_first_h.resize(c->n_win);
-        c->win_last_h.resize(c->n_win);
-        HIP_TRY(c, hipMemcpyAsync(c->win_first_h.data(), c->win_first.p, (size_t)c->n_win * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->win_last_h.data(), c->win_last.p, (size_t)c->n_win * 4, hipMemcpyDeviceToHost, c->stream));
+        c->sites.win_first_h.resize(c->sites.n_win);
+        c->sites.win_last_h.resize(c->sites.n_win);
+        HIP_TRY(c, hipMemcpyAsync(c->sites.win_first_h.data(), c->sites.win_first.p, (size_t)c->sites.n_win * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->sites.win_last_h.data(), c->sites.win_last.p, (size_t)c->sites.n_win * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->win_bounds_valid = true;
+        c->sites.win_bounds_valid = true;
     }
-    for (uint32_t w = 0; w < c->n_win; ++w) {
-        const uint64_t b = (uint64_t)w * c->window;
-        const uint64_t e = std::min<uint64_t>(b + c->window, c->n_cov);
-        if (first) first[w] = c->win_first_h[w];
-        if (last) last[w] = c->win_last_h[w];
+    for (uint32_t w = 0; w < c->sites.n_win; ++w) {
+        const uint64_t b = (uint64_t)w * c->sites.window;
+        const uint64_t e = std::min<uint64_t>(b + c->sites.window, c->sites.n_cov);
+        if (first) first[w] = c->sites.win_first_h[w];
+        if (last) last[w] = c->sites.win_last_h[w];
         if (n_covered) n_covered[w] = (uint32_t)(e - b);
     }
     return 0;
@@ -1643,6 +1396,7 @@ int ibdg_get_windows(ibdg_ctx *c, uint32_t *first, uint32_t *last, uint32_t *n_c
 namespace {        // ibdg_run's stages
 
 using Ring = ibdg_ctx::Ring;
+using EvSet = ibdg_ctx::Timeline::EvSet;
 
 // slot i of a buffer cut into n equal slots, each a multiple of `align` bytes (the per-individual ring, ibdg_ctx::Ring)
 template <class P>
@@ -1695,7 +1449,7 @@ int ring_prepare(ibdg_ctx *c, const uint32_t *targets, size_t T, size_t lanes)
         HIP_TRY(c, hipEventSynchronize(R.stage_ev[st]));      // (its copy was queued STAGE_SLOTS runs ago; never recorded: no wait)
         std::copy(targets, targets + T, R.stage[st]);
     }
-    const bool on_s3 = ahead && c->opt_prep_ahead && c->opt_async;
+    const bool on_s3 = ahead && c->opt.prep_ahead && c->opt.async;
     const hipStream_t ps = on_s3 ? c->stream3 : c->stream;
     if (on_s3)
         R.unsettled = true;
@@ -1716,8 +1470,8 @@ int ring_prepare(ibdg_ctx *c, const uint32_t *targets, size_t T, size_t lanes)
         HIP_TRY(c, hipMemcpyAsync(d_tg, R.stage[st], T * 4, hipMemcpyHostToDevice, ps));
         HIP_TRY(c, hipEventRecord(R.stage_ev[st], ps));
     }
-    ibdg::launch_target_weights((const double *)c->base_w.p, d_tg, inline_tg ? targets : nullptr, (uint32_t)T, (uint32_t)lanes,
-                                c->base_sum, ring_slot<double>(c->weight, R.cur, Ring::SLOTS),
+    ibdg::launch_target_weights((const double *)c->bg.base_w.p, d_tg, inline_tg ? targets : nullptr, (uint32_t)T, (uint32_t)lanes,
+                                c->bg.base_sum, ring_slot<double>(c->weight, R.cur, Ring::SLOTS),
                                 ring_slot<int>(c->nrefpanel, R.nref, Ring::NREF_SLOTS), ps);
     if (!on_s3) {
         // prepared on the main stream (more than AHEAD_MAX_T individuals, "prep_ahead" 0, no queue): the second stream reads
@@ -1726,8 +1480,7 @@ int ring_prepare(ibdg_ctx *c, const uint32_t *targets, size_t T, size_t lanes)
         HIP_TRY(c, hipEventRecord(R.ready, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->stream2, R.ready, 0));
     }
-    c->prev_targets.assign(targets, targets + T);
-    c->wt_key.gen = 0;         // the images in wtarget / twords are another individual's
+    targets_changed(c, targets, T);
     return 0;
 }
 
@@ -1749,21 +1502,21 @@ int set_background(ibdg_ctx *c, const uint8_t *bg_count, int pu_id, size_t lanes
 {
     std::vector<double> wb(lanes, 0.0);
     int sum = 0;
-    for (unsigned n = 0; n < c->n_ids; ++n) {
+    for (unsigned n = 0; n < c->pan.n_ids; ++n) {
         const unsigned k = bg_count ? bg_count[n] : 1u;
         if ((int)n != pu_id && k != 0) {
             wb[n] = (double)k;
             sum += (int)k;
         }
     }
-    if (ensure(c, c->base_w, lanes * 8)) return 1;
-    HIP_TRY(c, hipMemcpyAsync(c->base_w.p, wb.data(), lanes * 8, hipMemcpyHostToDevice, c->stream));
+    if (ensure(c, c->bg.base_w, lanes * 8)) return 1;
+    HIP_TRY(c, hipMemcpyAsync(c->bg.base_w.p, wb.data(), lanes * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));          // the host vector goes out of scope
-    c->chain_ok = false;
-    ++c->bg_gen;
-    c->base_sum = sum;
-    c->prev_pu = pu_id; c->prev_has_bg = bg_count ? 1 : 0; c->prev_lanes = lanes;
-    c->prev_bg.assign(bg_count, bg_count + (bg_count ? c->n_ids : 0));
+    c->tl.chain_ok = false;
+    background_changed(c);
+    c->bg.base_sum = sum;
+    c->bg.prev_pu = pu_id; c->bg.prev_has_bg = bg_count ? 1 : 0; c->bg.prev_lanes = lanes;
+    c->bg.prev_bg.assign(bg_count, bg_count + (bg_count ? c->pan.n_ids : 0));
     return 0;
 }
 
@@ -1783,15 +1536,15 @@ int set_background(ibdg_ctx *c, const uint8_t *bg_count, int pu_id, size_t lanes
 // 0.18 ms, 15 until round 5)
 int relayout_when_paid(ibdg_ctx *c, size_t T)
 {
-    if (!(c->pop_lut_ok && c->pop_sites_ok && !c->compact && c->opt_compact == 0 && c->opt_variant != 1 &&
-          c->opt_variant != 3 && c->pop_dense_enough))
+    if (!(c->tab.pop_lut_ok && c->lay.pop_sites_ok && !c->lay.compact && c->opt.compact == 0 && c->opt.variant != 1 &&
+          c->opt.variant != 3 && c->lay.pop_dense_enough))
         return 0;
-    const bool to_mfma = c->opt_mfma_targets && c->tab_in_lds && T >= (size_t)c->opt_mfma_min;
-    c->relayout_credit += to_mfma ? (uint64_t)((T + IBDG_TG - 1) / IBDG_TG) * 20u : (uint64_t)T * (c->opt_mx_counts ? 12u : 16u);
-    if (c->relayout_credit >= (uint64_t)std::max<long>(1, c->opt_compact_targets)) {
+    const bool to_mfma = c->opt.mfma_targets && c->lay.tab_in_lds && T >= (size_t)c->opt.mfma_min;
+    c->lay.relayout_credit += to_mfma ? (uint64_t)((T + IBDG_TG - 1) / IBDG_TG) * 20u : (uint64_t)T * (c->opt.mx_counts ? 12u : 16u);
+    if (c->lay.relayout_credit >= (uint64_t)std::max<long>(1, c->opt.compact_targets)) {
         if (quiesce(c)) return 1;
         if (build_segments(c, true)) return 1;
-        if (!c->pop_sites_ok && build_segments(c, false)) return 1;     // (cannot happen: it applied a moment ago)
+        if (!c->lay.pop_sites_ok && build_segments(c, false)) return 1;     // (cannot happen: it applied a moment ago)
     }
     return 0;
 }
@@ -1818,78 +1571,76 @@ struct RunPlan {
 int plan_run(ibdg_ctx *c, size_t T, size_t lanes, int ld_mode, bool row_table, RunPlan &P)
 {
     P.T = T; P.lanes = lanes; P.ld = ld_mode != 0;
-    P.rt_build = row_table && c->rt_gen != c->up_gen;
+    P.rt_build = row_table && !c->rt.fresh(*c);
     if (ld_mode) {
-        const bool can = c->pop_lut_ok && c->pop_sites_ok && (c->compact ? c->t32c.p : c->t32.p);
-        if (c->opt_variant == 2 && !can)
+        const bool can = c->tab.pop_lut_ok && c->lay.pop_sites_ok && (c->lay.compact ? c->lay.t32c.p : c->pan.t32.p);
+        if (c->opt.variant == 2 && !can)
             return fail(c, "[::] ERROR in ibdg_run: ld_variant 2 (exponent counting) is not applicable here "
                            "(clamped P(D|G) table, epsilon outside (0,1), max_cov > 50 or rows out of order)");
-        P.use_pop = can && c->opt_variant != 1 && c->opt_variant != 3 && (c->opt_variant == 2 || c->pop_dense_enough);
+        P.use_pop = can && c->opt.variant != 1 && c->opt.variant != 3 && (c->opt.variant == 2 || c->lay.pop_dense_enough);
     }
-    P.variant = ld_mode ? (P.use_pop ? 2 : (c->opt_variant == 3 ? 3 : 1)) : 0;
-    P.recount = c->opt_count_in_run || !c->counts_valid;
+    P.variant = ld_mode ? (P.use_pop ? 2 : (c->opt.variant == 3 ? 3 : 1)) : 0;
+    P.recount = c->opt.count_in_run || !c->pan.counts_valid;
     // a non-LD run is one kernel: it goes to the main stream (no second stream to start, wait for and join)
     P.rows_on_main = !ld_mode && !P.recount;
-    P.dispatch_events = P.use_pop && c->opt_dispatch_events && c->n_win > 0;
+    P.dispatch_events = P.use_pop && c->opt.dispatch_events && c->sites.n_win > 0;
     if (P.use_pop) {
         // Comparison individuals in groups of MT share one workgroup (and the counts that do not
         // depend on them) in k_ld_popcount_mt; what is left over goes one per workgroup.
         P.MT = (size_t)ibdg::ld_popcount_mt_width();
-        const bool mt_fits = ibdg::ld_popcount_lds_bytes(c->max_seg, c->wpg, c->ct_max + 1, c->tab_in_lds, c->seg_ring,
+        const bool mt_fits = ibdg::ld_popcount_lds_bytes(c->lay.max_seg, c->lay.wpg, c->lay.ct_max + 1, c->lay.tab_in_lds, c->lay.seg_ring,
                                                          1) <= 150 * 1024;
         // Five or more comparison individuals: groups of IBDG_TG through the matrix cores (k_ld_mfma); the
         // last group may be short, fewer than mfma_min individuals take the counting kernels below.
         // (one group's partial sums and operands must stay modest: tiny windows over millions of rows go the old way)
         // (a group's partial sums: 16 doubles per window and half chunk -- per group of eight half chunks where the kernel's
         //  workgroups add their waves' sums up themselves, MfmaArgs::wg_sum)
-        P.mfma_wg_sum = c->opt_mfma_wg_sum && ibdg::ld_mfma_wg_sum(c->wpg, c->ct_max + 1, c->max_seg);
-        P.ph_group = (size_t)c->n_win * (P.mfma_wg_sum ? (size_t)((2 * c->n_chunks + 7) / 8) * 128 : (size_t)c->n_chunks * 2 * 128) + 128;
-        const size_t group_bytes = P.ph_group + (size_t)c->n_segs * 1024 + (size_t)c->n_win * 512;
-        if (c->opt_mfma_targets && c->tab_in_lds && !P.dispatch_events && T >= (size_t)c->opt_mfma_min && (c->compact ? c->n_pairs_c : c->n_pairs) < (1u << 21) && c->n_segs < (1u << 21) &&     // (32-bit byte offsets of its buffer loads)
+        P.mfma_wg_sum = c->opt.mfma_wg_sum && ibdg::ld_mfma_wg_sum(c->lay.wpg, c->lay.ct_max + 1, c->lay.max_seg);
+        P.ph_group = (size_t)c->sites.n_win * (P.mfma_wg_sum ? (size_t)((2 * c->pan.n_chunks + 7) / 8) * 128 : (size_t)c->pan.n_chunks * 2 * 128) + 128;
+        const size_t group_bytes = P.ph_group + (size_t)c->lay.n_segs * 1024 + (size_t)c->sites.n_win * 512;
+        if (c->opt.mfma_targets && c->lay.tab_in_lds && !P.dispatch_events && T >= (size_t)c->opt.mfma_min && (c->lay.compact ? c->lay.n_pairs_c : c->pan.n_pairs) < (1u << 21) && c->lay.n_segs < (1u << 21) &&     // (32-bit byte offsets of its buffer loads)
             group_bytes <= ((size_t)4 << 30) &&
-            ibdg::ld_mfma_lds_bytes(c->wpg, c->ct_max + 1, c->max_seg) <= 64 * 1024) {
-            P.n_gg = T / IBDG_TG + (T % IBDG_TG >= (size_t)c->opt_mfma_min);
+            ibdg::ld_mfma_lds_bytes(c->lay.wpg, c->lay.ct_max + 1, c->lay.max_seg) <= 64 * 1024) {
+            P.n_gg = T / IBDG_TG + (T % IBDG_TG >= (size_t)c->opt.mfma_min);
             P.T_g = std::min(P.n_gg * IBDG_TG, T);
         }
         P.T_cnt = T - P.T_g;
-        P.n_grp = (c->opt_multi_target && mt_fits && P.T_cnt >= P.MT) ? P.T_cnt / P.MT : 0;
+        P.n_grp = (c->opt.multi_target && mt_fits && P.T_cnt >= P.MT) ? P.T_cnt / P.MT : 0;
         P.T_one = P.T_cnt - P.n_grp * P.MT;
         // target operands (1 KiB per segment and group) and partial sums (32 B per window, chunk and individual)
         // exist for one batch of groups at a time: about 1 GiB of operands, eight groups at most
         // (option "mfma_batch_groups": at most that many groups per launch, within 1/16 of the device's memory for each of
         //  the two buffers)
         const size_t mem_cap = std::max<size_t>((size_t)1 << 30, c->dev_mem_bytes / 16);
-        const size_t fit = std::min(c->n_segs ? mem_cap / ((size_t)c->n_segs * 1024) : P.n_gg, mem_cap / P.ph_group);
-        P.gg_batch = std::min({std::max<size_t>(fit, 1), (size_t)std::max<long>(1, c->opt_mfma_batch), P.n_gg});
+        const size_t fit = std::min(c->lay.n_segs ? mem_cap / ((size_t)c->lay.n_segs * 1024) : P.n_gg, mem_cap / P.ph_group);
+        P.gg_batch = std::min({std::max<size_t>(fit, 1), (size_t)std::max<long>(1, c->opt.mfma_batch), P.n_gg});
         // one comparison individual per workgroup: the counts of a haplotype word on the matrix cores where the larger
         // records leave the run's LDS image within reach (option "mx_counts")
         // ... and its power tables in LDS are plain doubles, rho^n as rho^n 2^(s n): s = the integer nearest to -log2 rho keeps
         // every entry, and every product of a rho and a sigma entry whose exponents add up to a window's reads, a normal number
-        const double log2_rho = std::log2(c->eps / (1 - c->eps)), log2_sigma = std::log2(0.5 / (1 - c->eps));
+        const double log2_rho = std::log2(c->tab.eps / (1 - c->tab.eps)), log2_sigma = std::log2(0.5 / (1 - c->tab.eps));
         // (8 where the table allows it: the window end then makes the exponent up with one subtraction)
-        const bool shift8 = (double)(c->ct_max + 1) * std::max(std::fabs(log2_rho + 8.0), std::fabs(log2_sigma)) <= 1000.0;
+        const bool shift8 = (double)(c->lay.ct_max + 1) * std::max(std::fabs(log2_rho + 8.0), std::fabs(log2_sigma)) <= 1000.0;
         P.rho_shift = shift8 ? 8 : std::lround(-log2_rho);
         const double per_read = std::max(std::fabs(log2_rho + (double)P.rho_shift), std::fabs(log2_sigma));
-        P.mx_counts = c->opt_mx_counts && P.rho_shift >= 0 && P.rho_shift <= 40 &&
-                      (!c->tab_in_lds || (double)(c->ct_max + 1) * per_read <= 1000.0) &&
-                      ibdg::ld_popcount_lds_bytes(c->max_seg, c->wpg, c->ct_max + 1, c->tab_in_lds, c->seg_ring, 2) <= 150 * 1024;
-        P.part_bytes = T * (size_t)c->n_win * c->n_chunks * 16;
+        P.mx_counts = c->opt.mx_counts && P.rho_shift >= 0 && P.rho_shift <= 40 &&
+                      (!c->lay.tab_in_lds || (double)(c->lay.ct_max + 1) * per_read <= 1000.0) &&
+                      ibdg::ld_popcount_lds_bytes(c->lay.max_seg, c->lay.wpg, c->lay.ct_max + 1, c->lay.tab_in_lds, c->lay.seg_ring, 2) <= 150 * 1024;
+        P.part_bytes = T * (size_t)c->sites.n_win * c->pan.n_chunks * 16;
         // single individuals in the IBD1 form (counts on the matrix cores, tables in LDS): at once where the IBD0 pass exists,
         // otherwise when the runs on this upload and background have added up
-        const bool p2_stale = c->p2_gen != c->sites_gen || c->p2_bg_gen != c->bg_gen || c->p2_mx != P.mx_counts;
-        if (P.T_one && P.mx_counts && c->tab_in_lds && c->opt_ibd0_after > 0) {
-            if (c->ibd0_bg_gen != c->bg_gen) {
-                c->ibd0_bg_gen = c->bg_gen;
-                c->ibd0_runs = 0;
-            }
-            c->ibd0_runs += P.T_one;
-            P.ibd1 = !p2_stale || (P.n_gg > 0) || c->ibd0_runs >= (uint64_t)c->opt_ibd0_after;
+        const bool p2_stale = !c->p2.fresh(*c, P.mx_counts);
+        if (P.T_one && P.mx_counts && c->lay.tab_in_lds && c->opt.ibd0_after > 0) {
+            if (!c->ibd0.fresh(*c))
+                c->ibd0.made(*c);
+            c->ibd0.ibd0_runs += P.T_one;
+            P.ibd1 = !p2_stale || (P.n_gg > 0) || c->ibd0.ibd0_runs >= (uint64_t)c->opt.ibd0_after;
         }
         P.ibd0_pass = p2_stale && (P.n_gg > 0 || P.ibd1);
-        P.fin_in_next = c->opt_fin_next && c->opt_async && P.T_one > 0 && P.T_one == P.T_cnt && P.n_gg == 0;
+        P.fin_in_next = c->opt.fin_next && c->opt.async && P.T_one > 0 && P.T_one == P.T_cnt && P.n_gg == 0;
         // (option "end_in_dispatch": the run's end event is the --LD kernel's own completion signal -- no event packet
         // of its own behind the kernel -- where that kernel is the run's last launch on the main stream)
-        P.end_in_dispatch = c->opt_end_in_dispatch && P.fin_in_next && !P.dispatch_events && P.T_one == T;
+        P.end_in_dispatch = c->opt.end_in_dispatch && P.fin_in_next && !P.dispatch_events && P.T_one == T;
         P.count_unit = P.T_one ? (P.mx_counts ? (P.ibd1 ? 3 : 2) : 1) : 0;
         // k_ld_mfma (4 waves per SIMD) leaves wave slots to the second stream: its kernels run in their fast forms
         // (also with a few individuals left to the counting kernels: T = 16 5.5 ms against 6.0; beside
@@ -1897,13 +1648,13 @@ int plan_run(ibdg_ctx *c, size_t T, size_t lanes, int ld_mode, bool row_table, R
         P.side_fast = P.n_gg > 0;
     }
     // stream2's per-row values and window products, one launch (k_rows_windows).  Beside the exponent-counting --LD
-    // kernel, which holds every wave slot, it gets few long-lived workgroups (opt_site_blocks per CU, shared among
+    // kernel, which holds every wave slot, it gets few long-lived workgroups (opt.site_blocks per CU, shared among
     // the targets): its gathers wait on memory either way, and the --LD workgroups keep their wave slots
     // (not when the alt counts are recounted in this run: the second stream's chain count -> rows is then the
     // longer one of the two, and its kernels should be short; and not beside the matrix-core kernel, which leaves
     // half of the wave slots free)
-    if (ld_mode && !P.recount && !P.side_fast && c->opt_site_blocks > 0)
-        P.row_blocks = std::max<unsigned>(1u, (unsigned)((size_t)c->n_cu * c->opt_site_blocks / T));
+    if (ld_mode && !P.recount && !P.side_fast && c->opt.site_blocks > 0)
+        P.row_blocks = std::max<unsigned>(1u, (unsigned)((size_t)c->n_cu * c->opt.site_blocks / T));
     return 0;
 }
 
@@ -1917,18 +1668,18 @@ int plan_run(ibdg_ctx *c, size_t T, size_t lanes, int ld_mode, bool row_table, R
 // kernel alone from inside the process).
 // A finalising step flushed by this run (`flushed`) writes LIBD0 / LIBD1 of the rows a non-LD run's stream2 writes too: the
 // previous run's end lies before that step, so it cannot be the start stream2 waits for.  (Steady queues never flush.)
-int start_run(ibdg_ctx *c, const RunPlan &P, ibdg_ctx::EvSet &E, bool flushed)
+int start_run(ibdg_ctx *c, const RunPlan &P, EvSet &E, bool flushed)
 {
     E.recount = P.recount; E.ld = P.ld; E.rows_on_main = P.rows_on_main; E.has_kernel_times = P.dispatch_events;
-    const bool chained = c->chain_ok && c->opt_async;
+    const bool chained = c->tl.chain_ok && c->opt.async;
     if (P.dispatch_events) {                       // (an --LD run: its stream2 writes no entry the step writes)
         E.start = E.start_own;                     // filled in by the first --LD dispatch
         if (chained)                               // stream2 keeps one run behind the main stream at most
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->evs[c->ev_head].ld_end, 0));
+            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->tl.evs[c->tl.ev_head].ld_end, 0));
         return 0;
     }
     if (chained && !flushed) {
-        E.start = c->evs[c->ev_head].ld_end;       // back-to-back runs: the previous end is this start
+        E.start = c->tl.evs[c->tl.ev_head].ld_end;       // back-to-back runs: the previous end is this start
     } else {
         HIP_TRY(c, hipEventRecord(E.start_own, c->stream));
         E.start = E.start_own;
@@ -1941,17 +1692,32 @@ int start_run(ibdg_ctx *c, const RunPlan &P, ibdg_ctx::EvSet &E, bool flushed)
 ibdg::RowsArgs rows_args(const ibdg_ctx *c, int ld_mode, bool row_table)
 {
     ibdg::RowsArgs sa{};
-    sa.panel = (const uint64_t *)c->panel.p; sa.stride = c->stride; sa.n_ids = c->n_ids;
-    sa.rec_all = (const uint2 *)c->rec_all.p; sa.n_sites = c->n_sites;
-    sa.lut = (const double *)c->lut.p; sa.alt_count = (const uint32_t *)c->alt_count.p; sa.pow_tab = (const double *)c->pow_tab.p;
-    sa.fo = c->have_fo ? (const double *)c->fo.p : nullptr;
+    sa.panel = (const uint64_t *)c->pan.panel.p; sa.stride = c->pan.stride; sa.n_ids = c->pan.n_ids;
+    sa.rec_all = (const uint2 *)c->sites.rec_all.p; sa.n_sites = c->sites.n_sites;
+    sa.lut = (const double *)c->tab.lut.p; sa.alt_count = (const uint32_t *)c->pan.alt_count.p; sa.pow_tab = (const double *)c->pan.pow_tab.p;
+    sa.fo = c->sites.have_fo ? (const double *)c->sites.fo.p : nullptr;
     sa.targets = ring_slot<const uint32_t>(c->targets, c->ring.cur, Ring::SLOTS);
-    sa.t32 = c->pop_lut_ok ? (const uint4 *)c->t32.p : nullptr; sa.n_pairs = c->n_pairs;
-    sa.cov_site = (const uint32_t *)c->cov_site.p; sa.rec_cov = (const uint2 *)c->rec_cov.p; sa.n_cov = c->n_cov;
-    sa.window = c->window; sa.n_win = c->n_win; sa.ld_mode = ld_mode ? 1 : 0;
-    sa.site_ll = c->opt_site_results && !row_table ? (double *)c->site_ll.p : nullptr;
+    sa.t32 = c->tab.pop_lut_ok ? (const uint4 *)c->pan.t32.p : nullptr; sa.n_pairs = c->pan.n_pairs;
+    sa.cov_site = (const uint32_t *)c->sites.cov_site.p; sa.rec_cov = (const uint2 *)c->sites.rec_cov.p; sa.n_cov = c->sites.n_cov;
+    sa.window = c->sites.window; sa.n_win = c->sites.n_win; sa.ld_mode = ld_mode ? 1 : 0;
+    sa.site_ll = c->opt.site_results && !row_table ? (double *)c->site_ll.p : nullptr;
     sa.win_ll = (double *)c->win_ll.p;
     return sa;
+}
+
+// What the counting kernels' and k_ld_mfma's arguments share: the layout's tiles, segments, windows and runs, the power
+// tables and the run's individuals (A: ibdg::PopArgs or ibdg::MfmaArgs, which name these fields alike)
+template <class A>
+void common_args(const ibdg_ctx *c, A &a, size_t lanes)
+{
+    const ibdg_ctx::Layout &L = c->lay;
+    a.t32 = (const uint32_t *)(L.compact ? L.t32c.p : c->pan.t32.p); a.n_pairs = L.compact ? L.n_pairs_c : c->pan.n_pairs;
+    a.n_chunks = c->pan.n_chunks;
+    a.segs = (const ibdg::Seg *)L.segs.p; a.n_segs = L.n_segs; a.max_seg = L.max_seg;
+    a.wconst = (const ibdg::WinConst *)L.wconst.p; a.n_win = c->sites.n_win; a.win_per_group = L.wpg;
+    a.run_begin = (const uint32_t *)L.runs.p; a.n_runs = L.n_runs;
+    a.pow_1me = (const ibdg::PowEntry *)c->tab.pow1.p; a.pow_eps = (const ibdg::PowEntry *)c->tab.pow2.p; a.tab_len = L.ct_max + 1;
+    a.targets = ring_slot<const uint32_t>(c->targets, c->ring.cur, Ring::SLOTS); a.lanes = (uint32_t)lanes;
 }
 
 // The counting kernels' arguments, made once per run; the stages copy and adjust them.
@@ -1959,35 +1725,28 @@ ibdg::PopArgs pop_args(const ibdg_ctx *c, const RunPlan &P)
 {
     const Ring &R = c->ring;
     ibdg::PopArgs pa;
-    pa.t32 = (const uint32_t *)(c->compact ? c->t32c.p : c->t32.p); pa.n_pairs = c->compact ? c->n_pairs_c : c->n_pairs;
-    pa.n_chunks = c->n_chunks;
-    pa.segs = (const ibdg::Seg *)c->segs.p; pa.n_segs = c->n_segs; pa.max_seg = c->max_seg;
-    pa.wconst = (const ibdg::WinConst *)c->wconst.p; pa.n_win = c->n_win; pa.win_per_group = c->wpg;
-    pa.run_begin = (const uint32_t *)c->runs.p; pa.n_runs = c->n_runs;
-    pa.n_cgroups = (c->n_chunks + 7) / 8;
-    pa.waves_per_group = (c->n_chunks + pa.n_cgroups - 1) / pa.n_cgroups;   // 40 chunks: 5 x 8; 9: 5 + 4; 2: 1 x 2
-    pa.rec_ready = ring_slot<const uint32_t>(c->twords, R.cur, Ring::SLOTS, 16);
-    pa.wc_ready = ring_slot<const uint32_t>(c->wtarget, R.cur, Ring::SLOTS, 16);
-    pa.pow_1me = (const ibdg::PowEntry *)c->pow1.p; pa.pow_eps = (const ibdg::PowEntry *)c->pow2.p;
-    pa.targets = ring_slot<const uint32_t>(c->targets, R.cur, Ring::SLOTS); pa.t_base = (uint32_t)P.T_g;
-    pa.weight = ring_slot<const double>(c->weight, R.cur, Ring::SLOTS); pa.lanes = (uint32_t)P.lanes;
+    common_args(c, pa, P.lanes);
+    pa.n_cgroups = (c->pan.n_chunks + 7) / 8;
+    pa.waves_per_group = (c->pan.n_chunks + pa.n_cgroups - 1) / pa.n_cgroups;   // 40 chunks: 5 x 8; 9: 5 + 4; 2: 1 x 2
+    pa.rec_ready = ring_slot<const uint32_t>(c->img.twords, R.cur, Ring::SLOTS, 16);
+    pa.wc_ready = ring_slot<const uint32_t>(c->img.wtarget, R.cur, Ring::SLOTS, 16);
+    pa.t_base = (uint32_t)P.T_g;
+    pa.weight = ring_slot<const double>(c->weight, R.cur, Ring::SLOTS);
     pa.partial = (double *)((char *)c->partial.p + (P.fin_in_next ? (size_t)c->fin.half * P.part_bytes : 0));
-    pa.ring_slots = (uint32_t)c->seg_ring; pa.tab_len = c->ct_max + 1; pa.tab_in_lds = (uint32_t)c->tab_in_lds;
-    pa.mx_counts = (uint32_t)P.mx_counts; pa.rho_shift = (uint32_t)P.rho_shift; pa.sum_dpp = (uint32_t)c->opt_sum_dpp;
+    pa.ring_slots = (uint32_t)c->lay.seg_ring; pa.tab_in_lds = (uint32_t)c->lay.tab_in_lds;
+    pa.mx_counts = (uint32_t)P.mx_counts; pa.rho_shift = (uint32_t)P.rho_shift; pa.sum_dpp = (uint32_t)c->opt.sum_dpp;
     return pa;
 }
 
 // k_ld_mfma's arguments: the counting kernels' site list, windows, tables and individuals, and its own operands and sums
-ibdg::MfmaArgs mfma_args(const ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa)
+ibdg::MfmaArgs mfma_args(const ibdg_ctx *c, const RunPlan &P)
 {
     ibdg::MfmaArgs ma;
-    ma.t32 = pa.t32; ma.n_pairs = pa.n_pairs; ma.n_chunks = pa.n_chunks;
-    ma.segs = pa.segs; ma.n_segs = pa.n_segs; ma.max_seg = pa.max_seg;
-    ma.wconst = pa.wconst; ma.n_win = pa.n_win; ma.run_begin = pa.run_begin; ma.n_runs = pa.n_runs; ma.win_per_group = pa.win_per_group;
-    ma.pow_1me = pa.pow_1me; ma.pow_eps = pa.pow_eps; ma.pow_tau = (const ibdg::PowEntry *)c->pow3.p; ma.tab_len = pa.tab_len;
-    ma.plain_tau = c->opt_mfma_plain_tau ? 1u : 0u;
-    ma.targets = pa.targets; ma.lanes = pa.lanes; ma.base_weight = (const double *)c->base_w.p;
-    ma.p2w = (const double *)c->p2w.p; ma.p2c = (const double *)c->p2c.p;
+    common_args(c, ma, P.lanes);
+    ma.pow_tau = (const ibdg::PowEntry *)c->tab.pow3.p;
+    ma.plain_tau = c->opt.mfma_plain_tau ? 1u : 0u;
+    ma.base_weight = (const double *)c->bg.base_w.p;
+    ma.p2w = (const double *)c->p2.p2w.p; ma.p2c = (const double *)c->p2.p2c.p;
     ma.aimg = (uint4 *)c->aimg.p; ma.wc_slot = (uint4 *)c->wc_slot.p;
     // one batch's partial sums: t1 [groups][windows][half chunks][16], t0 [groups][windows][half chunks], ov [groups][windows][16]
     ma.part_t1 = (double *)c->partial_h.p; ma.wg_sum = P.mfma_wg_sum ? 1u : 0u;
@@ -2000,26 +1759,26 @@ ibdg::MfmaArgs mfma_args(const ibdg_ctx *c, const RunPlan &P, const ibdg::PopArg
 int ibd0_pass(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa)
 {
     if (ring_settle(c)) return 1;
-    if (ensure(c, c->p2w, (size_t)c->n_win * P.lanes * 8) || ensure(c, c->p2c, (size_t)c->n_win * c->n_chunks * 16) ||
-        ensure(c, c->p2_tw, (size_t)c->n_segs * ibdg::ld_popcount_rec_bytes(P.mx_counts)) ||
-        ensure(c, c->p2_wt, (size_t)c->n_win * 32))
+    if (ensure(c, c->p2.p2w, (size_t)c->sites.n_win * P.lanes * 8) || ensure(c, c->p2.p2c, (size_t)c->sites.n_win * c->pan.n_chunks * 16) ||
+        ensure(c, c->p2.p2_tw, (size_t)c->lay.n_segs * ibdg::ld_popcount_rec_bytes(P.mx_counts)) ||
+        ensure(c, c->p2.p2_wt, (size_t)c->sites.n_win * 32))
         return 1;
     ibdg::PopArgs pp = pa;
-    pp.rec_ready = (const uint32_t *)c->p2_tw.p; pp.wc_ready = (const uint32_t *)c->p2_wt.p;
-    pp.weight = (const double *)c->base_w.p; pp.t_base = 0;
-    pp.partial = (double *)c->p2c.p; pp.p2_out = (double *)c->p2w.p;
+    pp.rec_ready = (const uint32_t *)c->p2.p2_tw.p; pp.wc_ready = (const uint32_t *)c->p2.p2_wt.p;
+    pp.weight = (const double *)c->bg.base_w.p; pp.t_base = 0;
+    pp.partial = (double *)c->p2.p2c.p; pp.p2_out = (double *)c->p2.p2w.p;
     ibdg::launch_win_target(pp, 1, c->stream);
-    if (ibdg::launch_ld_popcount(pp, 1, c->planes, c->stream))
-        return fail(c, "[::] ERROR in ibdg_run: unsupported number of weight bit-planes %d", c->planes);
-    c->p2_gen = c->sites_gen; c->p2_bg_gen = c->bg_gen; c->p2_mx = P.mx_counts;
+    if (ibdg::launch_ld_popcount(pp, 1, c->lay.planes, c->stream))
+        return fail(c, "[::] ERROR in ibdg_run: unsupported number of weight bit-planes %d", c->lay.planes);
+    c->p2.made(*c, P.mx_counts);
     return 0;
 }
 
 // groups of IBDG_TG individuals through the matrix cores (k_ld_mfma), gg_batch groups per launch
-int launch_mfma_groups(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa, ibdg_ctx::EvSet &E)
+int launch_mfma_groups(ibdg_ctx *c, const RunPlan &P, EvSet &E)
 {
     if (ring_settle(c)) return 1;
-    ibdg::MfmaArgs ma = mfma_args(c, P, pa);
+    ibdg::MfmaArgs ma = mfma_args(c, P);
     const int *d_nref = ring_slot<const int>(c->nrefpanel, c->ring.nref, Ring::NREF_SLOTS);
     for (size_t g0 = 0; g0 < P.n_gg; g0 += P.gg_batch) {
         const size_t nb = std::min(P.n_gg - g0, P.gg_batch);
@@ -2054,7 +1813,7 @@ int launch_mt_groups(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa, ibd
 
 // the single individuals [T_g + n_grp MT, T), one per workgroup (k_ld_popcount), with their images (k_win_target)
 int launch_singles(ibdg_ctx *c, const RunPlan &P, ibdg::PopArgs pa, ibdg::KernelEvents first, ibdg::KernelEvents dominant,
-                   bool same_inputs, ibdg_ctx::EvSet &E)
+                   bool same_inputs, EvSet &E)
 {
     Ring &R = c->ring;
     pa.t_base = (uint32_t)(P.T_g + P.n_grp * P.MT);
@@ -2062,8 +1821,8 @@ int launch_singles(ibdg_ctx *c, const RunPlan &P, ibdg::PopArgs pa, ibdg::Kernel
     // (skipped when the previous run made the very same images: same prepared sites, same comparison individuals --
     // a caller that runs a comparison again, e.g. timed steps: one launch of ~10 us less per run, which on an
     // eighth of a chromosome is a tenth of the step)
-    const ibdg_ctx::ImgKey key = {c->sites_gen, pa.t_base, (uint32_t)P.T_one, P.mx_counts, (int)P.ibd1, R.cur};
-    const bool wt_cached = same_inputs && key == c->wt_key && !P.dispatch_events;
+    const ibdg_ctx::Images::Key key = c->img.key_for(*c, pa.t_base, (uint32_t)P.T_one, P.mx_counts, (int)P.ibd1, R.cur);
+    const bool wt_cached = same_inputs && c->img.fresh(key) && !P.dispatch_events;
     // a new individual's images: on stream3 with its weights (under the --LD kernel of the run before) unless the
     // launch carries the run's start event (dispatch_events: that belongs on the main stream)
     const bool wt_ahead = R.unsettled && !P.dispatch_events;
@@ -2077,26 +1836,26 @@ int launch_singles(ibdg_ctx *c, const RunPlan &P, ibdg::PopArgs pa, ibdg::Kernel
         R.s3_gen = c->sites_gen;
     }
     if (P.ibd1) {
-        if (c->fb_gen != c->sites_gen) {
+        if (!c->fb.fresh(*c)) {
             // once per site list (and layout): the three fragments per segment an individual's images select between
-            if (ensure(c, c->fragb, (size_t)c->n_segs * 72)) return 1;
-            if (!c->ev_fb)
-                HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fb, hipEventDisableTiming));
-            ibdg::launch_frag_base(pa, (uint32_t *)c->fragb.p, is);
-            HIP_TRY(c, hipEventRecord(c->ev_fb, is));
-            HIP_TRY(c, hipStreamWaitEvent(wt_ahead ? c->stream : c->stream3, c->ev_fb, 0));   // (whichever makes the next images)
-            c->fb_gen = c->sites_gen;
+            if (ensure(c, c->fb.fragb, (size_t)c->lay.n_segs * 72)) return 1;
+            if (!c->fb.ev_fb)
+                HIP_TRY(c, hipEventCreateWithFlags(&c->fb.ev_fb, hipEventDisableTiming));
+            ibdg::launch_frag_base(pa, (uint32_t *)c->fb.fragb.p, is);
+            HIP_TRY(c, hipEventRecord(c->fb.ev_fb, is));
+            HIP_TRY(c, hipStreamWaitEvent(wt_ahead ? c->stream : c->stream3, c->fb.ev_fb, 0));   // (whichever makes the next images)
+            c->fb.made(*c);
         }
-        pa.frag_base = (const uint32_t *)c->fragb.p;
+        pa.frag_base = (const uint32_t *)c->fb.fragb.p;
     }
     if (!wt_cached)
         ibdg::launch_win_target(pa, (unsigned)P.T_one, is, first);
     if (ring_settle(c)) return 1;
-    c->wt_key = key;
+    c->img.made(key);
     if (P.end_in_dispatch)
         dominant.stop = E.ld_end;
-    if (ibdg::launch_ld_popcount(pa, (unsigned)P.T_one, c->planes, c->stream, dominant))
-        return fail(c, "[::] ERROR in ibdg_run: unsupported number of weight bit-planes %d", c->planes);
+    if (ibdg::launch_ld_popcount(pa, (unsigned)P.T_one, c->lay.planes, c->stream, dominant))
+        return fail(c, "[::] ERROR in ibdg_run: unsupported number of weight bit-planes %d", c->lay.planes);
     return 0;
 }
 
@@ -2106,16 +1865,16 @@ int launch_singles(ibdg_ctx *c, const RunPlan &P, ibdg::PopArgs pa, ibdg::Kernel
 // chromosome -- is left to the NEXT run's --LD launch, whose first workgroups do it on the way (the kernel boundary between
 // the two launches is all the ordering it needs), and this run's launch does the same for its predecessor.  The partial
 // sums alternate between two halves of their buffer.
-int finalise(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa, ibdg::KernelEvents last, ibdg_ctx::EvSet &E)
+int finalise(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa, ibdg::KernelEvents last, EvSet &E)
 {
     if (!P.T_cnt) return 0;
     const int *d_nref = ring_slot<const int>(c->nrefpanel, c->ring.nref, Ring::NREF_SLOTS);
     ibdg::PopFinalArgs fa;
-    fa.wconst = pa.wconst; fa.n_win = c->n_win; fa.n_chunks = c->n_chunks;
+    fa.wconst = pa.wconst; fa.n_win = c->sites.n_win; fa.n_chunks = c->pan.n_chunks;
     fa.n_refpanel = d_nref; fa.win_ll = (double *)c->win_ll.p;
     fa.partial = pa.partial; fa.t_base = (uint32_t)P.T_g; fa.halves = 0;
     if (P.ibd1) {                      // (whatever kernel made an individual's IBD1 sums)
-        fa.p2c = (const double *)c->p2c.p; fa.p2w = (const double *)c->p2w.p; fa.lanes = (uint32_t)P.lanes;
+        fa.p2c = (const double *)c->p2.p2c.p; fa.p2w = (const double *)c->p2.p2w.p; fa.lanes = (uint32_t)P.lanes;
         fa.targets = (const uint32_t *)(d_nref + P.T);      // (this run's individuals, from the longer ring: k_target_weights)
     }
     if (!P.fin_in_next) {
@@ -2129,22 +1888,19 @@ int finalise(ibdg_ctx *c, const RunPlan &P, const ibdg::PopArgs &pa, ibdg::Kerne
 }
 
 // the exponent-counting --LD path: k_ld_mfma groups, k_ld_popcount_mt groups, single individuals, the finalising step
-int launch_pop(ibdg_ctx *c, const RunPlan &P, ibdg_ctx::EvSet &E, bool same_inputs)
+int launch_pop(ibdg_ctx *c, const RunPlan &P, EvSet &E, bool same_inputs)
 {
     // (the single individuals' images in ring slots like the other per-individual data)
     const size_t img_slots = P.T <= Ring::AHEAD_MAX_T ? Ring::SLOTS : 1;
-    const size_t wt_cap0 = c->wtarget.cap, tw_cap0 = c->twords.cap;
-    if (ensure(c, c->wtarget, img_slots * P.T_one * (size_t)c->n_win * 32) ||
-        ensure(c, c->twords, img_slots * P.T_one * (size_t)c->n_segs * ibdg::ld_popcount_rec_bytes(P.mx_counts)) ||
-        ensure(c, c->wtarget_mt, P.n_grp * (size_t)c->n_win * ibdg::ld_popcount_mt_wc_bytes()) ||
-        ensure(c, c->twords_mt, P.n_grp * (size_t)c->n_segs * ibdg::ld_popcount_mt_rec_bytes()) ||
+    if (ensure(c, c->img.wtarget, img_slots * P.T_one * (size_t)c->sites.n_win * 32) ||
+        ensure(c, c->img.twords, img_slots * P.T_one * (size_t)c->lay.n_segs * ibdg::ld_popcount_rec_bytes(P.mx_counts)) ||
+        ensure(c, c->wtarget_mt, P.n_grp * (size_t)c->sites.n_win * ibdg::ld_popcount_mt_wc_bytes()) ||
+        ensure(c, c->twords_mt, P.n_grp * (size_t)c->lay.n_segs * ibdg::ld_popcount_mt_rec_bytes()) ||
         ensure(c, c->partial, P.T_cnt ? 2 * P.part_bytes : 0) ||
-        ensure(c, c->aimg, P.gg_batch * (size_t)c->n_segs * 1024) ||
-        ensure(c, c->wc_slot, P.gg_batch * (size_t)c->n_win * 512) ||
+        ensure(c, c->aimg, P.gg_batch * (size_t)c->lay.n_segs * 1024) ||
+        ensure(c, c->wc_slot, P.gg_batch * (size_t)c->sites.n_win * 512) ||
         ensure(c, c->partial_h, P.gg_batch * P.ph_group))
         return 1;
-    if (c->wtarget.cap != wt_cap0 || c->twords.cap != tw_cap0)
-        c->wt_key.gen = 0;                // new buffers: no images in them
     ibdg::PopArgs pa = pop_args(c, P);
     if (P.ibd0_pass && ibd0_pass(c, P, pa)) return 1;
     if (c->fin.pending) {                 // the finalising step the run before left to this run's launch
@@ -2159,7 +1915,7 @@ int launch_pop(ibdg_ctx *c, const RunPlan &P, ibdg_ctx::EvSet &E, bool same_inpu
         first.start = E.start_own; last.stop = E.ld_end;
         dominant.start = E.k_start; dominant.stop = E.k_stop;
     }
-    if ((P.n_gg && launch_mfma_groups(c, P, pa, E)) || (P.n_grp && launch_mt_groups(c, P, pa, first, dominant)) ||
+    if ((P.n_gg && launch_mfma_groups(c, P, E)) || (P.n_grp && launch_mt_groups(c, P, pa, first, dominant)) ||
         (P.T_one && launch_singles(c, P, pa, first, dominant, same_inputs, E)))
         return 1;
     return finalise(c, P, pa, last, E);
@@ -2169,20 +1925,20 @@ int launch_pop(ibdg_ctx *c, const RunPlan &P, ibdg_ctx::EvSet &E, bool same_inpu
 // individual bg_count times in the panel's order
 int background_order(ibdg_ctx *c, const uint8_t *bg_count, std::vector<uint32_t> &order)
 {
-    if (c->bg_order.empty()) {
-        for (unsigned n = 0; n < c->n_ids; ++n)
+    if (c->opt.bg_order.empty()) {
+        for (unsigned n = 0; n < c->pan.n_ids; ++n)
             for (unsigned k = bg_count ? bg_count[n] : 1u; k > 0; --k)
                 order.push_back(n);
         return 0;
     }
-    order = c->bg_order;
-    std::vector<unsigned> cnt(c->n_ids, 0);
+    order = c->opt.bg_order;
+    std::vector<unsigned> cnt(c->pan.n_ids, 0);
     for (uint32_t n : order) {
-        if (n >= c->n_ids)
-            return fail(c, "[::] ERROR in ibdg_run: background order names individual %u of %u", n, c->n_ids);
+        if (n >= c->pan.n_ids)
+            return fail(c, "[::] ERROR in ibdg_run: background order names individual %u of %u", n, c->pan.n_ids);
         cnt[n]++;
     }
-    for (unsigned n = 0; n < c->n_ids; ++n)
+    for (unsigned n = 0; n < c->pan.n_ids; ++n)
         if (cnt[n] != (bg_count ? bg_count[n] : 1u))
             return fail(c, "[::] ERROR in ibdg_run: background order and bg_count disagree for individual %u", n);
     return 0;
@@ -2194,32 +1950,32 @@ int launch_strict(ibdg_ctx *c, const RunPlan &P, const uint32_t *targets, const 
 {
     if (ring_settle(c)) return 1;
     ibdg::LdArgs la{};
-    la.panel = (const uint64_t *)c->panel.p; la.stride = c->stride; la.n_groups = c->n_groups;
-    la.rec_cov = (const uint2 *)c->rec_cov.p; la.n_cov = c->n_cov; la.window = c->window; la.n_win = c->n_win;
-    la.lut = (const double *)c->lut.p; la.win_ll = (double *)c->win_ll.p;
+    la.panel = (const uint64_t *)c->pan.panel.p; la.stride = c->pan.stride; la.n_groups = c->pan.n_groups;
+    la.rec_cov = (const uint2 *)c->sites.rec_cov.p; la.n_cov = c->sites.n_cov; la.window = c->sites.window; la.n_win = c->sites.n_win;
+    la.lut = (const double *)c->tab.lut.p; la.win_ll = (double *)c->win_ll.p;
     la.targets = ring_slot<const uint32_t>(c->targets, c->ring.cur, Ring::SLOTS);
     la.weight = ring_slot<const double>(c->weight, c->ring.cur, Ring::SLOTS);
     la.n_refpanel = ring_slot<const int>(c->nrefpanel, c->ring.nref, Ring::NREF_SLOTS);
-    if (c->opt_variant != 3) {
-        if (ibdg::launch_ld(la, (unsigned)P.T, c->cpw, (unsigned)c->opt_waves, c->stream))
-            return fail(c, "[::] ERROR in ibdg_run: unsupported chunks_per_wave %d", c->cpw);
+    if (c->opt.variant != 3) {
+        if (ibdg::launch_ld(la, (unsigned)P.T, c->pan.cpw, (unsigned)c->opt.waves, c->stream))
+            return fail(c, "[::] ERROR in ibdg_run: unsupported chunks_per_wave %d", c->pan.cpw);
         return 0;
     }
     std::vector<uint32_t> order;
     if (background_order(c, bg_count, order)) return 1;
-    if (ensure(c, c->vals, (size_t)c->n_win * P.lanes * 16) || ensure(c, c->order, order.size() * 4)) return 1;
+    if (ensure(c, c->vals, (size_t)c->sites.n_win * P.lanes * 16) || ensure(c, c->order, order.size() * 4)) return 1;
     HIP_TRY(c, hipMemcpyAsync(c->order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));        // `order` is a local
     la.vals = (double2 *)c->vals.p;
     ibdg::OrdArgs oa;
-    oa.vals = la.vals; oa.lanes = (uint32_t)P.lanes; oa.n_win = c->n_win; oa.pu_id = pu_id;
+    oa.vals = la.vals; oa.lanes = (uint32_t)P.lanes; oa.n_win = c->sites.n_win; oa.pu_id = pu_id;
     oa.order = (const uint32_t *)c->order.p; oa.n_order = (uint32_t)order.size();
     for (size_t t = 0; t < P.T; ++t) {
         la.t_base = (uint32_t)t;
-        if (ibdg::launch_ld(la, 1, c->cpw, (unsigned)c->opt_waves, c->stream))
-            return fail(c, "[::] ERROR in ibdg_run: unsupported chunks_per_wave %d", c->cpw);
+        if (ibdg::launch_ld(la, 1, c->pan.cpw, (unsigned)c->opt.waves, c->stream))
+            return fail(c, "[::] ERROR in ibdg_run: unsupported chunks_per_wave %d", c->pan.cpw);
         oa.target = targets[t];
-        oa.win_ll = (double *)c->win_ll.p + t * (size_t)c->n_win * 3;
+        oa.win_ll = (double *)c->win_ll.p + t * (size_t)c->sites.n_win * 3;
         ibdg::launch_ld_ordered_sum(oa, c->stream);
     }
     return 0;
@@ -2227,17 +1983,17 @@ int launch_strict(ibdg_ctx *c, const RunPlan &P, const uint32_t *targets, const 
 
 // stream2's share of the run, queued after the critical path so that the --LD launches reach the device first: the
 // recount of the alt counts, the per-row values and the window products
-int queue_stream2(ibdg_ctx *c, const RunPlan &P, const ibdg::RowsArgs &sa, ibdg_ctx::EvSet &E)
+int queue_stream2(ibdg_ctx *c, const RunPlan &P, const ibdg::RowsArgs &sa, EvSet &E)
 {
     if (P.n_gg)                        // (behind the matrix-core groups' operands, launch_mfma_groups)
         HIP_TRY(c, hipStreamWaitEvent(c->stream2, E.prep, 0));
     HIP_TRY(c, hipEventRecord(E.s2_start, c->stream2));
     if (P.recount) {
-        // beside the --LD kernel: few long-lived waves (opt_recount_blocks per CU), so that the recount does not
+        // beside the --LD kernel: few long-lived waves (opt.recount_blocks per CU), so that the recount does not
         // take the wave slots the --LD workgroups need -- it is bound by HBM, they by instruction issue
-        ibdg::launch_alt_count((const uint64_t *)c->panel.p, c->stride, c->n_rows, (uint32_t *)c->alt_count.p,
-                               c->stream2, P.ld ? (unsigned)(c->n_cu * c->opt_recount_blocks) : 0u);
-        c->counts_valid = true;
+        ibdg::launch_alt_count((const uint64_t *)c->pan.panel.p, c->pan.stride, c->pan.n_rows, (uint32_t *)c->pan.alt_count.p,
+                               c->stream2, P.ld ? (unsigned)(c->n_cu * c->opt.recount_blocks) : 0u);
+        c->pan.counts_valid = true;
         HIP_TRY(c, hipEventRecord(E.s2_count, c->stream2));
     }
     // The site list's row table, when stale: one comparison individual's run makes it in the launch it makes anyway
@@ -2246,7 +2002,7 @@ int queue_stream2(ibdg_ctx *c, const RunPlan &P, const ibdg::RowsArgs &sa, ibdg_
     // (stream2, behind this run's recount of the alt counts; readers: see ibdg_ctx::row_tab)
     ibdg::RowsArgs ra = sa;
     if (P.rt_build) {
-        ra.row_tab = (double *)c->row_tab.p;
+        ra.row_tab = (double *)c->rt.row_tab.p;
         if (P.T > 1) {
             ibdg::launch_row_table(ra, c->stream2);
             ra.row_tab = nullptr;
@@ -2254,8 +2010,8 @@ int queue_stream2(ibdg_ctx *c, const RunPlan &P, const ibdg::RowsArgs &sa, ibdg_
     }
     ibdg::launch_rows_windows(ra, (unsigned)P.T, c->stream2, P.row_blocks);
     HIP_TRY(c, hipEventRecord(E.s2_end, c->stream2));
-    c->last_s2 = E.s2_end;
-    c->s2_pending = true;
+    c->tl.last_s2 = E.s2_end;
+    c->tl.s2_pending = true;
     return 0;
 }
 
@@ -2266,33 +2022,30 @@ extern "C" {
 int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_count, int pu_id, int ld_mode)
 {
     if (!c) return 1;
-    if (!c->panel.p || c->n_ids == 0) return fail(c, "[::] ERROR in ibdg_run: no panel uploaded");
-    if (!c->sites_valid) return fail(c, "[::] ERROR in ibdg_run: no sites uploaded");
+    if (!c->pan.panel.p || c->pan.n_ids == 0) return fail(c, "[::] ERROR in ibdg_run: no panel uploaded");
+    if (!c->sites.sites_valid) return fail(c, "[::] ERROR in ibdg_run: no sites uploaded");
     if (T == 0 || !targets) return fail(c, "[::] ERROR in ibdg_run: no targets");
     if (T > 65535) return fail(c, "[::] ERROR in ibdg_run: at most 65535 targets per call");
     for (size_t t = 0; t < T; ++t)
-        if (targets[t] >= c->n_ids)
+        if (targets[t] >= c->pan.n_ids)
             return fail(c, "[::] ERROR in ibdg_run: target %u is not a panel individual (n_ids=%u)", targets[t],
-                        c->n_ids);
+                        c->pan.n_ids);
     HIP_TRY(c, hipSetDevice(c->device));
 
-    const size_t lanes = (size_t)c->n_groups * c->cpw * 64;
-    const bool want_ll = c->opt_site_results != 0;
+    const size_t lanes = (size_t)c->pan.n_groups * c->pan.cpw * 64;
+    const bool want_ll = c->opt.site_results != 0;
     // --LD: the per-site values come from the site list's row table (one for every comparison individual: they differ by the
     // genotype picked), made once per upload; an individual's per-site table is put together when it is fetched (k_site_expand)
     const bool row_table = want_ll && ld_mode;
-    const size_t rt_cap0 = c->row_tab.cap;
-    if (ensure(c, c->targets, Ring::SLOTS * T * 4) || (want_ll && ensure(c, c->site_ll, (row_table ? 1 : T) * c->n_sites * 24)) ||
-        (row_table && ensure(c, c->row_tab, c->n_sites * 32)) || ensure(c, c->win_ll, T * (size_t)c->n_win * 24))
+    if (ensure(c, c->targets, Ring::SLOTS * T * 4) || (want_ll && ensure(c, c->site_ll, (row_table ? 1 : T) * c->sites.n_sites * 24)) ||
+        (row_table && ensure(c, c->rt.row_tab, c->sites.n_sites * 32)) || ensure(c, c->win_ll, T * (size_t)c->sites.n_win * 24))
         return 1;
-    if (c->row_tab.cap != rt_cap0)
-        c->rt_gen = 0;                  // a new buffer (grown: the capacity tells, the address may be the old one): no table in it
     // targets / background weights change rarely between calls (a loop over windows sizes, repeated
     // timing steps): their device copies are rebuilt only when the inputs differ
-    const bool same_bg = c->prev_pu == pu_id && c->prev_has_bg == (bg_count ? 1 : 0) && c->prev_lanes == lanes &&
-                         (!bg_count || (c->prev_bg.size() == c->n_ids &&
-                                        std::equal(bg_count, bg_count + c->n_ids, c->prev_bg.begin()))) &&
-                         c->base_w.p;
+    const bool same_bg = c->bg.prev_pu == pu_id && c->bg.prev_has_bg == (bg_count ? 1 : 0) && c->bg.prev_lanes == lanes &&
+                         (!bg_count || (c->bg.prev_bg.size() == c->pan.n_ids &&
+                                        std::equal(bg_count, bg_count + c->pan.n_ids, c->bg.prev_bg.begin()))) &&
+                         c->bg.base_w.p;
     const bool same_inputs = same_bg && c->prev_targets.size() == T && std::equal(targets, targets + T, c->prev_targets.begin()) &&
                              c->weight.p;
     if (!same_bg && set_background(c, bg_count, pu_id, lanes)) return 1;
@@ -2309,8 +2062,8 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     const bool flush = c->fin.pending && (!same_bg || c->fin.sites_gen != c->sites_gen || !P.use_pop || P.ibd0_pass ||
                                           !P.fin_in_next || c->fin.count != (unsigned)P.T_cnt || c->fin.args.t_base != (uint32_t)P.T_g);
     if (flush && flush_finalize(c)) return 1;
-    const int ev_slot = (c->ev_head + 1) % ibdg_ctx::EV_RING;      // becomes the head once the run is queued
-    ibdg_ctx::EvSet &E = c->evs[ev_slot];
+    const int ev_slot = (c->tl.ev_head + 1) % ibdg_ctx::Timeline::EV_RING;      // becomes the head once the run is queued
+    EvSet &E = c->tl.evs[ev_slot];
     if (start_run(c, P, E, flush)) return 1;
 
     const ibdg::RowsArgs sa = rows_args(c, ld_mode, row_table);
@@ -2322,8 +2075,8 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
         // with the next window's records kept in flight -- measured slower at every size (rows_blocks_per_cu 4..28:
         // 0.048-0.041 ms against 0.040)
         unsigned blocks = 0;
-        if (c->opt_rows_blocks > 0)
-            blocks = std::max<unsigned>(1u, (unsigned)((size_t)c->n_cu * c->opt_rows_blocks / T));
+        if (c->opt.rows_blocks > 0)
+            blocks = std::max<unsigned>(1u, (unsigned)((size_t)c->n_cu * c->opt.rows_blocks / T));
         ibdg::launch_rows_windows(sa, (unsigned)T, c->stream, blocks);
     }
     if (!P.dispatch_events && !P.end_in_dispatch)
@@ -2332,11 +2085,11 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     ring_mark_readers(c, T, E.ld_end, P.rows_on_main ? nullptr : E.s2_end);
     HIP_TRY(c, hipGetLastError());
     if (P.rt_build)
-        c->rt_gen = c->up_gen;
-    c->ev_head = ev_slot; ++c->runs_done; c->chain_ok = true;
-    if (!c->opt_async && quiesce(c)) return 1;
+        c->rt.made(*c);
+    c->tl.ev_head = ev_slot; ++c->tl.runs_done; c->tl.chain_ok = true;
+    if (!c->opt.async && quiesce(c)) return 1;
     c->n_targets = T; c->have_results = true;
-    c->res_site_mode = row_table ? 2 : (int)c->opt_site_results;
+    c->res_site_mode = row_table ? 2 : (int)c->opt.site_results;
     return 0;
 }
 
@@ -2353,21 +2106,21 @@ int ibdg_get_site_af(ibdg_ctx *c, double *af)
 {
     if (!c) return 1;
     if (!c->have_results) return fail(c, "[::] ERROR in ibdg_get_site_af: no results (call ibdg_run)");
-    if (!c->counts_valid) return fail(c, "[::] ERROR in ibdg_get_site_af: alt counts not computed yet");
+    if (!c->pan.counts_valid) return fail(c, "[::] ERROR in ibdg_get_site_af: alt counts not computed yet");
     // made when asked for: it depends on the panel row (or the -A value) only, and no run needs it
     HIP_TRY(c, hipSetDevice(c->device));
-    if (ensure(c, c->af, c->n_sites * 8)) return 1;
+    if (ensure(c, c->af, c->sites.n_sites * 8)) return 1;
     if (join_streams(c)) return 1;
     ibdg::RowsArgs ra = {};
-    ra.rec_all = (const uint2 *)c->rec_all.p;
-    ra.n_sites = c->n_sites;
-    ra.n_ids = c->n_ids;
-    ra.alt_count = (const uint32_t *)c->alt_count.p;
-    ra.fo = c->have_fo ? (const double *)c->fo.p : nullptr;
+    ra.rec_all = (const uint2 *)c->sites.rec_all.p;
+    ra.n_sites = c->sites.n_sites;
+    ra.n_ids = c->pan.n_ids;
+    ra.alt_count = (const uint32_t *)c->pan.alt_count.p;
+    ra.fo = c->sites.have_fo ? (const double *)c->sites.fo.p : nullptr;
     ra.af = (double *)c->af.p;
     ibdg::launch_site_af(ra, c->stream);
     HIP_TRY(c, hipGetLastError());
-    return fetch(c, af, c->af.p, c->n_sites * 8);
+    return fetch(c, af, c->af.p, c->sites.n_sites * 8);
 }
 
 int ibdg_get_site_ll(ibdg_ctx *c, size_t t, double *out)
@@ -2381,34 +2134,34 @@ int ibdg_get_site_ll(ibdg_ctx *c, size_t t, double *out)
         HIP_TRY(c, hipSetDevice(c->device));
         if (join_streams(c)) return 1;
         ibdg::RowsArgs ra = {};
-        ra.panel = (const uint64_t *)c->panel.p;
-        ra.stride = c->stride;
-        ra.n_ids = c->n_ids;
-        ra.rec_all = (const uint2 *)c->rec_all.p;
-        ra.n_sites = c->n_sites;
-        ra.lut = (const double *)c->lut.p;
-        ra.t32 = c->pop_lut_ok ? (const uint4 *)c->t32.p : nullptr;
-        ra.n_pairs = c->n_pairs;
-        ra.row_tab = (double *)c->row_tab.p;
+        ra.panel = (const uint64_t *)c->pan.panel.p;
+        ra.stride = c->pan.stride;
+        ra.n_ids = c->pan.n_ids;
+        ra.rec_all = (const uint2 *)c->sites.rec_all.p;
+        ra.n_sites = c->sites.n_sites;
+        ra.lut = (const double *)c->tab.lut.p;
+        ra.t32 = c->tab.pop_lut_ok ? (const uint4 *)c->pan.t32.p : nullptr;
+        ra.n_pairs = c->pan.n_pairs;
+        ra.row_tab = (double *)c->rt.row_tab.p;
         ibdg::launch_site_expand(ra, c->prev_targets[t], (double *)c->site_ll.p, c->stream);
         HIP_TRY(c, hipGetLastError());
-        return fetch(c, out, c->site_ll.p, c->n_sites * 24);
+        return fetch(c, out, c->site_ll.p, c->sites.n_sites * 24);
     }
-    return fetch(c, out, (const char *)c->site_ll.p + t * c->n_sites * 24, c->n_sites * 24);
+    return fetch(c, out, (const char *)c->site_ll.p + t * c->sites.n_sites * 24, c->sites.n_sites * 24);
 }
 
 int ibdg_get_window_ll(ibdg_ctx *c, size_t t, double *out)
 {
     if (!c) return 1;
     if (!c->have_results || t >= c->n_targets) return fail(c, "[::] ERROR in ibdg_get_window_ll: no results for target %zu", t);
-    return fetch(c, out, (const char *)c->win_ll.p + t * (size_t)c->n_win * 24, (size_t)c->n_win * 24);
+    return fetch(c, out, (const char *)c->win_ll.p + t * (size_t)c->sites.n_win * 24, (size_t)c->sites.n_win * 24);
 }
 
 int ibdg_get_window_ll_all(ibdg_ctx *c, double *out)
 {
     if (!c) return 1;
     if (!c->have_results) return fail(c, "[::] ERROR in ibdg_get_window_ll_all: no results (call ibdg_run)");
-    return fetch(c, out, c->win_ll.p, c->n_targets * (size_t)c->n_win * 24);
+    return fetch(c, out, c->win_ll.p, c->n_targets * (size_t)c->sites.n_win * 24);
 }
 
 // Segmented sums over the window table of the last run (ibdg_llr.hip).  On the main stream behind join_streams: LIBD2 comes
@@ -2422,8 +2175,8 @@ int ibdg_window_llr_sums(ibdg_ctx *c, const uint32_t *first, const uint32_t *end
     for (size_t s = 0; s < n_seg; ++s) {
         if (end[s] < first[s])
             return fail(c, "[::] ERROR in ibdg_window_llr_sums: range %zu is reversed ([%u, %u))", s, first[s], end[s]);
-        if (end[s] > c->n_win)
-            return fail(c, "[::] ERROR in ibdg_window_llr_sums: range %zu ends at %u, past the %u windows", s, end[s], c->n_win);
+        if (end[s] > c->sites.n_win)
+            return fail(c, "[::] ERROR in ibdg_window_llr_sums: range %zu ends at %u, past the %u windows", s, end[s], c->sites.n_win);
     }
     if (n_seg == 0 || c->n_targets == 0) return 0;
     constexpr size_t LLR_SLAB = (size_t)1 << 22;
@@ -2443,7 +2196,7 @@ int ibdg_window_llr_sums(ibdg_ctx *c, const uint32_t *first, const uint32_t *end
     for (size_t s0 = 0; s0 < n_seg; s0 += chunk) {
         const size_t m = std::min(chunk, n_seg - s0);
         HIP_TRY(c, hipMemcpyAsync(c->llr_seg.p, seg.data() + 2 * s0, m * 8, hipMemcpyHostToDevice, c->stream));
-        ibdg::launch_llr_sums((const double *)c->win_ll.p, c->n_win, (uint32_t)T, (const uint32_t *)c->llr_seg.p, (uint32_t)m,
+        ibdg::launch_llr_sums((const double *)c->win_ll.p, c->sites.n_win, (uint32_t)T, (const uint32_t *)c->llr_seg.p, (uint32_t)m,
                               nb, (double *)c->llr_part.p, (double *)c->llr_out.p, c->stream);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpy2DAsync(out + s0 * 4, n_seg * 32, c->llr_out.p, m * 32, m * 32, T, hipMemcpyDeviceToHost, c->stream));
@@ -2456,17 +2209,17 @@ int ibdg_window_llr_sums(ibdg_ctx *c, const uint32_t *first, const uint32_t *end
 int ibdg_get_alt_counts(ibdg_ctx *c, size_t first_row, size_t n, uint32_t *out)
 {
     if (!c) return 1;
-    if (!c->counts_valid) return fail(c, "[::] ERROR in ibdg_get_alt_counts: counts not computed yet");
-    if (first_row + n > c->n_rows) return fail(c, "[::] ERROR in ibdg_get_alt_counts: range outside the panel");
-    return fetch(c, out, (const char *)c->alt_count.p + first_row * 4, n * 4);
+    if (!c->pan.counts_valid) return fail(c, "[::] ERROR in ibdg_get_alt_counts: counts not computed yet");
+    if (first_row + n > c->pan.n_rows) return fail(c, "[::] ERROR in ibdg_get_alt_counts: range outside the panel");
+    return fetch(c, out, (const char *)c->pan.alt_count.p + first_row * 4, n * 4);
 }
 
 int ibdg_run_ms(ibdg_ctx *c, unsigned back, float out[5])
 {
     if (!c || !out) return 1;
-    if (back + 1 >= (unsigned)ibdg_ctx::EV_RING || (long)back >= c->runs_done)
+    if (back + 1 >= (unsigned)ibdg_ctx::Timeline::EV_RING || (long)back >= c->tl.runs_done)
         return fail(c, "[::] ERROR in ibdg_run_ms: no timing kept for the run %u calls back", back);
-    const ibdg_ctx::EvSet &E = c->evs[(c->ev_head + ibdg_ctx::EV_RING - (int)back) % ibdg_ctx::EV_RING];
+    const EvSet &E = c->tl.evs[(c->tl.ev_head + ibdg_ctx::Timeline::EV_RING - (int)back) % ibdg_ctx::Timeline::EV_RING];
     if (quiesce(c)) return 1;
     float v, w;
     HIP_TRY(c, hipEventElapsedTime(&v, E.start, E.ld_end));
@@ -2489,9 +2242,9 @@ int ibdg_run_ms(ibdg_ctx *c, unsigned back, float out[5])
 int ibdg_run_kernel_ms(ibdg_ctx *c, unsigned back, float *ms)
 {
     if (!c || !ms) return 1;
-    if (back + 1 >= (unsigned)ibdg_ctx::EV_RING || (long)back >= c->runs_done)
+    if (back + 1 >= (unsigned)ibdg_ctx::Timeline::EV_RING || (long)back >= c->tl.runs_done)
         return fail(c, "[::] ERROR in ibdg_run_kernel_ms: no timing kept for the run %u calls back", back);
-    const ibdg_ctx::EvSet &E = c->evs[(c->ev_head + ibdg_ctx::EV_RING - (int)back) % ibdg_ctx::EV_RING];
+    const EvSet &E = c->tl.evs[(c->tl.ev_head + ibdg_ctx::Timeline::EV_RING - (int)back) % ibdg_ctx::Timeline::EV_RING];
     if (!E.has_kernel_times)
         return fail(c, "[::] ERROR in ibdg_run_kernel_ms: that run did not use the exponent-counting --LD kernel");
     if (quiesce(c)) return 1;
@@ -2502,7 +2255,7 @@ int ibdg_run_kernel_ms(ibdg_ctx *c, unsigned back, float *ms)
 int ibdg_last_run_ms(ibdg_ctx *c, float out[5])
 {
     if (!c || !out) return 1;
-    if (c->runs_done == 0) {
+    if (c->tl.runs_done == 0) {
         for (int i = 0; i < 5; ++i) out[i] = 0.f;
         return 0;
     }
@@ -2515,111 +2268,27 @@ int ibdg_last_count_unit(const ibdg_ctx *c) { return c ? c->last_count_unit : 0;
 
 int ibdg_ld_layout(const ibdg_ctx *c)
 {
-    if (!c || !c->sites_valid || !c->pop_sites_ok)
+    if (!c || !c->sites.sites_valid || !c->lay.pop_sites_ok)
         return 0;
-    return c->compact ? 2 : 1;
+    return c->lay.compact ? 2 : 1;
 }
 
 int ibdg_set_option(ibdg_ctx *c, const char *name, long value)
 {
     if (!c || !name) return 1;
-    if (!strcmp(name, "count_in_run")) { c->opt_count_in_run = value != 0; return 0; }
-    if (!strcmp(name, "multi_target")) { c->opt_multi_target = value != 0; return 0; }
-    if (!strcmp(name, "mfma_targets")) { c->opt_mfma_targets = value != 0; return 0; }
-    if (!strcmp(name, "mfma_plain_tau")) { c->opt_mfma_plain_tau = value != 0; return 0; }
-    if (!strcmp(name, "mfma_min")) {
-        if (value < 1 || value > IBDG_TG) return fail(c, "[::] ERROR in ibdg_set_option: mfma_min must be 1..%d", IBDG_TG);
-        c->opt_mfma_min = value;
+    for (const OptionRow &o : OPTION_TABLE) {
+        if (strcmp(name, o.name))
+            continue;
+        const bool in_set = o.kind == OptionRow::SET && value >= 0 && value < 63 && ((o.lo >> value) & 1);
+        if ((o.kind == OptionRow::RANGE && (value < o.lo || value > o.hi)) || (o.kind == OptionRow::SET && !in_set)) {
+            if (o.text)
+                return fail(c, "[::] ERROR in ibdg_set_option: %s must be %s", o.name, o.text);
+            return fail(c, "[::] ERROR in ibdg_set_option: %s must be %ld..%ld", o.name, o.lo, o.hi);
+        }
+        if (o.effect == OptionRow::JOIN_STREAMS && join_streams(c)) return 1;
+        if (o.effect == OptionRow::FIX_WPG) c->opt.wpg_fixed = true;
+        c->opt.*o.member = o.kind == OptionRow::BOOL ? value != 0 : o.kind == OptionRow::CLAMP ? std::min(std::max(value, o.lo), o.hi) : value;
         return 0;
-    }
-    if (!strcmp(name, "guided_runs")) { c->opt_guided = value; return 0; }
-    if (!strcmp(name, "compact_align")) {
-        if (value != 1 && value != 2 && value != 4 && value != 8 && value != 16 && value != 32)
-            return fail(c, "[::] ERROR in ibdg_set_option: compact_align must be 1, 2, 4, 8, 16 or 32");
-        c->opt_compact_align = value;
-        return 0;
-    }
-    if (!strcmp(name, "mfma_wg_sum")) { c->opt_mfma_wg_sum = value != 0; return 0; }
-    if (!strcmp(name, "mfma_batch_groups")) { c->opt_mfma_batch = value < 1 ? 1 : (value > 64 ? 64 : value); return 0; }
-    if (!strcmp(name, "ibd0_after")) { c->opt_ibd0_after = value < 0 ? 0 : value; return 0; }
-    if (!strcmp(name, "end_in_dispatch")) { c->opt_end_in_dispatch = value != 0; return 0; }
-    if (!strcmp(name, "prep_ahead")) { c->opt_prep_ahead = value != 0; return 0; }
-    if (!strcmp(name, "dispatch_events")) { c->opt_dispatch_events = value != 0; return 0; }
-    if (!strcmp(name, "async")) { c->opt_async = value != 0; return 0; }
-    if (!strcmp(name, "dev_inputs_ready")) { c->opt_dev_inputs_ready = value != 0; return 0; }
-    if (!strcmp(name, "staged_upload")) { c->opt_staged_upload = value != 0; return 0; }
-    if (!strcmp(name, "stage_workers")) {
-        if (value < 1 || value > ibdg_ctx::STAGE_WORKERS) return fail(c, "[::] ERROR in ibdg_set_option: stage_workers must be 1..%d", ibdg_ctx::STAGE_WORKERS);
-        c->opt_stage_workers = value; return 0;
-    }
-    if (!strcmp(name, "compact_tiles")) {
-        if (value < -1 || value > 1) return fail(c, "[::] ERROR in ibdg_set_option: compact_tiles must be -1 (never), 0 (auto) or 1 (always)");
-        c->opt_compact = value; return 0;
-    }
-    if (!strcmp(name, "finalize_in_next")) {
-        if (value < 0 || value > 1) return fail(c, "[::] ERROR in ibdg_set_option: finalize_in_next must be 0 or 1");
-        if (join_streams(c)) return 1;
-        c->opt_fin_next = value; return 0;
-    }
-    if (!strcmp(name, "sum_dpp")) {
-        if (value < 0 || value > 1) return fail(c, "[::] ERROR in ibdg_set_option: sum_dpp must be 0 or 1");
-        c->opt_sum_dpp = value; return 0;
-    }
-    if (!strcmp(name, "mx_counts")) {
-        if (value < 0 || value > 1) return fail(c, "[::] ERROR in ibdg_set_option: mx_counts must be 0 or 1");
-        c->opt_mx_counts = value; return 0;
-    }
-    if (!strcmp(name, "reserve_compact")) {
-        if (value < 0 || value > 1) return fail(c, "[::] ERROR in ibdg_set_option: reserve_compact must be 0 or 1");
-        c->opt_reserve_compact = value; return 0;
-    }
-    if (!strcmp(name, "compact_density")) {
-        if (value < 1 || value > 1000000) return fail(c, "[::] ERROR in ibdg_set_option: compact_density must be 1..1000000");
-        c->opt_compact_density = value; return 0;
-    }
-    if (!strcmp(name, "compact_targets")) {
-        if (value < 1 || value > 65536) return fail(c, "[::] ERROR in ibdg_set_option: compact_targets must be 1..65536");
-        c->opt_compact_targets = value; return 0;
-    }
-    if (!strcmp(name, "site_results")) {
-        if (value < 0 || value > 1) return fail(c, "[::] ERROR in ibdg_set_option: site_results must be 0 or 1");
-        c->opt_site_results = value; return 0;
-    }
-    if (!strcmp(name, "rows_blocks_per_cu")) {
-        if (value < 0 || value > 128) return fail(c, "[::] ERROR in ibdg_set_option: rows_blocks_per_cu must be 0..128");
-        c->opt_rows_blocks = value; return 0;
-    }
-    if (!strcmp(name, "site_blocks_per_cu")) {
-        if (value < 0 || value > 128) return fail(c, "[::] ERROR in ibdg_set_option: site_blocks_per_cu must be 0..128");
-        c->opt_site_blocks = value; return 0;
-    }
-    if (!strcmp(name, "recount_blocks_per_cu")) {
-        if (value < 0 || value > 128) return fail(c, "[::] ERROR in ibdg_set_option: recount_blocks_per_cu must be 0..128");
-        c->opt_recount_blocks = value; return 0;
-    }
-    if (!strcmp(name, "chunks_per_wave")) {
-        if (value < 0 || value > 5) return fail(c, "[::] ERROR in ibdg_set_option: chunks_per_wave must be 0..5");
-        c->opt_cpw = value; return 0;
-    }
-    if (!strcmp(name, "waves_per_block")) {
-        if (value < 1 || value > 8) return fail(c, "[::] ERROR in ibdg_set_option: waves_per_block must be 1..8");
-        c->opt_waves = value; return 0;
-    }
-    if (!strcmp(name, "ld_variant")) {
-        if (value < 0 || value > 3) return fail(c, "[::] ERROR in ibdg_set_option: ld_variant must be 0 (auto), 1 (strict), 2 (exponent counting) or 3 (reference order)");
-        c->opt_variant = value; return 0;
-    }
-    if (!strcmp(name, "ring_slots")) {
-        if (value != 2 && value != 3 && value != 4 && value != 8) return fail(c, "[::] ERROR in ibdg_set_option: ring_slots must be 2, 3, 4 or 8");
-        c->opt_ring = value; return 0;
-    }
-    if (!strcmp(name, "record_lds_bytes")) {
-        if (value < 1024 || value > 96 * 1024) return fail(c, "[::] ERROR in ibdg_set_option: record_lds_bytes must be 1024..98304");
-        c->opt_recbytes = value; return 0;
-    }
-    if (!strcmp(name, "windows_per_wave")) {
-        if (value < 1 || value > 65536) return fail(c, "[::] ERROR in ibdg_set_option: windows_per_wave must be 1..65536");
-        c->opt_wpg = value; c->opt_wpg_fixed = true; return 0;
     }
     return fail(c, "[::] ERROR in ibdg_set_option: unknown option '%s'", name);
 }
@@ -2628,7 +2297,7 @@ int ibdg_set_background_order(ibdg_ctx *c, const uint32_t *ids, size_t n)
 {
     if (!c) return 1;
     if (n && !ids) return fail(c, "[::] ERROR in ibdg_set_background_order: ids is NULL");
-    c->bg_order.assign(ids, ids + n);
+    c->opt.bg_order.assign(ids, ids + n);
     return 0;
 }
 

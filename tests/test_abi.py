@@ -144,12 +144,18 @@ OPTIONS_WITHOUT_A_TEST = {}
 
 def test_every_option_is_set_by_a_gpu_test():
     """include/ibdgem_hip.h promises the same results whatever an option says; that holds only for options some test sets.
-    Every name ibdg_set_option compares against must appear as a quoted string in a tests/test_gpu_*.py."""
+    Every name ibdg_set_option compares against (the rows of OPTION_TABLE, ibdg_ctx.h, which it walks) must appear as a
+    quoted string in a tests/test_gpu_*.py."""
     import glob
     src = open(os.path.join(REPO, "ibdgem_amd", "csrc", "ibdg_api.cpp")).read()
     body = src[src.index("int ibdg_set_option("):]
     body = body[:body.index("\n}\n")]
-    names = re.findall(r'!strcmp\(name, "([a-z0-9_]+)"\)', body)
+    assert "for (const OptionRow &o : OPTION_TABLE)" in body and "strcmp(name, o.name)" in body
+    table = open(os.path.join(REPO, "ibdgem_amd", "csrc", "ibdg_ctx.h")).read()
+    table = table[table.index("const OptionRow OPTION_TABLE[] = {"):]
+    table = table[:table.index("\n};\n")]
+    names = re.findall(r'^    \{"([a-z0-9_]+)", &Opt::', table, flags=re.M)
+    assert len(names) == table.count("\n    {")                                 # (every row was read)
     assert len(names) >= 20 and len(set(names)) == len(names), names
     assert "unknown option" in body                                            # (the function was read to its last line)
     files = sorted(glob.glob(os.path.join(REPO, "tests", "test_gpu_*.py")))

@@ -305,7 +305,7 @@ ROWS_CASES = {
 def test_row_and_window_kernels_on_several_trips(oracle, name):
     L, option, value, more, runs, checked = ROWS_CASES[name]
     c = rows_case(L)
-    per_cu = 2 if value is None else value                # (ibdg_ctx::opt_site_blocks = 2)
+    per_cu = 2 if value is None else value                # (ibdg_ctx::Options::site_blocks = 2)
     for targets, ld in runs:
         trips = rows_trips(c["n_win"], len(targets), per_cu)
         assert trips >= 2, (name, trips)
@@ -619,3 +619,147 @@ def test_staging_team_of_fewer_threads(tmp_path, workers):
             assert_bits(eng.window_ll(0), ref, f"panel staged by {workers} threads")
         with pytest.raises(E.EngineError, match="stage_workers must be"):
             eng.set_option("stage_workers", 0)
+
+
+# --------------------------------------------------------------------------- 6. one context through every change of input
+LIFE_N, LIFE_L = 130, 3000                    # three chunks of 64 individuals, the last one partial
+LIFE_N2 = 70
+
+
+def life_case():
+    """synth at a mean depth of 0.7: about half of the rows carry reads.  (Checked with the oracle when the test was
+    written: at every (panel, window) used below the --LD columns of all windows are finite and non-zero.)"""
+    alle, nr, na = synth(7001, LIFE_L, LIFE_N, cov_mean=0.7)
+    alle2 = synth(7002, LIFE_L, LIFE_N2)[0]
+    n_cov = int(((nr.astype(int) + na) > 0).sum())
+    assert 0.4 * LIFE_L < n_cov < 0.6 * LIFE_L and cdiv(LIFE_N, 64) == 3 and LIFE_N % 64 != 0
+    bg = np.ones(LIFE_N, dtype=np.uint8)
+    bg[::3] = 2
+    bg[5] = 0
+    return dict(alle=alle, alle2=alle2, nr=nr, na=na, bg=bg, rows=np.arange(LIFE_L, dtype=np.uint32))
+
+
+def life_results(eng, T, site_of=()):
+    win = [eng.window_ll(i) for i in range(T)]
+    for w in win:
+        assert np.isfinite(w).all() and (w != 0).all()              # (a comparison of zeros would prove nothing)
+    return dict(win=win, site={i: eng.site_ll(i) for i in site_of}, variant=eng.last_ld_variant(),
+                unit=eng.last_count_unit(), layout=eng.ld_layout())
+
+
+def life_fresh(c, panel, N, W, opts, targets, ld, bg, site_of):
+    """A context of its own given only one step's inputs: the options in force, the panel, the sites, the run."""
+    with E.Engine(0, 0.02, 20) as ref:
+        for k, v in opts.items():
+            ref.set_option(k, v)
+        ref.upload_panel(panel, N)
+        ref.upload_sites(c["rows"], c["nr"], c["na"], W)
+        ref.run(targets, ld=ld, bg_count=bg)
+        return life_results(ref, len(targets), site_of)
+
+
+def test_one_context_lives_through_every_change_of_input():
+    """Panel, sites, layout, background and comparison individuals change under ONE context, in the order in which the cached
+    products (row table, IBD0 pass, fragment base, images, the count towards ibd0_after) are made, kept and dropped; after every
+    step the tables are those of a fresh context given only that step's inputs, bit for bit.  Single steps have tests of their
+    own -- the kept pass: test_gpu_parity.test_ibd0_from_one_pass_over_the_site_list; the re-layout in the middle of a series:
+    the test around test_gpu_parity.py's `compact_targets`; a second panel: test_staging_team_of_fewer_threads -- the point
+    here is the sequence.  --LD variant and count unit are compared with the fresh context's where that has made as many runs
+    (step 1); the count units named otherwise are what plan_run's rules give for this history."""
+    c = life_case()
+    panel, panel2 = E.pack_alleles_fast(c["alle"]), E.pack_alleles_fast(c["alle2"])
+    opts = {"async": 1}
+    # (what, options set before it, upload of sites with this window or None, targets, ld, background, per-site tables of,
+    #  the count unit expected of the long-lived context, its layout after the run)
+    steps = [
+        ("1: --LD, one individual", {}, 50, [7], True, None, (0,), 2, 1),
+        ("2: again (images reused)", {}, None, [7], True, None, (), 2, 1),
+        ("3: another individual", {}, None, [129], True, None, (0,), 2, 1),
+        ("4: five through the matrix cores (IBD0 pass)", {}, None, [3, 64, 7, 128, 90], True, None, (), 0, 1),
+        ("5: one again (IBD1 form from the kept pass)", {}, None, [129], True, None, (), 3, 1),
+        ("6: another background", {}, None, [129], True, c["bg"], (), 2, 1),
+        ("7: re-layout in the middle of the series", {"compact_targets": 1}, None, [129], True, c["bg"], (0,), 2, 2),
+        ("8: the same sites with window 32", {}, 32, [129], True, c["bg"], (), 2, 2),
+        ("9+10: twenty individuals, per-site tables of two", {"site_results": 1}, None, list(range(40, 60)), True, c["bg"],
+         (0, 19), 0, 2),
+        ("11: non-LD (a pending finalising step is flushed)", {}, None, [61], False, c["bg"], (0,), 0, 2),
+    ]
+    with E.Engine(0, 0.02, 20) as eng:
+        eng.set_option("async", 1)
+        eng.upload_panel(panel, LIFE_N)
+        W = None
+        for n, (what, more, new_w, targets, ld, bg, site_of, unit, layout) in enumerate(steps):
+            for k, v in more.items():
+                eng.set_option(k, v)
+            opts.update(more)
+            if new_w is not None:
+                W = new_w
+                eng.upload_sites(c["rows"], c["nr"], c["na"], W)
+            if what.startswith("11"):
+                eng.run([61], ld=True, bg_count=bg)                     # (leaves its finalising step to a successor)
+            eng.run(targets, ld=ld, bg_count=bg)
+            got = life_results(eng, len(targets), site_of)
+            want = life_fresh(c, panel, LIFE_N, W, opts, targets, ld, bg, site_of)
+            for i in range(len(targets)):
+                assert_bits(got["win"][i], want["win"][i], f"step {what}: windows of #{i}")
+            for i in site_of:
+                assert_bits(got["site"][i], want["site"][i], f"step {what}: per-site values of #{i}")
+            assert got["variant"] == want["variant"] == (2 if ld else 0), what
+            assert got["unit"] == unit and got["layout"] == layout, (what, got["unit"], got["layout"])
+            if n == 0:
+                assert got["unit"] == want["unit"] and got["layout"] == want["layout"], what
+        # 12: a second panel, then sites and one individual
+        eng.upload_panel(panel2, LIFE_N2)
+        with pytest.raises(E.EngineError, match="no sites"):
+            eng.run([69], ld=True)
+        eng.upload_sites(c["rows"], c["nr"], c["na"], 50)
+        eng.run([69], ld=True)
+        got = life_results(eng, 1, (0,))
+        want = life_fresh(c, panel2, LIFE_N2, 50, opts, [69], True, None, (0,))
+        assert_bits(got["win"][0], want["win"][0], "step 12: windows on the second panel")
+        assert_bits(got["site"][0], want["site"][0], "step 12: per-site values on the second panel")
+        assert got["variant"] == want["variant"] == 2
+
+
+# --------------------------------------------------------------------------- 7. ibdg_set_option, option by option
+# Written from the chain of comparisons ibdg_set_option was before it became a table: name -> (accepted values at both ends,
+# refused values on either side).  Nothing refused: the option takes any value (stored as value != 0, clamped, or as it is).
+OPTION_CASES = {
+    "count_in_run": ((0, 1, -5, 1 << 40), ()), "multi_target": ((0, 1, -5, 1 << 40), ()),
+    "mfma_targets": ((0, 1, -5, 1 << 40), ()), "mfma_plain_tau": ((0, 1, -5, 1 << 40), ()),
+    "mfma_wg_sum": ((0, 1, -5, 1 << 40), ()), "end_in_dispatch": ((0, 1, -5, 1 << 40), ()),
+    "prep_ahead": ((0, 1, -5, 1 << 40), ()), "dispatch_events": ((0, 1, -5, 1 << 40), ()),
+    "async": ((0, 1, -5, 1 << 40), ()), "dev_inputs_ready": ((0, 1, -5, 1 << 40), ()),
+    "staged_upload": ((0, 1, -5, 1 << 40), ()),
+    "guided_runs": ((0, 4, -3, 1 << 40), ()),                            # unchecked
+    "mfma_batch_groups": ((1, 64, -7, 0, 65, 1 << 40), ()),              # clamped to 1..64
+    "ibd0_after": ((0, 1 << 40, -1, -(1 << 40)), ()),                    # clamped to >= 0
+    "mfma_min": ((1, 15), (0, 16)), "stage_workers": ((1, 8), (0, 9)), "compact_tiles": ((-1, 1), (-2, 2)),
+    "finalize_in_next": ((0, 1), (-1, 2)), "sum_dpp": ((0, 1), (-1, 2)), "mx_counts": ((0, 1), (-1, 2)),
+    "reserve_compact": ((0, 1), (-1, 2)), "site_results": ((0, 1), (-1, 2)),
+    "compact_density": ((1, 1000000), (0, 1000001)), "compact_targets": ((1, 65536), (0, 65537)),
+    "rows_blocks_per_cu": ((0, 128), (-1, 129)), "site_blocks_per_cu": ((0, 128), (-1, 129)),
+    "recount_blocks_per_cu": ((0, 128), (-1, 129)), "chunks_per_wave": ((0, 5), (-1, 6)),
+    "waves_per_block": ((1, 8), (0, 9)), "ld_variant": ((0, 3), (-1, 4)),
+    "record_lds_bytes": ((1024, 98304), (1023, 98305)), "windows_per_wave": ((1, 65536), (0, 65537)),
+    "compact_align": ((1, 2, 4, 8, 16, 32), (0, -1, 3, 24, 33, 64, 1 << 40)),
+    "ring_slots": ((2, 3, 4, 8), (1, 0, -2, 5, 6, 7, 9, 64, 1 << 40)),
+}
+
+
+def test_every_option_accepts_and_refuses_what_it_did():
+    with E.Engine() as eng:
+        for name, (good, bad) in OPTION_CASES.items():
+            for v in bad:
+                with pytest.raises(E.EngineError, match=rf"ERROR in ibdg_set_option: {name} must be "):
+                    eng.set_option(name, v)
+            for v in good:
+                assert eng.lib.ibdg_set_option(eng.ctx, name.encode(), v) == 0, (name, v)
+        with pytest.raises(E.EngineError, match="unknown option 'no_such_option'"):
+            eng.set_option("no_such_option", 1)
+        with pytest.raises(E.EngineError, match="mfma_min must be 1..15"):
+            eng.set_option("mfma_min", 99)
+        with pytest.raises(E.EngineError, match=r"compact_tiles must be -1 \(never\), 0 \(auto\) or 1 \(always\)"):
+            eng.set_option("compact_tiles", 7)
+        with pytest.raises(E.EngineError, match="ring_slots must be 2, 3, 4 or 8"):
+            eng.set_option("ring_slots", 5)
