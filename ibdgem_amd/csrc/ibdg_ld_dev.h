@@ -1,6 +1,6 @@
 // ibdg_ld_dev.h -- device helpers shared by the --LD kernels (ibdg_ld_popcount.hip, ibdg_ld_mfma.hip):
 // tile words of the transposed panel, fixed-order wave sums, the single-instruction integer forms of the
-// window end, LDS reads in assembly, the table product.
+// window end, LDS reads in assembly, the table product, the finalising step of a window.
 #pragma once
 #include "ibdg_kernels.h"
 
@@ -78,6 +78,39 @@ __device__ __forceinline__ double ibd0_from_pass(const double *__restrict__ p2c,
     for (uint32_t c = lane; c < n_chunks; c += 64)
         t0 += c == c_own ? own : pc[2 * c];
     return wave_sum_to_lane63(t0);
+}
+
+// Sum the per-chunk partials {IBD0, IBD1} of one window: lane c adds chunks c, c+64, .. (coalesced 16-byte loads)
+__device__ __forceinline__ void chunk_partial_sums(const double2 *__restrict__ p, uint32_t n_chunks, uint32_t lane, double &t0, double &t1)
+{
+    for (uint32_t c = lane; c < n_chunks; c += 64) {
+        const double2 v = p[c];
+        t0 += v.x;
+        t1 += v.y;
+    }
+}
+
+// The finalising step of window w for comparison individual t (one wave; src/ibdgem.c:751-752): the lanes' sums over the
+// chunks (t0: IBD0, t1: IBD1) meet in the fixed order of wave_sum_to_lane63 -- the same order whatever the launch --, IBD0
+// comes from the one pass over the site list instead where there was one (p2c non-null), and lane 63 applies the mantissa
+// of K' (its exponent went into every term) and takes the background average.
+__device__ __forceinline__ void finalize_window(double t0, double t1, const double *__restrict__ p2c, const double *__restrict__ p2w,
+                                                const uint32_t *__restrict__ targets, uint32_t lanes, uint32_t n_chunks,
+                                                uint32_t n_win, uint32_t w, uint32_t t, uint32_t lane,
+                                                const WinConst *__restrict__ wconst, const int *__restrict__ n_refpanel,
+                                                double *__restrict__ win_ll, const char *where)
+{
+    uint32_t tgt_own = p2c ? targets[t] : 0u;
+    IBDG_CHECK_TGT(tgt_own, p2c ? lanes : 1u, where);
+    t0 = p2c ? ibd0_from_pass(p2c, p2w, lanes, n_chunks, w, tgt_own, lane) : wave_sum_to_lane63(t0);
+    t1 = wave_sum_to_lane63(t1);
+    if (lane == 63) {
+        const int nref = n_refpanel[t];
+        const double mK = wconst[w].mK;
+        double *o = win_ll + ((size_t)t * n_win + w) * 3;
+        o[0] = (t0 * mK) / (double)nref;
+        o[1] = (t1 * mK) / (double)(nref * 4);
+    }
 }
 
 // The same additions for lane 63 alone: without the row masks of the two row_bcast steps the other rows take sums nobody
@@ -188,6 +221,68 @@ __device__ __forceinline__ void lds_read_pow8(uint4 (&p)[8], const uint32_t (&ad
                  : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4]), "v"(ad[5]), "v"(ad[6]), "v"(ad[7])
                  : "memory");
 }
+
+// ten power-table entries (16 B each) for the five products of one window
+__device__ __forceinline__ void lds_read_pow10(uint4 (&p)[10], const uint32_t (&ad)[10])
+{
+    asm volatile("ds_read_b128 %0, %10\n\t"
+                 "ds_read_b128 %1, %11\n\t"
+                 "ds_read_b128 %2, %12\n\t"
+                 "ds_read_b128 %3, %13\n\t"
+                 "ds_read_b128 %4, %14\n\t"
+                 "ds_read_b128 %5, %15\n\t"
+                 "ds_read_b128 %6, %16\n\t"
+                 "ds_read_b128 %7, %17\n\t"
+                 "ds_read_b128 %8, %18\n\t"
+                 "ds_read_b128 %9, %19\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(p[0]), "=&v"(p[1]), "=&v"(p[2]), "=&v"(p[3]), "=&v"(p[4]), "=&v"(p[5]), "=&v"(p[6]),
+                   "=&v"(p[7]), "=&v"(p[8]), "=&v"(p[9])
+                 : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4]), "v"(ad[5]), "v"(ad[6]), "v"(ad[7]),
+                   "v"(ad[8]), "v"(ad[9])
+                 : "memory");
+}
+
+// ten 8-byte power-table entries (the matrix-core form's tables of plain doubles)
+__device__ __forceinline__ void lds_read_pow10_b64(uint2 (&p)[10], const uint32_t (&ad)[10])
+{
+    asm volatile("ds_read_b64 %0, %10\n\t"
+                 "ds_read_b64 %1, %11\n\t"
+                 "ds_read_b64 %2, %12\n\t"
+                 "ds_read_b64 %3, %13\n\t"
+                 "ds_read_b64 %4, %14\n\t"
+                 "ds_read_b64 %5, %15\n\t"
+                 "ds_read_b64 %6, %16\n\t"
+                 "ds_read_b64 %7, %17\n\t"
+                 "ds_read_b64 %8, %18\n\t"
+                 "ds_read_b64 %9, %19\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(p[0]), "=&v"(p[1]), "=&v"(p[2]), "=&v"(p[3]), "=&v"(p[4]), "=&v"(p[5]), "=&v"(p[6]),
+                   "=&v"(p[7]), "=&v"(p[8]), "=&v"(p[9])
+                 : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4]), "v"(ad[5]), "v"(ad[6]), "v"(ad[7]),
+                   "v"(ad[8]), "v"(ad[9])
+                 : "memory");
+}
+
+// eight 8-byte power-table entries (the four IBD1 products of the IBD1 form)
+__device__ __forceinline__ void lds_read_pow8_b64(uint2 (&p)[8], const uint32_t (&ad)[8])
+{
+    asm volatile("ds_read_b64 %0, %8\n\t"
+                 "ds_read_b64 %1, %9\n\t"
+                 "ds_read_b64 %2, %10\n\t"
+                 "ds_read_b64 %3, %11\n\t"
+                 "ds_read_b64 %4, %12\n\t"
+                 "ds_read_b64 %5, %13\n\t"
+                 "ds_read_b64 %6, %14\n\t"
+                 "ds_read_b64 %7, %15\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(p[0]), "=&v"(p[1]), "=&v"(p[2]), "=&v"(p[3]), "=&v"(p[4]), "=&v"(p[5]), "=&v"(p[6]), "=&v"(p[7])
+                 : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4]), "v"(ad[5]), "v"(ad[6]), "v"(ad[7])
+                 : "memory");
+}
+
+// (the four statements above are one pattern -- N reads of BYTES bytes and one wait -- but stay four: a template cannot paste
+// its parameters into an asm statement's text or grow its operand list)
 
 // rho^E2 * sigma^E3 * 2^eK from two table entries {m (2 words), e, pad}; the mantissa of K' is
 // applied once per window in k_ld_finalize

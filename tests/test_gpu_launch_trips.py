@@ -8,7 +8,8 @@ test whose loops wrap is tests/test_gpu_fullsize.py: minutes, one shape and one 
   3. k_alt_count<LOADS> past its block cap at upload and beside an --LD kernel, k_alt_count_long past its wave count, every
      one with a partial last group;
   4. k_llr_partial past LLR_MAX_BLOCKS items;
-  5. the options sum_dpp 0, end_in_dispatch 0, reserve_compact 0, compact_density, stage_workers.
+  5. the options sum_dpp 0, end_in_dispatch 0, reserve_compact 0, compact_density, stage_workers;
+  6. ring_slots 2, 3, 4, 8 in every counting form (vector, matrix-core, IBD1, groups of four), tables in LDS and in memory.
 
 Every multi-trip test restates the formula of its launch wrapper (next to the name of the lines it mirrors) and asserts the
 trip count BEFORE it compares anything: a shape that stops wrapping must fail, not pass with one trip.  No numeric bar is
@@ -486,6 +487,94 @@ def test_wave_sums_by_ds_swizzle(oracle, which):
                 assert eng.last_ld_variant() == 2 and eng.last_count_unit() in (2, 3)
                 tables[dpp] = eng.window_ll(0)
         assert_bits(tables[0], tables[1], f"{form}: sum_dpp 0 vs 1")
+
+
+# --------------------------------------------------------------------------- 6. every counting form at every ring depth
+RING_DEPTHS = (2, 3, 4, 8)
+# form -> FORMS entry, further options, comparison individuals, ibdg_last_count_unit with the power tables in LDS / in
+# global memory (the IBD1 form needs them in LDS and falls back to the matrix-core form that counts everything).  Groups of
+# four: T = 5 is one group in k_ld_popcount_mt plus one single launch, whose unit is the one reported (ibd0_after 1: the
+# IBD1 form where it can be); T = 4 leaves no single launch (unit 0), so the group kernel is what ran.
+RING_FORMS = {
+    "vector": ("popcount mx0", {}, 1, 1, 1),
+    "matrix all-terms": ("popcount mx1", {}, 1, 2, 2),
+    "IBD1": ("popcount IBD1 form", {}, 1, 3, 2),
+    "groups of four": ("popcount_mt T4", {"ibd0_after": 1}, 5, 3, 2),
+}
+# placement -> N, L, W, tables in LDS.  In LDS: N = 130 is three chunks, the last partial.  In global memory: a window of
+# 1024 rows holds about 2000 reads, well past the 767 whose tables fit.
+RING_PLACEMENTS = {"tables in LDS": (130, 3000, 100, True), "tables in global memory": (70, 2600, 1024, False)}
+# uniform runs of 16 windows (guided_runs 0; windows_per_wave fixes the run length, ibdg_api.cpp build_segments), and a
+# record budget that never halves them
+RING_RUN_OPTS = {"windows_per_wave": 16, "guided_runs": 0, "record_lds_bytes": 96 * 1024}
+
+
+@functools.lru_cache(maxsize=None)
+def ring_case(placement):
+    N, L = RING_PLACEMENTS[placement][:2]
+    return synth(97, L, N, 2.0)
+
+
+def ring_runs(nr, na, W):
+    """make_runs (ibdg_api.cpp) without guided lengths: runs of windows_per_wave windows, the last one shorter; the run
+    length stands while a run's records fit the budget, max_seg * (sizeof(Seg) + 8) <= record_lds_bytes (build_segments).
+    Per run on the panel's own tiles (layout 1: row = position in the site list): tile pairs spanned, segments."""
+    rows = np.flatnonzero((nr.astype(int) + na) > 0)
+    n_win = cdiv(len(rows), W)
+    g = RING_RUN_OPTS["windows_per_wave"]
+    pairs, segs = [], []
+    for w0 in range(0, n_win, g):
+        r = rows[w0 * W:min(w0 + g, n_win) * W]
+        pairs.append(int(r[-1] // 64 - r[0] // 64 + 1))
+        win = (np.arange(len(r)) // W).astype(np.int64)
+        segs.append(len(np.unique(win * (1 << 32) + r // 32)))
+    assert max(segs) * (80 + 8) <= RING_RUN_OPTS["record_lds_bytes"], segs
+    return pairs
+
+
+def ring_run(form_opts, ring, alle, nr, na, W, eps, M, targets, unit, what):
+    L, N = alle.shape[0], alle.shape[1] // 2
+    with E.Engine(0, eps, M) as eng:
+        for k, v in dict(form_opts, ring_slots=ring).items():
+            eng.set_option(k, v)
+        eng.upload_panel(E.pack_alleles_fast(alle), N)
+        eng.upload_sites(np.arange(L), nr, na, W)
+        eng.run(targets, ld=True)
+        assert eng.last_ld_variant() == 2 and eng.ld_layout() == 1, what
+        assert eng.last_count_unit() == unit, (what, eng.last_count_unit())
+        return [eng.window_ll(i) for i in range(len(targets))]
+
+
+@pytest.mark.parametrize("placement", list(RING_PLACEMENTS))
+@pytest.mark.parametrize("form", list(RING_FORMS))
+def test_every_counting_form_at_every_ring_depth(oracle, form, placement):
+    """ring_slots 2, 3, 4, 8 in all four counting forms (both guard policies of the tile ring: the vector forms stop at the
+    run's last pair, the matrix-core forms request it again), with the power tables in LDS and in global memory.  Depth 2
+    goes through run_form -- the oracle and the hp_ref bound --, the other depths must give its bits.  Before anything is
+    compared: the longest run spans three laps of the deepest ring."""
+    N, L, W, in_lds = RING_PLACEMENTS[placement]
+    alle, nr, na = ring_case(placement)
+    eps, M = 0.02, 20
+    assert tab_in_lds(nr, na, W) == in_lds, placement                 # the precondition: where the tables sit
+    pairs = ring_runs(nr, na, W)
+    assert all(max(pairs) >= 3 * ring for ring in RING_DEPTHS), pairs  # ... and every depth wraps at least three times
+    name, more, T, unit_lds, unit_mem = RING_FORMS[form]
+    unit = unit_lds if in_lds else unit_mem
+    opts = dict(FORMS[name]["opts"], **more, **RING_RUN_OPTS)
+    first = {}
+    run_form(oracle, name, alle, nr, na, W, eps, M, seed=5, spec=dict(FORMS[name], T=T, unit=unit, opts=dict(opts, ring_slots=2)),
+             keep=first)
+    targets, ref = first["targets"], first["windows"]
+    for ring in RING_DEPTHS[1:]:
+        got = ring_run(opts, ring, alle, nr, na, W, eps, M, targets, unit, (form, placement, ring))
+        for i, want in ref.items():
+            assert_bits(got[i], want, f"{form}, {placement}: ring_slots {ring} vs 2, individual {i}")
+    if T > 4:           # the group alone: no single launch is left, and its individuals' tables are the same bits
+        for ring in RING_DEPTHS:
+            got = ring_run(opts, ring, alle, nr, na, W, eps, M, targets[:4], 0, (form, placement, ring, "T = 4"))
+            for i, want in ref.items():
+                if i < 4:
+                    assert_bits(got[i], want, f"{form}, {placement}: ring_slots {ring}, the group alone, individual {i}")
 
 
 @pytest.mark.parametrize("dispatch_events", [0, 1])

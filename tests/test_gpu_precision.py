@@ -56,8 +56,9 @@ def _truth_factors(oracle, form, eps, M):
     return H.table_factors(lambda r, a: oracle.pdg(eps, M, r, a), M)
 
 
-def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=0, expect=None, spec=None):
-    """One run of `form`; the parity checks and the bound on three of its comparison individuals.  Returns the truths."""
+def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=0, expect=None, spec=None, keep=None):
+    """One run of `form`; the parity checks and the bound on three of its comparison individuals.  Returns the truths;
+    `keep` (a dict) receives the comparison individuals and the window tables of the checked ones."""
     spec = spec or FORMS[form]
     L, N = alle.shape[0], alle.shape[1] // 2
     T = spec["T"]
@@ -79,6 +80,8 @@ def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=
                 assert got[k] in (v if isinstance(v, tuple) else (v,)), f"{form}: {k} {got[k]}, expected {v}"
         checked = sorted({0, T // 2, T - 1})
         out = {i: (eng.site_ll(i), eng.window_ll(i)) for i in checked}
+    if keep is not None:
+        keep.update(targets=targets, windows={i: out[i][1] for i in checked})
     fac = _truth_factors(oracle, form, eps, M)
     truths = []
     for i in checked:
