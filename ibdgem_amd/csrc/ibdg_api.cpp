@@ -1640,7 +1640,8 @@ int plan_run(ibdg_ctx *c, size_t T, size_t lanes, int ld_mode, bool row_table, R
         P.fin_in_next = c->opt.fin_next && c->opt.async && P.T_one > 0 && P.T_one == P.T_cnt && P.n_gg == 0;
         // (option "end_in_dispatch": the run's end event is the --LD kernel's own completion signal -- no event packet
         // of its own behind the kernel -- where that kernel is the run's last launch on the main stream)
-        P.end_in_dispatch = c->opt.end_in_dispatch && P.fin_in_next && !P.dispatch_events && P.T_one == T;
+        // (not with "log_windows": the run's end is then an event behind everything its main stream holds, see ibdg_ctx::WinLog)
+        P.end_in_dispatch = c->opt.end_in_dispatch && P.fin_in_next && !P.dispatch_events && P.T_one == T && !c->opt.log_windows;
         P.count_unit = P.T_one ? (P.mx_counts ? (P.ibd1 ? 3 : 2) : 1) : 0;
         // k_ld_mfma (4 waves per SIMD) leaves wave slots to the second stream: its kernels run in their fast forms
         // (also with a few individuals left to the counting kernels: T = 16 5.5 ms against 6.0; beside
@@ -1981,6 +1982,41 @@ int launch_strict(ibdg_ctx *c, const RunPlan &P, const uint32_t *targets, const 
     return 0;
 }
 
+// Option "log_windows", the --LD columns of the log table: why the exponent-counting form cannot serve this site list (the
+// conditions under which "ld_variant" 2 is refused), or null.  The strict and reference-order variants of the linear columns
+// do not stop it: k_ld_log reads the layout, not their results.
+const char *ld_log_refused(const ibdg_ctx *c)
+{
+    if (c->tab.max_cov > 50)
+        return "max_cov > 50";
+    if (!c->tab.pop_lut_ok)
+        return "a clamped P(D|G) table (or epsilon outside (0,1))";
+    if (!c->lay.pop_sites_ok || !(c->lay.compact ? c->lay.t32c.p : c->pan.t32.p))
+        return "no prepared segments for this site list (rows out of file order or too far apart)";
+    if (ibdg::ld_log_lds_bytes(c->pan.n_chunks) > 64 * 1024)
+        return "more individuals than its workgroup's LDS holds chunk sums for";
+    return nullptr;
+}
+
+// k_ld_log on the main stream, in front of the run's --LD launches (ibdg_ctx::WinLog)
+int launch_log_windows(ibdg_ctx *c, const RunPlan &P)
+{
+    if (ring_settle(c)) return 1;
+    ibdg::LdLogArgs la{};
+    const ibdg_ctx::Layout &L = c->lay;
+    la.t32 = (const uint4 *)(L.compact ? L.t32c.p : c->pan.t32.p); la.n_pairs = L.compact ? L.n_pairs_c : c->pan.n_pairs;
+    la.n_chunks = c->pan.n_chunks;
+    la.segs = (const ibdg::Seg *)L.segs.p; la.n_segs = L.n_segs;
+    la.wconst = (const ibdg::WinConst *)L.wconst.p; la.n_win = c->sites.n_win;
+    la.pow_rho = (const ibdg::PowEntry *)c->tab.pow1.p; la.pow_sigma = (const ibdg::PowEntry *)c->tab.pow2.p; la.tab_len = L.ct_max + 1;
+    la.targets = ring_slot<const uint32_t>(c->targets, c->ring.cur, Ring::SLOTS);
+    la.base_w = (const double *)c->bg.base_w.p; la.lanes = (uint32_t)P.lanes; la.base_sum = c->bg.base_sum;
+    la.win_log2 = (double *)c->wlog.win_log2.p;
+    ibdg::launch_ld_log(la, (unsigned)P.T, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
 // stream2's share of the run, queued after the critical path so that the --LD launches reach the device first: the
 // recount of the alt counts, the per-row values and the window products
 int queue_stream2(ibdg_ctx *c, const RunPlan &P, const ibdg::RowsArgs &sa, EvSet &E)
@@ -2009,6 +2045,8 @@ int queue_stream2(ibdg_ctx *c, const RunPlan &P, const ibdg::RowsArgs &sa, EvSet
         }
     }
     ibdg::launch_rows_windows(ra, (unsigned)P.T, c->stream2, P.row_blocks);
+    if (c->opt.log_windows)            // (the row-sum columns of the log table: ibdg_ctx::WinLog)
+        ibdg::launch_win_log_rows(sa, (unsigned)P.T, (double *)c->wlog.win_log2.p, c->stream2);
     HIP_TRY(c, hipEventRecord(E.s2_end, c->stream2));
     c->tl.last_s2 = E.s2_end;
     c->tl.s2_pending = true;
@@ -2038,7 +2076,8 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     // genotype picked), made once per upload; an individual's per-site table is put together when it is fetched (k_site_expand)
     const bool row_table = want_ll && ld_mode;
     if (ensure(c, c->targets, Ring::SLOTS * T * 4) || (want_ll && ensure(c, c->site_ll, (row_table ? 1 : T) * c->sites.n_sites * 24)) ||
-        (row_table && ensure(c, c->rt.row_tab, c->sites.n_sites * 32)) || ensure(c, c->win_ll, T * (size_t)c->sites.n_win * 24))
+        (row_table && ensure(c, c->rt.row_tab, c->sites.n_sites * 32)) || ensure(c, c->win_ll, T * (size_t)c->sites.n_win * 24) ||
+        (c->opt.log_windows && ensure(c, c->wlog.win_log2, T * (size_t)c->sites.n_win * 24)))
         return 1;
     // targets / background weights change rarely between calls (a loop over windows sizes, repeated
     // timing steps): their device copies are rebuilt only when the inputs differ
@@ -2053,6 +2092,9 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     if (ld_mode && relayout_when_paid(c, T)) return 1;
     RunPlan P;
     if (plan_run(c, T, lanes, ld_mode, row_table, P)) return 1;
+    const bool ld_log = c->opt.log_windows && ld_mode && c->sites.n_win > 0;
+    if (ld_log && ld_log_refused(c))
+        return fail(c, "[::] ERROR in ibdg_run: log_windows cannot give the --LD columns here: %s", ld_log_refused(c));
     c->last_variant = P.variant;
     c->last_count_unit = P.count_unit;
     // A finalising step left by the run before rides in this run's k_ld_popcount launch only where this run is of the same
@@ -2067,6 +2109,7 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     if (start_run(c, P, E, flush)) return 1;
 
     const ibdg::RowsArgs sa = rows_args(c, ld_mode, row_table);
+    if (ld_log && launch_log_windows(c, P)) return 1;
     if (P.use_pop ? launch_pop(c, P, E, same_inputs) : ld_mode && launch_strict(c, P, targets, bg_count, pu_id)) return 1;
     if (ring_settle(c)) return 1;
     if (P.rows_on_main) {
@@ -2078,6 +2121,8 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
         if (c->opt.rows_blocks > 0)
             blocks = std::max<unsigned>(1u, (unsigned)((size_t)c->n_cu * c->opt.rows_blocks / T));
         ibdg::launch_rows_windows(sa, (unsigned)T, c->stream, blocks);
+        if (c->opt.log_windows)
+            ibdg::launch_win_log_rows(sa, (unsigned)T, (double *)c->wlog.win_log2.p, c->stream);
     }
     if (!P.dispatch_events && !P.end_in_dispatch)
         HIP_TRY(c, hipEventRecord(E.ld_end, c->stream));
@@ -2090,6 +2135,7 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     if (!c->opt.async && quiesce(c)) return 1;
     c->n_targets = T; c->have_results = true;
     c->res_site_mode = row_table ? 2 : (int)c->opt.site_results;
+    c->wlog.valid = c->opt.log_windows != 0;
     return 0;
 }
 
@@ -2162,6 +2208,22 @@ int ibdg_get_window_ll_all(ibdg_ctx *c, double *out)
     if (!c) return 1;
     if (!c->have_results) return fail(c, "[::] ERROR in ibdg_get_window_ll_all: no results (call ibdg_run)");
     return fetch(c, out, c->win_ll.p, c->n_targets * (size_t)c->sites.n_win * 24);
+}
+
+int ibdg_get_window_log2(ibdg_ctx *c, size_t t, double *out)
+{
+    if (!c) return 1;
+    if (!c->have_results || t >= c->n_targets) return fail(c, "[::] ERROR in ibdg_get_window_log2: no results for target %zu", t);
+    if (!c->wlog.valid) return fail(c, "[::] ERROR in ibdg_get_window_log2: the last run kept no window logs (option log_windows)");
+    return fetch(c, out, (const char *)c->wlog.win_log2.p + t * (size_t)c->sites.n_win * 24, (size_t)c->sites.n_win * 24);
+}
+
+int ibdg_get_window_log2_all(ibdg_ctx *c, double *out)
+{
+    if (!c) return 1;
+    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_get_window_log2_all: no results (call ibdg_run)");
+    if (!c->wlog.valid) return fail(c, "[::] ERROR in ibdg_get_window_log2_all: the last run kept no window logs (option log_windows)");
+    return fetch(c, out, c->wlog.win_log2.p, c->n_targets * (size_t)c->sites.n_win * 24);
 }
 
 // Segmented sums over the window table of the last run (ibdg_llr.hip).  On the main stream behind join_streams: LIBD2 comes

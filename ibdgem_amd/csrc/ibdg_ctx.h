@@ -107,6 +107,8 @@ struct ibdg_ctx {
         long site_results = 1;       // 1: per-site LIBD0/1/2 kept for ibdg_get_site_ll; 0: not -- no T x n_sites x 24 B of HBM,
                                      // no per-site stores (window results only).  (The AF column is made on demand.)
         long staged_upload = 1;      // panels of 256 MB and more from pageable memory go through the staging team
+        long log_windows = 0;        // 1: every run also leaves log2 of its window columns on the device (WinLog below); 0: no
+                                     // allocation, no launch and no event edge of it
         long stage_workers = Staging::WORKERS;    // host threads of the staging team (two 8 MB page-locked buffers each): a caller with
                                                   // several contexts uploading at once gives each a share of the cores
     } opt;
@@ -319,6 +321,26 @@ struct ibdg_ctx {
         void drop() { key.gen = 0; }
     } img;
 
+    // Option "log_windows": log2 of LIBD0, LIBD1, LIBD2 of every window and comparison individual of the last run,
+    // [T][n_win][3] (ibdg_ld_log.hip; ibdg_get_window_log2[_all]).  A result of a run like win_ll, not a cached product: every
+    // run with the option on writes all of it, `valid` says whether the last run did.  Replaced by: the next run (whole), an
+    // ensure() that swaps the buffer (which waits on the host for every stream first).  Stream edges:
+    //   writers  k_ld_log (columns 0, 1 of an --LD run) on the main stream, in front of the run's --LD launches -- behind
+    //            ring_settle, i.e. behind stream3's preparation of the individuals it reads, and inside the run's start / end
+    //            events, so that ring_prepare's wait for a slot's last reader covers it ("end_in_dispatch" is off with the
+    //            option on: the run's end is an event behind everything);
+    //            k_win_log_rows (column 2 of an --LD run, all three otherwise) behind the run's k_rows_windows on ITS stream:
+    //            stream2 in front of the run's s2_end, or the main stream of a non-LD run that needs no recount
+    //   readers  the copies of ibdg_get_window_log2[_all] only, on the main stream behind join_streams (the main stream waits
+    //            for stream2's last event), followed by a host wait: no reader outlives its call
+    //   the two writers of an --LD run are on different streams and write different columns; a queued next run's k_ld_log may
+    //   overtake this run's k_win_log_rows as its --LD kernels overtake k_win_ibd2 on win_ll -- entries of results nobody can
+    //   fetch any more.
+    struct WinLog {
+        DevBuf win_log2;
+        bool valid = false;              // the last run was made with the option on
+    } wlog;
+
     // The finalising step of the last run of single individuals (k_ld_finalize's work) when it has been left to the NEXT
     // run's k_ld_popcount launch (option "finalize_in_next"): whoever reads results or replaces inputs first makes up for
     // it with a launch of its own (flush_finalize).  The partial sums alternate between the two halves of their buffer.
@@ -384,7 +406,7 @@ struct ibdg_ctx {
         tab.free_bufs(); pan.free_bufs(); cand.free_bufs(); sites.free_bufs(); lay.free_bufs(); bg.free_bufs();
         release_all({&rt.row_tab, &p2.p2w, &p2.p2c, &p2.p2_tw, &p2.p2_wt, &fb.fragb, &img.wtarget, &img.twords});
         release_all({&wtarget_mt, &twords_mt, &partial, &aimg, &wc_slot, &partial_h, &vals, &order});
-        release_all({&targets, &weight, &nrefpanel, &af, &site_ll, &win_ll, &llr_seg, &llr_part, &llr_out});
+        release_all({&targets, &weight, &nrefpanel, &af, &site_ll, &win_ll, &llr_seg, &llr_part, &llr_out, &wlog.win_log2});
     }
 };
 
@@ -436,6 +458,7 @@ const OptionRow OPTION_TABLE[] = {
     {"compact_density", &Opt::compact_density, OptionRow::RANGE, 1, 1000000},
     {"compact_targets", &Opt::compact_targets, OptionRow::RANGE, 1, 65536},
     {"site_results", &Opt::site_results, OptionRow::RANGE, 0, 1, "0 or 1"},
+    {"log_windows", &Opt::log_windows, OptionRow::RANGE, 0, 1, "0 or 1"},
     {"rows_blocks_per_cu", &Opt::rows_blocks, OptionRow::RANGE, 0, 128},
     {"site_blocks_per_cu", &Opt::site_blocks, OptionRow::RANGE, 0, 128},
     {"recount_blocks_per_cu", &Opt::recount_blocks, OptionRow::RANGE, 0, 128},

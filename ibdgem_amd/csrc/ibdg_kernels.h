@@ -351,4 +351,27 @@ constexpr uint64_t LLR_MAX_BLOCKS = 8192;
 void launch_llr_sums(const double *win_ll, uint32_t n_win, uint32_t n_targets, const uint32_t *seg, uint32_t n_seg,
                      uint32_t nb, double *part, double *out, hipStream_t st);
 
+// log2 of the window likelihoods (ibdg_ld_log.hip, option "log_windows"): win_log2[T][n_win][3].
+// k_ld_log: columns 0 and 1 of an --LD run from the layout's tiles, segments, window constants and power tables (what
+// the counting kernels read), the background multiplicities without any comparison individual's exclusion and their sum.
+struct LdLogArgs {
+    const uint4 *t32;           // the tiles the segments were cut from (PopArgs::t32)
+    uint32_t n_pairs, n_chunks;
+    const Seg *segs;
+    uint32_t n_segs;
+    const WinConst *wconst;     // [n_win + 1]
+    uint32_t n_win;
+    const PowEntry *pow_rho, *pow_sigma;    // rho^n, sigma^n
+    uint32_t tab_len;
+    const uint32_t *targets;    // [T]
+    const double *base_w;       // [lanes]
+    uint32_t lanes;
+    int base_sum;
+    double *win_log2;
+};
+size_t ld_log_lds_bytes(uint32_t n_chunks);
+void launch_ld_log(const LdLogArgs &a, unsigned n_targets, hipStream_t st);
+// every other column from the per-site values: all three of a non-LD run, column 2 of an --LD run (a.ld_mode)
+void launch_win_log_rows(const RowsArgs &a, unsigned n_targets, double *win_log2, hipStream_t st);
+
 }  // namespace ibdg

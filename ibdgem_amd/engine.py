@@ -47,6 +47,8 @@ SYMBOLS = {
     "ibdg_get_site_ll": (C.c_int, [_P, C.c_size_t, _P]),
     "ibdg_get_window_ll": (C.c_int, [_P, C.c_size_t, _P]),
     "ibdg_get_window_ll_all": (C.c_int, [_P, _P]),
+    "ibdg_get_window_log2": (C.c_int, [_P, C.c_size_t, _P]),
+    "ibdg_get_window_log2_all": (C.c_int, [_P, _P]),
     "ibdg_window_llr_sums": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
@@ -290,6 +292,25 @@ class Engine:
             out = np.empty((n_targets, self.n_windows, 3), dtype=np.float64)
         assert out.dtype == np.float64 and out.size >= n_targets * self.n_windows * 3 and out.flags.c_contiguous
         self._chk(self.lib.ibdg_get_window_ll_all(self.ctx, out.ctypes.data))
+        return out
+
+    def window_log2(self, t=0, out=None):
+        """log2 of LIBD0, LIBD1, LIBD2 per window of target t (option "log_windows"): [n_windows][3]."""
+        if out is None:
+            out = np.empty((self.n_windows, 3), dtype=np.float64)
+        assert out.dtype == np.float64 and out.size >= self.n_windows * 3 and out.flags.c_contiguous
+        self._chk(self.lib.ibdg_get_window_log2(self.ctx, t, out.ctypes.data))
+        return out
+
+    def window_log2_all(self, n_targets, out=None):
+        """The log tables of all `n_targets` comparison individuals of the last run in one copy: [n_targets][n_windows][3]."""
+        have = self.lib.ibdg_num_targets(self.ctx)
+        if have != n_targets:
+            raise EngineError(f"window_log2_all({n_targets}): the last run had {have} comparison individuals")
+        if out is None:
+            out = np.empty((n_targets, self.n_windows, 3), dtype=np.float64)
+        assert out.dtype == np.float64 and out.size >= n_targets * self.n_windows * 3 and out.flags.c_contiguous
+        self._chk(self.lib.ibdg_get_window_log2_all(self.ctx, out.ctypes.data))
         return out
 
     def window_llr_sums(self, first, end):

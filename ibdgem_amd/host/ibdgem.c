@@ -63,6 +63,7 @@ static int has_S = 0, has_s = 0, has_B = 0, has_A = 0, has_p = 0, has_v = 0, has
 static int opt_threads = 0;
 static const char *cache_fn = NULL, *dump_panel_fn = NULL;
 static int opt_stats_only = 0, has_arm = 0;
+static int opt_log_summary = 0;          /* --log-summary: the summary's likelihoods as log2, from the engine's option "log_windows" */
 static int opt_states = 0, has_pen = 0;  /* --states: the IBD-state path of every comparison (hgpath.c), --p01/--p02/--p12 its penalties */
 static double opt_p01 = HG_DEFAULT_P01, opt_p02 = HG_DEFAULT_P02, opt_p12 = HG_DEFAULT_P12;
 static unsigned long arm_c0, arm_c1;     /* --arm-stats: the centromeric range [c0, c1] of the run's chromosome */
@@ -74,6 +75,7 @@ static struct option longopts[] = {
     {"stats-only", no_argument, &opt_stats_only, 1},
     {"arm-stats", required_argument, 0, 1006},
     {"states", no_argument, &opt_states, 1},
+    {"log-summary", no_argument, &opt_log_summary, 1},
     {"p01", required_argument, 0, 1008},
     {"p02", required_argument, 0, 1009},
     {"p12", required_argument, 0, 1010},
@@ -157,6 +159,10 @@ static void usage(int code)
           "                            individual the windows in each state and their fractions, then the totals\n"
           "                            (the reference's bin/sum-hiddengem.py).  Computed in the individual's output\n"
           "                            job on the host, beside the device's next batch\n"
+          "  --log-summary             also write <out>/<pileup-name>.<individual>.logsummary.txt: the rows of the\n"
+          "                            summary with LOG2_LIBD0 LOG2_LIBD1 LOG2_LIBD2 in place of the likelihoods, which\n"
+          "                            leave the double range from moderate coverage on (0.000000e+00 in the summary);\n"
+          "                            --LD columns from the exact exponents of the window products, on the device\n"
           "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
           "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
           "  --stats-only              with --arm-stats and/or --states: write the armstats / ibdstates file only (no\n"
@@ -1457,9 +1463,17 @@ typedef struct {
     const uint32_t *s_row, *w_first, *w_last, *w_ncov;
     const unsigned long *pos_first, *pos_last;   /* the windows' first and last positions, or NULL (looked up row by row) */
     const double *win_ll;
+    int logs;                            /* the rows of the log summary: win_ll holds log2 values, printed %.6f, NaN as nan */
     char *buf;
     size_t len;
 } sum_job;
+
+static int fmt_log2(char *dst, double v, char sep)
+{
+    const int k = isnan(v) ? sprintf(dst, "nan") : sprintf(dst, "%.6f", v);
+    dst[k] = sep;
+    return k + 1;
+}
 
 static void *fmt_summary(void *arg)
 {
@@ -1469,9 +1483,8 @@ static void *fmt_summary(void *arg)
         q = put_u64(q, w + 1); *q++ = '\t';
         q = put_u64(q, j->pos_first ? j->pos_first[w] : rows[j->s_row[j->w_first[w]]].pos); *q++ = '\t';
         q = put_u64(q, j->pos_last ? j->pos_last[w] : rows[j->s_row[j->w_last[w]]].pos); *q++ = '\t';
-        q += fmt_ll(q, j->win_ll[3 * w], '\t');
-        q += fmt_ll(q, j->win_ll[3 * w + 1], '\t');
-        q += fmt_ll(q, j->win_ll[3 * w + 2], '\t');
+        for (int k = 0; k < 3; ++k)
+            q += j->logs ? fmt_log2(q, j->win_ll[3 * w + k], '\t') : fmt_ll(q, j->win_ll[3 * w + k], '\t');
         q = put_u64(q, j->w_ncov[w]); *q++ = '\n';
     }
     j->len = (size_t)(q - j->buf);
@@ -1644,6 +1657,7 @@ typedef struct {
     double *site_ll;
     uint32_t *w_first, *w_last, *w_ncov;     /* slice-local arrays, window indices local */
     double *win_ll;
+    double *win_log;                         /* --log-summary: log2 of the same table (ibdg_get_window_log2), else NULL */
     size_t n_win;
     int failed;
     int dev_idx;                             /* which of the run's devices (its slot of win_cache) */
@@ -1670,7 +1684,8 @@ typedef struct {
     /* a batch's window tables, taken off the device in one copy, so that the next batch can run while the host goes through
      * them (one table at a time left the device idle for the 4 ms the host needs per batch of 30, beside 6 ms of running) */
     double *batch_ll;
-    size_t batch_cap, batch_T;
+    double *batch_log;                       /* --log-summary: their logs, taken off the device with them */
+    size_t batch_cap, batch_log_cap, batch_T;
     const uint32_t *batch_of;                /* the batch (its targets) the tables belong to; NULL: none */
     double *arm_sums;                        /* --arm-stats: the sums of the last run's individuals, [T][2][4] */
     size_t arm_cap;
@@ -1738,9 +1753,16 @@ static void *shard_run(void *arg)
                 wc->batch_ll = ibdg_host_alloc(need);
                 wc->batch_cap = wc->batch_ll ? need : 0;
             }
-            if (wc->batch_ll && !j->want_sites) {
+            if (opt_log_summary && wc->batch_log_cap < need) {
+                free(wc->batch_log);
+                wc->batch_log = malloc(need);
+                wc->batch_log_cap = wc->batch_log ? need : 0;
+            }
+            if (wc->batch_ll && !j->want_sites && (!opt_log_summary || wc->batch_log)) {
                 /* (the copy is as large as the LAST RUN's results: it must be the run of this very batch) */
                 if (!same_run_size(j) || ibdg_get_window_ll_all(j->eng, wc->batch_ll))        /* waits for the run */
+                    return NULL;
+                if (opt_log_summary && ibdg_get_window_log2_all(j->eng, wc->batch_log))
                     return NULL;
                 wc->batch_of = j->targets;
                 wc->batch_T = j->n_targets;
@@ -1765,7 +1787,8 @@ static void *shard_run(void *arg)
     j->w_last = malloc((j->n_win + 1) * 4);
     j->w_ncov = malloc((j->n_win + 1) * 4);
     j->win_ll = malloc((j->n_win + 1) * 24);
-    if (!j->w_first || !j->w_last || !j->w_ncov || !j->win_ll)
+    j->win_log = opt_log_summary ? malloc((j->n_win + 1) * 24) : NULL;
+    if (!j->w_first || !j->w_last || !j->w_ncov || !j->win_ll || (opt_log_summary && !j->win_log))
         return NULL;
     if (j->same_sites && wc->valid && wc->n_win == j->n_win) {
         memcpy(j->w_first, wc->first, j->n_win * 4);
@@ -1790,6 +1813,8 @@ static void *shard_run(void *arg)
     }
     if (wc->batch_of == j->targets && j->t_local < wc->batch_T) {
         memcpy(j->win_ll, wc->batch_ll + j->t_local * j->n_win * 3, j->n_win * 24);
+        if (j->win_log)
+            memcpy(j->win_log, wc->batch_log + j->t_local * j->n_win * 3, j->n_win * 24);
         j->failed = 0;
         return NULL;                             /* (window tables only: want_sites is off on this path) */
     }
@@ -1804,6 +1829,8 @@ static void *shard_run(void *arg)
             return NULL;
         memcpy(j->win_ll, wc->stage, j->n_win * 24);
     } else if (ibdg_get_window_ll(j->eng, j->t_local, j->win_ll))
+        return NULL;
+    if (j->win_log && ibdg_get_window_log2(j->eng, j->t_local, j->win_log))
         return NULL;
     if (j->want_sites && ibdg_get_site_ll(j->eng, j->t_local, j->site_ll + 3 * j->a))
         return NULL;
@@ -1962,7 +1989,7 @@ static void *host_site_rows(void *arg)
 
 static void host_nonld(const cand_t *cand, const uint32_t *s_cand, const uint8_t *s_nr, const uint8_t *s_na, size_t n,
                        unsigned tgt, const double *pdg, int threads, double *site_ll,
-                       const uint32_t *w_first, const uint32_t *w_last, size_t n_win, double *win_ll)
+                       const uint32_t *w_first, const uint32_t *w_last, size_t n_win, double *win_ll, double *win_log)
 {
     host_site_job jobs[64];
     pthread_t th[64];
@@ -1990,6 +2017,15 @@ static void host_nonld(const cand_t *cand, const uint32_t *s_cand, const uint8_t
             s0 *= site_ll[3 * i]; s1 *= site_ll[3 * i + 1]; s2 *= site_ll[3 * i + 2];
         }
         win_ll[3 * w] = s0; win_ll[3 * w + 1] = s1; win_ll[3 * w + 2] = s2;
+        if (win_log) {                                                        /* --log-summary: long-double sums of log2l */
+            long double l[3] = {0, 0, 0};
+            for (size_t i = w_first[w]; i <= w_last[w]; ++i)
+                if (s_nr[i] + s_na[i] != 0)
+                    for (int k = 0; k < 3; ++k)
+                        l[k] += log2l((long double)site_ll[3 * i + k]);
+            for (int k = 0; k < 3; ++k)
+                win_log[3 * w + k] = (double)l[k];
+        }
     }
 }
 
@@ -2020,6 +2056,8 @@ static void *upload_run(void *arg)
     /* the per-site table needs LIBD0/1/2 of every row (its AF column the host has itself); --summary-only needs
      * nothing per row: the engine then neither keeps nor computes per-row results beyond the IBD2 pick */
     if (ibdg_set_option(j->eng, "site_results", opt_summary_only ? 0 : 1))
+        return NULL;
+    if (opt_log_summary && ibdg_set_option(j->eng, "log_windows", 1))
         return NULL;
     /* the uploads of all devices run side by side: each staging team gets its share of the host's threads (and locks
      * as much less memory: two 8 MB buffers per thread) */
@@ -2181,8 +2219,10 @@ typedef struct {
     const char *pre;                            /* columns 1-9 of every row as text (row_prefix_build), or NULL */
     const uint32_t *pre_off;
     FILE *tab, *sum;                            /* open (stdout with --plan); closed by the job */
+    FILE *lsum;                                 /* --log-summary: the individual's *.logsummary.txt, else NULL; closed by the job */
     uint32_t *w_first, *w_last, *w_ncov;        /* owned: freed when the files are closed */
     double *win_ll;
+    double *win_log;                            /* owned: log2 of win_ll's entries (--log-summary), or NULL */
     int threads;
     /* when it runs beside the main thread */
     pthread_t th;
@@ -2219,6 +2259,8 @@ static void outs_settle_one(out_job *outs, int failing)
             if (o->tab && !opt_summary_only && ftruncate(fileno(o->tab), 0) != 0)
                 fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
             if (o->sum && ftruncate(fileno(o->sum), 0) != 0)
+                fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
+            if (o->lsum && ftruncate(fileno(o->lsum), 0) != 0)
                 fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
             if (o->hg && ftruncate(fileno(o->hg), 0) != 0)
                 fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
@@ -2356,7 +2398,7 @@ static void *output_individual(void *arg)
                o->n_win, o->cull_p);
     else {
         if ((!opt_summary_only && ftruncate(fileno(tab), 0) != 0) || ftruncate(fileno(sum), 0) != 0 ||
-            (o->hg && ftruncate(fileno(o->hg), 0) != 0)) {
+            (o->hg && ftruncate(fileno(o->hg), 0) != 0) || (o->lsum && ftruncate(fileno(o->lsum), 0) != 0)) {
             fprintf(o->err, "[::] ERROR in compare_impute(): Cannot empty the output files of %s.\n", o->tname);
             return NULL;
         }
@@ -2405,6 +2447,16 @@ static void *output_individual(void *arg)
             fprintf(o->err, "[::] ERROR writing the summary rows of %s.\n", o->tname);
             return NULL;
         }
+        if (o->lsum) {
+            /* the same rows with the three likelihoods as log2: columns 1-3 and 7 through the same conversions */
+            fprintf(o->lsum, "# SEGMENT\tSTART\tEND\tLOG2_LIBD0\tLOG2_LIBD1\tLOG2_LIBD2\tNUM_SITES\n");
+            sj.win_ll = o->win_log;
+            sj.logs = 1;
+            if (write_summary_parallel(o->lsum, sj, o->n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
+                fprintf(o->err, "[::] ERROR writing the log summary rows of %s.\n", o->tname);
+                return NULL;
+            }
+        }
     }
     /* footer (:761-768) */
     fprintf(tab, "# FINAL COVERAGE DISTRIBUTION:\n# COVERAGE N_SITES\n");
@@ -2417,14 +2469,17 @@ static void *output_individual(void *arg)
     if (!opt_plan) {
         bad |= fclose(tab) != 0;
         bad |= fclose(sum) != 0;
+        if (o->lsum)
+            bad |= fclose(o->lsum) != 0;
+        o->lsum = NULL;
     }
     if (opt_states && states_individual(o)) {
         fprintf(o->err, "[::] ERROR writing the IBD-state path of %s.\n", o->tname);
         bad = 1;
     }
-    free(o->w_first); free(o->w_last); free(o->w_ncov); free(o->win_ll);
+    free(o->w_first); free(o->w_last); free(o->w_ncov); free(o->win_ll); free(o->win_log);
     o->w_first = o->w_last = o->w_ncov = NULL;
-    o->win_ll = NULL;
+    o->win_ll = o->win_log = NULL;
     o->failed = bad;
     return NULL;
 }
@@ -2908,12 +2963,15 @@ static int pj_run(pile_job *pj, worker_t *w)
         /* windows: runs of opt_window covered rows (:572, :657-663, :723-730) */
         size_t n_win = 0;
         uint32_t *w_first = NULL, *w_last = NULL, *w_ncov = NULL;
-        double *win_ll = NULL;
+        double *win_ll = NULL, *win_log = NULL;
         if (no_engine) {
             n_win = host_windows(s_nr, s_na, n, (unsigned)opt_window, &w_first, &w_last, &w_ncov);
             if (host_math) {
                 win_ll = malloc((n_win + 1) * 24);
-                host_nonld(cand, s_cand, s_nr, s_na, n, tgt, g_pdg_tab, all_threads(), site_ll, w_first, w_last, n_win, win_ll);
+                win_log = opt_log_summary ? malloc((n_win + 1) * 24) : NULL;
+                if (opt_log_summary && !win_log)
+                    PFAIL("[::] ERROR: out of memory for %zu windows.\n", n_win);
+                host_nonld(cand, s_cand, s_nr, s_na, n, tgt, g_pdg_tab, all_threads(), site_ll, w_first, w_last, n_win, win_ll, win_log);
             }
             if (arm_on) {
                 uint32_t seg[4];
@@ -3055,9 +3113,11 @@ static int pj_run(pile_job *pj, worker_t *w)
             } else if (n_eng == 1 && jobs[0].a == 0) {
                 /* one device, the whole site list: its arrays as they are (a copy of 1.2 MB per individual otherwise) */
                 w_first = jobs[0].w_first; w_last = jobs[0].w_last; w_ncov = jobs[0].w_ncov; win_ll = jobs[0].win_ll;
+                win_log = jobs[0].win_log;
             } else {
                 w_first = malloc((n_win + 1) * 4); w_last = malloc((n_win + 1) * 4); w_ncov = malloc((n_win + 1) * 4);
                 win_ll = malloc((n_win + 1) * 24);
+                win_log = opt_log_summary ? malloc((n_win + 1) * 24) : NULL;
                 size_t wo = 0;
                 for (int d = 0; d < n_eng; ++d) {
                     shard_job *j = &jobs[d];
@@ -3068,8 +3128,10 @@ static int pj_run(pile_job *pj, worker_t *w)
                     }
                     memcpy(w_ncov + wo, j->w_ncov, j->n_win * 4);
                     memcpy(win_ll + 3 * wo, j->win_ll, j->n_win * 24);
+                    if (win_log && j->win_log)
+                        memcpy(win_log + 3 * wo, j->win_log, j->n_win * 24);
                     wo += j->n_win;
-                    free(j->w_first); free(j->w_last); free(j->w_ncov); free(j->win_ll);
+                    free(j->w_first); free(j->w_last); free(j->w_ncov); free(j->win_ll); free(j->win_log);
                 }
             }
         }
@@ -3078,7 +3140,7 @@ static int pj_run(pile_job *pj, worker_t *w)
             (n_win != arm_nw || memcmp(w_first, arm_wfirst, n_win * 4) || memcmp(w_last, arm_wlast, n_win * 4)))
             PFAIL("[::] ERROR: the engine's windows are not the ones the chromosome arms were cut from.\n");
         if (tables_stay) {
-            free(w_first); free(w_last); free(w_ncov); free(win_ll);
+            free(w_first); free(w_last); free(w_ncov); free(win_ll); free(win_log);
             phase("per individual: engine (upload, run, arm sums)");
             continue;
         }
@@ -3103,9 +3165,10 @@ static int pj_run(pile_job *pj, worker_t *w)
         memcpy(o->final_dist, final_dist, sizeof o->final_dist);
         o->site_ll = site_ll;
         o->pre = row_pre; o->pre_off = row_pre_off;
-        o->w_first = w_first; o->w_last = w_last; o->w_ncov = w_ncov; o->win_ll = win_ll;
+        o->w_first = w_first; o->w_last = w_last; o->w_ncov = w_ncov; o->win_ll = win_ll; o->win_log = win_log;
         o->sq = sq; o->err = err;
         o->hg = NULL;
+        o->lsum = NULL;
         o->st_count = st_res ? st_res + 3 * ti : NULL;
         if (opt_plan) {
             o->tab = o->sum = stdout;
@@ -3131,6 +3194,17 @@ static int pj_run(pile_job *pj, worker_t *w)
                 PFAIL("[::] ERROR in compare_impute(): Cannot open '%s' and/or '%s' for writing.\n", tab_fn, sum_fn);
             free(tab_fn);
             free(sum_fn);
+            if (opt_log_summary) {
+                char *ls_fn;
+                if (asprintf(&ls_fn, "%s/%s.%s.logsummary.txt", out_dir, sq, tname) < 0)
+                    goto fail;
+                const int ls_fd = open(ls_fn, O_WRONLY | O_CREAT, 0666);
+                o->lsum = ls_fd >= 0 ? fdopen(ls_fd, "w") : NULL;
+                if (!o->lsum)
+                    PFAIL("[::] ERROR in compare_impute(): Cannot open '%s' for writing.\n", ls_fn);
+                pj_add_file(pj, ls_fn);
+                free(ls_fn);
+            }
             if (opt_states) {
                 char *hg_fn;
                 if (asprintf(&hg_fn, "%s/%s.%s.hiddengem.txt", out_dir, sq, tname) < 0)
@@ -3357,6 +3431,8 @@ int main(int argc, char **argv)
     if (opt_states && opt_plan) { fprintf(stderr, "[::] ERROR: --states writes files --plan does not make; use one of them.\n"); exit(1); }
     if (opt_stats_only && !has_arm && !opt_states) { fprintf(stderr, "[::] ERROR: --stats-only needs --arm-stats START,END.\n"); exit(1); }
     if (opt_stats_only && opt_plan) { fprintf(stderr, "[::] ERROR: --stats-only writes a file --plan does not make; use one of them.\n"); exit(1); }
+    if (opt_log_summary && opt_plan) { fprintf(stderr, "[::] ERROR: --log-summary writes files --plan does not make; use one of them.\n"); exit(1); }
+    if (opt_log_summary && opt_stats_only) { fprintf(stderr, "[::] ERROR: --log-summary writes files --stats-only leaves out; use one of them.\n"); exit(1); }
     if (opt_stats_only)
         opt_summary_only = 1;                 /* (what the engine does for it: no per-site values, batches queued ahead) */
 

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define IBDG_ABI_VERSION 5   /* (still 5, additions only: ibdg_upload_candidates, ibdg_num_candidates, ibdg_select_variable_sites, ibdg_get_site_candidates -- the -v site lists made on the device.)  5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
+#define IBDG_ABI_VERSION 5   /* (still 5, additions only: option log_windows with ibdg_get_window_log2, ibdg_get_window_log2_all -- window likelihoods as logs that do not underflow; ibdg_upload_candidates, ibdg_num_candidates, ibdg_select_variable_sites, ibdg_get_site_candidates -- the -v site lists made on the device.)  5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
                               * longer what a sparse pileup gets.  3: options site_results, stage_workers; ibdg_get_site_af
                               * computes on demand; ibdg_last_run_ms out[4] is 0 */
 
@@ -210,6 +210,17 @@ int ibdg_get_window_ll(ibdg_ctx *ctx, size_t t, double *out);
  * comparison individuals takes a batch's tables off the device at once and can queue the next batch before it goes
  * through them: the host program's --summary-only loop, reference src/ibdgem.c:522 with :751-756). */
 int ibdg_get_window_ll_all(ibdg_ctx *ctx, double *out);
+/* Option "log_windows": log2 of LIBD0, LIBD1, LIBD2 per window of target t, out[n_windows][3] -- the summary columns for
+ * windows whose likelihoods leave the double range (at 30x coverage every LIBD0 of a window of 100 rows is below 2^-1074
+ * and ibdg_get_window_ll returns 0).  --LD, LIBD0 and LIBD1: log2 of the mean over the background (bg_count's multiplicities,
+ * the target and pu_id excluded, src/ibdgem.c:714) of the exact binomial window products, each kept as a mantissa and an
+ * integer exponent to the end -- no product is ever brought into the double range; NaN for an empty background, like the
+ * linear columns.  Every other column (all three of a non-LD run, LIBD2 of an --LD run): the sum over the window's rows
+ * with reads of log2 of the fp64 per-site value ibdg_get_site_ll returns (DBL_MIN clamp included), as a double-double
+ * rounded once.  Same waits as ibdg_get_window_ll ("async").  An error if the last ibdg_run was made with the option off. */
+int ibdg_get_window_log2(ibdg_ctx *ctx, size_t t, double *out);
+/* The same for every target of the last ibdg_run in one copy: out[ibdg_num_targets][n_windows][3]. */
+int ibdg_get_window_log2_all(ibdg_ctx *ctx, double *out);
 /* For each comparison individual t of the last ibdg_run and each window range s = [first[s], end[s]) of its
  * site list: the sums over the range of log2(L2') - log2(L0') and log2(L1') - log2(L0') (L' = L, or 2^-1074 where
  * L == 0), each as a double-double: out[((t * n_seg) + s) * 4 + {0,1,2,3}] = {IBD2/IBD0 hi, lo, IBD1/IBD0 hi, lo}.
@@ -285,7 +296,12 @@ int ibdg_last_count_unit(const ibdg_ctx *ctx);
  * per row, made by the first such run on an upload; 0 nothing -- no n_targets x n_sites x 24 bytes
  * of device memory, no per-row stores, and in --LD mode only the IBD2 pick of a row is computed at all: for callers that
  * want the window table only, e.g. hundreds of comparison individuals in one call; ibdg_get_site_ll then fails.  The AF
- * column never costs a run anything: ibdg_get_site_af computes it when called); "stage_workers" (1..8, default 8: host threads of that staging team -- a caller
+ * column never costs a run anything: ibdg_get_site_af computes it when called); "log_windows" (0/1, default 0: every later
+ * ibdg_run also leaves log2 of its window columns on the device for ibdg_get_window_log2[_all], T x n_windows x 24 bytes and
+ * two small launches per run; works with "site_results" 0 and 1; an --LD run then fails, naming the reason, where the
+ * exponent-counting form cannot serve the site list -- a clamped P(D|G) table, max_cov > 50, no prepared segments: the
+ * conditions under which "ld_variant" 2 is refused -- while the strict and reference-order variants of the linear columns do
+ * not stop it; 0: no allocation, no launch, nothing else changes); "stage_workers" (1..8, default 8: host threads of that staging team -- a caller
  * whose contexts upload at the same time gives each its share); "staged_upload" (0/1, default 1: a panel of 256 MB or more in
  * ordinary host memory goes to the device through page-locked staging buffers filled by a team of host
  * threads instead of the runtime's pageable-memory path); "ld_variant" (0 = pick automatically,
