@@ -1635,6 +1635,21 @@ static size_t host_windows(const uint8_t *nr, const uint8_t *na, size_t n, unsig
     return n_win;
 }
 
+/* an individual's window table: arrays of n_win + 1 entries, owned by whoever holds the struct (a shard's job, the
+ * pileup's run, the individual's output job: handed over by assignment, the giver's copy zeroed or dropped) */
+typedef struct {
+    size_t n_win;
+    uint32_t *first, *last, *ncov;           /* first and last site of each window, its covered rows */
+    double *ll;                              /* LIBD0/1/2 per window */
+    double *log;                             /* --log-summary: log2 of the same table, else NULL */
+} win_table;
+
+static void win_table_free(win_table *t)
+{
+    free(t->first); free(t->last); free(t->ncov); free(t->ll); free(t->log);
+    memset(t, 0, sizeof *t);
+}
+
 /* ---- one comparison spread over several GPUs (window ranges, host-side gather) ------------ */
 typedef struct {
     ibdg_ctx *eng;
@@ -1655,10 +1670,7 @@ typedef struct {
     int pu_id, ld;
     /* outputs, written at the slice's offsets of the comparison-wide arrays */
     double *site_ll;
-    uint32_t *w_first, *w_last, *w_ncov;     /* slice-local arrays, window indices local */
-    double *win_ll;
-    double *win_log;                         /* --log-summary: log2 of the same table (ibdg_get_window_log2), else NULL */
-    size_t n_win;
+    win_table wt;                            /* slice-local arrays, window indices local */
     int failed;
     int dev_idx;                             /* which of the run's devices (its slot of win_cache) */
     int same_sites;                          /* the site list is the same for every comparison individual of the run */
@@ -1778,59 +1790,59 @@ static void *shard_run(void *arg)
     }
     if (j->arm_seg)
         memcpy(j->arm, wc->arm_sums + j->t_local * 8, sizeof j->arm);
-    j->n_win = ibdg_num_windows(j->eng);
+    j->wt.n_win = ibdg_num_windows(j->eng);
     if (j->stats_only) {
         j->failed = 0;
         return NULL;
     }
-    j->w_first = malloc((j->n_win + 1) * 4);
-    j->w_last = malloc((j->n_win + 1) * 4);
-    j->w_ncov = malloc((j->n_win + 1) * 4);
-    j->win_ll = malloc((j->n_win + 1) * 24);
-    j->win_log = opt_log_summary ? malloc((j->n_win + 1) * 24) : NULL;
-    if (!j->w_first || !j->w_last || !j->w_ncov || !j->win_ll || (opt_log_summary && !j->win_log))
+    j->wt.first = malloc((j->wt.n_win + 1) * 4);
+    j->wt.last = malloc((j->wt.n_win + 1) * 4);
+    j->wt.ncov = malloc((j->wt.n_win + 1) * 4);
+    j->wt.ll = malloc((j->wt.n_win + 1) * 24);
+    j->wt.log = opt_log_summary ? malloc((j->wt.n_win + 1) * 24) : NULL;
+    if (!j->wt.first || !j->wt.last || !j->wt.ncov || !j->wt.ll || (opt_log_summary && !j->wt.log))
         return NULL;
-    if (j->same_sites && wc->valid && wc->n_win == j->n_win) {
-        memcpy(j->w_first, wc->first, j->n_win * 4);
-        memcpy(j->w_last, wc->last, j->n_win * 4);
-        memcpy(j->w_ncov, wc->ncov, j->n_win * 4);
+    if (j->same_sites && wc->valid && wc->n_win == j->wt.n_win) {
+        memcpy(j->wt.first, wc->first, j->wt.n_win * 4);
+        memcpy(j->wt.last, wc->last, j->wt.n_win * 4);
+        memcpy(j->wt.ncov, wc->ncov, j->wt.n_win * 4);
     } else {
-        if (ibdg_get_windows(j->eng, j->w_first, j->w_last, j->w_ncov))
+        if (ibdg_get_windows(j->eng, j->wt.first, j->wt.last, j->wt.ncov))
             return NULL;
         if (j->same_sites) {
             free(wc->first); free(wc->last); free(wc->ncov);
-            wc->first = malloc((j->n_win + 1) * 4);
-            wc->last = malloc((j->n_win + 1) * 4);
-            wc->ncov = malloc((j->n_win + 1) * 4);
+            wc->first = malloc((j->wt.n_win + 1) * 4);
+            wc->last = malloc((j->wt.n_win + 1) * 4);
+            wc->ncov = malloc((j->wt.n_win + 1) * 4);
             if (wc->first && wc->last && wc->ncov) {
-                memcpy(wc->first, j->w_first, j->n_win * 4);
-                memcpy(wc->last, j->w_last, j->n_win * 4);
-                memcpy(wc->ncov, j->w_ncov, j->n_win * 4);
-                wc->n_win = j->n_win;
+                memcpy(wc->first, j->wt.first, j->wt.n_win * 4);
+                memcpy(wc->last, j->wt.last, j->wt.n_win * 4);
+                memcpy(wc->ncov, j->wt.ncov, j->wt.n_win * 4);
+                wc->n_win = j->wt.n_win;
                 wc->valid = 1;
             }
         }
     }
     if (wc->batch_of == j->targets && j->t_local < wc->batch_T) {
-        memcpy(j->win_ll, wc->batch_ll + j->t_local * j->n_win * 3, j->n_win * 24);
-        if (j->win_log)
-            memcpy(j->win_log, wc->batch_log + j->t_local * j->n_win * 3, j->n_win * 24);
+        memcpy(j->wt.ll, wc->batch_ll + j->t_local * j->wt.n_win * 3, j->wt.n_win * 24);
+        if (j->wt.log)
+            memcpy(j->wt.log, wc->batch_log + j->t_local * j->wt.n_win * 3, j->wt.n_win * 24);
         j->failed = 0;
         return NULL;                             /* (window tables only: want_sites is off on this path) */
     }
-    if (wc->stage_cap < (j->n_win + 1) * 24) {
+    if (wc->stage_cap < (j->wt.n_win + 1) * 24) {
         if (wc->stage)
             ibdg_host_free(wc->stage);
-        wc->stage = ibdg_host_alloc((j->n_win + 1) * 24);
-        wc->stage_cap = wc->stage ? (j->n_win + 1) * 24 : 0;
+        wc->stage = ibdg_host_alloc((j->wt.n_win + 1) * 24);
+        wc->stage_cap = wc->stage ? (j->wt.n_win + 1) * 24 : 0;
     }
     if (wc->stage) {
         if (ibdg_get_window_ll(j->eng, j->t_local, wc->stage))
             return NULL;
-        memcpy(j->win_ll, wc->stage, j->n_win * 24);
-    } else if (ibdg_get_window_ll(j->eng, j->t_local, j->win_ll))
+        memcpy(j->wt.ll, wc->stage, j->wt.n_win * 24);
+    } else if (ibdg_get_window_ll(j->eng, j->t_local, j->wt.ll))
         return NULL;
-    if (j->win_log && ibdg_get_window_log2(j->eng, j->t_local, j->win_log))
+    if (j->wt.log && ibdg_get_window_log2(j->eng, j->t_local, j->wt.log))
         return NULL;
     if (j->want_sites && ibdg_get_site_ll(j->eng, j->t_local, j->site_ll + 3 * j->a))
         return NULL;
@@ -2213,16 +2225,14 @@ typedef struct {
     /* this individual */
     const char *tname;
     uint32_t tgt;
-    size_t n, n_win;
+    size_t n;
     unsigned long processed, skipped, final_total, final_dist[128];
     const double *site_ll;                      /* per-row values (NULL with --summary-only) */
     const char *pre;                            /* columns 1-9 of every row as text (row_prefix_build), or NULL */
     const uint32_t *pre_off;
     FILE *tab, *sum;                            /* open (stdout with --plan); closed by the job */
     FILE *lsum;                                 /* --log-summary: the individual's *.logsummary.txt, else NULL; closed by the job */
-    uint32_t *w_first, *w_last, *w_ncov;        /* owned: freed when the files are closed */
-    double *win_ll;
-    double *win_log;                            /* owned: log2 of win_ll's entries (--log-summary), or NULL */
+    win_table wt;                               /* owned: freed when the files are closed */
     int threads;
     /* when it runs beside the main thread */
     pthread_t th;
@@ -2256,14 +2266,10 @@ static void outs_settle_one(out_job *outs, int failing)
         }
         if (failing && o->pending && !opt_plan) {
             o->pending = 0;
-            if (o->tab && !opt_summary_only && ftruncate(fileno(o->tab), 0) != 0)
-                fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
-            if (o->sum && ftruncate(fileno(o->sum), 0) != 0)
-                fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
-            if (o->lsum && ftruncate(fileno(o->lsum), 0) != 0)
-                fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
-            if (o->hg && ftruncate(fileno(o->hg), 0) != 0)
-                fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
+            FILE *const files[4] = {opt_summary_only ? NULL : o->tab, o->sum, o->lsum, o->hg};
+            for (int f = 0; f < 4; ++f)
+                if (files[f] && ftruncate(fileno(files[f]), 0) != 0)
+                    fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
         }
     }
 }
@@ -2363,9 +2369,9 @@ static int states_individual(out_job *o)
 {
     hg_path *h = &o->hgp;
     hg_reset(h);
-    for (size_t w = 0; w < o->n_win; ++w)
-        if (hg_add(h, summary_round_trip(o->win_ll[3 * w]), summary_round_trip(o->win_ll[3 * w + 1]),
-                   summary_round_trip(o->win_ll[3 * w + 2])))
+    for (size_t w = 0; w < o->wt.n_win; ++w)
+        if (hg_add(h, summary_round_trip(o->wt.ll[3 * w]), summary_round_trip(o->wt.ll[3 * w + 1]),
+                   summary_round_trip(o->wt.ll[3 * w + 2])))
             return 1;
     if (hg_solve(h, opt_p01, opt_p02, opt_p12))
         return 1;
@@ -2386,16 +2392,14 @@ static void *output_individual(void *arg)
         const int bad = states_individual(o);
         if (bad)
             fprintf(o->err, "[::] ERROR finding the IBD states of %s.\n", o->tname);
-        free(o->w_first); free(o->w_last); free(o->w_ncov); free(o->win_ll);
-        o->w_first = o->w_last = o->w_ncov = NULL;
-        o->win_ll = NULL;
+        win_table_free(&o->wt);
         o->failed = bad;
         return NULL;
     }
     FILE *tab = o->tab, *sum = o->sum;           /* opened by the main thread: a directory that cannot be written stops the run at once */
     if (opt_plan)
         printf("## PLAN %s %s processed=%lu skipped=%lu windows=%zu cull_p=%f\n", o->sq, o->tname, o->processed, o->skipped,
-               o->n_win, o->cull_p);
+               o->wt.n_win, o->cull_p);
     else {
         if ((!opt_summary_only && ftruncate(fileno(tab), 0) != 0) || ftruncate(fileno(sum), 0) != 0 ||
             (o->hg && ftruncate(fileno(o->hg), 0) != 0) || (o->lsum && ftruncate(fileno(o->lsum), 0) != 0)) {
@@ -2432,27 +2436,27 @@ static void *output_individual(void *arg)
         }
     }
     if (opt_plan) {
-        for (size_t w = 0; w < o->n_win; ++w)
-            printf("## WINDOW %zu\t%lu\t%lu\t%u\n", w + 1, rows[o->s_row[o->w_first[w]]].pos, rows[o->s_row[o->w_last[w]]].pos,
-                   o->w_ncov[w]);
+        for (size_t w = 0; w < o->wt.n_win; ++w)
+            printf("## WINDOW %zu\t%lu\t%lu\t%u\n", w + 1, rows[o->s_row[o->wt.first[w]]].pos, rows[o->s_row[o->wt.last[w]]].pos,
+                   o->wt.ncov[w]);
     } else {
         /* the summary rows (:751-756) through the program's own conversions, by the team of threads: with many
          * comparison individuals per run the seven stdio calls per window were the longest item of an individual
          * (25 ms of 33 at 35 000 windows) */
         sum_job sj;
         memset(&sj, 0, sizeof sj);
-        sj.s_row = o->s_row; sj.w_first = o->w_first; sj.w_last = o->w_last; sj.w_ncov = o->w_ncov; sj.win_ll = o->win_ll;
+        sj.s_row = o->s_row; sj.w_first = o->wt.first; sj.w_last = o->wt.last; sj.w_ncov = o->wt.ncov; sj.win_ll = o->wt.ll;
         sj.pos_first = o->pos_first; sj.pos_last = o->pos_last;
-        if (write_summary_parallel(sum, sj, o->n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
+        if (write_summary_parallel(sum, sj, o->wt.n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
             fprintf(o->err, "[::] ERROR writing the summary rows of %s.\n", o->tname);
             return NULL;
         }
         if (o->lsum) {
             /* the same rows with the three likelihoods as log2: columns 1-3 and 7 through the same conversions */
             fprintf(o->lsum, "# SEGMENT\tSTART\tEND\tLOG2_LIBD0\tLOG2_LIBD1\tLOG2_LIBD2\tNUM_SITES\n");
-            sj.win_ll = o->win_log;
+            sj.win_ll = o->wt.log;
             sj.logs = 1;
-            if (write_summary_parallel(o->lsum, sj, o->n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
+            if (write_summary_parallel(o->lsum, sj, o->wt.n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
                 fprintf(o->err, "[::] ERROR writing the log summary rows of %s.\n", o->tname);
                 return NULL;
             }
@@ -2477,9 +2481,7 @@ static void *output_individual(void *arg)
         fprintf(o->err, "[::] ERROR writing the IBD-state path of %s.\n", o->tname);
         bad = 1;
     }
-    free(o->w_first); free(o->w_last); free(o->w_ncov); free(o->win_ll); free(o->win_log);
-    o->w_first = o->w_last = o->w_ncov = NULL;
-    o->win_ll = o->win_log = NULL;
+    win_table_free(&o->wt);
     o->failed = bad;
     return NULL;
 }
@@ -2748,514 +2750,627 @@ typedef struct {
     int started;
 } worker_t;
 
-#define PFAIL(...)                        \
-    do {                                  \
-        fprintf(err, __VA_ARGS__);        \
-        goto fail;                        \
-    } while (0)
+/* ---- the run of one pileup over its comparison individuals (:522-773) -------------------------------------------------
+ * pj_run is the loop; what it does is a sequence of stage functions over one pile_run, each returning 0, or 1 after its own
+ * message to the pileup's stream.  The state is grouped by what replaces it:
+ *   the pileup's run -- decided (run_modes) or set up (run_begin, candidates_to_device) once, given back by run_release;
+ *   the site list at hand -- RULE: rebuilt exactly when the site list changes.  It changes for every comparison individual
+ *     with -v or -D and for the first one alone otherwise (one_list).  site_list_reset drops the whole group, the site_list
+ *     stage fills the list, and what is derived from it is made by its stage on first need and kept until the next reset;
+ *   the comparison individual -- set by the loop, its window table handed to its output job. */
+typedef struct {
+    uint32_t *s_row, *s_cand;       /* the list: arrays of the pileup's candidate count (run_begin), n entries filled per list */
+    uint8_t *s_nr, *s_na;
+    double *s_fo;
+    size_t n, n_gt_failed;
+    unsigned long skipped, final_total, final_dist[128];
+    int cuts_made;                  /* derived, engine path: the list cut into one window range per device (window_cuts) */
+    size_t cuts[65];
+    uint32_t *s_row_dev;            /* derived, slice_mode: the site list's rows counted from each device's first row */
+    /* derived, --arm-stats on the engine path: the windows the arms were cut from (checked against the engine's), the windows
+     * per device and the arms in each device's own window indices */
+    uint32_t *arm_wfirst, *arm_wlast, arm_wcut[65], arm_local[64][4];
+    size_t arm_nw;
+    int arm_ok[2];
+    /* derived: the positions a summary row names (:751-756) are the same for every individual over a common site list: looked
+     * up once -- row by row they are two dependent loads into 160 MB of row records per window and individual */
+    unsigned long *sum_pos_first, *sum_pos_last;
+    size_t sum_pos_n;
+    int sum_pos_made;
+    char *row_pre;                  /* derived: columns 1-9 of every row as text, shared by all individuals' tables */
+    uint32_t *row_pre_off;
+} site_list;
 
-/* ---- per comparison individual (:522-773) of one pileup ------------------------------------------ */
-static int pj_run(pile_job *pj, worker_t *w)
+typedef struct {
+    /* ---- the pileup's run ---- */
+    pile_job *pj;
+    worker_t *w;
+    FILE *err;
+    int one_list;                   /* no -v, no -D: the site list does not depend on the comparison individual (:584, :627-628) */
+    int overlap, dev_v, batchable, arm_on, tables_stay, out_slots, out_threads_env;
+    size_t n_site_out;              /* entries of an individual's per-site array */
+    double *arm_res;                /* --arm-stats, per individual: p20, q20, p10, q10; the run's armstats.txt */
+    size_t *st_res;                 /* --states: per individual the windows in IBD0, IBD1, IBD2; the run's ibdstates.txt */
+    FILE *st_file;
+    char *st_fn;
+    double *site_slot[OUT_SLOTS];   /* the per-site array of each output slot */
+    uint32_t *c_row;                /* dev_v: the candidates as the engine takes them */
+    uint8_t *c_nr, *c_na;
+    double *c_fo;
+    size_t c_gt_failed;             /* ... and how many of the rows before the -v test have genotypes that did not parse */
+    /* ---- the site list at hand ---- */
+    site_list sl;
+    /* ---- the comparison individual ---- */
+    size_t ti;
+    uint32_t tgt;
+    const char *tname;
+    int same_sites;                 /* it runs over the site list of the one before it */
+    win_table wt;                   /* owned here until its output job takes it */
+    double *site_ll;                /* its slot's per-site array */
+} pile_run;
+
+/* a stage's failing exit: its message to the pileup's stream, 1 to pj_run */
+#define SFAIL(...) do { fprintf(r->err, __VA_ARGS__); return 1; } while (0)
+
+static void run_modes(pile_run *r)
 {
-    grand_seed(1);                  /* a fresh process's read-thinning stream (-D) */
-    if (g_list_mode)
-        timing_tag = pj->name;
-    FILE *err = pj->err;
-    const char *sq = pj->name;
-    const pileup_t *pu = pj->pu;
-    const cand_t *cand = pj->cand;
-    const uint8_t *row_fate = pj->row_fate;
-    const size_t n_cand = pj->n_cand;
-    const double cull_p = pj->cull_p;
-    const long pu_id = pj->pu_id;
-    const idlist_t targets = g_targets;
-    const int no_engine = g_no_engine, host_math = g_host_math;
-    ibdg_ctx *const *engs = w->engs;
-    const int n_eng = w->n_eng;
-    upload_job *const ups = w->ups;
-    const int slice_mode = w->slice_mode;
-    out_job *const outs = w->outs;
-    const int batchable = !no_engine && !has_v && cull_p == 1.0;
-    const char *out_dir = g_out_dir;
-    size_t *st_res = NULL;          /* --states: per individual the windows in IBD0, IBD1, IBD2; the run's ibdstates.txt */
-    FILE *st_file = NULL;
-    char *st_fn = NULL;
-    /* Round 2 page-locked the arrays that cross the engine's boundary (ibdg_host_alloc).  Measured since: locking 128 MB costs 0.1 s, giving it
-     * back at exit 0.2 s, and the copies it was meant to speed up (24 MB in, 96 MB out per comparison) run at the same
-     * 56 GB/s from ordinary memory (bench.py results_to_host) -- so they are ordinary memory now (malloc / free). */
-    uint32_t *s_row = malloc((n_cand ? n_cand : 1) * 4), *s_cand = malloc((n_cand ? n_cand : 1) * 4);
-    uint8_t *s_nr = malloc(n_cand ? n_cand : 1), *s_na = malloc(n_cand ? n_cand : 1);
-    double *s_fo = has_A ? malloc((n_cand ? n_cand : 1) * 8) : NULL;
+    const int no_engine = g_no_engine;
+    r->one_list = !has_v && r->pj->cull_p == 1.0;
+    r->batchable = !no_engine && r->one_list;
     /* the per-site values are only fetched for the per-site table: no 128 MB of page-locked memory for --summary-only */
-    const size_t n_site_out = opt_summary_only && !no_engine ? 1 : (n_cand ? n_cand : 1);
-    double *site_ll = malloc(n_site_out * 24);
-    if (!s_row || !s_cand || !s_nr || !s_na || !site_ll)
-        PFAIL("[::] ERROR: out of memory for %zu rows.\n", n_cand);
-    phase("result arrays");
-    uint32_t *s_row_dev = NULL;     /* slice_mode: the site list's rows counted from each device's first row */
+    r->n_site_out = opt_summary_only && !no_engine ? 1 : (r->pj->n_cand ? r->pj->n_cand : 1);
     /* The files of up to out_slots individuals are written beside the main thread's work on the ones after them, each from
      * a per-row array of its own -- when the site list is the same for all of them (it is read by the writers), the rows go
      * to files (stdout keeps its order) and there is a table to write at all. */
     /* (--summary-only: the summary files alone, 2.5 MB each at 35 000 windows -- 1.5 ms per individual when written one
      * after the other, most of a whole-panel job whose engine time is 0.2 ms per individual) */
-    const int overlap = !has_v && cull_p == 1.0 && !opt_plan && targets.n > 1;
+    r->overlap = r->one_list && !opt_plan && g_targets.n > 1;
     /* -v with one context and no -D: the rows that passed every filter but :584 are the pileup's; they go to the device once
      * (ibdg_upload_candidates) and every individual's list is cut from them there (ibdg_select_variable_sites) -- the host
      * walks the selected rows only: 3.5 ms per individual at 4M rows x 2504 where the scan of all rows took 58
      * (profiles/r09_variable_sites.txt).  (IBDGEM_VARSITES=host: the host's own scan, for the tests and for measurements.) */
     const char *vs_env = has_v ? getenv("IBDGEM_VARSITES") : NULL;
-    const int dev_v = has_v && !no_engine && n_eng == 1 && g_n_ups == 1 && cull_p == 1.0 && !(vs_env && !strcmp(vs_env, "host"));
-    uint32_t *c_row = NULL;                     /* dev_v: the candidates as the engine takes them */
-    uint8_t *c_nr = NULL, *c_na = NULL;
-    double *c_fo = NULL;
-    double *site_slot[OUT_SLOTS] = {site_ll};
+    r->dev_v = has_v && !no_engine && r->w->n_eng == 1 && g_n_ups == 1 && r->pj->cull_p == 1.0 && !(vs_env && !strcmp(vs_env, "host"));
     /* (--summary-only: 2.5 MB per individual instead of 330: twelve individuals at a time with four formatter threads each --
      * 0.52 ms per individual in a run of 960 against 0.65 with six and eight, 0.90 with four, tools/many_summaries.py) */
-    int out_slots = opt_summary_only ? 12 : 4;
-    char *row_pre = NULL;                       /* columns 1-9 of every row as text, shared by all individuals' tables */
-    uint32_t *row_pre_off = NULL;                  /* (IBDGEM_OUT_SLOTS=1..12, default 4, 12 with --summary-only: for the tests and for measurements) */
+    r->out_slots = opt_summary_only ? 12 : 4;
+    /* (IBDGEM_OUT_SLOTS=1..12, default 4, 12 with --summary-only: for the tests and for measurements) */
     if (getenv("IBDGEM_OUT_SLOTS") && atoi(getenv("IBDGEM_OUT_SLOTS")) >= 1 && atoi(getenv("IBDGEM_OUT_SLOTS")) <= OUT_SLOTS)
-        out_slots = atoi(getenv("IBDGEM_OUT_SLOTS"));
-    const int out_threads_env = getenv("IBDGEM_OUT_THREADS") ? atoi(getenv("IBDGEM_OUT_THREADS")) : 0;   /* (measurement switch) */
-    const int arm_on = has_arm && !opt_plan;
+        r->out_slots = atoi(getenv("IBDGEM_OUT_SLOTS"));
+    r->out_threads_env = getenv("IBDGEM_OUT_THREADS") ? atoi(getenv("IBDGEM_OUT_THREADS")) : 0;   /* (measurement switch) */
+    r->arm_on = has_arm && !opt_plan;
     /* --stats-only keeps the window tables on the device unless the states are asked for: the path is found on the host */
-    const int tables_stay = opt_stats_only && !opt_states;
+    r->tables_stay = opt_stats_only && !opt_states;
+}
+
+/* the run's arrays and its --states file */
+static int run_begin(pile_run *r)
+{
+    site_list *sl = &r->sl;
+    const size_t room = r->pj->n_cand ? r->pj->n_cand : 1;
+    /* Round 2 page-locked the arrays that cross the engine's boundary (ibdg_host_alloc).  Measured since: locking 128 MB costs 0.1 s, giving it
+     * back at exit 0.2 s, and the copies it was meant to speed up (24 MB in, 96 MB out per comparison) run at the same
+     * 56 GB/s from ordinary memory (bench.py results_to_host) -- so they are ordinary memory now (malloc / free). */
+    sl->s_row = malloc(room * 4); sl->s_cand = malloc(room * 4);
+    sl->s_nr = malloc(room); sl->s_na = malloc(room);
+    sl->s_fo = has_A ? malloc(room * 8) : NULL;
+    r->site_ll = r->site_slot[0] = malloc(r->n_site_out * 24);
+    if (!sl->s_row || !sl->s_cand || !sl->s_nr || !sl->s_na || !r->site_ll)
+        SFAIL("[::] ERROR: out of memory for %zu rows.\n", r->pj->n_cand);
+    phase("result arrays");
     if (opt_states) {
-        st_res = calloc(targets.n + 1, 3 * sizeof(size_t));
+        r->st_res = calloc(g_targets.n + 1, 3 * sizeof(size_t));
         /* opened before the run, like the individuals' files: a directory that cannot be written stops the run at once */
-        if (!st_res)
-            PFAIL("[::] ERROR: out of memory.\n");
-        if (asprintf(&st_fn, "%s/%s.ibdstates.txt", out_dir, sq) < 0)
-            goto fail;
-        if (!(st_file = fopen(st_fn, "w")))
-            PFAIL("[::] ERROR: Cannot open '%s' for writing.\n", st_fn);
-        pj_add_file(pj, st_fn);
+        if (!r->st_res)
+            SFAIL("[::] ERROR: out of memory.\n");
+        if (asprintf(&r->st_fn, "%s/%s.ibdstates.txt", g_out_dir, r->pj->name) < 0)
+            return r->st_fn = NULL, 1;
+        if (!(r->st_file = fopen(r->st_fn, "w")))
+            SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->st_fn);
+        pj_add_file(r->pj, r->st_fn);
     }
-    double *arm_res = arm_on ? malloc((targets.n + 1) * 4 * sizeof(double)) : NULL;   /* per individual: p20, q20, p10, q10 */
-    if (arm_on && !arm_res)
-        PFAIL("[::] ERROR: out of memory.\n");
-    uint32_t *arm_wfirst = NULL, *arm_wlast = NULL;   /* engine path: the windows the arms were cut from (checked against the engine's) */
-    size_t arm_nw = 0;
-    /* kept from one comparison individual to the next while the site list is the same for them */
-    unsigned long skipped = 0, final_total = 0, final_dist[128] = {0};
-    size_t n = 0, n_gt_failed = 0;
-    size_t cuts[65] = {0};
-    uint32_t arm_local[64][4], arm_wcut[65];
-    int arm_ok[2] = {0, 0};
-    /* the positions a summary row names (:751-756) are the same for every individual over a common site list: looked up
-     * once -- row by row they are two dependent loads into 160 MB of row records per window and individual */
-    unsigned long *sum_pos_first = NULL, *sum_pos_last = NULL;
-    size_t sum_pos_n = 0;
-    for (size_t ti = 0; ti < targets.n; ++ti) {
-        const uint32_t tgt = targets.idx[ti];
-        if (overlap) {
-            out_job *prev = &outs[ti % (size_t)out_slots]; /* the slot's previous individual: its files must be closed */
-            if (prev->running) {
-                pthread_join(prev->th, NULL);
-                prev->running = 0;
-                if (prev->failed)
-                    goto fail;
-                phase("per individual: waiting for the output files of an earlier individual");
-            }
-            if (!site_slot[ti % (size_t)out_slots]) {
-                site_slot[ti % (size_t)out_slots] = malloc(n_site_out * 24);
-                if (!site_slot[ti % (size_t)out_slots])
-                    PFAIL("[::] ERROR: out of memory for %zu rows.\n", n_cand);
-            }
-            site_ll = site_slot[ti % (size_t)out_slots];
-        }
-        const char *tname = g_ids.names[tgt];
-        fprintf(err, "Running %s-vs-%s comparison...\n", sq, tname);
-        /* Without -v and -D the site list does not depend on the comparison individual (:584, :627-628): it is
-         * built for the first one and kept -- 9 ms per individual at 4M rows, more than its engine time.  The
-         * reference's message for rows whose genotypes did not parse is repeated per individual as it prints it. */
-        const int same_sites = !has_v && cull_p == 1.0 && ti > 0;
-        if (dev_v && ti == 0) {
-            /* the candidate arrays, once per pileup: cand[] holds the rows of fate 1 in row order */
-            c_row = malloc((n_cand ? n_cand : 1) * 4);
-            c_nr = malloc(n_cand ? n_cand : 1);
-            c_na = malloc(n_cand ? n_cand : 1);
-            c_fo = has_A ? malloc((n_cand ? n_cand : 1) * 8) : NULL;
-            if (!c_row || !c_nr || !c_na || (has_A && !c_fo))
-                PFAIL("[::] ERROR: out of memory for %zu rows.\n", n_cand);
-            for (size_t i = 0; i < n_cand; ++i) {
-                c_row[i] = cand[i].row; c_nr[i] = cand[i].n_ref; c_na[i] = cand[i].n_alt;
-                if (c_fo) c_fo[i] = cand[i].f_is_override ? cand[i].f : NAN;
-            }
-            n_gt_failed = 0;
-            for (size_t r = 0; r < n_rows; ++r)
-                n_gt_failed += row_fate[r] == 0 && rows[r].gt_failed;
-            if (w->ups_pending) {                /* (the candidates name rows of the panel: it must be there) */
-                const int bad = uploads_join(ups, w->n_ups);
-                w->ups_pending = 0;
-                if (bad >= 0)
-                    PFAIL("%s\n", ibdg_last_error(ups[bad].eng));
-                phase("panel upload (copy, alt counts, transposition; the part not hidden behind the filter chain)");
-            }
-            if (ibdg_upload_candidates(engs[0], c_row, c_nr, c_na, c_fo, n_cand))
-                PFAIL("%s\n", ibdg_last_error(engs[0]));
-            phase("candidate rows of the pileup to the device");
-        }
-        if (same_sites || dev_v) {
-            for (size_t r = 0; r < n_rows && n_gt_failed; ++r)
-                if (row_fate[r] == 0 && rows[r].gt_failed)
-                    fprintf(err, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[r].pos);
-        } else {
-            n_gt_failed = 0;
-        }
-        if (!same_sites) {
-            skipped = final_total = 0;
-            memset(final_dist, 0, sizeof final_dist);
-            n = 0;
-        }
-        if (dev_v) {
-            /* every row is either skipped or on the list (:584-626): the rows not selected are the skipped ones */
-            if (ibdg_select_variable_sites(engs[0], tgt, (unsigned)opt_window))
-                PFAIL("%s\n", ibdg_last_error(engs[0]));
-            n = ibdg_num_sites(engs[0]);
-            if (n > n_cand || ibdg_get_site_candidates(engs[0], s_cand))
-                PFAIL("%s\n", n > n_cand ? "[::] ERROR: more sites selected than candidates." : ibdg_last_error(engs[0]));
-            for (size_t i = 0; i < n; ++i) {
-                const size_t my = s_cand[i];
-                s_row[i] = c_row[my]; s_nr[i] = c_nr[my]; s_na[i] = c_na[my];
-                if (s_fo) s_fo[i] = c_fo[my];
-                final_total += (unsigned long)c_nr[my] + c_na[my];
-                final_dist[c_nr[my] + c_na[my]]++;
-            }
-            skipped = n_rows - n;
-        }
-        for (size_t r = 0, ci = 0; r < n_rows && !same_sites && !dev_v; ++r) {
-            if (row_fate[r] == 0) {
-                if (rows[r].gt_failed) {
-                    fprintf(err, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[r].pos);
-                    n_gt_failed++;
-                }
-                skipped++;
-                continue;
-            }
-            const int is_cand = row_fate[r] == 1;
-            const size_t my = ci;
-            if (is_cand) ci++;
-            if (has_v && row_allele(r, tgt, 0) == 0 && row_allele(r, tgt, 1) == 0) { skipped++; continue; }   /* :584 */
-            if (!is_cand) { skipped++; continue; }
-            const cand_t *c = &cand[my];
-            const unsigned nr = cull(c->n_ref, cull_p), na = cull(c->n_alt, cull_p);                          /* :627-628 */
-            final_total += nr + na;
-            final_dist[nr + na]++;
-            s_row[n] = c->row; s_cand[n] = (uint32_t)my; s_nr[n] = (uint8_t)nr; s_na[n] = (uint8_t)na;
-            if (s_fo) s_fo[n] = c->f_is_override ? c->f : NAN;
-            n++;
-        }
-        const unsigned long processed = n;
-        phase(dev_v ? "per individual: site list on the device" : "per individual: site list");
-        if (ti == 0 && overlap && !opt_summary_only && targets.n >= 3 && n > 0) {
-            /* nine of a row's fourteen columns are the same for every comparison individual: their text is made once */
-            fmt_job pp;
-            memset(&pp, 0, sizeof pp);
-            pp.cand = cand; pp.s_cand = s_cand; pp.pu = pu; pp.s_nr = s_nr; pp.s_na = s_na;
-            if (row_prefix_build(pp, n, all_threads(), &row_pre, &row_pre_off)) {
-                row_pre = NULL;
-                row_pre_off = NULL;
-            }
-            phase("columns 1-9 of every row as text, once for all individuals");
-        }
+    r->arm_res = r->arm_on ? malloc((g_targets.n + 1) * 4 * sizeof(double)) : NULL;
+    if (r->arm_on && !r->arm_res)
+        SFAIL("[::] ERROR: out of memory.\n");
+    return 0;
+}
 
-        /* windows: runs of opt_window covered rows (:572, :657-663, :723-730) */
-        size_t n_win = 0;
-        uint32_t *w_first = NULL, *w_last = NULL, *w_ncov = NULL;
-        double *win_ll = NULL, *win_log = NULL;
-        if (no_engine) {
-            n_win = host_windows(s_nr, s_na, n, (unsigned)opt_window, &w_first, &w_last, &w_ncov);
-            if (host_math) {
-                win_ll = malloc((n_win + 1) * 24);
-                win_log = opt_log_summary ? malloc((n_win + 1) * 24) : NULL;
-                if (opt_log_summary && !win_log)
-                    PFAIL("[::] ERROR: out of memory for %zu windows.\n", n_win);
-                host_nonld(cand, s_cand, s_nr, s_na, n, tgt, g_pdg_tab, all_threads(), site_ll, w_first, w_last, n_win, win_ll, win_log);
-            }
-            if (arm_on) {
-                uint32_t seg[4];
-                int ok[2];
-                double p[4], q[4];
-                arm_segments(s_row, w_first, w_last, n_win, seg, ok);
-                llr_range_host(win_ll, seg[0], seg[1], p);
-                llr_range_host(win_ll, seg[2], seg[3], q);
-                arm_res[4 * ti] = ok[0] ? p[0] : NAN;
-                arm_res[4 * ti + 1] = ok[1] ? q[0] : NAN;
-                arm_res[4 * ti + 2] = ok[0] ? p[2] : NAN;
-                arm_res[4 * ti + 3] = ok[1] ? q[2] : NAN;
-            }
-        } else {
-            /* one contiguous window range per GPU, evaluated concurrently, gathered in order */
-            shard_job jobs[64];
-            pthread_t th[64];
-            /* --arm-stats: the arms of the site list in its global windows, cut into each device's window range */
-            if (!same_sites)
-                window_cuts(s_nr, s_na, n, (unsigned)opt_window, n_eng, cuts);
-            if (arm_on && !same_sites) {
-                uint32_t *an, seg[4];
-                free(arm_wfirst); free(arm_wlast);
-                const size_t nw = arm_nw = host_windows(s_nr, s_na, n, (unsigned)opt_window, &arm_wfirst, &arm_wlast, &an);
-                arm_segments(s_row, arm_wfirst, arm_wlast, nw, seg, arm_ok);
-                free(an);
-                for (int d = 0; d <= n_eng; ++d)
-                    arm_wcut[d] = (uint32_t)(nw * (size_t)d / (size_t)n_eng);     /* window_cuts' windows per device */
-                for (int d = 0; d < n_eng; ++d)
-                    for (int k = 0; k < 4; ++k) {
-                        const uint32_t v = seg[k] < arm_wcut[d] ? arm_wcut[d] : seg[k] > arm_wcut[d + 1] ? arm_wcut[d + 1] : seg[k];
-                        arm_local[d][k] = v - arm_wcut[d];
-                    }
-            }
-            if (slice_mode && ti == 0) {
-                /* every device gets the panel rows from its first site's row to its last site's row, and its
-                 * sites are numbered within that slice */
-                s_row_dev = malloc((n ? n : 1) * 4);
-                if (!s_row_dev)
-                    PFAIL("[::] ERROR: out of memory for %zu rows.\n", n);
-                for (int d = 0; d < n_eng; ++d) {
-                    const size_t a = cuts[d], b = cuts[d + 1];
-                    ups[d].r0 = a < b ? s_row[a] : 0;
-                    ups[d].n = a < b ? (size_t)s_row[b - 1] + 1 - ups[d].r0 : 0;
-                    for (size_t i = a; i < b; ++i)
-                        s_row_dev[i] = s_row[i] - (uint32_t)ups[d].r0;
-                    if (timing_on > 0)
-                        fprintf(stderr, "## panel slice of device %d: rows %zu + %zu of %zu\n", d, ups[d].r0, ups[d].n, n_rows);
-                }
-                g_n_ups = n_eng;                     /* (a single -P run: this is the main thread; quit() joins them) */
-                uploads_start(ups, n_eng);
-                g_uploads_pending = 1;
-                w->ups_pending = 1;
-            }
-            if (w->ups_pending) {
-                const int bad = uploads_join(ups, w->n_ups);
-                w->ups_pending = 0;
-                if (bad >= 0)
-                    PFAIL("%s\n", ibdg_last_error(ups[bad].eng));
-                phase("panel upload (copy, alt counts, transposition; the part not hidden behind the filter chain)");
-            }
-            if (g_list_mode && ti == 0) {
-                /* what upload_run decides for a single run's contexts (share_sites), per pileup: whether this pileup's
-                 * individuals share one site list depends on its own cull ratio, so each pileup gets the layout choice
-                 * its single run makes ("auto" otherwise) */
-                const int compact = batchable && opt_ld && !opt_ref_order && targets.n >= 240;
-                for (int d = 0; d < n_eng; ++d)
-                    if (ibdg_set_option(engs[d], "compact_tiles", compact))
-                        PFAIL("%s\n", ibdg_last_error(engs[d]));
-            }
-            int th_started[64] = {0};
-            for (int d = 0; d < n_eng; ++d) {
-                shard_job *j = &jobs[d];
-                memset(j, 0, sizeof *j);
-                j->eng = engs[d]; j->row = slice_mode ? s_row_dev : s_row; j->nr = s_nr; j->na = s_na; j->fo = s_fo;
-                j->a = cuts[d]; j->b = cuts[d + 1]; j->window = (unsigned)opt_window;
-                j->want_sites = !opt_summary_only;
-                if (batchable) {
-                    const size_t b0 = ti - ti % TARGET_BATCH;
-                    j->targets = targets.idx + b0;
-                    j->n_targets = targets.n - b0 < TARGET_BATCH ? targets.n - b0 : TARGET_BATCH;
-                    j->t_local = ti - b0;
-                    j->do_upload = ti == 0;
-                    j->do_run = ti == b0;
-                    if (b0 + TARGET_BATCH < targets.n && opt_summary_only) {
-                        j->next_targets = targets.idx + b0 + TARGET_BATCH;
-                        j->n_next = targets.n - (b0 + TARGET_BATCH) < TARGET_BATCH ? targets.n - (b0 + TARGET_BATCH) : TARGET_BATCH;
-                    }
-                } else {
-                    j->targets = &targets.idx[ti];
-                    j->n_targets = 1;
-                    j->t_local = 0;
-                    j->do_upload = !dev_v;       /* (dev_v: the engine holds the individual's list already) */
-                    j->do_run = 1;
-                }
-                j->bg_count = g_bg_count; j->pu_id = (int)pu_id; j->ld = opt_ld;
-                j->dev_idx = w->dev_base + d; j->same_sites = batchable;
-                j->site_ll = site_ll;
-                j->arm_seg = arm_on ? arm_local[d] : NULL;
-                j->stats_only = tables_stay;
-                j->err = err;
-                /* (no thread to be had: the shard runs here -- never exit() while other shard threads are
-                 * inside the GPU runtime) */
-                th_started[d] = n_eng > 1 && pthread_create(&th[d], NULL, shard_run, j) == 0;
-                if (!th_started[d])
-                    shard_run(j);
-            }
-            n_win = 0;
-            int shard_failed = -1;
-            for (int d = 0; d < n_eng; ++d) {
-                if (th_started[d])
-                    pthread_join(th[d], NULL);
-                if (jobs[d].failed && shard_failed < 0)
-                    shard_failed = d;
-                n_win += jobs[d].n_win;
-            }
-            if (shard_failed >= 0) {
-                if (jobs[shard_failed].reported)
-                    goto fail;
-                PFAIL("%s\n", ibdg_last_error(jobs[shard_failed].eng));
-            }
-            if (arm_on) {
-                /* each device's parts of the two arms, added in device order, then rounded */
-                double acc[8] = {0};
-                for (int d = 0; d < n_eng; ++d) {
-                    if (jobs[d].n_win != arm_wcut[d + 1] - arm_wcut[d])
-                        PFAIL("[::] ERROR: device %d holds %zu windows, not the %u of its range.\n", d, jobs[d].n_win,
-                              arm_wcut[d + 1] - arm_wcut[d]);
-                    for (int k = 0; k < 4; ++k)
-                        dd_add(acc + 2 * k, jobs[d].arm[2 * k], jobs[d].arm[2 * k + 1]);
-                }
-                arm_res[4 * ti] = arm_ok[0] ? acc[0] + acc[1] : NAN;
-                arm_res[4 * ti + 1] = arm_ok[1] ? acc[4] + acc[5] : NAN;
-                arm_res[4 * ti + 2] = arm_ok[0] ? acc[2] + acc[3] : NAN;
-                arm_res[4 * ti + 3] = arm_ok[1] ? acc[6] + acc[7] : NAN;
-            }
-            if (tables_stay) {
-                /* no window table left the device */
-            } else if (n_eng == 1 && jobs[0].a == 0) {
-                /* one device, the whole site list: its arrays as they are (a copy of 1.2 MB per individual otherwise) */
-                w_first = jobs[0].w_first; w_last = jobs[0].w_last; w_ncov = jobs[0].w_ncov; win_ll = jobs[0].win_ll;
-                win_log = jobs[0].win_log;
-            } else {
-                w_first = malloc((n_win + 1) * 4); w_last = malloc((n_win + 1) * 4); w_ncov = malloc((n_win + 1) * 4);
-                win_ll = malloc((n_win + 1) * 24);
-                win_log = opt_log_summary ? malloc((n_win + 1) * 24) : NULL;
-                size_t wo = 0;
-                for (int d = 0; d < n_eng; ++d) {
-                    shard_job *j = &jobs[d];
-                    const uint32_t a0 = (uint32_t)j->a;
-                    for (size_t wi = 0; wi < j->n_win; ++wi) {
-                        w_first[wo + wi] = j->w_first[wi] + a0;
-                        w_last[wo + wi] = j->w_last[wi] + a0;
-                    }
-                    memcpy(w_ncov + wo, j->w_ncov, j->n_win * 4);
-                    memcpy(win_ll + 3 * wo, j->win_ll, j->n_win * 24);
-                    if (win_log && j->win_log)
-                        memcpy(win_log + 3 * wo, j->win_log, j->n_win * 24);
-                    wo += j->n_win;
-                    free(j->w_first); free(j->w_last); free(j->w_ncov); free(j->win_ll); free(j->win_log);
-                }
-            }
-        }
+/* overlap: the individual's output slot.  INVARIANT: a slot's previous output job is joined -- its files closed, its arrays
+ * read for the last time -- before the slot's arrays are reused. */
+static int output_slot_wait(pile_run *r)
+{
+    const size_t k = r->ti % (size_t)r->out_slots;
+    out_job *prev = &r->w->outs[k];
+    if (prev->running) {
+        pthread_join(prev->th, NULL);
+        prev->running = 0;
+        if (prev->failed)
+            return 1;
+        phase("per individual: waiting for the output files of an earlier individual");
+    }
+    if (!r->site_slot[k] && !(r->site_slot[k] = malloc(r->n_site_out * 24)))
+        SFAIL("[::] ERROR: out of memory for %zu rows.\n", r->pj->n_cand);
+    r->site_ll = r->site_slot[k];
+    return 0;
+}
 
-        if (arm_on && !no_engine && !tables_stay &&
-            (n_win != arm_nw || memcmp(w_first, arm_wfirst, n_win * 4) || memcmp(w_last, arm_wlast, n_win * 4)))
-            PFAIL("[::] ERROR: the engine's windows are not the ones the chromosome arms were cut from.\n");
-        if (tables_stay) {
-            free(w_first); free(w_last); free(w_ncov); free(win_ll); free(win_log);
-            phase("per individual: engine (upload, run, arm sums)");
+/* the worker's panel uploads, joined where the panel is first needed on the device */
+static int join_uploads(pile_run *r)
+{
+    worker_t *w = r->w;
+    if (!w->ups_pending)
+        return 0;
+    const int bad = uploads_join(w->ups, w->n_ups);
+    w->ups_pending = 0;
+    if (bad >= 0)
+        SFAIL("%s\n", ibdg_last_error(w->ups[bad].eng));
+    phase("panel upload (copy, alt counts, transposition; the part not hidden behind the filter chain)");
+    return 0;
+}
+
+/* dev_v: the candidate arrays, once per pileup: cand[] holds the rows of fate 1 in row order */
+static int candidates_to_device(pile_run *r)
+{
+    const cand_t *cand = r->pj->cand;
+    const size_t n_cand = r->pj->n_cand, room = n_cand ? n_cand : 1;
+    r->c_row = malloc(room * 4);
+    r->c_nr = malloc(room);
+    r->c_na = malloc(room);
+    r->c_fo = has_A ? malloc(room * 8) : NULL;
+    if (!r->c_row || !r->c_nr || !r->c_na || (has_A && !r->c_fo))
+        SFAIL("[::] ERROR: out of memory for %zu rows.\n", n_cand);
+    for (size_t i = 0; i < n_cand; ++i) {
+        r->c_row[i] = cand[i].row; r->c_nr[i] = cand[i].n_ref; r->c_na[i] = cand[i].n_alt;
+        if (r->c_fo) r->c_fo[i] = cand[i].f_is_override ? cand[i].f : NAN;
+    }
+    for (size_t row = 0; row < n_rows; ++row)
+        r->c_gt_failed += r->pj->row_fate[row] == 0 && rows[row].gt_failed;
+    if (join_uploads(r))                     /* (the candidates name rows of the panel: it must be there) */
+        return 1;
+    if (ibdg_upload_candidates(r->w->engs[0], r->c_row, r->c_nr, r->c_na, r->c_fo, n_cand))
+        SFAIL("%s\n", ibdg_last_error(r->w->engs[0]));
+    phase("candidate rows of the pileup to the device");
+    return 0;
+}
+
+/* ---- the site list: kept, cut on the device, or scanned on the host ---- */
+static void site_list_reset(site_list *sl)
+{
+    const site_list empty = {.s_row = sl->s_row, .s_cand = sl->s_cand, .s_nr = sl->s_nr, .s_na = sl->s_na, .s_fo = sl->s_fo};
+    /* (no output job reads these now: jobs run beside the loop only over a list that is never reset, see overlap) */
+    free(sl->s_row_dev); free(sl->arm_wfirst); free(sl->arm_wlast);
+    free(sl->sum_pos_first); free(sl->sum_pos_last); free(sl->row_pre); free(sl->row_pre_off);
+    *sl = empty;
+}
+
+/* the reference's message for rows whose genotypes did not parse, repeated per individual as it prints it */
+static void gt_failed_replay(const pile_run *r)
+{
+    for (size_t row = 0; row < n_rows && r->sl.n_gt_failed; ++row)
+        if (r->pj->row_fate[row] == 0 && rows[row].gt_failed)
+            fprintf(r->err, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[row].pos);
+}
+
+/* every row is either skipped or on the list (:584-626): the rows not selected are the skipped ones */
+static int site_list_from_device(pile_run *r)
+{
+    site_list *sl = &r->sl;
+    ibdg_ctx *eng = r->w->engs[0];
+    sl->n_gt_failed = r->c_gt_failed;
+    gt_failed_replay(r);
+    if (ibdg_select_variable_sites(eng, r->tgt, (unsigned)opt_window))
+        SFAIL("%s\n", ibdg_last_error(eng));
+    const size_t n = sl->n = ibdg_num_sites(eng);
+    if (n > r->pj->n_cand || ibdg_get_site_candidates(eng, sl->s_cand))
+        SFAIL("%s\n", n > r->pj->n_cand ? "[::] ERROR: more sites selected than candidates." : ibdg_last_error(eng));
+    for (size_t i = 0; i < n; ++i) {
+        const size_t my = sl->s_cand[i];
+        sl->s_row[i] = r->c_row[my]; sl->s_nr[i] = r->c_nr[my]; sl->s_na[i] = r->c_na[my];
+        if (sl->s_fo) sl->s_fo[i] = r->c_fo[my];
+        sl->final_total += (unsigned long)r->c_nr[my] + r->c_na[my];
+        sl->final_dist[r->c_nr[my] + r->c_na[my]]++;
+    }
+    sl->skipped = n_rows - n;
+    return 0;
+}
+
+/* the reference's own walk over every row (:584-628) */
+static void site_list_host_scan(pile_run *r)
+{
+    site_list *sl = &r->sl;
+    const cand_t *cand = r->pj->cand;
+    const uint8_t *row_fate = r->pj->row_fate;
+    const double cull_p = r->pj->cull_p;
+    uint32_t *const s_row = sl->s_row, *const s_cand = sl->s_cand;    /* (locals: the byte stores below may alias *sl) */
+    uint8_t *const s_nr = sl->s_nr, *const s_na = sl->s_na;
+    double *const s_fo = sl->s_fo;
+    unsigned long skipped = 0, final_total = 0;
+    size_t n = 0;
+    for (size_t row = 0, ci = 0; row < n_rows; ++row) {
+        if (row_fate[row] == 0) {
+            if (rows[row].gt_failed) {
+                fprintf(r->err, "Failed to parse genotype fields at %lu. Skipping to next site.\n", rows[row].pos);
+                sl->n_gt_failed++;
+            }
+            skipped++;
             continue;
         }
-        if (overlap && !no_engine && (ti == 0 || sum_pos_n != n_win)) {
-            free(sum_pos_first); free(sum_pos_last);
-            sum_pos_first = malloc((n_win + 1) * sizeof *sum_pos_first);
-            sum_pos_last = malloc((n_win + 1) * sizeof *sum_pos_last);
-            sum_pos_n = n_win;
-            for (size_t wi = 0; wi < n_win && sum_pos_first && sum_pos_last; ++wi) {
-                sum_pos_first[wi] = rows[s_row[w_first[wi]]].pos;
-                sum_pos_last[wi] = rows[s_row[w_last[wi]]].pos;
-            }
+        const int is_cand = row_fate[row] == 1;
+        const size_t my = ci;
+        if (is_cand) ci++;
+        if (has_v && row_allele(row, r->tgt, 0) == 0 && row_allele(row, r->tgt, 1) == 0) { skipped++; continue; }   /* :584 */
+        if (!is_cand) { skipped++; continue; }
+        const cand_t *c = &cand[my];
+        const unsigned nr = cull(c->n_ref, cull_p), na = cull(c->n_alt, cull_p);                              /* :627-628 */
+        final_total += nr + na;
+        sl->final_dist[nr + na]++;
+        s_row[n] = c->row; s_cand[n] = (uint32_t)my; s_nr[n] = (uint8_t)nr; s_na[n] = (uint8_t)na;
+        if (s_fo) s_fo[n] = c->f_is_override ? c->f : NAN;
+        n++;
+    }
+    sl->n = n; sl->skipped = skipped; sl->final_total = final_total;
+}
+
+/* Without -v and -D the site list does not depend on the comparison individual (:584, :627-628): it is built for the first
+ * one and kept -- 9 ms per individual at 4M rows, more than its engine time. */
+static int site_list_stage(pile_run *r)
+{
+    if (r->same_sites)
+        gt_failed_replay(r);
+    else {
+        site_list_reset(&r->sl);
+        if (!r->dev_v)
+            site_list_host_scan(r);
+        else if (site_list_from_device(r))
+            return 1;
+    }
+    phase(r->dev_v ? "per individual: site list on the device" : "per individual: site list");
+    return 0;
+}
+
+/* nine of a row's fourteen columns are the same for every comparison individual: their text is made once */
+static void row_prefix_once(pile_run *r)
+{
+    site_list *sl = &r->sl;
+    fmt_job pp;
+    if (r->ti != 0 || !r->overlap || opt_summary_only || g_targets.n < 3 || sl->n == 0)
+        return;
+    memset(&pp, 0, sizeof pp);
+    pp.cand = r->pj->cand; pp.s_cand = sl->s_cand; pp.pu = r->pj->pu; pp.s_nr = sl->s_nr; pp.s_na = sl->s_na;
+    if (row_prefix_build(pp, sl->n, all_threads(), &sl->row_pre, &sl->row_pre_off)) {
+        sl->row_pre = NULL;
+        sl->row_pre_off = NULL;
+    }
+    phase("columns 1-9 of every row as text, once for all individuals");
+}
+
+/* ---- windows: runs of opt_window covered rows (:572, :657-663, :723-730) ---- */
+/* no device: the windows, their likelihoods (non-LD) and the arm sums on the host */
+static int windows_on_host(pile_run *r)
+{
+    const site_list *sl = &r->sl;
+    win_table *t = &r->wt;
+    t->n_win = host_windows(sl->s_nr, sl->s_na, sl->n, (unsigned)opt_window, &t->first, &t->last, &t->ncov);
+    if (g_host_math) {
+        t->ll = malloc((t->n_win + 1) * 24);
+        t->log = opt_log_summary ? malloc((t->n_win + 1) * 24) : NULL;
+        if (opt_log_summary && !t->log)
+            SFAIL("[::] ERROR: out of memory for %zu windows.\n", t->n_win);
+        host_nonld(r->pj->cand, sl->s_cand, sl->s_nr, sl->s_na, sl->n, r->tgt, g_pdg_tab, all_threads(), r->site_ll, t->first,
+                   t->last, t->n_win, t->ll, t->log);
+    }
+    if (r->arm_on) {
+        uint32_t seg[4];
+        int ok[2];
+        double p[4], q[4], *res = r->arm_res + 4 * r->ti;
+        arm_segments(sl->s_row, t->first, t->last, t->n_win, seg, ok);
+        llr_range_host(t->ll, seg[0], seg[1], p);
+        llr_range_host(t->ll, seg[2], seg[3], q);
+        res[0] = ok[0] ? p[0] : NAN; res[1] = ok[1] ? q[0] : NAN;
+        res[2] = ok[0] ? p[2] : NAN; res[3] = ok[1] ? q[2] : NAN;
+    }
+    return 0;
+}
+
+/* the site list cut into one window range per device, and (--arm-stats) its arms in their global windows cut likewise */
+static void site_cuts(pile_run *r)
+{
+    site_list *sl = &r->sl;
+    const int n_eng = r->w->n_eng;
+    uint32_t *an, seg[4];
+    sl->cuts_made = 1;
+    window_cuts(sl->s_nr, sl->s_na, sl->n, (unsigned)opt_window, n_eng, sl->cuts);
+    if (!r->arm_on)
+        return;
+    const size_t nw = sl->arm_nw = host_windows(sl->s_nr, sl->s_na, sl->n, (unsigned)opt_window, &sl->arm_wfirst, &sl->arm_wlast, &an);
+    arm_segments(sl->s_row, sl->arm_wfirst, sl->arm_wlast, nw, seg, sl->arm_ok);
+    free(an);
+    for (int d = 0; d <= n_eng; ++d)
+        sl->arm_wcut[d] = (uint32_t)(nw * (size_t)d / (size_t)n_eng);     /* window_cuts' windows per device */
+    for (int d = 0; d < n_eng; ++d)
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t lo = sl->arm_wcut[d], hi = sl->arm_wcut[d + 1];
+            sl->arm_local[d][k] = (seg[k] < lo ? lo : seg[k] > hi ? hi : seg[k]) - lo;
         }
-        phase("per individual: engine (upload, run, results)");
-        out_job *o = &outs[overlap ? ti % (size_t)out_slots : 0];
-        o->pos_first = overlap && !no_engine && sum_pos_first && sum_pos_last ? sum_pos_first : NULL;
-        o->pos_last = o->pos_first ? sum_pos_last : NULL;
-        o->out_dir = out_dir; o->user_cmd = g_user_cmd; o->in_dist = pj->in_dist; o->mean_cov = pj->mean_cov; o->cull_p = cull_p;
-        o->cand = cand; o->s_cand = s_cand; o->s_row = s_row; o->s_nr = s_nr; o->s_na = s_na; o->pu = pu;
-        o->tname = tname; o->tgt = tgt; o->n = n; o->n_win = n_win;
-        o->processed = processed; o->skipped = skipped; o->final_total = final_total;
-        memcpy(o->final_dist, final_dist, sizeof o->final_dist);
-        o->site_ll = site_ll;
-        o->pre = row_pre; o->pre_off = row_pre_off;
-        o->w_first = w_first; o->w_last = w_last; o->w_ncov = w_ncov; o->win_ll = win_ll; o->win_log = win_log;
-        o->sq = sq; o->err = err;
-        o->hg = NULL;
-        o->lsum = NULL;
-        o->st_count = st_res ? st_res + 3 * ti : NULL;
-        if (opt_plan) {
-            o->tab = o->sum = stdout;
-        } else if (opt_stats_only) {
-            o->tab = o->sum = NULL;               /* (--stats-only --states: the table is here for its path alone) */
+}
+
+/* slice_mode: every device gets the panel rows from its first site's row to its last site's row, and its sites are
+ * numbered within that slice */
+static int panel_slices(pile_run *r)
+{
+    site_list *sl = &r->sl;
+    worker_t *w = r->w;
+    if (!(sl->s_row_dev = malloc((sl->n ? sl->n : 1) * 4)))
+        SFAIL("[::] ERROR: out of memory for %zu rows.\n", sl->n);
+    for (int d = 0; d < w->n_eng; ++d) {
+        upload_job *u = &w->ups[d];
+        const size_t a = sl->cuts[d], b = sl->cuts[d + 1];
+        u->r0 = a < b ? sl->s_row[a] : 0;
+        u->n = a < b ? (size_t)sl->s_row[b - 1] + 1 - u->r0 : 0;
+        for (size_t i = a; i < b; ++i)
+            sl->s_row_dev[i] = sl->s_row[i] - (uint32_t)u->r0;
+        if (timing_on > 0)
+            fprintf(stderr, "## panel slice of device %d: rows %zu + %zu of %zu\n", d, u->r0, u->n, n_rows);
+    }
+    g_n_ups = w->n_eng;                      /* (a single -P run: this is the main thread; quit() joins them) */
+    uploads_start(w->ups, w->n_eng);
+    g_uploads_pending = 1;
+    w->ups_pending = 1;
+    return 0;
+}
+
+/* one contiguous window range per GPU */
+static void shards_fill(const pile_run *r, shard_job *jobs)
+{
+    const site_list *sl = &r->sl;
+    const worker_t *w = r->w;
+    const idlist_t targets = g_targets;
+    const size_t ti = r->ti;
+    for (int d = 0; d < w->n_eng; ++d) {
+        shard_job *j = &jobs[d];
+        memset(j, 0, sizeof *j);
+        j->eng = w->engs[d]; j->row = w->slice_mode ? sl->s_row_dev : sl->s_row; j->nr = sl->s_nr; j->na = sl->s_na; j->fo = sl->s_fo;
+        j->a = sl->cuts[d]; j->b = sl->cuts[d + 1]; j->window = (unsigned)opt_window;
+        j->want_sites = !opt_summary_only;
+        if (r->batchable) {
+            const size_t b0 = ti - ti % TARGET_BATCH;
+            j->targets = targets.idx + b0;
+            j->n_targets = targets.n - b0 < TARGET_BATCH ? targets.n - b0 : TARGET_BATCH;
+            j->t_local = ti - b0;
+            j->do_upload = ti == 0;
+            j->do_run = ti == b0;
+            if (b0 + TARGET_BATCH < targets.n && opt_summary_only) {
+                j->next_targets = targets.idx + b0 + TARGET_BATCH;
+                j->n_next = targets.n - (b0 + TARGET_BATCH) < TARGET_BATCH ? targets.n - (b0 + TARGET_BATCH) : TARGET_BATCH;
+            }
         } else {
-            char *tab_fn, *sum_fn;
-            if (asprintf(&tab_fn, "%s/%s.%s.tab.txt", out_dir, sq, tname) < 0 ||
-                asprintf(&sum_fn, "%s/%s.%s.summary.txt", out_dir, sq, tname) < 0)
-                goto fail;
-            /* opened here, emptied by whoever writes them: giving back the pages of an earlier run's 330 MB table takes
-             * tens of milliseconds, which belong to the individual's output job, not between two engine calls */
-            const int tab_fd = open(opt_summary_only ? "/dev/null" : tab_fn, O_WRONLY | O_CREAT, 0666);
-            const int sum_fd = open(sum_fn, O_WRONLY | O_CREAT, 0666);
-            o->tab = tab_fd >= 0 ? fdopen(tab_fd, "w") : NULL;
-            o->sum = sum_fd >= 0 ? fdopen(sum_fd, "w") : NULL;
-            o->pending = 1;
-            if (!opt_summary_only && tab_fd >= 0)
-                pj_add_file(pj, tab_fn);
-            if (sum_fd >= 0)
-                pj_add_file(pj, sum_fn);
-            if (!o->tab || !o->sum)
-                PFAIL("[::] ERROR in compare_impute(): Cannot open '%s' and/or '%s' for writing.\n", tab_fn, sum_fn);
-            free(tab_fn);
-            free(sum_fn);
-            if (opt_log_summary) {
-                char *ls_fn;
-                if (asprintf(&ls_fn, "%s/%s.%s.logsummary.txt", out_dir, sq, tname) < 0)
-                    goto fail;
-                const int ls_fd = open(ls_fn, O_WRONLY | O_CREAT, 0666);
-                o->lsum = ls_fd >= 0 ? fdopen(ls_fd, "w") : NULL;
-                if (!o->lsum)
-                    PFAIL("[::] ERROR in compare_impute(): Cannot open '%s' for writing.\n", ls_fn);
-                pj_add_file(pj, ls_fn);
-                free(ls_fn);
-            }
-            if (opt_states) {
-                char *hg_fn;
-                if (asprintf(&hg_fn, "%s/%s.%s.hiddengem.txt", out_dir, sq, tname) < 0)
-                    goto fail;
-                const int hg_fd = open(hg_fn, O_WRONLY | O_CREAT, 0666);
-                o->hg = hg_fd >= 0 ? fdopen(hg_fd, "w") : NULL;
-                if (!o->hg)
-                    PFAIL("[::] ERROR in compare_impute(): Cannot open '%s' for writing.\n", hg_fn);
-                pj_add_file(pj, hg_fn);
-                free(hg_fn);
-            }
+            j->targets = &targets.idx[ti];
+            j->n_targets = 1;
+            j->t_local = 0;
+            j->do_upload = !r->dev_v;        /* (dev_v: the engine holds the individual's list already) */
+            j->do_run = 1;
         }
-        const int threads = all_threads();
-        /* (tools/many_tables.py: files of 1 / 2 / 3 / 4 / 6 individuals at once with 8 threads each 73* / 66 / 57 / 47 / 54 ms per
-         * individual, *16 threads; 4 x 4 threads 58, 3 x 16 threads 57) */
-        o->threads = overlap && out_slots > 1 && threads > 3 ? (opt_summary_only ? (threads + 3) / 4 : threads / 2) : threads;
-        if (overlap && out_threads_env > 0)
-            o->threads = out_threads_env;
-        o->running = overlap && pthread_create(&o->th, NULL, output_individual, o) == 0;
-        if (!o->running) {
-            output_individual(o);
-            if (o->failed)
-                goto fail;
-        }
-        phase("per individual: output files");
+        j->bg_count = g_bg_count; j->pu_id = (int)r->pj->pu_id; j->ld = opt_ld;
+        j->dev_idx = w->dev_base + d; j->same_sites = r->batchable;
+        j->site_ll = r->site_ll;
+        j->arm_seg = r->arm_on ? sl->arm_local[d] : NULL;
+        j->stats_only = r->tables_stay;
+        j->err = r->err;
     }
-    for (int k = 0; k < OUT_SLOTS; ++k) {
-        if (outs[k].running) {
-            pthread_join(outs[k].th, NULL);
-            outs[k].running = 0;
-            if (outs[k].failed)
-                goto fail;
-        }
+}
+
+/* ... evaluated concurrently.  INVARIANT: every shard thread of the individual is joined before any shard's failure is acted
+ * on -- never exit() while other shard threads are inside the GPU runtime. */
+static int shards_run(pile_run *r, shard_job *jobs)
+{
+    const int n_eng = r->w->n_eng;
+    pthread_t th[64];
+    int th_started[64] = {0}, shard_failed = -1;
+    for (int d = 0; d < n_eng; ++d) {
+        th_started[d] = n_eng > 1 && pthread_create(&th[d], NULL, shard_run, &jobs[d]) == 0;
+        if (!th_started[d])                  /* (no thread to be had: the shard runs here) */
+            shard_run(&jobs[d]);
     }
-    if (overlap)
-        phase("output files of the last individuals (written beside the engine's work on the ones after them)");
-    if (arm_on) {
+    for (int d = 0; d < n_eng; ++d) {
+        if (th_started[d])
+            pthread_join(th[d], NULL);
+        if (jobs[d].failed && shard_failed < 0)
+            shard_failed = d;
+        r->wt.n_win += jobs[d].wt.n_win;
+    }
+    if (shard_failed >= 0 && !jobs[shard_failed].reported)
+        fprintf(r->err, "%s\n", ibdg_last_error(jobs[shard_failed].eng));
+    return shard_failed >= 0;
+}
+
+/* --arm-stats: each device's parts of the two arms, added in device order, then rounded */
+static int arm_gather(pile_run *r, const shard_job *jobs)
+{
+    const site_list *sl = &r->sl;
+    double acc[8] = {0}, *res = r->arm_res + 4 * r->ti;
+    for (int d = 0; d < r->w->n_eng; ++d) {
+        if (jobs[d].wt.n_win != sl->arm_wcut[d + 1] - sl->arm_wcut[d])
+            SFAIL("[::] ERROR: device %d holds %zu windows, not the %u of its range.\n", d, jobs[d].wt.n_win,
+                  sl->arm_wcut[d + 1] - sl->arm_wcut[d]);
+        for (int k = 0; k < 4; ++k)
+            dd_add(acc + 2 * k, jobs[d].arm[2 * k], jobs[d].arm[2 * k + 1]);
+    }
+    res[0] = sl->arm_ok[0] ? acc[0] + acc[1] : NAN; res[1] = sl->arm_ok[1] ? acc[4] + acc[5] : NAN;
+    res[2] = sl->arm_ok[0] ? acc[2] + acc[3] : NAN; res[3] = sl->arm_ok[1] ? acc[6] + acc[7] : NAN;
+    return 0;
+}
+
+/* the devices' window tables, gathered in order into the individual's */
+static void tables_gather(pile_run *r, shard_job *jobs)
+{
+    win_table *t = &r->wt;
+    if (r->w->n_eng == 1 && jobs[0].a == 0) {
+        *t = jobs[0].wt;   /* one device, the whole site list: its arrays as they are (a copy of 1.2 MB per individual otherwise) */
+        return;
+    }
+    t->first = malloc((t->n_win + 1) * 4); t->last = malloc((t->n_win + 1) * 4); t->ncov = malloc((t->n_win + 1) * 4);
+    t->ll = malloc((t->n_win + 1) * 24);
+    t->log = opt_log_summary ? malloc((t->n_win + 1) * 24) : NULL;
+    size_t wo = 0;
+    for (int d = 0; d < r->w->n_eng; ++d) {
+        win_table *s = &jobs[d].wt;
+        const uint32_t a0 = (uint32_t)jobs[d].a;
+        for (size_t wi = 0; wi < s->n_win; ++wi) {
+            t->first[wo + wi] = s->first[wi] + a0;
+            t->last[wo + wi] = s->last[wi] + a0;
+        }
+        memcpy(t->ncov + wo, s->ncov, s->n_win * 4);
+        memcpy(t->ll + 3 * wo, s->ll, s->n_win * 24);
+        if (t->log && s->log)
+            memcpy(t->log + 3 * wo, s->log, s->n_win * 24);
+        wo += s->n_win;
+        win_table_free(s);
+    }
+}
+
+static int windows_on_engine(pile_run *r)
+{
+    site_list *sl = &r->sl;
+    win_table *t = &r->wt;
+    shard_job jobs[64];
+    if (!sl->cuts_made)
+        site_cuts(r);
+    if (r->w->slice_mode && r->ti == 0 && panel_slices(r))
+        return 1;
+    if (join_uploads(r))
+        return 1;
+    /* --pileup-list: what upload_run decides for a single run's contexts (share_sites), per pileup: whether this pileup's
+     * individuals share one site list depends on its own cull ratio, so each pileup gets the layout choice its single run
+     * makes ("auto" otherwise) */
+    for (int d = 0; d < r->w->n_eng && g_list_mode && r->ti == 0; ++d)
+        if (ibdg_set_option(r->w->engs[d], "compact_tiles", r->batchable && opt_ld && !opt_ref_order && g_targets.n >= 240))
+            SFAIL("%s\n", ibdg_last_error(r->w->engs[d]));
+    shards_fill(r, jobs);
+    if (shards_run(r, jobs) || (r->arm_on && arm_gather(r, jobs)))
+        return 1;
+    if (r->tables_stay)                      /* no window table left the device */
+        return 0;
+    tables_gather(r, jobs);
+    if (r->arm_on && (t->n_win != sl->arm_nw || memcmp(t->first, sl->arm_wfirst, t->n_win * 4) || memcmp(t->last, sl->arm_wlast, t->n_win * 4)))
+        SFAIL("[::] ERROR: the engine's windows are not the ones the chromosome arms were cut from.\n");
+    return 0;
+}
+
+static void summary_positions(pile_run *r)
+{
+    site_list *sl = &r->sl;
+    const win_table *t = &r->wt;
+    if (!r->overlap || g_no_engine || (sl->sum_pos_made && sl->sum_pos_n == t->n_win))
+        return;
+    free(sl->sum_pos_first); free(sl->sum_pos_last);
+    sl->sum_pos_first = malloc((t->n_win + 1) * sizeof *sl->sum_pos_first);
+    sl->sum_pos_last = malloc((t->n_win + 1) * sizeof *sl->sum_pos_last);
+    sl->sum_pos_n = t->n_win;
+    sl->sum_pos_made = 1;
+    for (size_t wi = 0; wi < t->n_win && sl->sum_pos_first && sl->sum_pos_last; ++wi) {
+        sl->sum_pos_first[wi] = rows[sl->s_row[t->first[wi]]].pos;
+        sl->sum_pos_last[wi] = rows[sl->s_row[t->last[wi]]].pos;
+    }
+}
+
+/* ---- the individual's output job ---- */
+/* One output file of the individual, OUT/NAME.TARGET.KIND.txt: opened here, emptied by whoever writes it -- giving back the
+ * pages of an earlier run's 330 MB table takes tens of milliseconds, which belong to the individual's output job, not between
+ * two engine calls -- and listed among the pileup's files.  to_null: /dev/null in its place.  With fn_out the name goes to
+ * the caller, who reports a failure; otherwise it is reported here.  NULL: not opened. */
+static FILE *out_file_open(pile_run *r, const char *kind, int to_null, char **fn_out)
+{
+    char *fn = NULL;
+    FILE *f = NULL;
+    if (asprintf(&fn, "%s/%s.%s.%s.txt", g_out_dir, r->pj->name, r->tname, kind) >= 0) {
+        const int fd = open(to_null ? "/dev/null" : fn, O_WRONLY | O_CREAT, 0666);
+        f = fd >= 0 ? fdopen(fd, "w") : NULL;
+        if (f && !to_null)
+            pj_add_file(r->pj, fn);
+        if (!f && !fn_out)
+            fprintf(r->err, "[::] ERROR in compare_impute(): Cannot open '%s' for writing.\n", fn);
+    } else
+        fn = NULL;
+    if (fn_out)
+        *fn_out = fn;
+    else
+        free(fn);
+    return f;
+}
+
+static int outputs_open(pile_run *r, out_job *o)
+{
+    char *tab_fn, *sum_fn;
+    o->hg = o->lsum = NULL;
+    if (opt_plan || opt_stats_only) {         /* (--stats-only --states: the table is here for its path alone) */
+        o->tab = o->sum = opt_plan ? stdout : NULL;
+        return 0;
+    }
+    o->tab = out_file_open(r, "tab", opt_summary_only, &tab_fn);
+    o->sum = out_file_open(r, "summary", 0, &sum_fn);
+    o->pending = 1;
+    if ((!o->tab || !o->sum) && tab_fn && sum_fn)
+        fprintf(r->err, "[::] ERROR in compare_impute(): Cannot open '%s' and/or '%s' for writing.\n", tab_fn, sum_fn);
+    free(tab_fn);
+    free(sum_fn);
+    return !o->tab || !o->sum || (opt_log_summary && !(o->lsum = out_file_open(r, "logsummary", 0, NULL))) ||
+           (opt_states && !(o->hg = out_file_open(r, "hiddengem", 0, NULL)));
+}
+
+/* everything the individual's files are made of goes to its slot's job, the window table with it; the job runs beside the
+ * loop (overlap) or here */
+static int output_start(pile_run *r)
+{
+    const site_list *sl = &r->sl;
+    const pile_job *pj = r->pj;
+    out_job *o = &r->w->outs[r->overlap ? r->ti % (size_t)r->out_slots : 0];
+    o->pos_first = r->overlap && !g_no_engine && sl->sum_pos_first && sl->sum_pos_last ? sl->sum_pos_first : NULL;
+    o->pos_last = o->pos_first ? sl->sum_pos_last : NULL;
+    o->out_dir = g_out_dir; o->user_cmd = g_user_cmd; o->in_dist = pj->in_dist; o->mean_cov = pj->mean_cov; o->cull_p = pj->cull_p;
+    o->cand = pj->cand; o->s_cand = sl->s_cand; o->s_row = sl->s_row; o->s_nr = sl->s_nr; o->s_na = sl->s_na; o->pu = pj->pu;
+    o->tname = r->tname; o->tgt = r->tgt; o->n = sl->n;
+    o->processed = sl->n; o->skipped = sl->skipped; o->final_total = sl->final_total;
+    memcpy(o->final_dist, sl->final_dist, sizeof o->final_dist);
+    o->site_ll = r->site_ll;
+    o->pre = sl->row_pre; o->pre_off = sl->row_pre_off;
+    o->wt = r->wt;
+    memset(&r->wt, 0, sizeof r->wt);
+    o->sq = pj->name; o->err = r->err;
+    o->st_count = r->st_res ? r->st_res + 3 * r->ti : NULL;
+    if (outputs_open(r, o))
+        return 1;
+    const int threads = all_threads();
+    /* (tools/many_tables.py: files of 1 / 2 / 3 / 4 / 6 individuals at once with 8 threads each 73* / 66 / 57 / 47 / 54 ms per
+     * individual, *16 threads; 4 x 4 threads 58, 3 x 16 threads 57) */
+    o->threads = r->overlap && r->out_slots > 1 && threads > 3 ? (opt_summary_only ? (threads + 3) / 4 : threads / 2) : threads;
+    if (r->overlap && r->out_threads_env > 0)
+        o->threads = r->out_threads_env;
+    o->running = r->overlap && pthread_create(&o->th, NULL, output_individual, o) == 0;
+    if (!o->running)
+        output_individual(o);
+    return !o->running && o->failed;
+}
+
+/* the files the run writes once, after its last individual */
+static int run_end(pile_run *r)
+{
+    const idlist_t targets = g_targets;
+    if (r->arm_on) {
         /* one file for the run, written here once: the lines in comparison order, as bin/chrarm-stats.py prints them */
         char *arm_fn;
+        const pileup_t *pu = r->pj->pu;
         const char *chrom = g_uchr ? g_uchr : pu->n_lines ? pu->chr_names[pu->lines[0].chr] : ".";
-        if (asprintf(&arm_fn, "%s/%s.armstats.txt", out_dir, sq) < 0)
-            goto fail;
+        if (asprintf(&arm_fn, "%s/%s.armstats.txt", g_out_dir, r->pj->name) < 0)
+            return 1;
         FILE *af = fopen(arm_fn, "w");
         if (!af)
-            PFAIL("[::] ERROR: Cannot open '%s' for writing.\n", arm_fn);
-        pj_add_file(pj, arm_fn);
+            SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", arm_fn);
+        pj_add_file(r->pj, arm_fn);
         fprintf(af, "SAMPLE\tCHROM\tparm_IBD2/IBD0\tqarm_IBD2/IBD0\tparm_IBD1/IBD0\tqarm_IBD1/IBD0\n");
         for (size_t ti = 0; ti < targets.n; ++ti) {
             fprintf(af, "%s\t%s", g_ids.names[targets.idx[ti]], chrom);
             for (int k = 0; k < 4; ++k) {
-                const double v = arm_res[4 * ti + k];
+                const double v = r->arm_res[4 * ti + k];
                 if (isnan(v))
                     fprintf(af, "\tnan");
                 else
@@ -3264,7 +3379,7 @@ static int pj_run(pile_job *pj, worker_t *w)
             fputc('\n', af);
         }
         if (fclose(af) != 0)
-            PFAIL("[::] ERROR writing '%s'.\n", arm_fn);
+            SFAIL("[::] ERROR writing '%s'.\n", arm_fn);
         free(arm_fn);
         phase("arm statistics file");
     }
@@ -3272,38 +3387,97 @@ static int pj_run(pile_job *pj, worker_t *w)
         /* one file for the run, like the arm statistics: a line per comparison individual in the order of the summaries, as
          * bin/sum-hiddengem.py prints a row, then its totals over the pileup's individuals */
         size_t total[3] = {0, 0, 0};
-        fprintf(st_file, "# ID\tN_SEGMENTS\tN_IBD0\tN_IBD1\tN_IBD2\tFRAC_IBD0\tFRAC_IBD1\tFRAC_IBD2\n");
+        fprintf(r->st_file, "# ID\tN_SEGMENTS\tN_IBD0\tN_IBD1\tN_IBD2\tFRAC_IBD0\tFRAC_IBD1\tFRAC_IBD2\n");
         for (size_t ti = 0; ti < targets.n; ++ti) {
-            hg_frac_row(st_file, g_ids.names[targets.idx[ti]], st_res + 3 * ti);
+            hg_frac_row(r->st_file, g_ids.names[targets.idx[ti]], r->st_res + 3 * ti);
             for (int k = 0; k < 3; ++k)
-                total[k] += st_res[3 * ti + k];
+                total[k] += r->st_res[3 * ti + k];
         }
-        hg_frac_totals(st_file, total);
-        FILE *f = st_file;
-        st_file = NULL;
+        hg_frac_totals(r->st_file, total);
+        FILE *f = r->st_file;
+        r->st_file = NULL;
         if (fclose(f) != 0)
-            PFAIL("[::] ERROR writing '%s'.\n", st_fn);
-        free(st_fn);
-        free(st_res);
+            SFAIL("[::] ERROR writing '%s'.\n", r->st_fn);
         phase("IBD-state fractions file");
     }
-    if (g_list_mode) {
-        /* the next pileup's arrays take their place (a single -P run leaves them to the end of the process) */
-        for (int k = 0; k < OUT_SLOTS; ++k)
-            free(site_slot[k]);
-        free(s_row); free(s_cand); free(s_nr); free(s_na); free(s_fo); free(s_row_dev);
-        free(c_row); free(c_nr); free(c_na); free(c_fo);
-        free(row_pre); free(row_pre_off); free(arm_res); free(arm_wfirst); free(arm_wlast);
-        free(sum_pos_first); free(sum_pos_last);
-    } else {
-        free(row_pre);
-        free(row_pre_off);
+    return 0;
+}
+
+/* What the run holds, after a failure as well (every thread that read it has been joined).  The small things always; the large
+ * arrays for a list only, where the next pileup's take their place: a single -P run leaves them to the end of the process. */
+static void run_release(pile_run *r)
+{
+    site_list *sl = &r->sl;
+    free(r->st_fn); free(r->st_res); free(sl->row_pre); free(sl->row_pre_off);
+    r->st_fn = sl->row_pre = NULL;
+    r->st_res = NULL;
+    sl->row_pre_off = NULL;
+    if (!g_list_mode)
+        return;
+    for (int k = 0; k < OUT_SLOTS; ++k)
+        free(r->site_slot[k]);
+    free(r->c_row); free(r->c_nr); free(r->c_na); free(r->c_fo); free(r->arm_res);
+    site_list_reset(sl);
+    free(sl->s_row); free(sl->s_cand); free(sl->s_nr); free(sl->s_na); free(sl->s_fo);
+}
+
+static int pj_run(pile_job *pj, worker_t *w)
+{
+    pile_run r;
+    out_job *const outs = w->outs;
+    grand_seed(1);                  /* a fresh process's read-thinning stream (-D) */
+    if (g_list_mode)
+        timing_tag = pj->name;
+    memset(&r, 0, sizeof r);
+    r.pj = pj; r.w = w; r.err = pj->err;
+    run_modes(&r);
+    if (run_begin(&r))
+        goto fail;
+    for (r.ti = 0; r.ti < g_targets.n; ++r.ti) {
+        r.tgt = g_targets.idx[r.ti];
+        r.tname = g_ids.names[r.tgt];
+        r.same_sites = r.one_list && r.ti > 0;
+        memset(&r.wt, 0, sizeof r.wt);
+        if (r.overlap && output_slot_wait(&r))
+            goto fail;
+        fprintf(r.err, "Running %s-vs-%s comparison...\n", pj->name, r.tname);
+        if (r.dev_v && r.ti == 0 && candidates_to_device(&r))
+            goto fail;
+        if (site_list_stage(&r))
+            goto fail;
+        row_prefix_once(&r);
+        if (g_no_engine ? windows_on_host(&r) : windows_on_engine(&r))
+            goto fail;
+        if (r.tables_stay) {
+            win_table_free(&r.wt);
+            phase("per individual: engine (upload, run, arm sums)");
+            continue;
+        }
+        summary_positions(&r);
+        phase("per individual: engine (upload, run, results)");
+        if (output_start(&r))
+            goto fail;
+        phase("per individual: output files");
     }
+    for (int k = 0; k < OUT_SLOTS; ++k) {     /* the output jobs still running */
+        if (outs[k].running) {
+            pthread_join(outs[k].th, NULL);
+            outs[k].running = 0;
+            if (outs[k].failed)
+                goto fail;
+        }
+    }
+    if (r.overlap)
+        phase("output files of the last individuals (written beside the engine's work on the ones after them)");
+    if (run_end(&r))
+        goto fail;
+    run_release(&r);
     return 0;
 fail:
     outs_settle_one(outs, 1);
-    if (st_file)
-        fclose(st_file);                  /* (opened empty, left empty) */
+    if (r.st_file)
+        fclose(r.st_file);                /* (opened empty, left empty) */
+    run_release(&r);
     return 1;
 }
 

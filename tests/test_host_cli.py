@@ -589,3 +589,77 @@ def test_number_conversions_equal_printf():
     r = subprocess.run([_exe(), "--fmt-check", "2000000"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-500:]
     assert "2000000 values, 0 differences" in r.stdout
+
+
+# ---- the run of one pileup (pj_run and its stages): paths no other CPU test takes ----------------------------------------
+# What the parent commit's build did in each case (exit code, messages, every file's bytes as a SHA-256) is recorded in
+# tests/golden/pj_run/expected.json:  IBDGEM_EXE=<that build> python tests/test_host_cli.py --record
+FIX_ONE = ["-H", "test.hap", "-L", "test.legend", "-I", "test.indv", "-P", "test1.pileup", "-N", "sample1"]
+PJ_RUN_CASES = {
+    # a file of the second individual cannot be opened (a directory has its name) while the first one's job is writing
+    "summary_blocked": dict(args=FIX_ONE + ["--states", "--log-summary"], block="sample1.sample2.summary.txt"),
+    "logsummary_blocked": dict(args=FIX_ONE + ["--states", "--log-summary"], block="sample1.sample2.logsummary.txt"),
+    "hiddengem_blocked": dict(args=FIX_ONE + ["--states", "--log-summary", "--summary-only"], block="sample1.sample2.hiddengem.txt"),
+    "hiddengem_blocked_in_a_list": dict(args=FIX_ONE[:6] + ["--pileup-list", "LIST", "--states"], block="sample2.sample3.hiddengem.txt"),
+    # the run's own file cannot be opened once every individual is through
+    "armstats_blocked": dict(args=FIX_ONE + ["--arm-stats", "10,20"], block="sample1.armstats.txt"),
+    # rows whose genotypes do not parse: their message once per comparison individual over the kept site list
+    "unparsed_genotypes_two_individuals": dict(args=["-V", "panel.vcf.gz", "-P", "reads.pileup.gz", "-s", "ind64,ind3", "-q", "30"],
+                                               tag="synV"),
+    "out_threads_switch": dict(args=FIX_ONE, env={"IBDGEM_OUT_THREADS": "2", "IBDGEM_OUT_SLOTS": "2"}),
+}
+
+
+def _pj_run_case(exe, case, tmp):
+    import hashlib
+    c = PJ_RUN_CASES[case]
+    out = os.path.join(tmp, "o")
+    os.makedirs(out)
+    if "block" in c:
+        os.makedirs(os.path.join(out, c["block"]))
+    lst = os.path.join(tmp, "list.txt")
+    with open(lst, "w") as fh:
+        fh.write("".join(f"sample{k} test{k}.pileup\n" for k in (1, 2, 3)))
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="", IBDGEM_KEEP_TEARDOWN="1", **c.get("env", {}))
+    cwd = os.path.join(G.GOLD, c["tag"], "input") if "tag" in c else FIX_IN
+    r = subprocess.run([exe] + [lst if a == "LIST" else a for a in c["args"]] + ["-O", out], cwd=cwd, env=env,
+                       capture_output=True, text=True)
+    files = {}
+    for fn in sorted(os.listdir(out)):
+        data = open(os.path.join(out, fn), "rb").read() if os.path.isfile(os.path.join(out, fn)) else b"(directory)"
+        if data.startswith(b"# Entered command"):
+            data = data.split(b"\n", 1)[1]
+        files[fn] = hashlib.sha256(data).hexdigest() if data else "empty"
+    err = [l.replace(str(tmp), "TMP") for l in r.stderr.splitlines() if not l.startswith("Run time:")]
+    return {"exit": r.returncode, "stderr": err, "files": files}
+
+
+@pytest.mark.parametrize("case", sorted(PJ_RUN_CASES))
+def test_pileup_run_paths_do_what_the_recorded_build_did(case, tmp_path):
+    import json
+    with open(os.path.join(G.GOLD, "pj_run", "expected.json")) as fh:
+        want = json.load(fh)[case]
+    got = _pj_run_case(_exe(), case, str(tmp_path))
+    assert got["exit"] == want["exit"]
+    assert got["stderr"] == want["stderr"]
+    assert got["files"] == want["files"]
+    if "blocked" in case:
+        assert got["exit"] == 1 and any("Cannot open" in l for l in got["stderr"])
+    if case == "unparsed_genotypes_two_individuals":
+        n = sum("Failed to parse genotype fields at" in l for l in got["stderr"])
+        assert n > 0 and n % 2 == 0 and got["exit"] == 0
+
+
+if __name__ == "__main__":
+    import json
+    import sys
+    import tempfile
+    if sys.argv[1:] == ["--record"]:
+        rec = {}
+        for name in sorted(PJ_RUN_CASES):
+            with tempfile.TemporaryDirectory() as d:
+                rec[name] = _pj_run_case(_exe(), name, d)
+        os.makedirs(os.path.join(G.GOLD, "pj_run"), exist_ok=True)
+        with open(os.path.join(G.GOLD, "pj_run", "expected.json"), "w") as fh:
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write("\n")
