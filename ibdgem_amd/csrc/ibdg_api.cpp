@@ -5,6 +5,7 @@
 #include "../../include/ibdgem_hip.h"
 #include "ibdg_ctx.h"
 #include "ibdg_kernels.h"
+#include "ibdg_states.h"
 
 #include <hip/hip_runtime.h>
 
@@ -2229,16 +2230,17 @@ int ibdg_get_window_log2_all(ibdg_ctx *c, double *out)
 // Segmented sums over the window table of the last run (ibdg_llr.hip).  On the main stream behind join_streams: LIBD2 comes
 // from stream2, LIBD0/LIBD1 may come from a finalising launch still pending for the next run.  The segments go in chunks
 // whose slab of partials stays under LLR_SLAB items (one segment per chunk at least: its slab is then ~1/1500 of win_ll).
-int ibdg_window_llr_sums(ibdg_ctx *c, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out)
+static int llr_sums(ibdg_ctx *c, const char *fn, bool from_log, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out)
 {
     if (!c) return 1;
-    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_window_llr_sums: no results (call ibdg_run)");
-    if (n_seg && (!first || !end || !out)) return fail(c, "[::] ERROR in ibdg_window_llr_sums: NULL array");
+    if (!c->have_results) return fail(c, "[::] ERROR in %s: no results (call ibdg_run)", fn);
+    if (n_seg && (!first || !end || !out)) return fail(c, "[::] ERROR in %s: NULL array", fn);
+    if (from_log && !c->wlog.valid) return fail(c, "[::] ERROR in %s: the last run kept no window logs (option log_windows)", fn);
     for (size_t s = 0; s < n_seg; ++s) {
         if (end[s] < first[s])
-            return fail(c, "[::] ERROR in ibdg_window_llr_sums: range %zu is reversed ([%u, %u))", s, first[s], end[s]);
+            return fail(c, "[::] ERROR in %s: range %zu is reversed ([%u, %u))", fn, s, first[s], end[s]);
         if (end[s] > c->sites.n_win)
-            return fail(c, "[::] ERROR in ibdg_window_llr_sums: range %zu ends at %u, past the %u windows", s, end[s], c->sites.n_win);
+            return fail(c, "[::] ERROR in %s: range %zu ends at %u, past the %u windows", fn, s, end[s], c->sites.n_win);
     }
     if (n_seg == 0 || c->n_targets == 0) return 0;
     constexpr size_t LLR_SLAB = (size_t)1 << 22;
@@ -2258,13 +2260,70 @@ int ibdg_window_llr_sums(ibdg_ctx *c, const uint32_t *first, const uint32_t *end
     for (size_t s0 = 0; s0 < n_seg; s0 += chunk) {
         const size_t m = std::min(chunk, n_seg - s0);
         HIP_TRY(c, hipMemcpyAsync(c->llr_seg.p, seg.data() + 2 * s0, m * 8, hipMemcpyHostToDevice, c->stream));
-        ibdg::launch_llr_sums((const double *)c->win_ll.p, c->sites.n_win, (uint32_t)T, (const uint32_t *)c->llr_seg.p, (uint32_t)m,
-                              nb, (double *)c->llr_part.p, (double *)c->llr_out.p, c->stream);
+        ibdg::launch_llr_sums((const double *)(from_log ? c->wlog.win_log2.p : c->win_ll.p), c->sites.n_win, (uint32_t)T, (const uint32_t *)c->llr_seg.p, (uint32_t)m,
+                              nb, (double *)c->llr_part.p, (double *)c->llr_out.p, c->stream, from_log);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpy2DAsync(out + s0 * 4, n_seg * 32, c->llr_out.p, m * 32, m * 32, T, hipMemcpyDeviceToHost, c->stream));
         if (s0 + m < n_seg)                              // (the next chunk reuses the device buffers)
             HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
+    return quiesce(c);
+}
+
+int ibdg_window_llr_sums(ibdg_ctx *c, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out)
+{
+    return llr_sums(c, __func__, false, first, end, n_seg, out);
+}
+
+// The same over win_log2, whose entries are the terms (its writers are covered by join_streams like win_ll's: WinLog in ibdg_ctx.h)
+int ibdg_window_log2_llr_sums(ibdg_ctx *c, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out)
+{
+    return llr_sums(c, __func__, true, first, end, n_seg, out);
+}
+
+int ibdg_log2_states_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, uint8_t *path, int64_t *score,
+                          uint64_t count[3])
+{
+    char msg[256];
+    if (ibdg::log2_states_host(log2_tab, n_win, p01, p02, p12, path, score, count, msg, sizeof msg))
+        return fail(nullptr, "%s", msg);
+    return 0;
+}
+
+// IBD-state paths over win_log2 of the last run (ibdg_states.hip).  One launch on the main stream behind join_streams, as
+// the copies of ibdg_get_window_log2 (the table's writers: WinLog in ibdg_ctx.h), then the copies out and a host wait: no
+// reader of the table and no user of st_path / st_score / st_count outlives the call.
+int ibdg_window_log2_states(ibdg_ctx *c, double p01, double p02, double p12, uint8_t *path, int64_t *score, uint64_t *count)
+{
+    if (!c) return 1;
+    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_window_log2_states: no results (call ibdg_run)");
+    if (!c->wlog.valid) return fail(c, "[::] ERROR in ibdg_window_log2_states: the last run kept no window logs (option log_windows)");
+    if (!count) return fail(c, "[::] ERROR in ibdg_window_log2_states: NULL count");
+    int64_t P[3];
+    int bad = 0;
+    if (ibdg::states_penalties(p01, p02, p12, P, &bad)) {
+        static const char *const name[3] = {"p01", "p02", "p12"};
+        return fail(c, "[::] ERROR in ibdg_window_log2_states: %s = %g is not in (0, 1]", name[bad], bad == 0 ? p01 : bad == 1 ? p02 : p12);
+    }
+    const size_t T = c->n_targets, n_win = c->sites.n_win;
+    if (n_win > ibdg::STATES_MAX_WIN)
+        return fail(c, "[::] ERROR in ibdg_window_log2_states: %zu windows, more than the %zu (2^21) the integer scores allow", n_win,
+                    ibdg::STATES_MAX_WIN);
+    if (T == 0) return 0;
+    if (n_win == 0) {
+        memset(count, 0, T * 3 * sizeof *count);
+        return 0;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ensure(c, c->st_path, T * n_win) || ensure(c, c->st_count, T * 24) || (score && ensure(c, c->st_score, T * n_win * 24)))
+        return 1;
+    if (join_streams(c)) return 1;
+    ibdg::launch_log2_states((const double *)c->wlog.win_log2.p, (uint32_t)n_win, (uint32_t)T, P, (uint8_t *)c->st_path.p,
+                             score ? (int64_t *)c->st_score.p : nullptr, (uint64_t *)c->st_count.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(count, c->st_count.p, T * 24, hipMemcpyDeviceToHost, c->stream));
+    if (path) HIP_TRY(c, hipMemcpyAsync(path, c->st_path.p, T * n_win, hipMemcpyDeviceToHost, c->stream));
+    if (score) HIP_TRY(c, hipMemcpyAsync(score, c->st_score.p, T * n_win * 24, hipMemcpyDeviceToHost, c->stream));
     return quiesce(c);
 }
 

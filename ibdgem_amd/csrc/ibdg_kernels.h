@@ -348,8 +348,19 @@ int launch_ld(const LdArgs &a, unsigned n_targets, int cpw, unsigned waves, hipS
 // {sum log2 L2' - log2 L0' (hi, lo), sum log2 L1' - log2 L0' (hi, lo)}.  Two launches on `st`, no atomics.
 constexpr uint32_t LLR_BLK = 2048;
 constexpr uint64_t LLR_MAX_BLOCKS = 8192;
+// from_log: the table is win_log2 and its entries are the terms themselves (ibdg_window_log2_llr_sums: +l2, -l0 and +l1, -l0;
+// no log2, no 2^-1074 for a zero) -- the second instantiation of k_llr_partial, same geometry.
 void launch_llr_sums(const double *win_ll, uint32_t n_win, uint32_t n_targets, const uint32_t *seg, uint32_t n_seg,
-                     uint32_t nb, double *part, double *out, hipStream_t st);
+                     uint32_t nb, double *part, double *out, hipStream_t st, bool from_log = false);
+
+// IBD-state paths over win_log2[T][n_win][3] (ibdg_states.hip, ibdg_window_log2_states; the definition is in ibdg_states.h):
+// one workgroup of STATES_THREADS per comparison individual, grid-stride over the individuals under STATES_MAX_BLOCKS.
+// P: the penalties P_01, P_02, P_12 in quanta (states_penalties); path [T][n_win] (always: it holds `from` on the way); score
+// [T][n_win][3] or NULL; count [T][3].  n_win <= STATES_MAX_WIN.  One launch on `st`, no atomics.
+constexpr int STATES_THREADS = 256;
+constexpr uint32_t STATES_MAX_BLOCKS = 1024;
+void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], uint8_t *path,
+                        int64_t *score, uint64_t *count, hipStream_t st);
 
 // log2 of the window likelihoods (ibdg_ld_log.hip, option "log_windows"): win_log2[T][n_win][3].
 // k_ld_log: columns 0 and 1 of an --LD run from the layout's tiles, segments, window constants and power tables (what

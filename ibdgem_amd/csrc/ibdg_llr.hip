@@ -10,6 +10,7 @@
 // the log of a ratio, which overflows at L0' = 2^-1074): the sum is exact to ~2^-100 of the terms' magnitudes,
 // so its rounded value does not depend on how the windows were split into blocks, batches or devices.
 // Built with -ffp-contract=off (Makefile): TwoSum is exact only without fused multiply-add rewrites.
+// ibdg_window_log2_llr_sums: the same two kernels over win_log2 (option "log_windows"), whose entries are the terms.
 // Bytes: 24 per window read once per segment covering it, 32 per partial; the launch is bound by memory.
 #include "ibdg_kernels.h"
 
@@ -65,6 +66,8 @@ __device__ __forceinline__ DD shfl_down(DD v, int d)
 }
 
 // grid-stride over items (t, s, b); item i: b = i % nb, (t * n_seg + s) = i / nb
+// LOG: the table holds log2 of the columns already (win_log2): its entries are the terms
+template <bool LOG>
 __global__ __launch_bounds__(LLR_THREADS) void k_llr_partial(const double *__restrict__ win_ll, uint32_t n_win,
                                                              const uint32_t *__restrict__ seg, uint32_t n_seg, uint32_t nb,
                                                              uint64_t n_items, double *__restrict__ part)
@@ -81,7 +84,8 @@ __global__ __launch_bounds__(LLR_THREADS) void k_llr_partial(const double *__res
         const double *tab = win_ll + (size_t)t * n_win * 3;
         DD a = {0.0, 0.0}, c = {0.0, 0.0};
         for (uint64_t w = w0 + threadIdx.x; w < w1; w += LLR_THREADS) {
-            const double l0 = lg(tab[3 * w]), l1 = lg(tab[3 * w + 1]), l2 = lg(tab[3 * w + 2]);
+            const double l0 = LOG ? tab[3 * w] : lg(tab[3 * w]), l1 = LOG ? tab[3 * w + 1] : lg(tab[3 * w + 1]),
+                         l2 = LOG ? tab[3 * w + 2] : lg(tab[3 * w + 2]);
             dd_add_d(a, l2);
             dd_add_d(a, -l0);
             dd_add_d(c, l1);
@@ -136,14 +140,18 @@ __global__ __launch_bounds__(LLR_THREADS) void k_llr_combine(const double *__res
 }  // namespace
 
 void launch_llr_sums(const double *win_ll, uint32_t n_win, uint32_t n_targets, const uint32_t *seg, uint32_t n_seg,
-                     uint32_t nb, double *part, double *out, hipStream_t st)
+                     uint32_t nb, double *part, double *out, hipStream_t st, bool from_log)
 {
     const uint64_t n_ts = (uint64_t)n_targets * n_seg, n_items = n_ts * nb;
     if (n_items == 0)
         return;
     const uint64_t grid = n_items < LLR_MAX_BLOCKS ? n_items : LLR_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_llr_partial, dim3((unsigned)grid), dim3(LLR_THREADS), 0, st, win_ll, n_win, seg, n_seg, nb, n_items,
-                       part);
+    if (from_log)
+        hipLaunchKernelGGL(k_llr_partial<true>, dim3((unsigned)grid), dim3(LLR_THREADS), 0, st, win_ll, n_win, seg, n_seg, nb,
+                           n_items, part);
+    else
+        hipLaunchKernelGGL(k_llr_partial<false>, dim3((unsigned)grid), dim3(LLR_THREADS), 0, st, win_ll, n_win, seg, n_seg, nb,
+                           n_items, part);
     hipLaunchKernelGGL(k_llr_combine, dim3((unsigned)((n_ts + LLR_THREADS - 1) / LLR_THREADS)), dim3(LLR_THREADS), 0, st,
                        part, nb, n_ts, out);
 }

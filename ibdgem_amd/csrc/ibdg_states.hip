@@ -1,0 +1,229 @@
+// ibdg_states.hip -- IBD-state paths over the log2 window table of the last run (ibdg_window_log2_states): the integer
+// (max, +) recurrence of ibdg_states.h, whose host twin is ibdg_states_host.cpp.  Same integers by construction: the
+// emissions are exact products of an fp64 difference, everything behind them is int64 add / compare / select.
+//
+// k_log2_states: a workgroup of STATES_THREADS per comparison individual, grid-stride over the individuals.  Thread b owns
+// windows [b C, (b + 1) C), C = ceil(n_win / STATES_THREADS).
+//   pass 1  the block's step matrices A_w[q][s] = pen[q][s] + e_w[s] multiplied (max, +) into one 3 x 3 matrix in LDS (block
+//           0 starts from three copies of the row e_0); thread 0 then walks the blocks' matrices in order and leaves every
+//           block the exact score vector at the end of the block before it
+//   pass 2  the block's windows again from that vector: the sequential recurrence's own scores (written where asked for),
+//           `from` as 6 bits per window in the individual's path bytes, and the block's backward map (state at its last
+//           window -> state at the last window of the block before)
+//   pass 3  the backward maps composed from the last block down (a suffix scan over the 256 maps of 6 bits in LDS), every
+//           thread traces its own windows backward, overwriting `from` with the state; the counts meet in LDS
+// No atomics.  Reads: a thread walks its own 24-byte rows, lanes 24 C bytes apart (DESIGN 4.8 has the measurement).
+#include "ibdg_kernels.h"
+#include "ibdg_states.h"
+
+#include <hip/hip_runtime.h>
+
+namespace ibdg {
+
+namespace {
+
+struct Pen {
+    int64_t p01, p02, p12;
+};
+
+__device__ __forceinline__ void emission(const double *__restrict__ l, int64_t e[3])
+{
+    const double l0 = l[0], l1 = l[1], l2 = l[2];
+    e[0] = e[1] = e[2] = 0;
+    if (l0 != l0 || l1 != l1 || l2 != l2)
+        return;
+    double m = l0 > l1 ? l0 : l1;
+    m = m > l2 ? m : l2;
+    if (!(m - m == 0.0))                       // +-inf
+        return;
+    const double v[3] = {l0, l1, l2};
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        double d = v[s] - m;
+        d = d < STATES_D_MIN ? STATES_D_MIN : d;
+        e[s] = __double2ll_rn(d * STATES_QUANTA);
+    }
+}
+
+// v'[s] = max_q(v[q] + pen[q][s]) + e[s], lowest q on a tie; returns from[s] in bits 2 s, 2 s + 1
+__device__ __forceinline__ unsigned step(int64_t v[3], const int64_t pen[3][3], const int64_t e[3])
+{
+    int64_t nv[3];
+    unsigned f = 0;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        int64_t best = v[0] + pen[0][s];
+        unsigned m = 0;
+#pragma unroll
+        for (int q = 1; q < 3; ++q) {
+            const int64_t c = v[q] + pen[q][s];
+            const bool gt = c > best;
+            best = gt ? c : best;
+            m = gt ? q : m;
+        }
+        nv[s] = best + e[s];
+        f |= m << (2 * s);
+    }
+    v[0] = nv[0], v[1] = nv[1], v[2] = nv[2];
+    return f;
+}
+
+__device__ __forceinline__ int argmax3(const int64_t v[3])
+{
+    int m = v[1] > v[0] ? 1 : 0;
+    return v[2] > v[m] ? 2 : m;
+}
+
+// a map of the three states as 6 bits (state s -> bits 2 s, 2 s + 1); (a after b)(s) = a(b(s))
+__device__ __forceinline__ unsigned map_at(unsigned a, unsigned s) { return a >> (2 * s) & 3; }
+__device__ __forceinline__ unsigned map_after(unsigned a, unsigned b)
+{
+    return map_at(a, map_at(b, 0)) | map_at(a, map_at(b, 1)) << 2 | map_at(a, map_at(b, 2)) << 4;
+}
+constexpr unsigned MAP_ID = 0 | 1 << 2 | 2 << 4;
+
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__restrict__ win_log2, uint32_t n_win,
+                                                                uint32_t n_targets, Pen P, uint8_t *__restrict__ path,
+                                                                int64_t *__restrict__ score, uint64_t *__restrict__ count)
+{
+    __shared__ int64_t mat[STATES_THREADS][9];      // 18 KB
+    __shared__ int64_t vin[STATES_THREADS][3];      // score vector at the end of the block before
+    __shared__ uint8_t maps[2][STATES_THREADS];
+    __shared__ uint32_t cnt[STATES_THREADS / 64][3];
+    __shared__ int last_state;
+
+    const int64_t pen[3][3] = {{0, P.p01, P.p02}, {P.p01, 0, P.p12}, {P.p02, P.p12, 0}};
+    const uint32_t b = threadIdx.x;
+    const uint32_t C = (n_win + STATES_THREADS - 1) / STATES_THREADS;
+    const uint32_t nbk = (n_win + C - 1) / C;        // blocks that own windows (n_win >= 1)
+    const uint64_t w0 = (uint64_t)b * C;
+    const uint64_t w1 = w0 + C < n_win ? w0 + C : n_win;
+    const bool own = b < nbk;
+
+    for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
+        const double *tab = win_log2 + (size_t)t * n_win * 3;
+        uint8_t *pt = path + (size_t)t * n_win;
+        int64_t *sc = score ? score + (size_t)t * n_win * 3 : nullptr;
+
+        // pass 1
+        if (own) {
+            int64_t r[3][3], e[3];
+            emission(tab + 3 * w0, e);
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    r[q][s] = b == 0 ? e[s] : pen[q][s] + e[s];
+            for (uint64_t w = w0 + 1; w < w1; ++w) {
+                emission(tab + 3 * w, e);
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    (void)step(r[q], pen, e);
+            }
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    mat[b][3 * q + s] = r[q][s];
+        }
+        __syncthreads();
+        if (b == 0) {
+            // block 0's three rows are the score vector at its end
+            int64_t v[3] = {mat[0][0], mat[0][1], mat[0][2]};
+            for (uint32_t k = 1; k < nbk; ++k) {
+                vin[k][0] = v[0], vin[k][1] = v[1], vin[k][2] = v[2];
+                int64_t nv[3];
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    int64_t best = v[0] + mat[k][s];
+#pragma unroll
+                    for (int q = 1; q < 3; ++q) {
+                        const int64_t c = v[q] + mat[k][3 * q + s];
+                        best = c > best ? c : best;
+                    }
+                    nv[s] = best;
+                }
+                v[0] = nv[0], v[1] = nv[1], v[2] = nv[2];
+            }
+            last_state = argmax3(v);
+        }
+        __syncthreads();
+
+        // pass 2
+        unsigned back = MAP_ID;
+        if (own) {
+            int64_t v[3], e[3];
+            uint64_t w = w0;
+            if (b == 0) {
+                emission(tab, v);
+                pt[0] = (uint8_t)MAP_ID;
+                if (sc)
+                    sc[0] = v[0], sc[1] = v[1], sc[2] = v[2];
+                w = 1;
+            } else {
+                v[0] = vin[b][0], v[1] = vin[b][1], v[2] = vin[b][2];
+            }
+            for (; w < w1; ++w) {
+                emission(tab + 3 * w, e);
+                const unsigned f = step(v, pen, e);
+                pt[w] = (uint8_t)f;
+                if (sc)
+                    sc[3 * w] = v[0], sc[3 * w + 1] = v[1], sc[3 * w + 2] = v[2];
+                back = map_after(back, f);         // state at w -> state at w0 - 1 (block 0: at window 0)
+            }
+        }
+        maps[0][b] = (uint8_t)back;
+        __syncthreads();
+
+        // pass 3: maps[..][k] becomes block k's map after block k + 1's after ... after the last block's
+        int cur = 0;
+        for (uint32_t d = 1; d < STATES_THREADS; d <<= 1) {
+            unsigned m = maps[cur][b];
+            if (b + d < STATES_THREADS)
+                m = map_after(m, maps[cur][b + d]);
+            maps[cur ^ 1][b] = (uint8_t)m;
+            cur ^= 1;
+            __syncthreads();
+        }
+        uint32_t n[3] = {0, 0, 0};
+        if (own) {
+            // the state at this block's last window: the last block's is the best final score's, any other's is what the
+            // blocks behind it map that one to
+            unsigned st = b + 1 == nbk ? (unsigned)last_state : map_at(maps[cur][b + 1], (unsigned)last_state);
+            for (uint64_t w = w1; w-- > w0;) {
+                const unsigned f = pt[w];
+                pt[w] = (uint8_t)st;
+                n[0] += st == 0, n[1] += st == 1, n[2] += st == 2;
+                st = map_at(f, st);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+            for (int d = 32; d > 0; d >>= 1)
+                n[s] += __shfl_down(n[s], d, 64);
+        if ((b & 63) == 0)
+            cnt[b >> 6][0] = n[0], cnt[b >> 6][1] = n[1], cnt[b >> 6][2] = n[2];
+        __syncthreads();
+        if (b < 3) {
+            uint64_t sum = 0;
+            for (int k = 0; k < STATES_THREADS / 64; ++k)
+                sum += cnt[k][b];
+            count[(size_t)t * 3 + b] = sum;
+        }
+        __syncthreads();       // (LDS is reused by the next individual)
+    }
+}
+
+}  // namespace
+
+void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], uint8_t *path,
+                        int64_t *score, uint64_t *count, hipStream_t st)
+{
+    if (n_win == 0 || n_targets == 0)
+        return;
+    const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_log2_states, dim3(grid), dim3(STATES_THREADS), 0, st, win_log2, n_win, n_targets, Pen{P[0], P[1], P[2]},
+                       path, score, count);
+}
+
+}  // namespace ibdg

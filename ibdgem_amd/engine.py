@@ -50,6 +50,9 @@ SYMBOLS = {
     "ibdg_get_window_log2": (C.c_int, [_P, C.c_size_t, _P]),
     "ibdg_get_window_log2_all": (C.c_int, [_P, _P]),
     "ibdg_window_llr_sums": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
+    "ibdg_window_log2_llr_sums": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
+    "ibdg_log2_states_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
+    "ibdg_window_log2_states": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
     "ibdg_run_ms": (C.c_int, [_P, C.c_uint, _P]),
@@ -143,6 +146,22 @@ def pack_alleles_fast(alleles):
     bits = pad.reshape(L, chunks, 64, 2).transpose(0, 1, 3, 2)
     by = np.packbits(bits, axis=-1, bitorder="little")          # [L][chunk][plane][8 bytes]
     return np.ascontiguousarray(by).view("<u8").reshape(L, chunks * 2)
+
+
+def log2_states_host(log2_tab, p01, p02, p12, want_path=True, want_score=True):
+    """The integer log-domain IBD-state path of one window table [n_win][3] on the host (ibdg_log2_states_host):
+    (path uint8 [n_win] or None, score int64 [n_win][3] or None, count uint64 [3])."""
+    lib = load_library()
+    tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
+    n = tab.shape[0]
+    path = np.zeros(n, dtype=np.uint8) if want_path else None
+    score = np.zeros((n, 3), dtype=np.int64) if want_score else None
+    count = np.zeros(3, dtype=np.uint64)
+    rc = lib.ibdg_log2_states_host(tab.ctypes.data, n, p01, p02, p12, None if path is None else path.ctypes.data,
+                                   None if score is None else score.ctypes.data, count.ctypes.data)
+    if rc != 0:
+        raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
+    return path, score, count
 
 
 class Engine:
@@ -322,6 +341,26 @@ class Engine:
         out = np.zeros((self.lib.ibdg_num_targets(self.ctx), len(first), 4), dtype=np.float64)
         self._chk(self.lib.ibdg_window_llr_sums(self.ctx, first.ctypes.data, end.ctypes.data, len(first), out.ctypes.data))
         return out
+
+    def window_log2_llr_sums(self, first, end):
+        """window_llr_sums with the terms taken from the log2 table (option "log_windows"): +l2, -l0 and +l1, -l0."""
+        first = np.ascontiguousarray(first, dtype=np.uint32)
+        end = np.ascontiguousarray(end, dtype=np.uint32)
+        assert first.shape == end.shape and first.ndim == 1
+        out = np.zeros((self.lib.ibdg_num_targets(self.ctx), len(first), 4), dtype=np.float64)
+        self._chk(self.lib.ibdg_window_log2_llr_sums(self.ctx, first.ctypes.data, end.ctypes.data, len(first), out.ctypes.data))
+        return out
+
+    def window_log2_states(self, p01, p02, p12, want_path=True, want_score=True):
+        """Integer log-domain IBD-state paths of every comparison individual of the last run, on the device
+        (ibdg_window_log2_states): (path uint8 [T][n_win] or None, score int64 [T][n_win][3] or None, count uint64 [T][3])."""
+        T, n = self.lib.ibdg_num_targets(self.ctx), self.n_windows
+        path = np.zeros((T, n), dtype=np.uint8) if want_path else None
+        score = np.zeros((T, n, 3), dtype=np.int64) if want_score else None
+        count = np.zeros((T, 3), dtype=np.uint64)
+        self._chk(self.lib.ibdg_window_log2_states(self.ctx, p01, p02, p12, None if path is None else path.ctypes.data,
+                                                   None if score is None else score.ctypes.data, count.ctypes.data))
+        return path, score, count
 
     def alt_counts(self, first, n):
         out = np.empty(n, dtype=np.uint32)

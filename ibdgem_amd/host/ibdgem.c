@@ -64,6 +64,7 @@ static int opt_threads = 0;
 static const char *cache_fn = NULL, *dump_panel_fn = NULL;
 static int opt_stats_only = 0, has_arm = 0;
 static int opt_log_summary = 0;          /* --log-summary: the summary's likelihoods as log2, from the engine's option "log_windows" */
+static int opt_log_stats = 0;            /* --log-stats: --arm-stats and --states from the log2 window table (no underflow), into log* files */
 static int opt_states = 0, has_pen = 0;  /* --states: the IBD-state path of every comparison (hgpath.c), --p01/--p02/--p12 its penalties */
 static double opt_p01 = HG_DEFAULT_P01, opt_p02 = HG_DEFAULT_P02, opt_p12 = HG_DEFAULT_P12;
 static unsigned long arm_c0, arm_c1;     /* --arm-stats: the centromeric range [c0, c1] of the run's chromosome */
@@ -76,6 +77,7 @@ static struct option longopts[] = {
     {"arm-stats", required_argument, 0, 1006},
     {"states", no_argument, &opt_states, 1},
     {"log-summary", no_argument, &opt_log_summary, 1},
+    {"log-stats", no_argument, &opt_log_stats, 1},
     {"p01", required_argument, 0, 1008},
     {"p02", required_argument, 0, 1009},
     {"p12", required_argument, 0, 1010},
@@ -163,6 +165,14 @@ static void usage(int code)
           "                            summary with LOG2_LIBD0 LOG2_LIBD1 LOG2_LIBD2 in place of the likelihoods, which\n"
           "                            leave the double range from moderate coverage on (0.000000e+00 in the summary);\n"
           "                            --LD columns from the exact exponents of the window products, on the device\n"
+          "  --log-stats               with --arm-stats and/or --states: take the statistics from log2 of the window\n"
+          "                            likelihoods (what --log-summary prints) instead of the likelihoods, which are 0 from\n"
+          "                            moderate coverage on: <out>/<pileup-name>.logarmstats.txt (the sums of the logs\n"
+          "                            themselves, no 2^-1074 in place of a 0), <pileup-name>.<individual>.loghiddengem.txt\n"
+          "                            (the path with the largest sum of log2 emissions and penalties, in integers of\n"
+          "                            2^-16 bit: nothing underflows, a window of zeros poisons nothing) and\n"
+          "                            <pileup-name>.logibdstates.txt, in place of the three linear files; summed, and\n"
+          "                            with --stats-only on one device also traced, on the device\n"
           "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
           "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
           "  --stats-only              with --arm-stats and/or --states: write the armstats / ibdstates file only (no\n"
@@ -1560,12 +1570,14 @@ static double arm_log2(double v)
     return log2(v == 0.0 ? 0x1p-1074 : v);
 }
 
-/* the sums over windows [a, b) of a window table on the host: out = {IBD2/IBD0 hi, lo, IBD1/IBD0 hi, lo} */
-static void llr_range_host(const double *win_ll, size_t a, size_t b, double out[4])
+/* the sums over windows [a, b) of a window table on the host: out = {IBD2/IBD0 hi, lo, IBD1/IBD0 hi, lo}; logs: the table
+ * is the log2 table and its entries are the terms (--log-stats, ibdg_window_log2_llr_sums) */
+static void llr_range_host(const double *win_ll, int logs, size_t a, size_t b, double out[4])
 {
     out[0] = out[1] = out[2] = out[3] = 0.0;
     for (size_t w = a; w < b; ++w) {
-        const double l0 = arm_log2(win_ll[3 * w]), l1 = arm_log2(win_ll[3 * w + 1]), l2 = arm_log2(win_ll[3 * w + 2]);
+        const double l0 = logs ? win_ll[3 * w] : arm_log2(win_ll[3 * w]), l1 = logs ? win_ll[3 * w + 1] : arm_log2(win_ll[3 * w + 1]),
+                     l2 = logs ? win_ll[3 * w + 2] : arm_log2(win_ll[3 * w + 2]);
         dd_add(out, l2, 0.0);
         dd_add(out, -l0, 0.0);
         dd_add(out + 2, l1, 0.0);
@@ -1644,6 +1656,9 @@ typedef struct {
     double *log;                             /* --log-summary: log2 of the same table, else NULL */
 } win_table;
 
+/* the log2 tables leave the engine / are made on the host: for --log-summary's files and --log-stats' statistics */
+static int want_logs(void) { return opt_log_summary || opt_log_stats; }
+
 static void win_table_free(win_table *t)
 {
     free(t->first); free(t->last); free(t->ncov); free(t->ll); free(t->log);
@@ -1679,6 +1694,8 @@ typedef struct {
     const uint32_t *arm_seg;                 /* --arm-stats: {p first, p end, q first, q end} in the slice's window indices, or NULL */
     double arm[8];                           /* ... the individual's sums over them (ibdg_window_llr_sums) */
     int stats_only;                          /* --stats-only: no window table leaves the device */
+    int dev_states;                          /* --log-stats --states --stats-only on one context: the paths are found on the device */
+    uint64_t st[3];                          /* ... the individual's windows in IBD0, IBD1, IBD2 (ibdg_window_log2_states) */
     FILE *err;                               /* where the pileup's messages go */
     int reported;                            /* a failure was reported here already (not an engine error) */
 } shard_job;
@@ -1701,6 +1718,8 @@ typedef struct {
     const uint32_t *batch_of;                /* the batch (its targets) the tables belong to; NULL: none */
     double *arm_sums;                        /* --arm-stats: the sums of the last run's individuals, [T][2][4] */
     size_t arm_cap;
+    uint64_t *st_counts;                     /* --log-stats --states: the state counts of the last run's individuals, [T][3] */
+    size_t st_cap;
     const uint32_t *ahead_of;                /* the batch that has been queued ahead on the device; NULL: none */
 } win_cache;
 static win_cache g_wcache[64];
@@ -1746,7 +1765,19 @@ static void *shard_run(void *arg)
                 wc->arm_sums = malloc(j->n_targets * 8 * sizeof(double));
                 wc->arm_cap = wc->arm_sums ? j->n_targets * 8 : 0;
             }
-            if (!wc->arm_sums || !same_run_size(j) || ibdg_window_llr_sums(j->eng, sf, se, 2, wc->arm_sums))
+            if (!wc->arm_sums || !same_run_size(j) ||
+                (opt_log_stats ? ibdg_window_log2_llr_sums : ibdg_window_llr_sums)(j->eng, sf, se, 2, wc->arm_sums))
+                return NULL;
+        }
+        if (j->dev_states) {
+            /* likewise: only the counts leave the device */
+            if (wc->st_cap < j->n_targets * 3) {
+                free(wc->st_counts);
+                wc->st_counts = malloc(j->n_targets * 3 * sizeof(uint64_t));
+                wc->st_cap = wc->st_counts ? j->n_targets * 3 : 0;
+            }
+            if (!wc->st_counts || !same_run_size(j) ||
+                ibdg_window_log2_states(j->eng, opt_p01, opt_p02, opt_p12, NULL, NULL, wc->st_counts))
                 return NULL;
         }
         if (j->stats_only) {
@@ -1765,16 +1796,16 @@ static void *shard_run(void *arg)
                 wc->batch_ll = ibdg_host_alloc(need);
                 wc->batch_cap = wc->batch_ll ? need : 0;
             }
-            if (opt_log_summary && wc->batch_log_cap < need) {
+            if (want_logs() && wc->batch_log_cap < need) {
                 free(wc->batch_log);
                 wc->batch_log = malloc(need);
                 wc->batch_log_cap = wc->batch_log ? need : 0;
             }
-            if (wc->batch_ll && !j->want_sites && (!opt_log_summary || wc->batch_log)) {
+            if (wc->batch_ll && !j->want_sites && (!want_logs() || wc->batch_log)) {
                 /* (the copy is as large as the LAST RUN's results: it must be the run of this very batch) */
                 if (!same_run_size(j) || ibdg_get_window_ll_all(j->eng, wc->batch_ll))        /* waits for the run */
                     return NULL;
-                if (opt_log_summary && ibdg_get_window_log2_all(j->eng, wc->batch_log))
+                if (want_logs() && ibdg_get_window_log2_all(j->eng, wc->batch_log))
                     return NULL;
                 wc->batch_of = j->targets;
                 wc->batch_T = j->n_targets;
@@ -1790,6 +1821,8 @@ static void *shard_run(void *arg)
     }
     if (j->arm_seg)
         memcpy(j->arm, wc->arm_sums + j->t_local * 8, sizeof j->arm);
+    if (j->dev_states)
+        memcpy(j->st, wc->st_counts + j->t_local * 3, sizeof j->st);
     j->wt.n_win = ibdg_num_windows(j->eng);
     if (j->stats_only) {
         j->failed = 0;
@@ -1799,8 +1832,8 @@ static void *shard_run(void *arg)
     j->wt.last = malloc((j->wt.n_win + 1) * 4);
     j->wt.ncov = malloc((j->wt.n_win + 1) * 4);
     j->wt.ll = malloc((j->wt.n_win + 1) * 24);
-    j->wt.log = opt_log_summary ? malloc((j->wt.n_win + 1) * 24) : NULL;
-    if (!j->wt.first || !j->wt.last || !j->wt.ncov || !j->wt.ll || (opt_log_summary && !j->wt.log))
+    j->wt.log = want_logs() ? malloc((j->wt.n_win + 1) * 24) : NULL;
+    if (!j->wt.first || !j->wt.last || !j->wt.ncov || !j->wt.ll || (want_logs() && !j->wt.log))
         return NULL;
     if (j->same_sites && wc->valid && wc->n_win == j->wt.n_win) {
         memcpy(j->wt.first, wc->first, j->wt.n_win * 4);
@@ -2069,7 +2102,7 @@ static void *upload_run(void *arg)
      * nothing per row: the engine then neither keeps nor computes per-row results beyond the IBD2 pick */
     if (ibdg_set_option(j->eng, "site_results", opt_summary_only ? 0 : 1))
         return NULL;
-    if (opt_log_summary && ibdg_set_option(j->eng, "log_windows", 1))
+    if (want_logs() && ibdg_set_option(j->eng, "log_windows", 1))
         return NULL;
     /* the uploads of all devices run side by side: each staging team gets its share of the host's threads (and locks
      * as much less memory: two 8 MB buffers per thread) */
@@ -2364,9 +2397,50 @@ static int write_states_parallel(FILE *f, const hg_path *h, int threads, char **
     return rc || write_all(fd, tail, hg_format_tail(h, tail));
 }
 
+/* --log-stats: the path over the individual's log2 table in integers (ibdg_log2_states_host: the same bytes as the device's
+ * ibdg_window_log2_states), its scores printed in bits */
+static const char log_hg_header[] = "Segment\tIBD0_LogScore\tIBD1_LogScore\tIBD2_LogScore\tInferred_State\n";
+
+static int log_states_individual(out_job *o)
+{
+    const size_t n = o->wt.n_win;
+    uint64_t count[3];
+    uint8_t *path = o->hg ? malloc(n ? n : 1) : NULL;
+    int64_t *score = o->hg ? malloc((n ? n : 1) * 3 * sizeof *score) : NULL;
+    int bad = o->hg && (!path || !score);
+    if (!bad && ibdg_log2_states_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, path, score, count)) {
+        fprintf(o->err, "%s\n", ibdg_last_error(NULL));
+        bad = 1;
+    }
+    if (!bad) {
+        for (int s = 0; s < 3; ++s)
+            o->st_count[s] = (size_t)count[s];
+        if (o->hg) {
+            hg_path tail = {0};
+            char buf[256];
+            tail.n = n;
+            memcpy(tail.count, o->st_count, sizeof tail.count);
+            bad = fputs(log_hg_header, o->hg) < 0;
+            for (size_t w = 0; w < n && !bad; ++w)
+                bad = fprintf(o->hg, "%d\t%.4Lf\t%.4Lf\t%.4Lf\t%d\n", (int)(w + 1), (long double)score[3 * w] / 65536,
+                              (long double)score[3 * w + 1] / 65536, (long double)score[3 * w + 2] / 65536, path[w]) < 0;
+            bad = bad || fwrite(buf, 1, hg_format_tail(&tail, buf), o->hg) == 0;
+        }
+    }
+    if (o->hg) {
+        bad = fclose(o->hg) != 0 || bad;
+        o->hg = NULL;
+    }
+    free(path);
+    free(score);
+    return bad;
+}
+
 /* 0: the path is found, counted for ibdstates.txt and (o->hg) written and its file closed */
 static int states_individual(out_job *o)
 {
+    if (opt_log_stats)
+        return log_states_individual(o);
     hg_path *h = &o->hgp;
     hg_reset(h);
     for (size_t w = 0; w < o->wt.n_win; ++w)
@@ -2787,7 +2861,7 @@ typedef struct {
     worker_t *w;
     FILE *err;
     int one_list;                   /* no -v, no -D: the site list does not depend on the comparison individual (:584, :627-628) */
-    int overlap, dev_v, batchable, arm_on, tables_stay, out_slots, out_threads_env;
+    int overlap, dev_v, batchable, arm_on, tables_stay, dev_states, out_slots, out_threads_env;
     size_t n_site_out;              /* entries of an individual's per-site array */
     double *arm_res;                /* --arm-stats, per individual: p20, q20, p10, q10; the run's armstats.txt */
     size_t *st_res;                 /* --states: per individual the windows in IBD0, IBD1, IBD2; the run's ibdstates.txt */
@@ -2841,6 +2915,9 @@ static void run_modes(pile_run *r)
     r->arm_on = has_arm && !opt_plan;
     /* --stats-only keeps the window tables on the device unless the states are asked for: the path is found on the host */
     r->tables_stay = opt_stats_only && !opt_states;
+    /* ... or in the log domain (--log-stats), where one context has the whole table and finds the paths itself */
+    r->dev_states = opt_stats_only && opt_states && opt_log_stats && !no_engine && r->w->n_eng == 1;
+    r->tables_stay = r->tables_stay || r->dev_states;
 }
 
 /* the run's arrays and its --states file */
@@ -2863,7 +2940,7 @@ static int run_begin(pile_run *r)
         /* opened before the run, like the individuals' files: a directory that cannot be written stops the run at once */
         if (!r->st_res)
             SFAIL("[::] ERROR: out of memory.\n");
-        if (asprintf(&r->st_fn, "%s/%s.ibdstates.txt", g_out_dir, r->pj->name) < 0)
+        if (asprintf(&r->st_fn, "%s/%s.%s.txt", g_out_dir, r->pj->name, opt_log_stats ? "logibdstates" : "ibdstates") < 0)
             return r->st_fn = NULL, 1;
         if (!(r->st_file = fopen(r->st_fn, "w")))
             SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->st_fn);
@@ -3053,8 +3130,8 @@ static int windows_on_host(pile_run *r)
     t->n_win = host_windows(sl->s_nr, sl->s_na, sl->n, (unsigned)opt_window, &t->first, &t->last, &t->ncov);
     if (g_host_math) {
         t->ll = malloc((t->n_win + 1) * 24);
-        t->log = opt_log_summary ? malloc((t->n_win + 1) * 24) : NULL;
-        if (opt_log_summary && !t->log)
+        t->log = want_logs() ? malloc((t->n_win + 1) * 24) : NULL;
+        if (want_logs() && !t->log)
             SFAIL("[::] ERROR: out of memory for %zu windows.\n", t->n_win);
         host_nonld(r->pj->cand, sl->s_cand, sl->s_nr, sl->s_na, sl->n, r->tgt, g_pdg_tab, all_threads(), r->site_ll, t->first,
                    t->last, t->n_win, t->ll, t->log);
@@ -3064,8 +3141,9 @@ static int windows_on_host(pile_run *r)
         int ok[2];
         double p[4], q[4], *res = r->arm_res + 4 * r->ti;
         arm_segments(sl->s_row, t->first, t->last, t->n_win, seg, ok);
-        llr_range_host(t->ll, seg[0], seg[1], p);
-        llr_range_host(t->ll, seg[2], seg[3], q);
+        const double *tab = opt_log_stats ? t->log : t->ll;
+        llr_range_host(tab, opt_log_stats, seg[0], seg[1], p);
+        llr_range_host(tab, opt_log_stats, seg[2], seg[3], q);
         res[0] = ok[0] ? p[0] : NAN; res[1] = ok[1] ? q[0] : NAN;
         res[2] = ok[0] ? p[2] : NAN; res[3] = ok[1] ? q[2] : NAN;
     }
@@ -3155,6 +3233,7 @@ static void shards_fill(const pile_run *r, shard_job *jobs)
         j->site_ll = r->site_ll;
         j->arm_seg = r->arm_on ? sl->arm_local[d] : NULL;
         j->stats_only = r->tables_stay;
+        j->dev_states = r->dev_states;
         j->err = r->err;
     }
 }
@@ -3210,7 +3289,7 @@ static void tables_gather(pile_run *r, shard_job *jobs)
     }
     t->first = malloc((t->n_win + 1) * 4); t->last = malloc((t->n_win + 1) * 4); t->ncov = malloc((t->n_win + 1) * 4);
     t->ll = malloc((t->n_win + 1) * 24);
-    t->log = opt_log_summary ? malloc((t->n_win + 1) * 24) : NULL;
+    t->log = want_logs() ? malloc((t->n_win + 1) * 24) : NULL;
     size_t wo = 0;
     for (int d = 0; d < r->w->n_eng; ++d) {
         win_table *s = &jobs[d].wt;
@@ -3248,6 +3327,9 @@ static int windows_on_engine(pile_run *r)
     shards_fill(r, jobs);
     if (shards_run(r, jobs) || (r->arm_on && arm_gather(r, jobs)))
         return 1;
+    if (r->dev_states)
+        for (int k = 0; k < 3; ++k)
+            r->st_res[3 * r->ti + k] = (size_t)jobs[0].st[k];
     if (r->tables_stay)                      /* no window table left the device */
         return 0;
     tables_gather(r, jobs);
@@ -3314,7 +3396,7 @@ static int outputs_open(pile_run *r, out_job *o)
     free(tab_fn);
     free(sum_fn);
     return !o->tab || !o->sum || (opt_log_summary && !(o->lsum = out_file_open(r, "logsummary", 0, NULL))) ||
-           (opt_states && !(o->hg = out_file_open(r, "hiddengem", 0, NULL)));
+           (opt_states && !(o->hg = out_file_open(r, opt_log_stats ? "loghiddengem" : "hiddengem", 0, NULL)));
 }
 
 /* everything the individual's files are made of goes to its slot's job, the window table with it; the job runs beside the
@@ -3360,7 +3442,7 @@ static int run_end(pile_run *r)
         char *arm_fn;
         const pileup_t *pu = r->pj->pu;
         const char *chrom = g_uchr ? g_uchr : pu->n_lines ? pu->chr_names[pu->lines[0].chr] : ".";
-        if (asprintf(&arm_fn, "%s/%s.armstats.txt", g_out_dir, r->pj->name) < 0)
+        if (asprintf(&arm_fn, "%s/%s.%s.txt", g_out_dir, r->pj->name, opt_log_stats ? "logarmstats" : "armstats") < 0)
             return 1;
         FILE *af = fopen(arm_fn, "w");
         if (!af)
@@ -3607,6 +3689,17 @@ int main(int argc, char **argv)
     if (opt_stats_only && opt_plan) { fprintf(stderr, "[::] ERROR: --stats-only writes a file --plan does not make; use one of them.\n"); exit(1); }
     if (opt_log_summary && opt_plan) { fprintf(stderr, "[::] ERROR: --log-summary writes files --plan does not make; use one of them.\n"); exit(1); }
     if (opt_log_summary && opt_stats_only) { fprintf(stderr, "[::] ERROR: --log-summary writes files --stats-only leaves out; use one of them.\n"); exit(1); }
+    if (opt_log_stats && opt_plan) { fprintf(stderr, "[::] ERROR: --log-stats writes files --plan does not make; use one of them.\n"); exit(1); }
+    if (opt_log_stats && !has_arm && !opt_states) { fprintf(stderr, "[::] ERROR: --log-stats needs --arm-stats START,END and/or --states: it says where their numbers come from.\n"); exit(1); }
+    if (opt_log_stats && opt_states) {
+        const double pen[3] = {opt_p01, opt_p02, opt_p12};
+        static const char *const pen_name[3] = {"--p01", "--p02", "--p12"};
+        for (int k = 0; k < 3; ++k)
+            if (!(pen[k] > 0.0 && pen[k] <= 1.0)) {
+                fprintf(stderr, "[::] ERROR: --log-stats takes log2 of the penalties: %s of %g is not in (0, 1].\n", pen_name[k], pen[k]);
+                exit(1);
+            }
+    }
     if (opt_stats_only)
         opt_summary_only = 1;                 /* (what the engine does for it: no per-site values, batches queued ahead) */
 

@@ -229,6 +229,30 @@ int ibdg_get_window_log2_all(ibdg_ctx *ctx, double *out);
  * same for any split of a range into parts whose double-doubles are added in order.  Errors: no results, end[s] <
  * first[s], end[s] > ibdg_num_windows, NULL arrays with n_seg > 0.  Returns after the sums are in host memory. */
 int ibdg_window_llr_sums(ibdg_ctx *ctx, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out);
+/* The same sums from the log2 table of option "log_windows": the terms are the table's own entries, +l2, -l0 and +l1, -l0 --
+ * no log2 and no 2^-1074 in place of a likelihood that left the double range.  Same out layout, double-double, order of
+ * additions, NaN handling, empty ranges and errors; also an error if the last ibdg_run was made with the option off. */
+int ibdg_window_log2_llr_sums(ibdg_ctx *ctx, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out);
+
+/* The IBD-state path of one window table in the log domain, in integers.  log2_tab[n_win][3] = log2 LIBD0/1/2; p01, p02,
+ * p12 the switch penalties of the reference's hiddengem (in (0, 1]).  In quanta of 2^-16 bit: a window's emission is e_s =
+ * llrint((l_s - max(l)) * 65536), the difference clamped below at -2^24 -- (0, 0, 0) if a column is NaN or the maximum is not
+ * finite --; a penalty is llrint(log2(p) * 65536), clamped below at -2^40, 0 for staying; score[0][s] = e_0[s], score[i][s] =
+ * max_q(score[i-1][q] + pen[q][s]) + e_i[s] in int64, the lowest q winning a tie; the path is traced back from the best final
+ * score (lowest state on a tie), as the reference's program does with products of probabilities.  No product, so nothing
+ * underflows, and a window whose linear columns are all 0 is a window like any other.  path[n_win] (states 0, 1, 2) and
+ * score[n_win][3] may be NULL; count[3] = windows per state (all 0 for n_win = 0).  Needs no device.  Errors
+ * (ibdg_last_error(NULL)): a penalty outside (0, 1] or NaN, n_win > 2^21 (the bound that keeps |score| < 2^62), NULL count. */
+int ibdg_log2_states_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, uint8_t *path,
+                          int64_t *score, uint64_t count[3]);
+/* The same for every comparison individual of the last ibdg_run, on the device, over its log2 table (option "log_windows"):
+ * path[T][n_win], score[T][n_win][3] (either may be NULL: only what is asked for leaves the device), count[T][3].  The same
+ * integers as ibdg_log2_states_host on ibdg_get_window_log2's table, bit for bit: integer (max, +) is exact and
+ * associative, so the blocks the kernel cuts the windows into do not show.  Same waits as ibdg_get_window_log2; returns with
+ * the outputs in host memory.  Errors: no results, the last ibdg_run made with the option off, a penalty out of range,
+ * more than 2^21 windows, NULL count. */
+int ibdg_window_log2_states(ibdg_ctx *ctx, double p01, double p02, double p12, uint8_t *path, int64_t *score,
+                            uint64_t *count);
 /* Alt-allele count of panel rows [first_row, first_row+n): out[n] (for tests). */
 int ibdg_get_alt_counts(ibdg_ctx *ctx, size_t first_row, size_t n, uint32_t *out);
 
