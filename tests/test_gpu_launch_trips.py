@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 import hp_ref as H
+from gap_cases import run_structure
 from ibdgem_amd import engine as E
 from test_gpu_arm_stats import check_against_model, random_case
 from test_gpu_parity import assert_bits, assert_ld_close, synth, windows_numpy
@@ -518,18 +519,9 @@ def ring_case(placement):
 def ring_runs(nr, na, W):
     """make_runs (ibdg_api.cpp) without guided lengths: runs of windows_per_wave windows, the last one shorter; the run
     length stands while a run's records fit the budget, max_seg * (sizeof(Seg) + 8) <= record_lds_bytes (build_segments).
-    Per run on the panel's own tiles (layout 1: row = position in the site list): tile pairs spanned, segments."""
-    rows = np.flatnonzero((nr.astype(int) + na) > 0)
-    n_win = cdiv(len(rows), W)
-    g = RING_RUN_OPTS["windows_per_wave"]
-    pairs, segs = [], []
-    for w0 in range(0, n_win, g):
-        r = rows[w0 * W:min(w0 + g, n_win) * W]
-        pairs.append(int(r[-1] // 64 - r[0] // 64 + 1))
-        win = (np.arange(len(r)) // W).astype(np.int64)
-        segs.append(len(np.unique(win * (1 << 32) + r // 32)))
-    assert max(segs) * (80 + 8) <= RING_RUN_OPTS["record_lds_bytes"], segs
-    return pairs
+    Per run on the panel's own tiles (layout 1: row = position in the site list): tile pairs spanned.  (The model itself is
+    gap_cases.run_structure, shared with the gap cases; it asserts the budget.)"""
+    return run_structure(nr, na, W, RING_RUN_OPTS["windows_per_wave"], RING_RUN_OPTS["record_lds_bytes"])["pairs"]
 
 
 def ring_run(form_opts, ring, alle, nr, na, W, eps, M, targets, unit, what):

@@ -56,9 +56,10 @@ def _truth_factors(oracle, form, eps, M):
     return H.table_factors(lambda r, a: oracle.pdg(eps, M, r, a), M)
 
 
-def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=0, expect=None, spec=None, keep=None):
+def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=0, expect=None, spec=None, keep=None, rows=None):
     """One run of `form`; the parity checks and the bound on three of its comparison individuals.  Returns the truths;
-    `keep` (a dict) receives the comparison individuals and the window tables of the checked ones."""
+    `keep` (a dict) receives the comparison individuals and the window tables of the checked ones.  `rows`: the row_index to
+    upload (nr, na per site of it) instead of np.arange(L); the oracle and hp_ref then get the panel rows alle[rows]."""
     spec = spec or FORMS[form]
     L, N = alle.shape[0], alle.shape[1] // 2
     T = spec["T"]
@@ -69,7 +70,7 @@ def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=
         for k, v in spec["opts"].items():
             eng.set_option(k, v)
         eng.upload_panel(E.pack_alleles_fast(alle), N)
-        eng.upload_sites(np.arange(L), nr, na, W)
+        eng.upload_sites(np.arange(L) if rows is None else rows, nr, na, W)
         if spec["variant"] == 3:
             eng.set_background_order(refids if refids is not None else np.arange(N))
         eng.run(targets, ld=True, bg_count=bg_counts(refids, N), pu_id=pu)
@@ -83,6 +84,8 @@ def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=
     if keep is not None:
         keep.update(targets=targets, windows={i: out[i][1] for i in checked})
     fac = _truth_factors(oracle, form, eps, M)
+    if rows is not None:
+        alle = alle[rows]
     truths = []
     for i in checked:
         t = targets[i]
