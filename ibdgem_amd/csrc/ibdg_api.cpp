@@ -2327,6 +2327,65 @@ int ibdg_window_log2_states(ibdg_ctx *c, double p01, double p02, double p12, uin
     return quiesce(c);
 }
 
+int ibdg_log2_posteriors_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
+                              double expect[3], double *log2_z)
+{
+    char msg[256];
+    double zm = 1.0;
+    int ze = 0;
+    if (!log2_z) return fail(nullptr, "[::] ERROR in ibdg_log2_posteriors_host: NULL log2_z");
+    if (ibdg::log2_posteriors_host(log2_tab, n_win, p01, p02, p12, post, expect, &zm, &ze, msg, sizeof msg))
+        return fail(nullptr, "%s", msg);
+    *log2_z = std::log2(zm) + (double)ze;
+    return 0;
+}
+
+// IBD-state posteriors over win_log2 of the last run (k_log2_posteriors in ibdg_states.hip).  As ibdg_window_log2_states: one
+// launch on the main stream behind join_streams, the copies out and a host wait; st_post / st_pout / st_ptab are scratch of
+// the call (the tables' 4 KB go up with every call: nothing is kept).
+int ibdg_window_log2_posteriors(ibdg_ctx *c, double p01, double p02, double p12, double *post, double *expect, double *log2_z)
+{
+    if (!c) return 1;
+    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: no results (call ibdg_run)");
+    if (!c->wlog.valid) return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: the last run kept no window logs (option log_windows)");
+    if (!expect || !log2_z) return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: NULL %s", expect ? "log2_z" : "expect");
+    int64_t P[3];
+    int bad = 0;
+    if (ibdg::states_penalties(p01, p02, p12, P, &bad)) {
+        static const char *const name[3] = {"p01", "p02", "p12"};
+        return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: %s = %g is not in (0, 1]", name[bad], bad == 0 ? p01 : bad == 1 ? p02 : p12);
+    }
+    const size_t T = c->n_targets, n_win = c->sites.n_win;
+    if (n_win > ibdg::STATES_MAX_WIN)
+        return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: %zu windows, more than the %zu (2^21) of the path", n_win,
+                    ibdg::STATES_MAX_WIN);
+    if (T == 0) return 0;
+    if (n_win == 0) {
+        memset(expect, 0, T * 3 * sizeof *expect);
+        memset(log2_z, 0, T * sizeof *log2_z);
+        return 0;
+    }
+    double a[3];
+    ibdg::post_penalty_weights(P, a);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ensure(c, c->st_post, T * n_win * 24) || ensure(c, c->st_pout, T * 40) || ensure(c, c->st_ptab, 4096))
+        return 1;
+    if (join_streams(c)) return 1;
+    HIP_TRY(c, hipMemcpyAsync(c->st_ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
+    ibdg::launch_log2_posteriors((const double *)c->wlog.win_log2.p, (uint32_t)n_win, (uint32_t)T, a, (const double *)c->st_ptab.p,
+                                 (double *)c->st_post.p, (double *)c->st_pout.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<double> o(T * 5);
+    HIP_TRY(c, hipMemcpyAsync(o.data(), c->st_pout.p, T * 40, hipMemcpyDeviceToHost, c->stream));
+    if (post) HIP_TRY(c, hipMemcpyAsync(post, c->st_post.p, T * n_win * 24, hipMemcpyDeviceToHost, c->stream));
+    if (quiesce(c)) return 1;
+    for (size_t t = 0; t < T; ++t) {
+        expect[3 * t] = o[5 * t], expect[3 * t + 1] = o[5 * t + 1], expect[3 * t + 2] = o[5 * t + 2];
+        log2_z[t] = std::log2(o[5 * t + 3]) + o[5 * t + 4];
+    }
+    return 0;
+}
+
 int ibdg_get_alt_counts(ibdg_ctx *c, size_t first_row, size_t n, uint32_t *out)
 {
     if (!c) return 1;

@@ -399,6 +399,8 @@ struct ibdg_ctx {
     // ibdg_window_log2_states: `from`, then the paths [T][n_win]; the scores [T][n_win][3] (only when asked for); the counts
     // [T][3].  Scratch of one call like the llr_* above: nothing is kept from call to call, so there is nothing to invalidate.
     DevBuf st_path, st_score, st_count;
+    // ibdg_window_log2_posteriors, scratch of one call likewise: beta, then gamma [T][n_win][3]; expect, Z [T][5]; the two tables
+    DevBuf st_post, st_pout, st_ptab;
     size_t n_targets = 0;
     bool have_results = false;
     int res_site_mode = 0;           // the mode the last run's results were produced under
@@ -410,7 +412,7 @@ struct ibdg_ctx {
         release_all({&rt.row_tab, &p2.p2w, &p2.p2c, &p2.p2_tw, &p2.p2_wt, &fb.fragb, &img.wtarget, &img.twords});
         release_all({&wtarget_mt, &twords_mt, &partial, &aimg, &wc_slot, &partial_h, &vals, &order});
         release_all({&targets, &weight, &nrefpanel, &af, &site_ll, &win_ll, &llr_seg, &llr_part, &llr_out, &wlog.win_log2});
-        release_all({&st_path, &st_score, &st_count});
+        release_all({&st_path, &st_score, &st_count, &st_post, &st_pout, &st_ptab});
     }
 };
 

@@ -362,6 +362,13 @@ constexpr uint32_t STATES_MAX_BLOCKS = 1024;
 void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], uint8_t *path,
                         int64_t *score, uint64_t *count, hipStream_t st);
 
+// IBD-state posteriors over win_log2[T][n_win][3] (k_log2_posteriors in ibdg_states.hip, ibdg_window_log2_posteriors; the
+// definition is in ibdg_states.h): the launch of launch_log2_states.  a: the penalty weights (post_penalty_weights); tables: the
+// 512 doubles of post_tables on the device; scr [T][n_win][3]: scratch, then gamma; out [T][5] = expect[3], Z's mantissa, Z's
+// exponent.  One launch on `st`, no atomics.
+void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_targets, const double a[3], const double *tables,
+                            double *scr, double *out, hipStream_t st);
+
 // log2 of the window likelihoods (ibdg_ld_log.hip, option "log_windows"): win_log2[T][n_win][3].
 // k_ld_log: columns 0 and 1 of an --LD run from the layout's tiles, segments, window constants and power tables (what
 // the counting kernels read), the background multiplicities without any comparison individual's exclusion and their sum.

@@ -1,4 +1,5 @@
-// ibdg_states.hip -- IBD-state paths over the log2 window table of the last run (ibdg_window_log2_states): the integer
+// ibdg_states.hip -- IBD-state paths (ibdg_window_log2_states) and posteriors (ibdg_window_log2_posteriors, k_log2_posteriors
+// below) over the log2 window table of the last run.  The paths: the integer
 // (max, +) recurrence of ibdg_states.h, whose host twin is ibdg_states_host.cpp.  Same integers by construction: the
 // emissions are exact products of an fp64 difference, everything behind them is int64 add / compare / select.
 //
@@ -214,6 +215,163 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__
     }
 }
 
+struct PenW {
+    double a[3];      // the weights of P_01, P_02, P_12 (post_penalty_weights)
+};
+
+__device__ __forceinline__ void emission_weights(const double *__restrict__ l, const double *T, double b[3])
+{
+    int64_t e[3];
+    emission(l, e);
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+        b[s] = post_weight(e[s], T, T + 256);
+}
+
+// k_log2_posteriors: the sum-product pass of ibdg_states.h (its steps 1 .. 5 are the numbers below), same launch and blocking
+// as k_log2_states.  scr [T][n_win][3] holds beta_w from step 3 to step 4, which overwrites it with gamma_w: the thread
+// that wrote a row is the one that reads it.  out [T][5] = expect[3], Z's mantissa, Z's exponent (as a double).  The walks of
+// step 2 run in two waves side by side (thread 0 forward, thread 64 backward).  No atomics; the same reads as k_log2_states,
+// three times.
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double *__restrict__ win_log2, uint32_t n_win,
+                                                                    uint32_t n_targets, PenW W, const double *__restrict__ tables,
+                                                                    double *__restrict__ scr, double *__restrict__ out)
+{
+    __shared__ double mat[STATES_THREADS][9];       // 18 KB: B_b
+    __shared__ double fin[STATES_THREADS][3];       // F_b
+    __shared__ double gout[STATES_THREADS][3];      // G_b
+    __shared__ double part[STATES_THREADS][3];
+    __shared__ double T[512];                       // T1, T2
+    __shared__ int mexp[STATES_THREADS], fexp[STATES_THREADS];
+
+    const uint32_t b = threadIdx.x;
+    const uint32_t C = (n_win + STATES_THREADS - 1) / STATES_THREADS;
+    const uint32_t nbk = (n_win + C - 1) / C;
+    const uint64_t w0 = (uint64_t)b * C;
+    const uint64_t w1 = w0 + C < n_win ? w0 + C : n_win;
+    const bool own = b < nbk;
+    const double a[3] = {W.a[0], W.a[1], W.a[2]};
+
+    T[b] = tables[b], T[b + STATES_THREADS] = tables[b + STATES_THREADS];
+    __syncthreads();
+
+    for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
+        const double *tab = win_log2 + (size_t)t * n_win * 3;
+        double *sc = scr + (size_t)t * n_win * 3;
+
+        // 1
+        if (own) {
+            double R[9], bw[3], M[9];
+            int e = 0;
+            emission_weights(tab + 3 * w0, T, bw);
+            if (b == 0) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    R[3 * q] = bw[0], R[3 * q + 1] = bw[1], R[3 * q + 2] = bw[2];
+            } else {
+                post_step_matrix(a, bw, R);
+            }
+            for (uint64_t w = w0 + 1; w < w1; ++w) {
+                emission_weights(tab + 3 * w, T, bw);
+                post_step_matrix(a, bw, M);
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    post_vec_mat(R + 3 * q, M);
+                post_rescale<9>(R, e);
+            }
+#pragma unroll
+            for (int i = 0; i < 9; ++i)
+                mat[b][i] = R[i];
+            mexp[b] = e;
+        }
+        __syncthreads();
+        // 2
+        if (b == 0) {
+            double v[3] = {mat[0][0], mat[0][1], mat[0][2]};
+            int e = mexp[0];
+            for (uint32_t k = 1; k < nbk; ++k) {
+                fin[k][0] = v[0], fin[k][1] = v[1], fin[k][2] = v[2];
+                fexp[k] = e;
+                if (k + 1 < nbk) {
+                    double M[9];
+#pragma unroll
+                    for (int i = 0; i < 9; ++i)
+                        M[i] = mat[k][i];
+                    post_vec_mat(v, M);
+                    e += mexp[k];
+                    post_rescale<3>(v, e);
+                }
+            }
+        } else if (b == 64) {
+            double g[3] = {1.0, 1.0, 1.0};
+            int ge = 0;
+            for (uint32_t k = nbk; k-- > 0;) {
+                gout[k][0] = g[0], gout[k][1] = g[1], gout[k][2] = g[2];
+                if (k > 0) {
+                    double M[9];
+#pragma unroll
+                    for (int i = 0; i < 9; ++i)
+                        M[i] = mat[k][i];
+                    post_mat_vec(M, g);
+                    post_rescale<3>(g, ge);
+                }
+            }
+        }
+        __syncthreads();
+        double acc[3] = {0.0, 0.0, 0.0};
+        if (own) {
+            double bw[3], M[9];
+            // 3
+            double be[3] = {gout[b][0], gout[b][1], gout[b][2]};
+            int ge = 0;
+            for (uint64_t w = w1; w-- > w0;) {
+                sc[3 * w] = be[0], sc[3 * w + 1] = be[1], sc[3 * w + 2] = be[2];
+                if (w > w0) {
+                    emission_weights(tab + 3 * w, T, bw);
+                    post_step_matrix(a, bw, M);
+                    post_mat_vec(M, be);
+                    post_rescale<3>(be, ge);
+                }
+            }
+            // 4
+            double v[3] = {fin[b][0], fin[b][1], fin[b][2]};
+            int e = fexp[b];
+            for (uint64_t w = w0; w < w1; ++w) {
+                emission_weights(tab + 3 * w, T, bw);
+                if (w == 0) {
+                    v[0] = bw[0], v[1] = bw[1], v[2] = bw[2];
+                    e = 0;
+                } else {
+                    post_step_matrix(a, bw, M);
+                    post_vec_mat(v, M);
+                    post_rescale<3>(v, e);
+                }
+                const double p0 = v[0] * sc[3 * w], p1 = v[1] * sc[3 * w + 1], p2 = v[2] * sc[3 * w + 2];
+                const double D = (p0 + p1) + p2;
+                const double g0 = p0 / D, g1 = p1 / D, g2 = p2 / D;
+                sc[3 * w] = g0, sc[3 * w + 1] = g1, sc[3 * w + 2] = g2;
+                acc[0] += g0, acc[1] += g1, acc[2] += g2;
+                if (w + 1 == n_win)
+                    out[(size_t)t * 5 + 3] = D, out[(size_t)t * 5 + 4] = (double)e;
+            }
+        }
+        // 5
+        part[b][0] = acc[0], part[b][1] = acc[1], part[b][2] = acc[2];
+        __syncthreads();
+        for (uint32_t d = STATES_THREADS / 2; d > 0; d >>= 1) {
+            if (b < d) {
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    part[b][s] = part[b][s] + part[b + d][s];
+            }
+            __syncthreads();
+        }
+        if (b < 3)
+            out[(size_t)t * 5 + b] = part[0][b];
+        __syncthreads();       // (LDS is reused by the next individual)
+    }
+}
+
 }  // namespace
 
 void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], uint8_t *path,
@@ -224,6 +382,16 @@ void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targe
     const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
     hipLaunchKernelGGL(k_log2_states, dim3(grid), dim3(STATES_THREADS), 0, st, win_log2, n_win, n_targets, Pen{P[0], P[1], P[2]},
                        path, score, count);
+}
+
+void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_targets, const double a[3], const double *tables,
+                            double *scr, double *out, hipStream_t st)
+{
+    if (n_win == 0 || n_targets == 0)
+        return;
+    const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_log2_posteriors, dim3(grid), dim3(STATES_THREADS), 0, st, win_log2, n_win, n_targets, PenW{{a[0], a[1], a[2]}},
+                       tables, scr, out);
 }
 
 }  // namespace ibdg

@@ -111,4 +111,166 @@ int log2_states_host(const double *tab, size_t n_win, double p01, double p02, do
     return 0;
 }
 
+const double *post_tables()
+{
+    static const struct Tab {
+        double v[512];
+        Tab()
+        {
+            for (int j = 0; j < 256; ++j) {
+                v[j] = std::exp2(j / 256.0);
+                v[256 + j] = std::exp2(j / 65536.0);
+            }
+        }
+    } tab;
+    return tab.v;
+}
+
+void post_penalty_weights(const int64_t P[3], double a[3])
+{
+    const double *T = post_tables();
+    for (int k = 0; k < 3; ++k)
+        a[k] = std::ldexp(T[P[k] >> 8 & 255] * T[256 + (P[k] & 255)], (int)(P[k] >> 16));
+}
+
+static void emission_weights(const double *l, const double *T, double b[3])
+{
+    int64_t e[3];
+    emission(l, e);
+    for (int s = 0; s < 3; ++s)
+        b[s] = post_weight(e[s], T, T + 256);
+}
+
+// The sequence of ibdg_states.h, step for step (its numbers are in the comments); the kernel's threads are the loops over b.
+int log2_posteriors_host(const double *tab, size_t n_win, double p01, double p02, double p12, double *post, double expect[3],
+                         double *z_mant, int *z_exp, char *err, size_t err_len)
+{
+    int64_t P[3];
+    int bad = 0;
+    if (!expect || !z_mant || !z_exp) {
+        snprintf(err, err_len, "[::] ERROR in ibdg_log2_posteriors_host: NULL %s", expect ? "log2_z" : "expect");
+        return 1;
+    }
+    if (n_win && !tab) {
+        snprintf(err, err_len, "[::] ERROR in ibdg_log2_posteriors_host: NULL table");
+        return 1;
+    }
+    if (states_penalties(p01, p02, p12, P, &bad)) {
+        static const char *const name[3] = {"p01", "p02", "p12"};
+        snprintf(err, err_len, "[::] ERROR in ibdg_log2_posteriors_host: %s = %g is not in (0, 1]", name[bad],
+                 bad == 0 ? p01 : bad == 1 ? p02 : p12);
+        return 1;
+    }
+    if (n_win > STATES_MAX_WIN) {
+        snprintf(err, err_len, "[::] ERROR in ibdg_log2_posteriors_host: %zu windows, more than the %zu (2^21) of the path", n_win,
+                 STATES_MAX_WIN);
+        return 1;
+    }
+    expect[0] = expect[1] = expect[2] = 0.0;
+    *z_mant = 1.0, *z_exp = 0;
+    if (n_win == 0)
+        return 0;
+    const double *T = post_tables();
+    double a[3];
+    post_penalty_weights(P, a);
+    std::vector<double> own;
+    if (!post) {
+        own.resize(n_win * 3);
+        post = own.data();
+    }
+    const size_t C = (n_win + POST_BLOCKS - 1) / POST_BLOCKS;
+    const size_t nbk = (n_win + C - 1) / C;
+    std::vector<double> mat(nbk * 9), fin(nbk * 3), gout(nbk * 3);
+    std::vector<int> mexp(nbk), fexp(nbk);
+    // 1
+    for (size_t b = 0; b < nbk; ++b) {
+        const size_t w0 = b * C, w1 = w0 + C < n_win ? w0 + C : n_win;
+        double *R = &mat[9 * b], bw[3], M[9];
+        int e = 0;
+        emission_weights(tab + 3 * w0, T, bw);
+        if (b == 0)
+            for (int q = 0; q < 3; ++q)
+                R[3 * q] = bw[0], R[3 * q + 1] = bw[1], R[3 * q + 2] = bw[2];
+        else
+            post_step_matrix(a, bw, R);
+        for (size_t w = w0 + 1; w < w1; ++w) {
+            emission_weights(tab + 3 * w, T, bw);
+            post_step_matrix(a, bw, M);
+            for (int q = 0; q < 3; ++q)
+                post_vec_mat(R + 3 * q, M);
+            post_rescale<9>(R, e);
+        }
+        mexp[b] = e;
+    }
+    // 2
+    {
+        double v[3] = {mat[0], mat[1], mat[2]};
+        int e = mexp[0];
+        for (size_t k = 1; k < nbk; ++k) {
+            fin[3 * k] = v[0], fin[3 * k + 1] = v[1], fin[3 * k + 2] = v[2];
+            fexp[k] = e;
+            if (k + 1 < nbk) {
+                post_vec_mat(v, &mat[9 * k]);
+                e += mexp[k];
+                post_rescale<3>(v, e);
+            }
+        }
+        double g[3] = {1.0, 1.0, 1.0};
+        int ge = 0;
+        for (size_t k = nbk; k-- > 0;) {
+            gout[3 * k] = g[0], gout[3 * k + 1] = g[1], gout[3 * k + 2] = g[2];
+            if (k > 0) {
+                post_mat_vec(&mat[9 * k], g);
+                post_rescale<3>(g, ge);
+            }
+        }
+    }
+    double part[POST_BLOCKS][3] = {};
+    for (size_t b = 0; b < nbk; ++b) {
+        const size_t w0 = b * C, w1 = w0 + C < n_win ? w0 + C : n_win;
+        double bw[3], M[9];
+        // 3
+        double be[3] = {gout[3 * b], gout[3 * b + 1], gout[3 * b + 2]};
+        int ge = 0;
+        for (size_t w = w1; w-- > w0;) {
+            post[3 * w] = be[0], post[3 * w + 1] = be[1], post[3 * w + 2] = be[2];
+            if (w > w0) {
+                emission_weights(tab + 3 * w, T, bw);
+                post_step_matrix(a, bw, M);
+                post_mat_vec(M, be);
+                post_rescale<3>(be, ge);
+            }
+        }
+        // 4
+        double v[3] = {fin[3 * b], fin[3 * b + 1], fin[3 * b + 2]}, acc[3] = {0.0, 0.0, 0.0};
+        int e = fexp[b];
+        for (size_t w = w0; w < w1; ++w) {
+            emission_weights(tab + 3 * w, T, bw);
+            if (w == 0) {
+                v[0] = bw[0], v[1] = bw[1], v[2] = bw[2];
+                e = 0;
+            } else {
+                post_step_matrix(a, bw, M);
+                post_vec_mat(v, M);
+                post_rescale<3>(v, e);
+            }
+            const double p0 = v[0] * post[3 * w], p1 = v[1] * post[3 * w + 1], p2 = v[2] * post[3 * w + 2];
+            const double D = (p0 + p1) + p2;
+            const double g0 = p0 / D, g1 = p1 / D, g2 = p2 / D;
+            post[3 * w] = g0, post[3 * w + 1] = g1, post[3 * w + 2] = g2;
+            acc[0] += g0, acc[1] += g1, acc[2] += g2;
+            if (w + 1 == n_win)
+                *z_mant = D, *z_exp = e;
+        }
+        part[b][0] = acc[0], part[b][1] = acc[1], part[b][2] = acc[2];
+    }
+    // 5
+    for (int d = POST_BLOCKS / 2; d > 0; d >>= 1)
+        for (int b = 0; b < d; ++b)
+            for (int s = 0; s < 3; ++s)
+                part[b][s] = part[b][s] + part[b + d][s];
+    expect[0] = part[0][0], expect[1] = part[0][1], expect[2] = part[0][2];
+    return 0;
+}
+
 }  // namespace ibdg

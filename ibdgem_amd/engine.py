@@ -53,6 +53,8 @@ SYMBOLS = {
     "ibdg_window_log2_llr_sums": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     "ibdg_log2_states_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
     "ibdg_window_log2_states": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
+    "ibdg_log2_posteriors_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
+    "ibdg_window_log2_posteriors": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
     "ibdg_run_ms": (C.c_int, [_P, C.c_uint, _P]),
@@ -162,6 +164,22 @@ def log2_states_host(log2_tab, p01, p02, p12, want_path=True, want_score=True):
     if rc != 0:
         raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
     return path, score, count
+
+
+def log2_posteriors_host(log2_tab, p01, p02, p12, want_post=True):
+    """Forward-backward IBD-state probabilities of one window table [n_win][3] on the host (ibdg_log2_posteriors_host):
+    (post float64 [n_win][3] or None, expect float64 [3], log2_z float)."""
+    lib = load_library()
+    tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
+    n = tab.shape[0]
+    post = np.zeros((n, 3), dtype=np.float64) if want_post else None
+    expect = np.zeros(3, dtype=np.float64)
+    log2_z = C.c_double(0.0)
+    rc = lib.ibdg_log2_posteriors_host(tab.ctypes.data, n, p01, p02, p12, None if post is None else post.ctypes.data,
+                                       expect.ctypes.data, C.addressof(log2_z))
+    if rc != 0:
+        raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
+    return post, expect, log2_z.value
 
 
 class Engine:
@@ -361,6 +379,17 @@ class Engine:
         self._chk(self.lib.ibdg_window_log2_states(self.ctx, p01, p02, p12, None if path is None else path.ctypes.data,
                                                    None if score is None else score.ctypes.data, count.ctypes.data))
         return path, score, count
+
+    def window_log2_posteriors(self, p01, p02, p12, want_post=True):
+        """Forward-backward IBD-state probabilities of every comparison individual of the last run, on the device
+        (ibdg_window_log2_posteriors): (post float64 [T][n_win][3] or None, expect float64 [T][3], log2_z float64 [T])."""
+        T, n = self.lib.ibdg_num_targets(self.ctx), self.n_windows
+        post = np.zeros((T, n, 3), dtype=np.float64) if want_post else None
+        expect = np.zeros((T, 3), dtype=np.float64)
+        log2_z = np.zeros(T, dtype=np.float64)
+        self._chk(self.lib.ibdg_window_log2_posteriors(self.ctx, p01, p02, p12, None if post is None else post.ctypes.data,
+                                                       expect.ctypes.data, log2_z.ctypes.data))
+        return post, expect, log2_z
 
     def alt_counts(self, first, n):
         out = np.empty(n, dtype=np.uint32)

@@ -64,6 +64,7 @@ static int opt_threads = 0;
 static const char *cache_fn = NULL, *dump_panel_fn = NULL;
 static int opt_stats_only = 0, has_arm = 0;
 static int opt_log_summary = 0;          /* --log-summary: the summary's likelihoods as log2, from the engine's option "log_windows" */
+static int opt_posteriors = 0;           /* --posteriors: with --log-stats --states, the forward-backward probabilities of the states beside the path */
 static int opt_log_stats = 0;            /* --log-stats: --arm-stats and --states from the log2 window table (no underflow), into log* files */
 static int opt_states = 0, has_pen = 0;  /* --states: the IBD-state path of every comparison (hgpath.c), --p01/--p02/--p12 its penalties */
 static double opt_p01 = HG_DEFAULT_P01, opt_p02 = HG_DEFAULT_P02, opt_p12 = HG_DEFAULT_P12;
@@ -78,6 +79,7 @@ static struct option longopts[] = {
     {"states", no_argument, &opt_states, 1},
     {"log-summary", no_argument, &opt_log_summary, 1},
     {"log-stats", no_argument, &opt_log_stats, 1},
+    {"posteriors", no_argument, &opt_posteriors, 1},
     {"p01", required_argument, 0, 1008},
     {"p02", required_argument, 0, 1009},
     {"p12", required_argument, 0, 1010},
@@ -173,6 +175,13 @@ static void usage(int code)
           "                            2^-16 bit: nothing underflows, a window of zeros poisons nothing) and\n"
           "                            <pileup-name>.logibdstates.txt, in place of the three linear files; summed, and\n"
           "                            with --stats-only on one device also traced, on the device\n"
+          "  --posteriors              with --log-stats --states: also the sum over ALL paths of the weights whose best path\n"
+          "                            --log-stats finds (forward-backward, same --p01/--p02/--p12):\n"
+          "                            <out>/<pileup-name>.<individual>.logposteriors.txt, per window the probability of\n"
+          "                            IBD0/1/2 given all windows and the most probable state (the lowest on a tie); and\n"
+          "                            <out>/<pileup-name>.logibdposteriors.txt, per individual the expected windows per\n"
+          "                            state, their fractions and log2 of the paths' total weight, then the totals.  With\n"
+          "                            --stats-only only the second file, on one device computed there\n"
           "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
           "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
           "  --stats-only              with --arm-stats and/or --states: write the armstats / ibdstates file only (no\n"
@@ -1696,6 +1705,7 @@ typedef struct {
     int stats_only;                          /* --stats-only: no window table leaves the device */
     int dev_states;                          /* --log-stats --states --stats-only on one context: the paths are found on the device */
     uint64_t st[3];                          /* ... the individual's windows in IBD0, IBD1, IBD2 (ibdg_window_log2_states) */
+    double po[4];                            /* ... --posteriors: its expected windows per state and log2 Z (ibdg_window_log2_posteriors) */
     FILE *err;                               /* where the pileup's messages go */
     int reported;                            /* a failure was reported here already (not an engine error) */
 } shard_job;
@@ -1720,6 +1730,8 @@ typedef struct {
     size_t arm_cap;
     uint64_t *st_counts;                     /* --log-stats --states: the state counts of the last run's individuals, [T][3] */
     size_t st_cap;
+    double *po_vals;                         /* --posteriors: expect [T][3], then log2 Z [T], of the last run's individuals */
+    size_t po_cap;
     const uint32_t *ahead_of;                /* the batch that has been queued ahead on the device; NULL: none */
 } win_cache;
 static win_cache g_wcache[64];
@@ -1779,6 +1791,16 @@ static void *shard_run(void *arg)
             if (!wc->st_counts || !same_run_size(j) ||
                 ibdg_window_log2_states(j->eng, opt_p01, opt_p02, opt_p12, NULL, NULL, wc->st_counts))
                 return NULL;
+            if (opt_posteriors) {
+                if (wc->po_cap < j->n_targets * 4) {
+                    free(wc->po_vals);
+                    wc->po_vals = malloc(j->n_targets * 4 * sizeof(double));
+                    wc->po_cap = wc->po_vals ? j->n_targets * 4 : 0;
+                }
+                if (!wc->po_vals || ibdg_window_log2_posteriors(j->eng, opt_p01, opt_p02, opt_p12, NULL, wc->po_vals,
+                                                                wc->po_vals + j->n_targets * 3))
+                    return NULL;
+            }
         }
         if (j->stats_only) {
             if (j->next_targets) {                                        /* the next batch runs while the host goes on */
@@ -1823,6 +1845,10 @@ static void *shard_run(void *arg)
         memcpy(j->arm, wc->arm_sums + j->t_local * 8, sizeof j->arm);
     if (j->dev_states)
         memcpy(j->st, wc->st_counts + j->t_local * 3, sizeof j->st);
+    if (j->dev_states && opt_posteriors) {
+        memcpy(j->po, wc->po_vals + j->t_local * 3, 3 * sizeof(double));
+        j->po[3] = wc->po_vals[j->n_targets * 3 + j->t_local];
+    }
     j->wt.n_win = ibdg_num_windows(j->eng);
     if (j->stats_only) {
         j->failed = 0;
@@ -2279,6 +2305,8 @@ typedef struct {
     /* --states */
     FILE *hg;                                   /* the individual's *.hiddengem.txt (NULL with --stats-only); closed by the job */
     size_t *st_count;                           /* the individual's line of ibdstates.txt: windows in IBD0, IBD1, IBD2 */
+    FILE *lp;                                   /* --posteriors: the individual's *.logposteriors.txt (NULL with --stats-only); closed by the job */
+    double *po;                                 /* ... its line of logibdposteriors.txt: expected windows per state, log2 Z */
     hg_path hgp;                                /* the slot's path arrays and text buffer (kept between individuals) */
     char *hg_buf;
     size_t hg_cap;
@@ -2401,6 +2429,36 @@ static int write_states_parallel(FILE *f, const hg_path *h, int threads, char **
  * ibdg_window_log2_states), its scores printed in bits */
 static const char log_hg_header[] = "Segment\tIBD0_LogScore\tIBD1_LogScore\tIBD2_LogScore\tInferred_State\n";
 
+/* --posteriors: the sum-product pass over the same table (ibdg_log2_posteriors_host: the same bytes as the device's
+ * ibdg_window_log2_posteriors) */
+static int posteriors_individual(out_job *o)
+{
+    if (!opt_posteriors)
+        return 0;
+    const size_t n = o->wt.n_win;
+    double *post = o->lp ? malloc((n ? n : 1) * 3 * sizeof *post) : NULL;
+    int bad = o->lp && !post;
+    if (!bad && ibdg_log2_posteriors_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, post, o->po, o->po + 3)) {
+        fprintf(o->err, "%s\n", ibdg_last_error(NULL));
+        bad = 1;
+    }
+    if (!bad && o->lp) {
+        bad = fputs("Segment\tPost_IBD0\tPost_IBD1\tPost_IBD2\tMax_State\n", o->lp) < 0;
+        for (size_t w = 0; w < n && !bad; ++w) {
+            const double *g = post + 3 * w;
+            int m = g[1] > g[0] ? 1 : 0;
+            m = g[2] > g[m] ? 2 : m;
+            bad = fprintf(o->lp, "%d\t%.6f\t%.6f\t%.6f\t%d\n", (int)(w + 1), g[0], g[1], g[2], m) < 0;
+        }
+    }
+    if (o->lp) {
+        bad = fclose(o->lp) != 0 || bad;
+        o->lp = NULL;
+    }
+    free(post);
+    return bad;
+}
+
 static int log_states_individual(out_job *o)
 {
     const size_t n = o->wt.n_win;
@@ -2433,7 +2491,7 @@ static int log_states_individual(out_job *o)
     }
     free(path);
     free(score);
-    return bad;
+    return posteriors_individual(o) || bad;
 }
 
 /* 0: the path is found, counted for ibdstates.txt and (o->hg) written and its file closed */
@@ -2476,7 +2534,8 @@ static void *output_individual(void *arg)
                o->wt.n_win, o->cull_p);
     else {
         if ((!opt_summary_only && ftruncate(fileno(tab), 0) != 0) || ftruncate(fileno(sum), 0) != 0 ||
-            (o->hg && ftruncate(fileno(o->hg), 0) != 0) || (o->lsum && ftruncate(fileno(o->lsum), 0) != 0)) {
+            (o->hg && ftruncate(fileno(o->hg), 0) != 0) || (o->lsum && ftruncate(fileno(o->lsum), 0) != 0) ||
+            (o->lp && ftruncate(fileno(o->lp), 0) != 0)) {
             fprintf(o->err, "[::] ERROR in compare_impute(): Cannot empty the output files of %s.\n", o->tname);
             return NULL;
         }
@@ -2867,6 +2926,9 @@ typedef struct {
     size_t *st_res;                 /* --states: per individual the windows in IBD0, IBD1, IBD2; the run's ibdstates.txt */
     FILE *st_file;
     char *st_fn;
+    double *po_res;                 /* --posteriors: per individual the expected windows in IBD0, IBD1, IBD2 and log2 Z; the run's logibdposteriors.txt */
+    FILE *po_file;
+    char *po_fn;
     double *site_slot[OUT_SLOTS];   /* the per-site array of each output slot */
     uint32_t *c_row;                /* dev_v: the candidates as the engine takes them */
     uint8_t *c_nr, *c_na;
@@ -2945,6 +3007,16 @@ static int run_begin(pile_run *r)
         if (!(r->st_file = fopen(r->st_fn, "w")))
             SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->st_fn);
         pj_add_file(r->pj, r->st_fn);
+    }
+    if (opt_posteriors) {
+        r->po_res = calloc(g_targets.n + 1, 4 * sizeof(double));
+        if (!r->po_res)
+            SFAIL("[::] ERROR: out of memory.\n");
+        if (asprintf(&r->po_fn, "%s/%s.logibdposteriors.txt", g_out_dir, r->pj->name) < 0)
+            return r->po_fn = NULL, 1;
+        if (!(r->po_file = fopen(r->po_fn, "w")))
+            SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->po_fn);
+        pj_add_file(r->pj, r->po_fn);
     }
     r->arm_res = r->arm_on ? malloc((g_targets.n + 1) * 4 * sizeof(double)) : NULL;
     if (r->arm_on && !r->arm_res)
@@ -3330,6 +3402,8 @@ static int windows_on_engine(pile_run *r)
     if (r->dev_states)
         for (int k = 0; k < 3; ++k)
             r->st_res[3 * r->ti + k] = (size_t)jobs[0].st[k];
+    if (r->dev_states && opt_posteriors)
+        memcpy(r->po_res + 4 * r->ti, jobs[0].po, sizeof jobs[0].po);
     if (r->tables_stay)                      /* no window table left the device */
         return 0;
     tables_gather(r, jobs);
@@ -3383,7 +3457,7 @@ static FILE *out_file_open(pile_run *r, const char *kind, int to_null, char **fn
 static int outputs_open(pile_run *r, out_job *o)
 {
     char *tab_fn, *sum_fn;
-    o->hg = o->lsum = NULL;
+    o->hg = o->lsum = o->lp = NULL;
     if (opt_plan || opt_stats_only) {         /* (--stats-only --states: the table is here for its path alone) */
         o->tab = o->sum = opt_plan ? stdout : NULL;
         return 0;
@@ -3396,7 +3470,8 @@ static int outputs_open(pile_run *r, out_job *o)
     free(tab_fn);
     free(sum_fn);
     return !o->tab || !o->sum || (opt_log_summary && !(o->lsum = out_file_open(r, "logsummary", 0, NULL))) ||
-           (opt_states && !(o->hg = out_file_open(r, opt_log_stats ? "loghiddengem" : "hiddengem", 0, NULL)));
+           (opt_states && !(o->hg = out_file_open(r, opt_log_stats ? "loghiddengem" : "hiddengem", 0, NULL))) ||
+           (opt_posteriors && !(o->lp = out_file_open(r, "logposteriors", 0, NULL)));
 }
 
 /* everything the individual's files are made of goes to its slot's job, the window table with it; the job runs beside the
@@ -3419,6 +3494,7 @@ static int output_start(pile_run *r)
     memset(&r->wt, 0, sizeof r->wt);
     o->sq = pj->name; o->err = r->err;
     o->st_count = r->st_res ? r->st_res + 3 * r->ti : NULL;
+    o->po = r->po_res ? r->po_res + 4 * r->ti : NULL;
     if (outputs_open(r, o))
         return 1;
     const int threads = all_threads();
@@ -3482,6 +3558,38 @@ static int run_end(pile_run *r)
             SFAIL("[::] ERROR writing '%s'.\n", r->st_fn);
         phase("IBD-state fractions file");
     }
+    if (opt_posteriors) {
+        /* likewise, laid out like the fractions file: the expected windows per state where that one has counts, and log2 Z */
+        double total[3] = {0.0, 0.0, 0.0};
+        size_t total_n = 0;
+        fprintf(r->po_file, "# ID\tN_SEGMENTS\tE_IBD0\tE_IBD1\tE_IBD2\tFRAC_IBD0\tFRAC_IBD1\tFRAC_IBD2\tLOG2_Z\n");
+        for (size_t ti = 0; ti < targets.n; ++ti) {
+            const double *e = r->po_res + 4 * ti;
+            const size_t n = r->st_res[3 * ti] + r->st_res[3 * ti + 1] + r->st_res[3 * ti + 2];
+            fprintf(r->po_file, "%s\t%zu\t%.3f\t%.3f\t%.3f", g_ids.names[targets.idx[ti]], n, e[0], e[1], e[2]);
+            for (int k = 0; k < 3; ++k) {
+                if (n)
+                    fprintf(r->po_file, "\t%.6f", e[k] / (double)n);
+                else
+                    fputs("\tnan", r->po_file);
+                total[k] += e[k];
+            }
+            fprintf(r->po_file, "\t%.6f\n", e[3]);
+            total_n += n;
+        }
+        fprintf(r->po_file, "# Total segments = %zu\n", total_n);
+        for (int k = 0; k < 3; ++k) {
+            if (total_n)
+                fprintf(r->po_file, "# Total E_IBD%d = %.3f (%.3f %%)\n", k, total[k], total[k] / (double)total_n * 100);
+            else
+                fprintf(r->po_file, "# Total E_IBD%d = %.3f (nan %%)\n", k, total[k]);
+        }
+        FILE *f = r->po_file;
+        r->po_file = NULL;
+        if (fclose(f) != 0)
+            SFAIL("[::] ERROR writing '%s'.\n", r->po_fn);
+        phase("IBD-state posteriors file");
+    }
     return 0;
 }
 
@@ -3491,8 +3599,10 @@ static void run_release(pile_run *r)
 {
     site_list *sl = &r->sl;
     free(r->st_fn); free(r->st_res); free(sl->row_pre); free(sl->row_pre_off);
-    r->st_fn = sl->row_pre = NULL;
+    free(r->po_fn); free(r->po_res);
+    r->st_fn = r->po_fn = sl->row_pre = NULL;
     r->st_res = NULL;
+    r->po_res = NULL;
     sl->row_pre_off = NULL;
     if (!g_list_mode)
         return;
@@ -3559,6 +3669,8 @@ fail:
     outs_settle_one(outs, 1);
     if (r.st_file)
         fclose(r.st_file);                /* (opened empty, left empty) */
+    if (r.po_file)
+        fclose(r.po_file);
     run_release(&r);
     return 1;
 }
@@ -3691,6 +3803,8 @@ int main(int argc, char **argv)
     if (opt_log_summary && opt_stats_only) { fprintf(stderr, "[::] ERROR: --log-summary writes files --stats-only leaves out; use one of them.\n"); exit(1); }
     if (opt_log_stats && opt_plan) { fprintf(stderr, "[::] ERROR: --log-stats writes files --plan does not make; use one of them.\n"); exit(1); }
     if (opt_log_stats && !has_arm && !opt_states) { fprintf(stderr, "[::] ERROR: --log-stats needs --arm-stats START,END and/or --states: it says where their numbers come from.\n"); exit(1); }
+    if (opt_posteriors && opt_plan) { fprintf(stderr, "[::] ERROR: --posteriors writes files --plan does not make; use one of them.\n"); exit(1); }
+    if (opt_posteriors && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --posteriors needs --log-stats and --states: it is the sum over all paths of the weights whose best path they find, with their --p01, --p02, --p12.\n"); exit(1); }
     if (opt_log_stats && opt_states) {
         const double pen[3] = {opt_p01, opt_p02, opt_p12};
         static const char *const pen_name[3] = {"--p01", "--p02", "--p12"};

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define IBDG_ABI_VERSION 5   /* (still 5, additions only: option log_windows with ibdg_get_window_log2, ibdg_get_window_log2_all -- window likelihoods as logs that do not underflow; ibdg_upload_candidates, ibdg_num_candidates, ibdg_select_variable_sites, ibdg_get_site_candidates -- the -v site lists made on the device.)  5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
+#define IBDG_ABI_VERSION 5   /* (still 5, additions only: ibdg_log2_posteriors_host, ibdg_window_log2_posteriors -- forward-backward IBD-state probabilities over the log2 table; option log_windows with ibdg_get_window_log2, ibdg_get_window_log2_all -- window likelihoods as logs that do not underflow; ibdg_upload_candidates, ibdg_num_candidates, ibdg_select_variable_sites, ibdg_get_site_candidates -- the -v site lists made on the device.)  5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
                               * longer what a sparse pileup gets.  3: options site_results, stage_workers; ibdg_get_site_af
                               * computes on demand; ibdg_last_run_ms out[4] is 0 */
 
@@ -253,6 +253,24 @@ int ibdg_log2_states_host(const double *log2_tab, size_t n_win, double p01, doub
  * more than 2^21 windows, NULL count. */
 int ibdg_window_log2_states(ibdg_ctx *ctx, double p01, double p02, double p12, uint8_t *path, int64_t *score,
                             uint64_t *count);
+/* The sum-product companion of ibdg_log2_states_host: IBD-state posteriors of one window table.  The weights are the path's own
+ * integers: an emission e_s or a penalty P (quanta of 2^-16 bit, <= 0) weighs 2^(x / 65536), formed as ldexp(T1[j] * T2[i], k) for
+ * x = 65536 k + 256 j + i from two 256-entry tables of exp2 made once on the host; an emission weight below 2^-1000 is 0, a
+ * window's best state weighs exactly 1.  weight(path) = prod_w b_w[path_w] * prod_{w >= 1} a[path_{w-1}][path_w], Z its sum over
+ * all paths; post[n_win][3] (may be NULL) = P(state at window w | all windows), expect[3] = its sums over the windows (expected
+ * windows per state), *log2_z = log2 Z.  fp64 sums and products with an integer exponent carried beside every vector, so
+ * nothing leaves the double range at any depth or length; the order of the operations is fixed (ibdgem_amd/csrc/ibdg_states.h)
+ * and is the device's.  Needs no device.  n_win = 0: expect = 0, log2_z = 0.  Errors (ibdg_last_error(NULL)): a penalty outside
+ * (0, 1] or NaN, n_win > 2^21, NULL expect or log2_z. */
+int ibdg_log2_posteriors_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
+                              double expect[3], double *log2_z);
+/* The same for every comparison individual of the last ibdg_run, on the device, over its log2 table (option "log_windows"):
+ * post[T][n_win][3] (may be NULL: then 40 bytes per individual leave the device), expect[T][3], log2_z[T].  The same bytes as
+ * ibdg_log2_posteriors_host on ibdg_get_window_log2's table: the same operations in the same order, no atomics.  Same waits as
+ * ibdg_get_window_log2; returns with the outputs in host memory.  Errors: no results, the last ibdg_run made with the option
+ * off, a penalty out of range, more than 2^21 windows, NULL expect or log2_z. */
+int ibdg_window_log2_posteriors(ibdg_ctx *ctx, double p01, double p02, double p12, double *post, double *expect,
+                                double *log2_z);
 /* Alt-allele count of panel rows [first_row, first_row+n): out[n] (for tests). */
 int ibdg_get_alt_counts(ibdg_ctx *ctx, size_t first_row, size_t n, uint32_t *out);
 
