@@ -7,6 +7,8 @@
 #include "ibdg_kernels.h"
 #include "ibdg_states.h"
 
+static_assert(sizeof(ibdg_segment) == 56, "ibdg_segment has no padding");
+
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
@@ -2065,6 +2067,7 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     if (!c->sites.sites_valid) return fail(c, "[::] ERROR in ibdg_run: no sites uploaded");
     if (T == 0 || !targets) return fail(c, "[::] ERROR in ibdg_run: no targets");
     if (T > 65535) return fail(c, "[::] ERROR in ibdg_run: at most 65535 targets per call");
+    c->seg.valid = false;                    // (the paths ibdg_get_log2_segments would read belong to the run before)
     for (size_t t = 0; t < T; ++t)
         if (targets[t] >= c->pan.n_ids)
             return fail(c, "[::] ERROR in ibdg_run: target %u is not a panel individual (n_ids=%u)", targets[t],
@@ -2315,6 +2318,7 @@ int ibdg_window_log2_states(ibdg_ctx *c, double p01, double p02, double p12, uin
         return 0;
     }
     HIP_TRY(c, hipSetDevice(c->device));
+    c->seg.valid = false;                    // (st_path is rewritten)
     if (ensure(c, c->st_path, T * n_win) || ensure(c, c->st_count, T * 24) || (score && ensure(c, c->st_score, T * n_win * 24)))
         return 1;
     if (join_streams(c)) return 1;
@@ -2368,6 +2372,7 @@ int ibdg_window_log2_posteriors(ibdg_ctx *c, double p01, double p02, double p12,
     double a[3];
     ibdg::post_penalty_weights(P, a);
     HIP_TRY(c, hipSetDevice(c->device));
+    c->seg.valid = false;                    // (st_post is rewritten)
     if (ensure(c, c->st_post, T * n_win * 24) || ensure(c, c->st_pout, T * 40) || ensure(c, c->st_ptab, 4096))
         return 1;
     if (join_streams(c)) return 1;
@@ -2384,6 +2389,123 @@ int ibdg_window_log2_posteriors(ibdg_ctx *c, double p01, double p02, double p12,
         log2_z[t] = std::log2(o[5 * t + 3]) + o[5 * t + 4];
     }
     return 0;
+}
+
+int ibdg_log2_segments_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, int with_post,
+                            const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg,
+                            uint64_t summary[12])
+{
+    char msg[256];
+    if (ibdg::log2_segments_host(log2_tab, n_win, p01, p02, p12, with_post, pos_first, pos_last, seg, seg_cap, n_seg, summary, msg,
+                                 sizeof msg))
+        return fail(nullptr, "%s", msg);
+    return 0;
+}
+
+// The segments of the paths over win_log2 of the last run (k_log2_segments_count in ibdg_states.hip).  As its two neighbours: on
+// the main stream behind join_streams -- the states kernel, with with_post the posteriors kernel, the count kernel --, the copy
+// out and a host wait.  st_path and st_post stay as they are for ibdg_get_log2_segments (c->seg).
+int ibdg_window_log2_segments(ibdg_ctx *c, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,
+                              const uint64_t *pos_last, uint64_t *n_seg, uint64_t *summary)
+{
+    if (!c) return 1;
+    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_window_log2_segments: no results (call ibdg_run)");
+    if (!c->wlog.valid) return fail(c, "[::] ERROR in ibdg_window_log2_segments: the last run kept no window logs (option log_windows)");
+    if (!n_seg || !summary) return fail(c, "[::] ERROR in ibdg_window_log2_segments: NULL %s", n_seg ? "summary" : "n_seg");
+    if (!pos_first != !pos_last)
+        return fail(c, "[::] ERROR in ibdg_window_log2_segments: %s without %s", pos_first ? "pos_first" : "pos_last",
+                    pos_first ? "pos_last" : "pos_first");
+    int64_t P[3];
+    int bad = 0;
+    if (ibdg::states_penalties(p01, p02, p12, P, &bad)) {
+        static const char *const name[3] = {"p01", "p02", "p12"};
+        return fail(c, "[::] ERROR in ibdg_window_log2_segments: %s = %g is not in (0, 1]", name[bad], bad == 0 ? p01 : bad == 1 ? p02 : p12);
+    }
+    const size_t T = c->n_targets, n_win = c->sites.n_win;
+    if (n_win > ibdg::STATES_MAX_WIN)
+        return fail(c, "[::] ERROR in ibdg_window_log2_segments: %zu windows, more than the %zu (2^21) of the path", n_win,
+                    ibdg::STATES_MAX_WIN);
+    for (size_t w = 0; pos_first && w < n_win; ++w)
+        if (pos_last[w] < pos_first[w])
+            return fail(c, "[::] ERROR in ibdg_window_log2_segments: window %zu ends at %llu, before its start %llu", w,
+                        (unsigned long long)pos_last[w], (unsigned long long)pos_first[w]);
+    c->seg.valid = false;
+    c->seg.with_post = with_post != 0;
+    c->seg.n_seg.assign(T, 0);
+    if (T == 0) return 0;
+    memset(n_seg, 0, T * sizeof *n_seg);
+    memset(summary, 0, T * 12 * sizeof *summary);
+    if (n_win == 0) {
+        c->seg.valid = true;
+        return 0;
+    }
+    double a[3];
+    ibdg::post_penalty_weights(P, a);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ensure(c, c->st_path, T * n_win) || ensure(c, c->st_count, T * 24) || ensure(c, c->st_sout, T * 104) ||
+        (pos_first && ensure(c, c->st_spos, n_win * 16)) ||
+        (with_post && (ensure(c, c->st_post, T * n_win * 24) || ensure(c, c->st_pout, T * 40) || ensure(c, c->st_ptab, 4096))))
+        return 1;
+    if (join_streams(c)) return 1;
+    const uint64_t *d_first = nullptr, *d_last = nullptr;
+    if (pos_first) {
+        d_first = (const uint64_t *)c->st_spos.p, d_last = d_first + n_win;
+        HIP_TRY(c, hipMemcpyAsync(c->st_spos.p, pos_first, n_win * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync((char *)c->st_spos.p + n_win * 8, pos_last, n_win * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    ibdg::launch_log2_states((const double *)c->wlog.win_log2.p, (uint32_t)n_win, (uint32_t)T, P, (uint8_t *)c->st_path.p, nullptr,
+                             (uint64_t *)c->st_count.p, c->stream);
+    if (with_post) {
+        HIP_TRY(c, hipMemcpyAsync(c->st_ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
+        ibdg::launch_log2_posteriors((const double *)c->wlog.win_log2.p, (uint32_t)n_win, (uint32_t)T, a, (const double *)c->st_ptab.p,
+                                     (double *)c->st_post.p, (double *)c->st_pout.p, c->stream);
+    }
+    ibdg::launch_log2_segments_count((const uint8_t *)c->st_path.p, (uint32_t)n_win, (uint32_t)T, d_first, d_last,
+                                     (uint64_t *)c->st_sout.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint64_t> o(T * 13);
+    HIP_TRY(c, hipMemcpyAsync(o.data(), c->st_sout.p, T * 104, hipMemcpyDeviceToHost, c->stream));
+    if (quiesce(c)) return 1;
+    for (size_t t = 0; t < T; ++t) {
+        memcpy(summary + 12 * t, &o[13 * t], 96);
+        c->seg.n_seg[t] = n_seg[t] = o[13 * t + 12];
+        if (n_seg[t] == 0 || n_seg[t] > n_win)          // (what sizes the record buffer: never taken on trust)
+            return fail(c, "[::] ERROR in ibdg_window_log2_segments: individual %zu has %llu segments in %zu windows", t,
+                        (unsigned long long)n_seg[t], n_win);
+    }
+    c->seg.valid = true;
+    return 0;
+}
+
+// The records of that call (k_log2_segments_write): the offsets go up, the kernel writes the individuals' records back to
+// back into a buffer of their total, one copy out and a host wait.
+int ibdg_get_log2_segments(ibdg_ctx *c, ibdg_segment *seg, size_t cap)
+{
+    if (!c) return 1;
+    if (!c->have_results || !c->seg.valid)
+        return fail(c, "[::] ERROR in ibdg_get_log2_segments: no ibdg_window_log2_segments call since the last ibdg_run");
+    const size_t T = c->seg.n_seg.size(), n_win = c->sites.n_win;
+    std::vector<uint64_t> off(T ? T : 1);
+    uint64_t total = 0;
+    for (size_t t = 0; t < T; ++t) {
+        off[t] = total;
+        total += c->seg.n_seg[t];
+    }
+    if (cap < total)
+        return fail(c, "[::] ERROR in ibdg_get_log2_segments: room for %zu records, %llu are there", cap, (unsigned long long)total);
+    if (total == 0) return 0;
+    if (!seg) return fail(c, "[::] ERROR in ibdg_get_log2_segments: NULL seg");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ensure(c, c->st_soff, T * 8) || ensure(c, c->st_seg, total * sizeof(ibdg_segment)))
+        return 1;
+    if (join_streams(c)) return 1;
+    HIP_TRY(c, hipMemcpyAsync(c->st_soff.p, off.data(), T * 8, hipMemcpyHostToDevice, c->stream));
+    ibdg::launch_log2_segments_write((const double *)c->wlog.win_log2.p, (const uint8_t *)c->st_path.p,
+                                     c->seg.with_post ? (const double *)c->st_post.p : nullptr, (uint32_t)n_win, (uint32_t)T,
+                                     (const uint64_t *)c->st_soff.p, (ibdg_segment *)c->st_seg.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(seg, c->st_seg.p, total * sizeof(ibdg_segment), hipMemcpyDeviceToHost, c->stream));
+    return quiesce(c);
 }
 
 int ibdg_get_alt_counts(ibdg_ctx *c, size_t first_row, size_t n, uint32_t *out)

@@ -401,6 +401,15 @@ struct ibdg_ctx {
     DevBuf st_path, st_score, st_count;
     // ibdg_window_log2_posteriors, scratch of one call likewise: beta, then gamma [T][n_win][3]; expect, Z [T][5]; the two tables
     DevBuf st_post, st_pout, st_ptab;
+    // ibdg_window_log2_segments: the windows' positions [2][n_win], the summaries and counts [T][13]; ibdg_get_log2_segments: the
+    // record offsets [T], the records.  The one thing of this group that is kept from call to call: `seg` says that st_path (and
+    // st_post) hold what the last ibdg_window_log2_segments left, for ibdg_get_log2_segments to read.  It holds only while
+    // have_results does, and is dropped by ibdg_run and by the two other calls that write st_path or st_post.
+    DevBuf st_spos, st_sout, st_soff, st_seg;
+    struct SegCall {
+        bool valid = false, with_post = false;
+        std::vector<uint64_t> n_seg;     // per individual of that call
+    } seg;
     size_t n_targets = 0;
     bool have_results = false;
     int res_site_mode = 0;           // the mode the last run's results were produced under
@@ -412,7 +421,7 @@ struct ibdg_ctx {
         release_all({&rt.row_tab, &p2.p2w, &p2.p2c, &p2.p2_tw, &p2.p2_wt, &fb.fragb, &img.wtarget, &img.twords});
         release_all({&wtarget_mt, &twords_mt, &partial, &aimg, &wc_slot, &partial_h, &vals, &order});
         release_all({&targets, &weight, &nrefpanel, &af, &site_ll, &win_ll, &llr_seg, &llr_part, &llr_out, &wlog.win_log2});
-        release_all({&st_path, &st_score, &st_count, &st_post, &st_pout, &st_ptab});
+        release_all({&st_path, &st_score, &st_count, &st_post, &st_pout, &st_ptab, &st_spos, &st_sout, &st_soff, &st_seg});
     }
 };
 

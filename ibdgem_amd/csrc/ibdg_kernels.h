@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct ibdg_segment;        // include/ibdgem_hip.h
+
 namespace ibdg {
 
 // per-row values + window products (k_rows_windows)
@@ -368,6 +370,16 @@ void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targe
 // exponent.  One launch on `st`, no atomics.
 void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_targets, const double a[3], const double *tables,
                             double *scr, double *out, hipStream_t st);
+
+// The segments of the paths (k_log2_segments_count, k_log2_segments_write in ibdg_states.hip; ibdg_window_log2_segments,
+// ibdg_get_log2_segments; the definition is in ibdg_states.h): the launch of launch_log2_states.  path [T][n_win] as
+// launch_log2_states left it; pos_first, pos_last [n_win] or both NULL; out [T][13] = the summary's 12 words, the number of
+// segments.  write: post [T][n_win][3] as launch_log2_posteriors left it, or NULL; off [T] = the exclusive sums of the counts;
+// seg: room for their total.  One launch each on `st`, no atomics.
+void launch_log2_segments_count(const uint8_t *path, uint32_t n_win, uint32_t n_targets, const uint64_t *pos_first,
+                                const uint64_t *pos_last, uint64_t *out, hipStream_t st);
+void launch_log2_segments_write(const double *win_log2, const uint8_t *path, const double *post, uint32_t n_win, uint32_t n_targets,
+                                const uint64_t *off, ibdg_segment *seg, hipStream_t st);
 
 // log2 of the window likelihoods (ibdg_ld_log.hip, option "log_windows"): win_log2[T][n_win][3].
 // k_ld_log: columns 0 and 1 of an --LD run from the layout's tiles, segments, window constants and power tables (what

@@ -13,6 +13,8 @@
 // integers for any blocking of the windows.  n_win <= 2^21 keeps |score| < 2^62 (a step moves a score by at most 2^40
 // down -- its own state's emission -- and never up).
 #pragma once
+#include "../../include/ibdgem_hip.h"      // ibdg_segment
+
 #include <stddef.h>
 #include <stdint.h>
 
@@ -147,5 +149,29 @@ void post_penalty_weights(const int64_t P[3], double a[3]);
 // for n_win = 0)
 int log2_posteriors_host(const double *tab, size_t n_win, double p01, double p02, double p12, double *post, double expect[3],
                          double *z_mant, int *z_exp, char *err, size_t err_len);
+
+// ---- segments: the maximal runs of one state along the path, with what backs each of them -------------------
+//
+// Inputs: path[n_win] of 4.8; the emissions e_w[s] (the integers above); optionally gamma_w[s] of 4.9; optionally the positions
+// pos_first[w] <= pos_last[w] of every window's first and last site.  Window w starts a segment iff w == 0 or path[w] !=
+// path[w - 1]; segment k (0-based, in window order) runs from its start f to the window before the next start, or to n_win - 1.
+//   record   ibdg_segment (include/ibdgem_hip.h, 56 bytes): first = f, n_win = its windows, state = path[f], reserved = 0;
+//            e[s] = sum of e_w[s] over its windows (|e_w[s]| <= 2^40, n_win <= 2^21: |sum| <= 2^61; a window whose emission is
+//            (0, 0, 0) adds nothing); post_q = sum of q_w = llrint(gamma_w[state] * 2^32) (the product with a power of two is
+//            exact, ties to even: llrint in the default rounding mode here, __double2ll_rn on the device; q_w <= 2^32, the sum
+//            <= 2^53); post_min = min of gamma_w[state] (gamma is never NaN: no NaN rule).  post_q = 0 and post_min = 0.0 when the
+//            posteriors are not asked for
+//   summary  uint64[12] per individual, for s = 0, 1, 2: [s] n_seg[s], [3 + s] longest_win[s] (the largest n_win of a segment
+//            in state s, 0 if none), [6 + s] bp[s] = sum over the state's segments of span = pos_last[last window] -
+//            pos_first[f] + 1 (modulo 2^64), [9 + s] longest_bp[s]; the two bp groups are 0 without positions
+// Every one of these is an integer +, a max or an fp64 min of values that are themselves the same bits on either side:
+// associative and exact, so the result does not depend on how the windows are cut into blocks.  That is why the twin walks
+// the windows once in order, the kernels cut them into 256 blocks, and neither needs an order rule as the posteriors do.
+constexpr double SEG_POST_Q = 4294967296.0;      // 2^32: q_w = rint(gamma * 2^32)
+
+// the host twin (ibdg_log2_segments_host): seg [seg_cap] or NULL, *n_seg the true count, summary[12]
+int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,
+                       const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err,
+                       size_t err_len);
 
 }  // namespace ibdg

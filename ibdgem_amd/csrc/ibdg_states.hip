@@ -1,5 +1,6 @@
-// ibdg_states.hip -- IBD-state paths (ibdg_window_log2_states) and posteriors (ibdg_window_log2_posteriors, k_log2_posteriors
-// below) over the log2 window table of the last run.  The paths: the integer
+// ibdg_states.hip -- IBD-state paths (ibdg_window_log2_states), posteriors (ibdg_window_log2_posteriors, k_log2_posteriors
+// below) and segments (ibdg_window_log2_segments, ibdg_get_log2_segments: k_log2_segments_count, k_log2_segments_write at
+// the end) over the log2 window table of the last run.  The paths: the integer
 // (max, +) recurrence of ibdg_states.h, whose host twin is ibdg_states_host.cpp.  Same integers by construction: the
 // emissions are exact products of an fp64 difference, everything behind them is int64 add / compare / select.
 //
@@ -372,6 +373,240 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double
     }
 }
 
+// ---- segments (ibdg_states.h): same launch and blocking as the two kernels above -------------------------------
+// A window starts a segment iff its state differs from the window's before it (window 0 always: 3 stands for "no state").
+
+// k_log2_segments_count: out [T][13] = the summary's 12 words, then the individual's number of segments.  path as
+// k_log2_states left it.  Every thread finds the first start among its windows; a suffix minimum over the 256 blocks in LDS gives
+// each the next start behind its block (n_win if none), so a backward walk over its own windows knows where every segment
+// that starts there ends.  Sums and maxima by shuffles, then over the four waves in LDS.  No atomics.
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_count(const uint8_t *__restrict__ path, uint32_t n_win,
+                                                                        uint32_t n_targets, const uint64_t *__restrict__ pos_first,
+                                                                        const uint64_t *__restrict__ pos_last,
+                                                                        uint64_t *__restrict__ out)
+{
+    __shared__ uint32_t nxt[2][STATES_THREADS];
+    __shared__ uint64_t red[STATES_THREADS / 64][12];
+
+    const uint32_t b = threadIdx.x;
+    const uint32_t C = (n_win + STATES_THREADS - 1) / STATES_THREADS;
+    const uint32_t nbk = (n_win + C - 1) / C;
+    const uint32_t w0 = b * C < n_win ? b * C : n_win;
+    const uint32_t w1 = w0 + C < n_win ? w0 + C : n_win;
+    const bool own = b < nbk;
+
+    for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
+        const uint8_t *pt = path + (size_t)t * n_win;
+        uint32_t fs = n_win;
+        if (own) {
+            unsigned prev = b == 0 ? 3u : pt[w0 - 1];
+            for (uint32_t w = w0; w < w1; ++w) {
+                const unsigned s = pt[w];
+                if (s != prev) {
+                    fs = w;
+                    break;
+                }
+                prev = s;
+            }
+        }
+        nxt[0][b] = fs;
+        __syncthreads();
+        // nxt[..][k] becomes the first start in block k or behind it
+        int cur = 0;
+        for (uint32_t d = 1; d < STATES_THREADS; d <<= 1) {
+            uint32_t m = nxt[cur][b];
+            if (b + d < STATES_THREADS) {
+                const uint32_t o = nxt[cur][b + d];
+                m = o < m ? o : m;
+            }
+            nxt[cur ^ 1][b] = m;
+            cur ^= 1;
+            __syncthreads();
+        }
+        uint64_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (own) {
+            uint32_t end = b + 1 < STATES_THREADS ? nxt[cur][b + 1] : n_win;     // where the segment at hand ends (exclusive)
+            unsigned s = pt[w1 - 1];
+            for (uint32_t w = w1; w-- > w0;) {
+                const unsigned p = w == 0 ? 3u : pt[w - 1];
+                if (p != s) {
+                    const uint64_t len = end - w;
+                    const uint64_t span = pos_first ? pos_last[end - 1] - pos_first[w] + 1 : 0;
+#pragma unroll
+                    for (unsigned k = 0; k < 3; ++k) {
+                        const bool is = s == k;
+                        v[k] += is;
+                        v[3 + k] = is && len > v[3 + k] ? len : v[3 + k];
+                        v[6 + k] += is ? span : 0;
+                        v[9 + k] = is && span > v[9 + k] ? span : v[9 + k];
+                    }
+                    end = w;
+                }
+                s = p;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            for (int d = 32; d > 0; d >>= 1) {
+                const uint64_t o = __shfl_down((unsigned long long)v[i], d, 64);
+                v[i] = (i / 3 & 1) ? (o > v[i] ? o : v[i]) : v[i] + o;
+            }
+            if ((b & 63) == 0)
+                red[b >> 6][i] = v[i];
+        }
+        __syncthreads();
+        if (b < 13) {
+            uint64_t r = 0;
+            if (b < 12) {
+                for (int k = 0; k < STATES_THREADS / 64; ++k)
+                    r = (b / 3 & 1) ? (red[k][b] > r ? red[k][b] : r) : r + red[k][b];
+            } else {
+                for (int k = 0; k < STATES_THREADS / 64; ++k)
+                    r += red[k][0] + red[k][1] + red[k][2];
+            }
+            out[(size_t)t * 13 + b] = r;
+        }
+        __syncthreads();       // (LDS is reused by the next individual)
+    }
+}
+
+struct SegAcc {
+    int64_t e[3];
+    uint64_t q;
+    double mn;
+};
+
+__device__ __forceinline__ void seg_reset(SegAcc &a)
+{
+    a.e[0] = a.e[1] = a.e[2] = 0;
+    a.q = 0;
+    a.mn = __builtin_inf();
+}
+
+__device__ __forceinline__ void seg_record(ibdg_segment *__restrict__ r, uint32_t first, uint32_t n, unsigned state, const SegAcc &a,
+                                           bool with_post)
+{
+    r->first = first, r->n_win = n, r->state = state, r->reserved = 0;
+    r->e[0] = a.e[0], r->e[1] = a.e[1], r->e[2] = a.e[2];
+    r->post_q = a.q;
+    r->post_min = with_post ? a.mn : 0.0;
+}
+
+// k_log2_segments_write: the records, individual t's from seg[off[t]] on in window order (off: the exclusive sums of the counts
+// of k_log2_segments_count over the same paths).  post: gamma as k_log2_posteriors left it, or NULL.  A thread walks its windows
+// once with one accumulator: at a start it is the block's head (the windows before its first start: they belong to a segment
+// that started in an earlier block) or the total of a segment that lies inside the block, which is written there and then;
+// at the block's end it is the tail of the block's last segment (or the head, if the block has no start).  An inclusive scan
+// of the blocks' start counts gives every thread the index of its first record.  The owner of a tail then adds the heads of
+// the blocks behind it, up to and with the first one that has a start -- a segment may cover any number of whole blocks --
+// and writes that record.  No atomics: every record has one writer, every head one reader.
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_write(const double *__restrict__ win_log2,
+                                                                        const uint8_t *__restrict__ path,
+                                                                        const double *__restrict__ post, uint32_t n_win,
+                                                                        uint32_t n_targets, const uint64_t *__restrict__ off,
+                                                                        ibdg_segment *__restrict__ seg)
+{
+    __shared__ int64_t hd_e[STATES_THREADS][3];
+    __shared__ uint64_t hd_q[STATES_THREADS];
+    __shared__ double hd_mn[STATES_THREADS];
+    __shared__ uint32_t fst[STATES_THREADS];            // the block's first start, n_win if it has none
+    __shared__ uint32_t cnt[2][STATES_THREADS];
+
+    const uint32_t b = threadIdx.x;
+    const uint32_t C = (n_win + STATES_THREADS - 1) / STATES_THREADS;
+    const uint32_t nbk = (n_win + C - 1) / C;
+    const uint32_t w0 = b * C < n_win ? b * C : n_win;
+    const uint32_t w1 = w0 + C < n_win ? w0 + C : n_win;
+    const bool own = b < nbk;
+    const bool with_post = post != nullptr;
+    constexpr uint32_t NONE = 0xffffffffu;
+
+    for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
+        const double *tab = win_log2 + (size_t)t * n_win * 3;
+        const uint8_t *pt = path + (size_t)t * n_win;
+        const double *po = with_post ? post + (size_t)t * n_win * 3 : nullptr;
+        ibdg_segment *out = seg + off[t];
+
+        uint32_t ns = 0, fs = n_win;
+        const unsigned before = !own || b == 0 ? 3u : pt[w0 - 1];
+        if (own) {
+            unsigned prev = before;
+            for (uint32_t w = w0; w < w1; ++w) {
+                const unsigned s = pt[w];
+                if (s != prev) {
+                    fs = ns ? fs : w;
+                    ++ns;
+                }
+                prev = s;
+            }
+        }
+        cnt[0][b] = ns;
+        fst[b] = fs;
+        __syncthreads();
+        int cur = 0;
+        for (uint32_t d = 1; d < STATES_THREADS; d <<= 1) {
+            uint32_t m = cnt[cur][b];
+            if (b >= d)
+                m += cnt[cur][b - d];
+            cnt[cur ^ 1][b] = m;
+            cur ^= 1;
+            __syncthreads();
+        }
+        uint32_t k = cnt[cur][b] - ns;                  // the block's first record
+        SegAcc a;
+        seg_reset(a);
+        uint32_t start = NONE;
+        unsigned state = 0;
+        bool head_out = false;
+        if (own) {
+            unsigned prev = before;
+            for (uint32_t w = w0; w < w1; ++w) {
+                const unsigned s = pt[w];
+                if (s != prev) {
+                    if (start == NONE) {
+                        hd_e[b][0] = a.e[0], hd_e[b][1] = a.e[1], hd_e[b][2] = a.e[2];
+                        hd_q[b] = a.q, hd_mn[b] = a.mn;
+                        head_out = true;
+                    } else {
+                        seg_record(out + k, start, w - start, state, a, with_post);
+                        ++k;
+                    }
+                    seg_reset(a);
+                    start = w, state = s;
+                }
+                prev = s;
+                int64_t e[3];
+                emission(tab + 3 * (size_t)w, e);
+                a.e[0] += e[0], a.e[1] += e[1], a.e[2] += e[2];
+                if (with_post) {
+                    const double g = po[3 * (size_t)w + s];
+                    a.q += (uint64_t)__double2ll_rn(g * SEG_POST_Q);
+                    a.mn = g < a.mn ? g : a.mn;
+                }
+            }
+        }
+        if (!head_out) {                                // no start: all of the block (nothing, for a block without windows)
+            hd_e[b][0] = a.e[0], hd_e[b][1] = a.e[1], hd_e[b][2] = a.e[2];
+            hd_q[b] = a.q, hd_mn[b] = a.mn;
+        }
+        __syncthreads();
+        if (start != NONE) {
+            uint32_t end = n_win;
+            for (uint32_t j = b + 1; j < nbk; ++j) {
+                a.e[0] += hd_e[j][0], a.e[1] += hd_e[j][1], a.e[2] += hd_e[j][2];
+                a.q += hd_q[j];
+                a.mn = hd_mn[j] < a.mn ? hd_mn[j] : a.mn;
+                if (fst[j] != n_win) {
+                    end = fst[j];
+                    break;
+                }
+            }
+            seg_record(out + k, start, end - start, state, a, with_post);
+        }
+        __syncthreads();       // (LDS is reused by the next individual)
+    }
+}
+
 }  // namespace
 
 void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], uint8_t *path,
@@ -392,6 +627,25 @@ void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_t
     const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
     hipLaunchKernelGGL(k_log2_posteriors, dim3(grid), dim3(STATES_THREADS), 0, st, win_log2, n_win, n_targets, PenW{{a[0], a[1], a[2]}},
                        tables, scr, out);
+}
+
+void launch_log2_segments_count(const uint8_t *path, uint32_t n_win, uint32_t n_targets, const uint64_t *pos_first,
+                                const uint64_t *pos_last, uint64_t *out, hipStream_t st)
+{
+    if (n_win == 0 || n_targets == 0)
+        return;
+    const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_log2_segments_count, dim3(grid), dim3(STATES_THREADS), 0, st, path, n_win, n_targets, pos_first, pos_last, out);
+}
+
+void launch_log2_segments_write(const double *win_log2, const uint8_t *path, const double *post, uint32_t n_win, uint32_t n_targets,
+                                const uint64_t *off, ibdg_segment *seg, hipStream_t st)
+{
+    if (n_win == 0 || n_targets == 0)
+        return;
+    const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_log2_segments_write, dim3(grid), dim3(STATES_THREADS), 0, st, win_log2, path, post, n_win, n_targets, off,
+                       seg);
 }
 
 }  // namespace ibdg

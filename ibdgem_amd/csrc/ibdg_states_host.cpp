@@ -273,4 +273,72 @@ int log2_posteriors_host(const double *tab, size_t n_win, double p01, double p02
     return 0;
 }
 
+// One walk over the path in window order (ibdg_states.h: every quantity is exact and associative, so this is the kernels'
+// result whatever their blocks).
+int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,
+                       const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err,
+                       size_t err_len)
+{
+    if (!n_seg || !summary) {
+        snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: NULL %s", n_seg ? "summary" : "n_seg");
+        return 1;
+    }
+    if (!pos_first != !pos_last) {
+        snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: %s without %s", pos_first ? "pos_first" : "pos_last",
+                 pos_first ? "pos_last" : "pos_first");
+        return 1;
+    }
+    std::vector<uint8_t> path(n_win ? n_win : 1);
+    std::vector<double> post;
+    uint64_t count[3];
+    if (log2_states_host(tab, n_win, p01, p02, p12, path.data(), nullptr, count, err, err_len))
+        return 1;
+    if (with_post) {
+        double expect[3], zm;
+        int ze;
+        post.resize((n_win ? n_win : 1) * 3);
+        if (log2_posteriors_host(tab, n_win, p01, p02, p12, post.data(), expect, &zm, &ze, err, err_len))
+            return 1;
+    }
+    for (size_t w = 0; pos_first && w < n_win; ++w)
+        if (pos_last[w] < pos_first[w]) {
+            snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: window %zu ends at %llu, before its start %llu", w,
+                     (unsigned long long)pos_last[w], (unsigned long long)pos_first[w]);
+            return 1;
+        }
+    *n_seg = 0;
+    for (int i = 0; i < 12; ++i)
+        summary[i] = 0;
+    for (size_t f = 0; f < n_win;) {
+        const unsigned s = path[f];
+        ibdg_segment r = {(uint32_t)f, 0, s, 0, {0, 0, 0}, 0, 0.0};
+        double mn = INFINITY;
+        size_t w = f;
+        for (; w < n_win && path[w] == s; ++w) {
+            int64_t e[3];
+            emission(tab + 3 * w, e);
+            r.e[0] += e[0], r.e[1] += e[1], r.e[2] += e[2];
+            if (with_post) {
+                const double g = post[3 * w + s];
+                r.post_q += (uint64_t)std::llrint(g * SEG_POST_Q);
+                mn = g < mn ? g : mn;
+            }
+        }
+        r.n_win = (uint32_t)(w - f);
+        r.post_min = with_post ? mn : 0.0;
+        if (seg && *n_seg < seg_cap)
+            seg[*n_seg] = r;
+        ++*n_seg;
+        ++summary[s];
+        summary[3 + s] = r.n_win > summary[3 + s] ? r.n_win : summary[3 + s];
+        if (pos_first) {
+            const uint64_t span = pos_last[w - 1] - pos_first[f] + 1;
+            summary[6 + s] += span;
+            summary[9 + s] = span > summary[9 + s] ? span : summary[9 + s];
+        }
+        f = w;
+    }
+    return 0;
+}
+
 }  // namespace ibdg

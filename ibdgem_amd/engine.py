@@ -55,6 +55,10 @@ SYMBOLS = {
     "ibdg_window_log2_states": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
     "ibdg_log2_posteriors_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
     "ibdg_window_log2_posteriors": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
+    "ibdg_log2_segments_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P, C.c_size_t,
+                                          _P, _P]),
+    "ibdg_window_log2_segments": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P]),
+    "ibdg_get_log2_segments": (C.c_int, [_P, _P, C.c_size_t]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
     "ibdg_run_ms": (C.c_int, [_P, C.c_uint, _P]),
@@ -180,6 +184,49 @@ def log2_posteriors_host(log2_tab, p01, p02, p12, want_post=True):
     if rc != 0:
         raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
     return post, expect, log2_z.value
+
+
+# ibdg_segment (include/ibdgem_hip.h): 56 bytes, no padding
+SEGMENT_DTYPE = np.dtype([("first", "<u4"), ("n_win", "<u4"), ("state", "<u4"), ("reserved", "<u4"), ("e", "<i8", (3,)),
+                          ("post_q", "<u8"), ("post_min", "<f8")])
+assert SEGMENT_DTYPE.itemsize == 56
+
+
+def _positions(pos_first, pos_last, n):
+    """The two position arrays as contiguous uint64 [n], or None; one alone stays alone (the library refuses it)."""
+    out = []
+    for p in (pos_first, pos_last):
+        if p is not None:
+            p = np.ascontiguousarray(p, dtype=np.uint64)
+            if p.shape != (n,):
+                raise ValueError(f"positions: {p.shape}, not ({n},)")
+        out.append(p)
+    return out
+
+
+def log2_segments_host(log2_tab, p01, p02, p12, with_post=False, pos_first=None, pos_last=None, seg_cap=None, want_seg=True):
+    """The segments of one window table's path on the host (ibdg_log2_segments_host): (seg structured array of
+    SEGMENT_DTYPE -- min(n_seg, seg_cap) records, all of them with seg_cap None -- or None, n_seg int, summary uint64 [12])."""
+    lib = load_library()
+    tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
+    n = tab.shape[0]
+    pf, pl = _positions(pos_first, pos_last, n)
+    cap = n if seg_cap is None else int(seg_cap)
+    seg = np.zeros(cap + 1, dtype=SEGMENT_DTYPE) if want_seg else None        # (one more: nothing may land behind the cap)
+    if seg is not None:
+        seg[cap]["first"] = 0xffffffff
+    n_seg = C.c_uint64(0)
+    summary = np.zeros(12, dtype=np.uint64)
+    rc = lib.ibdg_log2_segments_host(tab.ctypes.data, n, p01, p02, p12, int(bool(with_post)),
+                                     None if pf is None else pf.ctypes.data, None if pl is None else pl.ctypes.data,
+                                     None if seg is None else seg.ctypes.data, cap, C.addressof(n_seg), summary.ctypes.data)
+    if rc != 0:
+        raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
+    if seg is not None:
+        if seg[cap]["first"] != 0xffffffff:
+            raise EngineError("ibdg_log2_segments_host wrote behind seg_cap")
+        seg = seg[:min(cap, n_seg.value)].copy()
+    return seg, n_seg.value, summary
 
 
 class Engine:
@@ -390,6 +437,28 @@ class Engine:
         self._chk(self.lib.ibdg_window_log2_posteriors(self.ctx, p01, p02, p12, None if post is None else post.ctypes.data,
                                                        expect.ctypes.data, log2_z.ctypes.data))
         return post, expect, log2_z
+
+    def window_log2_segments(self, p01, p02, p12, with_post=False, pos_first=None, pos_last=None):
+        """The segments of every comparison individual's path of the last run, counted on the device
+        (ibdg_window_log2_segments): (n_seg uint64 [T], summary uint64 [T][12]).  get_log2_segments has the records."""
+        T, n = self.lib.ibdg_num_targets(self.ctx), self.n_windows
+        pf, pl = _positions(pos_first, pos_last, n)
+        n_seg = np.zeros(T, dtype=np.uint64)
+        summary = np.zeros((T, 12), dtype=np.uint64)
+        self._chk(self.lib.ibdg_window_log2_segments(self.ctx, p01, p02, p12, int(bool(with_post)),
+                                                     None if pf is None else pf.ctypes.data,
+                                                     None if pl is None else pl.ctypes.data, n_seg.ctypes.data,
+                                                     summary.ctypes.data))
+        self._seg_total = int(n_seg.sum())
+        return n_seg, summary
+
+    def get_log2_segments(self, cap=None):
+        """The records of the last window_log2_segments call (ibdg_get_log2_segments): a structured array of SEGMENT_DTYPE, the
+        individuals' segments back to back.  cap: the room offered (default: what that call counted)."""
+        cap = getattr(self, "_seg_total", 0) if cap is None else int(cap)
+        seg = np.zeros(max(cap, 1), dtype=SEGMENT_DTYPE)
+        self._chk(self.lib.ibdg_get_log2_segments(self.ctx, seg.ctypes.data, cap))
+        return seg[:cap]
 
     def alt_counts(self, first, n):
         out = np.empty(n, dtype=np.uint32)

@@ -65,6 +65,7 @@ static const char *cache_fn = NULL, *dump_panel_fn = NULL;
 static int opt_stats_only = 0, has_arm = 0;
 static int opt_log_summary = 0;          /* --log-summary: the summary's likelihoods as log2, from the engine's option "log_windows" */
 static int opt_posteriors = 0;           /* --posteriors: with --log-stats --states, the forward-backward probabilities of the states beside the path */
+static int opt_segments = 0;             /* --segments: with --log-stats --states, the path's segments with their scores and support */
 static int opt_log_stats = 0;            /* --log-stats: --arm-stats and --states from the log2 window table (no underflow), into log* files */
 static int opt_states = 0, has_pen = 0;  /* --states: the IBD-state path of every comparison (hgpath.c), --p01/--p02/--p12 its penalties */
 static double opt_p01 = HG_DEFAULT_P01, opt_p02 = HG_DEFAULT_P02, opt_p12 = HG_DEFAULT_P12;
@@ -80,6 +81,7 @@ static struct option longopts[] = {
     {"log-summary", no_argument, &opt_log_summary, 1},
     {"log-stats", no_argument, &opt_log_stats, 1},
     {"posteriors", no_argument, &opt_posteriors, 1},
+    {"segments", no_argument, &opt_segments, 1},
     {"p01", required_argument, 0, 1008},
     {"p02", required_argument, 0, 1009},
     {"p12", required_argument, 0, 1010},
@@ -182,6 +184,15 @@ static void usage(int code)
           "                            <out>/<pileup-name>.logibdposteriors.txt, per individual the expected windows per\n"
           "                            state, their fractions and log2 of the paths' total weight, then the totals.  With\n"
           "                            --stats-only only the second file, on one device computed there\n"
+          "  --segments                with --log-stats --states: also the level above the path, its segments (maximal runs of\n"
+          "                            windows in one state): <out>/<pileup-name>.<individual>.logsegments.txt, per segment\n"
+          "                            its state, first and last window, START of the first and END of the last, length,\n"
+          "                            windows, sites, the sums of the three log2 emissions over it (exact, in bits) and the\n"
+          "                            state's sum less the larger of the other two (Log2_LR); with --posteriors also the\n"
+          "                            mean and the minimum of the state's probability inside it; and\n"
+          "                            <out>/<pileup-name>.logibdsegments.txt, per individual and state the number of\n"
+          "                            segments, the windows of the longest, the base pairs of all and of the longest, then\n"
+          "                            the totals.  With --stats-only only the second file, on one device computed there\n"
           "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
           "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
           "  --stats-only              with --arm-stats and/or --states: write the armstats / ibdstates file only (no\n"
@@ -1706,6 +1717,8 @@ typedef struct {
     int dev_states;                          /* --log-stats --states --stats-only on one context: the paths are found on the device */
     uint64_t st[3];                          /* ... the individual's windows in IBD0, IBD1, IBD2 (ibdg_window_log2_states) */
     double po[4];                            /* ... --posteriors: its expected windows per state and log2 Z (ibdg_window_log2_posteriors) */
+    uint64_t sg[12];                         /* ... --segments: its line of logibdsegments.txt (ibdg_window_log2_segments) */
+    const uint32_t *s_row;                   /* ... the site list's panel rows, for the windows' positions */
     FILE *err;                               /* where the pileup's messages go */
     int reported;                            /* a failure was reported here already (not an engine error) */
 } shard_job;
@@ -1732,9 +1745,49 @@ typedef struct {
     size_t st_cap;
     double *po_vals;                         /* --posteriors: expect [T][3], then log2 Z [T], of the last run's individuals */
     size_t po_cap;
+    uint64_t *sg_vals;                       /* --segments: summary [T][12], then the counts [T], of the last run's individuals */
+    size_t sg_cap;
+    uint64_t *sg_pos;                        /* ... the windows' first positions [n_win], then their last */
+    size_t sg_pos_cap;
     const uint32_t *ahead_of;                /* the batch that has been queued ahead on the device; NULL: none */
 } win_cache;
 static win_cache g_wcache[64];
+
+/* --segments where the tables stay on the device: the windows of the site list at hand in the context's cache (fetched once per
+ * list, like the ones the individuals' files take from there) and their positions, which go up with the call */
+static int segments_on_device(shard_job *j, win_cache *wc)
+{
+    const size_t n_win = ibdg_num_windows(j->eng), T = j->n_targets;
+    if (!(j->same_sites && wc->valid && wc->n_win == n_win)) {
+        free(wc->first); free(wc->last); free(wc->ncov);
+        wc->first = malloc((n_win + 1) * 4);
+        wc->last = malloc((n_win + 1) * 4);
+        wc->ncov = malloc((n_win + 1) * 4);
+        wc->valid = 0;
+        if (!wc->first || !wc->last || !wc->ncov || ibdg_get_windows(j->eng, wc->first, wc->last, wc->ncov))
+            return 1;
+        wc->n_win = n_win;
+        wc->valid = j->same_sites;
+    }
+    if (wc->sg_pos_cap < 2 * n_win + 1) {
+        free(wc->sg_pos);
+        wc->sg_pos = malloc((2 * n_win + 1) * sizeof(uint64_t));
+        wc->sg_pos_cap = wc->sg_pos ? 2 * n_win + 1 : 0;
+    }
+    if (wc->sg_cap < T * 13) {
+        free(wc->sg_vals);
+        wc->sg_vals = malloc(T * 13 * sizeof(uint64_t));
+        wc->sg_cap = wc->sg_vals ? T * 13 : 0;
+    }
+    if (!wc->sg_pos || !wc->sg_vals)
+        return 1;
+    for (size_t w = 0; w < n_win; ++w) {
+        wc->sg_pos[w] = rows[j->s_row[j->a + wc->first[w]]].pos;
+        wc->sg_pos[n_win + w] = rows[j->s_row[j->a + wc->last[w]]].pos;
+    }
+    return ibdg_window_log2_segments(j->eng, opt_p01, opt_p02, opt_p12, opt_posteriors, wc->sg_pos, wc->sg_pos + n_win,
+                                     wc->sg_vals + T * 12, wc->sg_vals);
+}
 
 /* the engine's last run must be the run of this very batch: its size says so (a diagnostic when it does not) */
 static int same_run_size(shard_job *j)
@@ -1801,6 +1854,8 @@ static void *shard_run(void *arg)
                                                                 wc->po_vals + j->n_targets * 3))
                     return NULL;
             }
+            if (opt_segments && segments_on_device(j, wc))
+                return NULL;
         }
         if (j->stats_only) {
             if (j->next_targets) {                                        /* the next batch runs while the host goes on */
@@ -1849,6 +1904,8 @@ static void *shard_run(void *arg)
         memcpy(j->po, wc->po_vals + j->t_local * 3, 3 * sizeof(double));
         j->po[3] = wc->po_vals[j->n_targets * 3 + j->t_local];
     }
+    if (j->dev_states && opt_segments)
+        memcpy(j->sg, wc->sg_vals + j->t_local * 12, sizeof j->sg);
     j->wt.n_win = ibdg_num_windows(j->eng);
     if (j->stats_only) {
         j->failed = 0;
@@ -2307,6 +2364,8 @@ typedef struct {
     size_t *st_count;                           /* the individual's line of ibdstates.txt: windows in IBD0, IBD1, IBD2 */
     FILE *lp;                                   /* --posteriors: the individual's *.logposteriors.txt (NULL with --stats-only); closed by the job */
     double *po;                                 /* ... its line of logibdposteriors.txt: expected windows per state, log2 Z */
+    FILE *ls;                                   /* --segments: the individual's *.logsegments.txt (NULL with --stats-only); closed by the job */
+    uint64_t *sg;                               /* ... its line of logibdsegments.txt: the summary of ibdg_log2_segments_host */
     hg_path hgp;                                /* the slot's path arrays and text buffer (kept between individuals) */
     char *hg_buf;
     size_t hg_cap;
@@ -2459,6 +2518,55 @@ static int posteriors_individual(out_job *o)
     return bad;
 }
 
+/* --segments: the path's segments over the same table (ibdg_log2_segments_host: the same bytes as the device's
+ * ibdg_window_log2_segments), with the positions and site counts of the individual's summary */
+static const char log_seg_header[] = "Segment\tState\tFirst_Window\tLast_Window\tStart\tEnd\tLength\tNum_Windows\tNum_Sites\t"
+                                     "IBD0_LogSum\tIBD1_LogSum\tIBD2_LogSum\tLog2_LR";
+
+static int segments_individual(out_job *o)
+{
+    if (!opt_segments)
+        return 0;
+    const size_t n = o->wt.n_win;
+    uint64_t *pos = malloc((2 * n + 1) * sizeof *pos), n_seg = 0;
+    ibdg_segment *seg = o->ls ? malloc((n ? n : 1) * sizeof *seg) : NULL;
+    int bad = !pos || (o->ls && !seg);
+    for (size_t w = 0; w < n && !bad; ++w) {
+        pos[w] = o->pos_first ? o->pos_first[w] : rows[o->s_row[o->wt.first[w]]].pos;
+        pos[n + w] = o->pos_last ? o->pos_last[w] : rows[o->s_row[o->wt.last[w]]].pos;
+    }
+    if (!bad && ibdg_log2_segments_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, opt_posteriors, pos, pos + n, seg, n, &n_seg, o->sg)) {
+        fprintf(o->err, "%s\n", ibdg_last_error(NULL));
+        bad = 1;
+    }
+    if (!bad && o->ls) {
+        bad = fprintf(o->ls, "%s%s\n", log_seg_header, opt_posteriors ? "\tPost_Mean\tPost_Min" : "") < 0;
+        for (size_t k = 0; k < n_seg && !bad; ++k) {
+            const ibdg_segment *g = &seg[k];
+            const size_t f = g->first, l = f + g->n_win - 1;
+            const int64_t own = g->e[g->state], a = g->e[(g->state + 1) % 3], b = g->e[(g->state + 2) % 3];
+            unsigned long sites = 0;
+            for (size_t w = f; w <= l; ++w)
+                sites += o->wt.ncov[w];
+            bad = fprintf(o->ls, "%zu\t%u\t%zu\t%zu\t%llu\t%llu\t%llu\t%u\t%lu\t%.4Lf\t%.4Lf\t%.4Lf\t%.4Lf", k + 1, g->state, f + 1,
+                          l + 1, (unsigned long long)pos[f], (unsigned long long)pos[n + l],
+                          (unsigned long long)(pos[n + l] - pos[f] + 1), g->n_win, sites, (long double)g->e[0] / 65536,
+                          (long double)g->e[1] / 65536, (long double)g->e[2] / 65536,
+                          (long double)(own - (a > b ? a : b)) / 65536) < 0;
+            if (!bad && opt_posteriors)
+                bad = fprintf(o->ls, "\t%.6Lf\t%.6f", (long double)g->post_q / ((long double)g->n_win * 4294967296.0L), g->post_min) < 0;
+            bad = bad || fputc('\n', o->ls) == EOF;
+        }
+    }
+    if (o->ls) {
+        bad = fclose(o->ls) != 0 || bad;
+        o->ls = NULL;
+    }
+    free(pos);
+    free(seg);
+    return bad;
+}
+
 static int log_states_individual(out_job *o)
 {
     const size_t n = o->wt.n_win;
@@ -2491,7 +2599,8 @@ static int log_states_individual(out_job *o)
     }
     free(path);
     free(score);
-    return posteriors_individual(o) || bad;
+    bad = posteriors_individual(o) || bad;
+    return segments_individual(o) || bad;
 }
 
 /* 0: the path is found, counted for ibdstates.txt and (o->hg) written and its file closed */
@@ -2535,7 +2644,7 @@ static void *output_individual(void *arg)
     else {
         if ((!opt_summary_only && ftruncate(fileno(tab), 0) != 0) || ftruncate(fileno(sum), 0) != 0 ||
             (o->hg && ftruncate(fileno(o->hg), 0) != 0) || (o->lsum && ftruncate(fileno(o->lsum), 0) != 0) ||
-            (o->lp && ftruncate(fileno(o->lp), 0) != 0)) {
+            (o->lp && ftruncate(fileno(o->lp), 0) != 0) || (o->ls && ftruncate(fileno(o->ls), 0) != 0)) {
             fprintf(o->err, "[::] ERROR in compare_impute(): Cannot empty the output files of %s.\n", o->tname);
             return NULL;
         }
@@ -2929,6 +3038,9 @@ typedef struct {
     double *po_res;                 /* --posteriors: per individual the expected windows in IBD0, IBD1, IBD2 and log2 Z; the run's logibdposteriors.txt */
     FILE *po_file;
     char *po_fn;
+    uint64_t *sg_res;               /* --segments: per individual the summary of its segments [12]; the run's logibdsegments.txt */
+    FILE *sg_file;
+    char *sg_fn;
     double *site_slot[OUT_SLOTS];   /* the per-site array of each output slot */
     uint32_t *c_row;                /* dev_v: the candidates as the engine takes them */
     uint8_t *c_nr, *c_na;
@@ -3017,6 +3129,16 @@ static int run_begin(pile_run *r)
         if (!(r->po_file = fopen(r->po_fn, "w")))
             SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->po_fn);
         pj_add_file(r->pj, r->po_fn);
+    }
+    if (opt_segments) {
+        r->sg_res = calloc(g_targets.n + 1, 12 * sizeof(uint64_t));
+        if (!r->sg_res)
+            SFAIL("[::] ERROR: out of memory.\n");
+        if (asprintf(&r->sg_fn, "%s/%s.logibdsegments.txt", g_out_dir, r->pj->name) < 0)
+            return r->sg_fn = NULL, 1;
+        if (!(r->sg_file = fopen(r->sg_fn, "w")))
+            SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->sg_fn);
+        pj_add_file(r->pj, r->sg_fn);
     }
     r->arm_res = r->arm_on ? malloc((g_targets.n + 1) * 4 * sizeof(double)) : NULL;
     if (r->arm_on && !r->arm_res)
@@ -3306,6 +3428,7 @@ static void shards_fill(const pile_run *r, shard_job *jobs)
         j->arm_seg = r->arm_on ? sl->arm_local[d] : NULL;
         j->stats_only = r->tables_stay;
         j->dev_states = r->dev_states;
+        j->s_row = sl->s_row;
         j->err = r->err;
     }
 }
@@ -3404,6 +3527,8 @@ static int windows_on_engine(pile_run *r)
             r->st_res[3 * r->ti + k] = (size_t)jobs[0].st[k];
     if (r->dev_states && opt_posteriors)
         memcpy(r->po_res + 4 * r->ti, jobs[0].po, sizeof jobs[0].po);
+    if (r->dev_states && opt_segments)
+        memcpy(r->sg_res + 12 * r->ti, jobs[0].sg, sizeof jobs[0].sg);
     if (r->tables_stay)                      /* no window table left the device */
         return 0;
     tables_gather(r, jobs);
@@ -3457,7 +3582,7 @@ static FILE *out_file_open(pile_run *r, const char *kind, int to_null, char **fn
 static int outputs_open(pile_run *r, out_job *o)
 {
     char *tab_fn, *sum_fn;
-    o->hg = o->lsum = o->lp = NULL;
+    o->hg = o->lsum = o->lp = o->ls = NULL;
     if (opt_plan || opt_stats_only) {         /* (--stats-only --states: the table is here for its path alone) */
         o->tab = o->sum = opt_plan ? stdout : NULL;
         return 0;
@@ -3471,7 +3596,8 @@ static int outputs_open(pile_run *r, out_job *o)
     free(sum_fn);
     return !o->tab || !o->sum || (opt_log_summary && !(o->lsum = out_file_open(r, "logsummary", 0, NULL))) ||
            (opt_states && !(o->hg = out_file_open(r, opt_log_stats ? "loghiddengem" : "hiddengem", 0, NULL))) ||
-           (opt_posteriors && !(o->lp = out_file_open(r, "logposteriors", 0, NULL)));
+           (opt_posteriors && !(o->lp = out_file_open(r, "logposteriors", 0, NULL))) ||
+           (opt_segments && !(o->ls = out_file_open(r, "logsegments", 0, NULL)));
 }
 
 /* everything the individual's files are made of goes to its slot's job, the window table with it; the job runs beside the
@@ -3495,6 +3621,7 @@ static int output_start(pile_run *r)
     o->sq = pj->name; o->err = r->err;
     o->st_count = r->st_res ? r->st_res + 3 * r->ti : NULL;
     o->po = r->po_res ? r->po_res + 4 * r->ti : NULL;
+    o->sg = r->sg_res ? r->sg_res + 12 * r->ti : NULL;
     if (outputs_open(r, o))
         return 1;
     const int threads = all_threads();
@@ -3590,6 +3717,37 @@ static int run_end(pile_run *r)
             SFAIL("[::] ERROR writing '%s'.\n", r->po_fn);
         phase("IBD-state posteriors file");
     }
+    if (opt_segments) {
+        /* likewise: per individual and state the four numbers of its segments, then the totals (sums of the counts and base
+         * pairs, maxima of the two longest) */
+        static const char *const col[4] = {"N_SEG", "LONGEST_WIN", "TOTAL_BP", "LONGEST_BP"};
+        uint64_t total[12] = {0};
+        fputs("# ID", r->sg_file);
+        for (int s = 0; s < 3; ++s)
+            for (int k = 0; k < 4; ++k)
+                fprintf(r->sg_file, "\tIBD%d_%s", s, col[k]);
+        fputc('\n', r->sg_file);
+        for (size_t ti = 0; ti < targets.n; ++ti) {
+            const uint64_t *g = r->sg_res + 12 * ti;
+            fputs(g_ids.names[targets.idx[ti]], r->sg_file);
+            for (int s = 0; s < 3; ++s)
+                for (int k = 0; k < 4; ++k) {
+                    const uint64_t v = g[3 * k + s];
+                    fprintf(r->sg_file, "\t%llu", (unsigned long long)v);
+                    total[3 * k + s] = k & 1 ? (v > total[3 * k + s] ? v : total[3 * k + s]) : total[3 * k + s] + v;
+                }
+            fputc('\n', r->sg_file);
+        }
+        for (int s = 0; s < 3; ++s)
+            fprintf(r->sg_file, "# Total IBD%d: N_SEG = %llu, LONGEST_WIN = %llu, TOTAL_BP = %llu, LONGEST_BP = %llu\n", s,
+                    (unsigned long long)total[s], (unsigned long long)total[3 + s], (unsigned long long)total[6 + s],
+                    (unsigned long long)total[9 + s]);
+        FILE *f = r->sg_file;
+        r->sg_file = NULL;
+        if (fclose(f) != 0)
+            SFAIL("[::] ERROR writing '%s'.\n", r->sg_fn);
+        phase("IBD-state segments file");
+    }
     return 0;
 }
 
@@ -3600,9 +3758,11 @@ static void run_release(pile_run *r)
     site_list *sl = &r->sl;
     free(r->st_fn); free(r->st_res); free(sl->row_pre); free(sl->row_pre_off);
     free(r->po_fn); free(r->po_res);
-    r->st_fn = r->po_fn = sl->row_pre = NULL;
+    free(r->sg_fn); free(r->sg_res);
+    r->st_fn = r->po_fn = r->sg_fn = sl->row_pre = NULL;
     r->st_res = NULL;
     r->po_res = NULL;
+    r->sg_res = NULL;
     sl->row_pre_off = NULL;
     if (!g_list_mode)
         return;
@@ -3671,6 +3831,8 @@ fail:
         fclose(r.st_file);                /* (opened empty, left empty) */
     if (r.po_file)
         fclose(r.po_file);
+    if (r.sg_file)
+        fclose(r.sg_file);
     run_release(&r);
     return 1;
 }
@@ -3805,6 +3967,8 @@ int main(int argc, char **argv)
     if (opt_log_stats && !has_arm && !opt_states) { fprintf(stderr, "[::] ERROR: --log-stats needs --arm-stats START,END and/or --states: it says where their numbers come from.\n"); exit(1); }
     if (opt_posteriors && opt_plan) { fprintf(stderr, "[::] ERROR: --posteriors writes files --plan does not make; use one of them.\n"); exit(1); }
     if (opt_posteriors && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --posteriors needs --log-stats and --states: it is the sum over all paths of the weights whose best path they find, with their --p01, --p02, --p12.\n"); exit(1); }
+    if (opt_segments && opt_plan) { fprintf(stderr, "[::] ERROR: --segments writes files --plan does not make; use one of them.\n"); exit(1); }
+    if (opt_segments && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --segments needs --log-stats and --states: it cuts the path they find into its runs of one state and sums that path's own emissions over each.\n"); exit(1); }
     if (opt_log_stats && opt_states) {
         const double pen[3] = {opt_p01, opt_p02, opt_p12};
         static const char *const pen_name[3] = {"--p01", "--p02", "--p12"};

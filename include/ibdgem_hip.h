@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define IBDG_ABI_VERSION 5   /* (still 5, additions only: ibdg_log2_posteriors_host, ibdg_window_log2_posteriors -- forward-backward IBD-state probabilities over the log2 table; option log_windows with ibdg_get_window_log2, ibdg_get_window_log2_all -- window likelihoods as logs that do not underflow; ibdg_upload_candidates, ibdg_num_candidates, ibdg_select_variable_sites, ibdg_get_site_candidates -- the -v site lists made on the device.)  5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
+#define IBDG_ABI_VERSION 5   /* (still 5, additions only: ibdg_log2_segments_host, ibdg_window_log2_segments, ibdg_get_log2_segments -- the path's segments with exact scores and support; ibdg_log2_posteriors_host, ibdg_window_log2_posteriors -- forward-backward IBD-state probabilities over the log2 table; option log_windows with ibdg_get_window_log2, ibdg_get_window_log2_all -- window likelihoods as logs that do not underflow; ibdg_upload_candidates, ibdg_num_candidates, ibdg_select_variable_sites, ibdg_get_site_candidates -- the -v site lists made on the device.)  5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
                               * longer what a sparse pileup gets.  3: options site_results, stage_workers; ibdg_get_site_af
                               * computes on demand; ibdg_last_run_ms out[4] is 0 */
 
@@ -271,6 +271,42 @@ int ibdg_log2_posteriors_host(const double *log2_tab, size_t n_win, double p01, 
  * off, a penalty out of range, more than 2^21 windows, NULL expect or log2_z. */
 int ibdg_window_log2_posteriors(ibdg_ctx *ctx, double p01, double p02, double p12, double *post, double *expect,
                                 double *log2_z);
+/* A segment of an IBD-state path: a maximal run of windows in one state (ibdgem_amd/csrc/ibdg_states.h).  56 bytes,
+ * no padding.  e[s]: the sum over its windows of the emission e_w[s] of ibdg_log2_states_host (quanta of 2^-16 bit; e[state] -
+ * max of the other two is the segment's log2 likelihood ratio); post_q: the sum over its windows of llrint(gamma_w[state] *
+ * 2^32), gamma the posteriors of ibdg_log2_posteriors_host (post_q / (n_win * 2^32) is their mean); post_min: their minimum.
+ * The last two are 0 where the posteriors were not asked for. */
+typedef struct ibdg_segment {
+    uint32_t first, n_win;      /* its first window (0-based) and how many it has */
+    uint32_t state, reserved;   /* 0, 1, 2; 0 */
+    int64_t e[3];
+    uint64_t post_q;
+    double post_min;
+} ibdg_segment;
+/* The segments of one window table's path.  Runs ibdg_log2_states_host, with with_post != 0 also ibdg_log2_posteriors_host,
+ * then walks the path once.  pos_first[n_win], pos_last[n_win]: the position of every window's first and last site, or both NULL.
+ * seg (may be NULL) takes at most seg_cap records in window order; *n_seg is always the true count.  summary[12], for state s
+ * = 0, 1, 2: [s] its segments, [3 + s] the windows of its longest, [6 + s] the sum over its segments of (pos_last of the last
+ * window - pos_first of the first + 1), [9 + s] the largest of these; the last six are 0 without positions.  Integer sums,
+ * maxima and an fp64 minimum only: exact whatever the order, hence the same bytes as the device's.  n_win = 0: no segment,
+ * summary 0.  Needs no device.  Errors (ibdg_last_error(NULL)): those of the two functions it runs, NULL n_seg or summary, one
+ * position array without the other, a window with pos_last < pos_first. */
+int ibdg_log2_segments_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, int with_post,
+                            const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap,
+                            uint64_t *n_seg, uint64_t summary[12]);
+/* The same for every comparison individual of the last ibdg_run, on the device: the kernel of ibdg_window_log2_states, with
+ * with_post that of ibdg_window_log2_posteriors, then one that counts.  pos_first / pos_last [n_win] (both or neither) are the
+ * site list's, shared by the individuals.  n_seg[T], summary[T][12]: 104 bytes per individual leave the device.  Same waits
+ * as ibdg_get_window_log2; returns with the outputs in host memory.  n_win = 0: zeros.  Errors: no results, the last ibdg_run
+ * made with option "log_windows" off, a penalty out of range, more than 2^21 windows, NULL n_seg or summary, one position
+ * array without the other, a window with pos_last < pos_first. */
+int ibdg_window_log2_segments(ibdg_ctx *ctx, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,
+                              const uint64_t *pos_last, uint64_t *n_seg, uint64_t *summary);
+/* The records of the last ibdg_window_log2_segments call: the individuals' segments back to back, individual t's n_seg[t]
+ * records behind those of the individuals before it (the device holds them as compactly).  cap: the records seg has room
+ * for.  Errors: no ibdg_window_log2_segments since the last ibdg_run (or since a later ibdg_window_log2_states /
+ * ibdg_window_log2_posteriors call, which reuse its paths), cap smaller than the sum of n_seg, NULL seg with a sum > 0. */
+int ibdg_get_log2_segments(ibdg_ctx *ctx, ibdg_segment *seg, size_t cap);
 /* Alt-allele count of panel rows [first_row, first_row+n): out[n] (for tests). */
 int ibdg_get_alt_counts(ibdg_ctx *ctx, size_t first_row, size_t n, uint32_t *out);
 
