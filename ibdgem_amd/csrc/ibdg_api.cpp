@@ -119,8 +119,9 @@ int ensure(ibdg_ctx *c, DevBuf &b, size_t bytes)
 
 // ---- what stops being valid when an input changes: each of these says all of it, and nobody else says any ----
 
-// A panel goes up: the alt counts, the results, the layout, the site list and the candidates (they name rows of the panel
-// that goes), and the device copies of targets / background weights, which were laid out for the previous panel.  The row
+// A panel goes up: the alt counts, the results (with what the log-domain calls kept of them: ls), the layout, the site list
+// and the candidates (they name rows of the panel that goes), and the device copies of targets / background weights, which
+// were laid out for the previous panel.  The row
 // table goes with up_gen (its alt counts and n_ids).  sites_gen stays: no run is accepted before the next upload of sites
 // (sites_valid) and no background is taken for the same (prev_pu).
 void panel_replaced(ibdg_ctx *c)
@@ -128,6 +129,7 @@ void panel_replaced(ibdg_ctx *c)
     ++c->up_gen;
     c->pan.counts_valid = false;
     c->have_results = false;
+    c->ls.drop();
     c->lay.pop_sites_ok = false;
     c->prev_targets.clear();
     c->bg.prev_bg.clear();
@@ -141,8 +143,8 @@ void panel_replaced(ibdg_ctx *c)
     c->cand.n_cand = 0;
 }
 
-// A site list goes up (from the host, the device or the candidates): the results, the layout and its credit, the window
-// bounds, the -A triples, the selection map; with sites_gen the IBD0 pass, the fragment base, the images, a pending
+// A site list goes up (from the host, the device or the candidates): the results (with ls), the layout and its credit, the
+// window bounds, the -A triples, the selection map; with sites_gen the IBD0 pass, the fragment base, the images, a pending
 // finalising step's right to ride along and stream3's order behind the prepared sites; with up_gen the row table; and
 // the count of runs towards "ibd0_after".
 void sites_replaced(ibdg_ctx *c)
@@ -156,6 +158,7 @@ void sites_replaced(ibdg_ctx *c)
     c->sites.have_fo = false;
     c->cand.sel_valid = false;
     c->have_results = false;
+    c->ls.drop();
     c->lay.pop_sites_ok = false;
     c->lay.compact = false;
     c->lay.relayout_credit = 0;
@@ -2067,7 +2070,7 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
     if (!c->sites.sites_valid) return fail(c, "[::] ERROR in ibdg_run: no sites uploaded");
     if (T == 0 || !targets) return fail(c, "[::] ERROR in ibdg_run: no targets");
     if (T > 65535) return fail(c, "[::] ERROR in ibdg_run: at most 65535 targets per call");
-    c->seg.valid = false;                    // (the paths ibdg_get_log2_segments would read belong to the run before)
+    c->ls.drop();                            // (the paths, posteriors and records belong to the run before)
     for (size_t t = 0; t < T; ++t)
         if (targets[t] >= c->pan.n_ids)
             return fail(c, "[::] ERROR in ibdg_run: target %u is not a panel individual (n_ids=%u)", targets[t],
@@ -2293,41 +2296,91 @@ int ibdg_log2_states_host(const double *log2_tab, size_t n_win, double p01, doub
     return 0;
 }
 
-// IBD-state paths over win_log2 of the last run (ibdg_states.hip).  One launch on the main stream behind join_streams, as
-// the copies of ibdg_get_window_log2 (the table's writers: WinLog in ibdg_ctx.h), then the copies out and a host wait: no
-// reader of the table and no user of st_path / st_score / st_count outlives the call.
+// ---- the log-domain state calls over win_log2 of the last run (ibdg_states.hip; LogStates in ibdg_ctx.h has the rule) ----
+// Each public call is: log_call_begin, join_streams (the table's writers: WinLog in ibdg_ctx.h), the stages it needs, its
+// copies out, quiesce -- no reader of the table and no kernel of the group outlives the call.
+struct LogCall {                     // an accepted call: the penalties in quanta, their weights, the size of the run
+    int64_t P[3];
+    double a[3];
+    size_t T, n_win;
+};
+
+// Every check the three calls share, in the order and with the text each had.  own: the caller's complaint about its own
+// arguments, or NULL; max_tail: how its refusal of too many windows ends.
+static int log_call_begin(ibdg_ctx *c, const char *fn, const char *own, const char *max_tail, double p01, double p02, double p12,
+                          LogCall &L)
+{
+    if (!c->have_results) return fail(c, "[::] ERROR in %s: no results (call ibdg_run)", fn);
+    if (!c->wlog.valid) return fail(c, "[::] ERROR in %s: the last run kept no window logs (option log_windows)", fn);
+    if (own) return fail(c, "[::] ERROR in %s: %s", fn, own);
+    int bad = 0;
+    if (ibdg::states_penalties(p01, p02, p12, L.P, &bad)) {
+        static const char *const name[3] = {"p01", "p02", "p12"};
+        return fail(c, "[::] ERROR in %s: %s = %g is not in (0, 1]", fn, name[bad], bad == 0 ? p01 : bad == 1 ? p02 : p12);
+    }
+    ibdg::post_penalty_weights(L.P, L.a);
+    L.T = c->n_targets, L.n_win = c->sites.n_win;
+    if (L.n_win > ibdg::STATES_MAX_WIN)
+        return fail(c, "[::] ERROR in %s: %zu windows, more than the %zu (2^21) %s", fn, L.n_win, ibdg::STATES_MAX_WIN, max_tail);
+    return 0;
+}
+
+// The stages: each makes sure of its buffers and queues its launch on the main stream, behind the caller's join_streams; none
+// waits on the host.  A product that is fresh for L.P is not made again; the scores are not kept, so want_score launches.
+static int enqueue_states(ibdg_ctx *c, const LogCall &L, bool want_score)
+{
+    ibdg_ctx::LogStates &S = c->ls;
+    if (ensure(c, S.path, L.T * L.n_win) || ensure(c, S.count, L.T * 24) || (want_score && ensure(c, S.score, L.T * L.n_win * 24)))
+        return 1;
+    if (S.fresh(S.PATH, L.P) && !want_score) return 0;
+    ibdg::launch_log2_states((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.P, (uint8_t *)S.path.p,
+                             want_score ? (int64_t *)S.score.p : nullptr, (uint64_t *)S.count.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    S.made(S.PATH, L.P);
+    return 0;
+}
+
+static int enqueue_posteriors(ibdg_ctx *c, const LogCall &L)
+{
+    ibdg_ctx::LogStates &S = c->ls;
+    if (ensure(c, S.post, L.T * L.n_win * 24) || ensure(c, S.pout, L.T * 40) || ensure(c, S.ptab, 4096))
+        return 1;
+    if (S.fresh(S.POST, L.P)) return 0;
+    HIP_TRY(c, hipMemcpyAsync(S.ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
+    ibdg::launch_log2_posteriors((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.a, (const double *)S.ptab.p,
+                                 (double *)S.post.p, (double *)S.pout.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    S.made(S.POST, L.P);
+    return 0;
+}
+
+// (behind enqueue_states: it reads the path; d_first, d_last: the windows' positions on the device, or both NULL)
+static int enqueue_segments_count(ibdg_ctx *c, const LogCall &L, const uint64_t *d_first, const uint64_t *d_last)
+{
+    if (ensure(c, c->ls.sout, L.T * 104)) return 1;
+    ibdg::launch_log2_segments_count((const uint8_t *)c->ls.path.p, (uint32_t)L.n_win, (uint32_t)L.T, d_first, d_last,
+                                     (uint64_t *)c->ls.sout.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+// IBD-state paths: the states stage, the counts (and what else is asked for) out
 int ibdg_window_log2_states(ibdg_ctx *c, double p01, double p02, double p12, uint8_t *path, int64_t *score, uint64_t *count)
 {
     if (!c) return 1;
-    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_window_log2_states: no results (call ibdg_run)");
-    if (!c->wlog.valid) return fail(c, "[::] ERROR in ibdg_window_log2_states: the last run kept no window logs (option log_windows)");
-    if (!count) return fail(c, "[::] ERROR in ibdg_window_log2_states: NULL count");
-    int64_t P[3];
-    int bad = 0;
-    if (ibdg::states_penalties(p01, p02, p12, P, &bad)) {
-        static const char *const name[3] = {"p01", "p02", "p12"};
-        return fail(c, "[::] ERROR in ibdg_window_log2_states: %s = %g is not in (0, 1]", name[bad], bad == 0 ? p01 : bad == 1 ? p02 : p12);
-    }
-    const size_t T = c->n_targets, n_win = c->sites.n_win;
-    if (n_win > ibdg::STATES_MAX_WIN)
-        return fail(c, "[::] ERROR in ibdg_window_log2_states: %zu windows, more than the %zu (2^21) the integer scores allow", n_win,
-                    ibdg::STATES_MAX_WIN);
-    if (T == 0) return 0;
-    if (n_win == 0) {
-        memset(count, 0, T * 3 * sizeof *count);
+    LogCall L;
+    if (log_call_begin(c, __func__, count ? nullptr : "NULL count", "the integer scores allow", p01, p02, p12, L)) return 1;
+    if (L.T == 0) return 0;
+    if (L.n_win == 0) {
+        memset(count, 0, L.T * 3 * sizeof *count);
         return 0;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    c->seg.valid = false;                    // (st_path is rewritten)
-    if (ensure(c, c->st_path, T * n_win) || ensure(c, c->st_count, T * 24) || (score && ensure(c, c->st_score, T * n_win * 24)))
-        return 1;
-    if (join_streams(c)) return 1;
-    ibdg::launch_log2_states((const double *)c->wlog.win_log2.p, (uint32_t)n_win, (uint32_t)T, P, (uint8_t *)c->st_path.p,
-                             score ? (int64_t *)c->st_score.p : nullptr, (uint64_t *)c->st_count.p, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(count, c->st_count.p, T * 24, hipMemcpyDeviceToHost, c->stream));
-    if (path) HIP_TRY(c, hipMemcpyAsync(path, c->st_path.p, T * n_win, hipMemcpyDeviceToHost, c->stream));
-    if (score) HIP_TRY(c, hipMemcpyAsync(score, c->st_score.p, T * n_win * 24, hipMemcpyDeviceToHost, c->stream));
+    c->ls.records_drop();
+    if (join_streams(c) || enqueue_states(c, L, score != nullptr)) return 1;
+    HIP_TRY(c, hipMemcpyAsync(count, c->ls.count.p, L.T * 24, hipMemcpyDeviceToHost, c->stream));
+    if (path) HIP_TRY(c, hipMemcpyAsync(path, c->ls.path.p, L.T * L.n_win, hipMemcpyDeviceToHost, c->stream));
+    if (score) HIP_TRY(c, hipMemcpyAsync(score, c->ls.score.p, L.T * L.n_win * 24, hipMemcpyDeviceToHost, c->stream));
     return quiesce(c);
 }
 
@@ -2344,45 +2397,26 @@ int ibdg_log2_posteriors_host(const double *log2_tab, size_t n_win, double p01, 
     return 0;
 }
 
-// IBD-state posteriors over win_log2 of the last run (k_log2_posteriors in ibdg_states.hip).  As ibdg_window_log2_states: one
-// launch on the main stream behind join_streams, the copies out and a host wait; st_post / st_pout / st_ptab are scratch of
-// the call (the tables' 4 KB go up with every call: nothing is kept).
+// IBD-state posteriors (k_log2_posteriors): the posteriors stage, expect and Z (and the gammas when asked for) out
 int ibdg_window_log2_posteriors(ibdg_ctx *c, double p01, double p02, double p12, double *post, double *expect, double *log2_z)
 {
     if (!c) return 1;
-    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: no results (call ibdg_run)");
-    if (!c->wlog.valid) return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: the last run kept no window logs (option log_windows)");
-    if (!expect || !log2_z) return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: NULL %s", expect ? "log2_z" : "expect");
-    int64_t P[3];
-    int bad = 0;
-    if (ibdg::states_penalties(p01, p02, p12, P, &bad)) {
-        static const char *const name[3] = {"p01", "p02", "p12"};
-        return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: %s = %g is not in (0, 1]", name[bad], bad == 0 ? p01 : bad == 1 ? p02 : p12);
-    }
-    const size_t T = c->n_targets, n_win = c->sites.n_win;
-    if (n_win > ibdg::STATES_MAX_WIN)
-        return fail(c, "[::] ERROR in ibdg_window_log2_posteriors: %zu windows, more than the %zu (2^21) of the path", n_win,
-                    ibdg::STATES_MAX_WIN);
+    LogCall L;
+    if (log_call_begin(c, __func__, !expect ? "NULL expect" : !log2_z ? "NULL log2_z" : nullptr, "of the path", p01, p02, p12, L))
+        return 1;
+    const size_t T = L.T;
     if (T == 0) return 0;
-    if (n_win == 0) {
+    if (L.n_win == 0) {
         memset(expect, 0, T * 3 * sizeof *expect);
         memset(log2_z, 0, T * sizeof *log2_z);
         return 0;
     }
-    double a[3];
-    ibdg::post_penalty_weights(P, a);
     HIP_TRY(c, hipSetDevice(c->device));
-    c->seg.valid = false;                    // (st_post is rewritten)
-    if (ensure(c, c->st_post, T * n_win * 24) || ensure(c, c->st_pout, T * 40) || ensure(c, c->st_ptab, 4096))
-        return 1;
-    if (join_streams(c)) return 1;
-    HIP_TRY(c, hipMemcpyAsync(c->st_ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
-    ibdg::launch_log2_posteriors((const double *)c->wlog.win_log2.p, (uint32_t)n_win, (uint32_t)T, a, (const double *)c->st_ptab.p,
-                                 (double *)c->st_post.p, (double *)c->st_pout.p, c->stream);
-    HIP_TRY(c, hipGetLastError());
+    c->ls.records_drop();
+    if (join_streams(c) || enqueue_posteriors(c, L)) return 1;
     std::vector<double> o(T * 5);
-    HIP_TRY(c, hipMemcpyAsync(o.data(), c->st_pout.p, T * 40, hipMemcpyDeviceToHost, c->stream));
-    if (post) HIP_TRY(c, hipMemcpyAsync(post, c->st_post.p, T * n_win * 24, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(o.data(), c->ls.pout.p, T * 40, hipMemcpyDeviceToHost, c->stream));
+    if (post) HIP_TRY(c, hipMemcpyAsync(post, c->ls.post.p, T * L.n_win * 24, hipMemcpyDeviceToHost, c->stream));
     if (quiesce(c)) return 1;
     for (size_t t = 0; t < T; ++t) {
         expect[3 * t] = o[5 * t], expect[3 * t + 1] = o[5 * t + 1], expect[3 * t + 2] = o[5 * t + 2];
@@ -2402,78 +2436,54 @@ int ibdg_log2_segments_host(const double *log2_tab, size_t n_win, double p01, do
     return 0;
 }
 
-// The segments of the paths over win_log2 of the last run (k_log2_segments_count in ibdg_states.hip).  As its two neighbours: on
-// the main stream behind join_streams -- the states kernel, with with_post the posteriors kernel, the count kernel --, the copy
-// out and a host wait.  st_path and st_post stay as they are for ibdg_get_log2_segments (c->seg).
+// The segments of the paths (k_log2_segments_count): the states stage, with with_post the posteriors stage, the count stage
+// -- the first two launch nothing where a states / posteriors call with these penalties went before on this run --, the
+// summaries and counts out.  The path and the posteriors stay as they are for ibdg_get_log2_segments (records_made).
 int ibdg_window_log2_segments(ibdg_ctx *c, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,
                               const uint64_t *pos_last, uint64_t *n_seg, uint64_t *summary)
 {
     if (!c) return 1;
-    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_window_log2_segments: no results (call ibdg_run)");
-    if (!c->wlog.valid) return fail(c, "[::] ERROR in ibdg_window_log2_segments: the last run kept no window logs (option log_windows)");
-    if (!n_seg || !summary) return fail(c, "[::] ERROR in ibdg_window_log2_segments: NULL %s", n_seg ? "summary" : "n_seg");
-    if (!pos_first != !pos_last)
-        return fail(c, "[::] ERROR in ibdg_window_log2_segments: %s without %s", pos_first ? "pos_first" : "pos_last",
-                    pos_first ? "pos_last" : "pos_first");
-    int64_t P[3];
-    int bad = 0;
-    if (ibdg::states_penalties(p01, p02, p12, P, &bad)) {
-        static const char *const name[3] = {"p01", "p02", "p12"};
-        return fail(c, "[::] ERROR in ibdg_window_log2_segments: %s = %g is not in (0, 1]", name[bad], bad == 0 ? p01 : bad == 1 ? p02 : p12);
-    }
-    const size_t T = c->n_targets, n_win = c->sites.n_win;
-    if (n_win > ibdg::STATES_MAX_WIN)
-        return fail(c, "[::] ERROR in ibdg_window_log2_segments: %zu windows, more than the %zu (2^21) of the path", n_win,
-                    ibdg::STATES_MAX_WIN);
+    LogCall L;
+    const char *own = !n_seg ? "NULL n_seg" : !summary ? "NULL summary" : pos_first && !pos_last ? "pos_first without pos_last"
+                      : pos_last && !pos_first ? "pos_last without pos_first" : nullptr;
+    if (log_call_begin(c, __func__, own, "of the path", p01, p02, p12, L)) return 1;
+    const size_t T = L.T, n_win = L.n_win;
     for (size_t w = 0; pos_first && w < n_win; ++w)
         if (pos_last[w] < pos_first[w])
             return fail(c, "[::] ERROR in ibdg_window_log2_segments: window %zu ends at %llu, before its start %llu", w,
                         (unsigned long long)pos_last[w], (unsigned long long)pos_first[w]);
-    c->seg.valid = false;
-    c->seg.with_post = with_post != 0;
-    c->seg.n_seg.assign(T, 0);
+    ibdg_ctx::LogStates &S = c->ls;
+    S.records_drop();
+    S.with_post = with_post != 0;
+    S.n_seg.assign(T, 0);
     if (T == 0) return 0;
     memset(n_seg, 0, T * sizeof *n_seg);
     memset(summary, 0, T * 12 * sizeof *summary);
     if (n_win == 0) {
-        c->seg.valid = true;
+        S.records_made();
         return 0;
     }
-    double a[3];
-    ibdg::post_penalty_weights(P, a);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (ensure(c, c->st_path, T * n_win) || ensure(c, c->st_count, T * 24) || ensure(c, c->st_sout, T * 104) ||
-        (pos_first && ensure(c, c->st_spos, n_win * 16)) ||
-        (with_post && (ensure(c, c->st_post, T * n_win * 24) || ensure(c, c->st_pout, T * 40) || ensure(c, c->st_ptab, 4096))))
-        return 1;
-    if (join_streams(c)) return 1;
+    if ((pos_first && ensure(c, S.spos, n_win * 16)) || join_streams(c)) return 1;
     const uint64_t *d_first = nullptr, *d_last = nullptr;
     if (pos_first) {
-        d_first = (const uint64_t *)c->st_spos.p, d_last = d_first + n_win;
-        HIP_TRY(c, hipMemcpyAsync(c->st_spos.p, pos_first, n_win * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync((char *)c->st_spos.p + n_win * 8, pos_last, n_win * 8, hipMemcpyHostToDevice, c->stream));
+        d_first = (const uint64_t *)S.spos.p, d_last = d_first + n_win;
+        HIP_TRY(c, hipMemcpyAsync(S.spos.p, pos_first, n_win * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync((char *)S.spos.p + n_win * 8, pos_last, n_win * 8, hipMemcpyHostToDevice, c->stream));
     }
-    ibdg::launch_log2_states((const double *)c->wlog.win_log2.p, (uint32_t)n_win, (uint32_t)T, P, (uint8_t *)c->st_path.p, nullptr,
-                             (uint64_t *)c->st_count.p, c->stream);
-    if (with_post) {
-        HIP_TRY(c, hipMemcpyAsync(c->st_ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
-        ibdg::launch_log2_posteriors((const double *)c->wlog.win_log2.p, (uint32_t)n_win, (uint32_t)T, a, (const double *)c->st_ptab.p,
-                                     (double *)c->st_post.p, (double *)c->st_pout.p, c->stream);
-    }
-    ibdg::launch_log2_segments_count((const uint8_t *)c->st_path.p, (uint32_t)n_win, (uint32_t)T, d_first, d_last,
-                                     (uint64_t *)c->st_sout.p, c->stream);
-    HIP_TRY(c, hipGetLastError());
+    if (enqueue_states(c, L, false) || (with_post && enqueue_posteriors(c, L)) || enqueue_segments_count(c, L, d_first, d_last))
+        return 1;
     std::vector<uint64_t> o(T * 13);
-    HIP_TRY(c, hipMemcpyAsync(o.data(), c->st_sout.p, T * 104, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(o.data(), S.sout.p, T * 104, hipMemcpyDeviceToHost, c->stream));
     if (quiesce(c)) return 1;
     for (size_t t = 0; t < T; ++t) {
         memcpy(summary + 12 * t, &o[13 * t], 96);
-        c->seg.n_seg[t] = n_seg[t] = o[13 * t + 12];
+        S.n_seg[t] = n_seg[t] = o[13 * t + 12];
         if (n_seg[t] == 0 || n_seg[t] > n_win)          // (what sizes the record buffer: never taken on trust)
             return fail(c, "[::] ERROR in ibdg_window_log2_segments: individual %zu has %llu segments in %zu windows", t,
                         (unsigned long long)n_seg[t], n_win);
     }
-    c->seg.valid = true;
+    S.records_made();
     return 0;
 }
 
@@ -2482,29 +2492,30 @@ int ibdg_window_log2_segments(ibdg_ctx *c, double p01, double p02, double p12, i
 int ibdg_get_log2_segments(ibdg_ctx *c, ibdg_segment *seg, size_t cap)
 {
     if (!c) return 1;
-    if (!c->have_results || !c->seg.valid)
+    ibdg_ctx::LogStates &S = c->ls;
+    if (!c->have_results || !S.records_fresh())
         return fail(c, "[::] ERROR in ibdg_get_log2_segments: no ibdg_window_log2_segments call since the last ibdg_run");
-    const size_t T = c->seg.n_seg.size(), n_win = c->sites.n_win;
+    const size_t T = S.n_seg.size(), n_win = c->sites.n_win;
     std::vector<uint64_t> off(T ? T : 1);
     uint64_t total = 0;
     for (size_t t = 0; t < T; ++t) {
         off[t] = total;
-        total += c->seg.n_seg[t];
+        total += S.n_seg[t];
     }
     if (cap < total)
         return fail(c, "[::] ERROR in ibdg_get_log2_segments: room for %zu records, %llu are there", cap, (unsigned long long)total);
     if (total == 0) return 0;
     if (!seg) return fail(c, "[::] ERROR in ibdg_get_log2_segments: NULL seg");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (ensure(c, c->st_soff, T * 8) || ensure(c, c->st_seg, total * sizeof(ibdg_segment)))
+    if (ensure(c, S.soff, T * 8) || ensure(c, S.recs, total * sizeof(ibdg_segment)))
         return 1;
     if (join_streams(c)) return 1;
-    HIP_TRY(c, hipMemcpyAsync(c->st_soff.p, off.data(), T * 8, hipMemcpyHostToDevice, c->stream));
-    ibdg::launch_log2_segments_write((const double *)c->wlog.win_log2.p, (const uint8_t *)c->st_path.p,
-                                     c->seg.with_post ? (const double *)c->st_post.p : nullptr, (uint32_t)n_win, (uint32_t)T,
-                                     (const uint64_t *)c->st_soff.p, (ibdg_segment *)c->st_seg.p, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(S.soff.p, off.data(), T * 8, hipMemcpyHostToDevice, c->stream));
+    ibdg::launch_log2_segments_write((const double *)c->wlog.win_log2.p, (const uint8_t *)S.path.p,
+                                     S.with_post ? (const double *)S.post.p : nullptr, (uint32_t)n_win, (uint32_t)T,
+                                     (const uint64_t *)S.soff.p, (ibdg_segment *)S.recs.p, c->stream);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(seg, c->st_seg.p, total * sizeof(ibdg_segment), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(seg, S.recs.p, total * sizeof(ibdg_segment), hipMemcpyDeviceToHost, c->stream));
     return quiesce(c);
 }
 

@@ -341,6 +341,42 @@ struct ibdg_ctx {
         bool valid = false;              // the last run was made with the option on
     } wlog;
 
+    // The log-domain state calls over win_log2 of the last run (ibdg_window_log2_states / _posteriors / _segments,
+    // ibdg_get_log2_segments; ibdg_states.hip).  Each product is a stage that is queued on the main stream behind join_streams
+    // and followed, in the public call, by the copies out and a host wait: no reader of the table and no kernel of this group
+    // outlives its call.  Two products are kept from call to call, with the penalties (in quanta) they were made for:
+    //   the path   `path` (`from` on the way, then the states [T][n_win]) + `count` [T][3]          k_log2_states
+    //   the post.  `post` (beta, then gamma [T][n_win][3]) + `pout` (expect, Z: [T][5])             k_log2_posteriors
+    // A stage whose product is fresh for the call's penalties does not launch; `score` [T][n_win][3] is not kept, so a call
+    // that wants scores launches anyway.  States, posteriors and segments with the same penalties on one run thus launch each
+    // kernel once.  The key is the penalties and nothing else: both products are functions of win_log2 and the penalties, and
+    // drop() is called where a run starts (ibdg_run) and wherever have_results is cleared (panel_replaced, sites_replaced) --
+    // the only places where the table, T or n_win can change.  The buffers' allocation counts are NOT part of the key (as
+    // they are for RowTable or Images): between two drops T and n_win are fixed, every ensure() of this group asks for the
+    // same size again, and so it cannot move a buffer that holds a fresh product.
+    // The records: records_made says that `path` (and with_post: `post`) are what the last ibdg_window_log2_segments used and
+    // `n_seg` its counts, for ibdg_get_log2_segments to cut the records from.  Reuse goes forward only: a states or
+    // posteriors call drops the records again (records_drop), whatever its penalties, and so does drop().
+    // The rest is scratch of one call: `ptab` (the two tables, uploaded with every posteriors launch), `spos` (the windows'
+    // positions [2][n_win]), `sout` (summaries and counts [T][13]), `soff` (record offsets [T]), `recs` (the records).
+    struct LogStates {
+        DevBuf path, score, count, post, pout, ptab, spos, sout, soff, recs;
+        enum Product { PATH, POST };
+        bool have[2] = {false, false};
+        int64_t P[2][3] = {};
+        bool recs_ok = false, with_post = false;
+        std::vector<uint64_t> n_seg;     // per individual of the last ibdg_window_log2_segments
+        bool fresh(Product k, const int64_t want[3]) const
+        { return have[k] && P[k][0] == want[0] && P[k][1] == want[1] && P[k][2] == want[2]; }
+        void made(Product k, const int64_t made_for[3])
+        { have[k] = true; P[k][0] = made_for[0]; P[k][1] = made_for[1]; P[k][2] = made_for[2]; }
+        bool records_fresh() const { return recs_ok; }
+        void records_made() { recs_ok = true; }
+        void records_drop() { recs_ok = false; }
+        void drop() { have[PATH] = have[POST] = recs_ok = false; }
+        void free_bufs() { release_all({&path, &score, &count, &post, &pout, &ptab, &spos, &sout, &soff, &recs}); }
+    } ls;
+
     // The finalising step of the last run of single individuals (k_ld_finalize's work) when it has been left to the NEXT
     // run's k_ld_popcount launch (option "finalize_in_next"): whoever reads results or replaces inputs first makes up for
     // it with a launch of its own (flush_finalize).  The partial sums alternate between the two halves of their buffer.
@@ -396,20 +432,6 @@ struct ibdg_ctx {
     // run state / results
     DevBuf targets, weight, nrefpanel, af, site_ll, win_ll;
     DevBuf llr_seg, llr_part, llr_out;  // ibdg_window_llr_sums: segments, partial sums per block of windows, the sums
-    // ibdg_window_log2_states: `from`, then the paths [T][n_win]; the scores [T][n_win][3] (only when asked for); the counts
-    // [T][3].  Scratch of one call like the llr_* above: nothing is kept from call to call, so there is nothing to invalidate.
-    DevBuf st_path, st_score, st_count;
-    // ibdg_window_log2_posteriors, scratch of one call likewise: beta, then gamma [T][n_win][3]; expect, Z [T][5]; the two tables
-    DevBuf st_post, st_pout, st_ptab;
-    // ibdg_window_log2_segments: the windows' positions [2][n_win], the summaries and counts [T][13]; ibdg_get_log2_segments: the
-    // record offsets [T], the records.  The one thing of this group that is kept from call to call: `seg` says that st_path (and
-    // st_post) hold what the last ibdg_window_log2_segments left, for ibdg_get_log2_segments to read.  It holds only while
-    // have_results does, and is dropped by ibdg_run and by the two other calls that write st_path or st_post.
-    DevBuf st_spos, st_sout, st_soff, st_seg;
-    struct SegCall {
-        bool valid = false, with_post = false;
-        std::vector<uint64_t> n_seg;     // per individual of that call
-    } seg;
     size_t n_targets = 0;
     bool have_results = false;
     int res_site_mode = 0;           // the mode the last run's results were produced under
@@ -421,7 +443,7 @@ struct ibdg_ctx {
         release_all({&rt.row_tab, &p2.p2w, &p2.p2c, &p2.p2_tw, &p2.p2_wt, &fb.fragb, &img.wtarget, &img.twords});
         release_all({&wtarget_mt, &twords_mt, &partial, &aimg, &wc_slot, &partial_h, &vals, &order});
         release_all({&targets, &weight, &nrefpanel, &af, &site_ll, &win_ll, &llr_seg, &llr_part, &llr_out, &wlog.win_log2});
-        release_all({&st_path, &st_score, &st_count, &st_post, &st_pout, &st_ptab, &st_spos, &st_sout, &st_soff, &st_seg});
+        ls.free_bufs();
     }
 };
 

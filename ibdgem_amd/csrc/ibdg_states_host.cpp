@@ -47,34 +47,33 @@ static int argmax3(const int64_t v[3])
     return m;
 }
 
-// path [n_win] or NULL, score [n_win][3] or NULL, count[3]; err: room for a message
-int log2_states_host(const double *tab, size_t n_win, double p01, double p02, double p12, uint8_t *path, int64_t *score,
-                     uint64_t count[3], char *err, size_t err_len)
+// What the three twins check alike, with the text each had.  own: the caller's complaint about its own pointers, or NULL;
+// max_tail: how its refusal of too many windows ends.  P: the penalties in quanta.
+static int check_log_args(const char *fn, const char *own, const double *tab, size_t n_win, double p01, double p02, double p12,
+                          const char *max_tail, int64_t P[3], char *err, size_t err_len)
 {
-    int64_t P[3];
+    static const char *const name[3] = {"p01", "p02", "p12"};
     int bad = 0;
-    if (!count) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_states_host: NULL count");
-        return 1;
-    }
-    if (n_win && !tab) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_states_host: NULL table");
-        return 1;
-    }
-    if (states_penalties(p01, p02, p12, P, &bad)) {
-        static const char *const name[3] = {"p01", "p02", "p12"};
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_states_host: %s = %g is not in (0, 1]", name[bad],
-                 bad == 0 ? p01 : bad == 1 ? p02 : p12);
-        return 1;
-    }
-    if (n_win > STATES_MAX_WIN) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_states_host: %zu windows, more than the %zu (2^21) the integer scores allow",
-                 n_win, STATES_MAX_WIN);
-        return 1;
-    }
+    if (own)
+        snprintf(err, err_len, "[::] ERROR in %s: NULL %s", fn, own);
+    else if (n_win && !tab)
+        snprintf(err, err_len, "[::] ERROR in %s: NULL table", fn);
+    else if (states_penalties(p01, p02, p12, P, &bad))
+        snprintf(err, err_len, "[::] ERROR in %s: %s = %g is not in (0, 1]", fn, name[bad], bad == 0 ? p01 : bad == 1 ? p02 : p12);
+    else if (n_win > STATES_MAX_WIN)
+        snprintf(err, err_len, "[::] ERROR in %s: %zu windows, more than the %zu (2^21) %s", fn, n_win, STATES_MAX_WIN, max_tail);
+    else
+        return 0;
+    return 1;
+}
+
+// The cores take checked arguments and check nothing.
+// The states recurrence: path [n_win] or NULL, score [n_win][3] or NULL, count[3]
+static void states_core(const double *tab, size_t n_win, const int64_t P[3], uint8_t *path, int64_t *score, uint64_t count[3])
+{
     count[0] = count[1] = count[2] = 0;
     if (n_win == 0)
-        return 0;
+        return;
     const int64_t pen[3][3] = {{0, P[0], P[1]}, {P[0], 0, P[2]}, {P[1], P[2], 0}};
     std::vector<uint8_t> from(n_win);            // from[i][s] in bits 2 s, 2 s + 1
     int64_t v[3];
@@ -108,6 +107,17 @@ int log2_states_host(const double *tab, size_t n_win, double p01, double p02, do
             path[i] = (uint8_t)st;
         st = from[i] >> (2 * st) & 3;
     }
+}
+
+// err: room for a message
+int log2_states_host(const double *tab, size_t n_win, double p01, double p02, double p12, uint8_t *path, int64_t *score,
+                     uint64_t count[3], char *err, size_t err_len)
+{
+    int64_t P[3];
+    if (check_log_args("ibdg_log2_states_host", count ? nullptr : "count", tab, n_win, p01, p02, p12, "the integer scores allow", P,
+                       err, err_len))
+        return 1;
+    states_core(tab, n_win, P, path, score, count);
     return 0;
 }
 
@@ -141,35 +151,15 @@ static void emission_weights(const double *l, const double *T, double b[3])
         b[s] = post_weight(e[s], T, T + 256);
 }
 
-// The sequence of ibdg_states.h, step for step (its numbers are in the comments); the kernel's threads are the loops over b.
-int log2_posteriors_host(const double *tab, size_t n_win, double p01, double p02, double p12, double *post, double expect[3],
-                         double *z_mant, int *z_exp, char *err, size_t err_len)
+// The sum-product pass: the sequence of ibdg_states.h, step for step (its numbers are in the comments); the kernel's threads are
+// the loops over b.  post [n_win][3] or NULL.
+static void posteriors_core(const double *tab, size_t n_win, const int64_t P[3], double *post, double expect[3], double *z_mant,
+                            int *z_exp)
 {
-    int64_t P[3];
-    int bad = 0;
-    if (!expect || !z_mant || !z_exp) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_posteriors_host: NULL %s", expect ? "log2_z" : "expect");
-        return 1;
-    }
-    if (n_win && !tab) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_posteriors_host: NULL table");
-        return 1;
-    }
-    if (states_penalties(p01, p02, p12, P, &bad)) {
-        static const char *const name[3] = {"p01", "p02", "p12"};
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_posteriors_host: %s = %g is not in (0, 1]", name[bad],
-                 bad == 0 ? p01 : bad == 1 ? p02 : p12);
-        return 1;
-    }
-    if (n_win > STATES_MAX_WIN) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_posteriors_host: %zu windows, more than the %zu (2^21) of the path", n_win,
-                 STATES_MAX_WIN);
-        return 1;
-    }
     expect[0] = expect[1] = expect[2] = 0.0;
     *z_mant = 1.0, *z_exp = 0;
     if (n_win == 0)
-        return 0;
+        return;
     const double *T = post_tables();
     double a[3];
     post_penalty_weights(P, a);
@@ -270,42 +260,24 @@ int log2_posteriors_host(const double *tab, size_t n_win, double p01, double p02
             for (int s = 0; s < 3; ++s)
                 part[b][s] = part[b][s] + part[b + d][s];
     expect[0] = part[0][0], expect[1] = part[0][1], expect[2] = part[0][2];
+}
+
+int log2_posteriors_host(const double *tab, size_t n_win, double p01, double p02, double p12, double *post, double expect[3],
+                         double *z_mant, int *z_exp, char *err, size_t err_len)
+{
+    int64_t P[3];
+    if (check_log_args("ibdg_log2_posteriors_host", !expect ? "expect" : !z_mant || !z_exp ? "log2_z" : nullptr, tab, n_win, p01, p02,
+                       p12, "of the path", P, err, err_len))
+        return 1;
+    posteriors_core(tab, n_win, P, post, expect, z_mant, z_exp);
     return 0;
 }
 
-// One walk over the path in window order (ibdg_states.h: every quantity is exact and associative, so this is the kernels'
-// result whatever their blocks).
-int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,
-                       const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err,
-                       size_t err_len)
+// The segment walk: one pass over the path in window order (ibdg_states.h: every quantity is exact and associative, so this is
+// the kernels' result whatever their blocks).  post: the gammas [n_win][3], or NULL for no support.
+static void segments_core(const double *tab, size_t n_win, const uint8_t *path, const double *post, const uint64_t *pos_first,
+                          const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg, uint64_t summary[12])
 {
-    if (!n_seg || !summary) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: NULL %s", n_seg ? "summary" : "n_seg");
-        return 1;
-    }
-    if (!pos_first != !pos_last) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: %s without %s", pos_first ? "pos_first" : "pos_last",
-                 pos_first ? "pos_last" : "pos_first");
-        return 1;
-    }
-    std::vector<uint8_t> path(n_win ? n_win : 1);
-    std::vector<double> post;
-    uint64_t count[3];
-    if (log2_states_host(tab, n_win, p01, p02, p12, path.data(), nullptr, count, err, err_len))
-        return 1;
-    if (with_post) {
-        double expect[3], zm;
-        int ze;
-        post.resize((n_win ? n_win : 1) * 3);
-        if (log2_posteriors_host(tab, n_win, p01, p02, p12, post.data(), expect, &zm, &ze, err, err_len))
-            return 1;
-    }
-    for (size_t w = 0; pos_first && w < n_win; ++w)
-        if (pos_last[w] < pos_first[w]) {
-            snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: window %zu ends at %llu, before its start %llu", w,
-                     (unsigned long long)pos_last[w], (unsigned long long)pos_first[w]);
-            return 1;
-        }
     *n_seg = 0;
     for (int i = 0; i < 12; ++i)
         summary[i] = 0;
@@ -318,14 +290,14 @@ int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, 
             int64_t e[3];
             emission(tab + 3 * w, e);
             r.e[0] += e[0], r.e[1] += e[1], r.e[2] += e[2];
-            if (with_post) {
+            if (post) {
                 const double g = post[3 * w + s];
                 r.post_q += (uint64_t)std::llrint(g * SEG_POST_Q);
                 mn = g < mn ? g : mn;
             }
         }
         r.n_win = (uint32_t)(w - f);
-        r.post_min = with_post ? mn : 0.0;
+        r.post_min = post ? mn : 0.0;
         if (seg && *n_seg < seg_cap)
             seg[*n_seg] = r;
         ++*n_seg;
@@ -338,6 +310,40 @@ int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, 
         }
         f = w;
     }
+}
+
+// (the table and the penalties are refused in the words of ibdg_log2_states_host, whose checks they are)
+int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,
+                       const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err,
+                       size_t err_len)
+{
+    int64_t P[3];
+    if (!n_seg || !summary) {
+        snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: NULL %s", n_seg ? "summary" : "n_seg");
+        return 1;
+    }
+    if (!pos_first != !pos_last) {
+        snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: %s without %s", pos_first ? "pos_first" : "pos_last",
+                 pos_first ? "pos_last" : "pos_first");
+        return 1;
+    }
+    if (check_log_args("ibdg_log2_states_host", nullptr, tab, n_win, p01, p02, p12, "the integer scores allow", P, err, err_len))
+        return 1;
+    for (size_t w = 0; pos_first && w < n_win; ++w)
+        if (pos_last[w] < pos_first[w]) {
+            snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: window %zu ends at %llu, before its start %llu", w,
+                     (unsigned long long)pos_last[w], (unsigned long long)pos_first[w]);
+            return 1;
+        }
+    std::vector<uint8_t> path(n_win);
+    std::vector<double> post(with_post ? n_win * 3 : 0);
+    uint64_t count[3];
+    double expect[3], zm;
+    int ze;
+    states_core(tab, n_win, P, path.data(), nullptr, count);
+    if (with_post)
+        posteriors_core(tab, n_win, P, post.data(), expect, &zm, &ze);
+    segments_core(tab, n_win, path.data(), with_post ? post.data() : nullptr, pos_first, pos_last, seg, seg_cap, n_seg, summary);
     return 0;
 }
 

@@ -1686,6 +1686,17 @@ static void win_table_free(win_table *t)
 }
 
 /* ---- one comparison spread over several GPUs (window ranges, host-side gather) ------------ */
+/* What the run's statistics files hold of one comparison individual, the same record from the device (or the individual's
+ * output job) to the files: a shard's double-double arm sums (ibdg_window_llr_sums), of which the run keeps the four rounded
+ * sums p20, q20, p10, q10 in arm[0..3]; its windows in IBD0, IBD1, IBD2; its expected windows per state and log2 Z; its line of
+ * logibdsegments.txt (the summary of ibdg_window_log2_segments / ibdg_log2_segments_host). */
+typedef struct {
+    double arm[8];
+    uint64_t st[3];
+    double po[4];
+    uint64_t sg[12];
+} ind_stats;
+
 typedef struct {
     ibdg_ctx *eng;
     /* inputs: a contiguous slice [a,b) of the comparison's site list */
@@ -1712,12 +1723,9 @@ typedef struct {
     const uint32_t *next_targets;            /* the batch after this one (NULL: none), queued on the device while the host goes */
     size_t n_next;                           /* through this batch's tables -- window tables only (--summary-only) */
     const uint32_t *arm_seg;                 /* --arm-stats: {p first, p end, q first, q end} in the slice's window indices, or NULL */
-    double arm[8];                           /* ... the individual's sums over them (ibdg_window_llr_sums) */
+    ind_stats out;                           /* ... the individual's sums over them, and with dev_states its other statistics */
     int stats_only;                          /* --stats-only: no window table leaves the device */
     int dev_states;                          /* --log-stats --states --stats-only on one context: the paths are found on the device */
-    uint64_t st[3];                          /* ... the individual's windows in IBD0, IBD1, IBD2 (ibdg_window_log2_states) */
-    double po[4];                            /* ... --posteriors: its expected windows per state and log2 Z (ibdg_window_log2_posteriors) */
-    uint64_t sg[12];                         /* ... --segments: its line of logibdsegments.txt (ibdg_window_log2_segments) */
     const uint32_t *s_row;                   /* ... the site list's panel rows, for the windows' positions */
     FILE *err;                               /* where the pileup's messages go */
     int reported;                            /* a failure was reported here already (not an engine error) */
@@ -1753,6 +1761,18 @@ typedef struct {
 } win_cache;
 static win_cache g_wcache[64];
 
+/* room for `need` elements of `elt` bytes in a scratch array that only grows (its contents are not kept); 0: out of memory */
+static int grow(void *ptr, size_t *cap, size_t need, size_t elt)
+{
+    void **p = ptr;
+    if (*cap < need) {
+        free(*p);
+        *p = malloc(need * elt);
+        *cap = *p ? need : 0;
+    }
+    return *p != NULL;
+}
+
 /* --segments where the tables stay on the device: the windows of the site list at hand in the context's cache (fetched once per
  * list, like the ones the individuals' files take from there) and their positions, which go up with the call */
 static int segments_on_device(shard_job *j, win_cache *wc)
@@ -1769,17 +1789,7 @@ static int segments_on_device(shard_job *j, win_cache *wc)
         wc->n_win = n_win;
         wc->valid = j->same_sites;
     }
-    if (wc->sg_pos_cap < 2 * n_win + 1) {
-        free(wc->sg_pos);
-        wc->sg_pos = malloc((2 * n_win + 1) * sizeof(uint64_t));
-        wc->sg_pos_cap = wc->sg_pos ? 2 * n_win + 1 : 0;
-    }
-    if (wc->sg_cap < T * 13) {
-        free(wc->sg_vals);
-        wc->sg_vals = malloc(T * 13 * sizeof(uint64_t));
-        wc->sg_cap = wc->sg_vals ? T * 13 : 0;
-    }
-    if (!wc->sg_pos || !wc->sg_vals)
+    if (!grow(&wc->sg_pos, &wc->sg_pos_cap, 2 * n_win + 1, sizeof(uint64_t)) || !grow(&wc->sg_vals, &wc->sg_cap, T * 13, sizeof(uint64_t)))
         return 1;
     for (size_t w = 0; w < n_win; ++w) {
         wc->sg_pos[w] = rows[j->s_row[j->a + wc->first[w]]].pos;
@@ -1799,6 +1809,46 @@ static int same_run_size(shard_job *j)
             "the batch at hand.\n", j->dev_idx, have, j->n_targets);
     j->reported = 1;
     return 0;
+}
+
+/* The statistics of every individual of the run at once, before a look-ahead replaces the run's window tables: the arm sums,
+ * and with dev_states the state counts, the posteriors' sums and the segments' summaries -- only these leave the device.  (On
+ * one run the library finds the paths and the posteriors once for the three calls.) */
+static int device_stats(shard_job *j, win_cache *wc)
+{
+    const size_t T = j->n_targets;
+    if (j->arm_seg) {
+        const uint32_t sf[2] = {j->arm_seg[0], j->arm_seg[2]}, se[2] = {j->arm_seg[1], j->arm_seg[3]};
+        if (!grow(&wc->arm_sums, &wc->arm_cap, T * 8, sizeof(double)) || !same_run_size(j) ||
+            (opt_log_stats ? ibdg_window_log2_llr_sums : ibdg_window_llr_sums)(j->eng, sf, se, 2, wc->arm_sums))
+            return 1;
+    }
+    if (!j->dev_states)
+        return 0;
+    if (!grow(&wc->st_counts, &wc->st_cap, T * 3, sizeof(uint64_t)) || !same_run_size(j) ||
+        ibdg_window_log2_states(j->eng, opt_p01, opt_p02, opt_p12, NULL, NULL, wc->st_counts))
+        return 1;
+    if (opt_posteriors && (!grow(&wc->po_vals, &wc->po_cap, T * 4, sizeof(double)) ||
+                           ibdg_window_log2_posteriors(j->eng, opt_p01, opt_p02, opt_p12, NULL, wc->po_vals, wc->po_vals + T * 3)))
+        return 1;
+    return opt_segments && segments_on_device(j, wc);
+}
+
+/* ... and the share of the job's individual in them */
+static void device_stats_of(shard_job *j, const win_cache *wc)
+{
+    const size_t t = j->t_local;
+    if (j->arm_seg)
+        memcpy(j->out.arm, wc->arm_sums + t * 8, sizeof j->out.arm);
+    if (!j->dev_states)
+        return;
+    memcpy(j->out.st, wc->st_counts + t * 3, sizeof j->out.st);
+    if (opt_posteriors) {
+        memcpy(j->out.po, wc->po_vals + t * 3, 3 * sizeof(double));
+        j->out.po[3] = wc->po_vals[j->n_targets * 3 + t];
+    }
+    if (opt_segments)
+        memcpy(j->out.sg, wc->sg_vals + t * 12, sizeof j->out.sg);
 }
 
 static void *shard_run(void *arg)
@@ -1822,41 +1872,8 @@ static void *shard_run(void *arg)
                 return NULL;
         }
         wc->ahead_of = NULL;
-        if (j->arm_seg) {
-            /* every individual of the run at once, before the look-ahead below replaces the run's window tables */
-            const uint32_t sf[2] = {j->arm_seg[0], j->arm_seg[2]}, se[2] = {j->arm_seg[1], j->arm_seg[3]};
-            if (wc->arm_cap < j->n_targets * 8) {
-                free(wc->arm_sums);
-                wc->arm_sums = malloc(j->n_targets * 8 * sizeof(double));
-                wc->arm_cap = wc->arm_sums ? j->n_targets * 8 : 0;
-            }
-            if (!wc->arm_sums || !same_run_size(j) ||
-                (opt_log_stats ? ibdg_window_log2_llr_sums : ibdg_window_llr_sums)(j->eng, sf, se, 2, wc->arm_sums))
-                return NULL;
-        }
-        if (j->dev_states) {
-            /* likewise: only the counts leave the device */
-            if (wc->st_cap < j->n_targets * 3) {
-                free(wc->st_counts);
-                wc->st_counts = malloc(j->n_targets * 3 * sizeof(uint64_t));
-                wc->st_cap = wc->st_counts ? j->n_targets * 3 : 0;
-            }
-            if (!wc->st_counts || !same_run_size(j) ||
-                ibdg_window_log2_states(j->eng, opt_p01, opt_p02, opt_p12, NULL, NULL, wc->st_counts))
-                return NULL;
-            if (opt_posteriors) {
-                if (wc->po_cap < j->n_targets * 4) {
-                    free(wc->po_vals);
-                    wc->po_vals = malloc(j->n_targets * 4 * sizeof(double));
-                    wc->po_cap = wc->po_vals ? j->n_targets * 4 : 0;
-                }
-                if (!wc->po_vals || ibdg_window_log2_posteriors(j->eng, opt_p01, opt_p02, opt_p12, NULL, wc->po_vals,
-                                                                wc->po_vals + j->n_targets * 3))
-                    return NULL;
-            }
-            if (opt_segments && segments_on_device(j, wc))
-                return NULL;
-        }
+        if (device_stats(j, wc))
+            return NULL;
         if (j->stats_only) {
             if (j->next_targets) {                                        /* the next batch runs while the host goes on */
                 if (ibdg_set_option(j->eng, "async", 1) ||
@@ -1896,16 +1913,7 @@ static void *shard_run(void *arg)
             }
         }
     }
-    if (j->arm_seg)
-        memcpy(j->arm, wc->arm_sums + j->t_local * 8, sizeof j->arm);
-    if (j->dev_states)
-        memcpy(j->st, wc->st_counts + j->t_local * 3, sizeof j->st);
-    if (j->dev_states && opt_posteriors) {
-        memcpy(j->po, wc->po_vals + j->t_local * 3, 3 * sizeof(double));
-        j->po[3] = wc->po_vals[j->n_targets * 3 + j->t_local];
-    }
-    if (j->dev_states && opt_segments)
-        memcpy(j->sg, wc->sg_vals + j->t_local * 12, sizeof j->sg);
+    device_stats_of(j, wc);
     j->wt.n_win = ibdg_num_windows(j->eng);
     if (j->stats_only) {
         j->failed = 0;
@@ -2361,11 +2369,9 @@ typedef struct {
     FILE *err;                                  /* where the pileup's messages go */
     /* --states */
     FILE *hg;                                   /* the individual's *.hiddengem.txt (NULL with --stats-only); closed by the job */
-    size_t *st_count;                           /* the individual's line of ibdstates.txt: windows in IBD0, IBD1, IBD2 */
+    ind_stats *res;                             /* the individual's lines of the run's statistics files: the twin's results go here */
     FILE *lp;                                   /* --posteriors: the individual's *.logposteriors.txt (NULL with --stats-only); closed by the job */
-    double *po;                                 /* ... its line of logibdposteriors.txt: expected windows per state, log2 Z */
     FILE *ls;                                   /* --segments: the individual's *.logsegments.txt (NULL with --stats-only); closed by the job */
-    uint64_t *sg;                               /* ... its line of logibdsegments.txt: the summary of ibdg_log2_segments_host */
     hg_path hgp;                                /* the slot's path arrays and text buffer (kept between individuals) */
     char *hg_buf;
     size_t hg_cap;
@@ -2488,6 +2494,14 @@ static int write_states_parallel(FILE *f, const hg_path *h, int threads, char **
  * ibdg_window_log2_states), its scores printed in bits */
 static const char log_hg_header[] = "Segment\tIBD0_LogScore\tIBD1_LogScore\tIBD2_LogScore\tInferred_State\n";
 
+/* an individual's statistics file, where there is one: closed, and forgotten by its job; 1: the close failed */
+static int out_close(FILE **f)
+{
+    const int bad = *f && fclose(*f) != 0;
+    *f = NULL;
+    return bad;
+}
+
 /* --posteriors: the sum-product pass over the same table (ibdg_log2_posteriors_host: the same bytes as the device's
  * ibdg_window_log2_posteriors) */
 static int posteriors_individual(out_job *o)
@@ -2497,7 +2511,7 @@ static int posteriors_individual(out_job *o)
     const size_t n = o->wt.n_win;
     double *post = o->lp ? malloc((n ? n : 1) * 3 * sizeof *post) : NULL;
     int bad = o->lp && !post;
-    if (!bad && ibdg_log2_posteriors_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, post, o->po, o->po + 3)) {
+    if (!bad && ibdg_log2_posteriors_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, post, o->res->po, o->res->po + 3)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
@@ -2510,10 +2524,7 @@ static int posteriors_individual(out_job *o)
             bad = fprintf(o->lp, "%d\t%.6f\t%.6f\t%.6f\t%d\n", (int)(w + 1), g[0], g[1], g[2], m) < 0;
         }
     }
-    if (o->lp) {
-        bad = fclose(o->lp) != 0 || bad;
-        o->lp = NULL;
-    }
+    bad = out_close(&o->lp) || bad;
     free(post);
     return bad;
 }
@@ -2535,7 +2546,7 @@ static int segments_individual(out_job *o)
         pos[w] = o->pos_first ? o->pos_first[w] : rows[o->s_row[o->wt.first[w]]].pos;
         pos[n + w] = o->pos_last ? o->pos_last[w] : rows[o->s_row[o->wt.last[w]]].pos;
     }
-    if (!bad && ibdg_log2_segments_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, opt_posteriors, pos, pos + n, seg, n, &n_seg, o->sg)) {
+    if (!bad && ibdg_log2_segments_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, opt_posteriors, pos, pos + n, seg, n, &n_seg, o->res->sg)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
@@ -2558,10 +2569,7 @@ static int segments_individual(out_job *o)
             bad = bad || fputc('\n', o->ls) == EOF;
         }
     }
-    if (o->ls) {
-        bad = fclose(o->ls) != 0 || bad;
-        o->ls = NULL;
-    }
+    bad = out_close(&o->ls) || bad;
     free(pos);
     free(seg);
     return bad;
@@ -2570,7 +2578,7 @@ static int segments_individual(out_job *o)
 static int log_states_individual(out_job *o)
 {
     const size_t n = o->wt.n_win;
-    uint64_t count[3];
+    uint64_t *const count = o->res->st;
     uint8_t *path = o->hg ? malloc(n ? n : 1) : NULL;
     int64_t *score = o->hg ? malloc((n ? n : 1) * 3 * sizeof *score) : NULL;
     int bad = o->hg && (!path || !score);
@@ -2578,25 +2586,16 @@ static int log_states_individual(out_job *o)
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
-    if (!bad) {
-        for (int s = 0; s < 3; ++s)
-            o->st_count[s] = (size_t)count[s];
-        if (o->hg) {
-            hg_path tail = {0};
-            char buf[256];
-            tail.n = n;
-            memcpy(tail.count, o->st_count, sizeof tail.count);
-            bad = fputs(log_hg_header, o->hg) < 0;
-            for (size_t w = 0; w < n && !bad; ++w)
-                bad = fprintf(o->hg, "%d\t%.4Lf\t%.4Lf\t%.4Lf\t%d\n", (int)(w + 1), (long double)score[3 * w] / 65536,
-                              (long double)score[3 * w + 1] / 65536, (long double)score[3 * w + 2] / 65536, path[w]) < 0;
-            bad = bad || fwrite(buf, 1, hg_format_tail(&tail, buf), o->hg) == 0;
-        }
+    if (!bad && o->hg) {
+        hg_path tail = {.n = n, .count = {(size_t)count[0], (size_t)count[1], (size_t)count[2]}};
+        char buf[256];
+        bad = fputs(log_hg_header, o->hg) < 0;
+        for (size_t w = 0; w < n && !bad; ++w)
+            bad = fprintf(o->hg, "%d\t%.4Lf\t%.4Lf\t%.4Lf\t%d\n", (int)(w + 1), (long double)score[3 * w] / 65536,
+                          (long double)score[3 * w + 1] / 65536, (long double)score[3 * w + 2] / 65536, path[w]) < 0;
+        bad = bad || fwrite(buf, 1, hg_format_tail(&tail, buf), o->hg) == 0;
     }
-    if (o->hg) {
-        bad = fclose(o->hg) != 0 || bad;
-        o->hg = NULL;
-    }
+    bad = out_close(&o->hg) || bad;
     free(path);
     free(score);
     bad = posteriors_individual(o) || bad;
@@ -2616,13 +2615,12 @@ static int states_individual(out_job *o)
             return 1;
     if (hg_solve(h, opt_p01, opt_p02, opt_p12))
         return 1;
-    memcpy(o->st_count, h->count, sizeof h->count);
+    for (int s = 0; s < 3; ++s)
+        o->res->st[s] = h->count[s];
     if (!o->hg)
         return 0;
-    int bad = write_states_parallel(o->hg, h, o->threads, &o->hg_buf, &o->hg_cap);
-    bad = fclose(o->hg) != 0 || bad;
-    o->hg = NULL;
-    return bad;
+    const int bad = write_states_parallel(o->hg, h, o->threads, &o->hg_buf, &o->hg_cap);
+    return out_close(&o->hg) || bad;
 }
 
 static void *output_individual(void *arg)
@@ -3023,6 +3021,8 @@ typedef struct {
     uint32_t *row_pre_off;
 } site_list;
 
+enum { N_RUN_FILES = 3 };           /* RUN_FILES below */
+
 typedef struct {
     /* ---- the pileup's run ---- */
     pile_job *pj;
@@ -3031,16 +3031,9 @@ typedef struct {
     int one_list;                   /* no -v, no -D: the site list does not depend on the comparison individual (:584, :627-628) */
     int overlap, dev_v, batchable, arm_on, tables_stay, dev_states, out_slots, out_threads_env;
     size_t n_site_out;              /* entries of an individual's per-site array */
-    double *arm_res;                /* --arm-stats, per individual: p20, q20, p10, q10; the run's armstats.txt */
-    size_t *st_res;                 /* --states: per individual the windows in IBD0, IBD1, IBD2; the run's ibdstates.txt */
-    FILE *st_file;
-    char *st_fn;
-    double *po_res;                 /* --posteriors: per individual the expected windows in IBD0, IBD1, IBD2 and log2 Z; the run's logibdposteriors.txt */
-    FILE *po_file;
-    char *po_fn;
-    uint64_t *sg_res;               /* --segments: per individual the summary of its segments [12]; the run's logibdsegments.txt */
-    FILE *sg_file;
-    char *sg_fn;
+    ind_stats *res;                 /* per individual, what the run's statistics files are written from (run_end) */
+    FILE *run_file[N_RUN_FILES];    /* the files of RUN_FILES, open from run_begin to run_end */
+    char *run_fn[N_RUN_FILES];
     double *site_slot[OUT_SLOTS];   /* the per-site array of each output slot */
     uint32_t *c_row;                /* dev_v: the candidates as the engine takes them */
     uint8_t *c_nr, *c_na;
@@ -3094,7 +3087,94 @@ static void run_modes(pile_run *r)
     r->tables_stay = r->tables_stay || r->dev_states;
 }
 
-/* the run's arrays and its --states file */
+/* ---- the statistics files a run writes once, after its last individual, from the individuals' records (r->res) ---- */
+
+/* one line per comparison individual in the order of the summaries, as bin/sum-hiddengem.py prints a row, then its totals over
+ * the pileup's individuals */
+static void write_states_file(pile_run *r, FILE *f)
+{
+    size_t total[3] = {0, 0, 0};
+    fprintf(f, "# ID\tN_SEGMENTS\tN_IBD0\tN_IBD1\tN_IBD2\tFRAC_IBD0\tFRAC_IBD1\tFRAC_IBD2\n");
+    for (size_t ti = 0; ti < g_targets.n; ++ti) {
+        const uint64_t *st = r->res[ti].st;
+        const size_t count[3] = {(size_t)st[0], (size_t)st[1], (size_t)st[2]};
+        hg_frac_row(f, g_ids.names[g_targets.idx[ti]], count);
+        for (int k = 0; k < 3; ++k)
+            total[k] += count[k];
+    }
+    hg_frac_totals(f, total);
+}
+
+/* likewise, laid out like the fractions file: the expected windows per state where that one has counts, and log2 Z */
+static void write_posteriors_file(pile_run *r, FILE *f)
+{
+    double total[3] = {0.0, 0.0, 0.0};
+    size_t total_n = 0;
+    fprintf(f, "# ID\tN_SEGMENTS\tE_IBD0\tE_IBD1\tE_IBD2\tFRAC_IBD0\tFRAC_IBD1\tFRAC_IBD2\tLOG2_Z\n");
+    for (size_t ti = 0; ti < g_targets.n; ++ti) {
+        const double *e = r->res[ti].po;
+        const size_t n = (size_t)(r->res[ti].st[0] + r->res[ti].st[1] + r->res[ti].st[2]);
+        fprintf(f, "%s\t%zu\t%.3f\t%.3f\t%.3f", g_ids.names[g_targets.idx[ti]], n, e[0], e[1], e[2]);
+        for (int k = 0; k < 3; ++k) {
+            if (n)
+                fprintf(f, "\t%.6f", e[k] / (double)n);
+            else
+                fputs("\tnan", f);
+            total[k] += e[k];
+        }
+        fprintf(f, "\t%.6f\n", e[3]);
+        total_n += n;
+    }
+    fprintf(f, "# Total segments = %zu\n", total_n);
+    for (int k = 0; k < 3; ++k) {
+        if (total_n)
+            fprintf(f, "# Total E_IBD%d = %.3f (%.3f %%)\n", k, total[k], total[k] / (double)total_n * 100);
+        else
+            fprintf(f, "# Total E_IBD%d = %.3f (nan %%)\n", k, total[k]);
+    }
+}
+
+/* likewise: per individual and state the four numbers of its segments, then the totals (sums of the counts and base pairs,
+ * maxima of the two longest) */
+static void write_segments_file(pile_run *r, FILE *f)
+{
+    static const char *const col[4] = {"N_SEG", "LONGEST_WIN", "TOTAL_BP", "LONGEST_BP"};
+    uint64_t total[12] = {0};
+    fputs("# ID", f);
+    for (int s = 0; s < 3; ++s)
+        for (int k = 0; k < 4; ++k)
+            fprintf(f, "\tIBD%d_%s", s, col[k]);
+    fputc('\n', f);
+    for (size_t ti = 0; ti < g_targets.n; ++ti) {
+        const uint64_t *g = r->res[ti].sg;
+        fputs(g_ids.names[g_targets.idx[ti]], f);
+        for (int s = 0; s < 3; ++s)
+            for (int k = 0; k < 4; ++k) {
+                const uint64_t v = g[3 * k + s];
+                fprintf(f, "\t%llu", (unsigned long long)v);
+                total[3 * k + s] = k & 1 ? (v > total[3 * k + s] ? v : total[3 * k + s]) : total[3 * k + s] + v;
+            }
+        fputc('\n', f);
+    }
+    for (int s = 0; s < 3; ++s)
+        fprintf(f, "# Total IBD%d: N_SEG = %llu, LONGEST_WIN = %llu, TOTAL_BP = %llu, LONGEST_BP = %llu\n", s,
+                (unsigned long long)total[s], (unsigned long long)total[3 + s], (unsigned long long)total[6 + s],
+                (unsigned long long)total[9 + s]);
+}
+
+/* <out>/<pileup-name>.[log]<kind>.txt (the last two exist with --log-stats only), in the order they are opened and written.
+ * armstats.txt is not among them: it is opened where it is written, in run_end. */
+static const struct {
+    const int *on;
+    const char *kind, *phase;
+    void (*write)(pile_run *, FILE *);
+} RUN_FILES[N_RUN_FILES] = {
+    {&opt_states, "ibdstates", "IBD-state fractions file", write_states_file},
+    {&opt_posteriors, "ibdposteriors", "IBD-state posteriors file", write_posteriors_file},
+    {&opt_segments, "ibdsegments", "IBD-state segments file", write_segments_file},
+};
+
+/* the run's arrays and its statistics files */
 static int run_begin(pile_run *r)
 {
     site_list *sl = &r->sl;
@@ -3109,40 +3189,19 @@ static int run_begin(pile_run *r)
     if (!sl->s_row || !sl->s_cand || !sl->s_nr || !sl->s_na || !r->site_ll)
         SFAIL("[::] ERROR: out of memory for %zu rows.\n", r->pj->n_cand);
     phase("result arrays");
-    if (opt_states) {
-        r->st_res = calloc(g_targets.n + 1, 3 * sizeof(size_t));
-        /* opened before the run, like the individuals' files: a directory that cannot be written stops the run at once */
-        if (!r->st_res)
-            SFAIL("[::] ERROR: out of memory.\n");
-        if (asprintf(&r->st_fn, "%s/%s.%s.txt", g_out_dir, r->pj->name, opt_log_stats ? "logibdstates" : "ibdstates") < 0)
-            return r->st_fn = NULL, 1;
-        if (!(r->st_file = fopen(r->st_fn, "w")))
-            SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->st_fn);
-        pj_add_file(r->pj, r->st_fn);
-    }
-    if (opt_posteriors) {
-        r->po_res = calloc(g_targets.n + 1, 4 * sizeof(double));
-        if (!r->po_res)
-            SFAIL("[::] ERROR: out of memory.\n");
-        if (asprintf(&r->po_fn, "%s/%s.logibdposteriors.txt", g_out_dir, r->pj->name) < 0)
-            return r->po_fn = NULL, 1;
-        if (!(r->po_file = fopen(r->po_fn, "w")))
-            SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->po_fn);
-        pj_add_file(r->pj, r->po_fn);
-    }
-    if (opt_segments) {
-        r->sg_res = calloc(g_targets.n + 1, 12 * sizeof(uint64_t));
-        if (!r->sg_res)
-            SFAIL("[::] ERROR: out of memory.\n");
-        if (asprintf(&r->sg_fn, "%s/%s.logibdsegments.txt", g_out_dir, r->pj->name) < 0)
-            return r->sg_fn = NULL, 1;
-        if (!(r->sg_file = fopen(r->sg_fn, "w")))
-            SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->sg_fn);
-        pj_add_file(r->pj, r->sg_fn);
-    }
-    r->arm_res = r->arm_on ? malloc((g_targets.n + 1) * 4 * sizeof(double)) : NULL;
-    if (r->arm_on && !r->arm_res)
+    r->res = calloc(g_targets.n + 1, sizeof *r->res);
+    if (!r->res)
         SFAIL("[::] ERROR: out of memory.\n");
+    /* opened before the run, like the individuals' files: a directory that cannot be written stops the run at once */
+    for (int k = 0; k < N_RUN_FILES; ++k) {
+        if (!*RUN_FILES[k].on)
+            continue;
+        if (asprintf(&r->run_fn[k], "%s/%s.%s%s.txt", g_out_dir, r->pj->name, opt_log_stats ? "log" : "", RUN_FILES[k].kind) < 0)
+            return r->run_fn[k] = NULL, 1;
+        if (!(r->run_file[k] = fopen(r->run_fn[k], "w")))
+            SFAIL("[::] ERROR: Cannot open '%s' for writing.\n", r->run_fn[k]);
+        pj_add_file(r->pj, r->run_fn[k]);
+    }
     return 0;
 }
 
@@ -3333,7 +3392,7 @@ static int windows_on_host(pile_run *r)
     if (r->arm_on) {
         uint32_t seg[4];
         int ok[2];
-        double p[4], q[4], *res = r->arm_res + 4 * r->ti;
+        double p[4], q[4], *res = r->res[r->ti].arm;
         arm_segments(sl->s_row, t->first, t->last, t->n_win, seg, ok);
         const double *tab = opt_log_stats ? t->log : t->ll;
         llr_range_host(tab, opt_log_stats, seg[0], seg[1], p);
@@ -3461,13 +3520,13 @@ static int shards_run(pile_run *r, shard_job *jobs)
 static int arm_gather(pile_run *r, const shard_job *jobs)
 {
     const site_list *sl = &r->sl;
-    double acc[8] = {0}, *res = r->arm_res + 4 * r->ti;
+    double acc[8] = {0}, *res = r->res[r->ti].arm;
     for (int d = 0; d < r->w->n_eng; ++d) {
         if (jobs[d].wt.n_win != sl->arm_wcut[d + 1] - sl->arm_wcut[d])
             SFAIL("[::] ERROR: device %d holds %zu windows, not the %u of its range.\n", d, jobs[d].wt.n_win,
                   sl->arm_wcut[d + 1] - sl->arm_wcut[d]);
         for (int k = 0; k < 4; ++k)
-            dd_add(acc + 2 * k, jobs[d].arm[2 * k], jobs[d].arm[2 * k + 1]);
+            dd_add(acc + 2 * k, jobs[d].out.arm[2 * k], jobs[d].out.arm[2 * k + 1]);
     }
     res[0] = sl->arm_ok[0] ? acc[0] + acc[1] : NAN; res[1] = sl->arm_ok[1] ? acc[4] + acc[5] : NAN;
     res[2] = sl->arm_ok[0] ? acc[2] + acc[3] : NAN; res[3] = sl->arm_ok[1] ? acc[6] + acc[7] : NAN;
@@ -3520,15 +3579,12 @@ static int windows_on_engine(pile_run *r)
         if (ibdg_set_option(r->w->engs[d], "compact_tiles", r->batchable && opt_ld && !opt_ref_order && g_targets.n >= 240))
             SFAIL("%s\n", ibdg_last_error(r->w->engs[d]));
     shards_fill(r, jobs);
-    if (shards_run(r, jobs) || (r->arm_on && arm_gather(r, jobs)))
+    if (shards_run(r, jobs))
         return 1;
     if (r->dev_states)
-        for (int k = 0; k < 3; ++k)
-            r->st_res[3 * r->ti + k] = (size_t)jobs[0].st[k];
-    if (r->dev_states && opt_posteriors)
-        memcpy(r->po_res + 4 * r->ti, jobs[0].po, sizeof jobs[0].po);
-    if (r->dev_states && opt_segments)
-        memcpy(r->sg_res + 12 * r->ti, jobs[0].sg, sizeof jobs[0].sg);
+        r->res[r->ti] = jobs[0].out;         /* (one context: its record is the individual's; the arm sums follow) */
+    if (r->arm_on && arm_gather(r, jobs))
+        return 1;
     if (r->tables_stay)                      /* no window table left the device */
         return 0;
     tables_gather(r, jobs);
@@ -3619,9 +3675,7 @@ static int output_start(pile_run *r)
     o->wt = r->wt;
     memset(&r->wt, 0, sizeof r->wt);
     o->sq = pj->name; o->err = r->err;
-    o->st_count = r->st_res ? r->st_res + 3 * r->ti : NULL;
-    o->po = r->po_res ? r->po_res + 4 * r->ti : NULL;
-    o->sg = r->sg_res ? r->sg_res + 12 * r->ti : NULL;
+    o->res = &r->res[r->ti];
     if (outputs_open(r, o))
         return 1;
     const int threads = all_threads();
@@ -3655,7 +3709,7 @@ static int run_end(pile_run *r)
         for (size_t ti = 0; ti < targets.n; ++ti) {
             fprintf(af, "%s\t%s", g_ids.names[targets.idx[ti]], chrom);
             for (int k = 0; k < 4; ++k) {
-                const double v = r->arm_res[4 * ti + k];
+                const double v = r->res[ti].arm[k];
                 if (isnan(v))
                     fprintf(af, "\tnan");
                 else
@@ -3668,85 +3722,15 @@ static int run_end(pile_run *r)
         free(arm_fn);
         phase("arm statistics file");
     }
-    if (opt_states) {
-        /* one file for the run, like the arm statistics: a line per comparison individual in the order of the summaries, as
-         * bin/sum-hiddengem.py prints a row, then its totals over the pileup's individuals */
-        size_t total[3] = {0, 0, 0};
-        fprintf(r->st_file, "# ID\tN_SEGMENTS\tN_IBD0\tN_IBD1\tN_IBD2\tFRAC_IBD0\tFRAC_IBD1\tFRAC_IBD2\n");
-        for (size_t ti = 0; ti < targets.n; ++ti) {
-            hg_frac_row(r->st_file, g_ids.names[targets.idx[ti]], r->st_res + 3 * ti);
-            for (int k = 0; k < 3; ++k)
-                total[k] += r->st_res[3 * ti + k];
-        }
-        hg_frac_totals(r->st_file, total);
-        FILE *f = r->st_file;
-        r->st_file = NULL;
+    for (int k = 0; k < N_RUN_FILES; ++k) {
+        FILE *f = r->run_file[k];
+        if (!f)
+            continue;
+        RUN_FILES[k].write(r, f);
+        r->run_file[k] = NULL;
         if (fclose(f) != 0)
-            SFAIL("[::] ERROR writing '%s'.\n", r->st_fn);
-        phase("IBD-state fractions file");
-    }
-    if (opt_posteriors) {
-        /* likewise, laid out like the fractions file: the expected windows per state where that one has counts, and log2 Z */
-        double total[3] = {0.0, 0.0, 0.0};
-        size_t total_n = 0;
-        fprintf(r->po_file, "# ID\tN_SEGMENTS\tE_IBD0\tE_IBD1\tE_IBD2\tFRAC_IBD0\tFRAC_IBD1\tFRAC_IBD2\tLOG2_Z\n");
-        for (size_t ti = 0; ti < targets.n; ++ti) {
-            const double *e = r->po_res + 4 * ti;
-            const size_t n = r->st_res[3 * ti] + r->st_res[3 * ti + 1] + r->st_res[3 * ti + 2];
-            fprintf(r->po_file, "%s\t%zu\t%.3f\t%.3f\t%.3f", g_ids.names[targets.idx[ti]], n, e[0], e[1], e[2]);
-            for (int k = 0; k < 3; ++k) {
-                if (n)
-                    fprintf(r->po_file, "\t%.6f", e[k] / (double)n);
-                else
-                    fputs("\tnan", r->po_file);
-                total[k] += e[k];
-            }
-            fprintf(r->po_file, "\t%.6f\n", e[3]);
-            total_n += n;
-        }
-        fprintf(r->po_file, "# Total segments = %zu\n", total_n);
-        for (int k = 0; k < 3; ++k) {
-            if (total_n)
-                fprintf(r->po_file, "# Total E_IBD%d = %.3f (%.3f %%)\n", k, total[k], total[k] / (double)total_n * 100);
-            else
-                fprintf(r->po_file, "# Total E_IBD%d = %.3f (nan %%)\n", k, total[k]);
-        }
-        FILE *f = r->po_file;
-        r->po_file = NULL;
-        if (fclose(f) != 0)
-            SFAIL("[::] ERROR writing '%s'.\n", r->po_fn);
-        phase("IBD-state posteriors file");
-    }
-    if (opt_segments) {
-        /* likewise: per individual and state the four numbers of its segments, then the totals (sums of the counts and base
-         * pairs, maxima of the two longest) */
-        static const char *const col[4] = {"N_SEG", "LONGEST_WIN", "TOTAL_BP", "LONGEST_BP"};
-        uint64_t total[12] = {0};
-        fputs("# ID", r->sg_file);
-        for (int s = 0; s < 3; ++s)
-            for (int k = 0; k < 4; ++k)
-                fprintf(r->sg_file, "\tIBD%d_%s", s, col[k]);
-        fputc('\n', r->sg_file);
-        for (size_t ti = 0; ti < targets.n; ++ti) {
-            const uint64_t *g = r->sg_res + 12 * ti;
-            fputs(g_ids.names[targets.idx[ti]], r->sg_file);
-            for (int s = 0; s < 3; ++s)
-                for (int k = 0; k < 4; ++k) {
-                    const uint64_t v = g[3 * k + s];
-                    fprintf(r->sg_file, "\t%llu", (unsigned long long)v);
-                    total[3 * k + s] = k & 1 ? (v > total[3 * k + s] ? v : total[3 * k + s]) : total[3 * k + s] + v;
-                }
-            fputc('\n', r->sg_file);
-        }
-        for (int s = 0; s < 3; ++s)
-            fprintf(r->sg_file, "# Total IBD%d: N_SEG = %llu, LONGEST_WIN = %llu, TOTAL_BP = %llu, LONGEST_BP = %llu\n", s,
-                    (unsigned long long)total[s], (unsigned long long)total[3 + s], (unsigned long long)total[6 + s],
-                    (unsigned long long)total[9 + s]);
-        FILE *f = r->sg_file;
-        r->sg_file = NULL;
-        if (fclose(f) != 0)
-            SFAIL("[::] ERROR writing '%s'.\n", r->sg_fn);
-        phase("IBD-state segments file");
+            SFAIL("[::] ERROR writing '%s'.\n", r->run_fn[k]);
+        phase(RUN_FILES[k].phase);
     }
     return 0;
 }
@@ -3756,19 +3740,21 @@ static int run_end(pile_run *r)
 static void run_release(pile_run *r)
 {
     site_list *sl = &r->sl;
-    free(r->st_fn); free(r->st_res); free(sl->row_pre); free(sl->row_pre_off);
-    free(r->po_fn); free(r->po_res);
-    free(r->sg_fn); free(r->sg_res);
-    r->st_fn = r->po_fn = r->sg_fn = sl->row_pre = NULL;
-    r->st_res = NULL;
-    r->po_res = NULL;
-    r->sg_res = NULL;
+    for (int k = 0; k < N_RUN_FILES; ++k) {
+        if (r->run_file[k])
+            fclose(r->run_file[k]);           /* (a failed run's: opened empty, left empty) */
+        free(r->run_fn[k]);
+        r->run_file[k] = NULL, r->run_fn[k] = NULL;
+    }
+    free(r->res); free(sl->row_pre); free(sl->row_pre_off);
+    r->res = NULL;
+    sl->row_pre = NULL;
     sl->row_pre_off = NULL;
     if (!g_list_mode)
         return;
     for (int k = 0; k < OUT_SLOTS; ++k)
         free(r->site_slot[k]);
-    free(r->c_row); free(r->c_nr); free(r->c_na); free(r->c_fo); free(r->arm_res);
+    free(r->c_row); free(r->c_nr); free(r->c_na); free(r->c_fo);
     site_list_reset(sl);
     free(sl->s_row); free(sl->s_cand); free(sl->s_nr); free(sl->s_na); free(sl->s_fo);
 }
@@ -3827,12 +3813,6 @@ static int pj_run(pile_job *pj, worker_t *w)
     return 0;
 fail:
     outs_settle_one(outs, 1);
-    if (r.st_file)
-        fclose(r.st_file);                /* (opened empty, left empty) */
-    if (r.po_file)
-        fclose(r.po_file);
-    if (r.sg_file)
-        fclose(r.sg_file);
     run_release(&r);
     return 1;
 }

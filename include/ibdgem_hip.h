@@ -295,7 +295,8 @@ int ibdg_log2_segments_host(const double *log2_tab, size_t n_win, double p01, do
                             const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap,
                             uint64_t *n_seg, uint64_t summary[12]);
 /* The same for every comparison individual of the last ibdg_run, on the device: the kernel of ibdg_window_log2_states, with
- * with_post that of ibdg_window_log2_posteriors, then one that counts.  pos_first / pos_last [n_win] (both or neither) are the
+ * with_post that of ibdg_window_log2_posteriors -- neither is launched again where that call was made with these penalties since
+ * the last ibdg_run --, then one that counts.  pos_first / pos_last [n_win] (both or neither) are the
  * site list's, shared by the individuals.  n_seg[T], summary[T][12]: 104 bytes per individual leave the device.  Same waits
  * as ibdg_get_window_log2; returns with the outputs in host memory.  n_win = 0: zeros.  Errors: no results, the last ibdg_run
  * made with option "log_windows" off, a penalty out of range, more than 2^21 windows, NULL n_seg or summary, one position

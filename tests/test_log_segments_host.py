@@ -128,6 +128,23 @@ def test_random_tables(n, pen):
     assert sum0[:6].tobytes() == summary[:6].tobytes()
 
 
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("pen", PENS)
+def test_the_three_twins_agree(n, pen):
+    """ibdg_log2_segments_host runs the same recurrence and the same sum-product pass as its two neighbours: its records and
+    summary with posteriors, assembled from THEIR path and gammas (restated), and the bytes of its post_min against the gammas'."""
+    tab, pos = random_table(n), positions(n)
+    seg, n_seg, summary = E.log2_segments_host(tab, *pen, with_post=True, pos_first=pos[0], pos_last=pos[1])
+    recs, summ, count = restated(tab, pen, with_post=True, pos=pos)
+    assert n_seg == len(recs) and as_tuples(seg) == recs and [int(x) for x in summary] == summ
+    path, _, count2 = E.log2_states_host(tab, *pen, want_score=False)
+    post = E.log2_posteriors_host(tab, *pen)[0]
+    assert count2.tobytes() == count.tobytes()
+    assert np.repeat(seg["state"], seg["n_win"]).astype(np.uint8).tobytes() == path.astype(np.uint8).tobytes()
+    mins = np.array([post[int(r["first"]):int(r["first"]) + int(r["n_win"]), int(r["state"])].min() for r in seg])
+    assert seg["post_min"].tobytes() == mins.astype(np.float64).tobytes()
+
+
 def test_random_tables_show_every_case():
     """What the random tables are there for: at 601 windows the small penalties give many segments of all three states."""
     seg, n_seg, _ = twin_checked(random_table(601), (0.5, 0.25, 0.5))

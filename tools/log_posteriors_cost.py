@@ -4,7 +4,8 @@ comparison individuals of one --LD run with "log_windows" 1, the wall clock of
   ibdg_window_log2_states      counts only, beside it,
   ibdg_log2_posteriors_host    the host twin over the same tables (one thread), after ibdg_get_window_log2_all: with that
                                copy, the ceiling the device route has to stay under,
-each the best and median of --reps calls, in ms per comparison individual; and that device and twin agree on every byte.
+each the best and median of --reps calls, in ms per comparison individual -- every timed call behind an untimed one with other
+penalties, so that it finds nothing kept from the repetition before --; and that device and twin agree on every byte.
 The kernels' own times (k_log2_posteriors beside k_log2_states) come from a kernel trace of this script, in a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/log_posteriors_cost.py --reps 3 --batches 60,240
     python tools/log_posteriors_cost.py [--sites N] [--reps R] [--batches 60,240]   (on a GPU box)"""
@@ -29,6 +30,7 @@ ROWS, N_IDS, W = arg("--sites", 4_000_000), 2504, 100
 REPS = arg("--reps", 5)
 BATCHES = [int(x) for x in arg("--batches", "60,240").split(",")]
 PEN = (1e-3, 1e-6, 1e-3)
+OTHER = (0.25, 0.125, 0.25)
 
 dev = torch.device("cuda", 0)
 panel, n_ref, n_alt = bench.build_shard(torch, dev, 0, ROWS, N_IDS, 7, 20241008)
@@ -45,9 +47,12 @@ print(f"{ROWS} rows x {N_IDS} individuals, W = {W}, {n} windows ({n * 24 / 1e6:.
       f"{-(-n // 256)} windows a thread; {REPS} repetitions", flush=True)
 
 
-def clock(fn):
+def clock(fn, before=None):
+    """before: untimed, in front of every repetition (a call with OTHER penalties, so that the timed one finds nothing kept)"""
     ms = []
     for _ in range(REPS):
+        if before:
+            before()
         t0 = time.perf_counter()
         out = fn()
         ms.append((time.perf_counter() - t0) * 1e3)
@@ -60,9 +65,11 @@ for T in BATCHES:
     eng.sync()
     eng.window_log2_posteriors(*PEN, want_post=False)                          # (buffers allocated: untimed)
     eng.window_log2_states(*PEN, want_path=False, want_score=False)
-    (_, e0, z0), b0, m0 = clock(lambda: eng.window_log2_posteriors(*PEN, want_post=False))
-    (p1, e1, z1), b1, m1 = clock(lambda: eng.window_log2_posteriors(*PEN))
-    _, bs, ms_ = clock(lambda: eng.window_log2_states(*PEN, want_path=False, want_score=False))
+    stale_post = lambda: eng.window_log2_posteriors(*OTHER, want_post=False)
+    (_, e0, z0), b0, m0 = clock(lambda: eng.window_log2_posteriors(*PEN, want_post=False), stale_post)
+    (p1, e1, z1), b1, m1 = clock(lambda: eng.window_log2_posteriors(*PEN), stale_post)
+    _, bs, ms_ = clock(lambda: eng.window_log2_states(*PEN, want_path=False, want_score=False),
+                       lambda: eng.window_log2_states(*OTHER, want_path=False, want_score=False))
     tabs, bt, mt = clock(lambda: eng.window_log2_all(T))
     twin, bh, mh = clock(lambda: [E.log2_posteriors_host(tabs[t], *PEN) for t in range(T)])
     same = all(twin[t][0].tobytes() == p1[t].tobytes() and twin[t][1].tobytes() == e1[t].tobytes() and

@@ -5,8 +5,11 @@ comparison individuals of one --LD run with "log_windows" 1, the wall clock of
   ibdg_window_log2_segments    without and with the posteriors (it runs the kernels of the two calls above and then counts:
                                what it adds is its time less theirs), with the windows' positions,
   ibdg_get_log2_segments       the records of that call,
+  the three calls in turn      states, posteriors, segments with the posteriors, as --stats-only --posteriors --segments issues
+                               them per batch (the segments call then finds the path and the posteriors made),
   ibdg_log2_segments_host      the host twin over the same tables (one thread), after ibdg_get_window_log2_all,
-each the best and median of --reps calls, in ms per comparison individual; and that device and twin agree on every byte.
+each the best and median of --reps calls, in ms per comparison individual -- every timed call behind untimed calls with other
+penalties, so that it finds nothing kept from the repetition before --; and that device and twin agree on every byte.
 The kernels' own times (k_log2_segments_count, k_log2_segments_write beside k_log2_states) come from a kernel trace of this
 script, in a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/log_segments_cost.py --reps 3 --batches 60,240
@@ -31,11 +34,15 @@ REPS = arg("--reps", 5)
 BATCHES = [int(x) for x in arg("--batches", "60,240").split(",")]
 PEN = (1e-3, 1e-6, 1e-3)
 SMALL = (0.5, 0.25, 0.5)             # about a bit a switch: many segments, for the records' cost
+OTHER = (0.25, 0.125, 0.25)          # what the untimed calls between two repetitions leave a path and posteriors for
 
 
-def clock(fn):
+def clock(fn, before=None):
+    """before: untimed, in front of every repetition (a call with OTHER penalties, so that the timed one finds nothing kept)"""
     ms = []
     for _ in range(REPS):
+        if before:
+            before()
         t0 = time.perf_counter()
         out = fn()
         ms.append((time.perf_counter() - t0) * 1e3)
@@ -91,15 +98,25 @@ for T in BATCHES:
     for name, pen in (("default penalties", PEN), ("(0.5, 0.25, 0.5)", SMALL)):
         eng.window_log2_segments(*pen, with_post=True, pos_first=pf, pos_last=pl)       # (buffers allocated: untimed)
         eng.get_log2_segments()
-        _, bs, ms_ = clock(lambda: eng.window_log2_states(*pen, want_path=False, want_score=False))
-        _, bp, mp = clock(lambda: eng.window_log2_posteriors(*pen, want_post=False))
-        (n0, s0), b0, m0 = clock(lambda: eng.window_log2_segments(*pen, pos_first=pf, pos_last=pl))
+        def stale():
+            eng.window_log2_states(*OTHER, want_path=False, want_score=False)
+            eng.window_log2_posteriors(*OTHER, want_post=False)
+
+        def as_shard_run():                  # the three calls of --stats-only --posteriors --segments on one batch
+            eng.window_log2_states(*pen, want_path=False, want_score=False)
+            eng.window_log2_posteriors(*pen, want_post=False)
+            return eng.window_log2_segments(*pen, with_post=True, pos_first=pf, pos_last=pl)
+
+        _, bs, ms_ = clock(lambda: eng.window_log2_states(*pen, want_path=False, want_score=False), stale)
+        _, bp, mp = clock(lambda: eng.window_log2_posteriors(*pen, want_post=False), stale)
+        (n0, s0), b0, m0 = clock(lambda: eng.window_log2_segments(*pen, pos_first=pf, pos_last=pl), stale)
         r0, bg0, mg0 = clock(lambda: eng.get_log2_segments())
-        (n1, s1), b1, m1 = clock(lambda: eng.window_log2_segments(*pen, with_post=True, pos_first=pf, pos_last=pl))
+        (n1, s1), b1, m1 = clock(lambda: eng.window_log2_segments(*pen, with_post=True, pos_first=pf, pos_last=pl), stale)
         r1, bg1, mg1 = clock(lambda: eng.get_log2_segments())
+        (n2, s2), b2, m2 = clock(as_shard_run, stale)
         tabs, bt, mt = clock(lambda: eng.window_log2_all(T))
         twin, bh, mh = clock(lambda: [E.log2_segments_host(tabs[t], *pen, with_post=True, pos_first=pf, pos_last=pl) for t in range(T)])
-        same = n0.tobytes() == n1.tobytes() and s0.tobytes() == s1.tobytes()
+        same = n0.tobytes() == n1.tobytes() == n2.tobytes() and s0.tobytes() == s1.tobytes() == s2.tobytes()
         same = same and all(int(n1[t]) == twin[t][1] and s1[t].tobytes() == twin[t][2].tobytes() for t in range(T))
         same = same and r1.tobytes() == b"".join(twin[t][0].tobytes() for t in range(T))
         add0, add1 = b0 - bs, b1 - bs - bp
@@ -112,6 +129,7 @@ for T in BATCHES:
               f"  ... their records                      {bg0 * f:8.4f} ({mg0 * f:.4f})\n"
               f"  segments, with posteriors              {b1 * f:8.4f} ({m1 * f:.4f})   adds {add1 * f:.4f} to the two calls\n"
               f"  ... their records                      {bg1 * f:8.4f} ({mg1 * f:.4f})\n"
+              f"  states, posteriors, segments in turn   {b2 * f:8.4f} ({m2 * f:.4f})   the three calls alone add up to {(bs + bp + b1) * f:.4f}\n"
               f"  tables to the host                     {bt * f:8.4f} ({mt * f:.4f})\n"
               f"  host twin with posteriors, one thread  {bh * f:8.4f} ({mh * f:.4f})\n"
               f"  device == twin on every byte: {same}; summary of individual 0: {s1[0].tolist()}", flush=True)
