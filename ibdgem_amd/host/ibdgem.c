@@ -1667,12 +1667,44 @@ static size_t host_windows(const uint8_t *nr, const uint8_t *na, size_t n, unsig
     return n_win;
 }
 
-/* an individual's window table: arrays of n_win + 1 entries, owned by whoever holds the struct (a shard's job, the
- * pileup's run, the individual's output job: handed over by assignment, the giver's copy zeroed or dropped) */
+/* a site list's windows: first and last site of each window and its covered rows, arrays of n_win + 1 entries */
 typedef struct {
     size_t n_win;
-    uint32_t *first, *last, *ncov;           /* first and last site of each window, its covered rows */
-    double *ll;                              /* LIBD0/1/2 per window */
+    uint32_t *first, *last, *ncov;
+} win_list;
+
+static void win_list_free(win_list *l)
+{
+    free(l->first); free(l->last); free(l->ncov);
+    memset(l, 0, sizeof *l);
+}
+
+/* 0: out of memory (and *l empty) */
+static int win_list_alloc(win_list *l, size_t n_win)
+{
+    l->n_win = n_win;
+    l->first = malloc((n_win + 1) * 4); l->last = malloc((n_win + 1) * 4); l->ncov = malloc((n_win + 1) * 4);
+    if (l->first && l->last && l->ncov)
+        return 1;
+    win_list_free(l);
+    return 0;
+}
+
+static int win_list_copy(win_list *to, const win_list *from)
+{
+    if (!win_list_alloc(to, from->n_win))
+        return 0;
+    memcpy(to->first, from->first, from->n_win * 4);
+    memcpy(to->last, from->last, from->n_win * 4);
+    memcpy(to->ncov, from->ncov, from->n_win * 4);
+    return 1;
+}
+
+/* an individual's window table, owned by whoever holds the struct (a shard's job, the pileup's run, the individual's output
+ * job: handed over by assignment, the giver's copy zeroed or dropped) */
+typedef struct {
+    win_list w;
+    double *ll;                              /* LIBD0/1/2 per window, n_win + 1 rows */
     double *log;                             /* --log-summary: log2 of the same table, else NULL */
 } win_table;
 
@@ -1681,8 +1713,17 @@ static int want_logs(void) { return opt_log_summary || opt_log_stats; }
 
 static void win_table_free(win_table *t)
 {
-    free(t->first); free(t->last); free(t->ncov); free(t->ll); free(t->log);
+    win_list_free(&t->w);
+    free(t->ll); free(t->log);
     memset(t, 0, sizeof *t);
+}
+
+/* 0: out of memory */
+static int win_table_alloc_ll(win_table *t)
+{
+    t->ll = malloc((t->w.n_win + 1) * 24);
+    t->log = want_logs() ? malloc((t->w.n_win + 1) * 24) : NULL;
+    return t->ll && (t->log || !want_logs());
 }
 
 /* ---- one comparison spread over several GPUs (window ranges, host-side gather) ------------ */
@@ -1697,69 +1738,71 @@ typedef struct {
     uint64_t sg[12];
 } ind_stats;
 
+/* The host's conversation with ONE context about a pileup's comparison individuals, owned by the context's worker.  It has
+ * three levels, each with a function of its own, called when the individual at hand starts that level (shards_fill decides):
+ *   conv_list        a new site list: the context's slice of it goes up, what was kept of the list before is dropped;
+ *   conv_batch       a new batch of individuals over that list (when the list does not depend on the individual -- no -v, no
+ *                    -D -- up to TARGET_BATCH of them per engine call: groups share a workgroup of the --LD kernels; else the
+ *                    individual alone): the run, its statistics, its tables where they come in one copy, the next batch queued;
+ *   conv_individual  the individual's share of all that, or its own fetch.
+ * The fields are grouped by the level that sets them. */
 typedef struct {
     ibdg_ctx *eng;
-    /* inputs: a contiguous slice [a,b) of the comparison's site list */
-    const uint32_t *row;
+    int idx;                                 /* which of the run's contexts, for messages */
+    /* ---- the pileup's run (run_modes) ---- */
+    FILE *err;                               /* where the pileup's messages go */
+    const uint8_t *bg_count;
+    int pu_id;
+    int shared_list;                         /* the site list is the same for every comparison individual of the run */
+    int list_on_device;                      /* -v lists made by the engine: it holds the individual's list already */
+    int tables_stay;                         /* --stats-only: no window table leaves the device */
+    int dev_states;                          /* --log-stats --states --stats-only on one context: the paths are found on the device */
+    int reported;                            /* a failure was reported here already (not an engine error) */
+    /* ---- the slice [a, b) of the site list at hand (shards_fill) ---- */
+    const uint32_t *row;                     /* the list's panel rows as this context counts them, */
+    const uint32_t *s_row;                   /* ... and as the host does, for the windows' positions */
     const uint8_t *nr, *na;
     const double *fo;
     size_t a, b;
-    unsigned window;
-    /* When the site list does not depend on the comparison individual (no -v, no -D), the engine
-     * evaluates a batch of them per call (groups of four share a workgroup in the --LD kernel):
-     * the first individual of a batch uploads (once) and runs, the others only fetch their slice. */
-    const uint32_t *targets;                 /* the batch */
-    size_t n_targets, t_local;               /* its size; which of them this call is for */
-    int do_upload, do_run;
-    int want_sites;                          /* 0: --summary-only, the per-site values stay on the device */
-    const uint8_t *bg_count;
-    int pu_id, ld;
-    /* outputs, written at the slice's offsets of the comparison-wide arrays */
-    double *site_ll;
-    win_table wt;                            /* slice-local arrays, window indices local */
-    int failed;
-    int dev_idx;                             /* which of the run's devices (its slot of win_cache) */
-    int same_sites;                          /* the site list is the same for every comparison individual of the run */
-    const uint32_t *next_targets;            /* the batch after this one (NULL: none), queued on the device while the host goes */
-    size_t n_next;                           /* through this batch's tables -- window tables only (--summary-only) */
     const uint32_t *arm_seg;                 /* --arm-stats: {p first, p end, q first, q end} in the slice's window indices, or NULL */
-    ind_stats out;                           /* ... the individual's sums over them, and with dev_states its other statistics */
-    int stats_only;                          /* --stats-only: no window table leaves the device */
-    int dev_states;                          /* --log-stats --states --stats-only on one context: the paths are found on the device */
-    const uint32_t *s_row;                   /* ... the site list's panel rows, for the windows' positions */
-    FILE *err;                               /* where the pileup's messages go */
-    int reported;                            /* a failure was reported here already (not an engine error) */
-} shard_job;
-
-/* Per device: the window table of the site list at hand (first row, last row, covered rows per window -- the same for
- * every comparison individual over that list: fetched once, not once per individual) and a page-locked buffer through
- * which an individual's window likelihoods come back at link speed (0.8 MB each at 35 000 windows: through pageable
- * memory the copy took longer than the individual's share of the engine's run). */
-typedef struct {
-    size_t n_win;
-    uint32_t *first, *last, *ncov;
-    int valid;
+    /* ---- the batch at hand and the one after it (NULL: none; window tables only, --summary-only), which is queued on the
+     * device while the host goes through this one's tables ---- */
+    const uint32_t *targets, *next;
+    size_t n_targets, n_next;
+    /* ---- kept from call to call ---- */
+    win_list wl;                             /* the windows of the list at hand: the same for every individual over a shared list, */
+    int wl_kept;                             /* ... fetched once then, not once per individual */
+    /* a page-locked buffer through which an individual's window likelihoods come back at link speed (0.8 MB each at 35 000
+     * windows: through pageable memory the copy took longer than the individual's share of the engine's run) */
     double *stage;
     size_t stage_cap;
     /* a batch's window tables, taken off the device in one copy, so that the next batch can run while the host goes through
      * them (one table at a time left the device idle for the 4 ms the host needs per batch of 30, beside 6 ms of running) */
-    double *batch_ll;
+    double *batch_ll;                        /* (page-locked) */
     double *batch_log;                       /* --log-summary: their logs, taken off the device with them */
-    size_t batch_cap, batch_log_cap, batch_T;
+    size_t batch_cap, batch_log_cap;
     const uint32_t *batch_of;                /* the batch (its targets) the tables belong to; NULL: none */
-    double *arm_sums;                        /* --arm-stats: the sums of the last run's individuals, [T][2][4] */
-    size_t arm_cap;
-    uint64_t *st_counts;                     /* --log-stats --states: the state counts of the last run's individuals, [T][3] */
-    size_t st_cap;
-    double *po_vals;                         /* --posteriors: expect [T][3], then log2 Z [T], of the last run's individuals */
-    size_t po_cap;
-    uint64_t *sg_vals;                       /* --segments: summary [T][12], then the counts [T], of the last run's individuals */
-    size_t sg_cap;
-    uint64_t *sg_pos;                        /* ... the windows' first positions [n_win], then their last */
-    size_t sg_pos_cap;
     const uint32_t *ahead_of;                /* the batch that has been queued ahead on the device; NULL: none */
-} win_cache;
-static win_cache g_wcache[64];
+    /* the statistics of the last run's individuals */
+    double *arm_sums;                        /* --arm-stats: [T][2][4] */
+    uint64_t *st_counts;                     /* --log-stats --states: the state counts, [T][3] */
+    double *po_vals;                         /* --posteriors: expect [T][3], then log2 Z [T] */
+    uint64_t *sg_vals;                       /* --segments: summary [T][12], then the counts [T] */
+    uint64_t *sg_pos;                        /* ... the windows' first positions [n_win], then their last */
+    size_t arm_cap, st_cap, po_cap, sg_cap, sg_pos_cap;
+} dev_conv;
+
+/* one comparison individual on one context: where it stands and what comes back for it */
+enum { AT_INDIVIDUAL, AT_BATCH, AT_LIST };   /* the outermost level the individual starts (a list starts a batch) */
+typedef struct {
+    dev_conv *c;
+    int level;
+    size_t t_local;                          /* which of the batch it is */
+    double *site_ll;                         /* out, per-site tables: the comparison-wide array, written at the slice's offset */
+    win_table wt;                            /* out: slice-local arrays, window indices local */
+    ind_stats out;                           /* out: its sums over the arms, and with dev_states its other statistics */
+    int failed;
+} shard_job;
 
 /* room for `need` elements of `elt` bytes in a scratch array that only grows (its contents are not kept); 0: out of memory */
 static int grow(void *ptr, size_t *cap, size_t need, size_t elt)
@@ -1773,204 +1816,221 @@ static int grow(void *ptr, size_t *cap, size_t need, size_t elt)
     return *p != NULL;
 }
 
-/* --segments where the tables stay on the device: the windows of the site list at hand in the context's cache (fetched once per
- * list, like the ones the individuals' files take from there) and their positions, which go up with the call */
-static int segments_on_device(shard_job *j, win_cache *wc)
+/* the same in page-locked memory (ibdg_host_alloc) */
+static int grow_pinned(void *ptr, size_t *cap, size_t need, size_t elt)
 {
-    const size_t n_win = ibdg_num_windows(j->eng), T = j->n_targets;
-    if (!(j->same_sites && wc->valid && wc->n_win == n_win)) {
-        free(wc->first); free(wc->last); free(wc->ncov);
-        wc->first = malloc((n_win + 1) * 4);
-        wc->last = malloc((n_win + 1) * 4);
-        wc->ncov = malloc((n_win + 1) * 4);
-        wc->valid = 0;
-        if (!wc->first || !wc->last || !wc->ncov || ibdg_get_windows(j->eng, wc->first, wc->last, wc->ncov))
-            return 1;
-        wc->n_win = n_win;
-        wc->valid = j->same_sites;
+    void **p = ptr;
+    if (*cap < need) {
+        if (*p)
+            ibdg_host_free(*p);
+        *p = ibdg_host_alloc(need * elt);
+        *cap = *p ? need : 0;
     }
-    if (!grow(&wc->sg_pos, &wc->sg_pos_cap, 2 * n_win + 1, sizeof(uint64_t)) || !grow(&wc->sg_vals, &wc->sg_cap, T * 13, sizeof(uint64_t)))
+    return *p != NULL;
+}
+
+/* what a context's conversation holds, given back on the orderly way out */
+static void conv_release(dev_conv *c)
+{
+    win_list_free(&c->wl);
+    if (c->stage)
+        ibdg_host_free(c->stage);
+    if (c->batch_ll)
+        ibdg_host_free(c->batch_ll);
+    free(c->batch_log); free(c->arm_sums); free(c->st_counts); free(c->po_vals); free(c->sg_vals); free(c->sg_pos);
+    memset(c, 0, sizeof *c);
+}
+
+/* a failure with a message of its own (every other one is the engine's: ibdg_last_error) */
+static int conv_oom(dev_conv *c, size_t n_win)
+{
+    fprintf(c->err ? c->err : stderr, "[::] ERROR: out of memory for %zu windows.\n", n_win);
+    c->reported = 1;
+    return 1;
+}
+
+/* The windows of the list at hand on this context (n_win of them: ibdg_num_windows), in c->wl: fetched once per list when
+ * the individuals share it, and every time otherwise.  NULL: failed. */
+static const win_list *conv_windows(dev_conv *c, size_t n_win)
+{
+    if (c->wl_kept && c->wl.n_win == n_win)
+        return &c->wl;
+    win_list_free(&c->wl);
+    c->wl_kept = 0;
+    if (!win_list_alloc(&c->wl, n_win))
+        return conv_oom(c, n_win), NULL;
+    if (ibdg_get_windows(c->eng, c->wl.first, c->wl.last, c->wl.ncov))
+        return NULL;
+    c->wl_kept = c->shared_list;
+    return &c->wl;
+}
+
+/* --segments where the tables stay on the device: the list's windows' positions go up with the call */
+static int segments_on_device(dev_conv *c)
+{
+    const size_t n_win = ibdg_num_windows(c->eng), T = c->n_targets;
+    const win_list *wl = conv_windows(c, n_win);
+    if (!wl)
         return 1;
+    if (!grow(&c->sg_pos, &c->sg_pos_cap, 2 * n_win + 1, sizeof(uint64_t)) || !grow(&c->sg_vals, &c->sg_cap, T * 13, sizeof(uint64_t)))
+        return conv_oom(c, n_win);
     for (size_t w = 0; w < n_win; ++w) {
-        wc->sg_pos[w] = rows[j->s_row[j->a + wc->first[w]]].pos;
-        wc->sg_pos[n_win + w] = rows[j->s_row[j->a + wc->last[w]]].pos;
+        c->sg_pos[w] = rows[c->s_row[c->a + wl->first[w]]].pos;
+        c->sg_pos[n_win + w] = rows[c->s_row[c->a + wl->last[w]]].pos;
     }
-    return ibdg_window_log2_segments(j->eng, opt_p01, opt_p02, opt_p12, opt_posteriors, wc->sg_pos, wc->sg_pos + n_win,
-                                     wc->sg_vals + T * 12, wc->sg_vals);
+    return ibdg_window_log2_segments(c->eng, opt_p01, opt_p02, opt_p12, opt_posteriors, c->sg_pos, c->sg_pos + n_win,
+                                     c->sg_vals + T * 12, c->sg_vals);
 }
 
 /* the engine's last run must be the run of this very batch: its size says so (a diagnostic when it does not) */
-static int same_run_size(shard_job *j)
+static int same_run_size(dev_conv *c)
 {
-    const size_t have = ibdg_num_targets(j->eng);
-    if (have == j->n_targets)
+    const size_t have = ibdg_num_targets(c->eng);
+    if (have == c->n_targets)
         return 1;
-    fprintf(j->err ? j->err : stderr, "[::] ERROR: context %d holds the results of %zu comparison individuals, not the %zu of "
-            "the batch at hand.\n", j->dev_idx, have, j->n_targets);
-    j->reported = 1;
+    fprintf(c->err ? c->err : stderr, "[::] ERROR: context %d holds the results of %zu comparison individuals, not the %zu of "
+            "the batch at hand.\n", c->idx, have, c->n_targets);
+    c->reported = 1;
     return 0;
 }
 
 /* The statistics of every individual of the run at once, before a look-ahead replaces the run's window tables: the arm sums,
  * and with dev_states the state counts, the posteriors' sums and the segments' summaries -- only these leave the device.  (On
  * one run the library finds the paths and the posteriors once for the three calls.) */
-static int device_stats(shard_job *j, win_cache *wc)
+static int device_stats(dev_conv *c)
 {
-    const size_t T = j->n_targets;
-    if (j->arm_seg) {
-        const uint32_t sf[2] = {j->arm_seg[0], j->arm_seg[2]}, se[2] = {j->arm_seg[1], j->arm_seg[3]};
-        if (!grow(&wc->arm_sums, &wc->arm_cap, T * 8, sizeof(double)) || !same_run_size(j) ||
-            (opt_log_stats ? ibdg_window_log2_llr_sums : ibdg_window_llr_sums)(j->eng, sf, se, 2, wc->arm_sums))
+    const size_t T = c->n_targets;
+    if (c->arm_seg) {
+        const uint32_t sf[2] = {c->arm_seg[0], c->arm_seg[2]}, se[2] = {c->arm_seg[1], c->arm_seg[3]};
+        if (!grow(&c->arm_sums, &c->arm_cap, T * 8, sizeof(double)))
+            return conv_oom(c, 0);
+        if (!same_run_size(c) || (opt_log_stats ? ibdg_window_log2_llr_sums : ibdg_window_llr_sums)(c->eng, sf, se, 2, c->arm_sums))
             return 1;
     }
-    if (!j->dev_states)
+    if (!c->dev_states)
         return 0;
-    if (!grow(&wc->st_counts, &wc->st_cap, T * 3, sizeof(uint64_t)) || !same_run_size(j) ||
-        ibdg_window_log2_states(j->eng, opt_p01, opt_p02, opt_p12, NULL, NULL, wc->st_counts))
+    if (!grow(&c->st_counts, &c->st_cap, T * 3, sizeof(uint64_t)) || (opt_posteriors && !grow(&c->po_vals, &c->po_cap, T * 4, sizeof(double))))
+        return conv_oom(c, 0);
+    if (!same_run_size(c) || ibdg_window_log2_states(c->eng, opt_p01, opt_p02, opt_p12, NULL, NULL, c->st_counts))
         return 1;
-    if (opt_posteriors && (!grow(&wc->po_vals, &wc->po_cap, T * 4, sizeof(double)) ||
-                           ibdg_window_log2_posteriors(j->eng, opt_p01, opt_p02, opt_p12, NULL, wc->po_vals, wc->po_vals + T * 3)))
+    if (opt_posteriors && ibdg_window_log2_posteriors(c->eng, opt_p01, opt_p02, opt_p12, NULL, c->po_vals, c->po_vals + T * 3))
         return 1;
-    return opt_segments && segments_on_device(j, wc);
+    return opt_segments && segments_on_device(c);
 }
 
-/* ... and the share of the job's individual in them */
-static void device_stats_of(shard_job *j, const win_cache *wc)
+/* ... and an individual's share in them */
+static void device_stats_of(const dev_conv *c, size_t t, ind_stats *out)
 {
-    const size_t t = j->t_local;
-    if (j->arm_seg)
-        memcpy(j->out.arm, wc->arm_sums + t * 8, sizeof j->out.arm);
-    if (!j->dev_states)
+    if (c->arm_seg)
+        memcpy(out->arm, c->arm_sums + t * 8, sizeof out->arm);
+    if (!c->dev_states)
         return;
-    memcpy(j->out.st, wc->st_counts + t * 3, sizeof j->out.st);
+    memcpy(out->st, c->st_counts + t * 3, sizeof out->st);
     if (opt_posteriors) {
-        memcpy(j->out.po, wc->po_vals + t * 3, 3 * sizeof(double));
-        j->out.po[3] = wc->po_vals[j->n_targets * 3 + t];
+        memcpy(out->po, c->po_vals + t * 3, 3 * sizeof(double));
+        out->po[3] = c->po_vals[c->n_targets * 3 + t];
     }
     if (opt_segments)
-        memcpy(j->out.sg, wc->sg_vals + t * 12, sizeof j->out.sg);
+        memcpy(out->sg, c->sg_vals + t * 12, sizeof out->sg);
 }
 
+/* a new site list for this context: its slice goes up (unless the engine made the list itself) */
+static int conv_list(dev_conv *c)
+{
+    c->wl_kept = 0;
+    c->batch_of = NULL;
+    return !c->list_on_device && ibdg_upload_sites(c->eng, c->row + c->a, c->nr + c->a, c->na + c->a, c->fo ? c->fo + c->a : NULL,
+                                                   c->b - c->a, (unsigned)opt_window);
+}
+
+/* the next batch runs while the host goes on with this one's statistics and files */
+static int queue_ahead(dev_conv *c)
+{
+    if (!c->next)
+        return 0;
+    if (ibdg_set_option(c->eng, "async", 1) || ibdg_run(c->eng, c->next, c->n_next, c->bg_count, c->pu_id, opt_ld) ||
+        ibdg_set_option(c->eng, "async", 0))
+        return 1;
+    c->ahead_of = c->next;
+    return 0;
+}
+
+/* A new batch: its run -- or the one queued ahead taken over --, the statistics of all its individuals, its window tables in
+ * one copy where only these are wanted of more than one individual (--summary-only; with per-site values every individual
+ * fetches its own, see conv_individual), then the next batch queued. */
+static int conv_batch(dev_conv *c)
+{
+    c->batch_of = NULL;
+    if (c->ahead_of != c->targets) {             /* not queued ahead (the first batch, or no look-ahead in this run) */
+        if (c->ahead_of && ibdg_sync(c->eng))
+            return 1;
+        if (ibdg_run(c->eng, c->targets, c->n_targets, c->bg_count, c->pu_id, opt_ld))
+            return 1;
+    }
+    c->ahead_of = NULL;
+    if (device_stats(c))
+        return 1;
+    if (!c->tables_stay && (c->next || c->n_targets > 1)) {
+        /* (the library is asked in runs with per-site tables too, as it always was: the calls a context sees are pinned) */
+        const size_t nw = ibdg_num_windows(c->eng), need = c->n_targets * (nw + 1) * 3;
+        if (opt_summary_only) {
+            if (!grow_pinned(&c->batch_ll, &c->batch_cap, need, sizeof(double)) ||
+                (want_logs() && !grow(&c->batch_log, &c->batch_log_cap, need, sizeof(double))))
+                return conv_oom(c, nw);
+            /* (the copy is as large as the LAST RUN's results: it must be the run of this very batch) */
+            if (!same_run_size(c) || ibdg_get_window_ll_all(c->eng, c->batch_ll))                /* waits for the run */
+                return 1;
+            if (want_logs() && ibdg_get_window_log2_all(c->eng, c->batch_log))
+                return 1;
+            c->batch_of = c->targets;
+        }
+    }
+    return queue_ahead(c);
+}
+
+/* the individual's share of the batch's statistics, its window table -- from the batch's copy, or fetched alone through the
+ * staging buffer -- and its per-site values */
+static int conv_individual(dev_conv *c, shard_job *j)
+{
+    const size_t t = j->t_local;
+    win_table *wt = &j->wt;
+    device_stats_of(c, t, &j->out);
+    const size_t n_win = wt->w.n_win = ibdg_num_windows(c->eng);
+    if (c->tables_stay)
+        return 0;
+    const win_list *wl = conv_windows(c, n_win);
+    if (!wl)
+        return 1;
+    if (!c->wl_kept) {                           /* the individual's own list: its windows go with it */
+        wt->w = c->wl;
+        memset(&c->wl, 0, sizeof c->wl);
+    } else if (!win_list_copy(&wt->w, wl))
+        return conv_oom(c, n_win);
+    if (!win_table_alloc_ll(wt))
+        return conv_oom(c, n_win);
+    if (c->batch_of == c->targets) {             /* (window tables only: no per-site values on this path) */
+        memcpy(wt->ll, c->batch_ll + t * n_win * 3, n_win * 24);
+        if (wt->log)
+            memcpy(wt->log, c->batch_log + t * n_win * 3, n_win * 24);
+        return 0;
+    }
+    /* (no page-locked memory to be had: straight into the table) */
+    double *const via = grow_pinned(&c->stage, &c->stage_cap, (n_win + 1) * 3, sizeof(double)) ? c->stage : wt->ll;
+    if (ibdg_get_window_ll(c->eng, t, via))
+        return 1;
+    if (via != wt->ll)
+        memcpy(wt->ll, via, n_win * 24);
+    if (wt->log && ibdg_get_window_log2(c->eng, t, wt->log))
+        return 1;
+    return !opt_summary_only && ibdg_get_site_ll(c->eng, t, j->site_ll + 3 * c->a);
+}
+
+/* an individual's call on one context (a thread per context when there are several) */
 static void *shard_run(void *arg)
 {
     shard_job *j = arg;
-    const size_t n = j->b - j->a;
-    win_cache *wc = &g_wcache[j->dev_idx & 63];
-    j->failed = 1;
-    if (j->do_upload) {
-        wc->valid = 0;
-        if (ibdg_upload_sites(j->eng, j->row + j->a, j->nr + j->a, j->na + j->a, j->fo ? j->fo + j->a : NULL, n, j->window))
-            return NULL;
-    }
-    if (j->do_upload || j->do_run)
-        wc->batch_of = NULL;
-    if (j->do_run) {
-        if (wc->ahead_of != j->targets) {        /* not queued ahead (the first batch, or no look-ahead in this run) */
-            if (wc->ahead_of && ibdg_sync(j->eng))
-                return NULL;
-            if (ibdg_run(j->eng, j->targets, j->n_targets, j->bg_count, j->pu_id, j->ld))
-                return NULL;
-        }
-        wc->ahead_of = NULL;
-        if (device_stats(j, wc))
-            return NULL;
-        if (j->stats_only) {
-            if (j->next_targets) {                                        /* the next batch runs while the host goes on */
-                if (ibdg_set_option(j->eng, "async", 1) ||
-                    ibdg_run(j->eng, j->next_targets, j->n_next, j->bg_count, j->pu_id, j->ld) ||
-                    ibdg_set_option(j->eng, "async", 0))
-                    return NULL;
-                wc->ahead_of = j->next_targets;
-            }
-        } else if (j->next_targets || j->n_targets > 1) {
-            const size_t nw = ibdg_num_windows(j->eng), need = j->n_targets * (nw + 1) * 24;
-            if (wc->batch_cap < need) {
-                if (wc->batch_ll)
-                    ibdg_host_free(wc->batch_ll);
-                wc->batch_ll = ibdg_host_alloc(need);
-                wc->batch_cap = wc->batch_ll ? need : 0;
-            }
-            if (want_logs() && wc->batch_log_cap < need) {
-                free(wc->batch_log);
-                wc->batch_log = malloc(need);
-                wc->batch_log_cap = wc->batch_log ? need : 0;
-            }
-            if (wc->batch_ll && !j->want_sites && (!want_logs() || wc->batch_log)) {
-                /* (the copy is as large as the LAST RUN's results: it must be the run of this very batch) */
-                if (!same_run_size(j) || ibdg_get_window_ll_all(j->eng, wc->batch_ll))        /* waits for the run */
-                    return NULL;
-                if (want_logs() && ibdg_get_window_log2_all(j->eng, wc->batch_log))
-                    return NULL;
-                wc->batch_of = j->targets;
-                wc->batch_T = j->n_targets;
-                if (j->next_targets) {                                    /* the next batch runs while this one's files are made */
-                    if (ibdg_set_option(j->eng, "async", 1) ||
-                        ibdg_run(j->eng, j->next_targets, j->n_next, j->bg_count, j->pu_id, j->ld) ||
-                        ibdg_set_option(j->eng, "async", 0))
-                        return NULL;
-                    wc->ahead_of = j->next_targets;
-                }
-            }
-        }
-    }
-    device_stats_of(j, wc);
-    j->wt.n_win = ibdg_num_windows(j->eng);
-    if (j->stats_only) {
-        j->failed = 0;
-        return NULL;
-    }
-    j->wt.first = malloc((j->wt.n_win + 1) * 4);
-    j->wt.last = malloc((j->wt.n_win + 1) * 4);
-    j->wt.ncov = malloc((j->wt.n_win + 1) * 4);
-    j->wt.ll = malloc((j->wt.n_win + 1) * 24);
-    j->wt.log = want_logs() ? malloc((j->wt.n_win + 1) * 24) : NULL;
-    if (!j->wt.first || !j->wt.last || !j->wt.ncov || !j->wt.ll || (want_logs() && !j->wt.log))
-        return NULL;
-    if (j->same_sites && wc->valid && wc->n_win == j->wt.n_win) {
-        memcpy(j->wt.first, wc->first, j->wt.n_win * 4);
-        memcpy(j->wt.last, wc->last, j->wt.n_win * 4);
-        memcpy(j->wt.ncov, wc->ncov, j->wt.n_win * 4);
-    } else {
-        if (ibdg_get_windows(j->eng, j->wt.first, j->wt.last, j->wt.ncov))
-            return NULL;
-        if (j->same_sites) {
-            free(wc->first); free(wc->last); free(wc->ncov);
-            wc->first = malloc((j->wt.n_win + 1) * 4);
-            wc->last = malloc((j->wt.n_win + 1) * 4);
-            wc->ncov = malloc((j->wt.n_win + 1) * 4);
-            if (wc->first && wc->last && wc->ncov) {
-                memcpy(wc->first, j->wt.first, j->wt.n_win * 4);
-                memcpy(wc->last, j->wt.last, j->wt.n_win * 4);
-                memcpy(wc->ncov, j->wt.ncov, j->wt.n_win * 4);
-                wc->n_win = j->wt.n_win;
-                wc->valid = 1;
-            }
-        }
-    }
-    if (wc->batch_of == j->targets && j->t_local < wc->batch_T) {
-        memcpy(j->wt.ll, wc->batch_ll + j->t_local * j->wt.n_win * 3, j->wt.n_win * 24);
-        if (j->wt.log)
-            memcpy(j->wt.log, wc->batch_log + j->t_local * j->wt.n_win * 3, j->wt.n_win * 24);
-        j->failed = 0;
-        return NULL;                             /* (window tables only: want_sites is off on this path) */
-    }
-    if (wc->stage_cap < (j->wt.n_win + 1) * 24) {
-        if (wc->stage)
-            ibdg_host_free(wc->stage);
-        wc->stage = ibdg_host_alloc((j->wt.n_win + 1) * 24);
-        wc->stage_cap = wc->stage ? (j->wt.n_win + 1) * 24 : 0;
-    }
-    if (wc->stage) {
-        if (ibdg_get_window_ll(j->eng, j->t_local, wc->stage))
-            return NULL;
-        memcpy(j->wt.ll, wc->stage, j->wt.n_win * 24);
-    } else if (ibdg_get_window_ll(j->eng, j->t_local, j->wt.ll))
-        return NULL;
-    if (j->wt.log && ibdg_get_window_log2(j->eng, j->t_local, j->wt.log))
-        return NULL;
-    if (j->want_sites && ibdg_get_site_ll(j->eng, j->t_local, j->site_ll + 3 * j->a))
-        return NULL;
-    j->failed = 0;
+    dev_conv *c = j->c;
+    j->failed = (j->level == AT_LIST && conv_list(c)) || (j->level >= AT_BATCH && conv_batch(c)) || conv_individual(c, j);
     return NULL;
 }
 
@@ -2508,7 +2568,7 @@ static int posteriors_individual(out_job *o)
 {
     if (!opt_posteriors)
         return 0;
-    const size_t n = o->wt.n_win;
+    const size_t n = o->wt.w.n_win;
     double *post = o->lp ? malloc((n ? n : 1) * 3 * sizeof *post) : NULL;
     int bad = o->lp && !post;
     if (!bad && ibdg_log2_posteriors_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, post, o->res->po, o->res->po + 3)) {
@@ -2538,13 +2598,13 @@ static int segments_individual(out_job *o)
 {
     if (!opt_segments)
         return 0;
-    const size_t n = o->wt.n_win;
+    const size_t n = o->wt.w.n_win;
     uint64_t *pos = malloc((2 * n + 1) * sizeof *pos), n_seg = 0;
     ibdg_segment *seg = o->ls ? malloc((n ? n : 1) * sizeof *seg) : NULL;
     int bad = !pos || (o->ls && !seg);
     for (size_t w = 0; w < n && !bad; ++w) {
-        pos[w] = o->pos_first ? o->pos_first[w] : rows[o->s_row[o->wt.first[w]]].pos;
-        pos[n + w] = o->pos_last ? o->pos_last[w] : rows[o->s_row[o->wt.last[w]]].pos;
+        pos[w] = o->pos_first ? o->pos_first[w] : rows[o->s_row[o->wt.w.first[w]]].pos;
+        pos[n + w] = o->pos_last ? o->pos_last[w] : rows[o->s_row[o->wt.w.last[w]]].pos;
     }
     if (!bad && ibdg_log2_segments_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, opt_posteriors, pos, pos + n, seg, n, &n_seg, o->res->sg)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
@@ -2558,7 +2618,7 @@ static int segments_individual(out_job *o)
             const int64_t own = g->e[g->state], a = g->e[(g->state + 1) % 3], b = g->e[(g->state + 2) % 3];
             unsigned long sites = 0;
             for (size_t w = f; w <= l; ++w)
-                sites += o->wt.ncov[w];
+                sites += o->wt.w.ncov[w];
             bad = fprintf(o->ls, "%zu\t%u\t%zu\t%zu\t%llu\t%llu\t%llu\t%u\t%lu\t%.4Lf\t%.4Lf\t%.4Lf\t%.4Lf", k + 1, g->state, f + 1,
                           l + 1, (unsigned long long)pos[f], (unsigned long long)pos[n + l],
                           (unsigned long long)(pos[n + l] - pos[f] + 1), g->n_win, sites, (long double)g->e[0] / 65536,
@@ -2577,7 +2637,7 @@ static int segments_individual(out_job *o)
 
 static int log_states_individual(out_job *o)
 {
-    const size_t n = o->wt.n_win;
+    const size_t n = o->wt.w.n_win;
     uint64_t *const count = o->res->st;
     uint8_t *path = o->hg ? malloc(n ? n : 1) : NULL;
     int64_t *score = o->hg ? malloc((n ? n : 1) * 3 * sizeof *score) : NULL;
@@ -2609,7 +2669,7 @@ static int states_individual(out_job *o)
         return log_states_individual(o);
     hg_path *h = &o->hgp;
     hg_reset(h);
-    for (size_t w = 0; w < o->wt.n_win; ++w)
+    for (size_t w = 0; w < o->wt.w.n_win; ++w)
         if (hg_add(h, summary_round_trip(o->wt.ll[3 * w]), summary_round_trip(o->wt.ll[3 * w + 1]),
                    summary_round_trip(o->wt.ll[3 * w + 2])))
             return 1;
@@ -2638,7 +2698,7 @@ static void *output_individual(void *arg)
     FILE *tab = o->tab, *sum = o->sum;           /* opened by the main thread: a directory that cannot be written stops the run at once */
     if (opt_plan)
         printf("## PLAN %s %s processed=%lu skipped=%lu windows=%zu cull_p=%f\n", o->sq, o->tname, o->processed, o->skipped,
-               o->wt.n_win, o->cull_p);
+               o->wt.w.n_win, o->cull_p);
     else {
         if ((!opt_summary_only && ftruncate(fileno(tab), 0) != 0) || ftruncate(fileno(sum), 0) != 0 ||
             (o->hg && ftruncate(fileno(o->hg), 0) != 0) || (o->lsum && ftruncate(fileno(o->lsum), 0) != 0) ||
@@ -2676,18 +2736,18 @@ static void *output_individual(void *arg)
         }
     }
     if (opt_plan) {
-        for (size_t w = 0; w < o->wt.n_win; ++w)
-            printf("## WINDOW %zu\t%lu\t%lu\t%u\n", w + 1, rows[o->s_row[o->wt.first[w]]].pos, rows[o->s_row[o->wt.last[w]]].pos,
-                   o->wt.ncov[w]);
+        for (size_t w = 0; w < o->wt.w.n_win; ++w)
+            printf("## WINDOW %zu\t%lu\t%lu\t%u\n", w + 1, rows[o->s_row[o->wt.w.first[w]]].pos, rows[o->s_row[o->wt.w.last[w]]].pos,
+                   o->wt.w.ncov[w]);
     } else {
         /* the summary rows (:751-756) through the program's own conversions, by the team of threads: with many
          * comparison individuals per run the seven stdio calls per window were the longest item of an individual
          * (25 ms of 33 at 35 000 windows) */
         sum_job sj;
         memset(&sj, 0, sizeof sj);
-        sj.s_row = o->s_row; sj.w_first = o->wt.first; sj.w_last = o->wt.last; sj.w_ncov = o->wt.ncov; sj.win_ll = o->wt.ll;
+        sj.s_row = o->s_row; sj.w_first = o->wt.w.first; sj.w_last = o->wt.w.last; sj.w_ncov = o->wt.w.ncov; sj.win_ll = o->wt.ll;
         sj.pos_first = o->pos_first; sj.pos_last = o->pos_last;
-        if (write_summary_parallel(sum, sj, o->wt.n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
+        if (write_summary_parallel(sum, sj, o->wt.w.n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
             fprintf(o->err, "[::] ERROR writing the summary rows of %s.\n", o->tname);
             return NULL;
         }
@@ -2696,7 +2756,7 @@ static void *output_individual(void *arg)
             fprintf(o->lsum, "# SEGMENT\tSTART\tEND\tLOG2_LIBD0\tLOG2_LIBD1\tLOG2_LIBD2\tNUM_SITES\n");
             sj.win_ll = o->wt.log;
             sj.logs = 1;
-            if (write_summary_parallel(o->lsum, sj, o->wt.n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
+            if (write_summary_parallel(o->lsum, sj, o->wt.w.n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
                 fprintf(o->err, "[::] ERROR writing the log summary rows of %s.\n", o->tname);
                 return NULL;
             }
@@ -2978,8 +3038,8 @@ static void list_finish(size_t i, int rc)
 
 /* a worker: the contexts it drives (all of them for a single -P run, one for a list), their panel uploads and its output slots */
 typedef struct {
-    ibdg_ctx *engs[64];
-    int n_eng, dev_base;
+    dev_conv conv[64];             /* per context: the context and the conversation with it */
+    int n_eng;
     upload_job *ups;
     int n_ups, ups_pending;
     int slice_mode;
@@ -3085,6 +3145,12 @@ static void run_modes(pile_run *r)
     /* ... or in the log domain (--log-stats), where one context has the whole table and finds the paths itself */
     r->dev_states = opt_stats_only && opt_states && opt_log_stats && !no_engine && r->w->n_eng == 1;
     r->tables_stay = r->tables_stay || r->dev_states;
+    for (int d = 0; d < r->w->n_eng; ++d) {      /* what the conversation with each context takes from these */
+        dev_conv *c = &r->w->conv[d];
+        c->err = r->err; c->bg_count = g_bg_count; c->pu_id = (int)r->pj->pu_id; c->reported = 0;
+        c->shared_list = r->batchable; c->list_on_device = r->dev_v;
+        c->tables_stay = r->tables_stay; c->dev_states = r->dev_states;
+    }
 }
 
 /* ---- the statistics files a run writes once, after its last individual, from the individuals' records (r->res) ---- */
@@ -3257,8 +3323,8 @@ static int candidates_to_device(pile_run *r)
         r->c_gt_failed += r->pj->row_fate[row] == 0 && rows[row].gt_failed;
     if (join_uploads(r))                     /* (the candidates name rows of the panel: it must be there) */
         return 1;
-    if (ibdg_upload_candidates(r->w->engs[0], r->c_row, r->c_nr, r->c_na, r->c_fo, n_cand))
-        SFAIL("%s\n", ibdg_last_error(r->w->engs[0]));
+    if (ibdg_upload_candidates(r->w->conv[0].eng, r->c_row, r->c_nr, r->c_na, r->c_fo, n_cand))
+        SFAIL("%s\n", ibdg_last_error(r->w->conv[0].eng));
     phase("candidate rows of the pileup to the device");
     return 0;
 }
@@ -3285,7 +3351,7 @@ static void gt_failed_replay(const pile_run *r)
 static int site_list_from_device(pile_run *r)
 {
     site_list *sl = &r->sl;
-    ibdg_ctx *eng = r->w->engs[0];
+    ibdg_ctx *eng = r->w->conv[0].eng;
     sl->n_gt_failed = r->c_gt_failed;
     gt_failed_replay(r);
     if (ibdg_select_variable_sites(eng, r->tgt, (unsigned)opt_window))
@@ -3380,20 +3446,18 @@ static int windows_on_host(pile_run *r)
 {
     const site_list *sl = &r->sl;
     win_table *t = &r->wt;
-    t->n_win = host_windows(sl->s_nr, sl->s_na, sl->n, (unsigned)opt_window, &t->first, &t->last, &t->ncov);
+    t->w.n_win = host_windows(sl->s_nr, sl->s_na, sl->n, (unsigned)opt_window, &t->w.first, &t->w.last, &t->w.ncov);
     if (g_host_math) {
-        t->ll = malloc((t->n_win + 1) * 24);
-        t->log = want_logs() ? malloc((t->n_win + 1) * 24) : NULL;
-        if (want_logs() && !t->log)
-            SFAIL("[::] ERROR: out of memory for %zu windows.\n", t->n_win);
-        host_nonld(r->pj->cand, sl->s_cand, sl->s_nr, sl->s_na, sl->n, r->tgt, g_pdg_tab, all_threads(), r->site_ll, t->first,
-                   t->last, t->n_win, t->ll, t->log);
+        if (!win_table_alloc_ll(t))
+            SFAIL("[::] ERROR: out of memory for %zu windows.\n", t->w.n_win);
+        host_nonld(r->pj->cand, sl->s_cand, sl->s_nr, sl->s_na, sl->n, r->tgt, g_pdg_tab, all_threads(), r->site_ll, t->w.first,
+                   t->w.last, t->w.n_win, t->ll, t->log);
     }
     if (r->arm_on) {
         uint32_t seg[4];
         int ok[2];
         double p[4], q[4], *res = r->res[r->ti].arm;
-        arm_segments(sl->s_row, t->first, t->last, t->n_win, seg, ok);
+        arm_segments(sl->s_row, t->w.first, t->w.last, t->w.n_win, seg, ok);
         const double *tab = opt_log_stats ? t->log : t->ll;
         llr_range_host(tab, opt_log_stats, seg[0], seg[1], p);
         llr_range_host(tab, opt_log_stats, seg[2], seg[3], q);
@@ -3450,45 +3514,37 @@ static int panel_slices(pile_run *r)
     return 0;
 }
 
-/* one contiguous window range per GPU */
-static void shards_fill(const pile_run *r, shard_job *jobs)
+/* One contiguous window range per GPU.  Where the individual stands is decided here and nowhere else: it starts a list when
+ * it does not run over the list of the one before it, a batch when it is the first of TARGET_BATCH over a shared list (on its
+ * own list it is a batch of one), and otherwise only takes its share.  The next batch is named where it will be queued ahead:
+ * window tables only (--summary-only). */
+static void shards_fill(pile_run *r, shard_job *jobs)
 {
     const site_list *sl = &r->sl;
-    const worker_t *w = r->w;
-    const idlist_t targets = g_targets;
-    const size_t ti = r->ti;
+    worker_t *w = r->w;
+    const uint32_t *ids = g_targets.idx;
+    const size_t n = g_targets.n, ti = r->ti, b0 = r->batchable ? ti - ti % TARGET_BATCH : ti, b1 = b0 + TARGET_BATCH;
+    const int level = !r->same_sites ? AT_LIST : ti == b0 ? AT_BATCH : AT_INDIVIDUAL;
     for (int d = 0; d < w->n_eng; ++d) {
+        dev_conv *c = &w->conv[d];
         shard_job *j = &jobs[d];
-        memset(j, 0, sizeof *j);
-        j->eng = w->engs[d]; j->row = w->slice_mode ? sl->s_row_dev : sl->s_row; j->nr = sl->s_nr; j->na = sl->s_na; j->fo = sl->s_fo;
-        j->a = sl->cuts[d]; j->b = sl->cuts[d + 1]; j->window = (unsigned)opt_window;
-        j->want_sites = !opt_summary_only;
-        if (r->batchable) {
-            const size_t b0 = ti - ti % TARGET_BATCH;
-            j->targets = targets.idx + b0;
-            j->n_targets = targets.n - b0 < TARGET_BATCH ? targets.n - b0 : TARGET_BATCH;
-            j->t_local = ti - b0;
-            j->do_upload = ti == 0;
-            j->do_run = ti == b0;
-            if (b0 + TARGET_BATCH < targets.n && opt_summary_only) {
-                j->next_targets = targets.idx + b0 + TARGET_BATCH;
-                j->n_next = targets.n - (b0 + TARGET_BATCH) < TARGET_BATCH ? targets.n - (b0 + TARGET_BATCH) : TARGET_BATCH;
-            }
-        } else {
-            j->targets = &targets.idx[ti];
-            j->n_targets = 1;
-            j->t_local = 0;
-            j->do_upload = !r->dev_v;        /* (dev_v: the engine holds the individual's list already) */
-            j->do_run = 1;
+        if (level == AT_LIST) {
+            c->row = w->slice_mode ? sl->s_row_dev : sl->s_row; c->s_row = sl->s_row;
+            c->nr = sl->s_nr; c->na = sl->s_na; c->fo = sl->s_fo;
+            c->a = sl->cuts[d]; c->b = sl->cuts[d + 1];
+            c->arm_seg = r->arm_on ? sl->arm_local[d] : NULL;
         }
-        j->bg_count = g_bg_count; j->pu_id = (int)r->pj->pu_id; j->ld = opt_ld;
-        j->dev_idx = w->dev_base + d; j->same_sites = r->batchable;
+        if (level >= AT_BATCH) {
+            c->targets = ids + b0;
+            c->n_targets = !r->batchable ? 1 : n - b0 < TARGET_BATCH ? n - b0 : TARGET_BATCH;
+            c->next = r->batchable && opt_summary_only && b1 < n ? ids + b1 : NULL;
+            c->n_next = !c->next ? 0 : n - b1 < TARGET_BATCH ? n - b1 : TARGET_BATCH;
+        }
+        memset(j, 0, sizeof *j);
+        j->c = c;
+        j->level = level;
+        j->t_local = ti - b0;
         j->site_ll = r->site_ll;
-        j->arm_seg = r->arm_on ? sl->arm_local[d] : NULL;
-        j->stats_only = r->tables_stay;
-        j->dev_states = r->dev_states;
-        j->s_row = sl->s_row;
-        j->err = r->err;
     }
 }
 
@@ -3509,10 +3565,10 @@ static int shards_run(pile_run *r, shard_job *jobs)
             pthread_join(th[d], NULL);
         if (jobs[d].failed && shard_failed < 0)
             shard_failed = d;
-        r->wt.n_win += jobs[d].wt.n_win;
+        r->wt.w.n_win += jobs[d].wt.w.n_win;
     }
-    if (shard_failed >= 0 && !jobs[shard_failed].reported)
-        fprintf(r->err, "%s\n", ibdg_last_error(jobs[shard_failed].eng));
+    if (shard_failed >= 0 && !jobs[shard_failed].c->reported)
+        fprintf(r->err, "%s\n", ibdg_last_error(jobs[shard_failed].c->eng));
     return shard_failed >= 0;
 }
 
@@ -3522,8 +3578,8 @@ static int arm_gather(pile_run *r, const shard_job *jobs)
     const site_list *sl = &r->sl;
     double acc[8] = {0}, *res = r->res[r->ti].arm;
     for (int d = 0; d < r->w->n_eng; ++d) {
-        if (jobs[d].wt.n_win != sl->arm_wcut[d + 1] - sl->arm_wcut[d])
-            SFAIL("[::] ERROR: device %d holds %zu windows, not the %u of its range.\n", d, jobs[d].wt.n_win,
+        if (jobs[d].wt.w.n_win != sl->arm_wcut[d + 1] - sl->arm_wcut[d])
+            SFAIL("[::] ERROR: device %d holds %zu windows, not the %u of its range.\n", d, jobs[d].wt.w.n_win,
                   sl->arm_wcut[d + 1] - sl->arm_wcut[d]);
         for (int k = 0; k < 4; ++k)
             dd_add(acc + 2 * k, jobs[d].out.arm[2 * k], jobs[d].out.arm[2 * k + 1]);
@@ -3534,31 +3590,35 @@ static int arm_gather(pile_run *r, const shard_job *jobs)
 }
 
 /* the devices' window tables, gathered in order into the individual's */
-static void tables_gather(pile_run *r, shard_job *jobs)
+static int tables_gather(pile_run *r, shard_job *jobs)
 {
     win_table *t = &r->wt;
-    if (r->w->n_eng == 1 && jobs[0].a == 0) {
+    if (r->w->n_eng == 1 && jobs[0].c->a == 0) {
         *t = jobs[0].wt;   /* one device, the whole site list: its arrays as they are (a copy of 1.2 MB per individual otherwise) */
-        return;
+        return 0;
     }
-    t->first = malloc((t->n_win + 1) * 4); t->last = malloc((t->n_win + 1) * 4); t->ncov = malloc((t->n_win + 1) * 4);
-    t->ll = malloc((t->n_win + 1) * 24);
-    t->log = want_logs() ? malloc((t->n_win + 1) * 24) : NULL;
+    const size_t n_win = t->w.n_win;
+    if (!win_list_alloc(&t->w, n_win) || !win_table_alloc_ll(t)) {
+        for (int d = 0; d < r->w->n_eng; ++d)
+            win_table_free(&jobs[d].wt);
+        SFAIL("[::] ERROR: out of memory for %zu windows.\n", n_win);
+    }
     size_t wo = 0;
     for (int d = 0; d < r->w->n_eng; ++d) {
         win_table *s = &jobs[d].wt;
-        const uint32_t a0 = (uint32_t)jobs[d].a;
-        for (size_t wi = 0; wi < s->n_win; ++wi) {
-            t->first[wo + wi] = s->first[wi] + a0;
-            t->last[wo + wi] = s->last[wi] + a0;
+        const uint32_t a0 = (uint32_t)jobs[d].c->a;
+        for (size_t wi = 0; wi < s->w.n_win; ++wi) {
+            t->w.first[wo + wi] = s->w.first[wi] + a0;
+            t->w.last[wo + wi] = s->w.last[wi] + a0;
         }
-        memcpy(t->ncov + wo, s->ncov, s->n_win * 4);
-        memcpy(t->ll + 3 * wo, s->ll, s->n_win * 24);
-        if (t->log && s->log)
-            memcpy(t->log + 3 * wo, s->log, s->n_win * 24);
-        wo += s->n_win;
+        memcpy(t->w.ncov + wo, s->w.ncov, s->w.n_win * 4);
+        memcpy(t->ll + 3 * wo, s->ll, s->w.n_win * 24);
+        if (t->log)
+            memcpy(t->log + 3 * wo, s->log, s->w.n_win * 24);
+        wo += s->w.n_win;
         win_table_free(s);
     }
+    return 0;
 }
 
 static int windows_on_engine(pile_run *r)
@@ -3576,8 +3636,8 @@ static int windows_on_engine(pile_run *r)
      * individuals share one site list depends on its own cull ratio, so each pileup gets the layout choice its single run
      * makes ("auto" otherwise) */
     for (int d = 0; d < r->w->n_eng && g_list_mode && r->ti == 0; ++d)
-        if (ibdg_set_option(r->w->engs[d], "compact_tiles", r->batchable && opt_ld && !opt_ref_order && g_targets.n >= 240))
-            SFAIL("%s\n", ibdg_last_error(r->w->engs[d]));
+        if (ibdg_set_option(r->w->conv[d].eng, "compact_tiles", r->batchable && opt_ld && !opt_ref_order && g_targets.n >= 240))
+            SFAIL("%s\n", ibdg_last_error(r->w->conv[d].eng));
     shards_fill(r, jobs);
     if (shards_run(r, jobs))
         return 1;
@@ -3587,8 +3647,9 @@ static int windows_on_engine(pile_run *r)
         return 1;
     if (r->tables_stay)                      /* no window table left the device */
         return 0;
-    tables_gather(r, jobs);
-    if (r->arm_on && (t->n_win != sl->arm_nw || memcmp(t->first, sl->arm_wfirst, t->n_win * 4) || memcmp(t->last, sl->arm_wlast, t->n_win * 4)))
+    if (tables_gather(r, jobs))
+        return 1;
+    if (r->arm_on && (t->w.n_win != sl->arm_nw || memcmp(t->w.first, sl->arm_wfirst, sl->arm_nw * 4) || memcmp(t->w.last, sl->arm_wlast, sl->arm_nw * 4)))
         SFAIL("[::] ERROR: the engine's windows are not the ones the chromosome arms were cut from.\n");
     return 0;
 }
@@ -3596,7 +3657,7 @@ static int windows_on_engine(pile_run *r)
 static void summary_positions(pile_run *r)
 {
     site_list *sl = &r->sl;
-    const win_table *t = &r->wt;
+    const win_list *t = &r->wt.w;
     if (!r->overlap || g_no_engine || (sl->sum_pos_made && sl->sum_pos_n == t->n_win))
         return;
     free(sl->sum_pos_first); free(sl->sum_pos_last);
@@ -4150,8 +4211,7 @@ int main(int argc, char **argv)
         const int one = n_workers > 1 || g_list_mode;        /* a context of its own */
         w->n_eng = no_engine ? 0 : one ? 1 : n_eng;
         for (int d = 0; d < w->n_eng; ++d)
-            w->engs[d] = engs[k + d];
-        w->dev_base = k;
+            w->conv[d].eng = engs[k + d], w->conv[d].idx = k + d;
         w->ups = ups + k;
         w->n_ups = w->n_eng;
         w->ups_pending = !no_engine && !slice_mode;
@@ -4208,6 +4268,9 @@ int main(int argc, char **argv)
         _exit(EXIT_SUCCESS);
     }
 #endif
+    for (int k = 0; k < n_workers; ++k)
+        for (int d = 0; d < workers[k].n_eng; ++d)
+            conv_release(&workers[k].conv[d]);
     for (int d = 0; d < n_eng; ++d)
         ibdg_destroy(engs[d]);
     phase("engine shutdown");

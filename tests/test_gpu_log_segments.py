@@ -246,3 +246,15 @@ def test_cli_every_route_gives_the_same_bytes(key, post, tmp_path):
     assert sorted(plain) == sorted(fn for fn in full["0"] if fn not in per and fn != "UNKWN.logibdsegments.txt")
     for fn, data in plain.items():
         assert full["0"][fn] == data, fn
+
+
+@pytest.mark.parametrize("devices", ["0", "0,0"])
+def test_stats_only_over_batches_of_individuals_equals_the_single_runs(devices, tmp_path):
+    """31 individuals with --stats-only and every log-domain statistic: a batch of 30, then the one queued ahead of its
+    statistics calls -- on one context the paths, posteriors and segments are found on the device, on two the tables are
+    gathered for the host twins.  Only the statistics files are written, and an individual's line in each is the line of its
+    run alone (which writes its files too)."""
+    import batch_cases as B
+    got = B.run(["--stats-only", "--devices", devices], B.NAMES, tmp_path)
+    assert sorted(got) == sorted(B.STATS_FILES)
+    B.check_statistics(got)

@@ -92,3 +92,18 @@ def test_logsummary_of_a_pileup_list_equals_the_single_runs(key, tmp_path):
     got = logs_of(run(args + ["--pileup-list", lst, "--devices", "0,0"], inp, tmp_path / "list"))
     assert sorted(got) == sorted(want) and len(got) >= 6
     assert got == want
+
+
+@pytest.mark.parametrize("devices", ["0", "0,0"])
+def test_batches_of_individuals_with_summary_only_equal_the_single_runs(devices, tmp_path):
+    """31 individuals with --log-summary --summary-only and every log-domain statistic: a batch of 30 whose linear and log2
+    tables leave the device in one copy each while the batch of one is queued ahead, on one context and cut over two.  Every
+    file of an individual is that of its run alone, byte for byte, and so is its line of every statistics file."""
+    import batch_cases as B
+    got = B.run(["--log-summary", "--summary-only", "--devices", devices], B.NAMES, tmp_path)
+    own = {fn: data for fn, data in got.items() if fn not in B.STATS_FILES}
+    want = {fn: data for name in B.NAMES for fn, data in B.singles()[name].items() if fn not in B.STATS_FILES}
+    assert sorted(own) == sorted(want) and len(own) == 31 * 5
+    for fn in want:
+        assert own[fn] == want[fn], fn
+    B.check_statistics(got)
