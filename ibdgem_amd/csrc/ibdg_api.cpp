@@ -165,7 +165,7 @@ void sites_replaced(ibdg_ctx *c)
     c->ibd0.drop();
 }
 
-// New segments, window constants and control words for the same site list (build_segments, also from
+// New segments, window constants and control words for the same site list (commit_layout, also from
 // relayout_when_paid): everything keyed by sites_gen -- the IBD0 pass, the fragment base, the images, a pending finalising
 // step, stream3's order.  The row table does not depend on the layout (up_gen stays).
 void layout_changed(ibdg_ctx *c) { ++c->sites_gen; }
@@ -497,29 +497,21 @@ void make_runs(const ibdg_ctx *c, uint32_t g, std::vector<uint32_t> &runs)
 // the range of the 32-bit fields (the strict kernel then serves).
 bool grow_pow_tables(ibdg_ctx *c, size_t need)
 {
-    if (need > c->tab.tab_fail_from)
-        return false;
-    if (need <= c->tab.p1_h.size())
-        return true;
-    const size_t old = c->tab.p1_h.size();
-    const size_t n = std::max(need, std::min<size_t>(old + old / 2 + 256, c->tab.tab_fail_from));
+    if (need > c->tab.tab_fail_from) return false;
+    if (need <= c->tab.p1_h.size()) return true;
+    const size_t old = c->tab.p1_h.size(), n = std::max(need, std::min<size_t>(old + old / 2 + 256, c->tab.tab_fail_from));
     const long double one_me = (long double)(double)(1 - c->tab.eps);
     const ME rho = me_norm((long double)c->tab.eps / one_me, 0), sigma = me_norm(0.5L / one_me, 0);
     // tau = rho / sigma^2 = 4 eps (1 - eps): the same long-double eps and 1 - eps as rho and sigma are made of
     const ME tau = me_norm(4.0L * (long double)c->tab.eps * one_me, 0);
-    c->tab.p1_h.resize(n);
-    c->tab.p2_h.resize(n);
-    c->tab.p3_h.resize(n);
-    c->tab.pb_h.resize(n);
+    const auto resize = [&](size_t k) { c->tab.p1_h.resize(k); c->tab.p2_h.resize(k); c->tab.p3_h.resize(k); c->tab.pb_h.resize(k); };
+    resize(n);
     for (size_t k = old; k < n; ++k) {
         const ME x = me_powl(rho, k), y = me_powl(sigma, k), z = me_pow(1 - c->tab.eps, k), u = me_powl(tau, k);
         if (x.e < -2000000000LL / 3 || y.e < -2000000000LL / 3 || z.e < -2000000000LL / 3 || u.e < -2000000000LL / 3 ||
             u.e > 2000000000LL / 3) {
             c->tab.tab_fail_from = k;
-            c->tab.p1_h.resize(k);
-            c->tab.p2_h.resize(k);
-            c->tab.p3_h.resize(k);
-            c->tab.pb_h.resize(k);
+            resize(k);
             c->tab.tab_dev = std::min(c->tab.tab_dev, k);
             return need <= k;
         }
@@ -568,7 +560,8 @@ double wait_timeout_s()
 // one word in host memory, which the last workgroup of the stage writes -- no copy to queue, no stream to drain
 // (each of those is a round trip of 10-15 us; an upload has two).  The stream is asked now and then whether it
 // has died under us, and the poll is bounded by wall time: a stream that neither finishes nor fails (a wedged queue)
-// ends the call with an error instead of a host thread spinning for ever.  prep_dirty stays set on every failure.
+// ends the call with an error instead of a host thread spinning for ever.  (The messages say ibdg_upload_sites whichever
+// entry point the stage belongs to, like upload_sites_check's.)
 int wait_info(ibdg_ctx *c, uint32_t seq)
 {
     hipError_t last = hipSuccess;
@@ -576,32 +569,66 @@ int wait_info(ibdg_ctx *c, uint32_t seq)
         last = hipStreamQuery(c->stream);
         return last == hipErrorNotReady ? 0 : (last == hipSuccess ? 1 : 2);
     });
-    if (rc == 0)
-        return 0;
-    if (rc == 1)
-        return fail(c, "[::] ERROR in ibdg_upload_sites: the site preparation finished without reporting");
+    if (rc == 0) return 0;
+    if (rc == 1) return fail(c, "[::] ERROR in ibdg_upload_sites: the site preparation finished without reporting");
     if (rc == 2)
         return fail(c, "[::] ERROR in ibdg_upload_sites: the site preparation did not report within %.0f s (stream: %s)",
                     wait_timeout_s(), hipGetErrorString(hipStreamQuery(c->stream)));
     return fail(c, "[::] ERROR in ibdg_upload_sites: %s", hipGetErrorString(last));
 }
 
-// Segments, per-window constants, control words and power tables of the fast --LD kernel, built on
-// the device from the covered-row list (ibdg_prep.hip); the host keeps what depends on the window
-// count only (the run structure) and the epsilon-only power tables.
-int build_segments(ibdg_ctx *c, bool compact)
+// A PrepInfo nothing has been reported into: the device's block between uploads, and the mirror of an empty site list
+ibdg::PrepInfo empty_prep_info()
 {
-    c->lay.pop_sites_ok = false;
-    if (!c->tab.pop_lut_ok || c->sites.n_cov == 0)
-        return 0;
-    const ibdg::PrepInfo &I = *c->sites.info_h;
+    ibdg::PrepInfo i{};
+    i.err_row_site = i.err_cov_site = i.first_row = 0xffffffffu;
+    return i;
+}
+
+// One stage of the preparation and its hand-over (the protocol: ibdg_ctx::Sites).  launch(seq) queues the stage, whose last
+// workgroup hands over as number seq, with the event records and waits that belong to it.  prep_dirty stays set on failure.
+template <class L>
+int hand_over(ibdg_ctx *c, L launch)
+{
+    c->sites.prep_dirty = true;
+    const uint32_t seq = ++c->sites.prep_seq;
+    if (launch(seq)) return 1;
+    HIP_TRY(c, hipGetLastError());
+    if (wait_info(c, seq)) return 1;
+    c->sites.prep_dirty = false;                      // the stage's last workgroup has left everything clean
+    return 0;
+}
+
+// ---- Segments, per-window constants, control words and power tables of the fast --LD kernel, built on the device from the
+// covered-row list (ibdg_prep.hip); the host keeps what depends on the window count only (the run structure) and the
+// epsilon-only power tables.  build_segments: plan, stages, verdict, commit. ----
+
+enum class Built { yes, not_applicable, failed };     // not_applicable: this layout does not serve the list, another may
+
+// One attempt at a layout: what plan_layout decides before anything is queued, then what stage B reported (cut_segments)
+struct LayoutTry {
+    bool compact = false;
+    uint32_t win_rows = 0, n_pairs_c = 0;   // compacted tiles: virtual rows per window, tile pairs of them all (else 0)
+    uint32_t seg_cap = 0, ring = 0;         // segments the device may write; ring depth of the control words
+    uint32_t g = 0, n_runs = 0;             // windows per workgroup run: the first length, then the one the cut ended on
+    ibdg::PrepInfo rep{};                   // stage B's last hand-over: n_segs, ct_max, max_seg, out_of_order, adv_overflow
+    int tab_in_lds() const { return (size_t)(rep.ct_max + 1) * 32 <= 24 * 1024; }
+    // what no run length mends: rows out of file order on the panel's own tiles; segments over the capacity (the device stopped writing)
+    bool beyond_mending() const { return (!compact && rep.out_of_order) || rep.n_segs > seg_cap; }
+};
+
+// Returns false where the compacted tiles' row or pair numbers would leave 31 bits.  Touches no device, writes nothing into c.
+bool plan_layout(const ibdg_ctx *c, bool compact, LayoutTry &P)
+{
     // virtual rows per window of the compacted layout: the window rounded up to the alignment asked for (1 = the rows back
     // to back, 32 = every window on a tile boundary)
     const uint32_t align = (uint32_t)std::min<long>(32, std::max<long>(1, c->opt.compact_align));
     const uint64_t win_rows = ((uint64_t)c->sites.window + align - 1) / align * align;
     const uint64_t vtiles = ((uint64_t)c->sites.n_win * win_rows + 31) / 32;        // tiles of all its virtual rows
-    if (compact && win_rows >= (1ull << 31))
-        return 0;
+    const uint64_t pairs = (vtiles + 1) / 2;
+    if (compact && (win_rows >= (1ull << 31) || pairs >= (1ull << 31))) return false;
+    P.compact = compact; P.win_rows = compact ? (uint32_t)win_rows : 0u;
+    P.n_pairs_c = compact ? (uint32_t)((pairs + 3) & ~3ull) : 0u;
     // segments <= windows + tiles spanned when the rows are in file order (otherwise the device stops
     // writing at the capacity and the exponent-counting kernel is not used); never more than stage A cleared
     uint64_t seg_cap = c->sites.n_cov;
@@ -610,112 +637,106 @@ int build_segments(ibdg_ctx *c, bool compact)
         seg_cap = std::min<uint64_t>(seg_cap, (uint64_t)c->sites.n_win + vtiles + 1);
     else if (last_row >= first_row)
         seg_cap = std::min<uint64_t>(seg_cap, (uint64_t)c->sites.n_win + ((last_row >> 5) - (first_row >> 5)) + 1);
-    seg_cap = std::min<uint64_t>(seg_cap, c->sites.seg_room);
-    if (compact) {
-        // the rows with reads, gathered and transposed into tiles that start with their window
-        const uint64_t pairs = (vtiles + 1) / 2;
-        if (pairs >= (1ull << 31))
-            return 0;
-        c->lay.n_pairs_c = (uint32_t)((pairs + 3) & ~3ull);
-        if (ensure(c, c->lay.t32c, (size_t)c->pan.n_chunks * c->lay.n_pairs_c * 64 * 16))
-            return 1;
-        ibdg::launch_gather_transpose32((const uint64_t *)c->pan.panel.p, c->pan.stride, (const uint2 *)c->sites.rec_cov.p, c->sites.n_cov,
-                                        c->sites.window, (uint32_t)win_rows, c->pan.n_chunks, c->lay.n_pairs_c, (uint32_t *)c->lay.t32c.p, c->stream);
-        HIP_TRY(c, hipGetLastError());
-    }
-    if (ensure(c, c->lay.wconst, ((size_t)c->sites.n_win + 1) * sizeof(ibdg::WinConst)) ||
-        ensure(c, c->lay.wraw, (size_t)c->sites.n_win * sizeof(ibdg::WinRaw)))
-        return 1;
-    if (!c->tab.nck_dev.p) {
-        // the coefficients normalised here (C << clz(C), 64 - clz(C)): the device multiplies them as they are
-        std::vector<ibdg::WinRaw> nn(c->tab.nck_h.size());
-        for (size_t i = 0; i < nn.size(); ++i) {
-            const unsigned long v = c->tab.nck_h[i];
-            const int z = v ? __builtin_clzl(v) : 63;
-            nn[i].m = v ? (uint64_t)v << z : (uint64_t)1 << 63;         // (0 is never looked up: r <= cov)
-            nn[i].e = v ? 64 - z : 1;
-            nn[i].pad = 0;
-        }
-        if (ensure(c, c->tab.nck_dev, nn.size() * sizeof(ibdg::WinRaw))) return 1;
-        // (a blocking copy, once per context: the kernel that reads the table runs on the second stream)
-        HIP_TRY(c, hipMemcpy(c->tab.nck_dev.p, nn.data(), nn.size() * sizeof(ibdg::WinRaw), hipMemcpyHostToDevice));
-    }
-    ibdg::PrepSegArgs sa;
-    sa.rec_cov = (const uint2 *)c->sites.rec_cov.p;
-    sa.n_cov = c->sites.n_cov;
-    sa.window = c->sites.window;
-    sa.n_win = c->sites.n_win;
-    sa.max_cov = c->tab.max_cov;
-    sa.nck = (const ibdg::WinRaw *)c->tab.nck_dev.p;
-    sa.segs = (ibdg::Seg *)c->lay.segs.p;
-    sa.seg_first = (uint32_t *)c->lay.seg_first.p;
-    sa.seg_cap = (uint32_t)seg_cap;
-    sa.wconst = (ibdg::WinConst *)c->lay.wconst.p;
-    sa.raw = (ibdg::WinRaw *)c->lay.wraw.p;
-    sa.block_tmp = (uint32_t *)c->sites.scan_tmp.p;
-    sa.info = (ibdg::PrepInfo *)c->sites.info_dev.p;
-    sa.mirror = c->sites.info_h;
-    sa.compact = compact ? (uint32_t)win_rows : 0u;
-    c->sites.prep_dirty = true;
-    // windows per workgroup run: as many as keep the run's records within the LDS budget
-    uint32_t g = (uint32_t)std::max<long>(1, c->opt.wpg);
+    P.seg_cap = (uint32_t)std::min<uint64_t>(seg_cap, c->sites.seg_room);
+    // windows per workgroup run: as many as keep the run's records within the LDS budget (cut_segments halves it)
+    P.g = (uint32_t)std::max<long>(1, c->opt.wpg);
     if (!c->opt.guided && !c->opt.wpg_fixed) {
         // uniform runs and few windows (a shard of a chromosome, a small region): shorter runs, so that
         // the grid still holds several rounds of workgroups for every CU
         const uint64_t rows_of_blocks = (c->pan.n_chunks + 7) / 8;
         const uint64_t want_blocks = (uint64_t)c->n_cu * 2 * 5;          // CUs x resident blocks x rounds
-        const uint64_t g_fit = std::max<uint64_t>(1, (uint64_t)c->sites.n_win * rows_of_blocks / want_blocks);
-        if (g_fit < g)
-            g = (uint32_t)g_fit;
+        P.g = (uint32_t)std::min<uint64_t>(P.g, std::max<uint64_t>(1, (uint64_t)c->sites.n_win * rows_of_blocks / want_blocks));
     }
-    const uint32_t NS = (uint32_t)c->opt.ring;
-    for (bool first_try = true;; g = (g + 1) / 2, first_try = false) {
-        make_runs(c, g, c->lay.runs_h);
-        c->lay.n_runs = (uint32_t)c->lay.runs_h.size() - 1;
-        if (ensure(c, c->lay.runs, c->lay.runs_h.size() * 4))
-            return 1;
-        // runs_h is a member: it outlives the copy (the next wait is wait_info below)
-        HIP_TRY(c, hipMemcpyAsync(c->lay.runs.p, c->lay.runs_h.data(), c->lay.runs_h.size() * 4, hipMemcpyHostToDevice, c->stream));
-        if (first_try) {
-            // the run structure goes ahead of the segment kernels, whose last one makes the control words for it
-            // (stream2 is idle: ibdg_upload_sites drained both streams before it began; it waits for stage A's records)
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->sites.ev_prepA, 0));
-            ibdg::launch_prep_segments(sa, (const uint32_t *)c->lay.runs.p, c->lay.n_runs, NS, c->stream, c->stream2);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipEventRecord(c->sites.ev_prep2, c->stream2));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sites.ev_prep2, 0));      // before the hand-over (ct_max) and K'
-        }
-        ibdg::launch_prep_seg_flags(sa, (const uint32_t *)c->lay.runs.p, c->lay.n_runs, NS, ++c->sites.prep_seq, c->stream, !first_try);
+    P.ring = (uint32_t)c->opt.ring;
+    return true;
+}
+
+// What stage B reads besides stage A's records and where it writes the windows' constants: the compacted tiles (the rows
+// with reads, gathered and transposed into tiles that start with their window) and, once per context, the binomial coefficients
+int layout_inputs(ibdg_ctx *c, const LayoutTry &T)
+{
+    if (T.compact) {
+        if (ensure(c, c->lay.t32c, (size_t)c->pan.n_chunks * T.n_pairs_c * 64 * 16)) return 1;
+        ibdg::launch_gather_transpose32((const uint64_t *)c->pan.panel.p, c->pan.stride, (const uint2 *)c->sites.rec_cov.p, c->sites.n_cov,
+                                        c->sites.window, T.win_rows, c->pan.n_chunks, T.n_pairs_c, (uint32_t *)c->lay.t32c.p, c->stream);
         HIP_TRY(c, hipGetLastError());
-        if (wait_info(c, c->sites.prep_seq))
-            return 1;
-        c->sites.prep_dirty = false;
-        if ((!compact && I.out_of_order) || I.n_segs > seg_cap)
-            return 0;                      // not in file order: the panel's own tiles do not apply
-        if ((size_t)I.max_seg * (sizeof(ibdg::Seg) + 8) <= (size_t)c->opt.recbytes || g == 1)
-            break;
     }
-    if (I.adv_overflow)
-        return 0;                          // rows too far apart for the record format: strict kernel
-    c->lay.wpg = g;
-    c->lay.max_seg = I.max_seg;
-    c->lay.seg_ring = (int)NS;
-    c->lay.n_segs = I.n_segs;
-    c->lay.ct_max = I.ct_max;
-    c->lay.tab_in_lds = (size_t)(c->lay.ct_max + 1) * 32 <= 24 * 1024;
-    if (ibdg::ld_popcount_lds_bytes(c->lay.max_seg, c->lay.wpg, c->lay.ct_max + 1, c->lay.tab_in_lds, c->lay.seg_ring, 0) > 150 * 1024)
-        return 0;                          // a single window with thousands of tiles: strict kernel
-    if (!grow_pow_tables(c, (size_t)c->lay.ct_max + 1))
-        return 0;
+    if (ensure(c, c->lay.wconst, ((size_t)c->sites.n_win + 1) * sizeof(ibdg::WinConst))) return 1;
+    if (ensure(c, c->lay.wraw, (size_t)c->sites.n_win * sizeof(ibdg::WinRaw))) return 1;
+    if (c->tab.nck_dev.p) return 0;
+    // the coefficients normalised here (C << clz(C), 64 - clz(C)): the device multiplies them as they are
+    std::vector<ibdg::WinRaw> nn(c->tab.nck_h.size());
+    for (size_t i = 0; i < nn.size(); ++i) {
+        const unsigned long v = c->tab.nck_h[i];
+        const int z = v ? __builtin_clzl(v) : 63;
+        nn[i] = {v ? (uint64_t)v << z : (uint64_t)1 << 63, v ? 64 - z : 1, 0};         // (0 is never looked up: r <= cov)
+    }
+    if (ensure(c, c->tab.nck_dev, nn.size() * sizeof(ibdg::WinRaw))) return 1;
+    // (a blocking copy, once per context: the kernel that reads the table runs on the second stream)
+    HIP_TRY(c, hipMemcpy(c->tab.nck_dev.p, nn.data(), nn.size() * sizeof(ibdg::WinRaw), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// Stage B for the run structure in c->lay.runs.  The first pass cuts the segments, whose last kernel makes the control
+// words for that structure; a later pass makes the control words anew for another one.
+int queue_stage_b(ibdg_ctx *c, const ibdg::PrepSegArgs &sa, uint32_t n_runs, uint32_t ring, uint32_t seq, bool first_pass)
+{
+    const uint32_t *runs = (const uint32_t *)c->lay.runs.p;
+    if (first_pass) {
+        // (stream2 is idle: ibdg_upload_sites drained both streams before it began; it waits for stage A's records)
+        HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->sites.ev_prepA, 0));
+        ibdg::launch_prep_segments(sa, runs, n_runs, ring, c->stream, c->stream2);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->sites.ev_prep2, c->stream2));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->sites.ev_prep2, 0));      // before the hand-over (ct_max) and K'
+    }
+    ibdg::launch_prep_seg_flags(sa, runs, n_runs, ring, seq, c->stream, !first_pass);
+    return 0;
+}
+
+// Stage B's first pass on runs of P.g windows, then the run length halved until a run's records fit the LDS budget
+int cut_segments(ibdg_ctx *c, LayoutTry &T)
+{
+    ibdg::PrepSegArgs sa;
+    sa.rec_cov = (const uint2 *)c->sites.rec_cov.p; sa.n_cov = c->sites.n_cov; sa.window = c->sites.window; sa.n_win = c->sites.n_win;
+    sa.max_cov = c->tab.max_cov; sa.nck = (const ibdg::WinRaw *)c->tab.nck_dev.p; sa.compact = T.win_rows;
+    sa.segs = (ibdg::Seg *)c->lay.segs.p; sa.seg_first = (uint32_t *)c->lay.seg_first.p; sa.seg_cap = T.seg_cap;
+    sa.wconst = (ibdg::WinConst *)c->lay.wconst.p; sa.raw = (ibdg::WinRaw *)c->lay.wraw.p;
+    sa.block_tmp = (uint32_t *)c->sites.scan_tmp.p; sa.info = (ibdg::PrepInfo *)c->sites.info_dev.p; sa.mirror = c->sites.info_h;
+    for (bool first_pass = true;; T.g = (T.g + 1) / 2, first_pass = false) {
+        // the run structure goes ahead of the kernels that make the control words for it
+        make_runs(c, T.g, c->lay.runs_h);
+        T.n_runs = (uint32_t)c->lay.runs_h.size() - 1;
+        if (ensure(c, c->lay.runs, c->lay.runs_h.size() * 4)) return 1;
+        // runs_h is a member: it outlives the copy (the next wait is the hand-over's)
+        HIP_TRY(c, hipMemcpyAsync(c->lay.runs.p, c->lay.runs_h.data(), c->lay.runs_h.size() * 4, hipMemcpyHostToDevice, c->stream));
+        if (hand_over(c, [&](uint32_t seq) { return queue_stage_b(c, sa, T.n_runs, T.ring, seq, first_pass); })) return 1;
+        T.rep = *c->sites.info_h;
+        if (T.beyond_mending() || (size_t)T.rep.max_seg * (sizeof(ibdg::Seg) + 8) <= (size_t)c->opt.recbytes || T.g == 1)
+            return 0;
+    }
+}
+
+// Every reason why the layout that was cut does not serve, in the order they are asked: rows out of file order on the
+// panel's own tiles, segments over the capacity; rows too far apart for the record format (adv_overflow); a single window with
+// thousands of tiles (LDS above 150 KiB); a power that leaves the 32-bit exponent field (asking grows the host's tables).
+bool layout_refused(ibdg_ctx *c, const LayoutTry &T)
+{
+    return T.beyond_mending() || T.rep.adv_overflow ||
+           ibdg::ld_popcount_lds_bytes(T.rep.max_seg, T.g, T.rep.ct_max + 1, T.tab_in_lds(), (int)T.ring, 0) > 150 * 1024 ||
+           !grow_pow_tables(c, (size_t)T.rep.ct_max + 1);
+}
+
+// An accepted layout takes effect: the power tables' new entries, K', and c->lay's scalar fields (their only writer)
+int commit_layout(ibdg_ctx *c, const LayoutTry &T)
+{
     if (c->tab.tab_dev < c->tab.p1_h.size()) {     // new entries since the last upload
-        const size_t n = c->tab.p1_h.size();
-        if (ensure(c, c->tab.pow1, n * sizeof(ibdg::PowEntry)) || ensure(c, c->tab.pow2, n * sizeof(ibdg::PowEntry)) ||
-            ensure(c, c->tab.pow3, n * sizeof(ibdg::PowEntry)) || ensure(c, c->tab.powb, n * sizeof(ibdg::WinRaw)))
-            return 1;
-        HIP_TRY(c, hipMemcpyAsync(c->tab.pow3.p, c->tab.p3_h.data(), n * sizeof(ibdg::PowEntry), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->tab.pow1.p, c->tab.p1_h.data(), n * sizeof(ibdg::PowEntry), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->tab.pow2.p, c->tab.p2_h.data(), n * sizeof(ibdg::PowEntry), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->tab.powb.p, c->tab.pb_h.data(), n * sizeof(ibdg::WinRaw), hipMemcpyHostToDevice, c->stream));
+        const size_t n = c->tab.p1_h.size(), pe = n * sizeof(ibdg::PowEntry), wr = n * sizeof(ibdg::WinRaw);
+        if (ensure(c, c->tab.pow1, pe) || ensure(c, c->tab.pow2, pe) || ensure(c, c->tab.pow3, pe) || ensure(c, c->tab.powb, wr)) return 1;
+        HIP_TRY(c, hipMemcpyAsync(c->tab.pow3.p, c->tab.p3_h.data(), pe, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->tab.pow1.p, c->tab.p1_h.data(), pe, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->tab.pow2.p, c->tab.p2_h.data(), pe, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->tab.powb.p, c->tab.pb_h.data(), wr, hipMemcpyHostToDevice, c->stream));
         c->tab.tab_dev = n;
     }
     // K' = K * (1-eps)^(all reads of the window): with it a product is K' * rho^E2 * sigma^E3,
@@ -723,10 +744,27 @@ int build_segments(ibdg_ctx *c, bool compact)
     ibdg::launch_prep_win_kp(c->sites.n_win, (const ibdg::WinRaw *)c->lay.wraw.p, (const ibdg::WinRaw *)c->tab.powb.p,
                              (ibdg::WinConst *)c->lay.wconst.p, c->stream);
     HIP_TRY(c, hipGetLastError());
-    c->lay.pop_sites_ok = true;
-    c->lay.compact = compact;
+    ibdg_ctx::Layout &L = c->lay;
+    L.compact = T.compact;
+    if (T.compact) L.n_pairs_c = T.n_pairs_c;
+    L.wpg = T.g; L.n_runs = T.n_runs; L.seg_ring = (int)T.ring;
+    L.max_seg = T.rep.max_seg; L.n_segs = T.rep.n_segs; L.ct_max = T.rep.ct_max; L.tab_in_lds = T.tab_in_lds();
+    L.pop_sites_ok = true;
     layout_changed(c);
     return 0;
+}
+
+// One attempt at one layout.  It overwrites the buffers of the layout before (segments, constants, runs), so there is none
+// from its start on; only an accepted one reaches commit_layout -- a refused or failed attempt leaves pop_sites_ok false
+// and no other scalar of c->lay touched.  (The caller has seen to pop_lut_ok and n_cov > 0.)
+Built build_segments(ibdg_ctx *c, bool compact)
+{
+    LayoutTry T;
+    c->lay.pop_sites_ok = false;
+    if (!plan_layout(c, compact, T)) return Built::not_applicable;
+    if (layout_inputs(c, T) || cut_segments(c, T)) return Built::failed;
+    if (layout_refused(c, T)) return Built::not_applicable;
+    return commit_layout(c, T) ? Built::failed : Built::yes;
 }
 
 // Sparse coverage: on the panel's own tiles the exponent-counting kernels stream every 32-row tile between a
@@ -735,8 +773,7 @@ int build_segments(ibdg_ctx *c, bool compact)
 // 100 rows).  Below about one covered row in four the compacted layout is the faster one for a single run.
 bool sparse_sites(const ibdg_ctx *c)
 {
-    if (c->sites.last_row < c->sites.first_row)
-        return true;                       // not even the ends are in file order
+    if (c->sites.last_row < c->sites.first_row) return true;        // not even the ends are in file order
     const uint64_t span = (uint64_t)c->sites.last_row - c->sites.first_row + 1;
     return (uint64_t)c->sites.n_cov * (uint64_t)std::max<long>(1, c->opt.compact_density) < span;
 }
@@ -748,14 +785,13 @@ int build_layout(ibdg_ctx *c)
     c->lay.pop_sites_ok = false;
     c->lay.compact = false;
     c->lay.pop_dense_enough = true;
-    if (!c->tab.pop_lut_ok || c->sites.n_cov == 0)
-        return 0;
+    if (!c->tab.pop_lut_ok || c->sites.n_cov == 0) return 0;
     const bool sparse = sparse_sites(c);
     const bool want_compact = c->opt.compact > 0 || (c->opt.compact == 0 && sparse);
-    if (build_segments(c, want_compact))
-        return 1;
-    if (!c->lay.pop_sites_ok && !want_compact && c->opt.compact == 0 && build_segments(c, true))
-        return 1;
+    Built b = build_segments(c, want_compact);
+    if (b == Built::not_applicable && !want_compact && c->opt.compact == 0)
+        b = build_segments(c, true);
+    if (b == Built::failed) return 1;
     if (c->opt.compact < 0 && sparse)
         c->lay.pop_dense_enough = false;       // the caller forbade the layout this pileup wants: the strict kernel is the faster one
     return 0;
@@ -1016,12 +1052,9 @@ int ibdg_upload_panel_dev(ibdg_ctx *c, const void *dev_rows, size_t n_rows, unsi
 static int clean_prep_info(ibdg_ctx *c)
 {
     const bool fresh_info = !c->sites.info_dev.p;
-    if (ensure(c, c->sites.info_dev, sizeof(ibdg::PrepInfo)))
-        return 1;
+    if (ensure(c, c->sites.info_dev, sizeof(ibdg::PrepInfo))) return 1;
     if (fresh_info || c->sites.prep_dirty) {
-        ibdg::PrepInfo init;
-        memset(&init, 0, sizeof init);
-        init.err_row_site = init.err_cov_site = init.first_row = 0xffffffffu;
+        const ibdg::PrepInfo init = empty_prep_info();
         HIP_TRY(c, hipMemcpyAsync(c->sites.info_dev.p, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));          // `init` is a local
         c->sites.prep_dirty = false;
@@ -1029,14 +1062,24 @@ static int clean_prep_info(ibdg_ctx *c)
     return 0;
 }
 
-// Everything an upload of sites does once the three input arrays are on the device.  fo_ready: the sites' -A triples are in
-// c->sites.fo already (ibdg_select_variable_sites compacts the candidates' there); f_override is not looked at.
-static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *d_ref, const uint8_t *d_alt,
-                             const double *f_override, size_t n_sites, unsigned window, bool fo_ready = false)
+// The -A triples {f, pow(1-f,2), pow(f,2)} with the host's libm, {NaN, 0, 0} where no frequency is given; whether any is
+static bool fo_triples(const double *f_override, size_t n, std::vector<double> &out)
 {
-    sites_replaced(c);
-    c->sites.n_sites = n_sites;
-    c->sites.window = window;
+    bool any = false;
+    out.resize(3 * n);
+    for (size_t s = 0; s < n; ++s) {
+        const double f = f_override[s];
+        out[3 * s] = f;
+        out[3 * s + 1] = f == f ? libm_pow(1 - f, 2.0) : 0.0;
+        out[3 * s + 2] = f == f ? libm_pow(f, 2.0) : 0.0;
+        any |= f == f;
+    }
+    return any;
+}
+
+// The steps of an upload of sites, in upload_sites_core's order.  First the buffers of stages A and B:
+static int size_site_buffers(ibdg_ctx *c, size_t n_sites, unsigned window)
+{
     // segments of stage B: at most one per site, and in file order at most windows + tiles of the panel
     // (compacted tiles: windows + tiles of their virtual rows, at most window + 31 per window)
     const size_t n_win_max = (n_sites + window - 1) / window;
@@ -1047,100 +1090,98 @@ static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *
         (c->tab.pop_lut_ok && (ensure(c, c->lay.segs, seg_room * sizeof(ibdg::Seg)) || ensure(c, c->lay.seg_first, seg_room * 4))))
         return 1;
     c->sites.seg_room = c->tab.pop_lut_ok ? seg_room : 0;
-    if (n_sites) {
-        c->sites.prep_dirty = true;
-        ibdg::PrepSiteArgs pa;
-        pa.row_index = d_row;
-        pa.n_ref = d_ref;
-        pa.n_alt = d_alt;
-        pa.n_sites = n_sites;
-        pa.n_rows = c->pan.n_rows;
-        pa.max_cov = c->tab.max_cov;
-        pa.rec_all = (uint2 *)c->sites.rec_all.p;
-        pa.rec_cov = (uint2 *)c->sites.rec_cov.p;
-        pa.cov_site = (uint32_t *)c->sites.cov_site.p;
-        pa.block_tmp = (uint32_t *)c->sites.scan_tmp.p;
-        pa.info = (ibdg::PrepInfo *)c->sites.info_dev.p;
-        pa.mirror = c->sites.info_h;
-        pa.seq = ++c->sites.prep_seq;
-        ibdg::launch_prep_sites(pa, c->stream);
-        HIP_TRY(c, hipGetLastError());
-        // (the hand-over comes from the scan, BEFORE the scatter kernel: whatever reads the site records on the second
-        // stream waits for this event; the main stream is ordered anyway)
-        HIP_TRY(c, hipEventRecord(c->sites.ev_prepA, c->stream));
-        if (wait_info(c, c->sites.prep_seq))
-            return 1;
-        c->sites.prep_dirty = false;                  // the stage's last workgroup has left everything clean
-    } else {
-        c->sites.prep_dirty = false;
-        memset(c->sites.info_h, 0, sizeof(ibdg::PrepInfo));
-        c->sites.info_h->err_row_site = c->sites.info_h->err_cov_site = c->sites.info_h->first_row = 0xffffffffu;
-        c->sites.info_h->seq = c->sites.prep_seq;
-    }
+    return 0;
+}
+
+// Stage A: the site records, the covered rows and their count, the first offending site
+static int queue_stage_a(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *d_ref, const uint8_t *d_alt, size_t n_sites, uint32_t seq)
+{
+    ibdg::PrepSiteArgs pa;
+    pa.row_index = d_row; pa.n_ref = d_ref; pa.n_alt = d_alt; pa.n_sites = n_sites; pa.n_rows = c->pan.n_rows; pa.max_cov = c->tab.max_cov;
+    pa.rec_all = (uint2 *)c->sites.rec_all.p; pa.rec_cov = (uint2 *)c->sites.rec_cov.p; pa.cov_site = (uint32_t *)c->sites.cov_site.p;
+    pa.block_tmp = (uint32_t *)c->sites.scan_tmp.p; pa.info = (ibdg::PrepInfo *)c->sites.info_dev.p; pa.mirror = c->sites.info_h; pa.seq = seq;
+    ibdg::launch_prep_sites(pa, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    // (the hand-over comes from the scan, BEFORE the scatter kernel: whatever reads the site records on the second
+    // stream waits for this event; the main stream is ordered anyway)
+    HIP_TRY(c, hipEventRecord(c->sites.ev_prepA, c->stream));
+    return 0;
+}
+
+// The selection in front of stage A (-v): the candidates at which `target` is not 0/0 into in_row / in_ref / in_alt (and
+// fo), their candidate numbers into sel_cand, their count into the mirror's n_cov
+static int queue_selection(ibdg_ctx *c, uint32_t target, uint32_t seq)
+{
+    ibdg::SelectArgs sa;
+    sa.row = c->cand.have_rows ? (const uint32_t *)c->cand.row.p : nullptr; sa.fo = c->cand.have_fo ? (const double *)c->cand.fo.p : nullptr;
+    sa.n_ref = (const uint8_t *)c->cand.ref.p; sa.n_alt = (const uint8_t *)c->cand.alt.p; sa.n_cand = c->cand.n_cand; sa.target = target;
+    sa.t32 = c->tab.pop_lut_ok ? (const uint4 *)c->pan.t32.p : nullptr;      // (no transposed panel with a clamped table)
+    sa.n_pairs = c->pan.n_pairs; sa.panel = (const uint64_t *)c->pan.panel.p; sa.stride = c->pan.stride;
+    sa.out_row = (uint32_t *)c->sites.in_row.p; sa.out_ref = (uint8_t *)c->sites.in_ref.p; sa.out_alt = (uint8_t *)c->sites.in_alt.p;
+    sa.out_cand = (uint32_t *)c->cand.sel_cand.p; sa.out_fo = (double *)c->sites.fo.p;
+    sa.block_tmp = (uint32_t *)c->sites.scan_tmp.p; sa.info = (ibdg::PrepInfo *)c->sites.info_dev.p; sa.mirror = c->sites.info_h; sa.seq = seq;
+    ibdg::launch_select_sites(sa, c->stream);
+    return 0;
+}
+
+// The first offending site in file order, its row checked before its counts (as a loop over the sites would); 0: there is none
+static int report_bad_site(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *d_ref, const uint8_t *d_alt)
+{
     const ibdg::PrepInfo &I = *c->sites.info_h;
-    if (I.err_row_site != 0xffffffffu || I.err_cov_site != 0xffffffffu) {
-        // the first offending site in file order, its row checked before its counts (as a loop over the sites would)
-        c->sites.n_sites = 0;
-        if (I.err_row_site <= I.err_cov_site) {
-            uint32_t row = 0;
-            HIP_TRY(c, hipMemcpy(&row, d_row + I.err_row_site, 4, hipMemcpyDeviceToHost));
-            return fail(c, "[::] ERROR in ibdg_upload_sites: row_index[%zu]=%u outside the panel (%zu rows)",
-                        (size_t)I.err_row_site, row, c->pan.n_rows);
-        }
-        uint8_t r = 0, a = 0;
-        HIP_TRY(c, hipMemcpy(&r, d_ref + I.err_cov_site, 1, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(&a, d_alt + I.err_cov_site, 1, hipMemcpyDeviceToHost));
-        return fail(c, "[::] ERROR in ibdg_upload_sites: site %zu has n_ref+n_alt=%u > max_cov=%u",
-                    (size_t)I.err_cov_site, (unsigned)r + a, c->tab.max_cov);
+    if (I.err_row_site == 0xffffffffu && I.err_cov_site == 0xffffffffu) return 0;
+    c->sites.n_sites = 0;
+    if (I.err_row_site <= I.err_cov_site) {
+        uint32_t row = 0;
+        HIP_TRY(c, hipMemcpy(&row, d_row + I.err_row_site, 4, hipMemcpyDeviceToHost));
+        return fail(c, "[::] ERROR in ibdg_upload_sites: row_index[%zu]=%u outside the panel (%zu rows)",
+                    (size_t)I.err_row_site, row, c->pan.n_rows);
     }
+    uint8_t r = 0, a = 0;
+    HIP_TRY(c, hipMemcpy(&r, d_ref + I.err_cov_site, 1, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&a, d_alt + I.err_cov_site, 1, hipMemcpyDeviceToHost));
+    return fail(c, "[::] ERROR in ibdg_upload_sites: site %zu has n_ref+n_alt=%u > max_cov=%u",
+                (size_t)I.err_cov_site, (unsigned)r + a, c->tab.max_cov);
+}
+
+// Everything an upload of sites does once the three input arrays are on the device.  fo_ready: the sites' -A triples are in
+// c->sites.fo already (ibdg_select_variable_sites compacts the candidates' there); f_override is not looked at.
+static int upload_sites_core(ibdg_ctx *c, const uint32_t *d_row, const uint8_t *d_ref, const uint8_t *d_alt,
+                             const double *f_override, size_t n_sites, unsigned window, bool fo_ready = false)
+{
+    sites_replaced(c);
+    c->sites.n_sites = n_sites;
+    c->sites.window = window;
+    if (size_site_buffers(c, n_sites, window)) return 1;
+    ibdg::PrepInfo &I = *c->sites.info_h;
+    if (n_sites && hand_over(c, [&](uint32_t seq) { return queue_stage_a(c, d_row, d_ref, d_alt, n_sites, seq); })) return 1;
+    if (n_sites == 0) {                           // nothing was launched: the mirror as stage A would have left it
+        I = empty_prep_info();
+        I.seq = c->sites.prep_seq;
+    }
+    if (report_bad_site(c, d_row, d_ref, d_alt)) return 1;
     c->sites.n_cov = I.n_cov;
-    c->sites.first_row = I.first_row;             // (the mirror is overwritten by stage B's hand-over)
-    c->sites.last_row = I.last_row;
+    c->sites.first_row = I.first_row; c->sites.last_row = I.last_row;     // (the mirror is overwritten by stage B's hand-over)
     c->sites.n_win = (uint32_t)(((uint64_t)c->sites.n_cov + window - 1) / window);
-    if (build_layout(c))
-        return 1;
-    if (fo_ready) {
-        c->sites.have_fo = true;
-    } else if (f_override) {
-        std::vector<double> fo(3 * n_sites);
-        for (size_t s = 0; s < n_sites; ++s) {
-            const double f = f_override[s];
-            fo[3 * s] = f;
-            if (f == f) {
-                fo[3 * s + 1] = libm_pow(1 - f, 2.0);
-                fo[3 * s + 2] = libm_pow(f, 2.0);
-                c->sites.have_fo = true;
-            } else {
-                fo[3 * s + 1] = fo[3 * s + 2] = 0.0;
-            }
-        }
-        if (c->sites.have_fo) {
-            if (ensure(c, c->sites.fo, fo.size() * 8)) return 1;
-            HIP_TRY(c, hipMemcpyAsync(c->sites.fo.p, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));          // `fo` is a local
-        }
+    if (build_layout(c)) return 1;
+    std::vector<double> fo;
+    c->sites.have_fo = fo_ready || (f_override && fo_triples(f_override, n_sites, fo));
+    if (c->sites.have_fo && !fo_ready) {
+        if (ensure(c, c->sites.fo, fo.size() * 8)) return 1;
+        HIP_TRY(c, hipMemcpyAsync(c->sites.fo.p, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));          // `fo` is a local
     }
     return 0;
 }
 
-static int upload_sites_check(ibdg_ctx *c, const void *n_ref, const void *n_alt, bool have_rows, size_t n_sites,
-                              unsigned window)
+static int upload_sites_check(ibdg_ctx *c, const void *n_ref, const void *n_alt, bool have_rows, size_t n_sites, unsigned window)
 {
     if (!c->pan.panel.p || c->pan.n_ids == 0) return fail(c, "[::] ERROR in ibdg_upload_sites: no panel uploaded");
     if (window < 1) return fail(c, "[::] ERROR: Invalid window size (-w) of %u (must be >= 1).", window);
-    if (n_sites && (!n_ref || !n_alt))
-        return fail(c, "[::] ERROR in ibdg_upload_sites: NULL input array");
-    if (n_sites > 0xffffffffull)
-        return fail(c, "[::] ERROR in ibdg_upload_sites: more than 2^32-1 rows in one call");
-    if (!have_rows && n_sites > c->pan.n_rows)
-        return fail(c, "[::] ERROR in ibdg_upload_sites: row_index[%zu]=%zu outside the panel (%zu rows)", c->pan.n_rows,
-                    c->pan.n_rows, c->pan.n_rows);
+    if (n_sites && (!n_ref || !n_alt)) return fail(c, "[::] ERROR in ibdg_upload_sites: NULL input array");
+    if (n_sites > 0xffffffffull) return fail(c, "[::] ERROR in ibdg_upload_sites: more than 2^32-1 rows in one call");
+    const size_t R = c->pan.n_rows;
+    if (!have_rows && n_sites > R) return fail(c, "[::] ERROR in ibdg_upload_sites: row_index[%zu]=%zu outside the panel (%zu rows)", R, R, R);
     return 0;
-}
-
-static double wall_ms(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // After the last kernel of an upload.  The call does not wait for it: everything the host needed it has polled
@@ -1148,12 +1189,11 @@ static double wall_ms(std::chrono::steady_clock::time_point t0)
 // (K' of the windows) on the same stream.  The event clocks are read when somebody asks (ibdg_upload_ms).
 static int upload_sites_finish(ibdg_ctx *c, int rc, std::chrono::steady_clock::time_point t0)
 {
-    if (rc)
-        return rc;
+    if (rc) return rc;
     c->sites.sites_valid = true;
     HIP_TRY(c, hipEventRecord(c->sites.ev_up[2], c->stream));
     c->sites.up_ms_pending = true;
-    c->sites.up_ms[2] = (float)wall_ms(t0);
+    c->sites.up_ms[2] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 
@@ -1227,22 +1267,8 @@ int ibdg_upload_candidates(ibdg_ctx *c, const uint32_t *row_index, const uint8_t
         return 1;
     // the -A triples with the host's libm, once for every list cut from these candidates
     std::vector<double> fo;
-    bool have_fo = false;
-    if (f_override) {
-        fo.resize(3 * n_cand);
-        for (size_t s = 0; s < n_cand; ++s) {
-            const double f = f_override[s];
-            fo[3 * s] = f;
-            if (f == f) {
-                fo[3 * s + 1] = libm_pow(1 - f, 2.0);
-                fo[3 * s + 2] = libm_pow(f, 2.0);
-                have_fo = true;
-            } else {
-                fo[3 * s + 1] = fo[3 * s + 2] = 0.0;
-            }
-        }
-        if (have_fo && ensure(c, c->cand.fo, fo.size() * 8)) return 1;
-    }
+    const bool have_fo = f_override && fo_triples(f_override, n_cand, fo);
+    if (have_fo && ensure(c, c->cand.fo, fo.size() * 8)) return 1;
     if (n_cand) {
         if (row_index)
             HIP_TRY(c, hipMemcpyAsync(c->cand.row.p, row_index, n_cand * 4, hipMemcpyHostToDevice, c->stream));
@@ -1268,8 +1294,7 @@ int ibdg_select_variable_sites(ibdg_ctx *c, uint32_t target, unsigned window)
     if (!c->pan.panel.p || c->pan.n_ids == 0) return fail(c, "[::] ERROR in ibdg_select_variable_sites: no panel uploaded");
     if (!c->cand.valid) return fail(c, "[::] ERROR in ibdg_select_variable_sites: no candidates uploaded");
     if (target >= c->pan.n_ids)
-        return fail(c, "[::] ERROR in ibdg_select_variable_sites: individual %u outside the panel (%u individuals)", target,
-                    c->pan.n_ids);
+        return fail(c, "[::] ERROR in ibdg_select_variable_sites: individual %u outside the panel (%u individuals)", target, c->pan.n_ids);
     if (window < 1) return fail(c, "[::] ERROR: Invalid window size (-w) of %u (must be >= 1).", window);
     if (quiesce(c)) return 1;
     const size_t n = c->cand.n_cand;
@@ -1279,38 +1304,11 @@ int ibdg_select_variable_sites(ibdg_ctx *c, uint32_t target, unsigned window)
         return 1;
     sites_replaced(c);                  // (the selection kernels overwrite in_* and sel_cand)
     HIP_TRY(c, hipEventRecord(c->sites.ev_up[0], c->stream));
-    size_t n_sel = 0;
-    if (n) {
-        ibdg::SelectArgs sa;
-        sa.row = c->cand.have_rows ? (const uint32_t *)c->cand.row.p : nullptr;
-        sa.n_ref = (const uint8_t *)c->cand.ref.p;
-        sa.n_alt = (const uint8_t *)c->cand.alt.p;
-        sa.fo = c->cand.have_fo ? (const double *)c->cand.fo.p : nullptr;
-        sa.n_cand = n;
-        sa.target = target;
-        sa.t32 = c->tab.pop_lut_ok ? (const uint4 *)c->pan.t32.p : nullptr;      // (no transposed panel with a clamped table)
-        sa.n_pairs = c->pan.n_pairs;
-        sa.panel = (const uint64_t *)c->pan.panel.p;
-        sa.stride = c->pan.stride;
-        sa.out_row = (uint32_t *)c->sites.in_row.p;
-        sa.out_ref = (uint8_t *)c->sites.in_ref.p;
-        sa.out_alt = (uint8_t *)c->sites.in_alt.p;
-        sa.out_cand = (uint32_t *)c->cand.sel_cand.p;
-        sa.out_fo = (double *)c->sites.fo.p;
-        sa.block_tmp = (uint32_t *)c->sites.scan_tmp.p;
-        sa.info = (ibdg::PrepInfo *)c->sites.info_dev.p;
-        sa.mirror = c->sites.info_h;
-        sa.seq = ++c->sites.prep_seq;
-        c->sites.prep_dirty = true;
-        ibdg::launch_select_sites(sa, c->stream);
-        HIP_TRY(c, hipGetLastError());
-        // the number selected comes with the scan's hand-over, like stage A's covered rows: the scatter kernel runs on while
-        // the host sizes stage A's buffers and queues it behind
-        if (wait_info(c, c->sites.prep_seq))
-            return 1;
-        c->sites.prep_dirty = false;
-        n_sel = c->sites.info_h->n_cov;
-    }
+    // the number selected comes with the scan's hand-over, like stage A's covered rows: the scatter kernel runs on while
+    // the host sizes stage A's buffers and queues it behind
+    if (n && hand_over(c, [&](uint32_t seq) { return queue_selection(c, target, seq); }))
+        return 1;
+    const size_t n_sel = n ? c->sites.info_h->n_cov : 0;
     HIP_TRY(c, hipEventRecord(c->sites.ev_up[1], c->stream));
     // candidates that are the panel's own rows: a selected site's candidate index is its row
     const uint32_t *d_row = (const uint32_t *)(c->cand.have_rows ? c->sites.in_row.p : c->cand.sel_cand.p);
@@ -1549,8 +1547,10 @@ int relayout_when_paid(ibdg_ctx *c, size_t T)
     c->lay.relayout_credit += to_mfma ? (uint64_t)((T + IBDG_TG - 1) / IBDG_TG) * 20u : (uint64_t)T * (c->opt.mx_counts ? 12u : 16u);
     if (c->lay.relayout_credit >= (uint64_t)std::max<long>(1, c->opt.compact_targets)) {
         if (quiesce(c)) return 1;
-        if (build_segments(c, true)) return 1;
-        if (!c->lay.pop_sites_ok && build_segments(c, false)) return 1;     // (cannot happen: it applied a moment ago)
+        Built b = build_segments(c, true);
+        if (b == Built::not_applicable)
+            b = build_segments(c, false);  // back to the panel's own tiles (cannot be refused: it applied a moment ago)
+        return b == Built::failed;
     }
     return 0;
 }

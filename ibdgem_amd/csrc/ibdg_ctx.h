@@ -159,7 +159,13 @@ struct ibdg_ctx {
         void free_bufs() { release_all({&row, &ref, &alt, &fo, &sel_cand}); }
     } cand;
 
-    // One upload of sites (the sites of the current comparison) and its hand-over from the preparation kernels
+    // One upload of sites (the sites of the current comparison) and its hand-over from the preparation kernels.
+    // The hand-over: every stage of the preparation (the selection of -v, stage A, each pass of stage B) accumulates what the
+    // host must learn in info_dev, and its last workgroup copies the block to info_h, writes the stage's number to
+    // info_h->seq last, and leaves info_dev as empty_prep_info() for the next.  The host takes the next number from prep_seq,
+    // queues the stage and polls info_h->seq for it (wait_info).  Writers: the device alone writes info_dev and info_h, but
+    // for clean_prep_info, which resets a fresh or dirty info_dev, and the upload of an empty list, which fills info_h itself;
+    // hand_over alone writes prep_seq and sets prep_dirty, and it or clean_prep_info clears it.
     struct Sites {
         DevBuf rec_all, rec_cov, cov_site, fo;
         DevBuf in_row, in_ref, in_alt;      // device copies of the caller's arrays (ibdg_upload_sites)
@@ -184,7 +190,11 @@ struct ibdg_ctx {
         { release_all({&rec_all, &rec_cov, &cov_site, &fo, &in_row, &in_ref, &in_alt, &scan_tmp, &info_dev, &win_first, &win_last}); }
     } sites;
 
-    // What build_segments produces from the site list: the fast --LD variant's layout (exponent counting, ibdg_ld_popcount.hip)
+    // What build_segments produces from the site list: the fast --LD variant's layout (exponent counting, ibdg_ld_popcount.hip).
+    // The scalar fields belong to the accepted layout: commit_layout alone writes them.  That there is none say
+    // build_segments at its start (pop_sites_ok), build_layout's reset (which also decides pop_dense_enough), sites_replaced
+    // and panel_replaced; the runs add to relayout_credit.  The buffers and runs_h are filled by the attempt itself, before
+    // its verdict: with pop_sites_ok false they may hold a refused attempt's.
     struct Layout {
         // the compacted tiles of the current site list (k_gather_transpose32) and whether the segments,
         // window constants and control words at hand were cut from them (true) or from the panel's own tiles (false)
