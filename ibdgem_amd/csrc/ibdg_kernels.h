@@ -358,8 +358,9 @@ void launch_llr_sums(const double *win_ll, uint32_t n_win, uint32_t n_targets, c
 // IBD-state paths over win_log2[T][n_win][3] (ibdg_states.hip, ibdg_window_log2_states; the definition is in ibdg_states.h):
 // one workgroup of STATES_THREADS per comparison individual, grid-stride over the individuals under STATES_MAX_BLOCKS.
 // P: the penalties P_01, P_02, P_12 in quanta (states_penalties); path [T][n_win] (always: it holds `from` on the way); score
-// [T][n_win][3] or NULL; count [T][3].  n_win <= STATES_MAX_WIN.  One launch on `st`, no atomics.
-constexpr int STATES_THREADS = 256;
+// [T][n_win][3] or NULL; count [T][3].  n_win <= STATES_MAX_WIN.  One launch on `st`, no atomics.  Nothing is launched for no
+// windows or no individuals: that holds for all four launches here.
+constexpr int STATES_THREADS = 256;        // = STATES_BLOCKS of ibdg_states.h (asserted in ibdg_states.hip): a thread per block
 constexpr uint32_t STATES_MAX_BLOCKS = 1024;
 void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], uint8_t *path,
                         int64_t *score, uint64_t *count, hipStream_t st);

@@ -1,13 +1,14 @@
-// ibdg_states.h -- the integer log-domain IBD-state path: what its host twin (ibdg_states_host.cpp), its
-// kernel (ibdg_states.hip) and the entry points share.  No HIP type in here: the host twin needs no device.
+// ibdg_states.h -- the integer log-domain IBD-state path, its posteriors (4.9) and segments (4.10): the definition,
+// and every step of it as one inline function that the kernels' threads (ibdg_states.hip) and the host twin's loops
+// (ibdg_states_host.cpp) both call.  No HIP type in here: the host twin needs no device.
 //
 // Input l[w][0..2] = log2 LIBD0/1/2 of window w and the switch penalties p01, p02, p12.  In quanta of 2^-16 bit:
 //   emission   a NaN column, or a maximum that is not finite: e = (0, 0, 0) (the window says nothing).  Otherwise
 //              d_s = l_s - max(l) (one fp64 subtraction), clamped below at -2^24, e_s = (int64) rint(d_s * 65536), ties to
-//              even: the product is exact, so e_s is the same integer wherever it is formed
+//              even: the product is exact, so e_s is the same integer wherever it is formed (states_emission)
 //   penalties  P_xy = llrint(log2(p_xy) * 65536) by the host's libm, clamped below at -2^40; 0 on the diagonal
 //   recurrence score[0][s] = e_0[s], from[0][s] = s; score[i][s] = max_q(score[i-1][q] + pen[q][s]) + e_i[s], q = 0, 1, 2
-//              with strict >: the lowest state wins a tie (argmax3 of hgpath.c)
+//              with strict >: the lowest state wins a tie (argmax3 of hgpath.c; states_step)
 //   traceback  from argmax3(score[n-1]), as hg_solve
 // (max, +) over integers is exact and associative: the scores, hence the `from` entries, hence the path are the same
 // integers for any blocking of the windows.  n_win <= 2^21 keeps |score| < 2^62 (a step moves a score by at most 2^40
@@ -18,12 +19,94 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#if defined(__HIP__) || defined(__HIPCC__)
+#define IBDG_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define IBDG_HD inline
+#endif
+
 namespace ibdg {
 
 constexpr size_t STATES_MAX_WIN = (size_t)1 << 21;
 constexpr double STATES_QUANTA = 65536.0;               // per bit
 constexpr double STATES_D_MIN = -16777216.0;            // clamp of l_s - max(l), bits
 constexpr int64_t STATES_PEN_MIN = -((int64_t)1 << 40); // clamp of a penalty, quanta
+
+// the nearest integer, ties to even (the default rounding mode on the host; v_rndne_f64 and a conversion on the device)
+IBDG_HD int64_t states_rint(double x)
+{
+    return (int64_t)__builtin_llrint(x);
+}
+
+// e[0..2] of the window whose row is l[0..2]
+IBDG_HD void states_emission(const double *__restrict__ l, int64_t e[3])
+{
+    const double v[3] = {l[0], l[1], l[2]};
+    e[0] = e[1] = e[2] = 0;
+    if (v[0] != v[0] || v[1] != v[1] || v[2] != v[2])
+        return;
+    double m = v[0] > v[1] ? v[0] : v[1];
+    m = m > v[2] ? m : v[2];
+    if (!(m - m == 0.0))                       // +-inf
+        return;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        double d = v[s] - m;
+        d = d < STATES_D_MIN ? STATES_D_MIN : d;
+        e[s] = states_rint(d * STATES_QUANTA);
+    }
+}
+
+// v'[s] = max_q(v[q] + pen[q][s]) + e[s], lowest q on a tie; returns from[s] in bits 2 s, 2 s + 1
+IBDG_HD unsigned states_step(int64_t v[3], const int64_t pen[3][3], const int64_t e[3])
+{
+    int64_t nv[3];
+    unsigned f = 0;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        int64_t best = v[0] + pen[0][s];
+        unsigned m = 0;
+#pragma unroll
+        for (int q = 1; q < 3; ++q) {
+            const int64_t c = v[q] + pen[q][s];
+            const bool gt = c > best;
+            best = gt ? c : best;
+            m = gt ? q : m;
+        }
+        nv[s] = best + e[s];
+        f |= m << (2 * s);
+    }
+    v[0] = nv[0], v[1] = nv[1], v[2] = nv[2];
+    return f;
+}
+
+IBDG_HD int argmax3(const int64_t v[3])
+{
+    const int m = v[1] > v[0] ? 1 : 0;
+    return v[2] > v[m] ? 2 : m;
+}
+
+// a map of the three states as 6 bits (state s -> bits 2 s, 2 s + 1), the form of `from`; (a after b)(s) = a(b(s))
+constexpr unsigned MAP_ID = 0 | 1 << 2 | 2 << 4;
+IBDG_HD unsigned map_at(unsigned a, unsigned s)
+{
+    return a >> (2 * s) & 3;
+}
+IBDG_HD unsigned map_after(unsigned a, unsigned b)
+{
+    return map_at(a, map_at(b, 0)) | map_at(a, map_at(b, 1)) << 2 | map_at(a, map_at(b, 2)) << 4;
+}
+
+// The blocking of all four kernels and of the posteriors' order: STATES_BLOCKS blocks of C = ceil(n_win / STATES_BLOCKS)
+// windows, block b owns [begin(b), end(b)); the first nbk = ceil(n_win / C) own windows, a b >= nbk owns nothing (begin = end
+// = n_win).  n_win <= 2^21, so windows are uint32_t; index the tables with size_t.
+constexpr int STATES_BLOCKS = 256;
+struct Blocks {
+    uint32_t n_win, C, nbk;
+    IBDG_HD explicit Blocks(uint32_t n) : n_win(n), C((n + STATES_BLOCKS - 1) / STATES_BLOCKS), nbk(C ? (n + C - 1) / C : 0) {}
+    IBDG_HD uint32_t begin(uint32_t b) const { return b * C < n_win ? b * C : n_win; }
+    IBDG_HD uint32_t end(uint32_t b) const { return begin(b) + C < n_win ? begin(b) + C : n_win; }
+};
 
 // P[0..2] = P_01, P_02, P_12; 1 if a p is NaN or outside (0, 1] (bad: its index 0..2)
 int states_penalties(double p01, double p02, double p12, int64_t P[3], int *bad);
@@ -52,8 +135,9 @@ int log2_states_host(const double *tab, size_t n_win, double p01, double p02, do
 // unless an entry falls below 2^-1022 of the largest, where it is rounded like any subnormal (the 2^-1000 of the tests' bar).
 // The exponents of the backward vectors cancel in gamma and are not carried.
 //
-// Order (part of the definition: floating-point products are not associative).  C = ceil(n_win / 256), block b owns windows
-// [b C, (b + 1) C) (w0 .. w1 - 1), nbk = ceil(n_win / C) blocks own windows.
+// Order (part of the definition: floating-point products are not associative).  Blocks above: C = ceil(n_win / 256), block b owns
+// windows [b C, (b + 1) C) (w0 .. w1 - 1), nbk = ceil(n_win / C) blocks own windows.  Steps 1 .. 4 are post_block_matrix,
+// post_forward_walk, post_backward_walk and post_block_gamma below: the kernel calls them per thread, the twin in loops over b.
 //   1  block matrix   B_b = M_w0, then for w = w0 + 1 .. w1 - 1: M = post_step_matrix(b_w); each row r of B_b <- post_vec_mat(row,
 //                     M); post_rescale of the 9 entries.  M_0[q][s] = b_0[s] for every q (the uniform start): block 0's rows are
 //                     three copies of alpha at its end.  The first matrix of a block is not rescaled (its largest entry is 1).
@@ -70,13 +154,6 @@ int log2_states_host(const double *tab, size_t n_win, double p01, double p02, do
 //                     part[b + d] for b < d; expect = part[0].
 // log2_z = log2(D) + exponent: one libm log2 and one addition on the host, in the device route too.
 // Roundings on the way to one gamma, counted as hp_post_ref.R counts them: at most 14 per window.
-#if defined(__HIP__) || defined(__HIPCC__)
-#define IBDG_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define IBDG_HD inline
-#endif
-
-constexpr int POST_BLOCKS = 256;         // blocks of windows (the kernel's STATES_THREADS)
 constexpr int64_t POST_K_MIN = -1000;    // an emission weight below 2^-1000 is 0
 
 IBDG_HD double post_pow2(int k)          // 2^k, -1022 <= k <= 1023
@@ -94,7 +171,9 @@ IBDG_HD double post_weight(int64_t x, const double *T1, const double *T2)
     return m * post_pow2((int)k);
 }
 
-// v[0..N) * 2^e stays what it is; the largest entry comes to [1, 2).  Nothing happens if that entry is 0 or subnormal.
+// v[0..N) * 2^e stays what it is; the largest entry comes to [1, 2).  Nothing happens if that entry is 0 or subnormal (or in
+// [1, 2) already): the factor is then exactly 1, which leaves every double as it is.  A wave takes that road without a branch;
+// the host, which predicts the common case, leaves early (the same result, and 7 % of the twin's time).
 template <int N>
 IBDG_HD void post_rescale(double *v, int &e)
 {
@@ -103,13 +182,16 @@ IBDG_HD void post_rescale(double *v, int &e)
     for (int i = 1; i < N; ++i)
         mx = v[i] > mx ? v[i] : mx;
     const int E = (int)(__builtin_bit_cast(uint64_t, mx) >> 52 & 0x7ff) - 1023;
-    if (E == 0 || E < -1022 || E > 1022)
+    const bool keep = E == 0 || E < -1022 || E > 1022;
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (keep)
         return;
-    const double sc = post_pow2(-E);
+#endif
+    const double sc = keep ? 1.0 : post_pow2(-E);
 #pragma unroll
     for (int i = 0; i < N; ++i)
         v[i] *= sc;
-    e += E;
+    e += keep ? 0 : E;
 }
 
 // M[3 q + s] = a[q][s] * b[s]; a = {a01, a02, a12}
@@ -140,6 +222,138 @@ IBDG_HD void post_mat_vec(const double M[9], double v[3])
     v[0] = n[0], v[1] = n[1], v[2] = n[2];
 }
 
+// what steps 1, 3 and 4 read: the individual's table [n_win][3], the penalty weights, the tables T1, T2 = T + 256
+struct PostIn {
+    const double *__restrict__ tab;
+    const double *T;
+    double a[3];
+};
+
+// b_w[0..2] of window w
+IBDG_HD void post_emission_weights(const PostIn &in, uint32_t w, double b[3])
+{
+    int64_t e[3];
+    states_emission(in.tab + 3 * (size_t)w, e);
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+        b[s] = post_weight(e[s], in.T, in.T + 256);
+}
+
+// step 1 for the block of windows [w0, w1), w0 < w1: B[9] = B_b, *Bexp its exponent
+IBDG_HD void post_block_matrix(const PostIn &in, uint32_t w0, uint32_t w1, double *B, int *Bexp)
+{
+    double R[9], bw[3], M[9];
+    int e = 0;
+    post_emission_weights(in, w0, bw);
+    if (w0 == 0) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            R[3 * q] = bw[0], R[3 * q + 1] = bw[1], R[3 * q + 2] = bw[2];
+    } else {
+        post_step_matrix(in.a, bw, R);
+    }
+    for (uint32_t w = w0 + 1; w < w1; ++w) {
+        post_emission_weights(in, w, bw);
+        post_step_matrix(in.a, bw, M);
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            post_vec_mat(R + 3 * q, M);
+        post_rescale<9>(R, e);
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+        B[i] = R[i];
+    *Bexp = e;
+}
+
+// step 2 over mat [nbk][9], mexp [nbk] (step 1's): the forward walk leaves F_k in fin [nbk][3] and its exponent in fexp [nbk], k =
+// 1 .. nbk - 1 (entry 0 of both is not touched: block 0 starts from b_0); the backward walk leaves G_k in gout [nbk][3]
+IBDG_HD void post_forward_walk(const double *mat, const int *mexp, uint32_t nbk, double *fin, int *fexp)
+{
+    double v[3] = {mat[0], mat[1], mat[2]};
+    int e = mexp[0], me = nbk > 2 ? mexp[1] : 0;
+    for (uint32_t k = 1; k < nbk; ++k) {
+        fin[3 * k] = v[0], fin[3 * k + 1] = v[1], fin[3 * k + 2] = v[2];
+        fexp[k] = e;
+        if (k + 1 < nbk) {
+            // B_k first, and the exponent of B_{k+1} a step ahead: on the device one thread walks, and every read it has to
+            // wait for in the middle of a step is LDS latency times 255
+            double M[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i)
+                M[i] = mat[9 * k + i];
+            const int me_next = mexp[k + 1];
+            post_vec_mat(v, M);
+            e += me;
+            post_rescale<3>(v, e);
+            me = me_next;
+        }
+    }
+}
+
+IBDG_HD void post_backward_walk(const double *mat, uint32_t nbk, double *gout)
+{
+    double g[3] = {1.0, 1.0, 1.0};
+    int ge = 0;
+#pragma unroll 1                      // (one dependent chain: a second copy of the step gains nothing)
+    for (uint32_t k = nbk; k-- > 0;) {
+        gout[3 * k] = g[0], gout[3 * k + 1] = g[1], gout[3 * k + 2] = g[2];
+        if (k > 0) {
+            double M[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i)
+                M[i] = mat[9 * k + i];
+            post_mat_vec(M, g);
+            post_rescale<3>(g, ge);
+        }
+    }
+}
+
+// steps 3 and 4 for the block of windows [w0, w1), w0 < w1, from G = G_b, F = F_b and its exponent Fexp (not used by block 0):
+// post [n_win][3] holds beta_w of the block's windows from step 3 to step 4, which leaves gamma_w there; acc = the block's sum of
+// gamma in window order; *D, *Dexp: D and v's exponent at window w1 - 1 (Z, for the last block)
+IBDG_HD void post_block_gamma(const PostIn &in, uint32_t w0, uint32_t w1, const double *G, const double *F, int Fexp,
+                              double *__restrict__ post, double acc[3], double *D, int *Dexp)
+{
+    double bw[3], M[9];
+    // 3
+    double be[3] = {G[0], G[1], G[2]};
+    int ge = 0;
+    for (uint32_t w = w1; w-- > w0;) {
+        double *p = post + 3 * (size_t)w;
+        p[0] = be[0], p[1] = be[1], p[2] = be[2];
+        if (w > w0) {
+            post_emission_weights(in, w, bw);
+            post_step_matrix(in.a, bw, M);
+            post_mat_vec(M, be);
+            post_rescale<3>(be, ge);
+        }
+    }
+    // 4
+    double v[3] = {F[0], F[1], F[2]}, d = 0.0;
+    int e = Fexp;
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (uint32_t w = w0; w < w1; ++w) {
+        double *p = post + 3 * (size_t)w;
+        post_emission_weights(in, w, bw);
+        if (w == 0) {
+            v[0] = bw[0], v[1] = bw[1], v[2] = bw[2];
+            e = 0;
+        } else {
+            post_step_matrix(in.a, bw, M);
+            post_vec_mat(v, M);
+            post_rescale<3>(v, e);
+        }
+        const double p0 = v[0] * p[0], p1 = v[1] * p[1], p2 = v[2] * p[2];
+        d = (p0 + p1) + p2;
+        const double g0 = p0 / d, g1 = p1 / d, g2 = p2 / d;
+        p[0] = g0, p[1] = g1, p[2] = g2;
+        sum[0] += g0, sum[1] += g1, sum[2] += g2;
+    }
+    acc[0] = sum[0], acc[1] = sum[1], acc[2] = sum[2];
+    *D = d, *Dexp = e;
+}
+
 // the two tables, T1 = tab[0..256), T2 = tab[256..512) (made once, by libm's exp2)
 const double *post_tables();
 // a[0..2] = the weights of P_01, P_02, P_12 (states_penalties' integers)
@@ -157,17 +371,74 @@ int log2_posteriors_host(const double *tab, size_t n_win, double p01, double p02
 // path[w - 1]; segment k (0-based, in window order) runs from its start f to the window before the next start, or to n_win - 1.
 //   record   ibdg_segment (include/ibdgem_hip.h, 56 bytes): first = f, n_win = its windows, state = path[f], reserved = 0;
 //            e[s] = sum of e_w[s] over its windows (|e_w[s]| <= 2^40, n_win <= 2^21: |sum| <= 2^61; a window whose emission is
-//            (0, 0, 0) adds nothing); post_q = sum of q_w = llrint(gamma_w[state] * 2^32) (the product with a power of two is
-//            exact, ties to even: llrint in the default rounding mode here, __double2ll_rn on the device; q_w <= 2^32, the sum
-//            <= 2^53); post_min = min of gamma_w[state] (gamma is never NaN: no NaN rule).  post_q = 0 and post_min = 0.0 when the
+//            (0, 0, 0) adds nothing); post_q = sum of q_w = states_rint(gamma_w[state] * 2^32) (the product with a power of two is
+//            exact, ties to even; q_w <= 2^32, the sum <= 2^53); post_min = min of gamma_w[state] (gamma is never NaN: no NaN rule).  post_q = 0 and post_min = 0.0 when the
 //            posteriors are not asked for
 //   summary  uint64[12] per individual, for s = 0, 1, 2: [s] n_seg[s], [3 + s] longest_win[s] (the largest n_win of a segment
 //            in state s, 0 if none), [6 + s] bp[s] = sum over the state's segments of span = pos_last[last window] -
 //            pos_first[f] + 1 (modulo 2^64), [9 + s] longest_bp[s]; the two bp groups are 0 without positions
 // Every one of these is an integer +, a max or an fp64 min of values that are themselves the same bits on either side:
 // associative and exact, so the result does not depend on how the windows are cut into blocks.  That is why the twin walks
-// the windows once in order, the kernels cut them into 256 blocks, and neither needs an order rule as the posteriors do.
+// the windows once in order, the kernels cut them into 256 blocks, and neither needs an order rule as the posteriors do.  Both
+// add windows to a SegAcc and finished segments to the summary with the functions below.
 constexpr double SEG_POST_Q = 4294967296.0;      // 2^32: q_w = rint(gamma * 2^32)
+
+// what a run of windows in one state adds up to: a whole segment, or a piece of one that the kernel's blocks cut
+struct SegAcc {
+    int64_t e[3];
+    uint64_t q;
+    double mn;
+};
+
+IBDG_HD void seg_reset(SegAcc &a)
+{
+    a.e[0] = a.e[1] = a.e[2] = 0;
+    a.q = 0;
+    a.mn = __builtin_inf();
+}
+
+// a window in state s: l its row of the table, g its row of gamma or NULL
+IBDG_HD void seg_add_window(SegAcc &a, const double *__restrict__ l, const double *__restrict__ g, unsigned s)
+{
+    int64_t e[3];
+    states_emission(l, e);
+    a.e[0] += e[0], a.e[1] += e[1], a.e[2] += e[2];
+    if (g) {
+        a.q += (uint64_t)states_rint(g[s] * SEG_POST_Q);
+        a.mn = g[s] < a.mn ? g[s] : a.mn;
+    }
+}
+
+// another piece of the same segment
+IBDG_HD void seg_add_piece(SegAcc &a, const SegAcc &h)
+{
+    a.e[0] += h.e[0], a.e[1] += h.e[1], a.e[2] += h.e[2];
+    a.q += h.q;
+    a.mn = h.mn < a.mn ? h.mn : a.mn;
+}
+
+IBDG_HD void seg_record(ibdg_segment *r, uint32_t first, uint32_t n, unsigned state, const SegAcc &a, bool with_post)
+{
+    r->first = first, r->n_win = n, r->state = state, r->reserved = 0;
+    r->e[0] = a.e[0], r->e[1] = a.e[1], r->e[2] = a.e[2];
+    r->post_q = a.q;
+    r->post_min = with_post ? a.mn : 0.0;
+}
+
+// word i of the summary joins two partial results: groups 0 and 2 (n_seg, bp) add, groups 1 and 3 (the two longest) take the larger
+IBDG_HD uint64_t seg_summary_join(int i, uint64_t x, uint64_t y)
+{
+    return (i / 3 & 1) ? (y > x ? y : x) : x + y;
+}
+
+// a finished segment of len windows and span bp (0 without positions) in state s enters the summary v[12]
+IBDG_HD void seg_summary_add(uint64_t v[12], unsigned s, uint64_t len, uint64_t span)
+{
+    const uint64_t one[4] = {1, len, span, span};
+#pragma unroll
+    for (int i = 0; i < 12; ++i)
+        v[i] = s == (unsigned)(i % 3) ? seg_summary_join(i, v[i], one[i / 3]) : v[i];
+}
 
 // the host twin (ibdg_log2_segments_host): seg [seg_cap] or NULL, *n_seg the true count, summary[12]
 int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,

@@ -1,11 +1,11 @@
 // ibdg_states.hip -- IBD-state paths (ibdg_window_log2_states), posteriors (ibdg_window_log2_posteriors, k_log2_posteriors
 // below) and segments (ibdg_window_log2_segments, ibdg_get_log2_segments: k_log2_segments_count, k_log2_segments_write at
-// the end) over the log2 window table of the last run.  The paths: the integer
-// (max, +) recurrence of ibdg_states.h, whose host twin is ibdg_states_host.cpp.  Same integers by construction: the
-// emissions are exact products of an fp64 difference, everything behind them is int64 add / compare / select.
+// the end) over the log2 window table of the last run.  ibdg_states.h has the definition and every step of it as a function:
+// the kernels here are its parallel callers, the host twin (ibdg_states_host.cpp) the serial one, so both give the same bits.
+// Only here: how a workgroup cuts the windows among its threads and joins their results (scan_lds, join_threads).
 //
 // k_log2_states: a workgroup of STATES_THREADS per comparison individual, grid-stride over the individuals.  Thread b owns
-// windows [b C, (b + 1) C), C = ceil(n_win / STATES_THREADS).
+// windows [b C, (b + 1) C), C = ceil(n_win / STATES_THREADS) (Blocks).
 //   pass 1  the block's step matrices A_w[q][s] = pen[q][s] + e_w[s] multiplied (max, +) into one 3 x 3 matrix in LDS (block
 //           0 starts from three copies of the row e_0); thread 0 then walks the blocks' matrices in order and leaves every
 //           block the exact score vector at the end of the block before it
@@ -24,83 +24,67 @@ namespace ibdg {
 
 namespace {
 
+static_assert(STATES_THREADS == STATES_BLOCKS, "a thread per block of windows");
+
 struct Pen {
     int64_t p01, p02, p12;
 };
 
-__device__ __forceinline__ void emission(const double *__restrict__ l, int64_t e[3])
+// Scans one value per thread with op (associative) through the double-buffered LDS array buf, 8 steps of all threads: entry b
+// becomes op(b, b + 1, .., 255) (BACK) or op(0, .., b - 1, b).  Returns the buffer that holds the result, behind a barrier.
+template <bool BACK, typename T, typename Op>
+__device__ __forceinline__ int scan_lds(T (*buf)[STATES_THREADS], uint32_t b, T mine, Op op)
 {
-    const double l0 = l[0], l1 = l[1], l2 = l[2];
-    e[0] = e[1] = e[2] = 0;
-    if (l0 != l0 || l1 != l1 || l2 != l2)
-        return;
-    double m = l0 > l1 ? l0 : l1;
-    m = m > l2 ? m : l2;
-    if (!(m - m == 0.0))                       // +-inf
-        return;
-    const double v[3] = {l0, l1, l2};
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        double d = v[s] - m;
-        d = d < STATES_D_MIN ? STATES_D_MIN : d;
-        e[s] = __double2ll_rn(d * STATES_QUANTA);
+    buf[0][b] = mine;
+    __syncthreads();
+    int cur = 0;
+    for (uint32_t d = 1; d < STATES_THREADS; d <<= 1) {
+        T m = buf[cur][b];
+        if (BACK ? b + d < STATES_THREADS : b >= d)
+            m = BACK ? (T)op(m, buf[cur][b + d]) : (T)op(buf[cur][b - d], m);
+        buf[cur ^ 1][b] = m;
+        cur ^= 1;
+        __syncthreads();
     }
+    return cur;
 }
 
-// v'[s] = max_q(v[q] + pen[q][s]) + e[s], lowest q on a tie; returns from[s] in bits 2 s, 2 s + 1
-__device__ __forceinline__ unsigned step(int64_t v[3], const int64_t pen[3][3], const int64_t e[3])
+// v[0..N) joined over the workgroup's threads with op(i, x, y) (associative, commutative, 0 neutral): by shuffles within a wave,
+// then over the waves' results in red (LDS), behind a barrier.  Thread i < N returns word i's result.
+template <int N, typename T, typename Op>
+__device__ __forceinline__ T join_threads(T (&v)[N], T (*red)[N], uint32_t b, Op op)
 {
-    int64_t nv[3];
-    unsigned f = 0;
 #pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        int64_t best = v[0] + pen[0][s];
-        unsigned m = 0;
-#pragma unroll
-        for (int q = 1; q < 3; ++q) {
-            const int64_t c = v[q] + pen[q][s];
-            const bool gt = c > best;
-            best = gt ? c : best;
-            m = gt ? q : m;
-        }
-        nv[s] = best + e[s];
-        f |= m << (2 * s);
+    for (int i = 0; i < N; ++i) {
+        for (int d = 32; d > 0; d >>= 1)
+            v[i] = op(i, v[i], __shfl_down(v[i], d, 64));
+        if ((b & 63) == 0)
+            red[b >> 6][i] = v[i];
     }
-    v[0] = nv[0], v[1] = nv[1], v[2] = nv[2];
-    return f;
+    __syncthreads();
+    T r = 0;
+    if (b < N)
+        for (int k = 0; k < STATES_THREADS / 64; ++k)
+            r = op((int)b, r, red[k][b]);
+    return r;
 }
-
-__device__ __forceinline__ int argmax3(const int64_t v[3])
-{
-    int m = v[1] > v[0] ? 1 : 0;
-    return v[2] > v[m] ? 2 : m;
-}
-
-// a map of the three states as 6 bits (state s -> bits 2 s, 2 s + 1); (a after b)(s) = a(b(s))
-__device__ __forceinline__ unsigned map_at(unsigned a, unsigned s) { return a >> (2 * s) & 3; }
-__device__ __forceinline__ unsigned map_after(unsigned a, unsigned b)
-{
-    return map_at(a, map_at(b, 0)) | map_at(a, map_at(b, 1)) << 2 | map_at(a, map_at(b, 2)) << 4;
-}
-constexpr unsigned MAP_ID = 0 | 1 << 2 | 2 << 4;
 
 __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__restrict__ win_log2, uint32_t n_win,
                                                                 uint32_t n_targets, Pen P, uint8_t *__restrict__ path,
                                                                 int64_t *__restrict__ score, uint64_t *__restrict__ count)
 {
-    __shared__ int64_t mat[STATES_THREADS][9];      // 18 KB
+    __shared__ int64_t mat[STATES_THREADS][3][3];   // 18 KB
     __shared__ int64_t vin[STATES_THREADS][3];      // score vector at the end of the block before
     __shared__ uint8_t maps[2][STATES_THREADS];
     __shared__ uint32_t cnt[STATES_THREADS / 64][3];
     __shared__ int last_state;
 
     const int64_t pen[3][3] = {{0, P.p01, P.p02}, {P.p01, 0, P.p12}, {P.p02, P.p12, 0}};
+    const int64_t none[3] = {0, 0, 0};
     const uint32_t b = threadIdx.x;
-    const uint32_t C = (n_win + STATES_THREADS - 1) / STATES_THREADS;
-    const uint32_t nbk = (n_win + C - 1) / C;        // blocks that own windows (n_win >= 1)
-    const uint64_t w0 = (uint64_t)b * C;
-    const uint64_t w1 = w0 + C < n_win ? w0 + C : n_win;
-    const bool own = b < nbk;
+    const Blocks B(n_win);                           // (n_win >= 1)
+    const uint32_t w0 = B.begin(b), w1 = B.end(b);
+    const bool own = b < B.nbk;
 
     for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
         const double *tab = win_log2 + (size_t)t * n_win * 3;
@@ -110,42 +94,31 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__
         // pass 1
         if (own) {
             int64_t r[3][3], e[3];
-            emission(tab + 3 * w0, e);
+            states_emission(tab + 3 * (size_t)w0, e);
 #pragma unroll
             for (int q = 0; q < 3; ++q)
 #pragma unroll
                 for (int s = 0; s < 3; ++s)
                     r[q][s] = b == 0 ? e[s] : pen[q][s] + e[s];
-            for (uint64_t w = w0 + 1; w < w1; ++w) {
-                emission(tab + 3 * w, e);
+            for (uint32_t w = w0 + 1; w < w1; ++w) {
+                states_emission(tab + 3 * (size_t)w, e);
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
-                    (void)step(r[q], pen, e);
+                    (void)states_step(r[q], pen, e);
             }
 #pragma unroll
             for (int q = 0; q < 3; ++q)
 #pragma unroll
                 for (int s = 0; s < 3; ++s)
-                    mat[b][3 * q + s] = r[q][s];
+                    mat[b][q][s] = r[q][s];
         }
         __syncthreads();
         if (b == 0) {
-            // block 0's three rows are the score vector at its end
-            int64_t v[3] = {mat[0][0], mat[0][1], mat[0][2]};
-            for (uint32_t k = 1; k < nbk; ++k) {
+            // block 0's three rows are the score vector at its end; a block's matrix steps a vector like penalties without an emission
+            int64_t v[3] = {mat[0][0][0], mat[0][0][1], mat[0][0][2]};
+            for (uint32_t k = 1; k < B.nbk; ++k) {
                 vin[k][0] = v[0], vin[k][1] = v[1], vin[k][2] = v[2];
-                int64_t nv[3];
-#pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    int64_t best = v[0] + mat[k][s];
-#pragma unroll
-                    for (int q = 1; q < 3; ++q) {
-                        const int64_t c = v[q] + mat[k][3 * q + s];
-                        best = c > best ? c : best;
-                    }
-                    nv[s] = best;
-                }
-                v[0] = nv[0], v[1] = nv[1], v[2] = nv[2];
+                (void)states_step(v, mat[k], none);
             }
             last_state = argmax3(v);
         }
@@ -155,9 +128,9 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__
         unsigned back = MAP_ID;
         if (own) {
             int64_t v[3], e[3];
-            uint64_t w = w0;
+            uint32_t w = w0;
             if (b == 0) {
-                emission(tab, v);
+                states_emission(tab, v);
                 pt[0] = (uint8_t)MAP_ID;
                 if (sc)
                     sc[0] = v[0], sc[1] = v[1], sc[2] = v[2];
@@ -166,52 +139,31 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__
                 v[0] = vin[b][0], v[1] = vin[b][1], v[2] = vin[b][2];
             }
             for (; w < w1; ++w) {
-                emission(tab + 3 * w, e);
-                const unsigned f = step(v, pen, e);
+                states_emission(tab + 3 * (size_t)w, e);
+                const unsigned f = states_step(v, pen, e);
                 pt[w] = (uint8_t)f;
                 if (sc)
-                    sc[3 * w] = v[0], sc[3 * w + 1] = v[1], sc[3 * w + 2] = v[2];
+                    sc[3 * (size_t)w] = v[0], sc[3 * (size_t)w + 1] = v[1], sc[3 * (size_t)w + 2] = v[2];
                 back = map_after(back, f);         // state at w -> state at w0 - 1 (block 0: at window 0)
             }
         }
-        maps[0][b] = (uint8_t)back;
-        __syncthreads();
-
         // pass 3: maps[..][k] becomes block k's map after block k + 1's after ... after the last block's
-        int cur = 0;
-        for (uint32_t d = 1; d < STATES_THREADS; d <<= 1) {
-            unsigned m = maps[cur][b];
-            if (b + d < STATES_THREADS)
-                m = map_after(m, maps[cur][b + d]);
-            maps[cur ^ 1][b] = (uint8_t)m;
-            cur ^= 1;
-            __syncthreads();
-        }
+        const int cur = scan_lds<true>(maps, b, (uint8_t)back, [](unsigned x, unsigned y) { return map_after(x, y); });
         uint32_t n[3] = {0, 0, 0};
         if (own) {
             // the state at this block's last window: the last block's is the best final score's, any other's is what the
             // blocks behind it map that one to
-            unsigned st = b + 1 == nbk ? (unsigned)last_state : map_at(maps[cur][b + 1], (unsigned)last_state);
-            for (uint64_t w = w1; w-- > w0;) {
+            unsigned st = b + 1 == B.nbk ? (unsigned)last_state : map_at(maps[cur][b + 1], (unsigned)last_state);
+            for (uint32_t w = w1; w-- > w0;) {
                 const unsigned f = pt[w];
                 pt[w] = (uint8_t)st;
                 n[0] += st == 0, n[1] += st == 1, n[2] += st == 2;
                 st = map_at(f, st);
             }
         }
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-            for (int d = 32; d > 0; d >>= 1)
-                n[s] += __shfl_down(n[s], d, 64);
-        if ((b & 63) == 0)
-            cnt[b >> 6][0] = n[0], cnt[b >> 6][1] = n[1], cnt[b >> 6][2] = n[2];
-        __syncthreads();
-        if (b < 3) {
-            uint64_t sum = 0;
-            for (int k = 0; k < STATES_THREADS / 64; ++k)
-                sum += cnt[k][b];
+        const uint32_t sum = join_threads(n, cnt, b, [](int, uint32_t x, uint32_t y) { return x + y; });
+        if (b < 3)
             count[(size_t)t * 3 + b] = sum;
-        }
         __syncthreads();       // (LDS is reused by the next individual)
     }
 }
@@ -220,20 +172,11 @@ struct PenW {
     double a[3];      // the weights of P_01, P_02, P_12 (post_penalty_weights)
 };
 
-__device__ __forceinline__ void emission_weights(const double *__restrict__ l, const double *T, double b[3])
-{
-    int64_t e[3];
-    emission(l, e);
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-        b[s] = post_weight(e[s], T, T + 256);
-}
-
-// k_log2_posteriors: the sum-product pass of ibdg_states.h (its steps 1 .. 5 are the numbers below), same launch and blocking
-// as k_log2_states.  scr [T][n_win][3] holds beta_w from step 3 to step 4, which overwrites it with gamma_w: the thread
-// that wrote a row is the one that reads it.  out [T][5] = expect[3], Z's mantissa, Z's exponent (as a double).  The walks of
-// step 2 run in two waves side by side (thread 0 forward, thread 64 backward).  No atomics; the same reads as k_log2_states,
-// three times.
+// k_log2_posteriors: the sum-product pass of ibdg_states.h (steps 1 .. 4 are its functions, called per thread with pointers into
+// LDS; step 5 is the tree below), same launch and blocking as k_log2_states.  scr [T][n_win][3] holds beta_w from step 3 to step
+// 4, which overwrites it with gamma_w: the thread that wrote a row is the one that reads it.  out [T][5] = expect[3], Z's
+// mantissa, Z's exponent (as a double).  The walks of step 2 run in two waves side by side (thread 0 forward, thread 64
+// backward).  No atomics; the same reads as k_log2_states, three times.
 __global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double *__restrict__ win_log2, uint32_t n_win,
                                                                     uint32_t n_targets, PenW W, const double *__restrict__ tables,
                                                                     double *__restrict__ scr, double *__restrict__ out)
@@ -246,115 +189,32 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double
     __shared__ int mexp[STATES_THREADS], fexp[STATES_THREADS];
 
     const uint32_t b = threadIdx.x;
-    const uint32_t C = (n_win + STATES_THREADS - 1) / STATES_THREADS;
-    const uint32_t nbk = (n_win + C - 1) / C;
-    const uint64_t w0 = (uint64_t)b * C;
-    const uint64_t w1 = w0 + C < n_win ? w0 + C : n_win;
-    const bool own = b < nbk;
-    const double a[3] = {W.a[0], W.a[1], W.a[2]};
+    const Blocks B(n_win);
+    const uint32_t w0 = B.begin(b), w1 = B.end(b);
+    const bool own = b < B.nbk;
 
     T[b] = tables[b], T[b + STATES_THREADS] = tables[b + STATES_THREADS];
     __syncthreads();
 
     for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
-        const double *tab = win_log2 + (size_t)t * n_win * 3;
-        double *sc = scr + (size_t)t * n_win * 3;
-
+        const PostIn in = {win_log2 + (size_t)t * n_win * 3, T, {W.a[0], W.a[1], W.a[2]}};
         // 1
-        if (own) {
-            double R[9], bw[3], M[9];
-            int e = 0;
-            emission_weights(tab + 3 * w0, T, bw);
-            if (b == 0) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q)
-                    R[3 * q] = bw[0], R[3 * q + 1] = bw[1], R[3 * q + 2] = bw[2];
-            } else {
-                post_step_matrix(a, bw, R);
-            }
-            for (uint64_t w = w0 + 1; w < w1; ++w) {
-                emission_weights(tab + 3 * w, T, bw);
-                post_step_matrix(a, bw, M);
-#pragma unroll
-                for (int q = 0; q < 3; ++q)
-                    post_vec_mat(R + 3 * q, M);
-                post_rescale<9>(R, e);
-            }
-#pragma unroll
-            for (int i = 0; i < 9; ++i)
-                mat[b][i] = R[i];
-            mexp[b] = e;
-        }
+        if (own)
+            post_block_matrix(in, w0, w1, mat[b], &mexp[b]);
         __syncthreads();
         // 2
-        if (b == 0) {
-            double v[3] = {mat[0][0], mat[0][1], mat[0][2]};
-            int e = mexp[0];
-            for (uint32_t k = 1; k < nbk; ++k) {
-                fin[k][0] = v[0], fin[k][1] = v[1], fin[k][2] = v[2];
-                fexp[k] = e;
-                if (k + 1 < nbk) {
-                    double M[9];
-#pragma unroll
-                    for (int i = 0; i < 9; ++i)
-                        M[i] = mat[k][i];
-                    post_vec_mat(v, M);
-                    e += mexp[k];
-                    post_rescale<3>(v, e);
-                }
-            }
-        } else if (b == 64) {
-            double g[3] = {1.0, 1.0, 1.0};
-            int ge = 0;
-            for (uint32_t k = nbk; k-- > 0;) {
-                gout[k][0] = g[0], gout[k][1] = g[1], gout[k][2] = g[2];
-                if (k > 0) {
-                    double M[9];
-#pragma unroll
-                    for (int i = 0; i < 9; ++i)
-                        M[i] = mat[k][i];
-                    post_mat_vec(M, g);
-                    post_rescale<3>(g, ge);
-                }
-            }
-        }
+        if (b == 0)
+            post_forward_walk(mat[0], mexp, B.nbk, fin[0], fexp);
+        else if (b == 64)
+            post_backward_walk(mat[0], B.nbk, gout[0]);
         __syncthreads();
-        double acc[3] = {0.0, 0.0, 0.0};
+        // 3, 4
+        double acc[3] = {0.0, 0.0, 0.0}, D;
+        int e;
         if (own) {
-            double bw[3], M[9];
-            // 3
-            double be[3] = {gout[b][0], gout[b][1], gout[b][2]};
-            int ge = 0;
-            for (uint64_t w = w1; w-- > w0;) {
-                sc[3 * w] = be[0], sc[3 * w + 1] = be[1], sc[3 * w + 2] = be[2];
-                if (w > w0) {
-                    emission_weights(tab + 3 * w, T, bw);
-                    post_step_matrix(a, bw, M);
-                    post_mat_vec(M, be);
-                    post_rescale<3>(be, ge);
-                }
-            }
-            // 4
-            double v[3] = {fin[b][0], fin[b][1], fin[b][2]};
-            int e = fexp[b];
-            for (uint64_t w = w0; w < w1; ++w) {
-                emission_weights(tab + 3 * w, T, bw);
-                if (w == 0) {
-                    v[0] = bw[0], v[1] = bw[1], v[2] = bw[2];
-                    e = 0;
-                } else {
-                    post_step_matrix(a, bw, M);
-                    post_vec_mat(v, M);
-                    post_rescale<3>(v, e);
-                }
-                const double p0 = v[0] * sc[3 * w], p1 = v[1] * sc[3 * w + 1], p2 = v[2] * sc[3 * w + 2];
-                const double D = (p0 + p1) + p2;
-                const double g0 = p0 / D, g1 = p1 / D, g2 = p2 / D;
-                sc[3 * w] = g0, sc[3 * w + 1] = g1, sc[3 * w + 2] = g2;
-                acc[0] += g0, acc[1] += g1, acc[2] += g2;
-                if (w + 1 == n_win)
-                    out[(size_t)t * 5 + 3] = D, out[(size_t)t * 5 + 4] = (double)e;
-            }
+            post_block_gamma(in, w0, w1, gout[b], fin[b], fexp[b], scr + (size_t)t * n_win * 3, acc, &D, &e);
+            if (w1 == n_win)
+                out[(size_t)t * 5 + 3] = D, out[(size_t)t * 5 + 4] = (double)e;
         }
         // 5
         part[b][0] = acc[0], part[b][1] = acc[1], part[b][2] = acc[2];
@@ -379,7 +239,7 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double
 // k_log2_segments_count: out [T][13] = the summary's 12 words, then the individual's number of segments.  path as
 // k_log2_states left it.  Every thread finds the first start among its windows; a suffix minimum over the 256 blocks in LDS gives
 // each the next start behind its block (n_win if none), so a backward walk over its own windows knows where every segment
-// that starts there ends.  Sums and maxima by shuffles, then over the four waves in LDS.  No atomics.
+// that starts there ends.  Sums and maxima over the threads by join_threads.  No atomics.
 __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_count(const uint8_t *__restrict__ path, uint32_t n_win,
                                                                         uint32_t n_targets, const uint64_t *__restrict__ pos_first,
                                                                         const uint64_t *__restrict__ pos_last,
@@ -389,11 +249,9 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_count(const ui
     __shared__ uint64_t red[STATES_THREADS / 64][12];
 
     const uint32_t b = threadIdx.x;
-    const uint32_t C = (n_win + STATES_THREADS - 1) / STATES_THREADS;
-    const uint32_t nbk = (n_win + C - 1) / C;
-    const uint32_t w0 = b * C < n_win ? b * C : n_win;
-    const uint32_t w1 = w0 + C < n_win ? w0 + C : n_win;
-    const bool own = b < nbk;
+    const Blocks B(n_win);
+    const uint32_t w0 = B.begin(b), w1 = B.end(b);
+    const bool own = b < B.nbk;
 
     for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
         const uint8_t *pt = path + (size_t)t * n_win;
@@ -409,20 +267,8 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_count(const ui
                 prev = s;
             }
         }
-        nxt[0][b] = fs;
-        __syncthreads();
         // nxt[..][k] becomes the first start in block k or behind it
-        int cur = 0;
-        for (uint32_t d = 1; d < STATES_THREADS; d <<= 1) {
-            uint32_t m = nxt[cur][b];
-            if (b + d < STATES_THREADS) {
-                const uint32_t o = nxt[cur][b + d];
-                m = o < m ? o : m;
-            }
-            nxt[cur ^ 1][b] = m;
-            cur ^= 1;
-            __syncthreads();
-        }
+        const int cur = scan_lds<true>(nxt, b, fs, [](uint32_t x, uint32_t y) { return y < x ? y : x; });
         uint64_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         if (own) {
             uint32_t end = b + 1 < STATES_THREADS ? nxt[cur][b + 1] : n_win;     // where the segment at hand ends (exclusive)
@@ -430,66 +276,20 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_count(const ui
             for (uint32_t w = w1; w-- > w0;) {
                 const unsigned p = w == 0 ? 3u : pt[w - 1];
                 if (p != s) {
-                    const uint64_t len = end - w;
-                    const uint64_t span = pos_first ? pos_last[end - 1] - pos_first[w] + 1 : 0;
-#pragma unroll
-                    for (unsigned k = 0; k < 3; ++k) {
-                        const bool is = s == k;
-                        v[k] += is;
-                        v[3 + k] = is && len > v[3 + k] ? len : v[3 + k];
-                        v[6 + k] += is ? span : 0;
-                        v[9 + k] = is && span > v[9 + k] ? span : v[9 + k];
-                    }
+                    seg_summary_add(v, s, end - w, pos_first ? pos_last[end - 1] - pos_first[w] + 1 : 0);
                     end = w;
                 }
                 s = p;
             }
         }
-#pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            for (int d = 32; d > 0; d >>= 1) {
-                const uint64_t o = __shfl_down((unsigned long long)v[i], d, 64);
-                v[i] = (i / 3 & 1) ? (o > v[i] ? o : v[i]) : v[i] + o;
-            }
-            if ((b & 63) == 0)
-                red[b >> 6][i] = v[i];
-        }
-        __syncthreads();
-        if (b < 13) {
-            uint64_t r = 0;
-            if (b < 12) {
-                for (int k = 0; k < STATES_THREADS / 64; ++k)
-                    r = (b / 3 & 1) ? (red[k][b] > r ? red[k][b] : r) : r + red[k][b];
-            } else {
-                for (int k = 0; k < STATES_THREADS / 64; ++k)
-                    r += red[k][0] + red[k][1] + red[k][2];
-            }
+        uint64_t r = join_threads(v, red, b, [](int i, uint64_t x, uint64_t y) { return seg_summary_join(i, x, y); });
+        if (b == 12)
+            for (int k = 0; k < STATES_THREADS / 64; ++k)
+                r += red[k][0] + red[k][1] + red[k][2];
+        if (b < 13)
             out[(size_t)t * 13 + b] = r;
-        }
         __syncthreads();       // (LDS is reused by the next individual)
     }
-}
-
-struct SegAcc {
-    int64_t e[3];
-    uint64_t q;
-    double mn;
-};
-
-__device__ __forceinline__ void seg_reset(SegAcc &a)
-{
-    a.e[0] = a.e[1] = a.e[2] = 0;
-    a.q = 0;
-    a.mn = __builtin_inf();
-}
-
-__device__ __forceinline__ void seg_record(ibdg_segment *__restrict__ r, uint32_t first, uint32_t n, unsigned state, const SegAcc &a,
-                                           bool with_post)
-{
-    r->first = first, r->n_win = n, r->state = state, r->reserved = 0;
-    r->e[0] = a.e[0], r->e[1] = a.e[1], r->e[2] = a.e[2];
-    r->post_q = a.q;
-    r->post_min = with_post ? a.mn : 0.0;
 }
 
 // k_log2_segments_write: the records, individual t's from seg[off[t]] on in window order (off: the exclusive sums of the counts
@@ -506,18 +306,14 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_write(const do
                                                                         uint32_t n_targets, const uint64_t *__restrict__ off,
                                                                         ibdg_segment *__restrict__ seg)
 {
-    __shared__ int64_t hd_e[STATES_THREADS][3];
-    __shared__ uint64_t hd_q[STATES_THREADS];
-    __shared__ double hd_mn[STATES_THREADS];
+    __shared__ SegAcc hd[STATES_THREADS];               // the blocks' heads
     __shared__ uint32_t fst[STATES_THREADS];            // the block's first start, n_win if it has none
     __shared__ uint32_t cnt[2][STATES_THREADS];
 
     const uint32_t b = threadIdx.x;
-    const uint32_t C = (n_win + STATES_THREADS - 1) / STATES_THREADS;
-    const uint32_t nbk = (n_win + C - 1) / C;
-    const uint32_t w0 = b * C < n_win ? b * C : n_win;
-    const uint32_t w1 = w0 + C < n_win ? w0 + C : n_win;
-    const bool own = b < nbk;
+    const Blocks B(n_win);
+    const uint32_t w0 = B.begin(b), w1 = B.end(b);
+    const bool own = b < B.nbk;
     const bool with_post = post != nullptr;
     constexpr uint32_t NONE = 0xffffffffu;
 
@@ -540,62 +336,36 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_write(const do
                 prev = s;
             }
         }
-        cnt[0][b] = ns;
         fst[b] = fs;
-        __syncthreads();
-        int cur = 0;
-        for (uint32_t d = 1; d < STATES_THREADS; d <<= 1) {
-            uint32_t m = cnt[cur][b];
-            if (b >= d)
-                m += cnt[cur][b - d];
-            cnt[cur ^ 1][b] = m;
-            cur ^= 1;
-            __syncthreads();
-        }
+        const int cur = scan_lds<false>(cnt, b, ns, [](uint32_t x, uint32_t y) { return x + y; });
         uint32_t k = cnt[cur][b] - ns;                  // the block's first record
         SegAcc a;
         seg_reset(a);
         uint32_t start = NONE;
         unsigned state = 0;
-        bool head_out = false;
         if (own) {
             unsigned prev = before;
             for (uint32_t w = w0; w < w1; ++w) {
                 const unsigned s = pt[w];
                 if (s != prev) {
-                    if (start == NONE) {
-                        hd_e[b][0] = a.e[0], hd_e[b][1] = a.e[1], hd_e[b][2] = a.e[2];
-                        hd_q[b] = a.q, hd_mn[b] = a.mn;
-                        head_out = true;
-                    } else {
-                        seg_record(out + k, start, w - start, state, a, with_post);
-                        ++k;
-                    }
+                    if (start == NONE)
+                        hd[b] = a;
+                    else
+                        seg_record(out + k++, start, w - start, state, a, with_post);
                     seg_reset(a);
                     start = w, state = s;
                 }
                 prev = s;
-                int64_t e[3];
-                emission(tab + 3 * (size_t)w, e);
-                a.e[0] += e[0], a.e[1] += e[1], a.e[2] += e[2];
-                if (with_post) {
-                    const double g = po[3 * (size_t)w + s];
-                    a.q += (uint64_t)__double2ll_rn(g * SEG_POST_Q);
-                    a.mn = g < a.mn ? g : a.mn;
-                }
+                seg_add_window(a, tab + 3 * (size_t)w, with_post ? po + 3 * (size_t)w : nullptr, s);
             }
         }
-        if (!head_out) {                                // no start: all of the block (nothing, for a block without windows)
-            hd_e[b][0] = a.e[0], hd_e[b][1] = a.e[1], hd_e[b][2] = a.e[2];
-            hd_q[b] = a.q, hd_mn[b] = a.mn;
-        }
+        if (start == NONE)                              // no start: all of the block (nothing, for a block without windows)
+            hd[b] = a;
         __syncthreads();
         if (start != NONE) {
             uint32_t end = n_win;
-            for (uint32_t j = b + 1; j < nbk; ++j) {
-                a.e[0] += hd_e[j][0], a.e[1] += hd_e[j][1], a.e[2] += hd_e[j][2];
-                a.q += hd_q[j];
-                a.mn = hd_mn[j] < a.mn ? hd_mn[j] : a.mn;
+            for (uint32_t j = b + 1; j < B.nbk; ++j) {
+                seg_add_piece(a, hd[j]);
                 if (fst[j] != n_win) {
                     end = fst[j];
                     break;
@@ -607,45 +377,41 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_write(const do
     }
 }
 
+// the one launch of all four: nothing for no windows or no individuals, else a workgroup per individual under STATES_MAX_BLOCKS
+template <typename K, typename... A>
+void launch_per_individual(K kernel, uint32_t n_win, uint32_t n_targets, hipStream_t st, A... args)
+{
+    if (n_win == 0 || n_targets == 0)
+        return;
+    const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(STATES_THREADS), 0, st, args...);
+}
+
 }  // namespace
 
 void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], uint8_t *path,
                         int64_t *score, uint64_t *count, hipStream_t st)
 {
-    if (n_win == 0 || n_targets == 0)
-        return;
-    const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_log2_states, dim3(grid), dim3(STATES_THREADS), 0, st, win_log2, n_win, n_targets, Pen{P[0], P[1], P[2]},
-                       path, score, count);
+    launch_per_individual(k_log2_states, n_win, n_targets, st, win_log2, n_win, n_targets, Pen{P[0], P[1], P[2]}, path, score, count);
 }
 
 void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_targets, const double a[3], const double *tables,
                             double *scr, double *out, hipStream_t st)
 {
-    if (n_win == 0 || n_targets == 0)
-        return;
-    const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_log2_posteriors, dim3(grid), dim3(STATES_THREADS), 0, st, win_log2, n_win, n_targets, PenW{{a[0], a[1], a[2]}},
-                       tables, scr, out);
+    launch_per_individual(k_log2_posteriors, n_win, n_targets, st, win_log2, n_win, n_targets, PenW{{a[0], a[1], a[2]}}, tables, scr,
+                          out);
 }
 
 void launch_log2_segments_count(const uint8_t *path, uint32_t n_win, uint32_t n_targets, const uint64_t *pos_first,
                                 const uint64_t *pos_last, uint64_t *out, hipStream_t st)
 {
-    if (n_win == 0 || n_targets == 0)
-        return;
-    const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_log2_segments_count, dim3(grid), dim3(STATES_THREADS), 0, st, path, n_win, n_targets, pos_first, pos_last, out);
+    launch_per_individual(k_log2_segments_count, n_win, n_targets, st, path, n_win, n_targets, pos_first, pos_last, out);
 }
 
 void launch_log2_segments_write(const double *win_log2, const uint8_t *path, const double *post, uint32_t n_win, uint32_t n_targets,
                                 const uint64_t *off, ibdg_segment *seg, hipStream_t st)
 {
-    if (n_win == 0 || n_targets == 0)
-        return;
-    const uint32_t grid = n_targets < STATES_MAX_BLOCKS ? n_targets : STATES_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_log2_segments_write, dim3(grid), dim3(STATES_THREADS), 0, st, win_log2, path, post, n_win, n_targets, off,
-                       seg);
+    launch_per_individual(k_log2_segments_write, n_win, n_targets, st, win_log2, path, post, n_win, n_targets, off, seg);
 }
 
 }  // namespace ibdg
