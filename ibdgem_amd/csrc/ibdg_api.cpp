@@ -1560,6 +1560,7 @@ struct RunPlan {
     size_t T = 0, lanes = 0;
     bool ld = false, use_pop = false;   // --LD; through the exponent-counting kernels (else the strict ones)
     int variant = 0, count_unit = 0;    // what ibdg_last_ld_variant / ibdg_last_count_unit report
+    int window_end = 0;                 // ... and ibdg_last_window_end
     bool recount = false, rows_on_main = false, dispatch_events = false, rt_build = false;
     // the individuals: [0, T_g) in n_gg groups of IBDG_TG through k_ld_mfma (gg_batch groups per launch), the T_cnt of
     // [T_g, T) through the counting kernels: n_grp groups of MT in k_ld_popcount_mt, then T_one one per workgroup
@@ -1569,6 +1570,7 @@ struct RunPlan {
     int mx_counts = 0;
     long rho_shift = 0;
     bool ibd1 = false, ibd0_pass = false, fin_in_next = false, end_in_dispatch = false;
+    bool pair_sums = false;             // the IBD1 form's paired window end (two windows per sum tree, LDS scratch)
     bool side_fast = false;             // stream2's kernels in their fast forms (beside k_ld_mfma)
     unsigned row_blocks = 0;            // workgroups of stream2's k_rows_windows (0: its full grid)
 };
@@ -1643,12 +1645,24 @@ int plan_run(ibdg_ctx *c, size_t T, size_t lanes, int ld_mode, bool row_table, R
             P.ibd1 = !p2_stale || (P.n_gg > 0) || c->ibd0.ibd0_runs >= (uint64_t)c->opt.ibd0_after;
         }
         P.ibd0_pass = p2_stale && (P.n_gg > 0 || P.ibd1);
+        // ... two windows per sum tree (option "pair_sums") where the 1 KiB of scratch per wave this takes leaves as many
+        // workgroups on a CU as the form has without it: 160 KiB over the workgroup's LDS, rounded down, and no more than the
+        // four workgroups of eight waves that the CU's wave slots hold at the kernel's 8 waves per SIMD (the LDS is sized for
+        // eight waves whatever the panel)
+        if (P.ibd1 && c->opt.pair_sums) {
+            const auto per_cu = [&](int form) {
+                return std::min<size_t>(4, (size_t)160 * 1024 / ibdg::ld_popcount_lds_bytes(c->lay.max_seg, c->lay.wpg, c->lay.ct_max + 1,
+                                                                                           c->lay.tab_in_lds, c->lay.seg_ring, form));
+            };
+            P.pair_sums = per_cu(4) == per_cu(3);
+        }
         P.fin_in_next = c->opt.fin_next && c->opt.async && P.T_one > 0 && P.T_one == P.T_cnt && P.n_gg == 0;
         // (option "end_in_dispatch": the run's end event is the --LD kernel's own completion signal -- no event packet
         // of its own behind the kernel -- where that kernel is the run's last launch on the main stream)
         // (not with "log_windows": the run's end is then an event behind everything its main stream holds, see ibdg_ctx::WinLog)
         P.end_in_dispatch = c->opt.end_in_dispatch && P.fin_in_next && !P.dispatch_events && P.T_one == T && !c->opt.log_windows;
         P.count_unit = P.T_one ? (P.mx_counts ? (P.ibd1 ? 3 : 2) : 1) : 0;
+        P.window_end = P.T_one ? (P.pair_sums ? 2 : 1) : 0;
         // k_ld_mfma (4 waves per SIMD) leaves wave slots to the second stream: its kernels run in their fast forms
         // (also with a few individuals left to the counting kernels: T = 16 5.5 ms against 6.0; beside
         // k_ld_popcount_mt alone it makes no difference)
@@ -1825,6 +1839,7 @@ int launch_singles(ibdg_ctx *c, const RunPlan &P, ibdg::PopArgs pa, ibdg::Kernel
     Ring &R = c->ring;
     pa.t_base = (uint32_t)(P.T_g + P.n_grp * P.MT);
     pa.ibd1 = P.ibd1 ? 1u : 0u;
+    pa.pair_sums = P.pair_sums ? 1u : 0u;
     // (skipped when the previous run made the very same images: same prepared sites, same comparison individuals --
     // a caller that runs a comparison again, e.g. timed steps: one launch of ~10 us less per run, which on an
     // eighth of a chromosome is a tenth of the step)
@@ -2104,6 +2119,7 @@ int ibdg_run(ibdg_ctx *c, const uint32_t *targets, size_t T, const uint8_t *bg_c
         return fail(c, "[::] ERROR in ibdg_run: log_windows cannot give the --LD columns here: %s", ld_log_refused(c));
     c->last_variant = P.variant;
     c->last_count_unit = P.count_unit;
+    c->last_window_end = P.window_end;
     // A finalising step left by the run before rides in this run's k_ld_popcount launch only where this run is of the same
     // shape over the same background and prepared sites (it reads the windows' constants and its own run's background sizes)
     // and no IBD0 pass rewrites its sums first; the strict and non-LD kernels write the same win_ll entries themselves, and
@@ -2578,6 +2594,7 @@ int ibdg_last_run_ms(ibdg_ctx *c, float out[5])
 int ibdg_last_ld_variant(const ibdg_ctx *c) { return c ? c->last_variant : 0; }
 
 int ibdg_last_count_unit(const ibdg_ctx *c) { return c ? c->last_count_unit : 0; }
+int ibdg_last_window_end(const ibdg_ctx *c) { return c ? c->last_window_end : 0; }
 
 int ibdg_ld_layout(const ibdg_ctx *c)
 {

@@ -93,6 +93,7 @@ struct ibdg_ctx {
         long end_in_dispatch = 1;    // the end event of a run of single individuals rides in its --LD kernel's dispatch packet (0: an event packet behind it): -7 us of a 91 us step on an eighth of a chromosome, profiles/r05_shard_steps.txt
         long fin_next = 1;           // queued runs of single individuals: a run's finalising step rides in the next run's --LD launch
         long sum_dpp = 1;            // ... its wave sums by DPP moves (0: ds_swizzle, as the vector-ALU form)
+        long pair_sums = 1;          // the IBD1 form sums two consecutive windows of a run in one tree through LDS scratch, where the scratch costs no workgroup per CU (0: every window by DPP moves alone)
         long mx_counts = 1;          // k_ld_popcount: the counts of a haplotype word by one matrix instruction (0: 12 (mask, count) pairs)
         long reserve_compact = 1;    // their buffer is allocated with the panel's (a panel's worth x 1.3 of HBM more per context)
         long compact_align = 1;      // rows a window of the compacted tiles is rounded up to: 1 = the rows back to back (no padding; a
@@ -405,6 +406,7 @@ struct ibdg_ctx {
 
     int last_variant = 0;
     int last_count_unit = 0;           // 2: the last --LD run's single-individual launches counted on the matrix cores, 1: by (mask, count) pairs, 0: no such launch
+    int last_window_end = 0;           // ... and their window ends: 2: two consecutive windows per sum tree (the IBD1 form's paired end), 1: every window summed on its own, 0: no such launch
     // the comparison individuals of the previous ibdg_run whose device copies are still valid
     std::vector<uint32_t> prev_targets;
     // New comparison individuals reach the device without a host wait (the reference's loop hands every individual of the panel
@@ -501,6 +503,7 @@ const OptionRow OPTION_TABLE[] = {
     {"finalize_in_next", &Opt::fin_next, OptionRow::RANGE, 0, 1, "0 or 1", OptionRow::JOIN_STREAMS},
     {"sum_dpp", &Opt::sum_dpp, OptionRow::RANGE, 0, 1, "0 or 1"},
     {"mx_counts", &Opt::mx_counts, OptionRow::RANGE, 0, 1, "0 or 1"},
+    {"pair_sums", &Opt::pair_sums, OptionRow::RANGE, 0, 1, "0 or 1"},
     {"reserve_compact", &Opt::reserve_compact, OptionRow::RANGE, 0, 1, "0 or 1"},
     {"compact_density", &Opt::compact_density, OptionRow::RANGE, 1, 1000000},
     {"compact_targets", &Opt::compact_targets, OptionRow::RANGE, 1, 65536},

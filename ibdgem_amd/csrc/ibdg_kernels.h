@@ -138,6 +138,7 @@ struct PopArgs {
     // (k_ld_popcount<.., IBD1 = true>): its matrix instructions return the table exponents of the four IBD1 products
     // themselves, and the finalising step takes IBD0 from the pass (ibd0_from_pass in ibdg_ld_dev.h).
     uint32_t ibd1 = 0;          // 1: images (k_win_target_mx) and kernel of that form; needs mx_counts and tab_in_lds
+    uint32_t pair_sums = 0;     // ibd1: two consecutive windows of a run share one sum tree through 1 KiB of LDS scratch per wave (the host: where that costs no workgroup per CU)
     const double *fin_p2c = nullptr, *fin_p2w = nullptr;   // fin_prev's run was of that form: the pass's sums per chunk / per individual
     const uint32_t *fin_targets = nullptr;                 // ... and its comparison individuals (that run's entry of the ring)
     const uint32_t *frag_base = nullptr;   // ibd1: [n_segs][3][6] the fragments COV, F0, F1 of the site list (k_frag_base); null: k_win_target_mx builds everything

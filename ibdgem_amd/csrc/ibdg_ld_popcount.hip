@@ -186,6 +186,35 @@ __device__ __forceinline__ double wave_sum2_dpp(double a, double b, uint32_t scr
     return v;
 }
 
+// Two CONSECUTIVE windows' sums in that tree (the IBD1 form's paired window end): the first window of a pair parks every
+// lane's value in the first array of the wave's scratch and goes on -- no wait, no reduction --, the second one writes the
+// second array and does the rest of wave_sum2_dpp.  Lane 31 ends up with the first window's total, lane 63 with the
+// second's; the last step goes without its row mask (wave_sum_lane63_only: the other rows take sums nobody reads, and the
+// step needs no zeroed destination).  The pair add is the lane ^ 1 level of wave_sum_lane63_only, the five steps are the
+// lane number's bits 1-5: the same additions, the same bits.  16 vector instructions for two windows instead of 36.
+__device__ __forceinline__ void wave_sum_park(double a, uint32_t scr_w)
+{
+    asm volatile("ds_write_b64 %0, %1" : : "v"(scr_w), "v"(a) : "memory");
+}
+
+__device__ __forceinline__ double wave_sum_pair_dpp(double b, uint32_t scr_w, uint32_t scr_r)
+{
+    uint4 r;
+    asm volatile("ds_write_b64 %1, %2 offset:512\n\t"
+                 "ds_read_b128 %0, %3\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(r)
+                 : "v"(scr_w), "v"(b), "v"(scr_r)
+                 : "memory");
+    double v = __hiloint2double((int)r.y, (int)r.x) + __hiloint2double((int)r.w, (int)r.z);
+    v = dpp_add<0xB1, 0xf>(v);      // quad_perm [1,0,3,2]
+    v = dpp_add<0x4E, 0xf>(v);      // quad_perm [2,3,0,1]
+    v = dpp_add<0x141, 0xf>(v);     // row_half_mirror
+    v = dpp_add<0x140, 0xf>(v);     // row_mirror
+    v = dpp_add<0x142, 0xf>(v);     // row_bcast:15: rows 1 and 3 take the other row of their half
+    return v;
+}
+
 // ---------------------------------------------------------------------------
 // The --LD loop.
 //
@@ -1008,8 +1037,10 @@ __device__ __forceinline__ double ibd1_window_value(const Run &r, const PopArgs 
     return wgt * (((val[0] + val[1]) + val[2]) + val[3]);
 }
 
-// the IBD1 form (ibd0_after 1): the timed kernel
-template <class Ring>
+// the IBD1 form (ibd0_after 1): the timed kernel.  PAIR (PopArgs::pair_sums): two consecutive windows of the run share one
+// sum tree through the wave's scratch (wave_sum_pair_dpp); a run's odd last window, and every window without PAIR, ends
+// with the DPP moves alone
+template <bool PAIR, class Ring>
 __device__ __forceinline__ void run_ibd1_form(Ring &ring, const Run &r, const PopArgs &a, unsigned t)
 {
     const double wgt = a.weight[(size_t)(a.t_base + t) * a.lanes + r.c * 64 + r.lane];
@@ -1019,16 +1050,30 @@ __device__ __forceinline__ void run_ibd1_form(Ring &ring, const Run &r, const Po
     mx_v4f bias4 = {12582912.f, 12582912.f, 12582912.f, 12582912.f};
     asm volatile("" : "+v"(bias4));
     SegCursor cur = {0, r.rec_addr + 24 * (r.lane & 3), r.x_off0, 0};
-    // the sum over the wave's 64 individuals in the tree of wave_sum2 (the lane number's bits in turn), by DPP moves alone:
-    // this form has no scratch in LDS (a third ring slot per wave at the same four workgroups a CU measured 3 % slower)
+    // the sum over the wave's 64 individuals in the tree of wave_sum2 (the lane number's bits in turn)
     uint32_t w = r.w0;
-    while (cur.s < r.nseg) {
+    // a window's segments and the lane's value of it
+    auto window_value = [&]() {
         uint32_t flags = segment_x1<true>(ring, cur, r, m, bias4);
         while (!(flags & (1u << 15)))
             flags = segment_x1<false>(ring, cur, r, m, bias4);
-        const double tot = wave_sum_lane63_only(ibd1_window_value(r, a, m, w, wgt));
-        if (r.lane == 63)
-            partial_of(a, r, t, w)[1] = tot;
+        return ibd1_window_value(r, a, m, w, wgt);
+    };
+    // PAIR: lane 31 stores the first window's sum, lane 63 the second's, one window's partials further on
+    const uint32_t second = PAIR ? (r.lane >> 5) * a.n_chunks * 2 : 0;
+    while (cur.s < r.nseg) {
+        const double v = window_value();
+        if (PAIR && cur.s < r.nseg) {           // another window of the run follows: the two share a tree
+            wave_sum_park(v, r.scr_w);
+            ++w;
+            const double tot = wave_sum_pair_dpp(window_value(), r.scr_w, r.scr_r);
+            if ((r.lane & 31) == 31)
+                partial_of(a, r, t, w - 1)[1 + second] = tot;
+        } else {
+            const double tot = wave_sum_lane63_only(v);
+            if (r.lane == 63)
+                partial_of(a, r, t, w)[1] = tot;
+        }
         ++w;
     }
     ring.drain();
@@ -1060,7 +1105,7 @@ __device__ __forceinline__ bool fused_finalize(uint32_t &bx, unsigned t, const W
     return true;
 }
 
-template <int NS, bool TAB_LDS, bool MX, bool IBD1 = false>
+template <int NS, bool TAB_LDS, bool MX, bool IBD1 = false, bool PAIR = false>
 __global__ __launch_bounds__(512) void k_ld_popcount(const uint4 *__restrict__ t32,
                                                      const Seg *__restrict__ segs,
                                                      const uint32_t *__restrict__ rec_ready,
@@ -1072,6 +1117,7 @@ __global__ __launch_bounds__(512) void k_ld_popcount(const uint4 *__restrict__ t
                                                      PopArgs a)
 {
     static_assert(!IBD1 || (MX && TAB_LDS), "the IBD1 form exists with the counts on the matrix cores and the tables in LDS");
+    static_assert(!PAIR || IBD1, "the paired window end is the IBD1 form's");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned t = blockIdx.z;
     uint32_t bx = blockIdx.x;
@@ -1081,12 +1127,12 @@ __global__ __launch_bounds__(512) void k_ld_popcount(const uint4 *__restrict__ t
     if (sp.nseg == 0)
         return;
     TileRing<NS, MX> ring;
-    const Run r = run_prologue<MX ? IBDG_RECX_WORDS : IBDG_REC_WORDS, IBDG_WC_WORDS, TAB_LDS, MX && TAB_LDS ? 8 : 16, !IBD1>(
+    const Run r = run_prologue<MX ? IBDG_RECX_WORDS : IBDG_REC_WORDS, IBDG_WC_WORDS, TAB_LDS, MX && TAB_LDS ? 8 : 16, !IBD1 || PAIR>(
         sp, ring, smem, t, t32, segs, rec_ready, wc_ready, pow_1me, pow_eps, a);
     if (!r.has_chunk)
         return;
     if constexpr (IBD1)
-        run_ibd1_form(ring, r, a, t);
+        run_ibd1_form<PAIR>(ring, r, a, t);
     else if constexpr (MX)
         run_matrix_form<TAB_LDS>(ring, r, a, t);
     else
@@ -1221,11 +1267,11 @@ __global__ __launch_bounds__(256) void k_ld_finalize(PopFinalArgs a)
 // ---------------------------------------------------------------------------
 // LDS of one workgroup: records + window constants (+ power tables) rounded to 1 KiB, then 8 rings (+ wave_sum2 scratch).
 // multi_target: 0 = one comparison individual (vector-ALU counts), 1 = groups of IBDG_MT, 2 = one, counts on the matrix
-// cores, 3 = the IBD1 form of 2: no scratch
+// cores, 3 = the IBD1 form of 2: no scratch, 4 = the IBD1 form with the paired window end: the scratch again
 size_t ld_popcount_lds_bytes(uint32_t max_seg, uint32_t win_per_group, uint32_t tab_len, int tab_in_lds,
                              int ring_slots, int multi_target)
 {
-    const bool mt = multi_target == 1, mx = multi_target == 2 || multi_target == 3;
+    const bool mt = multi_target == 1, mx = multi_target >= 2 && multi_target <= 4;
     return ld_lds_layout(max_seg, win_per_group, tab_len, mt ? IBDG_RECM_WORDS : mx ? IBDG_RECX_WORDS : IBDG_REC_WORDS,
                          mt ? IBDG_WCM_WORDS : IBDG_WC_WORDS, tab_in_lds ? (mx ? 8 : 16) : 0,      // (matrix-core form: plain doubles)
                          ring_slots, 8, multi_target != 3)
@@ -1263,12 +1309,12 @@ static int launch_counting(CountKernel kern, size_t lds, const PopArgs &a, dim3 
     return 0;
 }
 
-template <int NS, bool TAB, bool MX, bool IBD1 = false>
+template <int NS, bool TAB, bool MX, bool IBD1 = false, bool PAIR = false>
 static int launch_pop(const PopArgs &a, dim3 grid, hipStream_t st, KernelEvents ev)
 {
-    return launch_counting(k_ld_popcount<NS, TAB, MX, IBD1>,
-                           ld_popcount_lds_bytes(a.max_seg, a.win_per_group, a.tab_len, TAB, NS, IBD1 ? 3 : MX ? 2 : 0), a, grid,
-                           st, ev);
+    return launch_counting(k_ld_popcount<NS, TAB, MX, IBD1, PAIR>,
+                           ld_popcount_lds_bytes(a.max_seg, a.win_per_group, a.tab_len, TAB, NS, IBD1 ? (PAIR ? 4 : 3) : MX ? 2 : 0), a,
+                           grid, st, ev);
 }
 
 int launch_ld_popcount(const PopArgs &a, unsigned n_targets, int planes, hipStream_t st, KernelEvents ev)
@@ -1280,10 +1326,12 @@ int launch_ld_popcount(const PopArgs &a, unsigned n_targets, int planes, hipStre
     dim3 grid(a.n_runs * a.n_cgroups + (a.fin_prev ? (a.n_win + a.waves_per_group - 1) / a.waves_per_group : 0), 1, n_targets);
     if (a.ibd1 && (!a.mx_counts || !a.tab_in_lds || a.p2_out))
         return 1;
+    if (a.pair_sums && !a.ibd1)
+        return 1;
     return with_ring_slots(a.ring_slots, [&](auto ns) {
         constexpr int NS = decltype(ns)::value;
         if (a.ibd1)
-            return launch_pop<NS, true, true, true>(a, grid, st, ev);
+            return a.pair_sums ? launch_pop<NS, true, true, true, true>(a, grid, st, ev) : launch_pop<NS, true, true, true>(a, grid, st, ev);
         if (a.mx_counts)
             return a.tab_in_lds ? launch_pop<NS, true, true>(a, grid, st, ev) : launch_pop<NS, false, true>(a, grid, st, ev);
         return a.tab_in_lds ? launch_pop<NS, true, false>(a, grid, st, ev) : launch_pop<NS, false, false>(a, grid, st, ev);

@@ -66,6 +66,7 @@ SYMBOLS = {
     "ibdg_last_ld_variant": (C.c_int, [_P]),
     "ibdg_ld_layout": (C.c_int, [_P]),
     "ibdg_last_count_unit": (C.c_int, [_P]),
+    "ibdg_last_window_end": (C.c_int, [_P]),
     "ibdg_set_option": (C.c_int, [_P, C.c_char_p, C.c_long]),
     "ibdg_set_background_order": (C.c_int, [_P, _P, C.c_size_t]),
     "ibdg_selftest": (C.c_int, [C.c_char_p]),
@@ -494,6 +495,11 @@ class Engine:
         """2 = the last run's single-individual launches took the sums of a haplotype word on the matrix cores, 1 = by
         (mask, count) pairs, 0 = no such launch (ibdg_last_count_unit)."""
         return self.lib.ibdg_last_count_unit(self.ctx)
+
+    def last_window_end(self):
+        """2 = those launches summed two consecutive windows of a run in one tree (the IBD1 form's paired window end, option
+        pair_sums), 1 = every window on its own, 0 = no such launch (ibdg_last_window_end)."""
+        return self.lib.ibdg_last_window_end(self.ctx)
 
     def ld_layout(self):
         """0 none, 1 the panel's own tiles, 2 the compacted tiles of the site list (its rows with reads back to back)."""

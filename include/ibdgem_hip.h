@@ -360,6 +360,13 @@ int ibdg_ld_layout(const ibdg_ctx *ctx);
  * in the same order in every form: same results, bit for bit. */
 int ibdg_last_count_unit(const ibdg_ctx *ctx);
 
+/* How those launches of the last ibdg_run ended a window, i.e. summed its products over a wave's 64 background
+ * individuals: 2 = two consecutive windows of a run in one sum tree through 1 KiB of LDS scratch per wave (form 3 above
+ * with option "pair_sums" 1, the default, where the scratch leaves as many workgroups on a compute unit as the form has
+ * without it), 1 = every window on its own, 0 = no such launch in that run.  The same additions in the same order either
+ * way: same results, bit for bit. */
+int ibdg_last_window_end(const ibdg_ctx *ctx);
+
 /* Options: "dispatch_events" (0/1: time the --LD launches through their own
  * dispatch packets, which makes ibdg_run_kernel_ms available; costs ~10 us per
  * run more than the default single event record); "async" (0/1: ibdg_run returns as soon as its kernels are queued;
@@ -403,7 +410,7 @@ int ibdg_last_count_unit(const ibdg_ctx *ctx);
  * "mx_counts" (0/1, default 1: see ibdg_last_count_unit; applies where a run's records of 128 bytes per (window, tile)
  * segment fit the workgroup's LDS and the powers rho^n 2^(s n) of a window's table stay normal doubles, always so at the
  * table sizes kept in LDS); "sum_dpp" (0/1, default 1: the wave sums of that form exchange by DPP moves instead of
- * ds_swizzle -- same additions, same bits);
+ * ds_swizzle -- same additions, same bits); "pair_sums" (0/1, default 1: see ibdg_last_window_end);
  * "finalize_in_next" (0/1, default 1; with "async" only: a run of single comparison individuals leaves its finalising
  * step -- the sum over the chunks and the background average, src/ibdgem.c:751-752 -- to the next run's --LD launch when
  * that run has the same shape, background and prepared sites (ABI 5: the individuals may differ); whoever reads results or
