@@ -119,7 +119,8 @@ int ensure(ibdg_ctx *c, DevBuf &b, size_t bytes)
 
 // ---- what stops being valid when an input changes: each of these says all of it, and nobody else says any ----
 
-// A panel goes up: the alt counts, the results (with what the log-domain calls kept of them: ls), the layout, the site list
+// A panel goes up: the alt counts, the results (with what the log-domain calls kept of them: ls, and the window chains, which
+// belong to the site list that goes), the layout, the site list
 // and the candidates (they name rows of the panel that goes), and the device copies of targets / background weights, which
 // were laid out for the previous panel.  The row
 // table goes with up_gen (its alt counts and n_ids).  sites_gen stays: no run is accepted before the next upload of sites
@@ -129,7 +130,7 @@ void panel_replaced(ibdg_ctx *c)
     ++c->up_gen;
     c->pan.counts_valid = false;
     c->have_results = false;
-    c->ls.drop();
+    c->ls.chains_clear();
     c->lay.pop_sites_ok = false;
     c->prev_targets.clear();
     c->bg.prev_bg.clear();
@@ -143,7 +144,8 @@ void panel_replaced(ibdg_ctx *c)
     c->cand.n_cand = 0;
 }
 
-// A site list goes up (from the host, the device or the candidates): the results (with ls), the layout and its credit, the
+// A site list goes up (from the host, the device or the candidates): the results (with ls and the window chains of the list
+// before: ibdg_set_window_chains speaks of one list's windows), the layout and its credit, the
 // window bounds, the -A triples, the selection map; with sites_gen the IBD0 pass, the fragment base, the images, a pending
 // finalising step's right to ride along and stream3's order behind the prepared sites; with up_gen the row table; and
 // the count of runs towards "ibd0_after".
@@ -158,7 +160,7 @@ void sites_replaced(ibdg_ctx *c)
     c->sites.have_fo = false;
     c->cand.sel_valid = false;
     c->have_results = false;
-    c->ls.drop();
+    c->ls.chains_clear();
     c->lay.pop_sites_ok = false;
     c->lay.compact = false;
     c->lay.relayout_credit = 0;
@@ -2307,7 +2309,16 @@ int ibdg_log2_states_host(const double *log2_tab, size_t n_win, double p01, doub
                           uint64_t count[3])
 {
     char msg[256];
-    if (ibdg::log2_states_host(log2_tab, n_win, p01, p02, p12, path, score, count, msg, sizeof msg))
+    if (ibdg::log2_states_host(__func__, log2_tab, n_win, p01, p02, p12, nullptr, 0, path, score, count, msg, sizeof msg))
+        return fail(nullptr, "%s", msg);
+    return 0;
+}
+
+int ibdg_log2_states_chains_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, uint8_t *path, int64_t *score,
+                                 uint64_t count[3], const uint32_t *starts, size_t n_starts)
+{
+    char msg[256];
+    if (ibdg::log2_states_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, path, score, count, msg, sizeof msg))
         return fail(nullptr, "%s", msg);
     return 0;
 }
@@ -2349,7 +2360,7 @@ static int enqueue_states(ibdg_ctx *c, const LogCall &L, bool want_score)
     if (ensure(c, S.path, L.T * L.n_win) || ensure(c, S.count, L.T * 24) || (want_score && ensure(c, S.score, L.T * L.n_win * 24)))
         return 1;
     if (S.fresh(S.PATH, L.P) && !want_score) return 0;
-    ibdg::launch_log2_states((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.P, (uint8_t *)S.path.p,
+    ibdg::launch_log2_states((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.P, S.mask(), (uint8_t *)S.path.p,
                              want_score ? (int64_t *)S.score.p : nullptr, (uint64_t *)S.count.p, c->stream);
     HIP_TRY(c, hipGetLastError());
     S.made(S.PATH, L.P);
@@ -2364,7 +2375,7 @@ static int enqueue_posteriors(ibdg_ctx *c, const LogCall &L)
     if (S.fresh(S.POST, L.P)) return 0;
     HIP_TRY(c, hipMemcpyAsync(S.ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
     ibdg::launch_log2_posteriors((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.a, (const double *)S.ptab.p,
-                                 (double *)S.post.p, (double *)S.pout.p, c->stream);
+                                 S.mask(), (double *)S.post.p, (double *)S.pout.p, c->stream);
     HIP_TRY(c, hipGetLastError());
     S.made(S.POST, L.P);
     return 0;
@@ -2375,7 +2386,7 @@ static int enqueue_segments_count(ibdg_ctx *c, const LogCall &L, const uint64_t 
 {
     if (ensure(c, c->ls.sout, L.T * 104)) return 1;
     ibdg::launch_log2_segments_count((const uint8_t *)c->ls.path.p, (uint32_t)L.n_win, (uint32_t)L.T, d_first, d_last,
-                                     (uint64_t *)c->ls.sout.p, c->stream);
+                                     c->ls.mask(), (uint64_t *)c->ls.sout.p, c->stream);
     HIP_TRY(c, hipGetLastError());
     return 0;
 }
@@ -2400,17 +2411,29 @@ int ibdg_window_log2_states(ibdg_ctx *c, double p01, double p02, double p12, uin
     return quiesce(c);
 }
 
-int ibdg_log2_posteriors_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
-                              double expect[3], double *log2_z)
+static int posteriors_twin(const char *fn, const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
+                           double expect[3], double *log2_z, const uint32_t *starts, size_t n_starts)
 {
     char msg[256];
     double zm = 1.0;
     int ze = 0;
-    if (!log2_z) return fail(nullptr, "[::] ERROR in ibdg_log2_posteriors_host: NULL log2_z");
-    if (ibdg::log2_posteriors_host(log2_tab, n_win, p01, p02, p12, post, expect, &zm, &ze, msg, sizeof msg))
+    if (!log2_z) return fail(nullptr, "[::] ERROR in %s: NULL log2_z", fn);
+    if (ibdg::log2_posteriors_host(fn, log2_tab, n_win, p01, p02, p12, starts, n_starts, post, expect, &zm, &ze, msg, sizeof msg))
         return fail(nullptr, "%s", msg);
     *log2_z = std::log2(zm) + (double)ze;
     return 0;
+}
+
+int ibdg_log2_posteriors_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
+                              double expect[3], double *log2_z)
+{
+    return posteriors_twin(__func__, log2_tab, n_win, p01, p02, p12, post, expect, log2_z, nullptr, 0);
+}
+
+int ibdg_log2_posteriors_chains_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
+                                     double expect[3], double *log2_z, const uint32_t *starts, size_t n_starts)
+{
+    return posteriors_twin(__func__, log2_tab, n_win, p01, p02, p12, post, expect, log2_z, starts, n_starts);
 }
 
 // IBD-state posteriors (k_log2_posteriors): the posteriors stage, expect and Z (and the gammas when asked for) out
@@ -2446,10 +2469,50 @@ int ibdg_log2_segments_host(const double *log2_tab, size_t n_win, double p01, do
                             uint64_t summary[12])
 {
     char msg[256];
-    if (ibdg::log2_segments_host(log2_tab, n_win, p01, p02, p12, with_post, pos_first, pos_last, seg, seg_cap, n_seg, summary, msg,
-                                 sizeof msg))
+    if (ibdg::log2_segments_host(__func__, log2_tab, n_win, p01, p02, p12, nullptr, 0, with_post, pos_first, pos_last, seg, seg_cap,
+                                 n_seg, summary, msg, sizeof msg))
         return fail(nullptr, "%s", msg);
     return 0;
+}
+
+int ibdg_log2_segments_chains_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, int with_post,
+                                   const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap,
+                                   uint64_t *n_seg, uint64_t summary[12], const uint32_t *starts, size_t n_starts)
+{
+    char msg[256];
+    if (ibdg::log2_segments_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, with_post, pos_first, pos_last, seg,
+                                 seg_cap, n_seg, summary, msg, sizeof msg))
+        return fail(nullptr, "%s", msg);
+    return 0;
+}
+
+// The window chains of the current site list (LogStates in ibdg_ctx.h has the rule): checked, then kept on the
+// host and as a mask on the device for the four kernels.  The upload waits on the host: no call of the group is in flight
+// (each ends with quiesce), and the list it copies from may go once this returns.  A refused call changes nothing.
+int ibdg_set_window_chains(ibdg_ctx *c, const uint32_t *starts, size_t n_starts)
+{
+    if (!c) return 1;
+    if (!c->sites.sites_valid) return fail(c, "[::] ERROR in ibdg_set_window_chains: no valid site list (call ibdg_upload_sites)");
+    ibdg_ctx::LogStates &S = c->ls;
+    const size_t n_win = c->sites.n_win;
+    std::vector<uint32_t> mask(n_starts ? (n_win + 31) / 32 : 0);
+    char msg[256];
+    if (ibdg::chain_mask(__func__, starts, n_starts, n_win, mask.data(), msg, sizeof msg))
+        return fail(c, "%s", msg);
+    if (n_starts) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (quiesce(c) || ensure(c, S.cmask, mask.size() * 4)) return 1;
+        HIP_TRY(c, hipMemcpy(S.cmask.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice));
+    }
+    S.chains.assign(starts, starts + n_starts);
+    ++S.chain_gen;
+    S.drop();
+    return 0;
+}
+
+size_t ibdg_num_window_chains(const ibdg_ctx *c)
+{
+    return c && c->sites.sites_valid && c->sites.n_win ? c->ls.chains.size() + 1 : 0;
 }
 
 // The segments of the paths (k_log2_segments_count): the states stage, with with_post the posteriors stage, the count stage
@@ -2529,7 +2592,7 @@ int ibdg_get_log2_segments(ibdg_ctx *c, ibdg_segment *seg, size_t cap)
     HIP_TRY(c, hipMemcpyAsync(S.soff.p, off.data(), T * 8, hipMemcpyHostToDevice, c->stream));
     ibdg::launch_log2_segments_write((const double *)c->wlog.win_log2.p, (const uint8_t *)S.path.p,
                                      S.with_post ? (const double *)S.post.p : nullptr, (uint32_t)n_win, (uint32_t)T,
-                                     (const uint64_t *)S.soff.p, (ibdg_segment *)S.recs.p, c->stream);
+                                     (const uint64_t *)S.soff.p, S.mask(), (ibdg_segment *)S.recs.p, c->stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(seg, S.recs.p, total * sizeof(ibdg_segment), hipMemcpyDeviceToHost, c->stream));
     return quiesce(c);

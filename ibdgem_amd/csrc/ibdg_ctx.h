@@ -368,24 +368,34 @@ struct ibdg_ctx {
     // The records: records_made says that `path` (and with_post: `post`) are what the last ibdg_window_log2_segments used and
     // `n_seg` its counts, for ibdg_get_log2_segments to cut the records from.  Reuse goes forward only: a states or
     // posteriors call drops the records again (records_drop), whatever its penalties, and so does drop().
+    // The chains: the windows that start a chain besides window 0, as ibdg_set_window_chains took them (`chains`,
+    // strictly increasing in [1, n_win)), and their bits on the device (`cmask`, ceil(n_win / 32) words, uploaded by the setter
+    // behind a host wait, read by all four kernels; mask() is NULL without chains).  They belong to the site list, not to a
+    // run: the setter drops the kept products (drop()) and bumps `chain_gen`, which is part of both products' key beside the
+    // penalties; panel_replaced and sites_replaced clear them (chains_clear); the start of a run does not -- batches of
+    // individuals share a site list.
     // The rest is scratch of one call: `ptab` (the two tables, uploaded with every posteriors launch), `spos` (the windows'
     // positions [2][n_win]), `sout` (summaries and counts [T][13]), `soff` (record offsets [T]), `recs` (the records).
     struct LogStates {
-        DevBuf path, score, count, post, pout, ptab, spos, sout, soff, recs;
+        DevBuf path, score, count, post, pout, ptab, spos, sout, soff, recs, cmask;
         enum Product { PATH, POST };
         bool have[2] = {false, false};
         int64_t P[2][3] = {};
+        std::vector<uint32_t> chains;    // the chain starts of the site list at hand
+        uint64_t chain_gen = 1, gen[2] = {0, 0};     // bumped with every change of `chains`; what each product was made for
+        const uint32_t *mask() const { return chains.empty() ? nullptr : (const uint32_t *)cmask.p; }
+        void chains_clear() { if (!chains.empty()) ++chain_gen; chains.clear(); drop(); }
         bool recs_ok = false, with_post = false;
         std::vector<uint64_t> n_seg;     // per individual of the last ibdg_window_log2_segments
         bool fresh(Product k, const int64_t want[3]) const
-        { return have[k] && P[k][0] == want[0] && P[k][1] == want[1] && P[k][2] == want[2]; }
+        { return have[k] && gen[k] == chain_gen && P[k][0] == want[0] && P[k][1] == want[1] && P[k][2] == want[2]; }
         void made(Product k, const int64_t made_for[3])
-        { have[k] = true; P[k][0] = made_for[0]; P[k][1] = made_for[1]; P[k][2] = made_for[2]; }
+        { have[k] = true; gen[k] = chain_gen; P[k][0] = made_for[0]; P[k][1] = made_for[1]; P[k][2] = made_for[2]; }
         bool records_fresh() const { return recs_ok; }
         void records_made() { recs_ok = true; }
         void records_drop() { recs_ok = false; }
         void drop() { have[PATH] = have[POST] = recs_ok = false; }
-        void free_bufs() { release_all({&path, &score, &count, &post, &pout, &ptab, &spos, &sout, &soff, &recs}); }
+        void free_bufs() { release_all({&path, &score, &count, &post, &pout, &ptab, &spos, &sout, &soff, &recs, &cmask}); }
     } ls;
 
     // The finalising step of the last run of single individuals (k_ld_finalize's work) when it has been left to the NEXT

@@ -13,6 +13,19 @@
 // (max, +) over integers is exact and associative: the scores, hence the `from` entries, hence the path are the same
 // integers for any blocking of the windows.  n_win <= 2^21 keeps |score| < 2^62 (a step moves a score by at most 2^40
 // down -- its own state's emission -- and never up).
+//
+// Chains.  A chain start is a window that is treated the way window 0 is: uniform entry, no penalty into it.  The
+// starts are a mask of ceil(n_win / 32) words, bit w & 31 of word w >> 5 set iff window w >= 1 starts a chain; window 0 always
+// starts one, and a NULL mask means no further start (chain_start).  Everything else accumulates as before:
+//   path        at a start the step takes pen[q][s] = 0 for all q, s (states_chain_step): score[w][s] = max_q score[w-1][q] +
+//               e_w[s], from[w][s] = the lowest q of that maximum, the same for every s.  The scores are not reset, and a step
+//               still never moves a score up: the bound above holds.  Inside a chain [c0, c1) the scores are the chain's own
+//               plus one constant K = max_q score[c0-1][q], so `from`, the traceback and the path are what a call on the slice
+//               gives.
+//   posteriors  at a start M_w[q][s] = b_w[s] -- post_step_matrix with a = (1, 1, 1), products with 1.0, which are exact --
+//               in steps 1, 3 and 4 alike (post_window_matrix); "the first matrix of a block" is that of w0 == 0 or a start.
+//               Z is the product of the chains' Z, gamma inside a chain the chain's own.  No operation is added.
+//   segments    window w starts a segment iff w == 0, path[w] != path[w-1] or w starts a chain: no segment crosses a border.
 #pragma once
 #include "../../include/ibdgem_hip.h"      // ibdg_segment
 
@@ -80,6 +93,24 @@ IBDG_HD unsigned states_step(int64_t v[3], const int64_t pen[3][3], const int64_
     return f;
 }
 
+// whether window w >= 1 starts a chain; mask: the starts' bits, or NULL for none
+IBDG_HD bool chain_start(const uint32_t *__restrict__ mask, uint32_t w)
+{
+    return mask && (mask[w >> 5] >> (w & 31) & 1);
+}
+
+// states_step of a window that starts a chain (start) or not: the step's penalties by selects, one matrix
+IBDG_HD unsigned states_chain_step(int64_t v[3], const int64_t pen[3][3], const int64_t e[3], bool start)
+{
+    int64_t pw[3][3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+            pw[q][s] = start ? 0 : pen[q][s];
+    return states_step(v, pw, e);
+}
+
 IBDG_HD int argmax3(const int64_t v[3])
 {
     const int m = v[1] > v[0] ? 1 : 0;
@@ -111,9 +142,14 @@ struct Blocks {
 // P[0..2] = P_01, P_02, P_12; 1 if a p is NaN or outside (0, 1] (bad: its index 0..2)
 int states_penalties(double p01, double p02, double p12, int64_t P[3], int *bad);
 
-// the host twin (ibdg_log2_states_host): path [n_win] or NULL, score [n_win][3] or NULL, count[3]; err: room for a message
-int log2_states_host(const double *tab, size_t n_win, double p01, double p02, double p12, uint8_t *path, int64_t *score,
-                     uint64_t count[3], char *err, size_t err_len);
+// The chain starts as callers give them: a strictly increasing list with every entry in [1, n_win).  1 and a message in err
+// (fn: who refuses) for anything else; else mask holds the ceil(n_win / 32) words (none for an empty list).
+int chain_mask(const char *fn, const uint32_t *starts, size_t n_starts, size_t n_win, uint32_t *mask, char *err, size_t err_len);
+
+// the host twin (ibdg_log2_states[_chains]_host): path [n_win] or NULL, score [n_win][3] or NULL, count[3]; starts [n_starts]: the
+// chain starts (chain_mask's rules); fn: the public name, for messages; err: room for a message
+int log2_states_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                     size_t n_starts, uint8_t *path, int64_t *score, uint64_t count[3], char *err, size_t err_len);
 
 // ---- posteriors: the sum-product pass over the weights whose max-product the path takes ---------------------
 //
@@ -222,11 +258,13 @@ IBDG_HD void post_mat_vec(const double M[9], double v[3])
     v[0] = n[0], v[1] = n[1], v[2] = n[2];
 }
 
-// what steps 1, 3 and 4 read: the individual's table [n_win][3], the penalty weights, the tables T1, T2 = T + 256
+// what steps 1, 3 and 4 read: the individual's table [n_win][3], the penalty weights, the tables T1, T2 = T + 256, the chain
+// starts' mask or NULL
 struct PostIn {
     const double *__restrict__ tab;
     const double *T;
     double a[3];
+    const uint32_t *__restrict__ starts;
 };
 
 // b_w[0..2] of window w
@@ -237,6 +275,14 @@ IBDG_HD void post_emission_weights(const PostIn &in, uint32_t w, double b[3])
 #pragma unroll
     for (int s = 0; s < 3; ++s)
         b[s] = post_weight(e[s], in.T, in.T + 256);
+}
+
+// M_w of window w >= 1 from its b_w: the penalty weights, or (1, 1, 1) where w starts a chain, by selects
+IBDG_HD void post_window_matrix(const PostIn &in, uint32_t w, const double b[3], double M[9])
+{
+    const bool st = chain_start(in.starts, w);
+    const double a[3] = {st ? 1.0 : in.a[0], st ? 1.0 : in.a[1], st ? 1.0 : in.a[2]};
+    post_step_matrix(a, b, M);
 }
 
 // step 1 for the block of windows [w0, w1), w0 < w1: B[9] = B_b, *Bexp its exponent
@@ -250,11 +296,11 @@ IBDG_HD void post_block_matrix(const PostIn &in, uint32_t w0, uint32_t w1, doubl
         for (int q = 0; q < 3; ++q)
             R[3 * q] = bw[0], R[3 * q + 1] = bw[1], R[3 * q + 2] = bw[2];
     } else {
-        post_step_matrix(in.a, bw, R);
+        post_window_matrix(in, w0, bw, R);     // (a start gives the same three copies)
     }
     for (uint32_t w = w0 + 1; w < w1; ++w) {
         post_emission_weights(in, w, bw);
-        post_step_matrix(in.a, bw, M);
+        post_window_matrix(in, w, bw, M);
 #pragma unroll
         for (int q = 0; q < 3; ++q)
             post_vec_mat(R + 3 * q, M);
@@ -324,7 +370,7 @@ IBDG_HD void post_block_gamma(const PostIn &in, uint32_t w0, uint32_t w1, const 
         p[0] = be[0], p[1] = be[1], p[2] = be[2];
         if (w > w0) {
             post_emission_weights(in, w, bw);
-            post_step_matrix(in.a, bw, M);
+            post_window_matrix(in, w, bw, M);
             post_mat_vec(M, be);
             post_rescale<3>(be, ge);
         }
@@ -340,7 +386,7 @@ IBDG_HD void post_block_gamma(const PostIn &in, uint32_t w0, uint32_t w1, const 
             v[0] = bw[0], v[1] = bw[1], v[2] = bw[2];
             e = 0;
         } else {
-            post_step_matrix(in.a, bw, M);
+            post_window_matrix(in, w, bw, M);
             post_vec_mat(v, M);
             post_rescale<3>(v, e);
         }
@@ -359,16 +405,16 @@ const double *post_tables();
 // a[0..2] = the weights of P_01, P_02, P_12 (states_penalties' integers)
 void post_penalty_weights(const int64_t P[3], double a[3]);
 
-// the host twin (ibdg_log2_posteriors_host): post [n_win][3] or NULL, expect[3], z_mant and z_exp with Z = z_mant * 2^z_exp (1, 0
-// for n_win = 0)
-int log2_posteriors_host(const double *tab, size_t n_win, double p01, double p02, double p12, double *post, double expect[3],
-                         double *z_mant, int *z_exp, char *err, size_t err_len);
+// the host twin (ibdg_log2_posteriors[_chains]_host): post [n_win][3] or NULL, expect[3], z_mant and z_exp with Z = z_mant *
+// 2^z_exp (1, 0 for n_win = 0); starts, fn as above
+int log2_posteriors_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                         size_t n_starts, double *post, double expect[3], double *z_mant, int *z_exp, char *err, size_t err_len);
 
 // ---- segments: the maximal runs of one state along the path, with what backs each of them -------------------
 //
 // Inputs: path[n_win] of 4.8; the emissions e_w[s] (the integers above); optionally gamma_w[s] of 4.9; optionally the positions
-// pos_first[w] <= pos_last[w] of every window's first and last site.  Window w starts a segment iff w == 0 or path[w] !=
-// path[w - 1]; segment k (0-based, in window order) runs from its start f to the window before the next start, or to n_win - 1.
+// pos_first[w] <= pos_last[w] of every window's first and last site.  Window w starts a segment iff w == 0, path[w] !=
+// path[w - 1] or w starts a chain (seg_start; the chain of a segment follows from `first`); segment k (0-based, in window order) runs from its start f to the window before the next start, or to n_win - 1.
 //   record   ibdg_segment (include/ibdgem_hip.h, 56 bytes): first = f, n_win = its windows, state = path[f], reserved = 0;
 //            e[s] = sum of e_w[s] over its windows (|e_w[s]| <= 2^40, n_win <= 2^21: |sum| <= 2^61; a window whose emission is
 //            (0, 0, 0) adds nothing); post_q = sum of q_w = states_rint(gamma_w[state] * 2^32) (the product with a power of two is
@@ -389,6 +435,13 @@ struct SegAcc {
     uint64_t q;
     double mn;
 };
+
+// whether window w starts a segment: prev = the state of window w - 1 (3, "no state", before window 0), s = that of w
+IBDG_HD bool seg_start(const uint32_t *__restrict__ mask, uint32_t w, unsigned prev, unsigned s)
+{
+    const bool c = chain_start(mask, w);       // (asked first, not behind the states: its read does not wait for theirs)
+    return s != prev || c;
+}
 
 IBDG_HD void seg_reset(SegAcc &a)
 {
@@ -440,9 +493,9 @@ IBDG_HD void seg_summary_add(uint64_t v[12], unsigned s, uint64_t len, uint64_t 
         v[i] = s == (unsigned)(i % 3) ? seg_summary_join(i, v[i], one[i / 3]) : v[i];
 }
 
-// the host twin (ibdg_log2_segments_host): seg [seg_cap] or NULL, *n_seg the true count, summary[12]
-int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,
-                       const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err,
-                       size_t err_len);
+// the host twin (ibdg_log2_segments[_chains]_host): seg [seg_cap] or NULL, *n_seg the true count, summary[12]; starts, fn as above
+int log2_segments_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                       size_t n_starts, int with_post, const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg,
+                       size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err, size_t err_len);
 
 }  // namespace ibdg

@@ -15,6 +15,11 @@
 //   pass 3  the backward maps composed from the last block down (a suffix scan over the 256 maps of 6 bits in LDS), every
 //           thread traces its own windows backward, overwriting `from` with the state; the counts meet in LDS
 // No atomics.  Reads: a thread walks its own 24-byte rows, lanes 24 C bytes apart (DESIGN 4.8 has the measurement).
+// Chains: all four kernels take the starts' mask, or NULL; a thread reads the bits of its own windows
+// (chain_start) and takes a start's penalties, weights or segment border by a select.  Each kernel has two instantiations,
+// picked by the launch: CH = false for a NULL mask, in which every question about a start folds to "no" at compile time -- the
+// code of the kernels before there were chains --, and CH = true, which knows its mask is there and asks without a branch
+// (chains_of below).
 #include "ibdg_kernels.h"
 #include "ibdg_states.h"
 
@@ -69,10 +74,23 @@ __device__ __forceinline__ T join_threads(T (&v)[N], T (*red)[N], uint32_t b, Op
     return r;
 }
 
-__global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__restrict__ win_log2, uint32_t n_win,
-                                                                uint32_t n_targets, Pen P, uint8_t *__restrict__ path,
-                                                                int64_t *__restrict__ score, uint64_t *__restrict__ count)
+// the mask as instantiation CH sees it: a NULL the compiler knows about, or a pointer it may load from without asking
+template <bool CH>
+__device__ __forceinline__ const uint32_t *chains_of(const uint32_t *starts)
 {
+    if (!CH)
+        return nullptr;
+    __builtin_assume(starts != nullptr);
+    return starts;
+}
+
+template <bool CH>
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__restrict__ win_log2, uint32_t n_win,
+                                                                uint32_t n_targets, Pen P, const uint32_t *__restrict__ starts_arg,
+                                                                uint8_t *__restrict__ path, int64_t *__restrict__ score,
+                                                                uint64_t *__restrict__ count)
+{
+    const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
     __shared__ int64_t mat[STATES_THREADS][3][3];   // 18 KB
     __shared__ int64_t vin[STATES_THREADS][3];      // score vector at the end of the block before
     __shared__ uint8_t maps[2][STATES_THREADS];
@@ -95,16 +113,18 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__
         if (own) {
             int64_t r[3][3], e[3];
             states_emission(tab + 3 * (size_t)w0, e);
+            const bool first = b == 0 || chain_start(starts, w0);      // no penalty into the block's first window
 #pragma unroll
             for (int q = 0; q < 3; ++q)
 #pragma unroll
                 for (int s = 0; s < 3; ++s)
-                    r[q][s] = b == 0 ? e[s] : pen[q][s] + e[s];
+                    r[q][s] = first ? e[s] : pen[q][s] + e[s];
             for (uint32_t w = w0 + 1; w < w1; ++w) {
                 states_emission(tab + 3 * (size_t)w, e);
+                const bool st = chain_start(starts, w);
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
-                    (void)states_step(r[q], pen, e);
+                    (void)states_chain_step(r[q], pen, e, st);
             }
 #pragma unroll
             for (int q = 0; q < 3; ++q)
@@ -140,7 +160,7 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__
             }
             for (; w < w1; ++w) {
                 states_emission(tab + 3 * (size_t)w, e);
-                const unsigned f = states_step(v, pen, e);
+                const unsigned f = states_chain_step(v, pen, e, chain_start(starts, w));
                 pt[w] = (uint8_t)f;
                 if (sc)
                     sc[3 * (size_t)w] = v[0], sc[3 * (size_t)w + 1] = v[1], sc[3 * (size_t)w + 2] = v[2];
@@ -174,13 +194,17 @@ struct PenW {
 
 // k_log2_posteriors: the sum-product pass of ibdg_states.h (steps 1 .. 4 are its functions, called per thread with pointers into
 // LDS; step 5 is the tree below), same launch and blocking as k_log2_states.  scr [T][n_win][3] holds beta_w from step 3 to step
-// 4, which overwrites it with gamma_w: the thread that wrote a row is the one that reads it.  out [T][5] = expect[3], Z's
+// 4, which overwrites it with gamma_w: the thread that wrote a row is the one that reads it.  starts: the chains' mask or NULL
+// (PostIn carries it to the steps).  out [T][5] = expect[3], Z's
 // mantissa, Z's exponent (as a double).  The walks of step 2 run in two waves side by side (thread 0 forward, thread 64
 // backward).  No atomics; the same reads as k_log2_states, three times.
+template <bool CH>
 __global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double *__restrict__ win_log2, uint32_t n_win,
                                                                     uint32_t n_targets, PenW W, const double *__restrict__ tables,
+                                                                    const uint32_t *__restrict__ starts_arg,
                                                                     double *__restrict__ scr, double *__restrict__ out)
 {
+    const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
     __shared__ double mat[STATES_THREADS][9];       // 18 KB: B_b
     __shared__ double fin[STATES_THREADS][3];       // F_b
     __shared__ double gout[STATES_THREADS][3];      // G_b
@@ -197,7 +221,7 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double
     __syncthreads();
 
     for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
-        const PostIn in = {win_log2 + (size_t)t * n_win * 3, T, {W.a[0], W.a[1], W.a[2]}};
+        const PostIn in = {win_log2 + (size_t)t * n_win * 3, T, {W.a[0], W.a[1], W.a[2]}, starts};
         // 1
         if (own)
             post_block_matrix(in, w0, w1, mat[b], &mexp[b]);
@@ -234,17 +258,21 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double
 }
 
 // ---- segments (ibdg_states.h): same launch and blocking as the two kernels above -------------------------------
-// A window starts a segment iff its state differs from the window's before it (window 0 always: 3 stands for "no state").
+// A window starts a segment iff its state differs from the window's before it (window 0 always: 3 stands for "no state") or it
+// starts a chain (seg_start; starts: the chains' mask or NULL).
 
 // k_log2_segments_count: out [T][13] = the summary's 12 words, then the individual's number of segments.  path as
 // k_log2_states left it.  Every thread finds the first start among its windows; a suffix minimum over the 256 blocks in LDS gives
 // each the next start behind its block (n_win if none), so a backward walk over its own windows knows where every segment
 // that starts there ends.  Sums and maxima over the threads by join_threads.  No atomics.
+template <bool CH>
 __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_count(const uint8_t *__restrict__ path, uint32_t n_win,
                                                                         uint32_t n_targets, const uint64_t *__restrict__ pos_first,
                                                                         const uint64_t *__restrict__ pos_last,
+                                                                        const uint32_t *__restrict__ starts_arg,
                                                                         uint64_t *__restrict__ out)
 {
+    const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
     __shared__ uint32_t nxt[2][STATES_THREADS];
     __shared__ uint64_t red[STATES_THREADS / 64][12];
 
@@ -260,7 +288,7 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_count(const ui
             unsigned prev = b == 0 ? 3u : pt[w0 - 1];
             for (uint32_t w = w0; w < w1; ++w) {
                 const unsigned s = pt[w];
-                if (s != prev) {
+                if (seg_start(starts, w, prev, s)) {
                     fs = w;
                     break;
                 }
@@ -275,7 +303,7 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_count(const ui
             unsigned s = pt[w1 - 1];
             for (uint32_t w = w1; w-- > w0;) {
                 const unsigned p = w == 0 ? 3u : pt[w - 1];
-                if (p != s) {
+                if (seg_start(starts, w, p, s)) {
                     seg_summary_add(v, s, end - w, pos_first ? pos_last[end - 1] - pos_first[w] + 1 : 0);
                     end = w;
                 }
@@ -300,12 +328,15 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_count(const ui
 // of the blocks' start counts gives every thread the index of its first record.  The owner of a tail then adds the heads of
 // the blocks behind it, up to and with the first one that has a start -- a segment may cover any number of whole blocks --
 // and writes that record.  No atomics: every record has one writer, every head one reader.
+template <bool CH>
 __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_write(const double *__restrict__ win_log2,
                                                                         const uint8_t *__restrict__ path,
                                                                         const double *__restrict__ post, uint32_t n_win,
                                                                         uint32_t n_targets, const uint64_t *__restrict__ off,
+                                                                        const uint32_t *__restrict__ starts_arg,
                                                                         ibdg_segment *__restrict__ seg)
 {
+    const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
     __shared__ SegAcc hd[STATES_THREADS];               // the blocks' heads
     __shared__ uint32_t fst[STATES_THREADS];            // the block's first start, n_win if it has none
     __shared__ uint32_t cnt[2][STATES_THREADS];
@@ -329,7 +360,7 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_write(const do
             unsigned prev = before;
             for (uint32_t w = w0; w < w1; ++w) {
                 const unsigned s = pt[w];
-                if (s != prev) {
+                if (seg_start(starts, w, prev, s)) {
                     fs = ns ? fs : w;
                     ++ns;
                 }
@@ -347,7 +378,7 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_write(const do
             unsigned prev = before;
             for (uint32_t w = w0; w < w1; ++w) {
                 const unsigned s = pt[w];
-                if (s != prev) {
+                if (seg_start(starts, w, prev, s)) {
                     if (start == NONE)
                         hd[b] = a;
                     else
@@ -379,7 +410,7 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_write(const do
 
 // the one launch of all four: nothing for no windows or no individuals, else a workgroup per individual under STATES_MAX_BLOCKS
 template <typename K, typename... A>
-void launch_per_individual(K kernel, uint32_t n_win, uint32_t n_targets, hipStream_t st, A... args)
+void launch_kernel(K kernel, uint32_t n_win, uint32_t n_targets, hipStream_t st, A... args)
 {
     if (n_win == 0 || n_targets == 0)
         return;
@@ -387,31 +418,36 @@ void launch_per_individual(K kernel, uint32_t n_win, uint32_t n_targets, hipStre
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(STATES_THREADS), 0, st, args...);
 }
 
+// ... of the instantiation for this mask (with: CH = true, without: CH = false)
+#define launch_per_individual(kernel, starts, ...) \
+    ((starts) ? launch_kernel(kernel<true>, __VA_ARGS__) : launch_kernel(kernel<false>, __VA_ARGS__))
+
 }  // namespace
 
-void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], uint8_t *path,
-                        int64_t *score, uint64_t *count, hipStream_t st)
+void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], const uint32_t *starts,
+                        uint8_t *path, int64_t *score, uint64_t *count, hipStream_t st)
 {
-    launch_per_individual(k_log2_states, n_win, n_targets, st, win_log2, n_win, n_targets, Pen{P[0], P[1], P[2]}, path, score, count);
+    launch_per_individual(k_log2_states, starts, n_win, n_targets, st, win_log2, n_win, n_targets, Pen{P[0], P[1], P[2]}, starts, path, score,
+                          count);
 }
 
 void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_targets, const double a[3], const double *tables,
-                            double *scr, double *out, hipStream_t st)
+                            const uint32_t *starts, double *scr, double *out, hipStream_t st)
 {
-    launch_per_individual(k_log2_posteriors, n_win, n_targets, st, win_log2, n_win, n_targets, PenW{{a[0], a[1], a[2]}}, tables, scr,
-                          out);
+    launch_per_individual(k_log2_posteriors, starts, n_win, n_targets, st, win_log2, n_win, n_targets, PenW{{a[0], a[1], a[2]}}, tables, starts,
+                          scr, out);
 }
 
 void launch_log2_segments_count(const uint8_t *path, uint32_t n_win, uint32_t n_targets, const uint64_t *pos_first,
-                                const uint64_t *pos_last, uint64_t *out, hipStream_t st)
+                                const uint64_t *pos_last, const uint32_t *starts, uint64_t *out, hipStream_t st)
 {
-    launch_per_individual(k_log2_segments_count, n_win, n_targets, st, path, n_win, n_targets, pos_first, pos_last, out);
+    launch_per_individual(k_log2_segments_count, starts, n_win, n_targets, st, path, n_win, n_targets, pos_first, pos_last, starts, out);
 }
 
 void launch_log2_segments_write(const double *win_log2, const uint8_t *path, const double *post, uint32_t n_win, uint32_t n_targets,
-                                const uint64_t *off, ibdg_segment *seg, hipStream_t st)
+                                const uint64_t *off, const uint32_t *starts, ibdg_segment *seg, hipStream_t st)
 {
-    launch_per_individual(k_log2_segments_write, n_win, n_targets, st, win_log2, path, post, n_win, n_targets, off, seg);
+    launch_per_individual(k_log2_segments_write, starts, n_win, n_targets, st, win_log2, path, post, n_win, n_targets, off, starts, seg);
 }
 
 }  // namespace ibdg

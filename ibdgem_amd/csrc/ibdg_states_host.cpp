@@ -43,9 +43,44 @@ static int check_log_args(const char *fn, const char *own, const double *tab, si
     return 1;
 }
 
-// The cores take checked arguments and check nothing.
+int chain_mask(const char *fn, const uint32_t *starts, size_t n_starts, size_t n_win, uint32_t *mask, char *err, size_t err_len)
+{
+    if (n_starts && !starts) {
+        snprintf(err, err_len, "[::] ERROR in %s: NULL starts with n_starts = %zu", fn, n_starts);
+        return 1;
+    }
+    for (size_t i = 0; i < n_starts; ++i) {
+        if (starts[i] == 0)
+            snprintf(err, err_len, "[::] ERROR in %s: starts[%zu] = 0 (window 0 always starts a chain; the entries are 1 .. n_win - 1)", fn, i);
+        else if (starts[i] >= n_win)
+            snprintf(err, err_len, "[::] ERROR in %s: starts[%zu] = %u is not below the %zu windows", fn, i, starts[i], n_win);
+        else if (i && starts[i] <= starts[i - 1])
+            snprintf(err, err_len, "[::] ERROR in %s: starts[%zu] = %u does not lie above starts[%zu] = %u (strictly increasing)", fn, i,
+                     starts[i], i - 1, starts[i - 1]);
+        else
+            continue;
+        return 1;
+    }
+    for (size_t i = 0; n_starts && i < (n_win + 31) / 32; ++i)
+        mask[i] = 0;
+    for (size_t i = 0; i < n_starts; ++i)
+        mask[starts[i] >> 5] |= 1u << (starts[i] & 31);
+    return 0;
+}
+
+// chain_mask into a vector of the twins' own; *mask: its words, or NULL for no starts
+static int own_mask(const char *fn, const uint32_t *starts, size_t n_starts, size_t n_win, std::vector<uint32_t> &own,
+                    const uint32_t **mask, char *err, size_t err_len)
+{
+    own.resize(n_starts ? (n_win + 31) / 32 : 0);
+    *mask = n_starts ? own.data() : nullptr;
+    return chain_mask(fn, starts, n_starts, n_win, own.data(), err, err_len);
+}
+
+// The cores take checked arguments and check nothing.  mask: the chain starts' bits (chain_start), or NULL.
 // The states recurrence: path [n_win] or NULL, score [n_win][3] or NULL, count[3]
-static void states_core(const double *tab, size_t n_win, const int64_t P[3], uint8_t *path, int64_t *score, uint64_t count[3])
+static void states_core(const double *tab, size_t n_win, const int64_t P[3], const uint32_t *mask, uint8_t *path, int64_t *score,
+                        uint64_t count[3])
 {
     count[0] = count[1] = count[2] = 0;
     if (n_win == 0)
@@ -59,7 +94,7 @@ static void states_core(const double *tab, size_t n_win, const int64_t P[3], uin
         score[0] = v[0], score[1] = v[1], score[2] = v[2];
     for (size_t i = 1; i < n_win; ++i) {
         states_emission(tab + 3 * i, e);
-        from[i] = (uint8_t)states_step(v, pen, e);
+        from[i] = (uint8_t)states_chain_step(v, pen, e, chain_start(mask, (uint32_t)i));
         if (score)
             score[3 * i] = v[0], score[3 * i + 1] = v[1], score[3 * i + 2] = v[2];
     }
@@ -73,14 +108,16 @@ static void states_core(const double *tab, size_t n_win, const int64_t P[3], uin
 }
 
 // err: room for a message
-int log2_states_host(const double *tab, size_t n_win, double p01, double p02, double p12, uint8_t *path, int64_t *score,
-                     uint64_t count[3], char *err, size_t err_len)
+int log2_states_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                     size_t n_starts, uint8_t *path, int64_t *score, uint64_t count[3], char *err, size_t err_len)
 {
     int64_t P[3];
-    if (check_log_args("ibdg_log2_states_host", count ? nullptr : "count", tab, n_win, p01, p02, p12, "the integer scores allow", P,
-                       err, err_len))
+    std::vector<uint32_t> own;
+    const uint32_t *mask;
+    if (check_log_args(fn, count ? nullptr : "count", tab, n_win, p01, p02, p12, "the integer scores allow", P, err, err_len) ||
+        own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len))
         return 1;
-    states_core(tab, n_win, P, path, score, count);
+    states_core(tab, n_win, P, mask, path, score, count);
     return 0;
 }
 
@@ -108,14 +145,14 @@ void post_penalty_weights(const int64_t P[3], double a[3])
 
 // The sum-product pass: steps 1 .. 4 are the functions of ibdg_states.h that the kernel's threads call, here in loops over b; step
 // 5 is the same tree, serial.  post [n_win][3] or NULL.
-static void posteriors_core(const double *tab, size_t n_win, const int64_t P[3], double *post, double expect[3], double *z_mant,
-                            int *z_exp)
+static void posteriors_core(const double *tab, size_t n_win, const int64_t P[3], const uint32_t *mask, double *post,
+                            double expect[3], double *z_mant, int *z_exp)
 {
     expect[0] = expect[1] = expect[2] = 0.0;
     *z_mant = 1.0, *z_exp = 0;
     if (n_win == 0)
         return;
-    PostIn in = {tab, post_tables(), {}};
+    PostIn in = {tab, post_tables(), {}, mask};
     post_penalty_weights(P, in.a);
     std::vector<double> own;
     if (!post) {
@@ -143,22 +180,25 @@ static void posteriors_core(const double *tab, size_t n_win, const int64_t P[3],
     expect[0] = part[0][0], expect[1] = part[0][1], expect[2] = part[0][2];
 }
 
-int log2_posteriors_host(const double *tab, size_t n_win, double p01, double p02, double p12, double *post, double expect[3],
-                         double *z_mant, int *z_exp, char *err, size_t err_len)
+int log2_posteriors_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                         size_t n_starts, double *post, double expect[3], double *z_mant, int *z_exp, char *err, size_t err_len)
 {
     int64_t P[3];
-    if (check_log_args("ibdg_log2_posteriors_host", !expect ? "expect" : !z_mant || !z_exp ? "log2_z" : nullptr, tab, n_win, p01, p02,
-                       p12, "of the path", P, err, err_len))
+    std::vector<uint32_t> own;
+    const uint32_t *mask;
+    if (check_log_args(fn, !expect ? "expect" : !z_mant || !z_exp ? "log2_z" : nullptr, tab, n_win, p01, p02, p12, "of the path", P,
+                       err, err_len) ||
+        own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len))
         return 1;
-    posteriors_core(tab, n_win, P, post, expect, z_mant, z_exp);
+    posteriors_core(tab, n_win, P, mask, post, expect, z_mant, z_exp);
     return 0;
 }
 
 // The segment walk: one pass over the path in window order with the kernels' accumulator and summary functions (ibdg_states.h:
 // every quantity is exact and associative, so this is the kernels' result whatever their blocks).  post: the gammas [n_win][3],
 // or NULL for no support.
-static void segments_core(const double *tab, size_t n_win, const uint8_t *path, const double *post, const uint64_t *pos_first,
-                          const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg, uint64_t summary[12])
+static void segments_core(const double *tab, size_t n_win, const uint8_t *path, const uint32_t *mask, const double *post,
+                          const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg, uint64_t summary[12])
 {
     *n_seg = 0;
     for (int i = 0; i < 12; ++i)
@@ -168,7 +208,7 @@ static void segments_core(const double *tab, size_t n_win, const uint8_t *path, 
         SegAcc a;
         seg_reset(a);
         size_t w = f;
-        for (; w < n_win && path[w] == s; ++w)
+        for (; w < n_win && (w == f || !seg_start(mask, (uint32_t)w, s, path[w])); ++w)
             seg_add_window(a, tab + 3 * w, post ? post + 3 * w : nullptr, s);
         if (seg && *n_seg < seg_cap)
             seg_record(seg + *n_seg, (uint32_t)f, (uint32_t)(w - f), s, a, post != nullptr);
@@ -179,17 +219,19 @@ static void segments_core(const double *tab, size_t n_win, const uint8_t *path, 
 }
 
 // (the table and the penalties are refused in the words of ibdg_log2_states_host, whose checks they are)
-int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, double p12, int with_post, const uint64_t *pos_first,
-                       const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err,
-                       size_t err_len)
+int log2_segments_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                       size_t n_starts, int with_post, const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg,
+                       size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err, size_t err_len)
 {
     int64_t P[3];
+    std::vector<uint32_t> own;
+    const uint32_t *mask;
     if (!n_seg || !summary) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: NULL %s", n_seg ? "summary" : "n_seg");
+        snprintf(err, err_len, "[::] ERROR in %s: NULL %s", fn, n_seg ? "summary" : "n_seg");
         return 1;
     }
     if (!pos_first != !pos_last) {
-        snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: %s without %s", pos_first ? "pos_first" : "pos_last",
+        snprintf(err, err_len, "[::] ERROR in %s: %s without %s", fn, pos_first ? "pos_first" : "pos_last",
                  pos_first ? "pos_last" : "pos_first");
         return 1;
     }
@@ -197,19 +239,21 @@ int log2_segments_host(const double *tab, size_t n_win, double p01, double p02, 
         return 1;
     for (size_t w = 0; pos_first && w < n_win; ++w)
         if (pos_last[w] < pos_first[w]) {
-            snprintf(err, err_len, "[::] ERROR in ibdg_log2_segments_host: window %zu ends at %llu, before its start %llu", w,
+            snprintf(err, err_len, "[::] ERROR in %s: window %zu ends at %llu, before its start %llu", fn, w,
                      (unsigned long long)pos_last[w], (unsigned long long)pos_first[w]);
             return 1;
         }
+    if (own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len))
+        return 1;
     std::vector<uint8_t> path(n_win);
     std::vector<double> post(with_post ? n_win * 3 : 0);
     uint64_t count[3];
     double expect[3], zm;
     int ze;
-    states_core(tab, n_win, P, path.data(), nullptr, count);
+    states_core(tab, n_win, P, mask, path.data(), nullptr, count);
     if (with_post)
-        posteriors_core(tab, n_win, P, post.data(), expect, &zm, &ze);
-    segments_core(tab, n_win, path.data(), with_post ? post.data() : nullptr, pos_first, pos_last, seg, seg_cap, n_seg, summary);
+        posteriors_core(tab, n_win, P, mask, post.data(), expect, &zm, &ze);
+    segments_core(tab, n_win, path.data(), mask, with_post ? post.data() : nullptr, pos_first, pos_last, seg, seg_cap, n_seg, summary);
     return 0;
 }
 

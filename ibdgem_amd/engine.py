@@ -59,6 +59,13 @@ SYMBOLS = {
                                           _P, _P]),
     "ibdg_window_log2_segments": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P]),
     "ibdg_get_log2_segments": (C.c_int, [_P, _P, C.c_size_t]),
+    "ibdg_log2_states_chains_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, C.c_size_t]),
+    "ibdg_log2_posteriors_chains_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
+                                                   C.c_size_t]),
+    "ibdg_log2_segments_chains_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P,
+                                                 C.c_size_t, _P, _P, _P, C.c_size_t]),
+    "ibdg_set_window_chains": (C.c_int, [_P, _P, C.c_size_t]),
+    "ibdg_num_window_chains": (C.c_size_t, [_P]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
     "ibdg_run_ms": (C.c_int, [_P, C.c_uint, _P]),
@@ -155,33 +162,52 @@ def pack_alleles_fast(alleles):
     return np.ascontiguousarray(by).view("<u8").reshape(L, chunks * 2)
 
 
-def log2_states_host(log2_tab, p01, p02, p12, want_path=True, want_score=True):
+def _starts(starts):
+    """The chain starts as the library takes them: (contiguous uint32 array kept alive by the caller, pointer or None, count).
+    The entries go as they are: the library checks them."""
+    a = np.ascontiguousarray(starts, dtype=np.uint32).reshape(-1)
+    return a, (a.ctypes.data if len(a) else None), len(a)
+
+
+def log2_states_host(log2_tab, p01, p02, p12, want_path=True, want_score=True, starts=None):
     """The integer log-domain IBD-state path of one window table [n_win][3] on the host (ibdg_log2_states_host):
-    (path uint8 [n_win] or None, score int64 [n_win][3] or None, count uint64 [3])."""
+    (path uint8 [n_win] or None, score int64 [n_win][3] or None, count uint64 [3]).  starts: the windows >= 1 that start a chain
+    (ibdg_log2_states_chains_host); None: the call without chains."""
     lib = load_library()
     tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
     n = tab.shape[0]
     path = np.zeros(n, dtype=np.uint8) if want_path else None
     score = np.zeros((n, 3), dtype=np.int64) if want_score else None
     count = np.zeros(3, dtype=np.uint64)
-    rc = lib.ibdg_log2_states_host(tab.ctypes.data, n, p01, p02, p12, None if path is None else path.ctypes.data,
-                                   None if score is None else score.ctypes.data, count.ctypes.data)
+    args = (tab.ctypes.data, n, p01, p02, p12, None if path is None else path.ctypes.data,
+            None if score is None else score.ctypes.data, count.ctypes.data)
+    if starts is None:
+        rc = lib.ibdg_log2_states_host(*args)
+    else:
+        keep, ptr, ns = _starts(starts)
+        rc = lib.ibdg_log2_states_chains_host(*args, ptr, ns)
     if rc != 0:
         raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
     return path, score, count
 
 
-def log2_posteriors_host(log2_tab, p01, p02, p12, want_post=True):
+def log2_posteriors_host(log2_tab, p01, p02, p12, want_post=True, starts=None):
     """Forward-backward IBD-state probabilities of one window table [n_win][3] on the host (ibdg_log2_posteriors_host):
-    (post float64 [n_win][3] or None, expect float64 [3], log2_z float)."""
+    (post float64 [n_win][3] or None, expect float64 [3], log2_z float).  starts: as for log2_states_host
+    (ibdg_log2_posteriors_chains_host)."""
     lib = load_library()
     tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
     n = tab.shape[0]
     post = np.zeros((n, 3), dtype=np.float64) if want_post else None
     expect = np.zeros(3, dtype=np.float64)
     log2_z = C.c_double(0.0)
-    rc = lib.ibdg_log2_posteriors_host(tab.ctypes.data, n, p01, p02, p12, None if post is None else post.ctypes.data,
-                                       expect.ctypes.data, C.addressof(log2_z))
+    args = (tab.ctypes.data, n, p01, p02, p12, None if post is None else post.ctypes.data, expect.ctypes.data,
+            C.addressof(log2_z))
+    if starts is None:
+        rc = lib.ibdg_log2_posteriors_host(*args)
+    else:
+        keep, ptr, ns = _starts(starts)
+        rc = lib.ibdg_log2_posteriors_chains_host(*args, ptr, ns)
     if rc != 0:
         raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
     return post, expect, log2_z.value
@@ -205,9 +231,11 @@ def _positions(pos_first, pos_last, n):
     return out
 
 
-def log2_segments_host(log2_tab, p01, p02, p12, with_post=False, pos_first=None, pos_last=None, seg_cap=None, want_seg=True):
+def log2_segments_host(log2_tab, p01, p02, p12, with_post=False, pos_first=None, pos_last=None, seg_cap=None, want_seg=True,
+                       starts=None):
     """The segments of one window table's path on the host (ibdg_log2_segments_host): (seg structured array of
-    SEGMENT_DTYPE -- min(n_seg, seg_cap) records, all of them with seg_cap None -- or None, n_seg int, summary uint64 [12])."""
+    SEGMENT_DTYPE -- min(n_seg, seg_cap) records, all of them with seg_cap None -- or None, n_seg int, summary uint64 [12]).
+    starts: as for log2_states_host (ibdg_log2_segments_chains_host)."""
     lib = load_library()
     tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
     n = tab.shape[0]
@@ -218,9 +246,14 @@ def log2_segments_host(log2_tab, p01, p02, p12, with_post=False, pos_first=None,
         seg[cap]["first"] = 0xffffffff
     n_seg = C.c_uint64(0)
     summary = np.zeros(12, dtype=np.uint64)
-    rc = lib.ibdg_log2_segments_host(tab.ctypes.data, n, p01, p02, p12, int(bool(with_post)),
-                                     None if pf is None else pf.ctypes.data, None if pl is None else pl.ctypes.data,
-                                     None if seg is None else seg.ctypes.data, cap, C.addressof(n_seg), summary.ctypes.data)
+    args = (tab.ctypes.data, n, p01, p02, p12, int(bool(with_post)), None if pf is None else pf.ctypes.data,
+            None if pl is None else pl.ctypes.data, None if seg is None else seg.ctypes.data, cap, C.addressof(n_seg),
+            summary.ctypes.data)
+    if starts is None:
+        rc = lib.ibdg_log2_segments_host(*args)
+    else:
+        keep, ptr, ns = _starts(starts)
+        rc = lib.ibdg_log2_segments_chains_host(*args, ptr, ns)
     if rc != 0:
         raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
     if seg is not None:
@@ -460,6 +493,17 @@ class Engine:
         seg = np.zeros(max(cap, 1), dtype=SEGMENT_DTYPE)
         self._chk(self.lib.ibdg_get_log2_segments(self.ctx, seg.ctypes.data, cap))
         return seg[:cap]
+
+    def set_window_chains(self, starts=()):
+        """The windows >= 1 of the current site list that start a chain, for the three window_log2_* calls and
+        get_log2_segments (ibdg_set_window_chains); none clears them.  A new site list or panel clears them too."""
+        keep, ptr, ns = _starts(starts)
+        self._chk(self.lib.ibdg_set_window_chains(self.ctx, ptr, ns))
+
+    @property
+    def n_window_chains(self):
+        """The number of chains of the current site list (ibdg_num_window_chains): the starts set plus one; 0 without windows."""
+        return self.lib.ibdg_num_window_chains(self.ctx)
 
     def alt_counts(self, first, n):
         out = np.empty(n, dtype=np.uint32)

@@ -66,6 +66,8 @@ static int opt_stats_only = 0, has_arm = 0;
 static int opt_log_summary = 0;          /* --log-summary: the summary's likelihoods as log2, from the engine's option "log_windows" */
 static int opt_posteriors = 0;           /* --posteriors: with --log-stats --states, the forward-backward probabilities of the states beside the path */
 static int opt_segments = 0;             /* --segments: with --log-stats --states, the path's segments with their scores and support */
+static int has_chain_gap = 0;            /* --chain-gap BP: with --log-stats --states, a window more than BP behind the end of the one before starts a chain */
+static unsigned long opt_chain_gap = 0;
 static int opt_log_stats = 0;            /* --log-stats: --arm-stats and --states from the log2 window table (no underflow), into log* files */
 static int opt_states = 0, has_pen = 0;  /* --states: the IBD-state path of every comparison (hgpath.c), --p01/--p02/--p12 its penalties */
 static double opt_p01 = HG_DEFAULT_P01, opt_p02 = HG_DEFAULT_P02, opt_p12 = HG_DEFAULT_P12;
@@ -82,6 +84,7 @@ static struct option longopts[] = {
     {"log-stats", no_argument, &opt_log_stats, 1},
     {"posteriors", no_argument, &opt_posteriors, 1},
     {"segments", no_argument, &opt_segments, 1},
+    {"chain-gap", required_argument, 0, 1011},
     {"p01", required_argument, 0, 1008},
     {"p02", required_argument, 0, 1009},
     {"p12", required_argument, 0, 1010},
@@ -193,6 +196,12 @@ static void usage(int code)
           "                            <out>/<pileup-name>.logibdsegments.txt, per individual and state the number of\n"
           "                            segments, the windows of the longest, the base pairs of all and of the longest, then\n"
           "                            the totals.  With --stats-only only the second file, on one device computed there\n"
+          "  --chain-gap BP            with --log-stats --states: break the chain of windows wherever a window's START lies more\n"
+          "                            than BP (an integer >= 1) behind the END of the window before it -- a centromere, a\n"
+          "                            stretch without sites.  Such a window is entered like the first one: no switch penalty\n"
+          "                            into it, and no segment (hence no base pair of a length) crosses the gap; the chains'\n"
+          "                            paths, posteriors and segments are independent.  A gap inside a window breaks nothing.\n"
+          "                            The files keep their formats; *.logsegments.txt gains a first column Chain (1-based)\n"
           "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
           "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
           "  --stats-only              with --arm-stats and/or --states: write the armstats / ibdstates file only (no\n"
@@ -1726,6 +1735,19 @@ static int win_table_alloc_ll(win_table *t)
     return t->ll && (t->log || !want_logs());
 }
 
+/* --chain-gap BP, for every route: window w >= 1 starts a chain iff its first position lies more than BP behind the last
+ * position of window w - 1 (the START and END the summary prints); a gap inside a window starts nothing.  starts: room for n
+ * entries; returns how many there are (strictly increasing, in [1, n): what ibdg_set_window_chains and the _chains_host twins
+ * take).  Without the option: none. */
+static size_t chain_gap_starts(const uint64_t *pos_first, const uint64_t *pos_last, size_t n, uint32_t *starts)
+{
+    size_t k = 0;
+    for (size_t w = 1; has_chain_gap && w < n; ++w)
+        if (pos_first[w] > pos_last[w - 1] && pos_first[w] - pos_last[w - 1] > opt_chain_gap)
+            starts[k++] = (uint32_t)w;
+    return k;
+}
+
 /* ---- one comparison spread over several GPUs (window ranges, host-side gather) ------------ */
 /* What the run's statistics files hold of one comparison individual, the same record from the device (or the individual's
  * output job) to the files: a shard's double-double arm sums (ibdg_window_llr_sums), of which the run keeps the four rounded
@@ -1789,7 +1811,8 @@ typedef struct {
     double *po_vals;                         /* --posteriors: expect [T][3], then log2 Z [T] */
     uint64_t *sg_vals;                       /* --segments: summary [T][12], then the counts [T] */
     uint64_t *sg_pos;                        /* ... the windows' first positions [n_win], then their last */
-    size_t arm_cap, st_cap, po_cap, sg_cap, sg_pos_cap;
+    uint32_t *ch_starts;                     /* --chain-gap: the chain starts of the list at hand */
+    size_t arm_cap, st_cap, po_cap, sg_cap, sg_pos_cap, ch_cap;
 } dev_conv;
 
 /* one comparison individual on one context: where it stands and what comes back for it */
@@ -1837,7 +1860,7 @@ static void conv_release(dev_conv *c)
         ibdg_host_free(c->stage);
     if (c->batch_ll)
         ibdg_host_free(c->batch_ll);
-    free(c->batch_log); free(c->arm_sums); free(c->st_counts); free(c->po_vals); free(c->sg_vals); free(c->sg_pos);
+    free(c->batch_log); free(c->arm_sums); free(c->st_counts); free(c->po_vals); free(c->sg_vals); free(c->sg_pos); free(c->ch_starts);
     memset(c, 0, sizeof *c);
 }
 
@@ -1865,19 +1888,43 @@ static const win_list *conv_windows(dev_conv *c, size_t n_win)
     return &c->wl;
 }
 
-/* --segments where the tables stay on the device: the list's windows' positions go up with the call */
-static int segments_on_device(dev_conv *c)
+/* the positions of the windows of the list at hand in c->sg_pos: the first [n_win], then the last */
+static int conv_positions(dev_conv *c, size_t n_win)
 {
-    const size_t n_win = ibdg_num_windows(c->eng), T = c->n_targets;
     const win_list *wl = conv_windows(c, n_win);
     if (!wl)
         return 1;
-    if (!grow(&c->sg_pos, &c->sg_pos_cap, 2 * n_win + 1, sizeof(uint64_t)) || !grow(&c->sg_vals, &c->sg_cap, T * 13, sizeof(uint64_t)))
+    if (!grow(&c->sg_pos, &c->sg_pos_cap, 2 * n_win + 1, sizeof(uint64_t)))
         return conv_oom(c, n_win);
     for (size_t w = 0; w < n_win; ++w) {
         c->sg_pos[w] = rows[c->s_row[c->a + wl->first[w]]].pos;
         c->sg_pos[n_win + w] = rows[c->s_row[c->a + wl->last[w]]].pos;
     }
+    return 0;
+}
+
+/* --chain-gap where the paths are found on the device: the chain starts of a new site list go to the engine once, which keeps
+ * them for every run over the list */
+static int chains_on_device(dev_conv *c)
+{
+    if (!has_chain_gap || !c->dev_states)
+        return 0;
+    const size_t n_win = ibdg_num_windows(c->eng);
+    if (conv_positions(c, n_win))
+        return 1;
+    if (!grow(&c->ch_starts, &c->ch_cap, n_win + 1, sizeof(uint32_t)))
+        return conv_oom(c, n_win);
+    return ibdg_set_window_chains(c->eng, c->ch_starts, chain_gap_starts(c->sg_pos, c->sg_pos + n_win, n_win, c->ch_starts));
+}
+
+/* --segments where the tables stay on the device: the list's windows' positions go up with the call */
+static int segments_on_device(dev_conv *c)
+{
+    const size_t n_win = ibdg_num_windows(c->eng), T = c->n_targets;
+    if (conv_positions(c, n_win))
+        return 1;
+    if (!grow(&c->sg_vals, &c->sg_cap, T * 13, sizeof(uint64_t)))
+        return conv_oom(c, n_win);
     return ibdg_window_log2_segments(c->eng, opt_p01, opt_p02, opt_p12, opt_posteriors, c->sg_pos, c->sg_pos + n_win,
                                      c->sg_vals + T * 12, c->sg_vals);
 }
@@ -1939,8 +1986,10 @@ static int conv_list(dev_conv *c)
 {
     c->wl_kept = 0;
     c->batch_of = NULL;
-    return !c->list_on_device && ibdg_upload_sites(c->eng, c->row + c->a, c->nr + c->a, c->na + c->a, c->fo ? c->fo + c->a : NULL,
-                                                   c->b - c->a, (unsigned)opt_window);
+    if (!c->list_on_device && ibdg_upload_sites(c->eng, c->row + c->a, c->nr + c->a, c->na + c->a, c->fo ? c->fo + c->a : NULL,
+                                                c->b - c->a, (unsigned)opt_window))
+        return 1;
+    return chains_on_device(c);
 }
 
 /* the next batch runs while the host goes on with this one's statistics and files */
@@ -2562,16 +2611,25 @@ static int out_close(FILE **f)
     return bad;
 }
 
-/* --posteriors: the sum-product pass over the same table (ibdg_log2_posteriors_host: the same bytes as the device's
+/* what the three passes over an individual's log2 table share: the positions of its windows (first [n], then last; for
+ * --segments and --chain-gap, else NULL) and its chain starts (--chain-gap; none without it) */
+typedef struct {
+    uint64_t *pos;
+    uint32_t *starts;
+    size_t n_starts;
+} log_chains;
+
+/* --posteriors: the sum-product pass over the same table (ibdg_log2_posteriors_chains_host: the same bytes as the device's
  * ibdg_window_log2_posteriors) */
-static int posteriors_individual(out_job *o)
+static int posteriors_individual(out_job *o, const log_chains *lc)
 {
     if (!opt_posteriors)
         return 0;
     const size_t n = o->wt.w.n_win;
     double *post = o->lp ? malloc((n ? n : 1) * 3 * sizeof *post) : NULL;
     int bad = o->lp && !post;
-    if (!bad && ibdg_log2_posteriors_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, post, o->res->po, o->res->po + 3)) {
+    if (!bad && ibdg_log2_posteriors_chains_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, post, o->res->po, o->res->po + 3, lc->starts,
+                                                 lc->n_starts)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
@@ -2589,29 +2647,29 @@ static int posteriors_individual(out_job *o)
     return bad;
 }
 
-/* --segments: the path's segments over the same table (ibdg_log2_segments_host: the same bytes as the device's
- * ibdg_window_log2_segments), with the positions and site counts of the individual's summary */
+/* --segments: the path's segments over the same table (ibdg_log2_segments_chains_host: the same bytes as the device's
+ * ibdg_window_log2_segments), with the positions and site counts of the individual's summary; with --chain-gap a first column
+ * Chain (1-based), counted along lc->starts */
 static const char log_seg_header[] = "Segment\tState\tFirst_Window\tLast_Window\tStart\tEnd\tLength\tNum_Windows\tNum_Sites\t"
                                      "IBD0_LogSum\tIBD1_LogSum\tIBD2_LogSum\tLog2_LR";
 
-static int segments_individual(out_job *o)
+static int segments_individual(out_job *o, const log_chains *lc)
 {
     if (!opt_segments)
         return 0;
     const size_t n = o->wt.w.n_win;
-    uint64_t *pos = malloc((2 * n + 1) * sizeof *pos), n_seg = 0;
+    const uint64_t *pos = lc->pos;
+    uint64_t n_seg = 0;
     ibdg_segment *seg = o->ls ? malloc((n ? n : 1) * sizeof *seg) : NULL;
-    int bad = !pos || (o->ls && !seg);
-    for (size_t w = 0; w < n && !bad; ++w) {
-        pos[w] = o->pos_first ? o->pos_first[w] : rows[o->s_row[o->wt.w.first[w]]].pos;
-        pos[n + w] = o->pos_last ? o->pos_last[w] : rows[o->s_row[o->wt.w.last[w]]].pos;
-    }
-    if (!bad && ibdg_log2_segments_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, opt_posteriors, pos, pos + n, seg, n, &n_seg, o->res->sg)) {
+    int bad = o->ls && !seg;
+    if (!bad && ibdg_log2_segments_chains_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, opt_posteriors, pos, pos + n, seg, n, &n_seg,
+                                               o->res->sg, lc->starts, lc->n_starts)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
     if (!bad && o->ls) {
-        bad = fprintf(o->ls, "%s%s\n", log_seg_header, opt_posteriors ? "\tPost_Mean\tPost_Min" : "") < 0;
+        size_t chain = 0;                        /* the starts at or before the segment at hand */
+        bad = fprintf(o->ls, "%s%s%s\n", has_chain_gap ? "Chain\t" : "", log_seg_header, opt_posteriors ? "\tPost_Mean\tPost_Min" : "") < 0;
         for (size_t k = 0; k < n_seg && !bad; ++k) {
             const ibdg_segment *g = &seg[k];
             const size_t f = g->first, l = f + g->n_win - 1;
@@ -2619,7 +2677,10 @@ static int segments_individual(out_job *o)
             unsigned long sites = 0;
             for (size_t w = f; w <= l; ++w)
                 sites += o->wt.w.ncov[w];
-            bad = fprintf(o->ls, "%zu\t%u\t%zu\t%zu\t%llu\t%llu\t%llu\t%u\t%lu\t%.4Lf\t%.4Lf\t%.4Lf\t%.4Lf", k + 1, g->state, f + 1,
+            while (chain < lc->n_starts && lc->starts[chain] <= f)
+                ++chain;
+            bad = has_chain_gap && fprintf(o->ls, "%zu\t", chain + 1) < 0;
+            bad = bad || fprintf(o->ls, "%zu\t%u\t%zu\t%zu\t%llu\t%llu\t%llu\t%u\t%lu\t%.4Lf\t%.4Lf\t%.4Lf\t%.4Lf", k + 1, g->state, f + 1,
                           l + 1, (unsigned long long)pos[f], (unsigned long long)pos[n + l],
                           (unsigned long long)(pos[n + l] - pos[f] + 1), g->n_win, sites, (long double)g->e[0] / 65536,
                           (long double)g->e[1] / 65536, (long double)g->e[2] / 65536,
@@ -2630,7 +2691,6 @@ static int segments_individual(out_job *o)
         }
     }
     bad = out_close(&o->ls) || bad;
-    free(pos);
     free(seg);
     return bad;
 }
@@ -2641,8 +2701,16 @@ static int log_states_individual(out_job *o)
     uint64_t *const count = o->res->st;
     uint8_t *path = o->hg ? malloc(n ? n : 1) : NULL;
     int64_t *score = o->hg ? malloc((n ? n : 1) * 3 * sizeof *score) : NULL;
-    int bad = o->hg && (!path || !score);
-    if (!bad && ibdg_log2_states_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, path, score, count)) {
+    const int want_pos = opt_segments || has_chain_gap;
+    log_chains lc = {want_pos ? malloc((2 * n + 1) * sizeof *lc.pos) : NULL, has_chain_gap ? malloc((n + 1) * sizeof *lc.starts) : NULL, 0};
+    int bad = (o->hg && (!path || !score)) || (want_pos && !lc.pos) || (has_chain_gap && !lc.starts);
+    for (size_t w = 0; w < n && want_pos && !bad; ++w) {
+        lc.pos[w] = o->pos_first ? o->pos_first[w] : rows[o->s_row[o->wt.w.first[w]]].pos;
+        lc.pos[n + w] = o->pos_last ? o->pos_last[w] : rows[o->s_row[o->wt.w.last[w]]].pos;
+    }
+    if (!bad && has_chain_gap)
+        lc.n_starts = chain_gap_starts(lc.pos, lc.pos + n, n, lc.starts);
+    if (!bad && ibdg_log2_states_chains_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, path, score, count, lc.starts, lc.n_starts)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
@@ -2658,8 +2726,16 @@ static int log_states_individual(out_job *o)
     bad = out_close(&o->hg) || bad;
     free(path);
     free(score);
-    bad = posteriors_individual(o) || bad;
-    return segments_individual(o) || bad;
+    if ((want_pos && !lc.pos) || (has_chain_gap && !lc.starts)) {    /* (out of memory: the other two files are closed as they are) */
+        out_close(&o->lp);
+        out_close(&o->ls);
+    } else {
+        bad = posteriors_individual(o, &lc) || bad;
+        bad = segments_individual(o, &lc) || bad;
+    }
+    free(lc.pos);
+    free(lc.starts);
+    return bad;
 }
 
 /* 0: the path is found, counted for ibdstates.txt and (o->hg) written and its file closed */
@@ -3966,6 +4042,17 @@ int main(int argc, char **argv)
         case 1008: opt_p01 = atof(optarg); has_pen = 1; break;
         case 1009: opt_p02 = atof(optarg); has_pen = 1; break;
         case 1010: opt_p12 = atof(optarg); has_pen = 1; break;
+        case 1011: {
+            char *end = NULL;
+            errno = 0;
+            opt_chain_gap = strtoul(optarg, &end, 10);
+            if (!isdigit((unsigned char)optarg[0]) || *end || errno || opt_chain_gap < 1) {
+                fprintf(stderr, "[::] ERROR: Invalid chain gap (--chain-gap) '%s' (must be an integer >= 1, in base pairs).\n", optarg);
+                exit(1);
+            }
+            has_chain_gap = 1;
+            break;
+        }
         case 1006:
             if (!parse_arm_range(optarg)) {
                 fprintf(stderr, "[::] ERROR: Invalid centromeric range (--arm-stats) '%s' (must be START,END with START <= END).\n", optarg);
@@ -4010,6 +4097,8 @@ int main(int argc, char **argv)
     if (opt_posteriors && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --posteriors needs --log-stats and --states: it is the sum over all paths of the weights whose best path they find, with their --p01, --p02, --p12.\n"); exit(1); }
     if (opt_segments && opt_plan) { fprintf(stderr, "[::] ERROR: --segments writes files --plan does not make; use one of them.\n"); exit(1); }
     if (opt_segments && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --segments needs --log-stats and --states: it cuts the path they find into its runs of one state and sums that path's own emissions over each.\n"); exit(1); }
+    if (has_chain_gap && opt_plan) { fprintf(stderr, "[::] ERROR: --chain-gap changes files --plan does not make; use one of them.\n"); exit(1); }
+    if (has_chain_gap && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --chain-gap needs --log-stats and --states: it says where the chain of windows whose path they find is broken.\n"); exit(1); }
     if (opt_log_stats && opt_states) {
         const double pen[3] = {opt_p01, opt_p02, opt_p12};
         static const char *const pen_name[3] = {"--p01", "--p02", "--p12"};

@@ -308,6 +308,33 @@ int ibdg_window_log2_segments(ibdg_ctx *ctx, double p01, double p02, double p12,
  * for.  Errors: no ibdg_window_log2_segments since the last ibdg_run (or since a later ibdg_window_log2_states /
  * ibdg_window_log2_posteriors call, which reuse its paths), cap smaller than the sum of n_seg, NULL seg with a sum > 0. */
 int ibdg_get_log2_segments(ibdg_ctx *ctx, ibdg_segment *seg, size_t cap);
+/* Window chains: the three log-domain calls above treat the windows as one chain; a chain start is a window that is
+ * treated the way window 0 is -- uniform entry, no switch penalty into it.  starts[n_starts]: the windows >= 1 that start a chain,
+ * strictly increasing, every entry in [1, n_win); window 0 always starts one.  At a start the path's step takes every penalty as 0
+ * (score[w][s] = max_q score[w-1][q] + e_w[s]; the scores are not reset), the posteriors' step matrix is M_w[q][s] = b_w[s], and a
+ * segment begins whatever the state before.  The chains are then independent: inside chain [c0, c1) the path, the posteriors and
+ * the segments are those of the table's rows [c0, c1) alone (the scores are the slice's plus max_q score[c0-1][q]; the
+ * posteriors within the rounding of the joint pass), counts and expect are the sums, log2 Z the sum, and no segment crosses a
+ * border; the chain of a segment follows from its `first`.  The three functions below are ibdg_log2_states_host,
+ * ibdg_log2_posteriors_host and ibdg_log2_segments_host with the starts as two more arguments; n_starts = 0 (starts may be NULL)
+ * gives their bytes.  Errors, beside theirs: an entry that is 0, >= n_win, or not above the one before it (the message names
+ * it), NULL starts with n_starts > 0. */
+int ibdg_log2_states_chains_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, uint8_t *path,
+                                 int64_t *score, uint64_t count[3], const uint32_t *starts, size_t n_starts);
+int ibdg_log2_posteriors_chains_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
+                                     double expect[3], double *log2_z, const uint32_t *starts, size_t n_starts);
+int ibdg_log2_segments_chains_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, int with_post,
+                                   const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap,
+                                   uint64_t *n_seg, uint64_t summary[12], const uint32_t *starts, size_t n_starts);
+/* The chains of the current site list, for ibdg_window_log2_states / _posteriors / _segments and ibdg_get_log2_segments on the
+ * device: the same bytes as the three functions above with these starts.  n_starts = 0 (starts may be NULL) clears them.  They
+ * belong to the site list: a later upload of sites or of a panel clears them, an ibdg_run does not (batches of individuals share
+ * a list).  The call makes the paths, posteriors and records kept from earlier calls stale; it adds no launch to any call and
+ * nothing to ibdg_run.  Errors: the entries' as above (against ibdg_num_windows), no valid site list; a refused call leaves the
+ * chains as they were. */
+int ibdg_set_window_chains(ibdg_ctx *ctx, const uint32_t *starts, size_t n_starts);
+/* The number of chains of the current site list: the starts set plus window 0's; 0 without windows. */
+size_t ibdg_num_window_chains(const ibdg_ctx *ctx);
 /* Alt-allele count of panel rows [first_row, first_row+n): out[n] (for tests). */
 int ibdg_get_alt_counts(ibdg_ctx *ctx, size_t first_row, size_t n, uint32_t *out);
 
