@@ -56,16 +56,22 @@ def _truth_factors(oracle, form, eps, M):
     return H.table_factors(lambda r, a: oracle.pdg(eps, M, r, a), M)
 
 
-def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=0, expect=None, spec=None, keep=None, rows=None):
+def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=0, expect=None, spec=None, keep=None, rows=None,
+             targets=None, checked=None):
     """One run of `form`; the parity checks and the bound on three of its comparison individuals.  Returns the truths;
     `keep` (a dict) receives the comparison individuals and the window tables of the checked ones.  `rows`: the row_index to
-    upload (nr, na per site of it) instead of np.arange(L); the oracle and hp_ref then get the panel rows alle[rows]."""
+    upload (nr, na per site of it) instead of np.arange(L); the oracle and hp_ref then get the panel rows alle[rows].
+    `targets`: the form's T comparison individuals instead of a draw by `seed`; `checked`: the positions among them to check
+    instead of the first, the middle and the last one."""
     spec = spec or FORMS[form]
     L, N = alle.shape[0], alle.shape[1] // 2
     T = spec["T"]
-    rng = np.random.default_rng(seed)
-    cand = np.array([x for x in range(N) if x != pu])
-    targets = [int(x) for x in rng.choice(cand, size=T, replace=False)]
+    if targets is None:
+        rng = np.random.default_rng(seed)
+        cand = np.array([x for x in range(N) if x != pu])
+        targets = [int(x) for x in rng.choice(cand, size=T, replace=False)]
+    targets = [int(x) for x in targets]
+    assert len(targets) == T
     with E.Engine(0, eps, M) as eng:
         for k, v in spec["opts"].items():
             eng.set_option(k, v)
@@ -79,7 +85,7 @@ def run_form(oracle, form, alle, nr, na, W, eps, M, *, refids=None, pu=-1, seed=
         for k, v in want.items():
             if v is not None:
                 assert got[k] in (v if isinstance(v, tuple) else (v,)), f"{form}: {k} {got[k]}, expected {v}"
-        checked = sorted({0, T // 2, T - 1})
+        checked = sorted({0, T // 2, T - 1}) if checked is None else sorted(checked)
         out = {i: (eng.site_ll(i), eng.window_ll(i)) for i in checked}
     if keep is not None:
         keep.update(targets=targets, windows={i: out[i][1] for i in checked})
