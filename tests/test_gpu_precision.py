@@ -45,13 +45,27 @@ for _T in (5, 15, 16, 31):
                                               T=_T, variant=2, unit=0 if _T in (5, 15) else (2, 3), layout=1, hp="mfma")
 SINGLE_FORMS = [f for f, s in FORMS.items() if s["T"] == 1]
 GROUP_FORMS = [f for f, s in FORMS.items() if s["T"] > 1]
+# The forms on the route a context takes when no option is set (tests/route_cases.py), for tests/test_gpu_default_route.py:
+# the same schema, kept apart from FORMS, whose item lists stay as they are.  The first one is the instantiation bench.py times.
+ROUTE_FORMS = {
+    "popcount IBD1 compacted": dict(opts=dict(_SINGLE, ibd0_after=1, compact_tiles=1), T=1, variant=2, unit=3, layout=2,
+                                    hp="popcount"),
+    "popcount_mt compacted T9": dict(opts=dict(ld_variant=2, mfma_targets=0, multi_target=1, compact_tiles=1), T=9, variant=2,
+                                     unit=(2, 3), layout=2, hp="popcount_mt"),
+}
+for _tau in (0, 1):
+    ROUTE_FORMS[f"mfma compacted T16 tau{_tau}"] = dict(opts=dict(FORMS[f"mfma T16 tau{_tau}"]["opts"], compact_tiles=1), T=16,
+                                                        variant=2, unit=(2, 3), layout=2, hp="mfma")
+# no option at all: the layout is the upload's own choice (2 for a sparse list: the caller says which), the first run counts everything
+ROUTE_FORMS["defaults T1"] = dict(opts={}, T=1, variant=2, unit=2, layout=(1, 2), hp="popcount")
+ROUTE_FORMS["defaults T16"] = dict(opts={}, T=16, variant=2, unit=(2, 3), layout=(1, 2), hp="mfma")
 
 WORST = {}          # (form, window value normal) -> largest |got - t| / bound
 BANDS_HIT = {}      # form -> band -> windows
 
 
 def _truth_factors(oracle, form, eps, M):
-    if isinstance(FORMS[form]["hp"], str):
+    if isinstance((FORMS.get(form) or ROUTE_FORMS[form])["hp"], str):
         return H.binomial_factors(eps, M)
     return H.table_factors(lambda r, a: oracle.pdg(eps, M, r, a), M)
 
