@@ -131,6 +131,7 @@ void panel_replaced(ibdg_ctx *c)
     c->pan.counts_valid = false;
     c->have_results = false;
     c->ls.chains_clear();
+    c->ls.steps_clear();
     c->lay.pop_sites_ok = false;
     c->prev_targets.clear();
     c->bg.prev_bg.clear();
@@ -161,6 +162,7 @@ void sites_replaced(ibdg_ctx *c)
     c->cand.sel_valid = false;
     c->have_results = false;
     c->ls.chains_clear();
+    c->ls.steps_clear();
     c->lay.pop_sites_ok = false;
     c->lay.compact = false;
     c->lay.relayout_credit = 0;
@@ -2309,7 +2311,7 @@ int ibdg_log2_states_host(const double *log2_tab, size_t n_win, double p01, doub
                           uint64_t count[3])
 {
     char msg[256];
-    if (ibdg::log2_states_host(__func__, log2_tab, n_win, p01, p02, p12, nullptr, 0, path, score, count, msg, sizeof msg))
+    if (ibdg::log2_states_host(__func__, log2_tab, n_win, p01, p02, p12, nullptr, 0, nullptr, path, score, count, msg, sizeof msg))
         return fail(nullptr, "%s", msg);
     return 0;
 }
@@ -2318,7 +2320,16 @@ int ibdg_log2_states_chains_host(const double *log2_tab, size_t n_win, double p0
                                  uint64_t count[3], const uint32_t *starts, size_t n_starts)
 {
     char msg[256];
-    if (ibdg::log2_states_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, path, score, count, msg, sizeof msg))
+    if (ibdg::log2_states_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, nullptr, path, score, count, msg, sizeof msg))
+        return fail(nullptr, "%s", msg);
+    return 0;
+}
+
+int ibdg_log2_states_steps_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, uint8_t *path, int64_t *score,
+                                uint64_t count[3], const uint32_t *starts, size_t n_starts, const int32_t *shift)
+{
+    char msg[256];
+    if (ibdg::log2_states_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, shift, path, score, count, msg, sizeof msg))
         return fail(nullptr, "%s", msg);
     return 0;
 }
@@ -2360,7 +2371,7 @@ static int enqueue_states(ibdg_ctx *c, const LogCall &L, bool want_score)
     if (ensure(c, S.path, L.T * L.n_win) || ensure(c, S.count, L.T * 24) || (want_score && ensure(c, S.score, L.T * L.n_win * 24)))
         return 1;
     if (S.fresh(S.PATH, L.P) && !want_score) return 0;
-    ibdg::launch_log2_states((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.P, S.mask(), (uint8_t *)S.path.p,
+    ibdg::launch_log2_states((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.P, S.mask(), S.shift(), (uint8_t *)S.path.p,
                              want_score ? (int64_t *)S.score.p : nullptr, (uint64_t *)S.count.p, c->stream);
     HIP_TRY(c, hipGetLastError());
     S.made(S.PATH, L.P);
@@ -2374,8 +2385,8 @@ static int enqueue_posteriors(ibdg_ctx *c, const LogCall &L)
         return 1;
     if (S.fresh(S.POST, L.P)) return 0;
     HIP_TRY(c, hipMemcpyAsync(S.ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
-    ibdg::launch_log2_posteriors((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.a, (const double *)S.ptab.p,
-                                 S.mask(), (double *)S.post.p, (double *)S.pout.p, c->stream);
+    ibdg::launch_log2_posteriors((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.P, L.a, (const double *)S.ptab.p,
+                                 S.mask(), S.shift(), (double *)S.post.p, (double *)S.pout.p, c->stream);
     HIP_TRY(c, hipGetLastError());
     S.made(S.POST, L.P);
     return 0;
@@ -2412,13 +2423,13 @@ int ibdg_window_log2_states(ibdg_ctx *c, double p01, double p02, double p12, uin
 }
 
 static int posteriors_twin(const char *fn, const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
-                           double expect[3], double *log2_z, const uint32_t *starts, size_t n_starts)
+                           double expect[3], double *log2_z, const uint32_t *starts, size_t n_starts, const int32_t *shift)
 {
     char msg[256];
     double zm = 1.0;
     int ze = 0;
     if (!log2_z) return fail(nullptr, "[::] ERROR in %s: NULL log2_z", fn);
-    if (ibdg::log2_posteriors_host(fn, log2_tab, n_win, p01, p02, p12, starts, n_starts, post, expect, &zm, &ze, msg, sizeof msg))
+    if (ibdg::log2_posteriors_host(fn, log2_tab, n_win, p01, p02, p12, starts, n_starts, shift, post, expect, &zm, &ze, msg, sizeof msg))
         return fail(nullptr, "%s", msg);
     *log2_z = std::log2(zm) + (double)ze;
     return 0;
@@ -2427,13 +2438,19 @@ static int posteriors_twin(const char *fn, const double *log2_tab, size_t n_win,
 int ibdg_log2_posteriors_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
                               double expect[3], double *log2_z)
 {
-    return posteriors_twin(__func__, log2_tab, n_win, p01, p02, p12, post, expect, log2_z, nullptr, 0);
+    return posteriors_twin(__func__, log2_tab, n_win, p01, p02, p12, post, expect, log2_z, nullptr, 0, nullptr);
 }
 
 int ibdg_log2_posteriors_chains_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
                                      double expect[3], double *log2_z, const uint32_t *starts, size_t n_starts)
 {
-    return posteriors_twin(__func__, log2_tab, n_win, p01, p02, p12, post, expect, log2_z, starts, n_starts);
+    return posteriors_twin(__func__, log2_tab, n_win, p01, p02, p12, post, expect, log2_z, starts, n_starts, nullptr);
+}
+
+int ibdg_log2_posteriors_steps_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
+                                    double expect[3], double *log2_z, const uint32_t *starts, size_t n_starts, const int32_t *shift)
+{
+    return posteriors_twin(__func__, log2_tab, n_win, p01, p02, p12, post, expect, log2_z, starts, n_starts, shift);
 }
 
 // IBD-state posteriors (k_log2_posteriors): the posteriors stage, expect and Z (and the gammas when asked for) out
@@ -2469,7 +2486,7 @@ int ibdg_log2_segments_host(const double *log2_tab, size_t n_win, double p01, do
                             uint64_t summary[12])
 {
     char msg[256];
-    if (ibdg::log2_segments_host(__func__, log2_tab, n_win, p01, p02, p12, nullptr, 0, with_post, pos_first, pos_last, seg, seg_cap,
+    if (ibdg::log2_segments_host(__func__, log2_tab, n_win, p01, p02, p12, nullptr, 0, nullptr, with_post, pos_first, pos_last, seg, seg_cap,
                                  n_seg, summary, msg, sizeof msg))
         return fail(nullptr, "%s", msg);
     return 0;
@@ -2480,8 +2497,19 @@ int ibdg_log2_segments_chains_host(const double *log2_tab, size_t n_win, double 
                                    uint64_t *n_seg, uint64_t summary[12], const uint32_t *starts, size_t n_starts)
 {
     char msg[256];
-    if (ibdg::log2_segments_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, with_post, pos_first, pos_last, seg,
-                                 seg_cap, n_seg, summary, msg, sizeof msg))
+    if (ibdg::log2_segments_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, nullptr, with_post, pos_first, pos_last,
+                                 seg, seg_cap, n_seg, summary, msg, sizeof msg))
+        return fail(nullptr, "%s", msg);
+    return 0;
+}
+
+int ibdg_log2_segments_steps_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, int with_post,
+                                  const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap,
+                                  uint64_t *n_seg, uint64_t summary[12], const uint32_t *starts, size_t n_starts, const int32_t *shift)
+{
+    char msg[256];
+    if (ibdg::log2_segments_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, shift, with_post, pos_first, pos_last,
+                                 seg, seg_cap, n_seg, summary, msg, sizeof msg))
         return fail(nullptr, "%s", msg);
     return 0;
 }
@@ -2508,6 +2536,36 @@ int ibdg_set_window_chains(ibdg_ctx *c, const uint32_t *starts, size_t n_starts)
     ++S.chain_gen;
     S.drop();
     return 0;
+}
+
+// The step shifts of the current site list: the chains' rule in every respect -- checked, kept on the host and
+// uploaded behind a host wait, the kept products stale; a refused call changes nothing.
+int ibdg_set_window_steps(ibdg_ctx *c, const int32_t *shift, size_t n)
+{
+    if (!c) return 1;
+    if (!c->sites.sites_valid) return fail(c, "[::] ERROR in ibdg_set_window_steps: no valid site list (call ibdg_upload_sites)");
+    ibdg_ctx::LogStates &S = c->ls;
+    const size_t n_win = c->sites.n_win;
+    if (n && n != n_win)
+        return fail(c, "[::] ERROR in ibdg_set_window_steps: %zu shifts for the %zu windows of the site list (n is that number, or 0 to clear)", n, n_win);
+    if (n && !shift) return fail(c, "[::] ERROR in ibdg_set_window_steps: NULL shift with n = %zu", n);
+    char msg[256];
+    if (ibdg::shift_check(__func__, shift, n, msg, sizeof msg))
+        return fail(c, "%s", msg);
+    if (n) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (quiesce(c) || ensure(c, S.cshift, n * 4)) return 1;
+        HIP_TRY(c, hipMemcpy(S.cshift.p, shift, n * 4, hipMemcpyHostToDevice));
+    }
+    S.steps.assign(shift, shift + n);
+    ++S.chain_gen;
+    S.drop();
+    return 0;
+}
+
+int ibdg_has_window_steps(const ibdg_ctx *c)
+{
+    return c && c->sites.sites_valid && !c->ls.steps.empty();
 }
 
 size_t ibdg_num_window_chains(const ibdg_ctx *c)

@@ -374,17 +374,24 @@ struct ibdg_ctx {
     // run: the setter drops the kept products (drop()) and bumps `chain_gen`, which is part of both products' key beside the
     // penalties; panel_replaced and sites_replaced clear them (chains_clear); the start of a run does not -- batches of
     // individuals share a site list.
+    // The steps: the windows' step shifts as ibdg_set_window_steps took them (`steps`, n_win entries or none) and
+    // on the device (`cshift`, uploaded by the setter behind a host wait, read by k_log2_states and k_log2_posteriors; shift()
+    // is NULL without steps).  Their lifetime is the chains' in every respect: the same generation counter, the same two
+    // places that clear them (steps_clear), and a run that does not.
     // The rest is scratch of one call: `ptab` (the two tables, uploaded with every posteriors launch), `spos` (the windows'
     // positions [2][n_win]), `sout` (summaries and counts [T][13]), `soff` (record offsets [T]), `recs` (the records).
     struct LogStates {
-        DevBuf path, score, count, post, pout, ptab, spos, sout, soff, recs, cmask;
+        DevBuf path, score, count, post, pout, ptab, spos, sout, soff, recs, cmask, cshift;
         enum Product { PATH, POST };
         bool have[2] = {false, false};
         int64_t P[2][3] = {};
         std::vector<uint32_t> chains;    // the chain starts of the site list at hand
-        uint64_t chain_gen = 1, gen[2] = {0, 0};     // bumped with every change of `chains`; what each product was made for
+        uint64_t chain_gen = 1, gen[2] = {0, 0};     // bumped with every change of `chains` or `steps`; what each product was made for
         const uint32_t *mask() const { return chains.empty() ? nullptr : (const uint32_t *)cmask.p; }
         void chains_clear() { if (!chains.empty()) ++chain_gen; chains.clear(); drop(); }
+        std::vector<int32_t> steps;      // the step shifts of the site list at hand
+        const int32_t *shift() const { return steps.empty() ? nullptr : (const int32_t *)cshift.p; }
+        void steps_clear() { if (!steps.empty()) ++chain_gen; steps.clear(); drop(); }
         bool recs_ok = false, with_post = false;
         std::vector<uint64_t> n_seg;     // per individual of the last ibdg_window_log2_segments
         bool fresh(Product k, const int64_t want[3]) const
@@ -395,7 +402,7 @@ struct ibdg_ctx {
         void records_made() { recs_ok = true; }
         void records_drop() { recs_ok = false; }
         void drop() { have[PATH] = have[POST] = recs_ok = false; }
-        void free_bufs() { release_all({&path, &score, &count, &post, &pout, &ptab, &spos, &sout, &soff, &recs, &cmask}); }
+        void free_bufs() { release_all({&path, &score, &count, &post, &pout, &ptab, &spos, &sout, &soff, &recs, &cmask, &cshift}); }
     } ls;
 
     // The finalising step of the last run of single individuals (k_ld_finalize's work) when it has been left to the NEXT

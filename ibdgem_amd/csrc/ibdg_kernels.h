@@ -361,18 +361,20 @@ void launch_llr_sums(const double *win_ll, uint32_t n_win, uint32_t n_targets, c
 // P: the penalties P_01, P_02, P_12 in quanta (states_penalties); path [T][n_win] (always: it holds `from` on the way); score
 // [T][n_win][3] or NULL; count [T][3].  n_win <= STATES_MAX_WIN.  One launch on `st`, no atomics.  Nothing is launched for no
 // windows or no individuals: that holds for all four launches here.  starts, in all four: the chain starts' mask on the device,
-// ceil(n_win / 32) words (chain_start in ibdg_states.h), or NULL for none.
+// ceil(n_win / 32) words (chain_start in ibdg_states.h), or NULL for none.  shift, in the first two: the windows' step shifts on
+// the device, n_win int32, or NULL for none.
 constexpr int STATES_THREADS = 256;        // = STATES_BLOCKS of ibdg_states.h (asserted in ibdg_states.hip): a thread per block
 constexpr uint32_t STATES_MAX_BLOCKS = 1024;
 void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], const uint32_t *starts,
-                        uint8_t *path, int64_t *score, uint64_t *count, hipStream_t st);
+                        const int32_t *shift, uint8_t *path, int64_t *score, uint64_t *count, hipStream_t st);
 
 // IBD-state posteriors over win_log2[T][n_win][3] (k_log2_posteriors in ibdg_states.hip, ibdg_window_log2_posteriors; the
-// definition is in ibdg_states.h): the launch of launch_log2_states.  a: the penalty weights (post_penalty_weights); tables: the
+// definition is in ibdg_states.h): the launch of launch_log2_states.  P, a: the penalties and their weights (post_penalty_weights); tables: the
 // 512 doubles of post_tables on the device; scr [T][n_win][3]: scratch, then gamma; out [T][5] = expect[3], Z's mantissa, Z's
 // exponent.  One launch on `st`, no atomics.
-void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_targets, const double a[3], const double *tables,
-                            const uint32_t *starts, double *scr, double *out, hipStream_t st);
+void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], const double a[3],
+                            const double *tables, const uint32_t *starts, const int32_t *shift, double *scr, double *out,
+                            hipStream_t st);
 
 // The segments of the paths (k_log2_segments_count, k_log2_segments_write in ibdg_states.hip; ibdg_window_log2_segments,
 // ibdg_get_log2_segments; the definition is in ibdg_states.h): the launch of launch_log2_states.  path [T][n_win] as

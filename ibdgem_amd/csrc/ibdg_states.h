@@ -1,4 +1,4 @@
-// ibdg_states.h -- the integer log-domain IBD-state path, its posteriors (4.9) and segments (4.10): the definition,
+// ibdg_states.h -- the integer log-domain IBD-state path, its posteriors (4.9) and segments (4.10), chains (4.11) and step shifts (4.12): the definition,
 // and every step of it as one inline function that the kernels' threads (ibdg_states.hip) and the host twin's loops
 // (ibdg_states_host.cpp) both call.  No HIP type in here: the host twin needs no device.
 //
@@ -17,7 +17,7 @@
 // Chains.  A chain start is a window that is treated the way window 0 is: uniform entry, no penalty into it.  The
 // starts are a mask of ceil(n_win / 32) words, bit w & 31 of word w >> 5 set iff window w >= 1 starts a chain; window 0 always
 // starts one, and a NULL mask means no further start (chain_start).  Everything else accumulates as before:
-//   path        at a start the step takes pen[q][s] = 0 for all q, s (states_chain_step): score[w][s] = max_q score[w-1][q] +
+//   path        at a start the step takes pen[q][s] = 0 for all q, s (states_shift_step): score[w][s] = max_q score[w-1][q] +
 //               e_w[s], from[w][s] = the lowest q of that maximum, the same for every s.  The scores are not reset, and a step
 //               still never moves a score up: the bound above holds.  Inside a chain [c0, c1) the scores are the chain's own
 //               plus one constant K = max_q score[c0-1][q], so `from`, the traceback and the path are what a call on the slice
@@ -26,6 +26,20 @@
 //               in steps 1, 3 and 4 alike (post_window_matrix); "the first matrix of a block" is that of w0 == 0 or a start.
 //               Z is the product of the chains' Z, gamma inside a chain the chain's own.  No operation is added.
 //   segments    window w starts a segment iff w == 0, path[w] != path[w-1] or w starts a chain: no segment crosses a border.
+//
+// Step shifts.  A step shift is one int32 per window: shift[w] in quanta of 2^-16 bit, |shift| <= 2^30
+// (STATES_SHIFT_MAX); shift[0] is ignored.  For a window w >= 1 that does not start a chain the step into w uses
+//   P_xy(w) = min(0, max(STATES_PEN_MIN, P_xy + shift[w]))      xy = 01, 02, 12; the diagonal stays 0
+// (states_shift_penalty).  A chain start keeps its meaning and wins over the shift: penalty 0 into the window, and a segment
+// begins; a shift alone never begins a segment.  A NULL shift array gives the bytes of everything above.
+//   path        states_step with the window's own matrix (states_shift_step).  A penalty stays <= 0, so a step still never
+//               moves a score up and the bound on |score| stands; integer (max, +) is exact for any blocking.
+//   posteriors  a_xy(w) = post_weight(P_xy(w), T1, T2) -- the emissions' rule, so a switch weight below 2^-1000 is 0 --, the
+//               diagonal 1; M_w = post_step_matrix(a(w), b_w) in steps 1, 3 and 4 alike (post_window_matrix), the order of
+//               operations unchanged.  The weights are inputs, the same doubles on either side: the count of roundings per
+//               window stands.  A constant penalty's weight is never 0 (the host's ldexp), a window's own is 0 below 2^-1000:
+//               "all shifts 0" gives the bytes of "no shifts" for p >= 2^-1000.
+//   segments    seg_start does not change; the records change through the path and gamma only.
 #pragma once
 #include "../../include/ibdgem_hip.h"      // ibdg_segment
 
@@ -44,6 +58,7 @@ constexpr size_t STATES_MAX_WIN = (size_t)1 << 21;
 constexpr double STATES_QUANTA = 65536.0;               // per bit
 constexpr double STATES_D_MIN = -16777216.0;            // clamp of l_s - max(l), bits
 constexpr int64_t STATES_PEN_MIN = -((int64_t)1 << 40); // clamp of a penalty, quanta
+constexpr int32_t STATES_SHIFT_MAX = (int32_t)1 << 30;  // the largest |shift[w]|, quanta
 
 // the nearest integer, ties to even (the default rounding mode on the host; v_rndne_f64 and a conversion on the device)
 IBDG_HD int64_t states_rint(double x)
@@ -99,16 +114,37 @@ IBDG_HD bool chain_start(const uint32_t *__restrict__ mask, uint32_t w)
     return mask && (mask[w >> 5] >> (w & 31) & 1);
 }
 
-// states_step of a window that starts a chain (start) or not: the step's penalties by selects, one matrix
-IBDG_HD unsigned states_chain_step(int64_t v[3], const int64_t pen[3][3], const int64_t e[3], bool start)
+// P_xy(w): the penalty P of the step into a window whose shift is sh
+IBDG_HD int64_t states_shift_penalty(int64_t P, int32_t sh)
 {
-    int64_t pw[3][3];
+    int64_t x = P + sh;
+    x = x < STATES_PEN_MIN ? STATES_PEN_MIN : x;
+    return x > 0 ? 0 : x;
+}
+
+// the three penalties of the step into a window: 0 at a chain start, else P_xy(w) where the windows have shifts (shifted; sh: the
+// window's), else P_xy.  P = {P_01, P_02, P_12}
+IBDG_HD void states_window_penalties(const int64_t P[3], bool start, bool shifted, int32_t sh, int64_t Pw[3])
+{
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-            pw[q][s] = start ? 0 : pen[q][s];
+    for (int k = 0; k < 3; ++k)
+        Pw[k] = start ? 0 : shifted ? states_shift_penalty(P[k], sh) : P[k];
+}
+
+// states_step of a window that starts a chain (start) or not, with its own penalties (states_window_penalties): one matrix, by
+// selects
+IBDG_HD unsigned states_shift_step(int64_t v[3], const int64_t P[3], const int64_t e[3], bool start, bool shifted, int32_t sh)
+{
+    int64_t Pw[3];
+    states_window_penalties(P, start, shifted, sh, Pw);
+    const int64_t pw[3][3] = {{0, Pw[0], Pw[1]}, {Pw[0], 0, Pw[2]}, {Pw[1], Pw[2], 0}};
     return states_step(v, pw, e);
+}
+
+// shift[w] of a window w >= 1, or 0 without shifts (the caller says "shifted" beside it)
+IBDG_HD int32_t step_shift(const int32_t *__restrict__ shift, uint32_t w)
+{
+    return shift ? shift[w] : 0;
 }
 
 IBDG_HD int argmax3(const int64_t v[3])
@@ -146,10 +182,15 @@ int states_penalties(double p01, double p02, double p12, int64_t P[3], int *bad)
 // (fn: who refuses) for anything else; else mask holds the ceil(n_win / 32) words (none for an empty list).
 int chain_mask(const char *fn, const uint32_t *starts, size_t n_starts, size_t n_win, uint32_t *mask, char *err, size_t err_len);
 
-// the host twin (ibdg_log2_states[_chains]_host): path [n_win] or NULL, score [n_win][3] or NULL, count[3]; starts [n_starts]: the
-// chain starts (chain_mask's rules); fn: the public name, for messages; err: room for a message
+// The step shifts as callers give them: NULL, or n_win entries with |shift[w]| <= 2^30, w >= 1 (shift[0] is ignored).  1 and a
+// message in err (fn: who refuses) for anything else.
+int shift_check(const char *fn, const int32_t *shift, size_t n_win, char *err, size_t err_len);
+
+// the host twin (ibdg_log2_states[_chains|_steps]_host): path [n_win] or NULL, score [n_win][3] or NULL, count[3]; starts
+// [n_starts]: the chain starts (chain_mask's rules); shift: the step shifts (shift_check's rules); fn: the public name, for
+// messages; err: room for a message
 int log2_states_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
-                     size_t n_starts, uint8_t *path, int64_t *score, uint64_t count[3], char *err, size_t err_len);
+                     size_t n_starts, const int32_t *shift, uint8_t *path, int64_t *score, uint64_t count[3], char *err, size_t err_len);
 
 // ---- posteriors: the sum-product pass over the weights whose max-product the path takes ---------------------
 //
@@ -259,12 +300,14 @@ IBDG_HD void post_mat_vec(const double M[9], double v[3])
 }
 
 // what steps 1, 3 and 4 read: the individual's table [n_win][3], the penalty weights, the tables T1, T2 = T + 256, the chain
-// starts' mask or NULL
+// starts' mask or NULL, the step shifts [n_win] or NULL and the penalties in quanta (read with shifts only)
 struct PostIn {
     const double *__restrict__ tab;
     const double *T;
     double a[3];
     const uint32_t *__restrict__ starts;
+    const int32_t *__restrict__ shift;
+    int64_t P[3];
 };
 
 // b_w[0..2] of window w
@@ -277,11 +320,24 @@ IBDG_HD void post_emission_weights(const PostIn &in, uint32_t w, double b[3])
         b[s] = post_weight(e[s], in.T, in.T + 256);
 }
 
-// M_w of window w >= 1 from its b_w: the penalty weights, or (1, 1, 1) where w starts a chain, by selects
+// M_w of window w >= 1 from its b_w: the penalty weights -- with shifts the weights of the window's own penalties P_xy(w), formed
+// from the integers with the tables --, or (1, 1, 1) where w starts a chain, by selects
 IBDG_HD void post_window_matrix(const PostIn &in, uint32_t w, const double b[3], double M[9])
 {
     const bool st = chain_start(in.starts, w);
-    const double a[3] = {st ? 1.0 : in.a[0], st ? 1.0 : in.a[1], st ? 1.0 : in.a[2]};
+    double a[3];
+    if (in.shift) {
+        const int32_t sh = in.shift[w];        // (asked first: its address waits for nothing)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double aw = post_weight(states_shift_penalty(in.P[k], sh), in.T, in.T + 256);
+            a[k] = st ? 1.0 : aw;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            a[k] = st ? 1.0 : in.a[k];
+    }
     post_step_matrix(a, b, M);
 }
 
@@ -406,9 +462,9 @@ const double *post_tables();
 void post_penalty_weights(const int64_t P[3], double a[3]);
 
 // the host twin (ibdg_log2_posteriors[_chains]_host): post [n_win][3] or NULL, expect[3], z_mant and z_exp with Z = z_mant *
-// 2^z_exp (1, 0 for n_win = 0); starts, fn as above
+// 2^z_exp (1, 0 for n_win = 0); starts, shift, fn as above
 int log2_posteriors_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
-                         size_t n_starts, double *post, double expect[3], double *z_mant, int *z_exp, char *err, size_t err_len);
+                         size_t n_starts, const int32_t *shift, double *post, double expect[3], double *z_mant, int *z_exp, char *err, size_t err_len);
 
 // ---- segments: the maximal runs of one state along the path, with what backs each of them -------------------
 //
@@ -493,9 +549,9 @@ IBDG_HD void seg_summary_add(uint64_t v[12], unsigned s, uint64_t len, uint64_t 
         v[i] = s == (unsigned)(i % 3) ? seg_summary_join(i, v[i], one[i / 3]) : v[i];
 }
 
-// the host twin (ibdg_log2_segments[_chains]_host): seg [seg_cap] or NULL, *n_seg the true count, summary[12]; starts, fn as above
+// the host twin (ibdg_log2_segments[_chains]_host): seg [seg_cap] or NULL, *n_seg the true count, summary[12]; starts, shift, fn as above
 int log2_segments_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
-                       size_t n_starts, int with_post, const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg,
+                       size_t n_starts, const int32_t *shift, int with_post, const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg,
                        size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err, size_t err_len);
 
 }  // namespace ibdg

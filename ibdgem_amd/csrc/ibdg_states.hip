@@ -20,6 +20,11 @@
 // picked by the launch: CH = false for a NULL mask, in which every question about a start folds to "no" at compile time -- the
 // code of the kernels before there were chains --, and CH = true, which knows its mask is there and asks without a branch
 // (chains_of below).
+// Step shifts: k_log2_states and k_log2_posteriors take the windows' shifts [n_win], or NULL, as a second switch
+// SH of their instantiation (steps_of below): SH = false is the code above to the instruction, SH = true reads a window's shift
+// one window ahead of the step that uses it -- the address waits for nothing the recurrence makes -- and forms the window's
+// penalties (states_window_penalties) or weights (post_window_matrix) from the integers.  Steps without chains are the
+// instantiation <false, true>, not a zero mask: no mask to allocate, and no read of one.  The segment kernels read no shift.
 #include "ibdg_kernels.h"
 #include "ibdg_states.h"
 
@@ -84,25 +89,38 @@ __device__ __forceinline__ const uint32_t *chains_of(const uint32_t *starts)
     return starts;
 }
 
-template <bool CH>
+// the shifts as instantiation SH sees them, in the same way
+template <bool SH>
+__device__ __forceinline__ const int32_t *steps_of(const int32_t *shift)
+{
+    if (!SH)
+        return nullptr;
+    __builtin_assume(shift != nullptr);
+    return shift;
+}
+
+template <bool CH, bool SH>
 __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__restrict__ win_log2, uint32_t n_win,
                                                                 uint32_t n_targets, Pen P, const uint32_t *__restrict__ starts_arg,
-                                                                uint8_t *__restrict__ path, int64_t *__restrict__ score,
-                                                                uint64_t *__restrict__ count)
+                                                                const int32_t *__restrict__ shift_arg, uint8_t *__restrict__ path,
+                                                                int64_t *__restrict__ score, uint64_t *__restrict__ count)
 {
     const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
+    const int32_t *__restrict__ shift = steps_of<SH>(shift_arg);
     __shared__ int64_t mat[STATES_THREADS][3][3];   // 18 KB
     __shared__ int64_t vin[STATES_THREADS][3];      // score vector at the end of the block before
     __shared__ uint8_t maps[2][STATES_THREADS];
     __shared__ uint32_t cnt[STATES_THREADS / 64][3];
     __shared__ int last_state;
 
-    const int64_t pen[3][3] = {{0, P.p01, P.p02}, {P.p01, 0, P.p12}, {P.p02, P.p12, 0}};
+    const int64_t Pq[3] = {P.p01, P.p02, P.p12};
     const int64_t none[3] = {0, 0, 0};
     const uint32_t b = threadIdx.x;
     const Blocks B(n_win);                           // (n_win >= 1)
     const uint32_t w0 = B.begin(b), w1 = B.end(b);
     const bool own = b < B.nbk;
+    // the shift of window w of this block, read a window ahead: the last window's stands in behind the block's end (own: w0 < w1)
+    const auto shift_at = [&](uint32_t w) { return step_shift(shift, w < w1 ? w : w1 - 1); };
 
     for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
         const double *tab = win_log2 + (size_t)t * n_win * 3;
@@ -114,17 +132,23 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__
             int64_t r[3][3], e[3];
             states_emission(tab + 3 * (size_t)w0, e);
             const bool first = b == 0 || chain_start(starts, w0);      // no penalty into the block's first window
+            int64_t Pw[3];                                              // (else window w0's own penalties)
+            states_window_penalties(Pq, false, SH, shift_at(w0), Pw);
+            int32_t sh = shift_at(w0 + 1);
+            const int64_t pen[3][3] = {{0, Pw[0], Pw[1]}, {Pw[0], 0, Pw[2]}, {Pw[1], Pw[2], 0}};
 #pragma unroll
             for (int q = 0; q < 3; ++q)
 #pragma unroll
                 for (int s = 0; s < 3; ++s)
                     r[q][s] = first ? e[s] : pen[q][s] + e[s];
             for (uint32_t w = w0 + 1; w < w1; ++w) {
+                const int32_t sh_next = shift_at(w + 1);
                 states_emission(tab + 3 * (size_t)w, e);
                 const bool st = chain_start(starts, w);
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
-                    (void)states_chain_step(r[q], pen, e, st);
+                    (void)states_shift_step(r[q], Pq, e, st, SH, sh);
+                sh = sh_next;
             }
 #pragma unroll
             for (int q = 0; q < 3; ++q)
@@ -158,9 +182,12 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__
             } else {
                 v[0] = vin[b][0], v[1] = vin[b][1], v[2] = vin[b][2];
             }
+            int32_t sh = shift_at(w);
             for (; w < w1; ++w) {
+                const int32_t sh_next = shift_at(w + 1);
                 states_emission(tab + 3 * (size_t)w, e);
-                const unsigned f = states_chain_step(v, pen, e, chain_start(starts, w));
+                const unsigned f = states_shift_step(v, Pq, e, chain_start(starts, w), SH, sh);
+                sh = sh_next;
                 pt[w] = (uint8_t)f;
                 if (sc)
                     sc[3 * (size_t)w] = v[0], sc[3 * (size_t)w + 1] = v[1], sc[3 * (size_t)w + 2] = v[2];
@@ -190,21 +217,24 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_states(const double *__
 
 struct PenW {
     double a[3];      // the weights of P_01, P_02, P_12 (post_penalty_weights)
+    int64_t P[3];     // ... and the integers themselves, which a window with a shift forms its own weights from
 };
 
 // k_log2_posteriors: the sum-product pass of ibdg_states.h (steps 1 .. 4 are its functions, called per thread with pointers into
 // LDS; step 5 is the tree below), same launch and blocking as k_log2_states.  scr [T][n_win][3] holds beta_w from step 3 to step
 // 4, which overwrites it with gamma_w: the thread that wrote a row is the one that reads it.  starts: the chains' mask or NULL
-// (PostIn carries it to the steps).  out [T][5] = expect[3], Z's
+// (PostIn carries it to the steps), shift: the step shifts or NULL (likewise).  out [T][5] = expect[3], Z's
 // mantissa, Z's exponent (as a double).  The walks of step 2 run in two waves side by side (thread 0 forward, thread 64
 // backward).  No atomics; the same reads as k_log2_states, three times.
-template <bool CH>
+template <bool CH, bool SH>
 __global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double *__restrict__ win_log2, uint32_t n_win,
                                                                     uint32_t n_targets, PenW W, const double *__restrict__ tables,
                                                                     const uint32_t *__restrict__ starts_arg,
+                                                                    const int32_t *__restrict__ shift_arg,
                                                                     double *__restrict__ scr, double *__restrict__ out)
 {
     const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
+    const int32_t *__restrict__ shift = steps_of<SH>(shift_arg);
     __shared__ double mat[STATES_THREADS][9];       // 18 KB: B_b
     __shared__ double fin[STATES_THREADS][3];       // F_b
     __shared__ double gout[STATES_THREADS][3];      // G_b
@@ -221,7 +251,8 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_posteriors(const double
     __syncthreads();
 
     for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
-        const PostIn in = {win_log2 + (size_t)t * n_win * 3, T, {W.a[0], W.a[1], W.a[2]}, starts};
+        const PostIn in = {win_log2 + (size_t)t * n_win * 3, T, {W.a[0], W.a[1], W.a[2]}, starts, shift,
+                           {W.P[0], W.P[1], W.P[2]}};
         // 1
         if (own)
             post_block_matrix(in, w0, w1, mat[b], &mexp[b]);
@@ -422,20 +453,26 @@ void launch_kernel(K kernel, uint32_t n_win, uint32_t n_targets, hipStream_t st,
 #define launch_per_individual(kernel, starts, ...) \
     ((starts) ? launch_kernel(kernel<true>, __VA_ARGS__) : launch_kernel(kernel<false>, __VA_ARGS__))
 
+// ... and for these shifts (with: SH = true, without: SH = false)
+#define launch_per_individual_steps(kernel, starts, shift, ...)                                                               \
+    ((shift) ? ((starts) ? launch_kernel(kernel<true, true>, __VA_ARGS__) : launch_kernel(kernel<false, true>, __VA_ARGS__)) \
+             : ((starts) ? launch_kernel(kernel<true, false>, __VA_ARGS__) : launch_kernel(kernel<false, false>, __VA_ARGS__)))
+
 }  // namespace
 
 void launch_log2_states(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], const uint32_t *starts,
-                        uint8_t *path, int64_t *score, uint64_t *count, hipStream_t st)
+                        const int32_t *shift, uint8_t *path, int64_t *score, uint64_t *count, hipStream_t st)
 {
-    launch_per_individual(k_log2_states, starts, n_win, n_targets, st, win_log2, n_win, n_targets, Pen{P[0], P[1], P[2]}, starts, path, score,
-                          count);
+    launch_per_individual_steps(k_log2_states, starts, shift, n_win, n_targets, st, win_log2, n_win, n_targets, Pen{P[0], P[1], P[2]},
+                                starts, shift, path, score, count);
 }
 
-void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_targets, const double a[3], const double *tables,
-                            const uint32_t *starts, double *scr, double *out, hipStream_t st)
+void launch_log2_posteriors(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], const double a[3],
+                            const double *tables, const uint32_t *starts, const int32_t *shift, double *scr, double *out,
+                            hipStream_t st)
 {
-    launch_per_individual(k_log2_posteriors, starts, n_win, n_targets, st, win_log2, n_win, n_targets, PenW{{a[0], a[1], a[2]}}, tables, starts,
-                          scr, out);
+    launch_per_individual_steps(k_log2_posteriors, starts, shift, n_win, n_targets, st, win_log2, n_win, n_targets,
+                                PenW{{a[0], a[1], a[2]}, {P[0], P[1], P[2]}}, tables, starts, shift, scr, out);
 }
 
 void launch_log2_segments_count(const uint8_t *path, uint32_t n_win, uint32_t n_targets, const uint64_t *pos_first,

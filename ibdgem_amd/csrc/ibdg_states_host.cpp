@@ -68,6 +68,16 @@ int chain_mask(const char *fn, const uint32_t *starts, size_t n_starts, size_t n
     return 0;
 }
 
+int shift_check(const char *fn, const int32_t *shift, size_t n_win, char *err, size_t err_len)
+{
+    for (size_t w = 1; shift && w < n_win; ++w)
+        if (shift[w] > STATES_SHIFT_MAX || shift[w] < -STATES_SHIFT_MAX) {
+            snprintf(err, err_len, "[::] ERROR in %s: shift[%zu] = %d is not within +-2^30", fn, w, shift[w]);
+            return 1;
+        }
+    return 0;
+}
+
 // chain_mask into a vector of the twins' own; *mask: its words, or NULL for no starts
 static int own_mask(const char *fn, const uint32_t *starts, size_t n_starts, size_t n_win, std::vector<uint32_t> &own,
                     const uint32_t **mask, char *err, size_t err_len)
@@ -77,15 +87,15 @@ static int own_mask(const char *fn, const uint32_t *starts, size_t n_starts, siz
     return chain_mask(fn, starts, n_starts, n_win, own.data(), err, err_len);
 }
 
-// The cores take checked arguments and check nothing.  mask: the chain starts' bits (chain_start), or NULL.
+// The cores take checked arguments and check nothing.  mask: the chain starts' bits (chain_start), or NULL; shift: the step
+// shifts [n_win], or NULL.
 // The states recurrence: path [n_win] or NULL, score [n_win][3] or NULL, count[3]
-static void states_core(const double *tab, size_t n_win, const int64_t P[3], const uint32_t *mask, uint8_t *path, int64_t *score,
-                        uint64_t count[3])
+static void states_core(const double *tab, size_t n_win, const int64_t P[3], const uint32_t *mask, const int32_t *shift, uint8_t *path,
+                        int64_t *score, uint64_t count[3])
 {
     count[0] = count[1] = count[2] = 0;
     if (n_win == 0)
         return;
-    const int64_t pen[3][3] = {{0, P[0], P[1]}, {P[0], 0, P[2]}, {P[1], P[2], 0}};
     std::vector<uint8_t> from(n_win);            // from[i][s] in bits 2 s, 2 s + 1
     int64_t v[3], e[3];
     states_emission(tab, v);
@@ -94,7 +104,7 @@ static void states_core(const double *tab, size_t n_win, const int64_t P[3], con
         score[0] = v[0], score[1] = v[1], score[2] = v[2];
     for (size_t i = 1; i < n_win; ++i) {
         states_emission(tab + 3 * i, e);
-        from[i] = (uint8_t)states_chain_step(v, pen, e, chain_start(mask, (uint32_t)i));
+        from[i] = (uint8_t)states_shift_step(v, P, e, chain_start(mask, (uint32_t)i), shift != nullptr, step_shift(shift, (uint32_t)i));
         if (score)
             score[3 * i] = v[0], score[3 * i + 1] = v[1], score[3 * i + 2] = v[2];
     }
@@ -109,15 +119,15 @@ static void states_core(const double *tab, size_t n_win, const int64_t P[3], con
 
 // err: room for a message
 int log2_states_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
-                     size_t n_starts, uint8_t *path, int64_t *score, uint64_t count[3], char *err, size_t err_len)
+                     size_t n_starts, const int32_t *shift, uint8_t *path, int64_t *score, uint64_t count[3], char *err, size_t err_len)
 {
     int64_t P[3];
     std::vector<uint32_t> own;
     const uint32_t *mask;
     if (check_log_args(fn, count ? nullptr : "count", tab, n_win, p01, p02, p12, "the integer scores allow", P, err, err_len) ||
-        own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len))
+        own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len) || shift_check(fn, shift, n_win, err, err_len))
         return 1;
-    states_core(tab, n_win, P, mask, path, score, count);
+    states_core(tab, n_win, P, mask, shift, path, score, count);
     return 0;
 }
 
@@ -145,14 +155,14 @@ void post_penalty_weights(const int64_t P[3], double a[3])
 
 // The sum-product pass: steps 1 .. 4 are the functions of ibdg_states.h that the kernel's threads call, here in loops over b; step
 // 5 is the same tree, serial.  post [n_win][3] or NULL.
-static void posteriors_core(const double *tab, size_t n_win, const int64_t P[3], const uint32_t *mask, double *post,
+static void posteriors_core(const double *tab, size_t n_win, const int64_t P[3], const uint32_t *mask, const int32_t *shift, double *post,
                             double expect[3], double *z_mant, int *z_exp)
 {
     expect[0] = expect[1] = expect[2] = 0.0;
     *z_mant = 1.0, *z_exp = 0;
     if (n_win == 0)
         return;
-    PostIn in = {tab, post_tables(), {}, mask};
+    PostIn in = {tab, post_tables(), {}, mask, shift, {P[0], P[1], P[2]}};
     post_penalty_weights(P, in.a);
     std::vector<double> own;
     if (!post) {
@@ -181,16 +191,17 @@ static void posteriors_core(const double *tab, size_t n_win, const int64_t P[3],
 }
 
 int log2_posteriors_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
-                         size_t n_starts, double *post, double expect[3], double *z_mant, int *z_exp, char *err, size_t err_len)
+                         size_t n_starts, const int32_t *shift, double *post, double expect[3], double *z_mant, int *z_exp, char *err,
+                         size_t err_len)
 {
     int64_t P[3];
     std::vector<uint32_t> own;
     const uint32_t *mask;
     if (check_log_args(fn, !expect ? "expect" : !z_mant || !z_exp ? "log2_z" : nullptr, tab, n_win, p01, p02, p12, "of the path", P,
                        err, err_len) ||
-        own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len))
+        own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len) || shift_check(fn, shift, n_win, err, err_len))
         return 1;
-    posteriors_core(tab, n_win, P, mask, post, expect, z_mant, z_exp);
+    posteriors_core(tab, n_win, P, mask, shift, post, expect, z_mant, z_exp);
     return 0;
 }
 
@@ -220,7 +231,7 @@ static void segments_core(const double *tab, size_t n_win, const uint8_t *path, 
 
 // (the table and the penalties are refused in the words of ibdg_log2_states_host, whose checks they are)
 int log2_segments_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
-                       size_t n_starts, int with_post, const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg,
+                       size_t n_starts, const int32_t *shift, int with_post, const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg,
                        size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err, size_t err_len)
 {
     int64_t P[3];
@@ -243,16 +254,16 @@ int log2_segments_host(const char *fn, const double *tab, size_t n_win, double p
                      (unsigned long long)pos_last[w], (unsigned long long)pos_first[w]);
             return 1;
         }
-    if (own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len))
+    if (own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len) || shift_check(fn, shift, n_win, err, err_len))
         return 1;
     std::vector<uint8_t> path(n_win);
     std::vector<double> post(with_post ? n_win * 3 : 0);
     uint64_t count[3];
     double expect[3], zm;
     int ze;
-    states_core(tab, n_win, P, mask, path.data(), nullptr, count);
+    states_core(tab, n_win, P, mask, shift, path.data(), nullptr, count);
     if (with_post)
-        posteriors_core(tab, n_win, P, mask, post.data(), expect, &zm, &ze);
+        posteriors_core(tab, n_win, P, mask, shift, post.data(), expect, &zm, &ze);
     segments_core(tab, n_win, path.data(), mask, with_post ? post.data() : nullptr, pos_first, pos_last, seg, seg_cap, n_seg, summary);
     return 0;
 }

@@ -66,6 +66,13 @@ SYMBOLS = {
                                                  C.c_size_t, _P, _P, _P, C.c_size_t]),
     "ibdg_set_window_chains": (C.c_int, [_P, _P, C.c_size_t]),
     "ibdg_num_window_chains": (C.c_size_t, [_P]),
+    "ibdg_log2_states_steps_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ibdg_log2_posteriors_steps_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
+                                                  C.c_size_t, _P]),
+    "ibdg_log2_segments_steps_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P,
+                                                C.c_size_t, _P, _P, _P, C.c_size_t, _P]),
+    "ibdg_set_window_steps": (C.c_int, [_P, _P, C.c_size_t]),
+    "ibdg_has_window_steps": (C.c_int, [_P]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
     "ibdg_run_ms": (C.c_int, [_P, C.c_uint, _P]),
@@ -169,10 +176,20 @@ def _starts(starts):
     return a, (a.ctypes.data if len(a) else None), len(a)
 
 
-def log2_states_host(log2_tab, p01, p02, p12, want_path=True, want_score=True, starts=None):
+def _shift(shift, n):
+    """The step shifts of a table of n windows as the twins take them: a contiguous int32 array [n] (kept alive by the caller).
+    The entries go as they are: the library checks them."""
+    a = np.ascontiguousarray(shift, dtype=np.int32).reshape(-1)
+    if len(a) != n:
+        raise ValueError(f"shift: {len(a)} entries, not the {n} windows")
+    return a
+
+
+def log2_states_host(log2_tab, p01, p02, p12, want_path=True, want_score=True, starts=None, shift=None):
     """The integer log-domain IBD-state path of one window table [n_win][3] on the host (ibdg_log2_states_host):
     (path uint8 [n_win] or None, score int64 [n_win][3] or None, count uint64 [3]).  starts: the windows >= 1 that start a chain
-    (ibdg_log2_states_chains_host); None: the call without chains."""
+    (ibdg_log2_states_chains_host); None: the call without chains.  shift: the windows' step shifts, int32 [n_win]
+    (ibdg_log2_states_steps_host); None: the call without steps."""
     lib = load_library()
     tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
     n = tab.shape[0]
@@ -181,7 +198,11 @@ def log2_states_host(log2_tab, p01, p02, p12, want_path=True, want_score=True, s
     count = np.zeros(3, dtype=np.uint64)
     args = (tab.ctypes.data, n, p01, p02, p12, None if path is None else path.ctypes.data,
             None if score is None else score.ctypes.data, count.ctypes.data)
-    if starts is None:
+    if shift is not None:
+        keep, ptr, ns = _starts(() if starts is None else starts)
+        sh = _shift(shift, n)
+        rc = lib.ibdg_log2_states_steps_host(*args, ptr, ns, sh.ctypes.data)
+    elif starts is None:
         rc = lib.ibdg_log2_states_host(*args)
     else:
         keep, ptr, ns = _starts(starts)
@@ -191,10 +212,10 @@ def log2_states_host(log2_tab, p01, p02, p12, want_path=True, want_score=True, s
     return path, score, count
 
 
-def log2_posteriors_host(log2_tab, p01, p02, p12, want_post=True, starts=None):
+def log2_posteriors_host(log2_tab, p01, p02, p12, want_post=True, starts=None, shift=None):
     """Forward-backward IBD-state probabilities of one window table [n_win][3] on the host (ibdg_log2_posteriors_host):
-    (post float64 [n_win][3] or None, expect float64 [3], log2_z float).  starts: as for log2_states_host
-    (ibdg_log2_posteriors_chains_host)."""
+    (post float64 [n_win][3] or None, expect float64 [3], log2_z float).  starts, shift: as for log2_states_host
+    (ibdg_log2_posteriors_chains_host, ibdg_log2_posteriors_steps_host)."""
     lib = load_library()
     tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
     n = tab.shape[0]
@@ -203,7 +224,11 @@ def log2_posteriors_host(log2_tab, p01, p02, p12, want_post=True, starts=None):
     log2_z = C.c_double(0.0)
     args = (tab.ctypes.data, n, p01, p02, p12, None if post is None else post.ctypes.data, expect.ctypes.data,
             C.addressof(log2_z))
-    if starts is None:
+    if shift is not None:
+        keep, ptr, ns = _starts(() if starts is None else starts)
+        sh = _shift(shift, n)
+        rc = lib.ibdg_log2_posteriors_steps_host(*args, ptr, ns, sh.ctypes.data)
+    elif starts is None:
         rc = lib.ibdg_log2_posteriors_host(*args)
     else:
         keep, ptr, ns = _starts(starts)
@@ -232,10 +257,10 @@ def _positions(pos_first, pos_last, n):
 
 
 def log2_segments_host(log2_tab, p01, p02, p12, with_post=False, pos_first=None, pos_last=None, seg_cap=None, want_seg=True,
-                       starts=None):
+                       starts=None, shift=None):
     """The segments of one window table's path on the host (ibdg_log2_segments_host): (seg structured array of
     SEGMENT_DTYPE -- min(n_seg, seg_cap) records, all of them with seg_cap None -- or None, n_seg int, summary uint64 [12]).
-    starts: as for log2_states_host (ibdg_log2_segments_chains_host)."""
+    starts, shift: as for log2_states_host (ibdg_log2_segments_chains_host, ibdg_log2_segments_steps_host)."""
     lib = load_library()
     tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
     n = tab.shape[0]
@@ -249,7 +274,11 @@ def log2_segments_host(log2_tab, p01, p02, p12, with_post=False, pos_first=None,
     args = (tab.ctypes.data, n, p01, p02, p12, int(bool(with_post)), None if pf is None else pf.ctypes.data,
             None if pl is None else pl.ctypes.data, None if seg is None else seg.ctypes.data, cap, C.addressof(n_seg),
             summary.ctypes.data)
-    if starts is None:
+    if shift is not None:
+        keep, ptr, ns = _starts(() if starts is None else starts)
+        sh = _shift(shift, n)
+        rc = lib.ibdg_log2_segments_steps_host(*args, ptr, ns, sh.ctypes.data)
+    elif starts is None:
         rc = lib.ibdg_log2_segments_host(*args)
     else:
         keep, ptr, ns = _starts(starts)
@@ -499,6 +528,16 @@ class Engine:
         get_log2_segments (ibdg_set_window_chains); none clears them.  A new site list or panel clears them too."""
         keep, ptr, ns = _starts(starts)
         self._chk(self.lib.ibdg_set_window_chains(self.ctx, ptr, ns))
+
+    def set_window_steps(self, shift=None):
+        """The step shifts of the current site list's windows, int32 [n_windows], for the three window_log2_* calls and
+        get_log2_segments (ibdg_set_window_steps); None or an empty list clears them.  A new site list or panel clears them too."""
+        a = np.ascontiguousarray(() if shift is None else shift, dtype=np.int32).reshape(-1)
+        self._chk(self.lib.ibdg_set_window_steps(self.ctx, a.ctypes.data if len(a) else None, len(a)))
+
+    def has_window_steps(self):
+        """Whether the current site list has step shifts (ibdg_has_window_steps)."""
+        return bool(self.lib.ibdg_has_window_steps(self.ctx))
 
     @property
     def n_window_chains(self):

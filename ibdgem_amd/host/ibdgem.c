@@ -68,6 +68,11 @@ static int opt_posteriors = 0;           /* --posteriors: with --log-stats --sta
 static int opt_segments = 0;             /* --segments: with --log-stats --states, the path's segments with their scores and support */
 static int has_chain_gap = 0;            /* --chain-gap BP: with --log-stats --states, a window more than BP behind the end of the one before starts a chain */
 static unsigned long opt_chain_gap = 0;
+static int has_switch_scale = 0;         /* --switch-scale X: with --log-stats --states, the penalties hold for two windows X apart; a step's switch weight scales with its distance */
+static double opt_switch_scale = 0.0;
+static const char *genetic_map_fn = NULL; /* --genetic-map FILE: the distances of --switch-scale in centimorgans along this map */
+static double *gmap_pos = NULL, *gmap_cm = NULL;    /* ... its entries: position, cumulative cM */
+static size_t gmap_n = 0;
 static int opt_log_stats = 0;            /* --log-stats: --arm-stats and --states from the log2 window table (no underflow), into log* files */
 static int opt_states = 0, has_pen = 0;  /* --states: the IBD-state path of every comparison (hgpath.c), --p01/--p02/--p12 its penalties */
 static double opt_p01 = HG_DEFAULT_P01, opt_p02 = HG_DEFAULT_P02, opt_p12 = HG_DEFAULT_P12;
@@ -85,6 +90,8 @@ static struct option longopts[] = {
     {"posteriors", no_argument, &opt_posteriors, 1},
     {"segments", no_argument, &opt_segments, 1},
     {"chain-gap", required_argument, 0, 1011},
+    {"switch-scale", required_argument, 0, 1012},
+    {"genetic-map", required_argument, 0, 1013},
     {"p01", required_argument, 0, 1008},
     {"p02", required_argument, 0, 1009},
     {"p12", required_argument, 0, 1010},
@@ -202,6 +209,16 @@ static void usage(int code)
           "                            into it, and no segment (hence no base pair of a length) crosses the gap; the chains'\n"
           "                            paths, posteriors and segments are independent.  A gap inside a window breaks nothing.\n"
           "                            The files keep their formats; *.logsegments.txt gains a first column Chain (1-based)\n"
+          "  --switch-scale X          with --log-stats --states: --p01, --p02 and --p12 hold for two windows whose centres\n"
+          "                            ((START + END) / 2) lie X apart (a decimal > 0; base pairs, or centimorgans with\n"
+          "                            --genetic-map); a step of distance D has its switch weights multiplied by D / X, capped\n"
+          "                            at 1: switching costs more between close windows and less across sparse stretches.  In\n"
+          "                            the path's integers: log2(D / X) * 65536, rounded, is added to the step's penalties.\n"
+          "                            Combines with --chain-gap (a chain start stays free), --posteriors and --segments; no\n"
+          "                            file changes its format\n"
+          "  --genetic-map FILE        with --switch-scale: distances in centimorgans.  FILE: a header line, then lines of\n"
+          "                            position, rate in cM/Mb (not read) and cumulative cM, positions strictly increasing;\n"
+          "                            linear between two entries, the map's mean rate outside it\n"
           "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
           "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
           "  --stats-only              with --arm-stats and/or --states: write the armstats / ibdstates file only (no\n"
@@ -1748,6 +1765,100 @@ static size_t chain_gap_starts(const uint64_t *pos_first, const uint64_t *pos_la
     return k;
 }
 
+/* --genetic-map: g(x) in centimorgans.  Behind the map's last entry and before its first it continues at the map's mean rate;
+ * else it is linear between the entry at or below x and the one above it. */
+static double gmap_at(double x)
+{
+    const size_t n = gmap_n;
+    const double mean = (gmap_cm[n - 1] - gmap_cm[0]) / (gmap_pos[n - 1] - gmap_pos[0]);
+    if (x < gmap_pos[0])
+        return gmap_cm[0] + (x - gmap_pos[0]) * mean;
+    if (x >= gmap_pos[n - 1])
+        return gmap_cm[n - 1] + (x - gmap_pos[n - 1]) * mean;
+    size_t lo = 0, hi = n - 1;                   /* pos[lo] <= x < pos[hi] */
+    while (hi - lo > 1) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (gmap_pos[mid] <= x)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return gmap_cm[lo] + (x - gmap_pos[lo]) * ((gmap_cm[lo + 1] - gmap_cm[lo]) / (gmap_pos[lo + 1] - gmap_pos[lo]));
+}
+
+/* --genetic-map FILE is read once, before any pileup: exits with a message that names the line for anything but a header and
+ * lines of three numbers with strictly increasing positions */
+static void gmap_read(const char *fn)
+{
+    FILE *f = fopen(fn, "r");
+    if (!f) {
+        fprintf(stderr, "[::] ERROR: cannot open the genetic map (--genetic-map) %s.\n", fn);
+        exit(1);
+    }
+    char line[1024];
+    size_t cap = 0, ln = 1;
+    if (!fgets(line, sizeof line, f)) {
+        fprintf(stderr, "[::] ERROR: the genetic map (--genetic-map) %s is empty (a header line, then position, rate, cM).\n", fn);
+        exit(1);
+    }
+    while (fgets(line, sizeof line, f)) {
+        ++ln;
+        double pos, rate, cm;
+        char tail;
+        if (line[strspn(line, " \t\r\n")] == 0)
+            continue;
+        if (sscanf(line, "%lf %lf %lf %c", &pos, &rate, &cm, &tail) != 3 || !isfinite(pos) || !isfinite(cm)) {
+            fprintf(stderr, "[::] ERROR: genetic map (--genetic-map) %s, line %zu: not three numbers (position, rate in cM/Mb, cumulative cM).\n", fn, ln);
+            exit(1);
+        }
+        if (gmap_n && !(pos > gmap_pos[gmap_n - 1])) {
+            fprintf(stderr, "[::] ERROR: genetic map (--genetic-map) %s, line %zu: position %.17g does not lie above the %.17g of the entry before it (strictly increasing).\n",
+                    fn, ln, pos, gmap_pos[gmap_n - 1]);
+            exit(1);
+        }
+        if (gmap_n == cap) {
+            cap = cap ? 2 * cap : 1024;
+            gmap_pos = realloc(gmap_pos, cap * sizeof *gmap_pos);
+            gmap_cm = realloc(gmap_cm, cap * sizeof *gmap_cm);
+            if (!gmap_pos || !gmap_cm) {
+                fprintf(stderr, "[::] ERROR: out of memory for the genetic map.\n");
+                exit(1);
+            }
+        }
+        gmap_pos[gmap_n] = pos, gmap_cm[gmap_n] = cm;
+        ++gmap_n;
+    }
+    fclose(f);
+    if (gmap_n < 2) {
+        fprintf(stderr, "[::] ERROR: the genetic map (--genetic-map) %s has %zu entries; two make a rate.\n", fn, gmap_n);
+        exit(1);
+    }
+}
+
+/* --switch-scale X, for every route: the step shift of every window (what ibdg_set_window_steps and the _steps_host
+ * twins take) from the positions the summary prints.  D_w is the distance of the centres of windows w - 1 and w -- the integer
+ * difference of START + END first, then its half; with --genetic-map the difference of g at the two centres --, shift[w] =
+ * llrint(log2(D_w / X) * 65536): one division, one log2, one product, one rounding, kept within +-2^30; -2^30 where D_w <= 0.
+ * shift: room for n entries; shift[0] = 0 (not read). */
+static void switch_scale_shifts(const uint64_t *pos_first, const uint64_t *pos_last, size_t n, int32_t *shift)
+{
+    const double lim = 1073741824.0;
+    for (size_t w = 0; w < n; ++w) {
+        double D = 0.0, v = -lim;
+        if (w == 0) {
+            shift[0] = 0;
+            continue;
+        }
+        if (gmap_n)
+            D = gmap_at((double)(pos_first[w] + pos_last[w]) * 0.5) - gmap_at((double)(pos_first[w - 1] + pos_last[w - 1]) * 0.5);
+        else
+            D = (double)(int64_t)((pos_first[w] + pos_last[w]) - (pos_first[w - 1] + pos_last[w - 1])) * 0.5;
+        if (D > 0.0)
+            v = log2(D / opt_switch_scale) * 65536.0;
+        shift[w] = v >= lim ? (int32_t)lim : !(v > -lim) ? -(int32_t)lim : (int32_t)llrint(v);
+    }
+}
+
 /* ---- one comparison spread over several GPUs (window ranges, host-side gather) ------------ */
 /* What the run's statistics files hold of one comparison individual, the same record from the device (or the individual's
  * output job) to the files: a shard's double-double arm sums (ibdg_window_llr_sums), of which the run keeps the four rounded
@@ -1812,7 +1923,8 @@ typedef struct {
     uint64_t *sg_vals;                       /* --segments: summary [T][12], then the counts [T] */
     uint64_t *sg_pos;                        /* ... the windows' first positions [n_win], then their last */
     uint32_t *ch_starts;                     /* --chain-gap: the chain starts of the list at hand */
-    size_t arm_cap, st_cap, po_cap, sg_cap, sg_pos_cap, ch_cap;
+    int32_t *sw_shift;                       /* --switch-scale: the step shifts of the list at hand */
+    size_t arm_cap, st_cap, po_cap, sg_cap, sg_pos_cap, ch_cap, sw_cap;
 } dev_conv;
 
 /* one comparison individual on one context: where it stands and what comes back for it */
@@ -1860,7 +1972,7 @@ static void conv_release(dev_conv *c)
         ibdg_host_free(c->stage);
     if (c->batch_ll)
         ibdg_host_free(c->batch_ll);
-    free(c->batch_log); free(c->arm_sums); free(c->st_counts); free(c->po_vals); free(c->sg_vals); free(c->sg_pos); free(c->ch_starts);
+    free(c->batch_log); free(c->arm_sums); free(c->st_counts); free(c->po_vals); free(c->sg_vals); free(c->sg_pos); free(c->ch_starts); free(c->sw_shift);
     memset(c, 0, sizeof *c);
 }
 
@@ -1915,6 +2027,20 @@ static int chains_on_device(dev_conv *c)
     if (!grow(&c->ch_starts, &c->ch_cap, n_win + 1, sizeof(uint32_t)))
         return conv_oom(c, n_win);
     return ibdg_set_window_chains(c->eng, c->ch_starts, chain_gap_starts(c->sg_pos, c->sg_pos + n_win, n_win, c->ch_starts));
+}
+
+/* --switch-scale where the paths are found on the device: likewise, the step shifts of a new site list */
+static int steps_on_device(dev_conv *c)
+{
+    if (!has_switch_scale || !c->dev_states)
+        return 0;
+    const size_t n_win = ibdg_num_windows(c->eng);
+    if (conv_positions(c, n_win))
+        return 1;
+    if (!grow(&c->sw_shift, &c->sw_cap, n_win + 1, sizeof(int32_t)))
+        return conv_oom(c, n_win);
+    switch_scale_shifts(c->sg_pos, c->sg_pos + n_win, n_win, c->sw_shift);
+    return ibdg_set_window_steps(c->eng, c->sw_shift, n_win);
 }
 
 /* --segments where the tables stay on the device: the list's windows' positions go up with the call */
@@ -1989,7 +2115,7 @@ static int conv_list(dev_conv *c)
     if (!c->list_on_device && ibdg_upload_sites(c->eng, c->row + c->a, c->nr + c->a, c->na + c->a, c->fo ? c->fo + c->a : NULL,
                                                 c->b - c->a, (unsigned)opt_window))
         return 1;
-    return chains_on_device(c);
+    return chains_on_device(c) || steps_on_device(c);
 }
 
 /* the next batch runs while the host goes on with this one's statistics and files */
@@ -2612,14 +2738,16 @@ static int out_close(FILE **f)
 }
 
 /* what the three passes over an individual's log2 table share: the positions of its windows (first [n], then last; for
- * --segments and --chain-gap, else NULL) and its chain starts (--chain-gap; none without it) */
+ * --segments, --chain-gap and --switch-scale, else NULL), its chain starts (--chain-gap; none without it) and its step shifts
+ * (--switch-scale; NULL without it) */
 typedef struct {
     uint64_t *pos;
     uint32_t *starts;
     size_t n_starts;
+    int32_t *shift;
 } log_chains;
 
-/* --posteriors: the sum-product pass over the same table (ibdg_log2_posteriors_chains_host: the same bytes as the device's
+/* --posteriors: the sum-product pass over the same table (ibdg_log2_posteriors_steps_host: the same bytes as the device's
  * ibdg_window_log2_posteriors) */
 static int posteriors_individual(out_job *o, const log_chains *lc)
 {
@@ -2628,8 +2756,8 @@ static int posteriors_individual(out_job *o, const log_chains *lc)
     const size_t n = o->wt.w.n_win;
     double *post = o->lp ? malloc((n ? n : 1) * 3 * sizeof *post) : NULL;
     int bad = o->lp && !post;
-    if (!bad && ibdg_log2_posteriors_chains_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, post, o->res->po, o->res->po + 3, lc->starts,
-                                                 lc->n_starts)) {
+    if (!bad && ibdg_log2_posteriors_steps_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, post, o->res->po, o->res->po + 3, lc->starts,
+                                                lc->n_starts, lc->shift)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
@@ -2647,7 +2775,7 @@ static int posteriors_individual(out_job *o, const log_chains *lc)
     return bad;
 }
 
-/* --segments: the path's segments over the same table (ibdg_log2_segments_chains_host: the same bytes as the device's
+/* --segments: the path's segments over the same table (ibdg_log2_segments_steps_host: the same bytes as the device's
  * ibdg_window_log2_segments), with the positions and site counts of the individual's summary; with --chain-gap a first column
  * Chain (1-based), counted along lc->starts */
 static const char log_seg_header[] = "Segment\tState\tFirst_Window\tLast_Window\tStart\tEnd\tLength\tNum_Windows\tNum_Sites\t"
@@ -2662,8 +2790,8 @@ static int segments_individual(out_job *o, const log_chains *lc)
     uint64_t n_seg = 0;
     ibdg_segment *seg = o->ls ? malloc((n ? n : 1) * sizeof *seg) : NULL;
     int bad = o->ls && !seg;
-    if (!bad && ibdg_log2_segments_chains_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, opt_posteriors, pos, pos + n, seg, n, &n_seg,
-                                               o->res->sg, lc->starts, lc->n_starts)) {
+    if (!bad && ibdg_log2_segments_steps_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, opt_posteriors, pos, pos + n, seg, n, &n_seg,
+                                              o->res->sg, lc->starts, lc->n_starts, lc->shift)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
@@ -2701,16 +2829,19 @@ static int log_states_individual(out_job *o)
     uint64_t *const count = o->res->st;
     uint8_t *path = o->hg ? malloc(n ? n : 1) : NULL;
     int64_t *score = o->hg ? malloc((n ? n : 1) * 3 * sizeof *score) : NULL;
-    const int want_pos = opt_segments || has_chain_gap;
-    log_chains lc = {want_pos ? malloc((2 * n + 1) * sizeof *lc.pos) : NULL, has_chain_gap ? malloc((n + 1) * sizeof *lc.starts) : NULL, 0};
-    int bad = (o->hg && (!path || !score)) || (want_pos && !lc.pos) || (has_chain_gap && !lc.starts);
+    const int want_pos = opt_segments || has_chain_gap || has_switch_scale;
+    log_chains lc = {want_pos ? malloc((2 * n + 1) * sizeof *lc.pos) : NULL, has_chain_gap ? malloc((n + 1) * sizeof *lc.starts) : NULL, 0,
+                     has_switch_scale ? malloc((n + 1) * sizeof *lc.shift) : NULL};
+    int bad = (o->hg && (!path || !score)) || (want_pos && !lc.pos) || (has_chain_gap && !lc.starts) || (has_switch_scale && !lc.shift);
     for (size_t w = 0; w < n && want_pos && !bad; ++w) {
         lc.pos[w] = o->pos_first ? o->pos_first[w] : rows[o->s_row[o->wt.w.first[w]]].pos;
         lc.pos[n + w] = o->pos_last ? o->pos_last[w] : rows[o->s_row[o->wt.w.last[w]]].pos;
     }
     if (!bad && has_chain_gap)
         lc.n_starts = chain_gap_starts(lc.pos, lc.pos + n, n, lc.starts);
-    if (!bad && ibdg_log2_states_chains_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, path, score, count, lc.starts, lc.n_starts)) {
+    if (!bad && has_switch_scale)
+        switch_scale_shifts(lc.pos, lc.pos + n, n, lc.shift);
+    if (!bad && ibdg_log2_states_steps_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, path, score, count, lc.starts, lc.n_starts, lc.shift)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
@@ -2726,7 +2857,7 @@ static int log_states_individual(out_job *o)
     bad = out_close(&o->hg) || bad;
     free(path);
     free(score);
-    if ((want_pos && !lc.pos) || (has_chain_gap && !lc.starts)) {    /* (out of memory: the other two files are closed as they are) */
+    if ((want_pos && !lc.pos) || (has_chain_gap && !lc.starts) || (has_switch_scale && !lc.shift)) {    /* (out of memory: the other two files are closed as they are) */
         out_close(&o->lp);
         out_close(&o->ls);
     } else {
@@ -2735,6 +2866,7 @@ static int log_states_individual(out_job *o)
     }
     free(lc.pos);
     free(lc.starts);
+    free(lc.shift);
     return bad;
 }
 
@@ -4053,6 +4185,18 @@ int main(int argc, char **argv)
             has_chain_gap = 1;
             break;
         }
+        case 1012: {
+            char *end = NULL;
+            errno = 0;
+            opt_switch_scale = strtod(optarg, &end);
+            if (end == optarg || *end || errno || !isfinite(opt_switch_scale) || !(opt_switch_scale > 0.0)) {
+                fprintf(stderr, "[::] ERROR: Invalid switch scale (--switch-scale) '%s' (must be a decimal > 0: base pairs, or centimorgans with --genetic-map).\n", optarg);
+                exit(1);
+            }
+            has_switch_scale = 1;
+            break;
+        }
+        case 1013: genetic_map_fn = optarg; break;
         case 1006:
             if (!parse_arm_range(optarg)) {
                 fprintf(stderr, "[::] ERROR: Invalid centromeric range (--arm-stats) '%s' (must be START,END with START <= END).\n", optarg);
@@ -4099,6 +4243,13 @@ int main(int argc, char **argv)
     if (opt_segments && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --segments needs --log-stats and --states: it cuts the path they find into its runs of one state and sums that path's own emissions over each.\n"); exit(1); }
     if (has_chain_gap && opt_plan) { fprintf(stderr, "[::] ERROR: --chain-gap changes files --plan does not make; use one of them.\n"); exit(1); }
     if (has_chain_gap && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --chain-gap needs --log-stats and --states: it says where the chain of windows whose path they find is broken.\n"); exit(1); }
+    if (has_switch_scale && opt_plan) { fprintf(stderr, "[::] ERROR: --switch-scale changes files --plan does not make; use one of them.\n"); exit(1); }
+    if (has_switch_scale && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --switch-scale needs --log-stats and --states: it scales the switch penalties of the chain of windows whose path they find.\n"); exit(1); }
+    if (genetic_map_fn && opt_plan) { fprintf(stderr, "[::] ERROR: --genetic-map changes files --plan does not make; use one of them.\n"); exit(1); }
+    if (genetic_map_fn && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --genetic-map needs --log-stats and --states: it measures the distances their switch penalties are scaled by.\n"); exit(1); }
+    if (genetic_map_fn && !has_switch_scale) { fprintf(stderr, "[::] ERROR: --genetic-map needs --switch-scale X: it says in which unit X and the distances between windows are measured.\n"); exit(1); }
+    if (genetic_map_fn)
+        gmap_read(genetic_map_fn);
     if (opt_log_stats && opt_states) {
         const double pen[3] = {opt_p01, opt_p02, opt_p12};
         static const char *const pen_name[3] = {"--p01", "--p02", "--p12"};

@@ -335,6 +335,34 @@ int ibdg_log2_segments_chains_host(const double *log2_tab, size_t n_win, double 
 int ibdg_set_window_chains(ibdg_ctx *ctx, const uint32_t *starts, size_t n_starts);
 /* The number of chains of the current site list: the starts set plus window 0's; 0 without windows. */
 size_t ibdg_num_window_chains(const ibdg_ctx *ctx);
+/* Step shifts: every step of the chain pays the same p01 / p02 / p12 in the calls above; a step shift gives each
+ * window its own.  shift[n_win]: one int32 per window in quanta of 2^-16 bit, |shift[w]| <= 2^30; shift[0] is ignored.  For a
+ * window w >= 1 that does not start a chain the step into w uses P_xy(w) = min(0, max(-2^40, P_xy + shift[w])) for xy = 01, 02,
+ * 12 (P_xy = llrint(log2(p_xy) * 65536), the path's integers) and 0 on the diagonal: a shift of +65536 doubles the switch
+ * weights of that step, capped at 1, a shift of -65536 halves them.  A chain start wins over the shift (penalty 0, a segment
+ * begins); a shift alone never begins a segment.  The path takes its step with these integers; the posteriors take the
+ * weights of these integers by the emissions' rule (a weight below 2^-1000 is 0), so that all shifts 0 gives the bytes of
+ * no shifts for p >= 2^-1000; the segments change through the path and the posteriors only.  The three functions below are
+ * the _chains_host functions with the shifts as one more argument; NULL gives their bytes.  Errors, beside theirs: an entry
+ * w >= 1 outside +-2^30 (the message names it). */
+int ibdg_log2_states_steps_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, uint8_t *path,
+                                int64_t *score, uint64_t count[3], const uint32_t *starts, size_t n_starts, const int32_t *shift);
+int ibdg_log2_posteriors_steps_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
+                                    double expect[3], double *log2_z, const uint32_t *starts, size_t n_starts,
+                                    const int32_t *shift);
+int ibdg_log2_segments_steps_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, int with_post,
+                                  const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap,
+                                  uint64_t *n_seg, uint64_t summary[12], const uint32_t *starts, size_t n_starts,
+                                  const int32_t *shift);
+/* The step shifts of the current site list, for ibdg_window_log2_states / _posteriors / _segments and ibdg_get_log2_segments on
+ * the device: the same bytes as the three functions above with these shifts (and the chains set).  n: ibdg_num_windows, or 0
+ * (shift may be NULL) to clear them.  Their lifetime is the chains': a later upload of sites or of a panel clears them, an
+ * ibdg_run does not; the call makes the paths, posteriors and records kept from earlier calls stale; it adds no launch to any
+ * call and nothing to ibdg_run.  Errors: no valid site list, an n that is neither, NULL shift with n > 0, an entry outside
+ * +-2^30; a refused call leaves the steps as they were. */
+int ibdg_set_window_steps(ibdg_ctx *ctx, const int32_t *shift, size_t n);
+/* 1 if the current site list has step shifts, else 0. */
+int ibdg_has_window_steps(const ibdg_ctx *ctx);
 /* Alt-allele count of panel rows [first_row, first_row+n): out[n] (for tests). */
 int ibdg_get_alt_counts(ibdg_ctx *ctx, size_t first_row, size_t n, uint32_t *out);
 
