@@ -2656,6 +2656,130 @@ int ibdg_get_log2_segments(ibdg_ctx *c, ibdg_segment *seg, size_t cap)
     return quiesce(c);
 }
 
+int ibdg_log2_samples_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                           size_t n_starts, const int32_t *shift, size_t n_samples, uint64_t seed, uint64_t stream,
+                           const uint64_t *pos_first, const uint64_t *pos_last, uint8_t *paths, uint64_t *out)
+{
+    char msg[256];
+    if (ibdg::log2_samples_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, shift, n_samples, seed, stream, pos_first,
+                                pos_last, paths, out, msg, sizeof msg))
+        return fail(nullptr, "%s", msg);
+    return 0;
+}
+
+// The draws' scratch bound: the paths, records and summaries of the pairs in flight stay under this many bytes.
+// IBDG_SAMPLE_SCRATCH_BYTES is for tests that want more than one chunk on a small shape; ibdg_window_log2_samples alone reads it.
+static size_t sample_scratch_bytes()
+{
+    const char *e = getenv("IBDG_SAMPLE_SCRATCH_BYTES");
+    const unsigned long long v = e ? strtoull(e, nullptr, 10) : 0;
+    return v ? (size_t)v : (size_t)256 << 20;
+}
+
+// the alpha stage, under the stages' rule (enqueue_posteriors)
+static int enqueue_alpha(ibdg_ctx *c, const LogCall &L)
+{
+    ibdg_ctx::LogStates &S = c->ls;
+    if (ensure(c, S.alpha, L.T * L.n_win * 24) || ensure(c, S.ptab, 4096))
+        return 1;
+    if (S.fresh(S.ALPHA, L.P)) return 0;
+    HIP_TRY(c, hipMemcpyAsync(S.ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
+    ibdg::launch_log2_alpha((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)L.T, L.P, L.a, (const double *)S.ptab.p,
+                            S.mask(), S.shift(), (double *)S.alpha.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    S.made(S.ALPHA, L.P);
+    return 0;
+}
+
+// the draws of pairs p0 .. p0 + n - 1 (pair p: individual p / K, draw p % K) into `spath` and words 0..2 of `srec`, behind
+// enqueue_alpha and the streams' upload
+static int enqueue_sample_paths(ibdg_ctx *c, size_t n_win, uint64_t p0, size_t n)
+{
+    ibdg_ctx::LogStates &S = c->ls;
+    ibdg::launch_log2_sample_paths((const double *)S.alpha.p, (uint32_t)n_win, p0, (uint32_t)n, (uint32_t)S.smp.K, S.smp.P, S.smp.a,
+                                   (const double *)S.ptab.p, S.mask(), S.shift(), S.smp.seed, (const uint64_t *)S.sstream.p,
+                                   (uint8_t *)S.spath.p, (uint64_t *)S.srec.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+// Sampled paths (k_log2_alpha, k_log2_sample_paths, k_log2_segments_count over the drawn paths, k_log2_sample_records): the
+// alpha stage, then chunks of pairs under the scratch bound, each chunk's records out behind it.
+int ibdg_window_log2_samples(ibdg_ctx *c, double p01, double p02, double p12, size_t n_samples, uint64_t seed, const uint64_t *stream,
+                             const uint64_t *pos_first, const uint64_t *pos_last, uint64_t *out)
+{
+    if (!c) return 1;
+    LogCall L;
+    const char *own = !out ? "NULL out" : !stream ? "NULL stream" : pos_first && !pos_last ? "pos_first without pos_last"
+                      : pos_last && !pos_first ? "pos_last without pos_first" : nullptr;
+    if (log_call_begin(c, __func__, own, "of the path", p01, p02, p12, L)) return 1;
+    const size_t T = L.T, n_win = L.n_win, K = n_samples;
+    if (K < 1 || K > ibdg::SAMPLE_MAX_DRAWS)
+        return fail(c, "[::] ERROR in ibdg_window_log2_samples: n_samples = %zu is not in 1 .. %zu", K, ibdg::SAMPLE_MAX_DRAWS);
+    for (size_t w = 0; pos_first && w < n_win; ++w)
+        if (pos_last[w] < pos_first[w])
+            return fail(c, "[::] ERROR in ibdg_window_log2_samples: window %zu ends at %llu, before its start %llu", w,
+                        (unsigned long long)pos_last[w], (unsigned long long)pos_first[w]);
+    ibdg_ctx::LogStates &S = c->ls;
+    S.smp.ok = false;
+    if (T == 0) return 0;
+    if (n_win == 0) {
+        memset(out, 0, T * K * ibdg::SAMPLE_RECORD * sizeof *out);
+        return 0;
+    }
+    const size_t pairs = T * K, per_pair = n_win + 8 * (ibdg::SAMPLE_RECORD + 13);
+    size_t chunk = sample_scratch_bytes() / per_pair;
+    chunk = chunk < 1 ? 1 : chunk > pairs ? pairs : chunk;
+    chunk = chunk > ((size_t)1 << 30) ? (size_t)1 << 30 : chunk;       // (a launch counts its pairs in 32 bits)
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((pos_first && ensure(c, S.spos, n_win * 16)) || ensure(c, S.sstream, T * 8) || ensure(c, S.spath, chunk * n_win) ||
+        ensure(c, S.srec, chunk * 8 * ibdg::SAMPLE_RECORD) || ensure(c, S.ssum, chunk * 104) || join_streams(c))
+        return 1;
+    const uint64_t *d_first = nullptr, *d_last = nullptr;
+    if (pos_first) {
+        d_first = (const uint64_t *)S.spos.p, d_last = d_first + n_win;
+        HIP_TRY(c, hipMemcpyAsync(S.spos.p, pos_first, n_win * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync((char *)S.spos.p + n_win * 8, pos_last, n_win * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(S.sstream.p, stream, T * 8, hipMemcpyHostToDevice, c->stream));
+    if (enqueue_alpha(c, L)) return 1;
+    S.smp.K = K, S.smp.seed = seed;
+    S.smp.stream.assign(stream, stream + T);
+    for (int i = 0; i < 3; ++i)
+        S.smp.P[i] = L.P[i], S.smp.a[i] = L.a[i];
+    for (size_t p0 = 0; p0 < pairs; p0 += chunk) {
+        const size_t n = pairs - p0 < chunk ? pairs - p0 : chunk;
+        if (enqueue_sample_paths(c, n_win, p0, n)) return 1;
+        ibdg::launch_log2_segments_count((const uint8_t *)S.spath.p, (uint32_t)n_win, (uint32_t)n, d_first, d_last, S.mask(),
+                                         (uint64_t *)S.ssum.p, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        ibdg::launch_log2_sample_records((const uint64_t *)S.ssum.p, (uint32_t)n, (uint64_t *)S.srec.p, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(out + p0 * ibdg::SAMPLE_RECORD, S.srec.p, n * 8 * ibdg::SAMPLE_RECORD, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (quiesce(c)) return 1;
+    S.smp.ok = true;
+    return 0;
+}
+
+// One draw again: the pair's workgroup alone, its path out.  The streams on the device are the call's own still (`sstream` has
+// no other writer), alpha is fresh as long as smp.ok stands (drop() clears both).
+int ibdg_get_log2_sample_path(ibdg_ctx *c, size_t t, size_t k, uint8_t *path)
+{
+    if (!c) return 1;
+    ibdg_ctx::LogStates &S = c->ls;
+    if (!c->have_results || !S.smp.ok || !S.fresh(S.ALPHA, S.smp.P))
+        return fail(c, "[::] ERROR in ibdg_get_log2_sample_path: no ibdg_window_log2_samples call since the last ibdg_run or change of chains or steps");
+    const size_t T = S.smp.stream.size(), n_win = c->sites.n_win;
+    if (t >= T) return fail(c, "[::] ERROR in ibdg_get_log2_sample_path: individual %zu of %zu", t, T);
+    if (k >= S.smp.K) return fail(c, "[::] ERROR in ibdg_get_log2_sample_path: draw %zu of %zu", k, S.smp.K);
+    if (!path) return fail(c, "[::] ERROR in ibdg_get_log2_sample_path: NULL path");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (join_streams(c) || enqueue_sample_paths(c, n_win, (uint64_t)t * S.smp.K + k, 1)) return 1;
+    HIP_TRY(c, hipMemcpyAsync(path, S.spath.p, n_win, hipMemcpyDeviceToHost, c->stream));
+    return quiesce(c);
+}
+
 int ibdg_get_alt_counts(ibdg_ctx *c, size_t first_row, size_t n, uint32_t *out)
 {
     if (!c) return 1;

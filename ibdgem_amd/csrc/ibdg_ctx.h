@@ -378,15 +378,29 @@ struct ibdg_ctx {
     // on the device (`cshift`, uploaded by the setter behind a host wait, read by k_log2_states and k_log2_posteriors; shift()
     // is NULL without steps).  Their lifetime is the chains' in every respect: the same generation counter, the same two
     // places that clear them (steps_clear), and a run that does not.
+    // The draws: a third kept product under the same rule and key,
+    //   alpha      `alpha` (the forward vectors [T][n_win][3])                                        k_log2_alpha
+    // made by the first ibdg_window_log2_samples that finds it stale and by no other call; `smp` is what that call was made with
+    // (penalties, K, seed, the streams, host and device), for ibdg_get_log2_sample_path to draw one path again -- dropped with
+    // the products.  `spath` (the drawn paths of the pairs in flight), `srec` (their records) and `ssum` (their summaries
+    // [pairs][13]) are scratch of one chunk of pairs.
     // The rest is scratch of one call: `ptab` (the two tables, uploaded with every posteriors launch), `spos` (the windows'
     // positions [2][n_win]), `sout` (summaries and counts [T][13]), `soff` (record offsets [T]), `recs` (the records).
     struct LogStates {
-        DevBuf path, score, count, post, pout, ptab, spos, sout, soff, recs, cmask, cshift;
-        enum Product { PATH, POST };
-        bool have[2] = {false, false};
-        int64_t P[2][3] = {};
+        DevBuf path, score, count, post, pout, ptab, spos, sout, soff, recs, cmask, cshift, alpha, sstream, spath, srec, ssum;
+        enum Product { PATH, POST, ALPHA };
+        bool have[3] = {false, false, false};
+        int64_t P[3][3] = {};
+        struct Draws {
+            bool ok = false;
+            int64_t P[3] = {};
+            double a[3] = {};
+            size_t K = 0;
+            uint64_t seed = 0;
+            std::vector<uint64_t> stream;
+        } smp;
         std::vector<uint32_t> chains;    // the chain starts of the site list at hand
-        uint64_t chain_gen = 1, gen[2] = {0, 0};     // bumped with every change of `chains` or `steps`; what each product was made for
+        uint64_t chain_gen = 1, gen[3] = {0, 0, 0};     // bumped with every change of `chains` or `steps`; what each product was made for
         const uint32_t *mask() const { return chains.empty() ? nullptr : (const uint32_t *)cmask.p; }
         void chains_clear() { if (!chains.empty()) ++chain_gen; chains.clear(); drop(); }
         std::vector<int32_t> steps;      // the step shifts of the site list at hand
@@ -401,8 +415,12 @@ struct ibdg_ctx {
         bool records_fresh() const { return recs_ok; }
         void records_made() { recs_ok = true; }
         void records_drop() { recs_ok = false; }
-        void drop() { have[PATH] = have[POST] = recs_ok = false; }
-        void free_bufs() { release_all({&path, &score, &count, &post, &pout, &ptab, &spos, &sout, &soff, &recs, &cmask, &cshift}); }
+        void drop() { have[PATH] = have[POST] = have[ALPHA] = recs_ok = smp.ok = false; }
+        void free_bufs()
+        {
+            release_all({&path, &score, &count, &post, &pout, &ptab, &spos, &sout, &soff, &recs, &cmask, &cshift, &alpha, &sstream, &spath,
+                         &srec, &ssum});
+        }
     } ls;
 
     // The finalising step of the last run of single individuals (k_ld_finalize's work) when it has been left to the NEXT

@@ -386,6 +386,19 @@ void launch_log2_segments_count(const uint8_t *path, uint32_t n_win, uint32_t n_
 void launch_log2_segments_write(const double *win_log2, const uint8_t *path, const double *post, uint32_t n_win, uint32_t n_targets,
                                 const uint64_t *off, const uint32_t *starts, ibdg_segment *seg, hipStream_t st);
 
+// Sampled paths (k_log2_alpha, k_log2_sample_paths, k_log2_sample_records in ibdg_states.hip; ibdg_window_log2_samples; the
+// definition is in ibdg_states.h).  alpha: the launch of launch_log2_posteriors, alpha [T][n_win][3] out.  sample_paths: a
+// workgroup per (individual, draw) pair, grid-stride over the n_pairs pairs p0 .. p0 + n_pairs - 1 (pair p: individual p / K, draw
+// p % K) under STATES_MAX_BLOCKS; stream [T]: the individuals' streams on the device; path [n_pairs][n_win]: the drawn paths (the
+// maps on the way); rec [n_pairs][15]: words 0..2, the windows per state.  sample_records: words 3..14 from sout [n_pairs][13] as
+// launch_log2_segments_count leaves it over those paths.  One launch each on `st`, no atomics.
+void launch_log2_alpha(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], const double a[3],
+                       const double *tables, const uint32_t *starts, const int32_t *shift, double *alpha, hipStream_t st);
+void launch_log2_sample_paths(const double *alpha, uint32_t n_win, uint64_t p0, uint32_t n_pairs, uint32_t K, const int64_t P[3],
+                              const double a[3], const double *tables, const uint32_t *starts, const int32_t *shift, uint64_t seed,
+                              const uint64_t *stream, uint8_t *path, uint64_t *rec, hipStream_t st);
+void launch_log2_sample_records(const uint64_t *sout, uint32_t n_pairs, uint64_t *rec, hipStream_t st);
+
 // log2 of the window likelihoods (ibdg_ld_log.hip, option "log_windows"): win_log2[T][n_win][3].
 // k_ld_log: columns 0 and 1 of an --LD run from the layout's tiles, segments, window constants and power tables (what
 // the counting kernels read), the background multiplicities without any comparison individual's exclusion and their sum.

@@ -320,8 +320,28 @@ IBDG_HD void post_emission_weights(const PostIn &in, uint32_t w, double b[3])
         b[s] = post_weight(e[s], in.T, in.T + 256);
 }
 
-// M_w of window w >= 1 from its b_w: the penalty weights -- with shifts the weights of the window's own penalties P_xy(w), formed
-// from the integers with the tables --, or (1, 1, 1) where w starts a chain, by selects
+// a[0..2] = a01, a02, a12 of the step into window w >= 1: the penalty weights -- with shifts the weights of the window's own
+// penalties P_xy(w), formed from the integers with the tables --, or (1, 1, 1) where w starts a chain, by selects
+IBDG_HD void post_window_weights(const PostIn &in, uint32_t w, double a[3])
+{
+    const bool st = chain_start(in.starts, w);
+    if (in.shift) {
+        const int32_t sh = in.shift[w];        // (asked first: its address waits for nothing)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double aw = post_weight(states_shift_penalty(in.P[k], sh), in.T, in.T + 256);
+            a[k] = st ? 1.0 : aw;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            a[k] = st ? 1.0 : in.a[k];
+    }
+}
+
+// M_w of window w >= 1 from its b_w and those weights (formed here as there, not by a call: the posteriors' kernel keeps the
+// instructions it had before the weights were asked for on their own; tools/log_samples_asan.cpp holds the two against each other
+// at every window, with and without chains and shifts, and tests/test_log_samples_asan.py runs it)
 IBDG_HD void post_window_matrix(const PostIn &in, uint32_t w, const double b[3], double M[9])
 {
     const bool st = chain_start(in.starts, w);
@@ -553,5 +573,136 @@ IBDG_HD void seg_summary_add(uint64_t v[12], unsigned s, uint64_t len, uint64_t 
 int log2_segments_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
                        size_t n_starts, const int32_t *shift, int with_post, const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg,
                        size_t seg_cap, uint64_t *n_seg, uint64_t summary[12], char *err, size_t err_len);
+
+// ---- sampled paths: K paths drawn from P(path | all windows) under the weights of 4.9 -----------------------
+//
+// Forward filtering, backward sampling.  Inputs: the table, the penalties, the chains and shifts of the posteriors, the number of
+// draws K (1 .. SAMPLE_MAX_DRAWS), a 64-bit seed and a 64-bit stream per individual (callers pass the individual's index in the
+// panel: a draw depends on (seed, stream, k) and on nothing about batches, slots or devices).
+//   alpha     alpha_w[0..2] = the vector v that step 4 above holds at window w after post_rescale (b_0 at window 0), mantissas
+//             only: the common exponent cancels in the draw.  post_block_alpha is that half of step 4 and writes them
+//             [n_win][3]; the steps before it (post_block_matrix, post_forward_walk) are the posteriors' own.
+//   numbers   sm64(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+//             0x94D049BB133111EB; z ^ z >> 31 (uint64, wrapping).  key(t, k) = sm64(sm64(sm64(seed) ^ stream_t) ^ k), r(t, k, w) =
+//             sm64(key ^ w), U = (double)(r >> 11) * 2^-53 in [0, 1), exact.  One sm64 per window and draw, integers only.
+//   a draw    for w = n_win - 1 .. 0: c_q = alpha_w[q] at the last window, else c_q = alpha_w[q] * a_{w+1}[q][s'] with s' the
+//             state drawn at w + 1 and a_{w+1} the switch weights of the step into w + 1 (post_window_weights: (1, 1, 1) at a
+//             chain start, the shifted weights with shifts, 1 on the diagonal; b_{w+1}[s'] is common to the three and left
+//             out).  D = (c_0 + c_1) + c_2, x = U * D; the state is 0 if x < c_0, else 1 if x < c_0 + c_1, else 2
+//             (sample_pick).  fp64, no contraction.
+//   x < D     for every normal D: U <= 1 - 2^-53, so U D <= D - D 2^-53 <= D - ulp(D) / 2, and the product rounded to nearest
+//             is at most the double below D.  With x < D = (c_0 + c_1) + c_2 a state of weight 0 is never drawn: c_2 = 0 gives
+//             x < c_0 + c_1, and c_1 = 0 besides gives x < c_0; c_0 = 0 fails x < c_0 always.  (A subnormal D needs every
+//             c_q below 2^-1022 under an alpha whose largest entry is in [1, 2): an s' whose own probability is below 2^-1000.)
+//   total     D = 0 gives x = 0 and state 2.  That needs an s' of weight 0 at w + 1, which by the line above is never drawn.
+//   maps      the three answers for s' = 0, 1, 2 are window w's map in the form of `from` (sample_map); the last window's map
+//             is constant (sample_last_map).  Maps over three states compose associatively (map_after), so a draw is the same
+//             bytes for any blocking: the kernel composes per block and scans as k_log2_states does, the twin walks once from
+//             the back, and neither needs an order rule beyond alpha's.
+//   record    uint64[15] per draw: [0..2] the windows per state, [3..14] the 12 words of the segments' summary above for the
+//             drawn path (seg_start, seg_summary_add, chains respected; the last six 0 without positions).
+constexpr size_t SAMPLE_MAX_DRAWS = 65536;
+constexpr int SAMPLE_RECORD = 15;
+
+IBDG_HD uint64_t sm64(uint64_t z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ z >> 27) * 0x94D049BB133111EBull;
+    return z ^ z >> 31;
+}
+
+IBDG_HD uint64_t sample_key(uint64_t seed, uint64_t stream, uint64_t k)
+{
+    return sm64(sm64(sm64(seed) ^ stream) ^ k);
+}
+
+// U of window w under a draw's key
+IBDG_HD double sample_u(uint64_t key, uint32_t w)
+{
+    return (double)(sm64(key ^ w) >> 11) * post_pow2(-53);
+}
+
+IBDG_HD unsigned sample_pick(double c0, double c1, double c2, double U)
+{
+    const double c01 = c0 + c1;
+    const double x = U * (c01 + c2);
+    return x < c0 ? 0u : x < c01 ? 1u : 2u;
+}
+
+// the state at window w given s' = sp at w + 1, from alpha_w and a = a01, a02, a12 of the step into w + 1 (the product with the
+// diagonal's 1.0 is exact)
+IBDG_HD unsigned sample_state(const double al[3], const double a[3], unsigned sp, double U)
+{
+    const double c0 = al[0] * (sp == 0 ? 1.0 : sp == 1 ? a[0] : a[1]);
+    const double c1 = al[1] * (sp == 0 ? a[0] : sp == 1 ? 1.0 : a[2]);
+    const double c2 = al[2] * (sp == 0 ? a[1] : sp == 1 ? a[2] : 1.0);
+    return sample_pick(c0, c1, c2, U);
+}
+
+// window w's map: s' at w + 1 -> the state at w
+IBDG_HD unsigned sample_map(const double al[3], const double a[3], double U)
+{
+    return sample_state(al, a, 0, U) | sample_state(al, a, 1, U) << 2 | sample_state(al, a, 2, U) << 4;
+}
+
+// the last window's: its state whatever comes in
+IBDG_HD unsigned sample_last_map(const double al[3], double U)
+{
+    return sample_pick(al[0], al[1], al[2], U) * (1u | 1u << 2 | 1u << 4);
+}
+
+// the map of window w of a draw (n_win windows, alpha [n_win][3]), as the kernel's threads form it ...
+IBDG_HD unsigned sample_window_map(const PostIn &in, const double *__restrict__ alpha, uint32_t n_win, uint32_t w, uint64_t key)
+{
+    const double *al = alpha + 3 * (size_t)w;
+    const double U = sample_u(key, w);
+    if (w + 1 == n_win)
+        return sample_last_map(al, U);
+    double a[3];
+    post_window_weights(in, w + 1, a);
+    return sample_map(al, a, U);
+}
+
+// ... and that map's answer for sp alone, which is all the twin's single walk needs: map_at(sample_window_map(..), sp)
+IBDG_HD unsigned sample_window_state(const PostIn &in, const double *__restrict__ alpha, uint32_t n_win, uint32_t w, uint64_t key,
+                                     unsigned sp)
+{
+    const double *al = alpha + 3 * (size_t)w;
+    const double U = sample_u(key, w);
+    if (w + 1 == n_win)
+        return sample_pick(al[0], al[1], al[2], U);
+    double a[3];
+    post_window_weights(in, w + 1, a);
+    return sample_state(al, a, sp, U);
+}
+
+// the forward half of step 4 for the block of windows [w0, w1), w0 < w1, from F = F_b and its exponent (not used by block 0):
+// alpha_w into alpha [n_win][3]
+IBDG_HD void post_block_alpha(const PostIn &in, uint32_t w0, uint32_t w1, const double *F, int Fexp, double *__restrict__ alpha)
+{
+    double bw[3], M[9];
+    double v[3] = {F[0], F[1], F[2]};
+    int e = Fexp;
+    for (uint32_t w = w0; w < w1; ++w) {
+        double *p = alpha + 3 * (size_t)w;
+        post_emission_weights(in, w, bw);
+        if (w == 0) {
+            v[0] = bw[0], v[1] = bw[1], v[2] = bw[2];
+            e = 0;
+        } else {
+            post_window_matrix(in, w, bw, M);
+            post_vec_mat(v, M);
+            post_rescale<3>(v, e);
+        }
+        p[0] = v[0], p[1] = v[1], p[2] = v[2];
+    }
+}
+
+// the host twin (ibdg_log2_samples_host): K = n_samples draws of one individual under (seed, stream); paths [K][n_win] or NULL,
+// out [K][15]; pos_first, pos_last [n_win] or both NULL; starts, shift, fn as above
+int log2_samples_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                      size_t n_starts, const int32_t *shift, size_t n_samples, uint64_t seed, uint64_t stream, const uint64_t *pos_first,
+                      const uint64_t *pos_last, uint8_t *paths, uint64_t *out, char *err, size_t err_len);
 
 }  // namespace ibdg

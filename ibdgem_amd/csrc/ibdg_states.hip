@@ -3,6 +3,8 @@
 // the end) over the log2 window table of the last run.  ibdg_states.h has the definition and every step of it as a function:
 // the kernels here are its parallel callers, the host twin (ibdg_states_host.cpp) the serial one, so both give the same bits.
 // Only here: how a workgroup cuts the windows among its threads and joins their results (scan_lds, join_threads).
+// Paths drawn from the posterior (ibdg_window_log2_samples: k_log2_alpha, k_log2_sample_paths, k_log2_sample_records, behind the
+// segment kernels) use the same blocking, a workgroup per (individual, draw) pair.
 //
 // k_log2_states: a workgroup of STATES_THREADS per comparison individual, grid-stride over the individuals.  Thread b owns
 // windows [b C, (b + 1) C), C = ceil(n_win / STATES_THREADS) (Blocks).
@@ -439,6 +441,131 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_segments_write(const do
     }
 }
 
+// ---- sampled paths (ibdg_states.h) -----------------------------------------------------------------------------
+
+// k_log2_alpha: steps 1 and 2 (the forward walk alone) and the forward half of step 4 of the posteriors, with their launch, blocking
+// and step functions; alpha [T][n_win][3] out.  A kernel of its own, so that k_log2_posteriors keeps its code, its LDS and its one
+// launch.
+template <bool CH, bool SH>
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_alpha(const double *__restrict__ win_log2, uint32_t n_win, uint32_t n_targets,
+                                                               PenW W, const double *__restrict__ tables,
+                                                               const uint32_t *__restrict__ starts_arg,
+                                                               const int32_t *__restrict__ shift_arg, double *__restrict__ alpha)
+{
+    const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
+    const int32_t *__restrict__ shift = steps_of<SH>(shift_arg);
+    __shared__ double mat[STATES_THREADS][9];       // 18 KB: B_b
+    __shared__ double fin[STATES_THREADS][3];       // F_b
+    __shared__ double T[512];                       // T1, T2
+    __shared__ int mexp[STATES_THREADS], fexp[STATES_THREADS];
+
+    const uint32_t b = threadIdx.x;
+    const Blocks B(n_win);
+    const uint32_t w0 = B.begin(b), w1 = B.end(b);
+    const bool own = b < B.nbk;
+
+    T[b] = tables[b], T[b + STATES_THREADS] = tables[b + STATES_THREADS];
+    __syncthreads();
+
+    for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
+        const PostIn in = {win_log2 + (size_t)t * n_win * 3, T, {W.a[0], W.a[1], W.a[2]}, starts, shift,
+                           {W.P[0], W.P[1], W.P[2]}};
+        if (own)
+            post_block_matrix(in, w0, w1, mat[b], &mexp[b]);
+        __syncthreads();
+        if (b == 0)
+            post_forward_walk(mat[0], mexp, B.nbk, fin[0], fexp);
+        __syncthreads();
+        if (own)
+            post_block_alpha(in, w0, w1, fin[b], fexp[b], alpha + (size_t)t * n_win * 3);
+        __syncthreads();       // (LDS is reused by the next individual)
+    }
+}
+
+// k_log2_sample_paths: a workgroup per (individual, draw) pair, grid-stride over the launch's pairs; the blocking of k_log2_states,
+// whose passes 2 and 3 these are with sampled maps in place of argmax maps.
+//   pass A  a thread walks its windows backward: window w's map (state at w + 1 -> state at w) from alpha_w, the switch weights
+//           into w + 1 and r(t, k, w) (sample_window_map), kept as 6 bits in the pair's path bytes and composed into the block's
+//           map (state at the next block's first window -> state at this block's first)
+//   scan    the blocks' maps composed from the last block down (scan_lds); the last window's map is constant, so what enters
+//           behind it does not matter and there is no last_state to share
+//   pass B  every thread resolves its windows from the state the blocks behind it give, overwriting the maps; the counts meet in
+//           LDS (join_threads) and go to words 0..2 of the pair's record
+// No atomics, no transcendental; T1, T2 are read with shifts only (SH), as in k_log2_posteriors.
+template <bool CH, bool SH>
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_sample_paths(const double *__restrict__ alpha, uint32_t n_win, uint64_t p0,
+                                                                      uint32_t n_pairs, uint32_t K, PenW W,
+                                                                      const double *__restrict__ tables,
+                                                                      const uint32_t *__restrict__ starts_arg,
+                                                                      const int32_t *__restrict__ shift_arg, uint64_t seed,
+                                                                      const uint64_t *__restrict__ stream, uint8_t *__restrict__ path,
+                                                                      uint64_t *__restrict__ rec)
+{
+    const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
+    const int32_t *__restrict__ shift = steps_of<SH>(shift_arg);
+    __shared__ uint8_t maps[2][STATES_THREADS];
+    __shared__ uint32_t cnt[STATES_THREADS / 64][3];
+    __shared__ double T[SH ? 512 : 1];              // T1, T2
+
+    const uint32_t b = threadIdx.x;
+    const Blocks B(n_win);                           // (n_win >= 1)
+    const uint32_t w0 = B.begin(b), w1 = B.end(b);
+    const bool own = b < B.nbk;
+
+    if (SH) {
+        T[b] = tables[b], T[b + STATES_THREADS] = tables[b + STATES_THREADS];
+        __syncthreads();
+    }
+    const PostIn in = {nullptr, T, {W.a[0], W.a[1], W.a[2]}, starts, shift, {W.P[0], W.P[1], W.P[2]}};
+
+    for (uint32_t p = blockIdx.x; p < n_pairs; p += gridDim.x) {
+        const uint64_t g = p0 + p;
+        const uint64_t t = g / K, k = g % K;
+        const double *al = alpha + (size_t)t * n_win * 3;
+        uint8_t *pt = path + (size_t)p * n_win;
+        const uint64_t key = sample_key(seed, stream[t], k);
+
+        // pass A
+        unsigned blk = MAP_ID;
+        if (own) {
+            // (four windows a trip: their rows of alpha wait for nothing the loop makes, and asked for together they cost one
+            // latency, not four -- 58 ms against 87 for the call at 34 599 windows)
+#pragma unroll 4
+            for (uint32_t w = w1; w-- > w0;) {
+                const unsigned m = sample_window_map(in, al, n_win, w, key);
+                pt[w] = (uint8_t)m;
+                blk = map_after(m, blk);
+            }
+        }
+        // maps[..][j] becomes block j's map after block j + 1's after ... after the last block's
+        const int cur = scan_lds<true>(maps, b, (uint8_t)blk, [](unsigned x, unsigned y) { return map_after(x, y); });
+        // pass B
+        uint32_t n[3] = {0, 0, 0};
+        if (own) {
+            unsigned st = b + 1 < B.nbk ? map_at(maps[cur][b + 1], 0) : 0;     // the state at window w1 (none behind the last)
+#pragma unroll 8                  // (likewise the maps' bytes)
+            for (uint32_t w = w1; w-- > w0;) {
+                st = map_at(pt[w], st);
+                pt[w] = (uint8_t)st;
+                n[0] += st == 0, n[1] += st == 1, n[2] += st == 2;
+            }
+        }
+        const uint32_t sum = join_threads(n, cnt, b, [](int, uint32_t x, uint32_t y) { return x + y; });
+        if (b < 3)
+            rec[(size_t)p * SAMPLE_RECORD + b] = sum;
+        __syncthreads();       // (LDS is reused by the next pair)
+    }
+}
+
+// k_log2_sample_records: words 3..14 of every pair's record = the 12 summary words k_log2_segments_count left for its path
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_sample_records(const uint64_t *__restrict__ sout, uint32_t n_pairs,
+                                                                        uint64_t *__restrict__ rec)
+{
+    const size_t i = (size_t)blockIdx.x * STATES_THREADS + threadIdx.x;
+    if (i < (size_t)n_pairs * 12)
+        rec[i / 12 * SAMPLE_RECORD + 3 + i % 12] = sout[i / 12 * 13 + i % 12];
+}
+
 // the one launch of all four: nothing for no windows or no individuals, else a workgroup per individual under STATES_MAX_BLOCKS
 template <typename K, typename... A>
 void launch_kernel(K kernel, uint32_t n_win, uint32_t n_targets, hipStream_t st, A... args)
@@ -485,6 +612,29 @@ void launch_log2_segments_write(const double *win_log2, const uint8_t *path, con
                                 const uint64_t *off, const uint32_t *starts, ibdg_segment *seg, hipStream_t st)
 {
     launch_per_individual(k_log2_segments_write, starts, n_win, n_targets, st, win_log2, path, post, n_win, n_targets, off, starts, seg);
+}
+
+void launch_log2_alpha(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], const double a[3],
+                       const double *tables, const uint32_t *starts, const int32_t *shift, double *alpha, hipStream_t st)
+{
+    launch_per_individual_steps(k_log2_alpha, starts, shift, n_win, n_targets, st, win_log2, n_win, n_targets,
+                                PenW{{a[0], a[1], a[2]}, {P[0], P[1], P[2]}}, tables, starts, shift, alpha);
+}
+
+void launch_log2_sample_paths(const double *alpha, uint32_t n_win, uint64_t p0, uint32_t n_pairs, uint32_t K, const int64_t P[3],
+                              const double a[3], const double *tables, const uint32_t *starts, const int32_t *shift, uint64_t seed,
+                              const uint64_t *stream, uint8_t *path, uint64_t *rec, hipStream_t st)
+{
+    launch_per_individual_steps(k_log2_sample_paths, starts, shift, n_win, n_pairs, st, alpha, n_win, p0, n_pairs, K,
+                                PenW{{a[0], a[1], a[2]}, {P[0], P[1], P[2]}}, tables, starts, shift, seed, stream, path, rec);
+}
+
+void launch_log2_sample_records(const uint64_t *sout, uint32_t n_pairs, uint64_t *rec, hipStream_t st)
+{
+    if (n_pairs == 0)
+        return;
+    const uint32_t grid = (uint32_t)(((size_t)n_pairs * 12 + STATES_THREADS - 1) / STATES_THREADS);
+    hipLaunchKernelGGL(k_log2_sample_records, dim3(grid), dim3(STATES_THREADS), 0, st, sout, n_pairs, rec);
 }
 
 }  // namespace ibdg

@@ -268,4 +268,83 @@ int log2_segments_host(const char *fn, const double *tab, size_t n_win, double p
     return 0;
 }
 
+// alpha [n_win][3]: steps 1 and 2 (the forward walk) and the forward half of step 4, the kernel's calls in loops over b
+static void alpha_core(const PostIn &in, size_t n_win, double *alpha)
+{
+    const Blocks B((uint32_t)n_win);
+    std::vector<double> mat(B.nbk * 9), fin(B.nbk * 3);
+    std::vector<int> mexp(B.nbk), fexp(B.nbk);
+    for (uint32_t b = 0; b < B.nbk; ++b)
+        post_block_matrix(in, B.begin(b), B.end(b), &mat[9 * b], &mexp[b]);
+    post_forward_walk(mat.data(), mexp.data(), B.nbk, fin.data(), fexp.data());
+    for (uint32_t b = 0; b < B.nbk; ++b)
+        post_block_alpha(in, B.begin(b), B.end(b), &fin[3 * b], fexp[b], alpha);
+}
+
+// a draw's record from its path: the windows per state and the segments' summary, one pass in window order
+static void sample_record(const uint8_t *path, size_t n_win, const uint32_t *mask, const uint64_t *pos_first, const uint64_t *pos_last,
+                          uint64_t rec[SAMPLE_RECORD])
+{
+    for (int i = 0; i < SAMPLE_RECORD; ++i)
+        rec[i] = 0;
+    for (size_t f = 0; f < n_win;) {
+        const unsigned s = path[f];
+        size_t w = f + 1;
+        while (w < n_win && !seg_start(mask, (uint32_t)w, s, path[w]))
+            ++w;
+        rec[s] += w - f;
+        seg_summary_add(rec + 3, s, w - f, pos_first ? pos_last[w - 1] - pos_first[f] + 1 : 0);
+        f = w;
+    }
+}
+
+int log2_samples_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                      size_t n_starts, const int32_t *shift, size_t n_samples, uint64_t seed, uint64_t stream, const uint64_t *pos_first,
+                      const uint64_t *pos_last, uint8_t *paths, uint64_t *out, char *err, size_t err_len)
+{
+    int64_t P[3];
+    std::vector<uint32_t> own;
+    const uint32_t *mask;
+    if (check_log_args(fn, !out ? "out" : nullptr, tab, n_win, p01, p02, p12, "of the path", P, err, err_len))
+        return 1;
+    if (n_samples < 1 || n_samples > SAMPLE_MAX_DRAWS) {
+        snprintf(err, err_len, "[::] ERROR in %s: n_samples = %zu is not in 1 .. %zu", fn, n_samples, SAMPLE_MAX_DRAWS);
+        return 1;
+    }
+    if (!pos_first != !pos_last) {
+        snprintf(err, err_len, "[::] ERROR in %s: %s without %s", fn, pos_first ? "pos_first" : "pos_last",
+                 pos_first ? "pos_last" : "pos_first");
+        return 1;
+    }
+    for (size_t w = 0; pos_first && w < n_win; ++w)
+        if (pos_last[w] < pos_first[w]) {
+            snprintf(err, err_len, "[::] ERROR in %s: window %zu ends at %llu, before its start %llu", fn, w,
+                     (unsigned long long)pos_last[w], (unsigned long long)pos_first[w]);
+            return 1;
+        }
+    if (own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len) || shift_check(fn, shift, n_win, err, err_len))
+        return 1;
+    if (n_win == 0) {
+        for (size_t i = 0; i < n_samples * SAMPLE_RECORD; ++i)
+            out[i] = 0;
+        return 0;
+    }
+    PostIn in = {tab, post_tables(), {}, mask, shift, {P[0], P[1], P[2]}};
+    post_penalty_weights(P, in.a);
+    std::vector<double> alpha(n_win * 3);
+    alpha_core(in, n_win, alpha.data());
+    std::vector<uint8_t> one(paths ? 0 : n_win);
+    for (size_t k = 0; k < n_samples; ++k) {
+        uint8_t *path = paths ? paths + k * n_win : one.data();
+        const uint64_t key = sample_key(seed, stream, k);
+        unsigned st = 0;                              // (the last window's map takes anything)
+        for (size_t w = n_win; w-- > 0;) {
+            st = sample_window_state(in, alpha.data(), (uint32_t)n_win, (uint32_t)w, key, st);
+            path[w] = (uint8_t)st;
+        }
+        sample_record(path, n_win, mask, pos_first, pos_last, out + k * SAMPLE_RECORD);
+    }
+    return 0;
+}
+
 }  // namespace ibdg

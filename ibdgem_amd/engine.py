@@ -73,6 +73,10 @@ SYMBOLS = {
                                                 C.c_size_t, _P, _P, _P, C.c_size_t, _P]),
     "ibdg_set_window_steps": (C.c_int, [_P, _P, C.c_size_t]),
     "ibdg_has_window_steps": (C.c_int, [_P]),
+    "ibdg_log2_samples_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, C.c_size_t, _P, C.c_size_t,
+                                         C.c_uint64, C.c_uint64, _P, _P, _P, _P]),
+    "ibdg_window_log2_samples": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_size_t, C.c_uint64, _P, _P, _P, _P]),
+    "ibdg_get_log2_sample_path": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
     "ibdg_run_ms": (C.c_int, [_P, C.c_uint, _P]),
@@ -290,6 +294,29 @@ def log2_segments_host(log2_tab, p01, p02, p12, with_post=False, pos_first=None,
             raise EngineError("ibdg_log2_segments_host wrote behind seg_cap")
         seg = seg[:min(cap, n_seg.value)].copy()
     return seg, n_seg.value, summary
+
+
+def log2_samples_host(log2_tab, p01, p02, p12, n_samples, seed, stream, pos_first=None, pos_last=None, want_paths=True,
+                      starts=None, shift=None):
+    """n_samples IBD-state paths of one window table [n_win][3] drawn from the posterior on the host (ibdg_log2_samples_host):
+    (paths uint8 [n_samples][n_win] or None, out uint64 [n_samples][15] -- per draw the windows per state, then the segments'
+    summary of the drawn path).  seed, stream: uint64; a draw depends on them and its number alone.  starts, shift: as for
+    log2_states_host."""
+    lib = load_library()
+    tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
+    n, K = tab.shape[0], int(n_samples)
+    pf, pl = _positions(pos_first, pos_last, n)
+    rows = K if 0 < K <= 65536 else 1                       # (a refused count writes nothing)
+    paths = np.zeros((rows, n), dtype=np.uint8) if want_paths else None
+    out = np.zeros((rows, 15), dtype=np.uint64)
+    keep, ptr, ns = _starts(() if starts is None else starts)
+    sh = None if shift is None else _shift(shift, n)
+    rc = lib.ibdg_log2_samples_host(tab.ctypes.data, n, p01, p02, p12, ptr, ns, None if sh is None else sh.ctypes.data, K, seed, stream,
+                                    None if pf is None else pf.ctypes.data, None if pl is None else pl.ctypes.data,
+                                    None if paths is None else paths.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
+    return paths, out
 
 
 class Engine:
@@ -522,6 +549,27 @@ class Engine:
         seg = np.zeros(max(cap, 1), dtype=SEGMENT_DTYPE)
         self._chk(self.lib.ibdg_get_log2_segments(self.ctx, seg.ctypes.data, cap))
         return seg[:cap]
+
+    def window_log2_samples(self, p01, p02, p12, n_samples, seed, stream, pos_first=None, pos_last=None):
+        """n_samples paths per comparison individual of the last run drawn from the posterior, on the device
+        (ibdg_window_log2_samples): out uint64 [T][n_samples][15], the bytes of log2_samples_host with stream[t].  stream: uint64
+        [T], by convention the individuals' indices in the panel."""
+        T, n, K = self.lib.ibdg_num_targets(self.ctx), self.n_windows, int(n_samples)
+        pf, pl = _positions(pos_first, pos_last, n)
+        st = np.ascontiguousarray(stream, dtype=np.uint64).reshape(-1)
+        if len(st) != T:
+            raise ValueError(f"stream: {len(st)} entries, not the {T} individuals")
+        out = np.zeros((T, K if 0 < K <= 65536 else 1, 15), dtype=np.uint64)
+        self._chk(self.lib.ibdg_window_log2_samples(self.ctx, p01, p02, p12, K, seed, st.ctypes.data,
+                                                    None if pf is None else pf.ctypes.data,
+                                                    None if pl is None else pl.ctypes.data, out.ctypes.data))
+        return out
+
+    def get_log2_sample_path(self, t, k):
+        """Draw k of individual t of the last window_log2_samples call, drawn again (ibdg_get_log2_sample_path): uint8 [n_win]."""
+        path = np.zeros(max(self.n_windows, 1), dtype=np.uint8)
+        self._chk(self.lib.ibdg_get_log2_sample_path(self.ctx, t, k, path.ctypes.data))
+        return path[:self.n_windows]
 
     def set_window_chains(self, starts=()):
         """The windows >= 1 of the current site list that start a chain, for the three window_log2_* calls and

@@ -73,6 +73,10 @@ static double opt_switch_scale = 0.0;
 static const char *genetic_map_fn = NULL; /* --genetic-map FILE: the distances of --switch-scale in centimorgans along this map */
 static double *gmap_pos = NULL, *gmap_cm = NULL;    /* ... its entries: position, cumulative cM */
 static size_t gmap_n = 0;
+static int has_sample_paths = 0;         /* --sample-paths K: with --log-stats --states, K paths per individual drawn from the posterior of the weights whose best path they find */
+static unsigned long opt_sample_paths = 0;
+static int has_seed = 0;                 /* --seed N: the seed of those draws (uint64) */
+static uint64_t opt_seed = 1;
 static int opt_log_stats = 0;            /* --log-stats: --arm-stats and --states from the log2 window table (no underflow), into log* files */
 static int opt_states = 0, has_pen = 0;  /* --states: the IBD-state path of every comparison (hgpath.c), --p01/--p02/--p12 its penalties */
 static double opt_p01 = HG_DEFAULT_P01, opt_p02 = HG_DEFAULT_P02, opt_p12 = HG_DEFAULT_P12;
@@ -92,6 +96,8 @@ static struct option longopts[] = {
     {"chain-gap", required_argument, 0, 1011},
     {"switch-scale", required_argument, 0, 1012},
     {"genetic-map", required_argument, 0, 1013},
+    {"sample-paths", required_argument, 0, 1014},
+    {"seed", required_argument, 0, 1015},
     {"p01", required_argument, 0, 1008},
     {"p02", required_argument, 0, 1009},
     {"p12", required_argument, 0, 1010},
@@ -219,6 +225,18 @@ static void usage(int code)
           "  --genetic-map FILE        with --switch-scale: distances in centimorgans.  FILE: a header line, then lines of\n"
           "                            position, rate in cM/Mb (not read) and cumulative cM, positions strictly increasing;\n"
           "                            linear between two entries, the map's mean rate outside it\n"
+          "  --sample-paths K          with --log-stats --states: also K (1 .. 65536) whole paths per individual drawn from the\n"
+          "                            distribution over all paths that --posteriors sums (forward filtering, backward\n"
+          "                            sampling), for what its per-window probabilities cannot say -- how sure a segment is,\n"
+          "                            the range of the IBD1 base pairs, one long segment or five short ones:\n"
+          "                            <out>/<pileup-name>.<individual>.logsamples.txt, per draw the windows, segments, base\n"
+          "                            pairs and longest base pairs per state; and <out>/<pileup-name>.logibdsamples.txt, per\n"
+          "                            individual and state the mean and the 2.5 %, 50 % and 97.5 % order statistics of the\n"
+          "                            draws' windows, segments and base pairs and the share of draws with any IBD1 or IBD2\n"
+          "                            segment, then the same of the draws' sums over the individuals.  A draw depends on\n"
+          "                            --seed, the individual's place in the panel and its number, not on devices or batches.\n"
+          "                            With --stats-only only the second file, on one device drawn there\n"
+          "  --seed N                  with --sample-paths: the seed of the draws, 0 .. 2^64 - 1 (default 1)\n"
           "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
           "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
           "  --stats-only              with --arm-stats and/or --states: write the armstats / ibdstates file only (no\n"
@@ -1859,16 +1877,84 @@ static void switch_scale_shifts(const uint64_t *pos_first, const uint64_t *pos_l
     }
 }
 
+/* ---- --sample-paths: an individual's row of logibdsamples.txt, made when its draws are done, so that the K records of 120 bytes
+ * need not be kept to the run's end: what stays per individual is the row's text, and per run K sums of nine numbers ---- */
+enum { SMP_ROW_ROOM = 2048 };               /* 36 columns of at most 26 characters and the share */
+static pthread_mutex_t g_smp_mu = PTHREAD_MUTEX_INITIALIZER;   /* a run's totals: its output jobs add to them side by side */
+
+static int cmp_u64(const void *a, const void *b)
+{
+    const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+    return x < y ? -1 : x > y;
+}
+
+/* What K draws say of one quantity, appended to buf: v[K] is sorted in place; the mean is the integer sum divided once, the
+ * quantiles are the order statistics v[(K - 1) / 40], v[(K - 1) / 2] and v[(K - 1) - (K - 1) / 40] (integer division) */
+static size_t sample_columns(char *buf, size_t len, uint64_t *v, size_t K)
+{
+    uint64_t sum = 0;
+    for (size_t k = 0; k < K; ++k)
+        sum += v[k];
+    qsort(v, K, sizeof *v, cmp_u64);
+    return len + (size_t)snprintf(buf + len, SMP_ROW_ROOM - len, "\t%.3f\t%llu\t%llu\t%llu", (double)sum / (double)K,
+                                  (unsigned long long)v[(K - 1) / 40], (unsigned long long)v[(K - 1) / 2],
+                                  (unsigned long long)v[(K - 1) - (K - 1) / 40]);
+}
+
+/* A row behind its ID, N_SEGMENTS and K, from K rows of nine numbers, v[k] = windows, segments and base pairs per state: per state
+ * the three quantities' columns, then the share of draws with an IBD1 or IBD2 segment and the line's end.  buf [SMP_ROW_ROOM],
+ * col [K]: scratch */
+static void sample_row_tail(char *buf, const uint64_t (*v)[9], size_t K, uint64_t *col)
+{
+    size_t any = 0, len = 0;
+    for (int s = 0; s < 3; ++s)
+        for (int q = 0; q < 3; ++q) {
+            for (size_t k = 0; k < K; ++k)
+                col[k] = v[k][3 * q + s];
+            len = sample_columns(buf, len, col, K);
+        }
+    for (size_t k = 0; k < K; ++k)
+        any += v[k][3 + 1] + v[k][3 + 2] > 0;
+    snprintf(buf + len, SMP_ROW_ROOM - len, "\t%.6f\n", (double)any / (double)K);
+}
+
+/* An individual's draws are done: rec [K][15] (ibdg_window_log2_samples / ibdg_log2_samples_host).  Its row's tail as text of its
+ * own, and draw k added to the run's totals tot [K][9].  NULL: out of memory (nothing was added) */
+static char *sample_individual_row(const uint64_t *rec, size_t K, uint64_t (*tot)[9])
+{
+    uint64_t (*nine)[9] = malloc(K * sizeof *nine), *col = malloc(K * sizeof *col);
+    char *row = malloc(SMP_ROW_ROOM);
+    if (nine && col && row) {
+        for (size_t k = 0; k < K; ++k)
+            for (int i = 0; i < 9; ++i)
+                nine[k][i] = rec[15 * k + (i < 6 ? i : i + 3)];        /* windows [0..2], segments [3..5], base pairs [9..11] */
+        pthread_mutex_lock(&g_smp_mu);
+        for (size_t k = 0; k < K; ++k)
+            for (int i = 0; i < 9; ++i)
+                tot[k][i] += nine[k][i];
+        pthread_mutex_unlock(&g_smp_mu);
+        sample_row_tail(row, (const uint64_t (*)[9])nine, K, col);
+    } else {
+        free(row);
+        row = NULL;
+    }
+    free(nine);
+    free(col);
+    return row;
+}
+
 /* ---- one comparison spread over several GPUs (window ranges, host-side gather) ------------ */
 /* What the run's statistics files hold of one comparison individual, the same record from the device (or the individual's
  * output job) to the files: a shard's double-double arm sums (ibdg_window_llr_sums), of which the run keeps the four rounded
  * sums p20, q20, p10, q10 in arm[0..3]; its windows in IBD0, IBD1, IBD2; its expected windows per state and log2 Z; its line of
- * logibdsegments.txt (the summary of ibdg_window_log2_segments / ibdg_log2_segments_host). */
+ * logibdsegments.txt (the summary of ibdg_window_log2_segments / ibdg_log2_segments_host); its row of
+ * logibdsamples.txt behind the first three columns (sample_individual_row; its own allocation, freed with the run's records). */
 typedef struct {
     double arm[8];
     uint64_t st[3];
     double po[4];
     uint64_t sg[12];
+    char *smp_row;
 } ind_stats;
 
 /* The host's conversation with ONE context about a pileup's comparison individuals, owned by the context's worker.  It has
@@ -1924,7 +2010,10 @@ typedef struct {
     uint64_t *sg_pos;                        /* ... the windows' first positions [n_win], then their last */
     uint32_t *ch_starts;                     /* --chain-gap: the chain starts of the list at hand */
     int32_t *sw_shift;                       /* --switch-scale: the step shifts of the list at hand */
-    size_t arm_cap, st_cap, po_cap, sg_cap, sg_pos_cap, ch_cap, sw_cap;
+    uint64_t *smp_vals;                      /* --sample-paths: the draws' records [T][K][15] */
+    uint64_t *smp_stream;                    /* ... and the individuals' streams [T]: their indices in the panel */
+    uint64_t (*smp_tot)[9];                  /* ... and the run's totals [K][9], which every individual's draws are added to (the run's) */
+    size_t arm_cap, st_cap, po_cap, sg_cap, sg_pos_cap, ch_cap, sw_cap, smp_cap, smp_stream_cap;
 } dev_conv;
 
 /* one comparison individual on one context: where it stands and what comes back for it */
@@ -1973,6 +2062,7 @@ static void conv_release(dev_conv *c)
     if (c->batch_ll)
         ibdg_host_free(c->batch_ll);
     free(c->batch_log); free(c->arm_sums); free(c->st_counts); free(c->po_vals); free(c->sg_vals); free(c->sg_pos); free(c->ch_starts); free(c->sw_shift);
+    free(c->smp_vals); free(c->smp_stream);
     memset(c, 0, sizeof *c);
 }
 
@@ -2055,6 +2145,20 @@ static int segments_on_device(dev_conv *c)
                                      c->sg_vals + T * 12, c->sg_vals);
 }
 
+/* --sample-paths where the tables stay on the device: the positions go up with the call as the segments' do; a draw's stream is
+ * the individual's index in the panel, so that no batch, slot or device shows in it */
+static int samples_on_device(dev_conv *c)
+{
+    const size_t n_win = ibdg_num_windows(c->eng), T = c->n_targets, K = opt_sample_paths;
+    if (conv_positions(c, n_win))
+        return 1;
+    if (!grow(&c->smp_vals, &c->smp_cap, T * K * 15, sizeof(uint64_t)) || !grow(&c->smp_stream, &c->smp_stream_cap, T + 1, sizeof(uint64_t)))
+        return conv_oom(c, n_win);
+    for (size_t t = 0; t < T; ++t)
+        c->smp_stream[t] = c->targets[t];
+    return ibdg_window_log2_samples(c->eng, opt_p01, opt_p02, opt_p12, K, opt_seed, c->smp_stream, c->sg_pos, c->sg_pos + n_win, c->smp_vals);
+}
+
 /* the engine's last run must be the run of this very batch: its size says so (a diagnostic when it does not) */
 static int same_run_size(dev_conv *c)
 {
@@ -2088,16 +2192,16 @@ static int device_stats(dev_conv *c)
         return 1;
     if (opt_posteriors && ibdg_window_log2_posteriors(c->eng, opt_p01, opt_p02, opt_p12, NULL, c->po_vals, c->po_vals + T * 3))
         return 1;
-    return opt_segments && segments_on_device(c);
+    return (opt_segments && segments_on_device(c)) || (has_sample_paths && samples_on_device(c));
 }
 
-/* ... and an individual's share in them */
-static void device_stats_of(const dev_conv *c, size_t t, ind_stats *out)
+/* ... and an individual's share in them (1: out of memory for its row of the samples file) */
+static int device_stats_of(dev_conv *c, size_t t, ind_stats *out)
 {
     if (c->arm_seg)
         memcpy(out->arm, c->arm_sums + t * 8, sizeof out->arm);
     if (!c->dev_states)
-        return;
+        return 0;
     memcpy(out->st, c->st_counts + t * 3, sizeof out->st);
     if (opt_posteriors) {
         memcpy(out->po, c->po_vals + t * 3, 3 * sizeof(double));
@@ -2105,6 +2209,9 @@ static void device_stats_of(const dev_conv *c, size_t t, ind_stats *out)
     }
     if (opt_segments)
         memcpy(out->sg, c->sg_vals + t * 12, sizeof out->sg);
+    if (has_sample_paths && !(out->smp_row = sample_individual_row(c->smp_vals + t * opt_sample_paths * 15, opt_sample_paths, c->smp_tot)))
+        return conv_oom(c, 0);
+    return 0;
 }
 
 /* a new site list for this context: its slice goes up (unless the engine made the list itself) */
@@ -2169,7 +2276,8 @@ static int conv_individual(dev_conv *c, shard_job *j)
 {
     const size_t t = j->t_local;
     win_table *wt = &j->wt;
-    device_stats_of(c, t, &j->out);
+    if (device_stats_of(c, t, &j->out))
+        return 1;
     const size_t n_win = wt->w.n_win = ibdg_num_windows(c->eng);
     if (c->tables_stay)
         return 0;
@@ -2607,6 +2715,8 @@ typedef struct {
     ind_stats *res;                             /* the individual's lines of the run's statistics files: the twin's results go here */
     FILE *lp;                                   /* --posteriors: the individual's *.logposteriors.txt (NULL with --stats-only); closed by the job */
     FILE *ls;                                   /* --segments: the individual's *.logsegments.txt (NULL with --stats-only); closed by the job */
+    FILE *lsmp;                                 /* --sample-paths: the individual's *.logsamples.txt (NULL with --stats-only); closed by the job */
+    uint64_t (*smp_tot)[9];                     /* ... and the run's totals [K][9], which the individual's draws are added to */
     hg_path hgp;                                /* the slot's path arrays and text buffer (kept between individuals) */
     char *hg_buf;
     size_t hg_cap;
@@ -2823,13 +2933,51 @@ static int segments_individual(out_job *o, const log_chains *lc)
     return bad;
 }
 
+/* --sample-paths: K paths drawn from the posterior over the same table (ibdg_log2_samples_host: the same bytes as the device's
+ * ibdg_window_log2_samples), keyed by the individual's index in the panel; one row per draw goes to the individual's file, the
+ * individual's row of the run's file is made here and its draws are added to the run's totals (sample_individual_row): the records
+ * themselves do not outlive the job */
+static int samples_individual(out_job *o, const log_chains *lc)
+{
+    if (!has_sample_paths)
+        return 0;
+    const size_t n = o->wt.w.n_win, K = opt_sample_paths;
+    uint64_t *rec = malloc(K * 15 * sizeof *rec);
+    int bad = !rec;
+    if (bad)
+        fprintf(o->err, "[::] ERROR: out of memory for %zu draws.\n", K);
+    if (!bad && ibdg_log2_samples_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, lc->starts, lc->n_starts, lc->shift, K, opt_seed, o->tgt,
+                                       lc->pos, lc->pos + n, NULL, rec)) {
+        fprintf(o->err, "%s\n", ibdg_last_error(NULL));
+        bad = 1;
+    }
+    if (!bad && o->lsmp) {
+        bad = fputs("Sample\tWIN_IBD0\tWIN_IBD1\tWIN_IBD2\tSEG_IBD0\tSEG_IBD1\tSEG_IBD2\tBP_IBD0\tBP_IBD1\tBP_IBD2\t"
+                    "LONGEST_BP_IBD0\tLONGEST_BP_IBD1\tLONGEST_BP_IBD2\n", o->lsmp) < 0;
+        for (size_t k = 0; k < K && !bad; ++k) {
+            const uint64_t *r = rec + 15 * k;
+            bad = fprintf(o->lsmp, "%zu", k + 1) < 0;
+            for (int i = 0; i < 15 && !bad; ++i)
+                if (i < 6 || i >= 9)                 /* (the windows of the longest segments are not in this file) */
+                    bad = fprintf(o->lsmp, "\t%llu", (unsigned long long)r[i]) < 0;
+            bad = bad || fputc('\n', o->lsmp) == EOF;
+        }
+    }
+    if (!bad && !(o->res->smp_row = sample_individual_row(rec, K, o->smp_tot))) {
+        fprintf(o->err, "[::] ERROR: out of memory for %zu draws.\n", K);
+        bad = 1;
+    }
+    free(rec);
+    return out_close(&o->lsmp) || bad;
+}
+
 static int log_states_individual(out_job *o)
 {
     const size_t n = o->wt.w.n_win;
     uint64_t *const count = o->res->st;
     uint8_t *path = o->hg ? malloc(n ? n : 1) : NULL;
     int64_t *score = o->hg ? malloc((n ? n : 1) * 3 * sizeof *score) : NULL;
-    const int want_pos = opt_segments || has_chain_gap || has_switch_scale;
+    const int want_pos = opt_segments || has_chain_gap || has_switch_scale || has_sample_paths;
     log_chains lc = {want_pos ? malloc((2 * n + 1) * sizeof *lc.pos) : NULL, has_chain_gap ? malloc((n + 1) * sizeof *lc.starts) : NULL, 0,
                      has_switch_scale ? malloc((n + 1) * sizeof *lc.shift) : NULL};
     int bad = (o->hg && (!path || !score)) || (want_pos && !lc.pos) || (has_chain_gap && !lc.starts) || (has_switch_scale && !lc.shift);
@@ -2860,9 +3008,11 @@ static int log_states_individual(out_job *o)
     if ((want_pos && !lc.pos) || (has_chain_gap && !lc.starts) || (has_switch_scale && !lc.shift)) {    /* (out of memory: the other two files are closed as they are) */
         out_close(&o->lp);
         out_close(&o->ls);
+        out_close(&o->lsmp);
     } else {
         bad = posteriors_individual(o, &lc) || bad;
         bad = segments_individual(o, &lc) || bad;
+        bad = samples_individual(o, &lc) || bad;
     }
     free(lc.pos);
     free(lc.starts);
@@ -3289,7 +3439,7 @@ typedef struct {
     uint32_t *row_pre_off;
 } site_list;
 
-enum { N_RUN_FILES = 3 };           /* RUN_FILES below */
+enum { N_RUN_FILES = 4 };           /* RUN_FILES below */
 
 typedef struct {
     /* ---- the pileup's run ---- */
@@ -3300,6 +3450,7 @@ typedef struct {
     int overlap, dev_v, batchable, arm_on, tables_stay, dev_states, out_slots, out_threads_env;
     size_t n_site_out;              /* entries of an individual's per-site array */
     ind_stats *res;                 /* per individual, what the run's statistics files are written from (run_end) */
+    uint64_t (*smp_tot)[9], *smp_col;   /* --sample-paths: draw k summed over the individuals so far [K][9]; scratch [K] for their columns */
     FILE *run_file[N_RUN_FILES];    /* the files of RUN_FILES, open from run_begin to run_end */
     char *run_fn[N_RUN_FILES];
     double *site_slot[OUT_SLOTS];   /* the per-site array of each output slot */
@@ -3436,7 +3587,33 @@ static void write_segments_file(pile_run *r, FILE *f)
                 (unsigned long long)total[9 + s]);
 }
 
-/* <out>/<pileup-name>.[log]<kind>.txt (the last two exist with --log-stats only), in the order they are opened and written.
+/* likewise: per individual its row -- its text was made when the individual's draws were done (sample_individual_row) --, then
+ * the totals' from the run's sums of draw k over the individuals: the same statistics (the draws of different individuals are
+ * independent) */
+static void write_samples_file(pile_run *r, FILE *f)
+{
+    static const char *const what[3] = {"WIN", "SEG", "BP"}, *const stat[4] = {"MEAN", "Q025", "Q500", "Q975"};
+    const size_t K = opt_sample_paths;
+    char tail[SMP_ROW_ROOM];
+    size_t total_n = 0;
+    fputs("# ID\tN_SEGMENTS\tK", f);
+    for (int s = 0; s < 3; ++s)
+        for (int q = 0; q < 3; ++q)
+            for (int k = 0; k < 4; ++k)
+                fprintf(f, "\tIBD%d_%s_%s", s, what[q], stat[k]);
+    fputs("\tP_ANY_IBD12\n", f);
+    for (size_t ti = 0; ti < g_targets.n; ++ti) {
+        const size_t n = (size_t)(r->res[ti].st[0] + r->res[ti].st[1] + r->res[ti].st[2]);
+        if (!r->res[ti].smp_row)
+            continue;                             /* (an individual whose job failed: the run is failing, and has said so) */
+        fprintf(f, "%s\t%zu\t%zu%s", g_ids.names[g_targets.idx[ti]], n, K, r->res[ti].smp_row);
+        total_n += n;
+    }
+    sample_row_tail(tail, (const uint64_t (*)[9])r->smp_tot, K, r->smp_col);
+    fprintf(f, "# Total\t%zu\t%zu%s", total_n, K, tail);
+}
+
+/* <out>/<pileup-name>.[log]<kind>.txt (the last three exist with --log-stats only), in the order they are opened and written.
  * armstats.txt is not among them: it is opened where it is written, in run_end. */
 static const struct {
     const int *on;
@@ -3446,6 +3623,7 @@ static const struct {
     {&opt_states, "ibdstates", "IBD-state fractions file", write_states_file},
     {&opt_posteriors, "ibdposteriors", "IBD-state posteriors file", write_posteriors_file},
     {&opt_segments, "ibdsegments", "IBD-state segments file", write_segments_file},
+    {&has_sample_paths, "ibdsamples", "IBD-state samples file", write_samples_file},
 };
 
 /* the run's arrays and its statistics files */
@@ -3466,6 +3644,14 @@ static int run_begin(pile_run *r)
     r->res = calloc(g_targets.n + 1, sizeof *r->res);
     if (!r->res)
         SFAIL("[::] ERROR: out of memory.\n");
+    if (has_sample_paths) {
+        r->smp_tot = calloc(opt_sample_paths, sizeof *r->smp_tot);
+        r->smp_col = calloc(opt_sample_paths, sizeof *r->smp_col);
+        if (!r->smp_tot || !r->smp_col)
+            SFAIL("[::] ERROR: out of memory for %lu draws.\n", opt_sample_paths);
+        for (int d = 0; d < r->w->n_eng; ++d)
+            r->w->conv[d].smp_tot = r->smp_tot;
+    }
     /* opened before the run, like the individuals' files: a directory that cannot be written stops the run at once */
     for (int k = 0; k < N_RUN_FILES; ++k) {
         if (!*RUN_FILES[k].on)
@@ -3907,7 +4093,7 @@ static FILE *out_file_open(pile_run *r, const char *kind, int to_null, char **fn
 static int outputs_open(pile_run *r, out_job *o)
 {
     char *tab_fn, *sum_fn;
-    o->hg = o->lsum = o->lp = o->ls = NULL;
+    o->hg = o->lsum = o->lp = o->ls = o->lsmp = NULL;
     if (opt_plan || opt_stats_only) {         /* (--stats-only --states: the table is here for its path alone) */
         o->tab = o->sum = opt_plan ? stdout : NULL;
         return 0;
@@ -3922,7 +4108,8 @@ static int outputs_open(pile_run *r, out_job *o)
     return !o->tab || !o->sum || (opt_log_summary && !(o->lsum = out_file_open(r, "logsummary", 0, NULL))) ||
            (opt_states && !(o->hg = out_file_open(r, opt_log_stats ? "loghiddengem" : "hiddengem", 0, NULL))) ||
            (opt_posteriors && !(o->lp = out_file_open(r, "logposteriors", 0, NULL))) ||
-           (opt_segments && !(o->ls = out_file_open(r, "logsegments", 0, NULL)));
+           (opt_segments && !(o->ls = out_file_open(r, "logsegments", 0, NULL))) ||
+           (has_sample_paths && !(o->lsmp = out_file_open(r, "logsamples", 0, NULL)));
 }
 
 /* everything the individual's files are made of goes to its slot's job, the window table with it; the job runs beside the
@@ -3945,6 +4132,7 @@ static int output_start(pile_run *r)
     memset(&r->wt, 0, sizeof r->wt);
     o->sq = pj->name; o->err = r->err;
     o->res = &r->res[r->ti];
+    o->smp_tot = r->smp_tot;
     if (outputs_open(r, o))
         return 1;
     const int threads = all_threads();
@@ -4015,8 +4203,11 @@ static void run_release(pile_run *r)
         free(r->run_fn[k]);
         r->run_file[k] = NULL, r->run_fn[k] = NULL;
     }
-    free(r->res); free(sl->row_pre); free(sl->row_pre_off);
+    for (size_t ti = 0; r->res && ti < g_targets.n; ++ti)
+        free(r->res[ti].smp_row);
+    free(r->res); free(sl->row_pre); free(sl->row_pre_off); free(r->smp_tot); free(r->smp_col);
     r->res = NULL;
+    r->smp_tot = NULL, r->smp_col = NULL;
     sl->row_pre = NULL;
     sl->row_pre_off = NULL;
     if (!g_list_mode)
@@ -4197,6 +4388,28 @@ int main(int argc, char **argv)
             break;
         }
         case 1013: genetic_map_fn = optarg; break;
+        case 1014: {
+            char *end = NULL;
+            errno = 0;
+            opt_sample_paths = strtoul(optarg, &end, 10);
+            if (!isdigit((unsigned char)optarg[0]) || *end || errno || opt_sample_paths < 1 || opt_sample_paths > 65536) {
+                fprintf(stderr, "[::] ERROR: Invalid number of draws (--sample-paths) '%s' (must be an integer in 1 .. 65536).\n", optarg);
+                exit(1);
+            }
+            has_sample_paths = 1;
+            break;
+        }
+        case 1015: {
+            char *end = NULL;
+            errno = 0;
+            opt_seed = strtoull(optarg, &end, 10);
+            if (!isdigit((unsigned char)optarg[0]) || *end || errno) {
+                fprintf(stderr, "[::] ERROR: Invalid seed (--seed) '%s' (must be an integer in 0 .. 2^64 - 1).\n", optarg);
+                exit(1);
+            }
+            has_seed = 1;
+            break;
+        }
         case 1006:
             if (!parse_arm_range(optarg)) {
                 fprintf(stderr, "[::] ERROR: Invalid centromeric range (--arm-stats) '%s' (must be START,END with START <= END).\n", optarg);
@@ -4248,6 +4461,9 @@ int main(int argc, char **argv)
     if (genetic_map_fn && opt_plan) { fprintf(stderr, "[::] ERROR: --genetic-map changes files --plan does not make; use one of them.\n"); exit(1); }
     if (genetic_map_fn && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --genetic-map needs --log-stats and --states: it measures the distances their switch penalties are scaled by.\n"); exit(1); }
     if (genetic_map_fn && !has_switch_scale) { fprintf(stderr, "[::] ERROR: --genetic-map needs --switch-scale X: it says in which unit X and the distances between windows are measured.\n"); exit(1); }
+    if (has_sample_paths && opt_plan) { fprintf(stderr, "[::] ERROR: --sample-paths writes files --plan does not make; use one of them.\n"); exit(1); }
+    if (has_sample_paths && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --sample-paths needs --log-stats and --states: it draws paths from the distribution over all paths of the weights whose best path they find, with their --p01, --p02, --p12.\n"); exit(1); }
+    if (has_seed && !has_sample_paths) { fprintf(stderr, "[::] ERROR: --seed is the seed of --sample-paths K.\n"); exit(1); }
     if (genetic_map_fn)
         gmap_read(genetic_map_fn);
     if (opt_log_stats && opt_states) {

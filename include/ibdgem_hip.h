@@ -363,6 +363,32 @@ int ibdg_log2_segments_steps_host(const double *log2_tab, size_t n_win, double p
 int ibdg_set_window_steps(ibdg_ctx *ctx, const int32_t *shift, size_t n);
 /* 1 if the current site list has step shifts, else 0. */
 int ibdg_has_window_steps(const ibdg_ctx *ctx);
+/* Sampled paths: n_samples paths of one window table drawn from P(path | all windows) under the weights of
+ * ibdg_log2_posteriors_steps_host, by forward filtering and backward sampling (ibdgem_amd/csrc/ibdg_states.h has the rule to the
+ * bit: the forward vectors are that pass's own doubles, one splitmix64 value per (draw, window) keyed by seed, stream and the
+ * draw's number, three fp64 products, two sums and two comparisons per state drawn).  starts / n_starts and shift as in the
+ * _steps_host functions (n_starts = 0 and NULL for none); stream: the individual's, by convention its index in the panel -- a draw
+ * depends on (seed, stream, k) alone, and draw k is the same whatever n_samples is.  pos_first / pos_last [n_win] as for the
+ * segments, or both NULL.  paths [n_samples][n_win] (may be NULL): the drawn states.  out [n_samples][15], per draw: [0..2] its
+ * windows per state, [3..14] the summary[12] of ibdg_log2_segments_host for the drawn path.  Needs no device.  n_win = 0: every
+ * record 0.  Errors (ibdg_last_error(NULL)): those of ibdg_log2_posteriors_steps_host, n_samples outside 1 .. 65536, NULL out,
+ * one position array without the other, a window with pos_last < pos_first. */
+int ibdg_log2_samples_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                           size_t n_starts, const int32_t *shift, size_t n_samples, uint64_t seed, uint64_t stream,
+                           const uint64_t *pos_first, const uint64_t *pos_last, uint8_t *paths, uint64_t *out);
+/* The same for every comparison individual of the last ibdg_run, on the device, over the context's chains and steps: stream[T],
+ * out [T][n_samples][15] -- 120 n_samples bytes per individual leave the device.  The same bytes as ibdg_log2_samples_host on
+ * ibdg_get_window_log2's table with stream[t].  The forward vectors are made by the first call with these penalties on a run
+ * and kept as the paths and posteriors are; the draws run a workgroup per (individual, draw) pair in chunks of pairs whose
+ * paths and records stay under 256 MiB of device memory.  Same waits as ibdg_get_window_log2.  Errors: those of
+ * ibdg_window_log2_posteriors, n_samples outside 1 .. 65536, NULL out or stream, one position array without the other, a window
+ * with pos_last < pos_first. */
+int ibdg_window_log2_samples(ibdg_ctx *ctx, double p01, double p02, double p12, size_t n_samples, uint64_t seed,
+                             const uint64_t *stream, const uint64_t *pos_first, const uint64_t *pos_last, uint64_t *out);
+/* Draw k of individual t of the last ibdg_window_log2_samples call again: path[n_win], the bytes of ibdg_log2_samples_host's
+ * paths[k].  Errors: no such call since the last ibdg_run, ibdg_set_window_chains or ibdg_set_window_steps; t or k out of range;
+ * NULL path. */
+int ibdg_get_log2_sample_path(ibdg_ctx *ctx, size_t t, size_t k, uint8_t *path);
 /* Alt-allele count of panel rows [first_row, first_row+n): out[n] (for tests). */
 int ibdg_get_alt_counts(ibdg_ctx *ctx, size_t first_row, size_t n, uint32_t *out);
 

@@ -1,0 +1,23 @@
+"""The sampled paths' host twin under AddressSanitizer + UndefinedBehaviorSanitizer: tools/log_samples_asan.cpp, a program of
+its own (host code only, no device, nothing loaded into Python), built with the build line at its top -- the sanitizers'
+runtimes linked into the program itself, so that it runs in the environment as it is -- and run once.  Any sanitizer report
+aborts the program, which fails the test.  The program also holds post_window_matrix against the step matrix built from
+post_window_weights at every window of its shapes (the two are written out twice in ibdg_states.h)."""
+import os
+import subprocess
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_twin_runs_clean_under_asan_and_ubsan(tmp_path):
+    exe = str(tmp_path / "log_samples_asan")
+    subprocess.run(["c++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-o", exe,
+                    os.path.join(REPO, "tools", "log_samples_asan.cpp"),
+                    os.path.join(REPO, "ibdgem_amd", "csrc", "ibdg_states_host.cpp")], check=True, cwd=REPO)
+    env = dict(os.environ, ASAN_OPTIONS="abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([exe], env=env, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 2 and lines[0].startswith("257 windows, 3 draws: ") and lines[1].startswith("1279 windows, 3 draws: ")
+    assert all(" windows hold the weights' two copies together" in l for l in lines)
