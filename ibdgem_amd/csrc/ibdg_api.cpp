@@ -2253,6 +2253,28 @@ int ibdg_get_window_log2_all(ibdg_ctx *c, double *out)
     return fetch(c, out, c->wlog.win_log2.p, c->n_targets * (size_t)c->sites.n_win * 24);
 }
 
+// The caller's table in place of the last run's (tests, and callers that gathered a table elsewhere).  The copy is queued on the
+// main stream behind join_streams -- the run's own writers of the table are in front of it -- and waited for on the host: tab may
+// go once this returns.  Everything the log-domain state calls keep is a function of the table: drop().  Nothing else of the
+// run is touched; the next ibdg_run writes the whole table again.  A refused call changes nothing.
+int ibdg_set_window_log2(ibdg_ctx *c, const double *tab, size_t n_targets)
+{
+    if (!c) return 1;
+    if (!c->have_results) return fail(c, "[::] ERROR in ibdg_set_window_log2: no results (call ibdg_run)");
+    if (!c->wlog.valid) return fail(c, "[::] ERROR in ibdg_set_window_log2: the last run kept no window logs (option log_windows)");
+    if (n_targets != c->n_targets)
+        return fail(c, "[::] ERROR in ibdg_set_window_log2: %zu tables for the %zu comparison individuals of the last run", n_targets, c->n_targets);
+    if (!tab) return fail(c, "[::] ERROR in ibdg_set_window_log2: NULL tab");
+    const size_t bytes = c->n_targets * (size_t)c->sites.n_win * 24;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (join_streams(c)) return 1;
+    if (bytes)
+        HIP_TRY(c, hipMemcpyAsync(c->wlog.win_log2.p, tab, bytes, hipMemcpyHostToDevice, c->stream));
+    if (quiesce(c)) return 1;
+    c->ls.drop();
+    return 0;
+}
+
 // Segmented sums over the window table of the last run (ibdg_llr.hip).  On the main stream behind join_streams: LIBD2 comes
 // from stream2, LIBD0/LIBD1 may come from a finalising launch still pending for the next run.  The segments go in chunks
 // whose slab of partials stays under LLR_SLAB items (one segment per chunk at least: its slab is then ~1/1500 of win_ll).

@@ -341,7 +341,9 @@ struct ibdg_ctx {
     //            events, so that ring_prepare's wait for a slot's last reader covers it ("end_in_dispatch" is off with the
     //            option on: the run's end is an event behind everything);
     //            k_win_log_rows (column 2 of an --LD run, all three otherwise) behind the run's k_rows_windows on ITS stream:
-    //            stream2 in front of the run's s2_end, or the main stream of a non-LD run that needs no recount
+    //            stream2 in front of the run's s2_end, or the main stream of a non-LD run that needs no recount;
+    //            ibdg_set_window_log2's copy of the caller's table over the whole of it, on the main stream behind join_streams
+    //            and waited for on the host (it calls ls.drop(): what the state calls keep is a function of the table)
     //   readers  the copies of ibdg_get_window_log2[_all] only, on the main stream behind join_streams (the main stream waits
     //            for stream2's last event), followed by a host wait: no reader outlives its call
     //   the two writers of an --LD run are on different streams and write different columns; a queued next run's k_ld_log may
@@ -361,8 +363,8 @@ struct ibdg_ctx {
     // A stage whose product is fresh for the call's penalties does not launch; `score` [T][n_win][3] is not kept, so a call
     // that wants scores launches anyway.  States, posteriors and segments with the same penalties on one run thus launch each
     // kernel once.  The key is the penalties and nothing else: both products are functions of win_log2 and the penalties, and
-    // drop() is called where a run starts (ibdg_run) and wherever have_results is cleared (panel_replaced, sites_replaced) --
-    // the only places where the table, T or n_win can change.  The buffers' allocation counts are NOT part of the key (as
+    // drop() is called where a run starts (ibdg_run), wherever have_results is cleared (panel_replaced, sites_replaced) and by
+    // ibdg_set_window_log2 -- the only places where the table, T or n_win can change.  The buffers' allocation counts are NOT part of the key (as
     // they are for RowTable or Images): between two drops T and n_win are fixed, every ensure() of this group asks for the
     // same size again, and so it cannot move a buffer that holds a fresh product.
     // The records: records_made says that `path` (and with_post: `post`) are what the last ibdg_window_log2_segments used and

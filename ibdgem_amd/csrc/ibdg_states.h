@@ -225,12 +225,27 @@ int log2_states_host(const char *fn, const double *tab, size_t n_win, double p01
 //   3  block, backward  beta = G_b; for w = w1 - 1 .. w0: keep beta as beta_w; if w > w0: beta <- post_mat_vec(M_w, beta),
 //                     post_rescale.
 //   4  block, forward   v = F_b (block 0: none); for w = w0 .. w1 - 1: w = 0: v = b_0, exponent 0; else v <- post_vec_mat(v,
-//                     M_w), post_rescale.  p_s = v[s] * beta_w[s]; D = (p_0 + p_1) + p_2; gamma_w[s] = p_s / D; acc[s] +=
-//                     gamma_w[s] (acc starts at 0: the block's sum in window order).  At w = n_win - 1: Z = D * 2^(v's exponent).
+//                     M_w), post_rescale.  p_s = v[s] * beta_w[s]; D = (p_0 + p_1) + p_2; gamma_w[s] = p_s / D, or 0 if D ==
+//                     0 (the dead-chain rule below); acc[s] += gamma_w[s] (acc starts at 0: the block's sum in window order).
+//                     At w = n_win - 1: Z = D * 2^(v's exponent).
 //   5  expect         part[b] = acc (0 for a b that owns no window), b = 0 .. 255; for d = 128, 64, .. 1: part[b] = part[b] +
 //                     part[b + d] for b < d; expect = part[0].
 // log2_z = log2(D) + exponent: one libm log2 and one addition on the host, in the device route too.
 // Roundings on the way to one gamma, counted as hp_post_ref.R counts them: at most 14 per window.
+//
+// The dead-chain rule.  A switch weight of a window with a shift can be exactly 0 (below 2^-1000), and a product a * b of two tiny
+// weights can underflow to 0 (two switch weights of 2^-997 in one block matrix): legal inputs can leave every path of an
+// individual with weight 0.  alpha then becomes (0, 0, 0) at some window and stays so to the end, beta does the same towards
+// the front, and D = 0 at every window (after an underflow: at most of them, see below) -- a dead stretch kills the individual's posteriors across chain starts too (Z is the
+// product of the chains' Z).  v and beta are finite and non-negative, so D is never NaN, and D == 0 is the only case without
+// a quotient: there gamma_w = (0, 0, 0).  Nothing else needs a rule: expect omits the window, a segment's post_q adds 0 and
+// its post_min is 0.0, Z = 0 gives log2_z = -inf from the host's log2, and no gamma is ever NaN.  A row of gamma that sums to
+// 0 is the visible mark of an individual whose weights leave no path.  The path of 4.8 is not affected: its integers do not
+// underflow.  Of the two causes the exact reference (tests/hp_post_ref.py, hp_steps_ref.py) shares the first -- a weight
+// that is exactly 0 is an input, and its Z is 0 too --, not the second: an underflowing product is a rounding of this
+// arithmetic (it happens before the rescale, to an entry that is far above 2^-1022 of its vector's largest), the exact Z is
+// not 0, D may be 0 at some windows and not at others, and such an individual can only be held to "device == twin", not to
+// the exact truth.  Penalties of 1e-300 beside windows with a single live state are what it takes.
 constexpr int64_t POST_K_MIN = -1000;    // an emission weight below 2^-1000 is 0
 
 IBDG_HD double post_pow2(int k)          // 2^k, -1022 <= k <= 1023
@@ -468,7 +483,8 @@ IBDG_HD void post_block_gamma(const PostIn &in, uint32_t w0, uint32_t w1, const 
         }
         const double p0 = v[0] * p[0], p1 = v[1] * p[1], p2 = v[2] * p[2];
         d = (p0 + p1) + p2;
-        const double g0 = p0 / d, g1 = p1 / d, g2 = p2 / d;
+        const bool dead = d == 0.0;               // the dead-chain rule: no path has weight, gamma_w = (0, 0, 0), by selects
+        const double g0 = dead ? 0.0 : p0 / d, g1 = dead ? 0.0 : p1 / d, g2 = dead ? 0.0 : p2 / d;
         p[0] = g0, p[1] = g1, p[2] = g2;
         sum[0] += g0, sum[1] += g1, sum[2] += g2;
     }
@@ -494,7 +510,7 @@ int log2_posteriors_host(const char *fn, const double *tab, size_t n_win, double
 //   record   ibdg_segment (include/ibdgem_hip.h, 56 bytes): first = f, n_win = its windows, state = path[f], reserved = 0;
 //            e[s] = sum of e_w[s] over its windows (|e_w[s]| <= 2^40, n_win <= 2^21: |sum| <= 2^61; a window whose emission is
 //            (0, 0, 0) adds nothing); post_q = sum of q_w = states_rint(gamma_w[state] * 2^32) (the product with a power of two is
-//            exact, ties to even; q_w <= 2^32, the sum <= 2^53); post_min = min of gamma_w[state] (gamma is never NaN: no NaN rule).  post_q = 0 and post_min = 0.0 when the
+//            exact, ties to even; q_w <= 2^32, the sum <= 2^53); post_min = min of gamma_w[state] (gamma is never NaN -- a dead chain's is (0, 0, 0), the rule of 4.9 --: no NaN rule).  post_q = 0 and post_min = 0.0 when the
 //            posteriors are not asked for
 //   summary  uint64[12] per individual, for s = 0, 1, 2: [s] n_seg[s], [3 + s] longest_win[s] (the largest n_win of a segment
 //            in state s, 0 if none), [6 + s] bp[s] = sum over the state's segments of span = pos_last[last window] -
@@ -594,7 +610,11 @@ int log2_segments_host(const char *fn, const double *tab, size_t n_win, double p
 //             is at most the double below D.  With x < D = (c_0 + c_1) + c_2 a state of weight 0 is never drawn: c_2 = 0 gives
 //             x < c_0 + c_1, and c_1 = 0 besides gives x < c_0; c_0 = 0 fails x < c_0 always.  (A subnormal D needs every
 //             c_q below 2^-1022 under an alpha whose largest entry is in [1, 2): an s' whose own probability is below 2^-1000.)
-//   total     D = 0 gives x = 0 and state 2.  That needs an s' of weight 0 at w + 1, which by the line above is never drawn.
+//   total     D = 0 gives x = 0 and state 2, the same integer on either side.  Under a live alpha that needs an s' of weight 0
+//             at w + 1, which by the line above is never drawn.  In a dead chain (4.9) it does happen: where alpha_w itself is
+//             (0, 0, 0), from the window at which the chain dies to the end, and at the window in front of a step whose weights
+//             are all 0.  Such an individual's draws are state 2 there and the usual rule in front of that -- defined bytes, of
+//             a distribution that does not exist (the posteriors' gamma = 0 says so).
 //   maps      the three answers for s' = 0, 1, 2 are window w's map in the form of `from` (sample_map); the last window's map
 //             is constant (sample_last_map).  Maps over three states compose associatively (map_after), so a draw is the same
 //             bytes for any blocking: the kernel composes per block and scans as k_log2_states does, the twin walks once from

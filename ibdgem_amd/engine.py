@@ -49,6 +49,7 @@ SYMBOLS = {
     "ibdg_get_window_ll_all": (C.c_int, [_P, _P]),
     "ibdg_get_window_log2": (C.c_int, [_P, C.c_size_t, _P]),
     "ibdg_get_window_log2_all": (C.c_int, [_P, _P]),
+    "ibdg_set_window_log2": (C.c_int, [_P, _P, C.c_size_t]),
     "ibdg_window_llr_sums": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     "ibdg_window_log2_llr_sums": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     "ibdg_log2_states_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
@@ -486,6 +487,14 @@ class Engine:
         assert out.dtype == np.float64 and out.size >= n_targets * self.n_windows * 3 and out.flags.c_contiguous
         self._chk(self.lib.ibdg_get_window_log2_all(self.ctx, out.ctypes.data))
         return out
+
+    def set_window_log2_all(self, tabs):
+        """tabs [T][n_windows][3] in place of the last run's log tables (ibdg_set_window_log2): for tests, and for callers that
+        gathered a table elsewhere.  Any double goes; what the window_log2_* calls kept is stale afterwards."""
+        a = np.ascontiguousarray(tabs, dtype=np.float64)
+        if a.ndim != 3 or a.shape[1:] != (self.n_windows, 3):
+            raise ValueError(f"tabs: shape {a.shape}, not [T][{self.n_windows}][3]")
+        self._chk(self.lib.ibdg_set_window_log2(self.ctx, a.ctypes.data, a.shape[0]))
 
     def window_llr_sums(self, first, end):
         """Sums of log2(L2')-log2(L0') and log2(L1')-log2(L0') over the window ranges [first[s], end[s]) for every comparison

@@ -221,6 +221,12 @@ int ibdg_get_window_ll_all(ibdg_ctx *ctx, double *out);
 int ibdg_get_window_log2(ibdg_ctx *ctx, size_t t, double *out);
 /* The same for every target of the last ibdg_run in one copy: out[ibdg_num_targets][n_windows][3]. */
 int ibdg_get_window_log2_all(ibdg_ctx *ctx, double *out);
+/* The other direction: tab[n_targets][n_windows][3] replaces the log2 table of the last ibdg_run, for tests and for callers
+ * that gathered a table elsewhere.  Any double is allowed, NaN and +-inf included.  Everything the ibdg_window_log2_* calls keep
+ * (the path, the posteriors, alpha, the segment records, the draws) goes stale; nothing else of the run changes -- the linear
+ * window and per-site tables stay -- and the next ibdg_run writes its own table again.  Returns after the copy: tab may go.
+ * Errors: no results, the last ibdg_run made with the option off, n_targets != ibdg_num_targets, NULL tab. */
+int ibdg_set_window_log2(ibdg_ctx *ctx, const double *tab, size_t n_targets);
 /* For each comparison individual t of the last ibdg_run and each window range s = [first[s], end[s]) of its
  * site list: the sums over the range of log2(L2') - log2(L0') and log2(L1') - log2(L0') (L' = L, or 2^-1074 where
  * L == 0), each as a double-double: out[((t * n_seg) + s) * 4 + {0,1,2,3}] = {IBD2/IBD0 hi, lo, IBD1/IBD0 hi, lo}.
@@ -231,7 +237,8 @@ int ibdg_get_window_log2_all(ibdg_ctx *ctx, double *out);
 int ibdg_window_llr_sums(ibdg_ctx *ctx, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out);
 /* The same sums from the log2 table of option "log_windows": the terms are the table's own entries, +l2, -l0 and +l1, -l0 --
  * no log2 and no 2^-1074 in place of a likelihood that left the double range.  Same out layout, double-double, order of
- * additions, NaN handling, empty ranges and errors; also an error if the last ibdg_run was made with the option off. */
+ * additions, NaN handling, empty ranges and errors; also an error if the last ibdg_run was made with the option off.  An infinite
+ * entry (a run writes none; a table of ibdg_set_window_log2 may hold one) makes the sums of a range that holds it NaN, like a NaN. */
 int ibdg_window_log2_llr_sums(ibdg_ctx *ctx, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out);
 
 /* The IBD-state path of one window table in the log domain, in integers.  log2_tab[n_win][3] = log2 LIBD0/1/2; p01, p02,
@@ -260,7 +267,10 @@ int ibdg_window_log2_states(ibdg_ctx *ctx, double p01, double p02, double p12, u
  * all paths; post[n_win][3] (may be NULL) = P(state at window w | all windows), expect[3] = its sums over the windows (expected
  * windows per state), *log2_z = log2 Z.  fp64 sums and products with an integer exponent carried beside every vector, so
  * nothing leaves the double range at any depth or length; the order of the operations is fixed (ibdgem_amd/csrc/ibdg_states.h)
- * and is the device's.  Needs no device.  n_win = 0: expect = 0, log2_z = 0.  Errors (ibdg_last_error(NULL)): a penalty outside
+ * and is the device's.  No output is ever NaN: where the weights leave no path (Z = 0: a shifted switch weight that is exactly 0
+ * between windows with different single live states, or products of penalties near 1e-300 that underflow) a window's three
+ * probabilities are 0, expect omits it and *log2_z = -inf (the dead-chain rule).  Needs no device.  n_win = 0:
+ * expect = 0, log2_z = 0.  Errors (ibdg_last_error(NULL)): a penalty outside
  * (0, 1] or NaN, n_win > 2^21, NULL expect or log2_z. */
 int ibdg_log2_posteriors_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, double *post,
                               double expect[3], double *log2_z);

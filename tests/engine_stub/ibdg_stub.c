@@ -257,6 +257,12 @@ int ibdg_get_window_ll(ibdg_ctx *c, size_t t, double *out) { return table(c, "ge
 int ibdg_get_window_ll_all(ibdg_ctx *c, double *out) { return table(c, "get_window_ll_all", 0, c->n_targets, c->n_win, 0, out); }
 int ibdg_get_window_log2(ibdg_ctx *c, size_t t, double *out) { return table(c, "get_window_log2", t, t + 1, c->n_win, 1, out); }
 int ibdg_get_window_log2_all(ibdg_ctx *c, double *out) { return table(c, "get_window_log2_all", 0, c->n_targets, c->n_win, 1, out); }
+/* (the host program never sets a table; the stand-in's tables are functions of the individuals and stay so) */
+int ibdg_set_window_log2(ibdg_ctx *c, const double *tab, size_t n_targets)
+{
+    tr(c, "set_window_log2 n_targets=%z", n_targets);
+    return !tab || n_targets != c->n_targets;
+}
 
 static int llr_sums(ibdg_ctx *c, const char *what, const uint32_t *first, const uint32_t *end, size_t n_seg, double *out)
 {

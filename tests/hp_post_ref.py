@@ -30,6 +30,12 @@ is rounded as a subnormal, an absolute error below 2^-1022 of a quantity that is
 expect[s]: the gammas' bars summed, plus the C - 1 additions of a block and the 8 of the tree on the sum: (R n + C + 8) u truth
 + n 2^-1000.  log2_z: Z's count is below gamma's, an error e of Z moves log2 Z by e / ln 2 < 2 e; the library's log2 and the
 addition of the exponent are an ulp of the result each, and the truth's own float evaluation two more: 2 R n u + 4 u |truth| + 4 u.
+
+The dead-chain rule (ibdg_states.h).  Where a weight is exactly 0 -- a shifted switch weight below 2^-1000
+(hp_steps_ref.Truth; the constant penalties' weights are never 0) -- every path can have weight 0: Z == 0 here too, exactly.
+Then there is no quotient and the definition's answer is the truth: gamma_w = (0, 0, 0) at every window, expect = (0, 0, 0),
+log2_z = -inf, and check() asks for exactly these, no bar.  (The definition's other way to D = 0, a product of two tiny
+weights that underflows, is a rounding: the exact Z of such a table is not 0, and this truth has nothing to say about it.)
 """
 import ctypes
 import ctypes.util
@@ -164,14 +170,21 @@ class Truth:
             out[w - 1] = v
         return out
 
+    @property
+    def dead(self):
+        """No path has weight (the dead-chain rule): gamma is (0, 0, 0) everywhere, expect (0, 0, 0), log2_z -inf."""
+        return self.n > 0 and self.Z == 0
+
     def as_fraction(self, w, s):
-        return Fraction(self.P[w][s], self.Z)
+        return Fraction(0) if self.dead else Fraction(self.P[w][s], self.Z)
 
     def expect(self, s):
         """The lower end of expect[s]'s enclosure (expect[s] itself up to EXACT_WINDOWS windows)."""
-        return Fraction(self.S[s][0], self.Z)
+        return Fraction(0) if self.dead else Fraction(self.S[s][0], self.Z)
 
     def log2_z(self):
+        if self.dead:
+            return -math.inf
         bl = self.Z.bit_length()
         top = self.Z >> (bl - 64) if bl > 64 else self.Z << (64 - bl)
         return math.log2(top / 2.0 ** 64) + (bl + self.ez)
@@ -228,6 +241,12 @@ def check(tab, pen, post, expect, log2_z, truth=None):
     t = truth or Truth(tab, *pen)
     n = t.n
     worst = 0.0
+    if t.dead:                                       # the dead-chain rule: exact answers, no bar
+        for w in range(n):
+            assert [float(x) for x in post[w]] == [0.0, 0.0, 0.0], f"gamma[{w}] = {list(post[w])!r} of a dead chain (Z == 0)"
+        assert [float(x) for x in expect] == [0.0, 0.0, 0.0], f"expect = {list(expect)!r} of a dead chain"
+        assert log2_z == -math.inf, f"log2_z = {log2_z!r} of a dead chain"
+        return t, 0.0
     for w in range(n):
         for s in range(3):
             for P in set(t.bounds(w, s)):

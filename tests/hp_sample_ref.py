@@ -11,6 +11,11 @@ u_of and variant are the tests' handles: u_of(k, w) replaces U (its largest valu
 three wrong samplers that the statistical bars must catch.
 
 Exact.  For a table of at most 6 windows path_distribution gives P(path) of all 3^n paths as Fractions of the same weights.
+
+The dead-chain rule (ibdg_states.h).  Where a switch weight is exactly 0, every path can have weight 0.
+alpha is then (0, 0, 0) from some window on, every candidate there is 0, D = 0 and pick() answers state 2 -- the sampler's
+arithmetic as it is, the same integer on either side; in front of that window the usual rule holds.  Such draws are defined
+bytes, not samples: there is no distribution, and path_distribution gives {} (Z == 0).
 """
 import math
 from fractions import Fraction
@@ -234,6 +239,8 @@ def path_distribution(m):
             x *= Fraction(weights_into(m.a[w], p[w])[p[w - 1]]) * Fraction(m.b[w][p[w]])
         wt[p] = x
     Z = sum(wt.values())
+    if Z == 0:                                      # a dead chain: no path has weight, no distribution
+        return {}
     return {p: x / Z for p, x in wt.items()}
 
 

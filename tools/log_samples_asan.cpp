@@ -4,8 +4,12 @@
 //       -static-libasan -static-libubsan -o log_samples_asan tools/log_samples_asan.cpp ibdgem_amd/csrc/ibdg_states_host.cpp && ./log_samples_asan
 // Two shapes of the tests -- 257 windows (C = 2, a last block of one window) and 1279 (C = 5) -- with chain starts at 1, at a
 // block's first window and at n - 1, shifts that reach both caps, NaN windows, emissions below 2^-1000 and positions; with and
-// without the paths.  Exits 0 and prints a checksum per shape; a sanitizer report aborts.  On the same tables post_window_matrix is
-// held against the step matrix of post_window_weights (weights_agree).
+// without the paths.  Beside that table each shape walks two more (hard): one with NaN, +-inf, all-NaN and all -inf windows at its
+// first, middle and last windows and at a block's border, and a dead one (a window with state 0 alone alive, then one
+// with state 1 alone alive behind a shift of -2^30, so that no path has weight) -- the draws, the posteriors and the records with
+// their support, where gamma must hold no NaN and, for the dead table, nothing but 0.  Exits 0 and prints a checksum per shape; a
+// sanitizer report aborts.  On the same tables post_window_matrix is held against the step matrix of post_window_weights
+// (weights_agree).
 #include "../ibdgem_amd/csrc/ibdg_states.h"
 
 #include <cmath>
@@ -39,6 +43,52 @@ static size_t weights_agree(const double *tab, size_t n, const uint32_t *starts,
         }
     }
     return done;
+}
+
+// One hard table through the draws, the posteriors and the records with their support.  dead: gamma is 0 at every window, expect (0, 0,
+// 0), Z = 0, every record's post_q 0 and post_min 0.0; else no NaN and rows of gamma that are not all 0.  Folds what it saw into *sum.
+static int hard(const char *what, const std::vector<double> &tab, size_t n, size_t K, const uint32_t *starts, size_t n_starts,
+                const int32_t *shift, bool dead, uint64_t *sum)
+{
+    std::vector<uint8_t> paths(K * n);
+    std::vector<uint64_t> out(K * 15);
+    std::vector<double> post(n * 3);
+    std::vector<ibdg_segment> seg(n);
+    double expect[3], zm;
+    int ze;
+    uint64_t n_seg, summary[12];
+    char err[256];
+    if (ibdg::log2_samples_host("log_samples_asan", tab.data(), n, 0.05, 0.01, 0.05, starts, n_starts, shift, K, 7, 3, nullptr, nullptr,
+                                paths.data(), out.data(), err, sizeof err) ||
+        ibdg::log2_posteriors_host("log_samples_asan", tab.data(), n, 0.05, 0.01, 0.05, starts, n_starts, shift, post.data(), expect, &zm,
+                                   &ze, err, sizeof err) ||
+        ibdg::log2_segments_host("log_samples_asan", tab.data(), n, 0.05, 0.01, 0.05, starts, n_starts, shift, 1, nullptr, nullptr,
+                                 seg.data(), n, &n_seg, summary, err, sizeof err))
+        return fprintf(stderr, "%s\n", err), 1;
+    for (size_t w = 0; w < n; ++w) {
+        const double *g = &post[3 * w];
+        if (g[0] != g[0] || g[1] != g[1] || g[2] != g[2])
+            return fprintf(stderr, "%s table, %zu windows: gamma of window %zu is NaN\n", what, n, w), 1;
+        if (dead != (g[0] == 0.0 && g[1] == 0.0 && g[2] == 0.0))
+            return fprintf(stderr, "%s table, %zu windows: gamma of window %zu is %s\n", what, n, w, dead ? "not 0" : "0"), 1;
+    }
+    if (dead && (expect[0] != 0.0 || expect[1] != 0.0 || expect[2] != 0.0 || zm != 0.0))
+        return fprintf(stderr, "%s table, %zu windows: expect or Z is not 0\n", what, n), 1;
+    for (uint64_t i = 0; i < n_seg; ++i) {
+        if (seg[i].post_min != seg[i].post_min || (dead && (seg[i].post_q != 0 || seg[i].post_min != 0.0)))
+            return fprintf(stderr, "%s table, %zu windows: the support of record %llu\n", what, n, (unsigned long long)i), 1;
+        *sum = ibdg::sm64(*sum ^ seg[i].post_q ^ seg[i].first);
+    }
+    for (size_t k = 0; k < K; ++k) {
+        if (out[15 * k] + out[15 * k + 1] + out[15 * k + 2] != n)
+            return fprintf(stderr, "%s table, draw %zu of %zu windows: the states' windows do not add up\n", what, k, n), 1;
+        for (int i = 0; i < 15; ++i)
+            *sum = ibdg::sm64(*sum ^ out[15 * k + i]);
+    }
+    for (uint8_t s : paths)
+        if (s > 2)
+            return fprintf(stderr, "a state above 2\n"), 1;
+    return weights_agree(tab.data(), n, starts, n_starts, shift) ? 0 : 1;
 }
 
 static int shape(size_t n, size_t K)
@@ -79,6 +129,28 @@ static int shape(size_t n, size_t K)
             return fprintf(stderr, "a state above 2\n"), 1;
     const size_t held = weights_agree(tab.data(), n, starts, 3, shift.data());
     if (!held)
+        return 1;
+    // the two hard tables: on the moderate shifts alone (no cap: with the caps, any table might die), without the start at C
+    std::vector<double> nantab(tab), deadtab(tab);
+    std::vector<int32_t> mild(shift);
+    mild[n / 4] = mild[n / 5] = 0;
+    const size_t at[5] = {0, C - 1, C, n / 2, n - 1};
+    for (int i = 0; i < 5; ++i) {
+        double *r = &nantab[3 * at[i]];
+        if (i == 0) r[2] = NAN;
+        else if (i == 1) r[0] = r[1] = r[2] = NAN;
+        else if (i == 2) r[1] = -INFINITY;
+        else if (i == 3) r[0] = INFINITY;
+        else r[0] = r[1] = r[2] = -INFINITY;
+    }
+    const size_t p = (n / 2 / C) * C;             // the pair inside a block: windows p and p + 1 (C >= 2 at both shapes)
+    deadtab[3 * p] = -10.0, deadtab[3 * p + 1] = deadtab[3 * p + 2] = -5000.0;
+    deadtab[3 * p + 3] = deadtab[3 * p + 5] = -5000.0, deadtab[3 * p + 4] = -10.0;
+    std::vector<int32_t> kill(mild);
+    kill[p + 1] = -(1 << 30);
+    const uint32_t ends[2] = {1, (uint32_t)n - 1};
+    if (hard("NaN", nantab, n, K, ends, 2, mild.data(), false, &sum) || hard("NaN", nantab, n, K, nullptr, 0, nullptr, false, &sum) ||
+        hard("dead", deadtab, n, K, ends, 2, kill.data(), true, &sum) || hard("dead", deadtab, n, K, nullptr, 0, kill.data(), true, &sum))
         return 1;
     printf("%zu windows, %zu draws: %016llx; %zu windows hold the weights' two copies together\n", n, K, (unsigned long long)sum, held);
     return 0;
