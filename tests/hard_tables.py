@@ -24,6 +24,9 @@ Families (FINITE: the twin's posteriors are finite and sum to 1; DEAD: no path h
   dead-underflow  penalties 1e-300 (a switch weighs 2^-996.6: not 0) and a stretch of windows whose only live state alternates:
                   a block matrix of C >= 2 windows multiplies two switch weights, 2^-1993 is 0 in fp64, and the rows the
                   forward walk needs are gone.  Dead for C >= 2 only: at C = 1 no such product is ever formed (UNDERFLOW_DEAD)
+  plateaus        (LONG_FAMILIES only) one state best by 40 bits over stretches of 1, C - 1, C, C + 1, 3 C + 2, 20 C windows in
+                  turn (at least 1 each), the best state advancing by one per stretch; marks: a stretch's first window -> its
+                  state.  Segments that end at every position of a block, and segments that cover many whole blocks
 The edge1000 and clamp tables sit on a base cut to multiples of 2^-20, so that l_s - max(l) gives back the offset exactly.
 """
 import math
@@ -100,7 +103,7 @@ def _dead_pair(n, variant):
 
 
 def case(family, n, variant=0):
-    seed = 1000 * FAMILIES.index(family) + variant
+    seed = 1000 * LONG_FAMILIES.index(family) + variant
     tab, marks = base(n, seed), {}
     edges = edge_windows(n)
     if family == "naninf":
@@ -125,11 +128,12 @@ def case(family, n, variant=0):
             marks[w] = live
         return Case(family, tab, marks=marks)
     if family == "alternating":
-        for w in range(n):
-            live = (7 * w // 3 + variant) % 3
-            tab[w] = _one_live(tab[w], live, 4990.0)
-            marks[w] = live
-        return Case(family, tab, marks=marks)
+        rows = np.arange(n)
+        live = (7 * rows // 3 + variant) % 3
+        top = tab[rows, live]
+        tab[:] = (top - 4990.0)[:, None]               # (_one_live for every row at once: the same subtraction)
+        tab[rows, live] = top
+        return Case(family, tab, marks=dict(zip(rows.tolist(), live.tolist())))
     if family in ("edge1000", "clamp"):
         offs = EDGE_OFFSETS if family == "edge1000" else CLAMP_OFFSETS
         tab = np.round(tab * 2.0 ** 20) / 2.0 ** 20
@@ -163,7 +167,107 @@ def case(family, n, variant=0):
             tab[w] = _one_live(np.full(3, -10.0), live, 4990.0)
             marks[w] = live
         return Case(family, tab, pen=UNDERFLOW_PEN, marks=marks)
+    if family == "plateaus":
+        C = blocking(n)[0]
+        lengths = [max(1, x) for x in (1, C - 1, C, C + 1, 3 * C + 2, 20 * C)]
+        w, i = 0, variant
+        while w < n:
+            live, end = i % 3, min(n, w + lengths[i % 6])
+            for other in ((live + 1) % 3, (live + 2) % 3):
+                tab[w:end, other] = tab[w:end, live] - 40.0
+            marks[w] = live
+            w, i = end, i + 1
+        return Case(family, tab, marks=marks)
     raise KeyError(family)
+
+
+# ---- long blocks: many windows a thread (tests/test_hard_tables_long.py, tests/test_gpu_log_long_blocks.py) ----------------------
+# A thread of the kernels walks the C windows of its block in loops that the compiler may unroll or pipeline (two of them are
+# unrolled by hand, 4 and 8 ways), and reads the chain mask a word of 32 windows at a time.  The lattice 256 C - 5 puts the trip
+# counts C and C - 5 into one launch for C = 6 .. 16: every remainder mod 4 and mod 8, an unrolled body run not at all, once and
+# more often.  8192: every block is one aligned mask word; 8193: blocks straddle the words at every offset, 7 idle threads;
+# 40000: a chromosome's windows; 2^21: the most the calls take.
+
+LONG_SIZES = [256 * C - 5 for C in range(6, 17)] + [1793, 2048, 8192, 8193, 40000, 1 << 21]
+# n_win -> (C, owning blocks, windows of the last block), written out: the CPU tier asserts blocking()'s formula gives them
+LONG_SHAPES = dict([(256 * C - 5, (C, 256, C - 5)) for C in range(6, 17)]
+                   + [(1793, (8, 225, 1)), (2048, (8, 256, 8)), (8192, (32, 256, 32)), (8193, (33, 249, 9)),
+                      (40000, (157, 255, 122)), (1 << 21, (8192, 256, 8192))])
+LONG_FINITE = FINITE + ["plateaus"]
+TINY_WEIGHTS = ["edge1000"]                            # the families that keep emission weights near 2^-1000
+LONG_FAMILIES = FAMILIES + ["plateaus"]                # (behind the others: the seeds of FAMILIES stay what they are)
+EDGE_SHIFT_VALUES = [-SHIFT_MAX, SHIFT_MAX, 0, -3 * BIT]
+
+
+def DENSE_WORD_BLOCKS(nbk):
+    """The two blocks with a start at every multiple of 32."""
+    return 1, nbk // 2
+
+
+def block_end(n, w):
+    """The end (exclusive) of the block that owns window w."""
+    C = blocking(n)[0]
+    return min(n, (w // C + 1) * C)
+
+
+def dense_chain_starts(n):
+    """Starts that no thread escapes: every window with w % 37 == 5, the first window of every third block, the last window of
+    every fifth block, every multiple of 32 in two blocks (DENSE_WORD_BLOCKS), and n - 1.  Strictly increasing, in [1, n)."""
+    C, nbk = blocking(n)
+    ws = set(range(5, n, 37))
+    ws |= {b * C for b in range(0, nbk, 3)}
+    ws |= {min(n, (b + 1) * C) - 1 for b in range(0, nbk, 5)}
+    for b in DENSE_WORD_BLOCKS(nbk):
+        ws |= {w for w in range(b * C, min(n, (b + 1) * C)) if w % 32 == 0}
+    ws.add(n - 1)
+    return sorted(w for w in ws if 1 <= w < n)
+
+
+def edge_shifts(n, seed):
+    """shifts(n, seed) with -2^30, +2^30, 0 and -3 bits in turn on the first, the second and the last window of every seventh
+    block: where the one-window look-ahead of the kernels' shift_at begins, is one window in, and stands still at the block's end.
+    (A shift of -2^30 makes every switch weight of its step 0: a table whose live states differ across that step has no path, the
+    dead-chain rule -- chain_alive below says which.)"""
+    C, nbk = blocking(n)
+    sh, i = shifts(n, seed), 0
+    for b in range(0, nbk, 7):
+        w0, w1 = b * C, min(n, (b + 1) * C)
+        for w in sorted({w0, min(w0 + 1, w1 - 1), w1 - 1}):
+            sh[w] = EDGE_SHIFT_VALUES[i % 4]
+            i += 1
+    return sh
+
+
+def chain_alive(tab, pen, shift=None, starts=()):
+    """Whether some path through the table has a weight other than 0 (the exact Z is not 0), from the supports alone: which
+    emission and switch weights are exactly 0 (below 2^-1000), walked as sets of states.  Only the windows with a zero switch
+    weight are walked: behind any other step every state with an emission is alive.
+    False: the dead-chain rule's mark on every row.  True: rows of gamma that sum to 1 -- unless a product of kept weights
+    underflows, the other way to D = 0.  Across a step without switch weights alpha_w[s] = alpha_{w-1}[s] b_w[s]:
+    alpha_{w-1}[s] is at least a switch weight times an emission weight below the vector's largest entry, so with kept weights
+    of 2^-46 and more (every family but TINY_WEIGHTS, at the penalties of PENS) nothing comes near 2^-1022; with emissions kept at
+    2^-999.5 the product of two of them is 0 in fp64, and such a table may have rows of 0 although it has paths."""
+    import hp_post_ref as H
+    import hp_steps_ref as S
+    tab = np.asarray(tab, dtype=np.float64)
+    n = len(tab)
+    if shift is None or n < 2:
+        return True
+    sh = np.asarray(shift, dtype=np.int64)
+    Pmin = min(H.penalty(p) for p in pen)
+    cut = -1000 * BIT
+    special = np.nonzero(Pmin + sh < cut)[0]
+    starts = set(int(s) for s in starts)
+    support = lambda w: {s for s, e in enumerate(H.emission(tab[w])) if e >= cut}
+    alive, at = None, -1                                   # the states alive at window `at`
+    for w in (int(x) for x in special if x >= 1 and int(x) not in starts):
+        prev = alive if at == w - 1 else support(w - 1)
+        P = S.window_penalties(pen, {w: int(sh[w])}, starts, w)
+        ok = [[True, P[0] >= cut, P[1] >= cut], [P[0] >= cut, True, P[2] >= cut], [P[1] >= cut, P[2] >= cut, True]]
+        alive, at = {s for s in support(w) if any(ok[q][s] for q in prev)}, w
+        if not alive:
+            return False
+    return True
 
 
 # ---- a dead chain from real inputs: the host program's files -----------------------------------------------------------------

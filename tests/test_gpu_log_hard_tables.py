@@ -36,7 +36,7 @@ def run_of(eng, n_win, targets=TARGETS):
 def table_set(family, n):
     """(tables [T][n][3], penalties, the family's own shifts or None, the individuals that carry the family).  A finite family: its
     five variants.  A dead one: its two variants, then three finite tables that live under the same penalties and shifts."""
-    if family in HT.FINITE:
+    if family not in HT.DEAD:
         return np.stack([HT.case(family, n, v).tab for v in range(T)]), None, None, list(range(T))
     c0, c1 = HT.case(family, n, 0), HT.case(family, n, 1)
     shift = None if c0.shift is None else np.minimum(c0.shift, c1.shift)          # (both pairs' shifts: 0 or -2^30)
@@ -44,11 +44,12 @@ def table_set(family, n):
     return np.stack([c0.tab, c1.tab] + rest), c0.pen, shift, [0, 1]
 
 
-def forms(family, n, pen, own):
+def forms(family, n, pen, own, starts=None, rnd=None):
     """[(penalties, starts, shift)]: plain, with chain starts, with shifts, with both.  A dead-shift table keeps its own shifts in
-    all four (the others' shifts come from +-3 bits), and its chain starts keep away from the pairs."""
-    starts = HT.chain_starts(n)
-    rnd = HT.shifts(n, 9)
+    all four (the others' shifts come from +-3 bits), and its chain starts keep away from the pairs.  starts, rnd: other chain
+    starts and shifts than hard_tables.chain_starts and shifts(n, 9)."""
+    starts = HT.chain_starts(n) if starts is None else starts
+    rnd = HT.shifts(n, 9) if rnd is None else rnd
     if own is not None:
         rnd = np.where(own != 0, own, rnd).astype(np.int32)
         starts = [w for w in starts if own[w] == 0]

@@ -44,10 +44,10 @@ def _mat_vec(M, v):
     return [(M[3 * q] * v[0] + M[3 * q + 1] * v[1]) + M[3 * q + 2] * v[2] for q in range(3)]
 
 
-def restated_posteriors(tab, pen, shift=None, starts=(), rule=True):
+def restated_posteriors(tab, pen, shift=None, starts=(), rule=True, model=None):
     """(post [n][3], expect [3], log2_z) by steps 1 .. 5 of ibdg_states.h, on the weights of hp_sample_ref.Model.  rule: the
-    dead-chain rule; without it a window with D == 0 gets IEEE's 0 / 0."""
-    m = R.Model(tab, pen, None if shift is None else [int(x) for x in shift], starts)
+    dead-chain rule; without it a window with D == 0 gets IEEE's 0 / 0.  model: that Model, where the caller has it already."""
+    m = model or R.Model(tab, pen, None if shift is None else [int(x) for x in shift], starts)
     n = m.n
     _, nbk, blocks = H.blocking(n)
     mat, mexp = [], []
