@@ -2674,8 +2674,30 @@ static void *dev_start(void *arg)
         quit(1);                          \
     } while (0)
 
+/* <out>/<pileup-name>.<individual>.<kind>.txt: the files of one comparison individual, in the order they are opened (the run's
+ * own are RUN_FILES, further down).  RULE: every file is a row here, and a row is all it needs.  Each is opened without
+ * truncation by the loop (outputs_open: giving back the pages of an earlier run's 330 MB table takes tens of milliseconds,
+ * which belong to the output job, not between two engine calls), emptied by the job that writes it (outs_empty) or, when the
+ * run fails before that, by outs_settle_one, and closed by its writer (out_close) or the job's tail (outs_close). */
+enum { F_TAB, F_SUM, F_LSUM, F_HG, F_LP, F_LS, F_LSMP, N_IND_FILES };
+static const struct {
+    const char *kind;
+    const int *on;          /* the option that turns it on (NULL: always) */
+    const int *to_null;     /* the option that puts /dev/null in its place: nothing to list or to empty */
+    int log;                /* with --log-stats the kind is log<kind> */
+} IND_FILES[N_IND_FILES] = {
+    [F_TAB] = {"tab", .to_null = &opt_summary_only},
+    [F_SUM] = {"summary"},
+    [F_LSUM] = {"logsummary", &opt_log_summary},
+    [F_HG] = {"hiddengem", &opt_states, .log = 1},
+    [F_LP] = {"logposteriors", &opt_posteriors},
+    [F_LS] = {"logsegments", &opt_segments},
+    [F_LSMP] = {"logsamples", &has_sample_paths},
+};
+static int ind_file_on(int k) { return !IND_FILES[k].on || *IND_FILES[k].on; }
+static int ind_file_null(int k) { return IND_FILES[k].to_null && *IND_FILES[k].to_null; }
 
-/* ---- the two output files of one comparison individual (src/ibdgem.c:144-152, :547-548, :731-733, :751-768) ---------
+/* ---- the output files of one comparison individual (src/ibdgem.c:144-152, :547-548, :731-733, :751-768) --------------
  * Everything the files are made of, so that they can be written while the next individual is on the device: with the
  * site list shared by all individuals (no -v, no -D) a default run of many of them is bound by its 330 MB tables, and
  * tables of different individuals go into different files, which take writers side by side (tools/write_floor.c: one
@@ -2697,8 +2719,7 @@ typedef struct {
     const double *site_ll;                      /* per-row values (NULL with --summary-only) */
     const char *pre;                            /* columns 1-9 of every row as text (row_prefix_build), or NULL */
     const uint32_t *pre_off;
-    FILE *tab, *sum;                            /* open (stdout with --plan); closed by the job */
-    FILE *lsum;                                 /* --log-summary: the individual's *.logsummary.txt, else NULL; closed by the job */
+    FILE *file[N_IND_FILES];                    /* the files of IND_FILES that are open (tab and summary: stdout with --plan); closed by the job */
     win_table wt;                               /* owned: freed when the files are closed */
     int threads;
     /* when it runs beside the main thread */
@@ -2711,12 +2732,8 @@ typedef struct {
     const char *sq;                             /* the pileup's name (-N) */
     FILE *err;                                  /* where the pileup's messages go */
     /* --states */
-    FILE *hg;                                   /* the individual's *.hiddengem.txt (NULL with --stats-only); closed by the job */
     ind_stats *res;                             /* the individual's lines of the run's statistics files: the twin's results go here */
-    FILE *lp;                                   /* --posteriors: the individual's *.logposteriors.txt (NULL with --stats-only); closed by the job */
-    FILE *ls;                                   /* --segments: the individual's *.logsegments.txt (NULL with --stats-only); closed by the job */
-    FILE *lsmp;                                 /* --sample-paths: the individual's *.logsamples.txt (NULL with --stats-only); closed by the job */
-    uint64_t (*smp_tot)[9];                     /* ... and the run's totals [K][9], which the individual's draws are added to */
+    uint64_t (*smp_tot)[9];                     /* --sample-paths: the run's totals [K][9], which the individual's draws are added to */
     hg_path hgp;                                /* the slot's path arrays and text buffer (kept between individuals) */
     char *hg_buf;
     size_t hg_cap;
@@ -2725,6 +2742,34 @@ typedef struct {
 enum { OUT_SLOTS = 12, MAX_WORKERS = 64 };
 static out_job g_outs[MAX_WORKERS][OUT_SLOTS];  /* per worker (one per context with --pileup-list, else one) */
 static int g_n_workers = 1;
+
+/* every open file of the job emptied (a /dev/null in a file's place cannot be); how many could not be */
+static int outs_empty(out_job *o)
+{
+    int bad = 0;
+    o->pending = 0;
+    for (int k = 0; k < N_IND_FILES; ++k)
+        if (o->file[k] && !ind_file_null(k))
+            bad += ftruncate(fileno(o->file[k]), 0) != 0;
+    return bad;
+}
+
+/* a file of the individual's, where there is one: closed, and forgotten by its job; 1: the close failed */
+static int out_close(FILE **f)
+{
+    const int bad = *f && *f != stdout && fclose(*f) != 0;      /* (stdout: --plan's, not the job's to close) */
+    *f = NULL;
+    return bad;
+}
+
+/* every file of the job that is still open */
+static int outs_close(out_job *o)
+{
+    int bad = 0;
+    for (int k = 0; k < N_IND_FILES; ++k)
+        bad |= out_close(&o->file[k]);
+    return bad;
+}
 
 /* join a worker's output threads; when its run is failing, empty the files nobody got to */
 static void outs_settle_one(out_job *outs, int failing)
@@ -2736,11 +2781,9 @@ static void outs_settle_one(out_job *outs, int failing)
             pthread_join(o->th, NULL);
         }
         if (failing && o->pending && !opt_plan) {
-            o->pending = 0;
-            FILE *const files[4] = {opt_summary_only ? NULL : o->tab, o->sum, o->lsum, o->hg};
-            for (int f = 0; f < 4; ++f)
-                if (files[f] && ftruncate(fileno(files[f]), 0) != 0)
-                    fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
+            for (int bad = outs_empty(o); bad > 0; --bad)
+                fprintf(stderr, "[::] WARNING: could not empty an output file of %s.\n", o->tname);
+            outs_close(o);
         }
     }
 }
@@ -2839,14 +2882,6 @@ static int write_states_parallel(FILE *f, const hg_path *h, int threads, char **
  * ibdg_window_log2_states), its scores printed in bits */
 static const char log_hg_header[] = "Segment\tIBD0_LogScore\tIBD1_LogScore\tIBD2_LogScore\tInferred_State\n";
 
-/* an individual's statistics file, where there is one: closed, and forgotten by its job; 1: the close failed */
-static int out_close(FILE **f)
-{
-    const int bad = *f && fclose(*f) != 0;
-    *f = NULL;
-    return bad;
-}
-
 /* what the three passes over an individual's log2 table share: the positions of its windows (first [n], then last; for
  * --segments, --chain-gap and --switch-scale, else NULL), its chain starts (--chain-gap; none without it) and its step shifts
  * (--switch-scale; NULL without it) */
@@ -2864,23 +2899,24 @@ static int posteriors_individual(out_job *o, const log_chains *lc)
     if (!opt_posteriors)
         return 0;
     const size_t n = o->wt.w.n_win;
-    double *post = o->lp ? malloc((n ? n : 1) * 3 * sizeof *post) : NULL;
-    int bad = o->lp && !post;
+    FILE *const out = o->file[F_LP];
+    double *post = out ? malloc((n ? n : 1) * 3 * sizeof *post) : NULL;
+    int bad = out && !post;
     if (!bad && ibdg_log2_posteriors_steps_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, post, o->res->po, o->res->po + 3, lc->starts,
                                                 lc->n_starts, lc->shift)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
-    if (!bad && o->lp) {
-        bad = fputs("Segment\tPost_IBD0\tPost_IBD1\tPost_IBD2\tMax_State\n", o->lp) < 0;
+    if (!bad && out) {
+        bad = fputs("Segment\tPost_IBD0\tPost_IBD1\tPost_IBD2\tMax_State\n", out) < 0;
         for (size_t w = 0; w < n && !bad; ++w) {
             const double *g = post + 3 * w;
             int m = g[1] > g[0] ? 1 : 0;
             m = g[2] > g[m] ? 2 : m;
-            bad = fprintf(o->lp, "%d\t%.6f\t%.6f\t%.6f\t%d\n", (int)(w + 1), g[0], g[1], g[2], m) < 0;
+            bad = fprintf(out, "%d\t%.6f\t%.6f\t%.6f\t%d\n", (int)(w + 1), g[0], g[1], g[2], m) < 0;
         }
     }
-    bad = out_close(&o->lp) || bad;
+    bad = out_close(&o->file[F_LP]) || bad;
     free(post);
     return bad;
 }
@@ -2898,16 +2934,17 @@ static int segments_individual(out_job *o, const log_chains *lc)
     const size_t n = o->wt.w.n_win;
     const uint64_t *pos = lc->pos;
     uint64_t n_seg = 0;
-    ibdg_segment *seg = o->ls ? malloc((n ? n : 1) * sizeof *seg) : NULL;
-    int bad = o->ls && !seg;
+    FILE *const out = o->file[F_LS];
+    ibdg_segment *seg = out ? malloc((n ? n : 1) * sizeof *seg) : NULL;
+    int bad = out && !seg;
     if (!bad && ibdg_log2_segments_steps_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, opt_posteriors, pos, pos + n, seg, n, &n_seg,
                                               o->res->sg, lc->starts, lc->n_starts, lc->shift)) {
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
-    if (!bad && o->ls) {
+    if (!bad && out) {
         size_t chain = 0;                        /* the starts at or before the segment at hand */
-        bad = fprintf(o->ls, "%s%s%s\n", has_chain_gap ? "Chain\t" : "", log_seg_header, opt_posteriors ? "\tPost_Mean\tPost_Min" : "") < 0;
+        bad = fprintf(out, "%s%s%s\n", has_chain_gap ? "Chain\t" : "", log_seg_header, opt_posteriors ? "\tPost_Mean\tPost_Min" : "") < 0;
         for (size_t k = 0; k < n_seg && !bad; ++k) {
             const ibdg_segment *g = &seg[k];
             const size_t f = g->first, l = f + g->n_win - 1;
@@ -2917,18 +2954,18 @@ static int segments_individual(out_job *o, const log_chains *lc)
                 sites += o->wt.w.ncov[w];
             while (chain < lc->n_starts && lc->starts[chain] <= f)
                 ++chain;
-            bad = has_chain_gap && fprintf(o->ls, "%zu\t", chain + 1) < 0;
-            bad = bad || fprintf(o->ls, "%zu\t%u\t%zu\t%zu\t%llu\t%llu\t%llu\t%u\t%lu\t%.4Lf\t%.4Lf\t%.4Lf\t%.4Lf", k + 1, g->state, f + 1,
+            bad = has_chain_gap && fprintf(out, "%zu\t", chain + 1) < 0;
+            bad = bad || fprintf(out, "%zu\t%u\t%zu\t%zu\t%llu\t%llu\t%llu\t%u\t%lu\t%.4Lf\t%.4Lf\t%.4Lf\t%.4Lf", k + 1, g->state, f + 1,
                           l + 1, (unsigned long long)pos[f], (unsigned long long)pos[n + l],
                           (unsigned long long)(pos[n + l] - pos[f] + 1), g->n_win, sites, (long double)g->e[0] / 65536,
                           (long double)g->e[1] / 65536, (long double)g->e[2] / 65536,
                           (long double)(own - (a > b ? a : b)) / 65536) < 0;
             if (!bad && opt_posteriors)
-                bad = fprintf(o->ls, "\t%.6Lf\t%.6f", (long double)g->post_q / ((long double)g->n_win * 4294967296.0L), g->post_min) < 0;
-            bad = bad || fputc('\n', o->ls) == EOF;
+                bad = fprintf(out, "\t%.6Lf\t%.6f", (long double)g->post_q / ((long double)g->n_win * 4294967296.0L), g->post_min) < 0;
+            bad = bad || fputc('\n', out) == EOF;
         }
     }
-    bad = out_close(&o->ls) || bad;
+    bad = out_close(&o->file[F_LS]) || bad;
     free(seg);
     return bad;
 }
@@ -2942,6 +2979,7 @@ static int samples_individual(out_job *o, const log_chains *lc)
     if (!has_sample_paths)
         return 0;
     const size_t n = o->wt.w.n_win, K = opt_sample_paths;
+    FILE *const out = o->file[F_LSMP];
     uint64_t *rec = malloc(K * 15 * sizeof *rec);
     int bad = !rec;
     if (bad)
@@ -2951,16 +2989,16 @@ static int samples_individual(out_job *o, const log_chains *lc)
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
-    if (!bad && o->lsmp) {
+    if (!bad && out) {
         bad = fputs("Sample\tWIN_IBD0\tWIN_IBD1\tWIN_IBD2\tSEG_IBD0\tSEG_IBD1\tSEG_IBD2\tBP_IBD0\tBP_IBD1\tBP_IBD2\t"
-                    "LONGEST_BP_IBD0\tLONGEST_BP_IBD1\tLONGEST_BP_IBD2\n", o->lsmp) < 0;
+                    "LONGEST_BP_IBD0\tLONGEST_BP_IBD1\tLONGEST_BP_IBD2\n", out) < 0;
         for (size_t k = 0; k < K && !bad; ++k) {
             const uint64_t *r = rec + 15 * k;
-            bad = fprintf(o->lsmp, "%zu", k + 1) < 0;
+            bad = fprintf(out, "%zu", k + 1) < 0;
             for (int i = 0; i < 15 && !bad; ++i)
                 if (i < 6 || i >= 9)                 /* (the windows of the longest segments are not in this file) */
-                    bad = fprintf(o->lsmp, "\t%llu", (unsigned long long)r[i]) < 0;
-            bad = bad || fputc('\n', o->lsmp) == EOF;
+                    bad = fprintf(out, "\t%llu", (unsigned long long)r[i]) < 0;
+            bad = bad || fputc('\n', out) == EOF;
         }
     }
     if (!bad && !(o->res->smp_row = sample_individual_row(rec, K, o->smp_tot))) {
@@ -2968,19 +3006,20 @@ static int samples_individual(out_job *o, const log_chains *lc)
         bad = 1;
     }
     free(rec);
-    return out_close(&o->lsmp) || bad;
+    return out_close(&o->file[F_LSMP]) || bad;
 }
 
 static int log_states_individual(out_job *o)
 {
     const size_t n = o->wt.w.n_win;
     uint64_t *const count = o->res->st;
-    uint8_t *path = o->hg ? malloc(n ? n : 1) : NULL;
-    int64_t *score = o->hg ? malloc((n ? n : 1) * 3 * sizeof *score) : NULL;
+    FILE *const out = o->file[F_HG];
+    uint8_t *path = out ? malloc(n ? n : 1) : NULL;
+    int64_t *score = out ? malloc((n ? n : 1) * 3 * sizeof *score) : NULL;
     const int want_pos = opt_segments || has_chain_gap || has_switch_scale || has_sample_paths;
     log_chains lc = {want_pos ? malloc((2 * n + 1) * sizeof *lc.pos) : NULL, has_chain_gap ? malloc((n + 1) * sizeof *lc.starts) : NULL, 0,
                      has_switch_scale ? malloc((n + 1) * sizeof *lc.shift) : NULL};
-    int bad = (o->hg && (!path || !score)) || (want_pos && !lc.pos) || (has_chain_gap && !lc.starts) || (has_switch_scale && !lc.shift);
+    int bad = (out && (!path || !score)) || (want_pos && !lc.pos) || (has_chain_gap && !lc.starts) || (has_switch_scale && !lc.shift);
     for (size_t w = 0; w < n && want_pos && !bad; ++w) {
         lc.pos[w] = o->pos_first ? o->pos_first[w] : rows[o->s_row[o->wt.w.first[w]]].pos;
         lc.pos[n + w] = o->pos_last ? o->pos_last[w] : rows[o->s_row[o->wt.w.last[w]]].pos;
@@ -2993,23 +3032,19 @@ static int log_states_individual(out_job *o)
         fprintf(o->err, "%s\n", ibdg_last_error(NULL));
         bad = 1;
     }
-    if (!bad && o->hg) {
+    if (!bad && out) {
         hg_path tail = {.n = n, .count = {(size_t)count[0], (size_t)count[1], (size_t)count[2]}};
         char buf[256];
-        bad = fputs(log_hg_header, o->hg) < 0;
+        bad = fputs(log_hg_header, out) < 0;
         for (size_t w = 0; w < n && !bad; ++w)
-            bad = fprintf(o->hg, "%d\t%.4Lf\t%.4Lf\t%.4Lf\t%d\n", (int)(w + 1), (long double)score[3 * w] / 65536,
+            bad = fprintf(out, "%d\t%.4Lf\t%.4Lf\t%.4Lf\t%d\n", (int)(w + 1), (long double)score[3 * w] / 65536,
                           (long double)score[3 * w + 1] / 65536, (long double)score[3 * w + 2] / 65536, path[w]) < 0;
-        bad = bad || fwrite(buf, 1, hg_format_tail(&tail, buf), o->hg) == 0;
+        bad = bad || fwrite(buf, 1, hg_format_tail(&tail, buf), out) == 0;
     }
-    bad = out_close(&o->hg) || bad;
+    bad = out_close(&o->file[F_HG]) || bad;
     free(path);
     free(score);
-    if ((want_pos && !lc.pos) || (has_chain_gap && !lc.starts) || (has_switch_scale && !lc.shift)) {    /* (out of memory: the other two files are closed as they are) */
-        out_close(&o->lp);
-        out_close(&o->ls);
-        out_close(&o->lsmp);
-    } else {
+    if ((!want_pos || lc.pos) && (!has_chain_gap || lc.starts) && (!has_switch_scale || lc.shift)) {    /* (else out of memory: the other files are closed as they are) */
         bad = posteriors_individual(o, &lc) || bad;
         bad = segments_individual(o, &lc) || bad;
         bad = samples_individual(o, &lc) || bad;
@@ -3020,7 +3055,7 @@ static int log_states_individual(out_job *o)
     return bad;
 }
 
-/* 0: the path is found, counted for ibdstates.txt and (o->hg) written and its file closed */
+/* 0: the path is found, counted for ibdstates.txt and (with a file of F_HG open) written and its file closed */
 static int states_individual(out_job *o)
 {
     if (opt_log_stats)
@@ -3035,110 +3070,98 @@ static int states_individual(out_job *o)
         return 1;
     for (int s = 0; s < 3; ++s)
         o->res->st[s] = h->count[s];
-    if (!o->hg)
+    if (!o->file[F_HG])
         return 0;
-    const int bad = write_states_parallel(o->hg, h, o->threads, &o->hg_buf, &o->hg_cap);
-    return out_close(&o->hg) || bad;
+    const int bad = write_states_parallel(o->file[F_HG], h, o->threads, &o->hg_buf, &o->hg_cap);
+    return out_close(&o->file[F_HG]) || bad;
 }
 
-static void *output_individual(void *arg)
+/* The job is a sequence of stages over one out_job, each returning 0, or 1 after its own message to the pileup's stream, and
+ * one way out (output_individual).  The files were opened by the loop's thread: a directory that cannot be written stops the
+ * run at once. */
+#define OFAIL(...) do { fprintf(o->err, __VA_ARGS__); return 1; } while (0)
+
+/* the files emptied, the command line (--plan: its own line in their place) and the header block (:144-152, :547-548) */
+static int out_begin(out_job *o)
 {
-    out_job *o = arg;
-    o->failed = 1;
-    if (opt_stats_only) {                        /* --stats-only --states: the path's counts alone, no file of the individual's */
-        const int bad = states_individual(o);
-        if (bad)
-            fprintf(o->err, "[::] ERROR finding the IBD states of %s.\n", o->tname);
-        win_table_free(&o->wt);
-        o->failed = bad;
-        return NULL;
-    }
-    FILE *tab = o->tab, *sum = o->sum;           /* opened by the main thread: a directory that cannot be written stops the run at once */
+    FILE *const tab = o->file[F_TAB];
     if (opt_plan)
         printf("## PLAN %s %s processed=%lu skipped=%lu windows=%zu cull_p=%f\n", o->sq, o->tname, o->processed, o->skipped,
                o->wt.w.n_win, o->cull_p);
-    else {
-        if ((!opt_summary_only && ftruncate(fileno(tab), 0) != 0) || ftruncate(fileno(sum), 0) != 0 ||
-            (o->hg && ftruncate(fileno(o->hg), 0) != 0) || (o->lsum && ftruncate(fileno(o->lsum), 0) != 0) ||
-            (o->lp && ftruncate(fileno(o->lp), 0) != 0) || (o->ls && ftruncate(fileno(o->ls), 0) != 0)) {
-            fprintf(o->err, "[::] ERROR in compare_impute(): Cannot empty the output files of %s.\n", o->tname);
-            return NULL;
-        }
-        o->pending = 0;
+    else if (outs_empty(o))
+        OFAIL("[::] ERROR in compare_impute(): Cannot empty the output files of %s.\n", o->tname);
+    else
         fprintf(tab, "# Entered command: %s\n\n", o->user_cmd);
-    }
-    /* header block (:144-152, :547-548) */
     fprintf(tab, "# INPUT COVERAGE DISTRIBUTION:\n# COVERAGE N_SITES\n");
     for (unsigned c = 0; c <= opt_max_cov; ++c)
         fprintf(tab, "# %d %lu\n", c, o->in_dist[c]);
     fprintf(tab, "# MEAN DEPTH = %lf\n# CULL DEPTH RATIO = %lf\n", o->mean_cov, o->cull_p);
     fprintf(tab, "# CHR\trsID\tPOS\tREF\tALT\tAF\tDP\tSQ_NREF\tSQ_NALT\tGT_A0\tGT_A1\tLIBD0\tLIBD1\tLIBD2\n");
     if (!opt_plan)
-        fprintf(sum, "# SEGMENT\tSTART\tEND\tLIBD0\tLIBD1\tLIBD2\tNUM_SITES\n");
-    if (!opt_summary_only) {
-        fmt_job proto;
-        memset(&proto, 0, sizeof proto);
-        proto.cand = o->cand;
-        proto.s_cand = o->s_cand;
-        proto.pu = o->pu;
-        proto.site_ll = o->site_ll;
-        proto.s_nr = o->s_nr;
-        proto.s_na = o->s_na;
-        proto.tgt = o->tgt;
-        proto.plan = opt_plan;
-        proto.pre = o->pre;
-        proto.pre_off = o->pre_off;
-        if (write_rows_parallel(tab, proto, o->n, o->threads)) {
-            fprintf(o->err, "[::] ERROR writing the per-site rows of %s.\n", o->tname);
-            return NULL;
-        }
-    }
+        fprintf(o->file[F_SUM], "# SEGMENT\tSTART\tEND\tLIBD0\tLIBD1\tLIBD2\tNUM_SITES\n");
+    return 0;
+}
+
+/* the per-site rows (:731-733) */
+static int out_rows(out_job *o)
+{
+    const fmt_job proto = {.cand = o->cand, .s_cand = o->s_cand, .pu = o->pu, .site_ll = o->site_ll, .s_nr = o->s_nr, .s_na = o->s_na,
+                           .tgt = o->tgt, .plan = opt_plan, .pre = o->pre, .pre_off = o->pre_off};
+    if (!opt_summary_only && write_rows_parallel(o->file[F_TAB], proto, o->n, o->threads))
+        OFAIL("[::] ERROR writing the per-site rows of %s.\n", o->tname);
+    return 0;
+}
+
+/* the summary rows (:751-756) through the program's own conversions, by the team of threads: with many comparison
+ * individuals per run the seven stdio calls per window were the longest item of an individual (25 ms of 33 at 35 000
+ * windows); --plan: the windows' lines in their place */
+static int out_summaries(out_job *o)
+{
+    sum_job sj = {.s_row = o->s_row, .w_first = o->wt.w.first, .w_last = o->wt.w.last, .w_ncov = o->wt.w.ncov, .win_ll = o->wt.ll,
+                  .pos_first = o->pos_first, .pos_last = o->pos_last};
     if (opt_plan) {
         for (size_t w = 0; w < o->wt.w.n_win; ++w)
             printf("## WINDOW %zu\t%lu\t%lu\t%u\n", w + 1, rows[o->s_row[o->wt.w.first[w]]].pos, rows[o->s_row[o->wt.w.last[w]]].pos,
                    o->wt.w.ncov[w]);
-    } else {
-        /* the summary rows (:751-756) through the program's own conversions, by the team of threads: with many
-         * comparison individuals per run the seven stdio calls per window were the longest item of an individual
-         * (25 ms of 33 at 35 000 windows) */
-        sum_job sj;
-        memset(&sj, 0, sizeof sj);
-        sj.s_row = o->s_row; sj.w_first = o->wt.w.first; sj.w_last = o->wt.w.last; sj.w_ncov = o->wt.w.ncov; sj.win_ll = o->wt.ll;
-        sj.pos_first = o->pos_first; sj.pos_last = o->pos_last;
-        if (write_summary_parallel(sum, sj, o->wt.w.n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
-            fprintf(o->err, "[::] ERROR writing the summary rows of %s.\n", o->tname);
-            return NULL;
-        }
-        if (o->lsum) {
-            /* the same rows with the three likelihoods as log2: columns 1-3 and 7 through the same conversions */
-            fprintf(o->lsum, "# SEGMENT\tSTART\tEND\tLOG2_LIBD0\tLOG2_LIBD1\tLOG2_LIBD2\tNUM_SITES\n");
-            sj.win_ll = o->wt.log;
-            sj.logs = 1;
-            if (write_summary_parallel(o->lsum, sj, o->wt.w.n_win, o->threads, &o->sum_buf, &o->sum_cap)) {
-                fprintf(o->err, "[::] ERROR writing the log summary rows of %s.\n", o->tname);
-                return NULL;
-            }
-        }
+        return 0;
     }
-    /* footer (:761-768) */
+    if (write_summary_parallel(o->file[F_SUM], sj, o->wt.w.n_win, o->threads, &o->sum_buf, &o->sum_cap))
+        OFAIL("[::] ERROR writing the summary rows of %s.\n", o->tname);
+    if (!o->file[F_LSUM])
+        return 0;
+    /* the same rows with the three likelihoods as log2: columns 1-3 and 7 through the same conversions */
+    fprintf(o->file[F_LSUM], "# SEGMENT\tSTART\tEND\tLOG2_LIBD0\tLOG2_LIBD1\tLOG2_LIBD2\tNUM_SITES\n");
+    sj.win_ll = o->wt.log;
+    sj.logs = 1;
+    if (write_summary_parallel(o->file[F_LSUM], sj, o->wt.w.n_win, o->threads, &o->sum_buf, &o->sum_cap))
+        OFAIL("[::] ERROR writing the log summary rows of %s.\n", o->tname);
+    return 0;
+}
+
+/* footer (:761-768) */
+static int out_footer(out_job *o)
+{
+    FILE *const tab = o->file[F_TAB];
     fprintf(tab, "# FINAL COVERAGE DISTRIBUTION:\n# COVERAGE N_SITES\n");
     for (unsigned c = 0; c <= opt_max_cov; ++c)
         fprintf(tab, "# %d %lu\n", c, o->final_dist[c]);
     fprintf(tab, "# FINAL MEAN DEPTH = %lf\n", (double)o->final_total / o->processed);
     fprintf(tab, "## Number of sites processed: %lu\n", o->processed);
     fprintf(tab, "## Number of sites skipped: %lu\n", o->skipped);
-    int bad = 0;
-    if (!opt_plan) {
-        bad |= fclose(tab) != 0;
-        bad |= fclose(sum) != 0;
-        if (o->lsum)
-            bad |= fclose(o->lsum) != 0;
-        o->lsum = NULL;
-    }
-    if (opt_states && states_individual(o)) {
-        fprintf(o->err, "[::] ERROR writing the IBD-state path of %s.\n", o->tname);
+    return 0;
+}
+
+static void *output_individual(void *arg)
+{
+    out_job *o = arg;
+    /* (--stats-only --states: the path's counts alone, no file of the individual's is open) */
+    int bad = !opt_stats_only && (out_begin(o) || out_rows(o) || out_summaries(o) || out_footer(o));
+    if (!bad && opt_states && states_individual(o)) {
+        fprintf(o->err, opt_stats_only ? "[::] ERROR finding the IBD states of %s.\n" : "[::] ERROR writing the IBD-state path of %s.\n", o->tname);
         bad = 1;
     }
+    /* the one way out, of a job that failed as well: whatever is still open is closed, the window table given back */
+    bad = outs_close(o) || bad;
     win_table_free(&o->wt);
     o->failed = bad;
     return NULL;
@@ -4066,50 +4089,50 @@ static void summary_positions(pile_run *r)
 }
 
 /* ---- the individual's output job ---- */
-/* One output file of the individual, OUT/NAME.TARGET.KIND.txt: opened here, emptied by whoever writes it -- giving back the
- * pages of an earlier run's 330 MB table takes tens of milliseconds, which belong to the individual's output job, not between
- * two engine calls -- and listed among the pileup's files.  to_null: /dev/null in its place.  With fn_out the name goes to
- * the caller, who reports a failure; otherwise it is reported here.  NULL: not opened. */
-static FILE *out_file_open(pile_run *r, const char *kind, int to_null, char **fn_out)
+/* File k of IND_FILES for the individual at hand, OUT/NAME.TARGET.KIND.txt: opened without truncation (see the table) and
+ * listed among the pileup's files, with /dev/null in its place where its row says so.  NULL: not opened (fn NULL: no memory
+ * for the name); the caller reports it. */
+static FILE *out_file_open(pile_run *r, int k, const char *fn)
 {
-    char *fn = NULL;
-    FILE *f = NULL;
-    if (asprintf(&fn, "%s/%s.%s.%s.txt", g_out_dir, r->pj->name, r->tname, kind) >= 0) {
-        const int fd = open(to_null ? "/dev/null" : fn, O_WRONLY | O_CREAT, 0666);
-        f = fd >= 0 ? fdopen(fd, "w") : NULL;
-        if (f && !to_null)
-            pj_add_file(r->pj, fn);
-        if (!f && !fn_out)
-            fprintf(r->err, "[::] ERROR in compare_impute(): Cannot open '%s' for writing.\n", fn);
-    } else
-        fn = NULL;
-    if (fn_out)
-        *fn_out = fn;
-    else
-        free(fn);
+    const int fd = fn ? open(ind_file_null(k) ? "/dev/null" : fn, O_WRONLY | O_CREAT, 0666) : -1;
+    FILE *f = fd >= 0 ? fdopen(fd, "w") : NULL;
+    if (f && !ind_file_null(k))
+        pj_add_file(r->pj, fn);
     return f;
 }
 
+/* The individual's files, opened in the table's order up to the first that cannot be.  The files after that one are not
+ * opened, so no settle reaches them: where an earlier run left one it is emptied by name here (none is made), or it would
+ * outlive this failing run looking complete. */
 static int outputs_open(pile_run *r, out_job *o)
 {
-    char *tab_fn, *sum_fn;
-    o->hg = o->lsum = o->lp = o->ls = o->lsmp = NULL;
+    char *fn[N_IND_FILES] = {NULL};
+    int failed = -1;
+    memset(o->file, 0, sizeof o->file);
     if (opt_plan || opt_stats_only) {         /* (--stats-only --states: the table is here for its path alone) */
-        o->tab = o->sum = opt_plan ? stdout : NULL;
+        o->file[F_TAB] = o->file[F_SUM] = opt_plan ? stdout : NULL;
         return 0;
     }
-    o->tab = out_file_open(r, "tab", opt_summary_only, &tab_fn);
-    o->sum = out_file_open(r, "summary", 0, &sum_fn);
     o->pending = 1;
-    if ((!o->tab || !o->sum) && tab_fn && sum_fn)
-        fprintf(r->err, "[::] ERROR in compare_impute(): Cannot open '%s' and/or '%s' for writing.\n", tab_fn, sum_fn);
-    free(tab_fn);
-    free(sum_fn);
-    return !o->tab || !o->sum || (opt_log_summary && !(o->lsum = out_file_open(r, "logsummary", 0, NULL))) ||
-           (opt_states && !(o->hg = out_file_open(r, opt_log_stats ? "loghiddengem" : "hiddengem", 0, NULL))) ||
-           (opt_posteriors && !(o->lp = out_file_open(r, "logposteriors", 0, NULL))) ||
-           (opt_segments && !(o->ls = out_file_open(r, "logsegments", 0, NULL))) ||
-           (has_sample_paths && !(o->lsmp = out_file_open(r, "logsamples", 0, NULL)));
+    for (int k = 0; k < N_IND_FILES; ++k) {
+        if (!ind_file_on(k))
+            continue;
+        if (asprintf(&fn[k], "%s/%s.%s.%s%s.txt", g_out_dir, r->pj->name, r->tname, IND_FILES[k].log && opt_log_stats ? "log" : "",
+                     IND_FILES[k].kind) < 0)
+            fn[k] = NULL;
+        if (failed < 0 || k == F_SUM) {       /* (the summary is tried whatever became of the tab: one message names both) */
+            if (!(o->file[k] = out_file_open(r, k, fn[k])) && failed < 0)
+                failed = k;
+        } else if (fn[k])
+            (void)!truncate(fn[k], 0);
+    }
+    if (failed >= 0 && failed <= F_SUM && fn[F_TAB] && fn[F_SUM])
+        fprintf(r->err, "[::] ERROR in compare_impute(): Cannot open '%s' and/or '%s' for writing.\n", fn[F_TAB], fn[F_SUM]);
+    if (failed > F_SUM && fn[failed])
+        fprintf(r->err, "[::] ERROR in compare_impute(): Cannot open '%s' for writing.\n", fn[failed]);
+    for (int k = 0; k < N_IND_FILES; ++k)
+        free(fn[k]);
+    return failed >= 0;
 }
 
 /* everything the individual's files are made of goes to its slot's job, the window table with it; the job runs beside the
