@@ -2503,6 +2503,64 @@ int ibdg_window_log2_posteriors(ibdg_ctx *c, double p01, double p02, double p12,
     return 0;
 }
 
+int ibdg_log2_switches_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                            size_t n_starts, const int32_t *shift, double *sw, double expect[3], uint64_t counted[3])
+{
+    char msg[256];
+    if (ibdg::log2_switches_host(__func__, log2_tab, n_win, p01, p02, p12, starts, n_starts, shift, sw, expect, counted, msg, sizeof msg))
+        return fail(nullptr, "%s", msg);
+    return 0;
+}
+
+int ibdg_switch_penalty_update(const double p[3], const double total[3], size_t n_individuals, const double prior[3], double next[3])
+{
+    if (!p || !total || !prior || !next)
+        return fail(nullptr, "[::] ERROR in %s: NULL %s", __func__, !p ? "p" : !total ? "total" : !prior ? "prior" : "next");
+    ibdg::switch_penalty_update(p, total, n_individuals, prior, next);
+    return 0;
+}
+
+// the prior under the context's chains and steps: the twin on the NULL table, no device work
+int ibdg_window_log2_switches_prior(ibdg_ctx *c, double p01, double p02, double p12, double expect[3], uint64_t counted[3])
+{
+    if (!c) return 1;
+    if (!c->sites.sites_valid) return fail(c, "[::] ERROR in %s: no valid site list (call ibdg_upload_sites)", __func__);
+    const ibdg_ctx::LogStates &S = c->ls;
+    char msg[256];
+    if (ibdg::log2_switches_host(__func__, nullptr, c->sites.n_win, p01, p02, p12, S.chains.data(), S.chains.size(),
+                                 S.steps.empty() ? nullptr : S.steps.data(), nullptr, expect, counted, msg, sizeof msg))
+        return fail(c, "%s", msg);
+    return 0;
+}
+
+// Switches (k_log2_switches): one launch over the posteriors' scratch, which it leaves holding beta or sw -- the posteriors kept
+// there and the records cut from them go stale --, the expectations (and the rows when asked for) out
+int ibdg_window_log2_switches(ibdg_ctx *c, double p01, double p02, double p12, double *sw, double *expect)
+{
+    if (!c) return 1;
+    LogCall L;
+    if (log_call_begin(c, __func__, !expect ? "NULL expect" : nullptr, "of the path", p01, p02, p12, L)) return 1;
+    const size_t T = L.T;
+    if (T == 0) return 0;
+    if (L.n_win == 0) {
+        memset(expect, 0, T * 3 * sizeof *expect);
+        return 0;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    ibdg_ctx::LogStates &S = c->ls;
+    S.records_drop();
+    if (ensure(c, S.post, T * L.n_win * 24) || ensure(c, S.pout, T * 40) || ensure(c, S.ptab, 4096)) return 1;
+    if (join_streams(c)) return 1;
+    S.have[S.POST] = false;
+    HIP_TRY(c, hipMemcpyAsync(S.ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
+    ibdg::launch_log2_switches((const double *)c->wlog.win_log2.p, (uint32_t)L.n_win, (uint32_t)T, L.P, L.a, (const double *)S.ptab.p, S.mask(),
+                               S.shift(), sw != nullptr, (double *)S.post.p, (double *)S.pout.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(expect, S.pout.p, T * 24, hipMemcpyDeviceToHost, c->stream));
+    if (sw) HIP_TRY(c, hipMemcpyAsync(sw, S.post.p, T * L.n_win * 24, hipMemcpyDeviceToHost, c->stream));
+    return quiesce(c);
+}
+
 int ibdg_log2_segments_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, int with_post,
                             const uint64_t *pos_first, const uint64_t *pos_last, ibdg_segment *seg, size_t seg_cap, uint64_t *n_seg,
                             uint64_t summary[12])

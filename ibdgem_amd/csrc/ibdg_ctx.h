@@ -386,6 +386,8 @@ struct ibdg_ctx {
     // (penalties, K, seed, the streams, host and device), for ibdg_get_log2_sample_path to draw one path again -- dropped with
     // the products.  `spath` (the drawn paths of the pairs in flight), `srec` (their records) and `ssum` (their summaries
     // [pairs][13]) are scratch of one chunk of pairs.
+    // The switches keep nothing: ibdg_window_log2_switches runs k_log2_switches over `post` and `pout` as its own
+    // scratch and output, and marks the posteriors there stale (have[POST] = false, records_drop) before it launches.
     // The rest is scratch of one call: `ptab` (the two tables, uploaded with every posteriors launch), `spos` (the windows'
     // positions [2][n_win]), `sout` (summaries and counts [T][13]), `soff` (record offsets [T]), `recs` (the records).
     struct LogStates {

@@ -399,6 +399,13 @@ void launch_log2_sample_paths(const double *alpha, uint32_t n_win, uint64_t p0, 
                               const uint64_t *stream, uint8_t *path, uint64_t *rec, hipStream_t st);
 void launch_log2_sample_records(const uint64_t *sout, uint32_t n_pairs, uint64_t *rec, hipStream_t st);
 
+// Switches (k_log2_switches in ibdg_states.hip; ibdg_window_log2_switches; the definition is in ibdg_states.h): the launch and
+// arguments of launch_log2_posteriors.  scr [T][n_win][3]: scratch (beta), then with rows the switch probabilities sw_w; out
+// [T][3] = the expected counted switches.  One launch on `st`, no atomics.
+void launch_log2_switches(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], const double a[3],
+                          const double *tables, const uint32_t *starts, const int32_t *shift, bool rows, double *scr, double *out,
+                          hipStream_t st);
+
 // log2 of the window likelihoods (ibdg_ld_log.hip, option "log_windows"): win_log2[T][n_win][3].
 // k_ld_log: columns 0 and 1 of an --LD run from the layout's tiles, segments, window constants and power tables (what
 // the counting kernels read), the background multiplicities without any comparison individual's exclusion and their sum.

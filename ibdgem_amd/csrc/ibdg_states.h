@@ -1,4 +1,5 @@
-// ibdg_states.h -- the integer log-domain IBD-state path, its posteriors (4.9) and segments (4.10), chains (4.11) and step shifts (4.12): the definition,
+// ibdg_states.h -- the integer log-domain IBD-state path, its posteriors (4.9) and segments (4.10), chains (4.11), step shifts (4.12),
+// sampled paths (4.13) and switches (4.14): the definition,
 // and every step of it as one inline function that the kernels' threads (ibdg_states.hip) and the host twin's loops
 // (ibdg_states_host.cpp) both call.  No HIP type in here: the host twin needs no device.
 //
@@ -325,9 +326,16 @@ struct PostIn {
     int64_t P[3];
 };
 
-// b_w[0..2] of window w
+// b_w[0..2] of window w.  On the host a NULL table stands for "every window says nothing": e = (0, 0, 0), b = (1, 1, 1), the
+// weights post_weight gives a 0 (the switches' prior, 4.14).  The kernels' tables are never NULL and their code does not ask.
 IBDG_HD void post_emission_weights(const PostIn &in, uint32_t w, double b[3])
 {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (!in.tab) {
+        b[0] = b[1] = b[2] = 1.0;
+        return;
+    }
+#endif
     int64_t e[3];
     states_emission(in.tab + 3 * (size_t)w, e);
 #pragma unroll
@@ -724,5 +732,119 @@ IBDG_HD void post_block_alpha(const PostIn &in, uint32_t w0, uint32_t w1, const 
 int log2_samples_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
                       size_t n_starts, const int32_t *shift, size_t n_samples, uint64_t seed, uint64_t stream, const uint64_t *pos_first,
                       const uint64_t *pos_last, uint8_t *paths, uint64_t *out, char *err, size_t err_len);
+
+// ---- switches: the pairwise companion of the posteriors, and the expected number of switches ------------------
+//
+// For every step w - 1 -> w the joint probability of (state before, state after) given all windows, under the weights of 4.9:
+// xi_w[q][s] = alpha_{w-1}[q] M_w[q][s] beta_w[s] / Z.  Inputs, blocking and steps 1, 2 and 3 are the posteriors' own
+// (post_block_matrix, the two walks, the backward half of post_block_gamma); post_block_switches below does step 3 as it
+// stands and then a forward pass like step 4.  At every window w >= 1 of the block, before v is advanced into w -- v is alpha
+// at w - 1: F_b at a block's first window, b_0 at window 1 --, with M = M_w of post_window_matrix and beta_w what step 3 kept:
+//   x[q][s] = (v[q] * M[3 q + s]) * beta_w[s]             nine values; the exponents of v and beta are common factors of the
+//                                                         nine and are not carried
+//   r_q     = (x[q][0] + x[q][1]) + x[q][2],  X = (r_0 + r_1) + r_2
+//   y_01    = x[0][1] + x[1][0],  y_02 = x[0][2] + x[2][0],  y_12 = x[1][2] + x[2][1]
+//   sw_w[k] = y_k / X, or 0 if X == 0 (the dead-chain rule of 4.9: v, M and beta are finite and non-negative, so X is never
+//             NaN and no sw is)                           k = 0, 1, 2 for the pairs 01, 02, 12
+//   sw_0    = (0, 0, 0)
+// fp64, no contraction, in this order.  sw_w[k] = P(path_{w-1}, path_w are the two states of pair k | everything); their sum
+// is P(path_{w-1} != path_w | everything).
+// The counted rule.  A step is counted for pair k iff w >= 1, w does not start a chain, and there are no shifts or P_k +
+// shift[w] <= 0 (switch_counted): the steps whose weight is p_k up to the shift.  A chain start's weight is 1 and a step
+// capped at 1 does not depend on p_k either; neither is part of d log Z / d log p_k = E_post[n_k].  All shifts 0 count what
+// no shifts count.
+//   n[k]       the sum of sw_w[k] over the counted steps: the block's sum in window order from 0.0 (a step that is not counted
+//              adds +0.0, which leaves a sum that is never negative as it is), the 256 partial sums joined by step 5's tree
+//   counted[k] the number of counted steps: an integer, the same for every individual (switch_counted_steps, on the host)
+// Roundings on the way to one sw_w[k] and to n[k]: tests/hp_switch_ref.py counts them the way hp_post_ref counts R.
+// The prior.  The same pass over a table that says nothing (b = 1 everywhere: a NULL table in the host twin) gives the
+// expectation of n_k under the weights alone.  switch_penalty_update moves p_k by the ratio of the two.
+
+// whether the step into window w >= 1 is counted for pair k (0, 1, 2 = 01, 02, 12)
+IBDG_HD bool switch_counted(const PostIn &in, uint32_t w, int k)
+{
+    const bool st = chain_start(in.starts, w);
+    const bool capped = in.shift && in.P[k] + in.shift[w] > 0;
+    return !st && !capped;
+}
+
+// sw[0..2] of the step from v = alpha at w - 1 through M = M_w to be = beta_w
+IBDG_HD void switch_step(const double v[3], const double M[9], const double be[3], double sw[3])
+{
+    double x[9];
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+            x[3 * q + s] = (v[q] * M[3 * q + s]) * be[s];
+    const double r0 = (x[0] + x[1]) + x[2], r1 = (x[3] + x[4]) + x[5], r2 = (x[6] + x[7]) + x[8];
+    const double X = (r0 + r1) + r2;
+    const double y0 = x[1] + x[3], y1 = x[2] + x[6], y2 = x[5] + x[7];
+    const bool dead = X == 0.0;                   // the dead-chain rule, by selects
+    sw[0] = dead ? 0.0 : y0 / X, sw[1] = dead ? 0.0 : y1 / X, sw[2] = dead ? 0.0 : y2 / X;
+}
+
+// step 3 and the switches' forward pass for the block of windows [w0, w1), w0 < w1, from G = G_b, F = F_b and its exponent (not
+// used by block 0): scr [n_win][3] holds beta_w of the block's windows from step 3 on; ROWS: the forward pass leaves sw_w there
+// (else beta stays).  acc = the block's sum of the counted sw in window order
+template <bool ROWS>
+IBDG_HD void post_block_switches(const PostIn &in, uint32_t w0, uint32_t w1, const double *G, const double *F, int Fexp,
+                                 double *__restrict__ scr, double acc[3])
+{
+    double bw[3], M[9];
+    // 3
+    double be[3] = {G[0], G[1], G[2]};
+    int ge = 0;
+    for (uint32_t w = w1; w-- > w0;) {
+        double *p = scr + 3 * (size_t)w;
+        p[0] = be[0], p[1] = be[1], p[2] = be[2];
+        if (w > w0) {
+            post_emission_weights(in, w, bw);
+            post_window_matrix(in, w, bw, M);
+            post_mat_vec(M, be);
+            post_rescale<3>(be, ge);
+        }
+    }
+    // forward
+    double v[3] = {F[0], F[1], F[2]};
+    int e = Fexp;
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (uint32_t w = w0; w < w1; ++w) {
+        double *p = scr + 3 * (size_t)w;
+        double sw[3] = {0.0, 0.0, 0.0};
+        post_emission_weights(in, w, bw);
+        if (w == 0) {
+            v[0] = bw[0], v[1] = bw[1], v[2] = bw[2];
+            e = 0;
+        } else {
+            post_window_matrix(in, w, bw, M);
+            switch_step(v, M, p, sw);
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                sum[k] += switch_counted(in, w, k) ? sw[k] : 0.0;
+            post_vec_mat(v, M);
+            post_rescale<3>(v, e);
+        }
+        if (ROWS)
+            p[0] = sw[0], p[1] = sw[1], p[2] = sw[2];
+    }
+    acc[0] = sum[0], acc[1] = sum[1], acc[2] = sum[2];
+}
+
+// counted[k]: the counted steps of pair k among n_win windows (mask, shift: checked, or NULL)
+void switch_counted_steps(size_t n_win, const int64_t P[3], const uint32_t *mask, const int32_t *shift, uint64_t counted[3]);
+
+// the host twin (ibdg_log2_switches_host): tab [n_win][3] or NULL (every window says nothing), sw [n_win][3] or NULL, expect[3] =
+// n, counted[3]; starts, shift, fn as above
+int log2_switches_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                       size_t n_starts, const int32_t *shift, double *sw, double expect[3], uint64_t counted[3], char *err,
+                       size_t err_len);
+
+// The update: next[k] = min(1, max(1e-300, p[k] * total[k] / (T * prior[k]))) where total[k] and prior[k] are finite and > 0,
+// else next[k] = p[k].  total: the posterior n summed over T individuals; prior: one individual's n on the NULL table.  Plain
+// fp64, (p * total) / ((double)T * prior).  It is the multiplicative step towards the penalties at which the posterior
+// expectation of the counted switches equals the expectation under the weights alone (DESIGN 4.14 says what is and is not known
+// about where it goes).
+void switch_penalty_update(const double p[3], const double total[3], size_t T, const double prior[3], double next[3]);
 
 }  // namespace ibdg

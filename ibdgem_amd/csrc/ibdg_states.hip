@@ -5,6 +5,7 @@
 // Only here: how a workgroup cuts the windows among its threads and joins their results (scan_lds, join_threads).
 // Paths drawn from the posterior (ibdg_window_log2_samples: k_log2_alpha, k_log2_sample_paths, k_log2_sample_records, behind the
 // segment kernels) use the same blocking, a workgroup per (individual, draw) pair.
+// The switches (ibdg_window_log2_switches: k_log2_switches, behind those) are the posteriors' kernel with another forward pass.
 //
 // k_log2_states: a workgroup of STATES_THREADS per comparison individual, grid-stride over the individuals.  Thread b owns
 // windows [b C, (b + 1) C), C = ceil(n_win / STATES_THREADS) (Blocks).
@@ -566,6 +567,70 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_sample_records(const ui
         rec[i / 12 * SAMPLE_RECORD + 3 + i % 12] = sout[i / 12 * 13 + i % 12];
 }
 
+// ---- switches (ibdg_states.h) -----------------------------------------------------------------------------------
+
+// k_log2_switches: k_log2_posteriors with post_block_switches in the place of post_block_gamma -- its launch, blocking, walks
+// (threads 0 and 64), tree and LDS (42 KB; no D or Z to keep).  scr [T][n_win][3] holds beta_w from step 3 on, and with ROWS
+// sw_w after the forward pass: the thread that wrote a row is the one that reads it.  out [T][3] = n.  A kernel of its own, so
+// that the others keep their code.  No atomics; the same reads as k_log2_posteriors.
+template <bool CH, bool SH, bool ROWS>
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_switches(const double *__restrict__ win_log2, uint32_t n_win,
+                                                                  uint32_t n_targets, PenW W, const double *__restrict__ tables,
+                                                                  const uint32_t *__restrict__ starts_arg,
+                                                                  const int32_t *__restrict__ shift_arg,
+                                                                  double *__restrict__ scr, double *__restrict__ out)
+{
+    const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
+    const int32_t *__restrict__ shift = steps_of<SH>(shift_arg);
+    __shared__ double mat[STATES_THREADS][9];       // 18 KB: B_b
+    __shared__ double fin[STATES_THREADS][3];       // F_b
+    __shared__ double gout[STATES_THREADS][3];      // G_b
+    __shared__ double part[STATES_THREADS][3];
+    __shared__ double T[512];                       // T1, T2
+    __shared__ int mexp[STATES_THREADS], fexp[STATES_THREADS];
+
+    const uint32_t b = threadIdx.x;
+    const Blocks B(n_win);
+    const uint32_t w0 = B.begin(b), w1 = B.end(b);
+    const bool own = b < B.nbk;
+
+    T[b] = tables[b], T[b + STATES_THREADS] = tables[b + STATES_THREADS];
+    __syncthreads();
+
+    for (uint32_t t = blockIdx.x; t < n_targets; t += gridDim.x) {
+        const PostIn in = {win_log2 + (size_t)t * n_win * 3, T, {W.a[0], W.a[1], W.a[2]}, starts, shift,
+                           {W.P[0], W.P[1], W.P[2]}};
+        // 1
+        if (own)
+            post_block_matrix(in, w0, w1, mat[b], &mexp[b]);
+        __syncthreads();
+        // 2
+        if (b == 0)
+            post_forward_walk(mat[0], mexp, B.nbk, fin[0], fexp);
+        else if (b == 64)
+            post_backward_walk(mat[0], B.nbk, gout[0]);
+        __syncthreads();
+        // 3, forward
+        double acc[3] = {0.0, 0.0, 0.0};
+        if (own)
+            post_block_switches<ROWS>(in, w0, w1, gout[b], fin[b], fexp[b], scr + (size_t)t * n_win * 3, acc);
+        // 5
+        part[b][0] = acc[0], part[b][1] = acc[1], part[b][2] = acc[2];
+        __syncthreads();
+        for (uint32_t d = STATES_THREADS / 2; d > 0; d >>= 1) {
+            if (b < d) {
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    part[b][s] = part[b][s] + part[b + d][s];
+            }
+            __syncthreads();
+        }
+        if (b < 3)
+            out[(size_t)t * 3 + b] = part[0][b];
+        __syncthreads();       // (LDS is reused by the next individual)
+    }
+}
+
 // the one launch of all four: nothing for no windows or no individuals, else a workgroup per individual under STATES_MAX_BLOCKS
 template <typename K, typename... A>
 void launch_kernel(K kernel, uint32_t n_win, uint32_t n_targets, hipStream_t st, A... args)
@@ -627,6 +692,27 @@ void launch_log2_sample_paths(const double *alpha, uint32_t n_win, uint64_t p0, 
 {
     launch_per_individual_steps(k_log2_sample_paths, starts, shift, n_win, n_pairs, st, alpha, n_win, p0, n_pairs, K,
                                 PenW{{a[0], a[1], a[2]}, {P[0], P[1], P[2]}}, tables, starts, shift, seed, stream, path, rec);
+}
+
+template <bool ROWS>
+static void launch_switches(const double *win_log2, uint32_t n_win, uint32_t n_targets, const PenW &W, const double *tables,
+                            const uint32_t *starts, const int32_t *shift, double *scr, double *out, hipStream_t st)
+{
+    if (shift)
+        starts ? launch_kernel(k_log2_switches<true, true, ROWS>, n_win, n_targets, st, win_log2, n_win, n_targets, W, tables, starts, shift, scr, out)
+               : launch_kernel(k_log2_switches<false, true, ROWS>, n_win, n_targets, st, win_log2, n_win, n_targets, W, tables, starts, shift, scr, out);
+    else
+        starts ? launch_kernel(k_log2_switches<true, false, ROWS>, n_win, n_targets, st, win_log2, n_win, n_targets, W, tables, starts, shift, scr, out)
+               : launch_kernel(k_log2_switches<false, false, ROWS>, n_win, n_targets, st, win_log2, n_win, n_targets, W, tables, starts, shift, scr, out);
+}
+
+void launch_log2_switches(const double *win_log2, uint32_t n_win, uint32_t n_targets, const int64_t P[3], const double a[3],
+                          const double *tables, const uint32_t *starts, const int32_t *shift, bool rows, double *scr, double *out,
+                          hipStream_t st)
+{
+    const PenW W{{a[0], a[1], a[2]}, {P[0], P[1], P[2]}};
+    rows ? launch_switches<true>(win_log2, n_win, n_targets, W, tables, starts, shift, scr, out, st)
+         : launch_switches<false>(win_log2, n_win, n_targets, W, tables, starts, shift, scr, out, st);
 }
 
 void launch_log2_sample_records(const uint64_t *sout, uint32_t n_pairs, uint64_t *rec, hipStream_t st)

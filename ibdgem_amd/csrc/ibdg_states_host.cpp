@@ -1,4 +1,4 @@
-// ibdg_states_host.cpp -- the host twin of the log-domain IBD-state path, posteriors and segments: the serial caller of the steps
+// ibdg_states_host.cpp -- the host twin of the log-domain IBD-state path, posteriors, segments, sampled paths and switches: the serial caller of the steps
 // that ibdg_states.h defines (the kernels of ibdg_states.hip are the parallel one), one window after the other.  Host only;
 // built with -ffp-contract=off like the rest.
 #include "ibdg_states.h"
@@ -203,6 +203,78 @@ int log2_posteriors_host(const char *fn, const double *tab, size_t n_win, double
         return 1;
     posteriors_core(tab, n_win, P, mask, shift, post, expect, z_mant, z_exp);
     return 0;
+}
+
+void switch_counted_steps(size_t n_win, const int64_t P[3], const uint32_t *mask, const int32_t *shift, uint64_t counted[3])
+{
+    const PostIn in = {nullptr, nullptr, {}, mask, shift, {P[0], P[1], P[2]}};
+    counted[0] = counted[1] = counted[2] = 0;
+    for (size_t w = 1; w < n_win; ++w)
+        for (int k = 0; k < 3; ++k)
+            counted[k] += switch_counted(in, (uint32_t)w, k);
+}
+
+// The switches' pass: steps 1 and 2 as posteriors_core, then post_block_switches in a loop over b and step 5's
+// tree.  tab may be NULL (post_emission_weights); sw [n_win][3] or NULL.
+static void switches_core(const double *tab, size_t n_win, const int64_t P[3], const uint32_t *mask, const int32_t *shift, double *sw,
+                          double expect[3])
+{
+    expect[0] = expect[1] = expect[2] = 0.0;
+    if (n_win == 0)
+        return;
+    PostIn in = {tab, post_tables(), {}, mask, shift, {P[0], P[1], P[2]}};
+    post_penalty_weights(P, in.a);
+    std::vector<double> own;
+    if (!sw) {
+        own.resize(n_win * 3);
+        sw = own.data();
+    }
+    const Blocks B((uint32_t)n_win);
+    std::vector<double> mat(B.nbk * 9), fin(B.nbk * 3), gout(B.nbk * 3);
+    std::vector<int> mexp(B.nbk), fexp(B.nbk);
+    for (uint32_t b = 0; b < B.nbk; ++b)
+        post_block_matrix(in, B.begin(b), B.end(b), &mat[9 * b], &mexp[b]);
+    post_forward_walk(mat.data(), mexp.data(), B.nbk, fin.data(), fexp.data());
+    post_backward_walk(mat.data(), B.nbk, gout.data());
+    double part[STATES_BLOCKS][3] = {};
+    for (uint32_t b = 0; b < B.nbk; ++b)
+        post_block_switches<true>(in, B.begin(b), B.end(b), &gout[3 * b], &fin[3 * b], fexp[b], sw, part[b]);
+    for (int d = STATES_BLOCKS / 2; d > 0; d >>= 1)
+        for (int b = 0; b < d; ++b)
+            for (int s = 0; s < 3; ++s)
+                part[b][s] = part[b][s] + part[b + d][s];
+    expect[0] = part[0][0], expect[1] = part[0][1], expect[2] = part[0][2];
+}
+
+int log2_switches_host(const char *fn, const double *tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                       size_t n_starts, const int32_t *shift, double *sw, double expect[3], uint64_t counted[3], char *err,
+                       size_t err_len)
+{
+    int64_t P[3];
+    std::vector<uint32_t> own;
+    const uint32_t *mask;
+    static const double none[3] = {0.0, 0.0, 0.0};       // (a NULL table is an input here: check_log_args sees a table)
+    if (check_log_args(fn, !expect ? "expect" : !counted ? "counted" : nullptr, tab ? tab : none, n_win, p01, p02, p12, "of the path", P,
+                       err, err_len) ||
+        own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len) || shift_check(fn, shift, n_win, err, err_len))
+        return 1;
+    switches_core(tab, n_win, P, mask, shift, sw, expect);
+    switch_counted_steps(n_win, P, mask, shift, counted);
+    return 0;
+}
+
+void switch_penalty_update(const double p[3], const double total[3], size_t T, const double prior[3], double next[3])
+{
+    for (int k = 0; k < 3; ++k) {
+        const bool ok = std::isfinite(total[k]) && std::isfinite(prior[k]) && total[k] > 0.0 && prior[k] > 0.0;
+        double x = p[k];
+        if (ok) {
+            x = p[k] * total[k] / ((double)T * prior[k]);
+            x = x < 1e-300 ? 1e-300 : x;
+            x = x > 1.0 ? 1.0 : x;
+        }
+        next[k] = x;
+    }
 }
 
 // The segment walk: one pass over the path in window order with the kernels' accumulator and summary functions (ibdg_states.h:

@@ -78,6 +78,10 @@ SYMBOLS = {
                                          C.c_uint64, C.c_uint64, _P, _P, _P, _P]),
     "ibdg_window_log2_samples": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_size_t, C.c_uint64, _P, _P, _P, _P]),
     "ibdg_get_log2_sample_path": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
+    "ibdg_log2_switches_host": (C.c_int, [_P, C.c_size_t, C.c_double, C.c_double, C.c_double, _P, C.c_size_t, _P, _P, _P, _P]),
+    "ibdg_window_log2_switches": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P]),
+    "ibdg_window_log2_switches_prior": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P]),
+    "ibdg_switch_penalty_update": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
     "ibdg_run_ms": (C.c_int, [_P, C.c_uint, _P]),
@@ -318,6 +322,65 @@ def log2_samples_host(log2_tab, p01, p02, p12, n_samples, seed, stream, pos_firs
     if rc != 0:
         raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
     return paths, out
+
+
+def log2_switches_host(log2_tab, p01, p02, p12, want_sw=True, starts=None, shift=None, n_win=None):
+    """The switch probabilities of one window table [n_win][3] on the host (ibdg_log2_switches_host): (sw float64 [n_win][3] or
+    None -- per step the probability of a 0<->1, 0<->2, 1<->2 switch --, expect float64 [3] -- their sums over the counted steps --,
+    counted uint64 [3]).  log2_tab None with n_win: the table that says nothing, whose expect is the prior of
+    switch_penalty_update.  starts, shift: as for log2_states_host."""
+    lib = load_library()
+    if log2_tab is None:
+        tab, n = None, int(n_win)
+    else:
+        tab = np.ascontiguousarray(log2_tab, dtype=np.float64).reshape(-1, 3)
+        n = tab.shape[0]
+    sw = np.zeros((n, 3), dtype=np.float64) if want_sw else None
+    expect = np.zeros(3, dtype=np.float64)
+    counted = np.zeros(3, dtype=np.uint64)
+    keep, ptr, ns = _starts(() if starts is None else starts)
+    sh = None if shift is None else _shift(shift, n)
+    rc = lib.ibdg_log2_switches_host(None if tab is None else tab.ctypes.data, n, p01, p02, p12, ptr, ns,
+                                     None if sh is None else sh.ctypes.data, None if sw is None else sw.ctypes.data,
+                                     expect.ctypes.data, counted.ctypes.data)
+    if rc != 0:
+        raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
+    return sw, expect, counted
+
+
+def switch_penalty_update(p, total, n_individuals, prior):
+    """One step of the switch penalties (ibdg_switch_penalty_update): next[k] = min(1, max(1e-300, p[k] * total[k] /
+    (n_individuals * prior[k]))), or p[k] where total[k] or prior[k] is not finite and > 0.  float64 [3]."""
+    lib = load_library()
+    p, total, prior = (np.ascontiguousarray(x, dtype=np.float64).reshape(3) for x in (p, total, prior))
+    nxt = np.zeros(3, dtype=np.float64)
+    if lib.ibdg_switch_penalty_update(p.ctypes.data, total.ctypes.data, int(n_individuals), prior.ctypes.data, nxt.ctypes.data) != 0:
+        raise EngineError(lib.ibdg_last_error(None).decode())
+    return nxt
+
+
+def _total_in_order(expect):
+    """The individuals' expectations [T][3] added in their order from 0.0, as the host program adds them."""
+    total = np.zeros(3, dtype=np.float64)
+    for row in np.asarray(expect, dtype=np.float64).reshape(-1, 3):
+        total = total + row
+    return total
+
+
+def fit_switch_penalties_host(tables, p, iterations, starts=None, shift=None):
+    """The update repeated over given window tables (a list of [n_win][3], one per individual, of one site list) on the host:
+    per iteration log2_switches_host on every table, the prior from the table that says nothing, switch_penalty_update.  Returns
+    float64 [iterations][3], the penalties after each iteration.  Whether the sequence converges is an observation, not a
+    theorem."""
+    tabs = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 3) for t in tables]
+    p = np.array(p, dtype=np.float64).reshape(3)
+    out = np.zeros((int(iterations), 3), dtype=np.float64)
+    for it in range(int(iterations)):
+        expect = [log2_switches_host(t, *p, want_sw=False, starts=starts, shift=shift)[1] for t in tabs]
+        prior = log2_switches_host(None, *p, want_sw=False, starts=starts, shift=shift, n_win=tabs[0].shape[0] if tabs else 0)[1]
+        p = switch_penalty_update(p, _total_in_order(expect), len(tabs), prior)
+        out[it] = p
+    return out
 
 
 class Engine:
@@ -572,6 +635,38 @@ class Engine:
         self._chk(self.lib.ibdg_window_log2_samples(self.ctx, p01, p02, p12, K, seed, st.ctypes.data,
                                                     None if pf is None else pf.ctypes.data,
                                                     None if pl is None else pl.ctypes.data, out.ctypes.data))
+        return out
+
+    def window_log2_switches(self, p01, p02, p12, want_sw=True):
+        """The switch probabilities of every comparison individual of the last run, on the device (ibdg_window_log2_switches):
+        (sw float64 [T][n_win][3] or None, expect float64 [T][3]), the bytes of log2_switches_host under the context's chains and
+        steps.  The posteriors kept from an earlier call go stale."""
+        T, n = self.lib.ibdg_num_targets(self.ctx), self.n_windows
+        sw = np.zeros((T, n, 3), dtype=np.float64) if want_sw else None
+        expect = np.zeros((T, 3), dtype=np.float64)
+        self._chk(self.lib.ibdg_window_log2_switches(self.ctx, p01, p02, p12, None if sw is None else sw.ctypes.data,
+                                                     expect.ctypes.data))
+        return sw, expect
+
+    def window_log2_switches_prior(self, p01, p02, p12):
+        """The prior of switch_penalty_update under the context's chains and steps (ibdg_window_log2_switches_prior, on the
+        host): (expect float64 [3], counted uint64 [3])."""
+        expect = np.zeros(3, dtype=np.float64)
+        counted = np.zeros(3, dtype=np.uint64)
+        self._chk(self.lib.ibdg_window_log2_switches_prior(self.ctx, p01, p02, p12, expect.ctypes.data, counted.ctypes.data))
+        return expect, counted
+
+    def fit_switch_penalties(self, p, iterations):
+        """The update repeated over the resident table of the last run: per iteration window_log2_switches without the rows,
+        the prior, switch_penalty_update.  Returns float64 [iterations][3], the bytes of fit_switch_penalties_host over the same
+        tables, chains and steps."""
+        p = np.array(p, dtype=np.float64).reshape(3)
+        out = np.zeros((int(iterations), 3), dtype=np.float64)
+        for it in range(int(iterations)):
+            expect = self.window_log2_switches(*p, want_sw=False)[1]
+            prior = self.window_log2_switches_prior(*p)[0]
+            p = switch_penalty_update(p, _total_in_order(expect), len(expect), prior)
+            out[it] = p
         return out
 
     def get_log2_sample_path(self, t, k):

@@ -65,6 +65,7 @@ static const char *cache_fn = NULL, *dump_panel_fn = NULL;
 static int opt_stats_only = 0, has_arm = 0;
 static int opt_log_summary = 0;          /* --log-summary: the summary's likelihoods as log2, from the engine's option "log_windows" */
 static int opt_posteriors = 0;           /* --posteriors: with --log-stats --states, the forward-backward probabilities of the states beside the path */
+static int opt_switches = 0;             /* --switches: with --log-stats --states, the probability of a switch at every step, the expected switches and the penalties they suggest */
 static int opt_segments = 0;             /* --segments: with --log-stats --states, the path's segments with their scores and support */
 static int has_chain_gap = 0;            /* --chain-gap BP: with --log-stats --states, a window more than BP behind the end of the one before starts a chain */
 static unsigned long opt_chain_gap = 0;
@@ -93,6 +94,7 @@ static struct option longopts[] = {
     {"log-stats", no_argument, &opt_log_stats, 1},
     {"posteriors", no_argument, &opt_posteriors, 1},
     {"segments", no_argument, &opt_segments, 1},
+    {"switches", no_argument, &opt_switches, 1},
     {"chain-gap", required_argument, 0, 1011},
     {"switch-scale", required_argument, 0, 1012},
     {"genetic-map", required_argument, 0, 1013},
@@ -236,6 +238,15 @@ static void usage(int code)
           "                            segment, then the same of the draws' sums over the individuals.  A draw depends on\n"
           "                            --seed, the individual's place in the panel and its number, not on devices or batches.\n"
           "                            With --stats-only only the second file, on one device drawn there\n"
+          "  --switches                with --log-stats --states: also, for every step from one window to the next, the\n"
+          "                            probability given all windows that the state switches there, under the weights that\n"
+          "                            --posteriors sums: <out>/<pileup-name>.<individual>.logswitches.txt, per window the\n"
+          "                            probabilities of a 0<->1, 0<->2 and 1<->2 switch into it and their sum; and\n"
+          "                            <out>/<pileup-name>.logibdswitches.txt, per individual the expected number of switches\n"
+          "                            that pay each penalty, their totals, the same expectation under the penalties alone\n"
+          "                            (# Prior), the steps counted, the penalties used and the penalties one multiplicative\n"
+          "                            step p * total / (individuals * prior) suggests (# Next): running again with these\n"
+          "                            repeats the step.  With --stats-only only the second file, on one device made there\n"
           "  --seed N                  with --sample-paths: the seed of the draws, 0 .. 2^64 - 1 (default 1)\n"
           "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
           "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
@@ -1955,6 +1966,8 @@ typedef struct {
     double po[4];
     uint64_t sg[12];
     char *smp_row;
+    double sw[6];                            /* --switches: its expected switches, then the prior's of its site list */
+    uint64_t swc[3];                         /* ... and the list's counted steps */
 } ind_stats;
 
 /* The host's conversation with ONE context about a pileup's comparison individuals, owned by the context's worker.  It has
@@ -2013,6 +2026,11 @@ typedef struct {
     uint64_t *smp_vals;                      /* --sample-paths: the draws' records [T][K][15] */
     uint64_t *smp_stream;                    /* ... and the individuals' streams [T]: their indices in the panel */
     uint64_t (*smp_tot)[9];                  /* ... and the run's totals [K][9], which every individual's draws are added to (the run's) */
+    double *swi_vals;                        /* --switches: the expected switches [T][3] */
+    double swi_prior[3];                     /* ... the prior of the list at hand (made with the list's first batch) */
+    uint64_t swi_counted[3];                 /* ... and its counted steps */
+    int swi_have;
+    size_t swi_cap;
     size_t arm_cap, st_cap, po_cap, sg_cap, sg_pos_cap, ch_cap, sw_cap, smp_cap, smp_stream_cap;
 } dev_conv;
 
@@ -2062,7 +2080,7 @@ static void conv_release(dev_conv *c)
     if (c->batch_ll)
         ibdg_host_free(c->batch_ll);
     free(c->batch_log); free(c->arm_sums); free(c->st_counts); free(c->po_vals); free(c->sg_vals); free(c->sg_pos); free(c->ch_starts); free(c->sw_shift);
-    free(c->smp_vals); free(c->smp_stream);
+    free(c->smp_vals); free(c->smp_stream); free(c->swi_vals);
     memset(c, 0, sizeof *c);
 }
 
@@ -2159,6 +2177,20 @@ static int samples_on_device(dev_conv *c)
     return ibdg_window_log2_samples(c->eng, opt_p01, opt_p02, opt_p12, K, opt_seed, c->smp_stream, c->sg_pos, c->sg_pos + n_win, c->smp_vals);
 }
 
+/* --switches where the tables stay on the device: the expectations alone come back; the prior is the twin's on the table that
+ * says nothing under the context's chains and steps, once per site list.  (The last of the run's calls: it runs over the
+ * posteriors' scratch.) */
+static int switches_on_device(dev_conv *c)
+{
+    const size_t T = c->n_targets;
+    if (!grow(&c->swi_vals, &c->swi_cap, T * 3, sizeof(double)))
+        return conv_oom(c, 0);
+    if (!c->swi_have && ibdg_window_log2_switches_prior(c->eng, opt_p01, opt_p02, opt_p12, c->swi_prior, c->swi_counted))
+        return 1;
+    c->swi_have = 1;
+    return ibdg_window_log2_switches(c->eng, opt_p01, opt_p02, opt_p12, NULL, c->swi_vals);
+}
+
 /* the engine's last run must be the run of this very batch: its size says so (a diagnostic when it does not) */
 static int same_run_size(dev_conv *c)
 {
@@ -2192,7 +2224,7 @@ static int device_stats(dev_conv *c)
         return 1;
     if (opt_posteriors && ibdg_window_log2_posteriors(c->eng, opt_p01, opt_p02, opt_p12, NULL, c->po_vals, c->po_vals + T * 3))
         return 1;
-    return (opt_segments && segments_on_device(c)) || (has_sample_paths && samples_on_device(c));
+    return (opt_segments && segments_on_device(c)) || (has_sample_paths && samples_on_device(c)) || (opt_switches && switches_on_device(c));
 }
 
 /* ... and an individual's share in them (1: out of memory for its row of the samples file) */
@@ -2211,6 +2243,11 @@ static int device_stats_of(dev_conv *c, size_t t, ind_stats *out)
         memcpy(out->sg, c->sg_vals + t * 12, sizeof out->sg);
     if (has_sample_paths && !(out->smp_row = sample_individual_row(c->smp_vals + t * opt_sample_paths * 15, opt_sample_paths, c->smp_tot)))
         return conv_oom(c, 0);
+    if (opt_switches) {
+        memcpy(out->sw, c->swi_vals + t * 3, 3 * sizeof(double));
+        memcpy(out->sw + 3, c->swi_prior, sizeof c->swi_prior);
+        memcpy(out->swc, c->swi_counted, sizeof c->swi_counted);
+    }
     return 0;
 }
 
@@ -2219,6 +2256,7 @@ static int conv_list(dev_conv *c)
 {
     c->wl_kept = 0;
     c->batch_of = NULL;
+    c->swi_have = 0;
     if (!c->list_on_device && ibdg_upload_sites(c->eng, c->row + c->a, c->nr + c->a, c->na + c->a, c->fo ? c->fo + c->a : NULL,
                                                 c->b - c->a, (unsigned)opt_window))
         return 1;
@@ -2679,7 +2717,7 @@ static void *dev_start(void *arg)
  * truncation by the loop (outputs_open: giving back the pages of an earlier run's 330 MB table takes tens of milliseconds,
  * which belong to the output job, not between two engine calls), emptied by the job that writes it (outs_empty) or, when the
  * run fails before that, by outs_settle_one, and closed by its writer (out_close) or the job's tail (outs_close). */
-enum { F_TAB, F_SUM, F_LSUM, F_HG, F_LP, F_LS, F_LSMP, N_IND_FILES };
+enum { F_TAB, F_SUM, F_LSUM, F_HG, F_LP, F_LS, F_LSMP, F_LSW, N_IND_FILES };
 static const struct {
     const char *kind;
     const int *on;          /* the option that turns it on (NULL: always) */
@@ -2693,6 +2731,7 @@ static const struct {
     [F_LP] = {"logposteriors", &opt_posteriors},
     [F_LS] = {"logsegments", &opt_segments},
     [F_LSMP] = {"logsamples", &has_sample_paths},
+    [F_LSW] = {"logswitches", &opt_switches},
 };
 static int ind_file_on(int k) { return !IND_FILES[k].on || *IND_FILES[k].on; }
 static int ind_file_null(int k) { return IND_FILES[k].to_null && *IND_FILES[k].to_null; }
@@ -2734,10 +2773,20 @@ typedef struct {
     /* --states */
     ind_stats *res;                             /* the individual's lines of the run's statistics files: the twin's results go here */
     uint64_t (*smp_tot)[9];                     /* --sample-paths: the run's totals [K][9], which the individual's draws are added to */
+    struct sw_prior *swp;                       /* --switches: the prior of the site list all individuals share, or NULL (each its own) */
     hg_path hgp;                                /* the slot's path arrays and text buffer (kept between individuals) */
     char *hg_buf;
     size_t hg_cap;
 } out_job;
+
+/* --switches: the prior and the counted steps of a site list that every individual of the run shares, made by the first output
+ * job that needs them */
+struct sw_prior {
+    int have;
+    double prior[3];
+    uint64_t counted[3];
+};
+static pthread_mutex_t g_sw_prior_lock = PTHREAD_MUTEX_INITIALIZER;
 
 enum { OUT_SLOTS = 12, MAX_WORKERS = 64 };
 static out_job g_outs[MAX_WORKERS][OUT_SLOTS];  /* per worker (one per context with --pileup-list, else one) */
@@ -3009,6 +3058,51 @@ static int samples_individual(out_job *o, const log_chains *lc)
     return out_close(&o->file[F_LSMP]) || bad;
 }
 
+/* --switches: the pairwise pass over the same table (ibdg_log2_switches_host: the same bytes as the device's
+ * ibdg_window_log2_switches), and the prior of the individual's site list from the same twin on the table that says nothing:
+ * once per run where the individuals share the list (o->swp), else once per individual */
+static int switches_individual(out_job *o, const log_chains *lc)
+{
+    if (!opt_switches)
+        return 0;
+    const size_t n = o->wt.w.n_win;
+    FILE *const out = o->file[F_LSW];
+    double *sw = out ? malloc((n ? n : 1) * 3 * sizeof *sw) : NULL;
+    uint64_t counted[3];
+    int bad = out && !sw;
+    if (!bad && ibdg_log2_switches_host(o->wt.log, n, opt_p01, opt_p02, opt_p12, lc->starts, lc->n_starts, lc->shift, sw, o->res->sw, counted)) {
+        fprintf(o->err, "%s\n", ibdg_last_error(NULL));
+        bad = 1;
+    }
+    if (!bad) {
+        struct sw_prior own = {0}, *p = o->swp ? o->swp : &own;
+        if (o->swp)
+            pthread_mutex_lock(&g_sw_prior_lock);
+        if (!p->have) {
+            if (ibdg_log2_switches_host(NULL, n, opt_p01, opt_p02, opt_p12, lc->starts, lc->n_starts, lc->shift, NULL, p->prior, p->counted)) {
+                fprintf(o->err, "%s\n", ibdg_last_error(NULL));
+                bad = 1;
+            } else {
+                p->have = 1;
+            }
+        }
+        memcpy(o->res->sw + 3, p->prior, sizeof p->prior);
+        memcpy(o->res->swc, p->counted, sizeof p->counted);
+        if (o->swp)
+            pthread_mutex_unlock(&g_sw_prior_lock);
+    }
+    if (!bad && out) {
+        bad = fputs("Segment\tSw_01\tSw_02\tSw_12\tP_Switch\n", out) < 0;
+        for (size_t w = 0; w < n && !bad; ++w) {
+            const double *g = sw + 3 * w;
+            bad = fprintf(out, "%d\t%.6f\t%.6f\t%.6f\t%.6f\n", (int)(w + 1), g[0], g[1], g[2], (g[0] + g[1]) + g[2]) < 0;
+        }
+    }
+    bad = out_close(&o->file[F_LSW]) || bad;
+    free(sw);
+    return bad;
+}
+
 static int log_states_individual(out_job *o)
 {
     const size_t n = o->wt.w.n_win;
@@ -3048,6 +3142,7 @@ static int log_states_individual(out_job *o)
         bad = posteriors_individual(o, &lc) || bad;
         bad = segments_individual(o, &lc) || bad;
         bad = samples_individual(o, &lc) || bad;
+        bad = switches_individual(o, &lc) || bad;
     }
     free(lc.pos);
     free(lc.starts);
@@ -3462,7 +3557,7 @@ typedef struct {
     uint32_t *row_pre_off;
 } site_list;
 
-enum { N_RUN_FILES = 4 };           /* RUN_FILES below */
+enum { N_RUN_FILES = 5 };           /* RUN_FILES below */
 
 typedef struct {
     /* ---- the pileup's run ---- */
@@ -3473,6 +3568,7 @@ typedef struct {
     int overlap, dev_v, batchable, arm_on, tables_stay, dev_states, out_slots, out_threads_env;
     size_t n_site_out;              /* entries of an individual's per-site array */
     ind_stats *res;                 /* per individual, what the run's statistics files are written from (run_end) */
+    struct sw_prior sw_prior;       /* --switches: the shared site list's prior, made by the first output job */
     uint64_t (*smp_tot)[9], *smp_col;   /* --sample-paths: draw k summed over the individuals so far [K][9]; scratch [K] for their columns */
     FILE *run_file[N_RUN_FILES];    /* the files of RUN_FILES, open from run_begin to run_end */
     char *run_fn[N_RUN_FILES];
@@ -3636,7 +3732,43 @@ static void write_samples_file(pile_run *r, FILE *f)
     fprintf(f, "# Total\t%zu\t%zu%s", total_n, K, tail);
 }
 
-/* <out>/<pileup-name>.[log]<kind>.txt (the last three exist with --log-stats only), in the order they are opened and written.
+/* likewise: per individual the expected switches that pay each penalty, their totals added in the order of the panel, the
+ * expectation of one individual under the penalties alone, the steps counted, the penalties used and the ones the update
+ * suggests (ibdg_switch_penalty_update over the file's individuals).  The prior and the counted steps belong to the site list:
+ * with a list per individual (-v, -D) the prior shown is the individuals' sum in the order of the panel, the counted steps
+ * likewise, and the update takes that sum as the prior of one. */
+static void write_switches_file(pile_run *r, FILE *f)
+{
+    double total[3] = {0.0, 0.0, 0.0}, prior[3] = {0.0, 0.0, 0.0}, next[3];
+    const double p[3] = {opt_p01, opt_p02, opt_p12};
+    uint64_t counted[3] = {0, 0, 0};
+    const size_t T = g_targets.n;
+    int same = 1;
+    fprintf(f, "# ID\tN_WIN\tE_SW01\tE_SW02\tE_SW12\n");
+    for (size_t ti = 0; ti < T; ++ti) {
+        const ind_stats *s = &r->res[ti];
+        const size_t n = (size_t)(s->st[0] + s->st[1] + s->st[2]);
+        fprintf(f, "%s\t%zu\t%.6f\t%.6f\t%.6f\n", g_ids.names[g_targets.idx[ti]], n, s->sw[0], s->sw[1], s->sw[2]);
+        same = same && !memcmp(s->sw + 3, r->res[0].sw + 3, 3 * sizeof(double)) && !memcmp(s->swc, r->res[0].swc, sizeof s->swc);
+        for (int k = 0; k < 3; ++k) {
+            total[k] += s->sw[k];
+            prior[k] += s->sw[3 + k];
+            counted[k] += s->swc[k];
+        }
+    }
+    if (same && T) {
+        memcpy(prior, r->res[0].sw + 3, sizeof prior);
+        memcpy(counted, r->res[0].swc, sizeof counted);
+    }
+    ibdg_switch_penalty_update(p, total, same ? T : 1, prior, next);
+    fprintf(f, "# Total\t%.6f\t%.6f\t%.6f\n", total[0], total[1], total[2]);
+    fprintf(f, "# Prior%s\t%.6f\t%.6f\t%.6f\n", same ? "" : " (sum over the individuals' own site lists)", prior[0], prior[1], prior[2]);
+    fprintf(f, "# Counted\t%llu\t%llu\t%llu\n", (unsigned long long)counted[0], (unsigned long long)counted[1], (unsigned long long)counted[2]);
+    fprintf(f, "# Penalties\t%.6e\t%.6e\t%.6e\n", p[0], p[1], p[2]);
+    fprintf(f, "# Next\t%.6e\t%.6e\t%.6e\n", next[0], next[1], next[2]);
+}
+
+/* <out>/<pileup-name>.[log]<kind>.txt (the last four exist with --log-stats only), in the order they are opened and written.
  * armstats.txt is not among them: it is opened where it is written, in run_end. */
 static const struct {
     const int *on;
@@ -3647,6 +3779,7 @@ static const struct {
     {&opt_posteriors, "ibdposteriors", "IBD-state posteriors file", write_posteriors_file},
     {&opt_segments, "ibdsegments", "IBD-state segments file", write_segments_file},
     {&has_sample_paths, "ibdsamples", "IBD-state samples file", write_samples_file},
+    {&opt_switches, "ibdswitches", "IBD-state switches file", write_switches_file},
 };
 
 /* the run's arrays and its statistics files */
@@ -4156,6 +4289,7 @@ static int output_start(pile_run *r)
     o->sq = pj->name; o->err = r->err;
     o->res = &r->res[r->ti];
     o->smp_tot = r->smp_tot;
+    o->swp = r->one_list ? &r->sw_prior : NULL;
     if (outputs_open(r, o))
         return 1;
     const int threads = all_threads();
@@ -4484,6 +4618,8 @@ int main(int argc, char **argv)
     if (genetic_map_fn && opt_plan) { fprintf(stderr, "[::] ERROR: --genetic-map changes files --plan does not make; use one of them.\n"); exit(1); }
     if (genetic_map_fn && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --genetic-map needs --log-stats and --states: it measures the distances their switch penalties are scaled by.\n"); exit(1); }
     if (genetic_map_fn && !has_switch_scale) { fprintf(stderr, "[::] ERROR: --genetic-map needs --switch-scale X: it says in which unit X and the distances between windows are measured.\n"); exit(1); }
+    if (opt_switches && opt_plan) { fprintf(stderr, "[::] ERROR: --switches writes files --plan does not make; use one of them.\n"); exit(1); }
+    if (opt_switches && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --switches needs --log-stats and --states: it is the probability of a switch at every step under the weights whose best path they find, with their --p01, --p02, --p12.\n"); exit(1); }
     if (has_sample_paths && opt_plan) { fprintf(stderr, "[::] ERROR: --sample-paths writes files --plan does not make; use one of them.\n"); exit(1); }
     if (has_sample_paths && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --sample-paths needs --log-stats and --states: it draws paths from the distribution over all paths of the weights whose best path they find, with their --p01, --p02, --p12.\n"); exit(1); }
     if (has_seed && !has_sample_paths) { fprintf(stderr, "[::] ERROR: --seed is the seed of --sample-paths K.\n"); exit(1); }

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define IBDG_ABI_VERSION 5   /* (still 5, additions only: ibdg_log2_segments_host, ibdg_window_log2_segments, ibdg_get_log2_segments -- the path's segments with exact scores and support; ibdg_log2_posteriors_host, ibdg_window_log2_posteriors -- forward-backward IBD-state probabilities over the log2 table; option log_windows with ibdg_get_window_log2, ibdg_get_window_log2_all -- window likelihoods as logs that do not underflow; ibdg_upload_candidates, ibdg_num_candidates, ibdg_select_variable_sites, ibdg_get_site_candidates -- the -v site lists made on the device.)  5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
+#define IBDG_ABI_VERSION 5   /* (still 5, additions only: ibdg_log2_switches_host, ibdg_window_log2_switches, ibdg_window_log2_switches_prior, ibdg_switch_penalty_update -- the probability of a switch at every step, the expected switches and the penalties they suggest; ibdg_log2_segments_host, ibdg_window_log2_segments, ibdg_get_log2_segments -- the path's segments with exact scores and support; ibdg_log2_posteriors_host, ibdg_window_log2_posteriors -- forward-backward IBD-state probabilities over the log2 table; option log_windows with ibdg_get_window_log2, ibdg_get_window_log2_all -- window likelihoods as logs that do not underflow; ibdg_upload_candidates, ibdg_num_candidates, ibdg_select_variable_sites, ibdg_get_site_candidates -- the -v site lists made on the device.)  5: ibdg_num_targets, ibdg_upload_panel_fd, ibdg_window_llr_sums; a run over new comparison individuals queues without a host wait; options ibd0_after, mfma_batch_groups, mfma_wg_sum; ibdg_last_count_unit 3.  4: ibdg_ld_layout, ibdg_last_count_unit, ibdg_get_window_ll_all; options compact_tiles, compact_density, compact_targets; the strict kernel is no
                               * longer what a sparse pileup gets.  3: options site_results, stage_workers; ibdg_get_site_af
                               * computes on demand; ibdg_last_run_ms out[4] is 0 */
 
@@ -399,6 +399,37 @@ int ibdg_window_log2_samples(ibdg_ctx *ctx, double p01, double p02, double p12, 
  * paths[k].  Errors: no such call since the last ibdg_run, ibdg_set_window_chains or ibdg_set_window_steps; t or k out of range;
  * NULL path. */
 int ibdg_get_log2_sample_path(ibdg_ctx *ctx, size_t t, size_t k, uint8_t *path);
+/* Switches: the pairwise companion of ibdg_log2_posteriors_steps_host under the same weights, chains and shifts.  For
+ * every step w - 1 -> w, sw[w][k] = P(the states at w - 1 and w are the two of pair k | all windows), k = 0, 1, 2 for the pairs
+ * 01, 02, 12 (either direction); sw[0] = (0, 0, 0); their sum over k is P(a switch at that step).  sw[n_win][3] may be NULL.
+ * expect[3] = the sum of sw[w][k] over the counted steps of pair k: w >= 1, w does not start a chain, and without shifts or with
+ * P_k + shift[w] <= 0 (a step whose switch weight is capped at 1 does not depend on p_k) -- the expected number of switches that
+ * pay p_k, which is d log Z / d log p_k.  counted[3] = the number of counted steps, the same for every individual.  log2_tab ==
+ * NULL stands for a table that says nothing (every emission weight 1): expect is then the expectation under the switch weights
+ * alone, the prior of ibdg_switch_penalty_update.  The order of the fp64 operations is fixed (ibdgem_amd/csrc/ibdg_states.h) and is
+ * the device's; where the weights leave no path the three probabilities of a step are 0, never NaN (the dead-chain rule).  Needs
+ * no device.  n_win = 0 or 1: expect = 0, counted = 0.  Errors (ibdg_last_error(NULL)): a penalty outside (0, 1] or NaN, n_win >
+ * 2^21, NULL expect or counted, the chains' and the shifts' as in the _steps_host functions. */
+int ibdg_log2_switches_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, const uint32_t *starts,
+                            size_t n_starts, const int32_t *shift, double *sw, double expect[3], uint64_t counted[3]);
+/* The same for every comparison individual of the last ibdg_run, on the device, over its log2 table (or the one set by
+ * ibdg_set_window_log2) and the context's chains and steps: sw[T][n_win][3] (may be NULL: then 24 bytes per individual leave the
+ * device), expect[T][3].  The same bytes as ibdg_log2_switches_host on ibdg_get_window_log2's table.  One launch over the scratch
+ * of ibdg_window_log2_posteriors: the posteriors and segment records kept from earlier calls go stale (a later call makes them
+ * again).  Same waits as ibdg_get_window_log2; returns with the outputs in host memory.  Errors: those of
+ * ibdg_window_log2_posteriors, NULL expect. */
+int ibdg_window_log2_switches(ibdg_ctx *ctx, double p01, double p02, double p12, double *sw, double *expect);
+/* The prior that goes with it: expect[3] and counted[3] of ibdg_log2_switches_host on the NULL table with ibdg_num_windows
+ * windows and the context's chains and steps -- one individual's, the same for all.  Runs on the host, launches nothing and
+ * leaves everything kept as it is.  Errors: no valid site list, a penalty out of range, more than 2^21 windows, NULL expect or
+ * counted. */
+int ibdg_window_log2_switches_prior(ibdg_ctx *ctx, double p01, double p02, double p12, double expect[3], uint64_t counted[3]);
+/* One step of the penalties towards those at which the posterior expectation of the counted switches equals the expectation
+ * under the switch weights alone: next[k] = min(1, max(1e-300, p[k] * total[k] / (n_individuals * prior[k]))) where total[k] and
+ * prior[k] are finite and > 0, else next[k] = p[k].  total[3]: expect of the calls above summed over n_individuals individuals;
+ * prior[3]: expect of ibdg_log2_switches_host on the NULL table with the same penalties, chains and shifts.  Plain fp64.  Whether
+ * repeating the step converges is an observation on simulated input, not a theorem.  Errors: a NULL argument. */
+int ibdg_switch_penalty_update(const double p[3], const double total[3], size_t n_individuals, const double prior[3], double next[3]);
 /* Alt-allele count of panel rows [first_row, first_row+n): out[n] (for tests). */
 int ibdg_get_alt_counts(ibdg_ctx *ctx, size_t first_row, size_t n, uint32_t *out);
 
