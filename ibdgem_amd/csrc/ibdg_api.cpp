@@ -120,7 +120,7 @@ int ensure(ibdg_ctx *c, DevBuf &b, size_t bytes)
 // ---- what stops being valid when an input changes: each of these says all of it, and nobody else says any ----
 
 // A panel goes up: the alt counts, the results (with what the log-domain calls kept of them: ls, and the window chains, which
-// belong to the site list that goes), the layout, the site list
+// belong to the site list that goes, and the table store of that list), the layout, the site list
 // and the candidates (they name rows of the panel that goes), and the device copies of targets / background weights, which
 // were laid out for the previous panel.  The row
 // table goes with up_gen (its alt counts and n_ids).  sites_gen stays: no run is accepted before the next upload of sites
@@ -132,6 +132,7 @@ void panel_replaced(ibdg_ctx *c)
     c->have_results = false;
     c->ls.chains_clear();
     c->ls.steps_clear();
+    c->lstore.empty();
     c->lay.pop_sites_ok = false;
     c->prev_targets.clear();
     c->bg.prev_bg.clear();
@@ -146,7 +147,7 @@ void panel_replaced(ibdg_ctx *c)
 }
 
 // A site list goes up (from the host, the device or the candidates): the results (with ls and the window chains of the list
-// before: ibdg_set_window_chains speaks of one list's windows), the layout and its credit, the
+// before: ibdg_set_window_chains speaks of one list's windows; the table store, whose tables are over that list's windows), the layout and its credit, the
 // window bounds, the -A triples, the selection map; with sites_gen the IBD0 pass, the fragment base, the images, a pending
 // finalising step's right to ride along and stream3's order behind the prepared sites; with up_gen the row table; and
 // the count of runs towards "ibd0_after".
@@ -163,6 +164,7 @@ void sites_replaced(ibdg_ctx *c)
     c->have_results = false;
     c->ls.chains_clear();
     c->ls.steps_clear();
+    c->lstore.empty();
     c->lay.pop_sites_ok = false;
     c->lay.compact = false;
     c->lay.relayout_credit = 0;
@@ -2559,6 +2561,165 @@ int ibdg_window_log2_switches(ibdg_ctx *c, double p01, double p02, double p12, d
     HIP_TRY(c, hipMemcpyAsync(expect, S.pout.p, T * 24, hipMemcpyDeviceToHost, c->stream));
     if (sw) HIP_TRY(c, hipMemcpyAsync(sw, S.post.p, T * L.n_win * 24, hipMemcpyDeviceToHost, c->stream));
     return quiesce(c);
+}
+
+// ---- the fit of the switch penalties: one step, the twin's loop, the table store and the loop over it ----
+
+int ibdg_switch_fit_step(const double p[3], const double total[3], size_t n_individuals, const double prior[3],
+                         const uint64_t counted[3], ibdg_fit_row *row, double next[3], int *stood)
+{
+    static const char *const name[3] = {"p01", "p02", "p12"};
+    const char *null_arg = !p ? "p" : !total ? "total" : !prior ? "prior" : !counted ? "counted" : !row ? "row" : !next ? "next" :
+                           !stood ? "stood" : nullptr;
+    if (null_arg)
+        return fail(nullptr, "[::] ERROR in %s: NULL %s", __func__, null_arg);
+    const int bad = ibdg::switch_fit_step(p, total, n_individuals, prior, counted, row, next, stood);
+    if (bad)
+        return fail(nullptr, "[::] ERROR in %s: %s = %g is not in (0, 1]", __func__, name[bad - 1], p[bad - 1]);
+    return 0;
+}
+
+int ibdg_log2_fit_host(const double *const *tabs, size_t n_individuals, size_t n_win, const double p[3], const uint32_t *starts,
+                       size_t n_starts, const int32_t *shift, size_t max_iter, ibdg_fit_row *rows, size_t *n_rows, int *stood,
+                       double fitted[3])
+{
+    char msg[256];
+    if (ibdg::log2_fit_host(__func__, tabs, n_individuals, n_win, p, starts, n_starts, shift, max_iter, rows, n_rows, stood, fitted, msg,
+                            sizeof msg))
+        return fail(nullptr, "%s", msg);
+    return 0;
+}
+
+// The store (LogStore in ibdg_ctx.h has the rule).  A device buffer of `bytes` for it, kept when large enough; a failure names
+// the bytes asked for.  (ensure()'s wait for queued runs: the buffer may be read by a launch of an earlier call only, and every
+// such call ends in a host wait.)
+static int store_buffer(ibdg_ctx *c, const char *fn, DevBuf &b, size_t bytes, const char *what)
+{
+    if (bytes == 0)
+        bytes = 16;
+    if (b.cap >= bytes)
+        return 0;
+    b.release();
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return fail(c, "[::] ERROR in %s: cannot allocate %zu bytes of device memory for %s: %s", fn, bytes, what, hipGetErrorString(e));
+    }
+    b.cap = bytes;
+    ++b.allocs;
+    return 0;
+}
+
+int ibdg_log2_store_reserve(ibdg_ctx *c, size_t n_individuals)
+{
+    if (!c) return 1;
+    if (!c->sites.sites_valid) return fail(c, "[::] ERROR in %s: no valid site list (call ibdg_upload_sites)", __func__);
+    if (n_individuals > 0x7fffffffu)
+        return fail(c, "[::] ERROR in %s: %zu individuals, more than the 2^31 - 1 a store holds", __func__, n_individuals);
+    c->lstore.empty();
+    c->lstore.cap = n_individuals;
+    c->lstore.reserved = true;
+    return 0;
+}
+
+size_t ibdg_log2_store_count(ibdg_ctx *c) { return c ? c->lstore.count : 0; }
+
+int ibdg_log2_store_append(ibdg_ctx *c)
+{
+    if (!c) return 1;
+    if (!c->have_results) return fail(c, "[::] ERROR in %s: no results (call ibdg_run)", __func__);
+    if (!c->wlog.valid) return fail(c, "[::] ERROR in %s: the last run kept no window logs (option log_windows)", __func__);
+    ibdg_ctx::LogStore &R = c->lstore;
+    if (!R.reserved) return fail(c, "[::] ERROR in %s: no store (call ibdg_log2_store_reserve)", __func__);
+    const size_t T = c->n_targets, row = (size_t)c->sites.n_win * 24;
+    if (T > R.cap - R.count)
+        return fail(c, "[::] ERROR in %s: %zu individuals stored and %zu more, beyond the reserve of %zu", __func__, R.count, T, R.cap);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (store_buffer(c, __func__, R.tabs, R.cap * row, "the table store")) return 1;
+    if (join_streams(c)) return 1;
+    if (T * row)
+        HIP_TRY(c, hipMemcpyAsync((char *)R.tabs.p + R.count * row, c->wlog.win_log2.p, T * row, hipMemcpyDeviceToDevice, c->stream));
+    if (quiesce(c)) return 1;
+    R.count += T;
+    return 0;
+}
+
+// what ibdg_log2_store_switches and ibdg_log2_store_fit refuse alike, and the launch with its copy out and host wait
+static int store_begin(ibdg_ctx *c, const char *fn, const char *own, double p01, double p02, double p12, LogCall &L)
+{
+    if (log_call_begin(c, fn, own, "of the path", p01, p02, p12, L)) return 1;
+    if (!c->lstore.reserved) return fail(c, "[::] ERROR in %s: no store (call ibdg_log2_store_reserve)", fn);
+    return 0;
+}
+
+// (tables: the 4 KB of post_tables go up in front of the launch -- a fit's iterations after the first find them there: every
+// one ends in a host wait, and nothing else runs on the context inside the call)
+static int store_expect(ibdg_ctx *c, const char *fn, const LogCall &L, bool tables, double *expect)
+{
+    ibdg_ctx::LogStore &R = c->lstore;
+    ibdg_ctx::LogStates &S = c->ls;
+    const size_t n = R.count;
+    if (n == 0) return 0;
+    if (L.n_win == 0) {
+        memset(expect, 0, n * 3 * sizeof *expect);
+        return 0;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t grid = ibdg::switch_expect_grid(n, c->n_cu);
+    if (store_buffer(c, fn, R.scr, (size_t)grid * L.n_win * 24, "the workgroups' scratch") || store_buffer(c, fn, R.out, n * 24, "the expectations") ||
+        ensure(c, S.ptab, 4096))
+        return 1;
+    if (join_streams(c)) return 1;
+    if (tables)
+        HIP_TRY(c, hipMemcpyAsync(S.ptab.p, ibdg::post_tables(), 4096, hipMemcpyHostToDevice, c->stream));
+    ibdg::launch_log2_switch_expect((const double *)R.tabs.p, (uint32_t)L.n_win, (uint32_t)n, grid, L.P, L.a, (const double *)S.ptab.p, S.mask(),
+                                    S.shift(), (double *)R.scr.p, (double *)R.out.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(expect, R.out.p, n * 24, hipMemcpyDeviceToHost, c->stream));
+    return quiesce(c);
+}
+
+int ibdg_log2_store_switches(ibdg_ctx *c, double p01, double p02, double p12, double *expect)
+{
+    if (!c) return 1;
+    LogCall L;
+    if (store_begin(c, __func__, !expect ? "NULL expect" : nullptr, p01, p02, p12, L)) return 1;
+    return store_expect(c, __func__, L, true, expect);
+}
+
+int ibdg_log2_store_fit(ibdg_ctx *c, const double p[3], size_t max_iter, ibdg_fit_row *rows, size_t *n_rows, int *stood, double fitted[3])
+{
+    if (!c) return 1;
+    LogCall L;
+    const char *own = !p ? "NULL p" : !n_rows ? "NULL n_rows" : !stood ? "NULL stood" : !fitted ? "NULL fitted" :
+                      max_iter && !rows ? "NULL rows" : nullptr;
+    if (store_begin(c, __func__, own, p ? p[0] : 1.0, p ? p[1] : 1.0, p ? p[2] : 1.0, L)) return 1;
+    const ibdg_ctx::LogStates &S = c->ls;
+    const size_t T = c->lstore.count;
+    double cur[3] = {p[0], p[1], p[2]};
+    *n_rows = 0, *stood = 0;
+    fitted[0] = cur[0], fitted[1] = cur[1], fitted[2] = cur[2];
+    std::vector<double> expect(T * 3);
+    for (size_t it = 0; T && it < max_iter && !*stood; ++it) {
+        double total[3] = {0.0, 0.0, 0.0}, prior[3], next[3];
+        uint64_t counted[3];
+        char msg[256];
+        (void)ibdg::states_penalties(cur[0], cur[1], cur[2], L.P, nullptr);     // (checked: p above, then the update's range)
+        ibdg::post_penalty_weights(L.P, L.a);
+        if (store_expect(c, __func__, L, it == 0, expect.data())) return 1;
+        for (size_t t = 0; t < T; ++t)              // the round trip of 24 T bytes and this sum stay on the host: microseconds
+            for (int k = 0; k < 3; ++k)              // beside the launch, and the order of the additions is the twin's
+                total[k] = total[k] + expect[3 * t + k];
+        if (ibdg::log2_switches_host(__func__, nullptr, L.n_win, cur[0], cur[1], cur[2], S.chains.data(), S.chains.size(),
+                                     S.steps.empty() ? nullptr : S.steps.data(), nullptr, prior, counted, msg, sizeof msg))
+            return fail(c, "%s", msg);
+        (void)ibdg::switch_fit_step(cur, total, T, prior, counted, &rows[it], next, stood);
+        *n_rows = it + 1;
+        for (int k = 0; k < 3; ++k)
+            cur[k] = fitted[k] = next[k];
+    }
+    return 0;
 }
 
 int ibdg_log2_segments_host(const double *log2_tab, size_t n_win, double p01, double p02, double p12, int with_post,

@@ -354,6 +354,24 @@ struct ibdg_ctx {
         bool valid = false;              // the last run was made with the option on
     } wlog;
 
+    // The table store (ibdg_log2_store_*): win_log2 of many runs over ONE site list kept side by side,
+    // `tabs` [cap][n_win][3] with `count` of them filled, for the fit of the switch penalties over every individual of a pileup.
+    // Replaced by: a site list or a panel (sites_replaced, panel_replaced call empty(): the tables speak of the windows of the list
+    // that goes; the reserve goes with them, so nothing is appended to a store that was sized for another list).  Runs, chains and
+    // steps do not touch it: batches of individuals share a site list, and the chains and steps are read when a call is made.
+    // `tabs` is allocated by the first append behind a reserve (n_win is known then) and keeps its memory when emptied; `scr`
+    // [grid][n_win][3] and `out` [count][3] are k_log2_switch_expect's own scratch and output, so that nothing LogStates keeps
+    // goes stale.  Stream edges:
+    //   writer  ibdg_log2_store_append's device-to-device copy on the main stream behind join_streams (win_log2's writers are in
+    //           front of it: WinLog above), waited for on the host before the call returns -- the next run may replace win_log2
+    //   reader  k_log2_switch_expect on the main stream, followed by the copy of `out` and a host wait: no reader outlives its call
+    struct LogStore {
+        DevBuf tabs, scr, out;
+        size_t cap = 0, count = 0;       // individuals reserved / stored
+        bool reserved = false;
+        void empty() { cap = count = 0; reserved = false; }
+    } lstore;
+
     // The log-domain state calls over win_log2 of the last run (ibdg_window_log2_states / _posteriors / _segments,
     // ibdg_get_log2_segments; ibdg_states.hip).  Each product is a stage that is queued on the main stream behind join_streams
     // and followed, in the public call, by the copies out and a host wait: no reader of the table and no kernel of this group
@@ -494,6 +512,7 @@ struct ibdg_ctx {
         release_all({&rt.row_tab, &p2.p2w, &p2.p2c, &p2.p2_tw, &p2.p2_wt, &fb.fragb, &img.wtarget, &img.twords});
         release_all({&wtarget_mt, &twords_mt, &partial, &aimg, &wc_slot, &partial_h, &vals, &order});
         release_all({&targets, &weight, &nrefpanel, &af, &site_ll, &win_ll, &llr_seg, &llr_part, &llr_out, &wlog.win_log2});
+        release_all({&lstore.tabs, &lstore.scr, &lstore.out});
         ls.free_bufs();
     }
 };

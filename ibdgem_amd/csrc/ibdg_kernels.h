@@ -406,6 +406,21 @@ void launch_log2_switches(const double *win_log2, uint32_t n_win, uint32_t n_tar
                           const double *tables, const uint32_t *starts, const int32_t *shift, bool rows, double *scr, double *out,
                           hipStream_t st);
 
+// The switches' expectations over a table store (k_log2_switch_expect in ibdg_states.hip; ibdg_log2_store_switches):
+// tabs [n_tables][n_win][3]; out [n_tables][3]; scr [grid][n_win][3], the scratch of the launched workgroups, where grid =
+// switch_expect_grid(n_tables, n_cu).  The cap on the grid is what is resident: 3 workgroups per CU at the kernel's 41 984 bytes of
+// LDS (160 KiB per CU), under STATES_MAX_BLOCKS.  One launch on `st`, no atomics.
+constexpr uint32_t SWITCH_EXPECT_PER_CU = 3;
+inline uint32_t switch_expect_grid(size_t n_tables, int n_cu)
+{
+    const size_t resident = (size_t)SWITCH_EXPECT_PER_CU * (size_t)(n_cu > 0 ? n_cu : 1);
+    const size_t cap = resident < STATES_MAX_BLOCKS ? resident : STATES_MAX_BLOCKS;
+    return (uint32_t)(n_tables < cap ? n_tables : cap);
+}
+void launch_log2_switch_expect(const double *tabs, uint32_t n_win, uint32_t n_tables, uint32_t grid, const int64_t P[3],
+                               const double a[3], const double *tables, const uint32_t *starts, const int32_t *shift, double *scr,
+                               double *out, hipStream_t st);
+
 // log2 of the window likelihoods (ibdg_ld_log.hip, option "log_windows"): win_log2[T][n_win][3].
 // k_ld_log: columns 0 and 1 of an --LD run from the layout's tiles, segments, window constants and power tables (what
 // the counting kernels read), the background multiplicities without any comparison individual's exclusion and their sum.

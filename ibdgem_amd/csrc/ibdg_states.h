@@ -847,4 +847,23 @@ int log2_switches_host(const char *fn, const double *tab, size_t n_win, double p
 // about where it goes).
 void switch_penalty_update(const double p[3], const double total[3], size_t T, const double prior[3], double next[3]);
 
+// ---- the fit: the update repeated over the tables of all T individuals of a site list --------------------------
+//
+// An iteration with penalties p: total[k] = the individuals' n[k] under p added in their order from 0.0; prior and counted from the
+// NULL table under p; next = switch_penalty_update(p, total, T, prior).  The iteration stood iff for every pair
+// |states_penalties(next)[k] - states_penalties(p)[k]| <= 1: no penalty moved by more than one quantum, the resolution at which
+// the kernels and the twin read a penalty at all.  (Exact repetition is not the rule: once inside a quantum the integers jitter
+// by a few quanta for as long as one iterates.)  The fit from p_0 runs iterations 1, 2, ... with p_{i} = next_{i-1}, and ends
+// behind the first that stood or behind max_iter; the fitted penalties are that iteration's next.  One function makes the row,
+// the update and the verdict for every route: the device's loop, the twin's and the host program's.
+
+// row = (p, total, prior, counted), next, *stood.  0, or 1 + k where p[k] is not in (0, 1]
+int switch_fit_step(const double p[3], const double total[3], size_t T, const double prior[3], const uint64_t counted[3],
+                    ibdg_fit_row *row, double next[3], int *stood);
+
+// the host twin of the fit (ibdg_log2_fit_host): tabs[T] tables [n_win][3]; rows [max_iter]; starts, shift, fn, err as above
+int log2_fit_host(const char *fn, const double *const *tabs, size_t T, size_t n_win, const double p[3], const uint32_t *starts,
+                  size_t n_starts, const int32_t *shift, size_t max_iter, ibdg_fit_row *rows, size_t *n_rows, int *stood,
+                  double fitted[3], char *err, size_t err_len);
+
 }  // namespace ibdg

@@ -6,6 +6,8 @@
 // Paths drawn from the posterior (ibdg_window_log2_samples: k_log2_alpha, k_log2_sample_paths, k_log2_sample_records, behind the
 // segment kernels) use the same blocking, a workgroup per (individual, draw) pair.
 // The switches (ibdg_window_log2_switches: k_log2_switches, behind those) are the posteriors' kernel with another forward pass.
+// The fit's pass (ibdg_log2_store_switches: k_log2_switch_expect, behind it) is that kernel over a table store, with the beta
+// scratch of the launched workgroups in place of every individual's.
 //
 // k_log2_states: a workgroup of STATES_THREADS per comparison individual, grid-stride over the individuals.  Thread b owns
 // windows [b C, (b + 1) C), C = ceil(n_win / STATES_THREADS) (Blocks).
@@ -572,7 +574,8 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_sample_records(const ui
 // k_log2_switches: k_log2_posteriors with post_block_switches in the place of post_block_gamma -- its launch, blocking, walks
 // (threads 0 and 64), tree and LDS (42 KB; no D or Z to keep).  scr [T][n_win][3] holds beta_w from step 3 on, and with ROWS
 // sw_w after the forward pass: the thread that wrote a row is the one that reads it.  out [T][3] = n.  A kernel of its own, so
-// that the others keep their code.  No atomics; the same reads as k_log2_posteriors.
+// that the others keep their code.  No atomics; the same reads as k_log2_posteriors.  k_log2_switch_expect below is this body
+// with ROWS = false and another scratch base: a change here is a change there.
 template <bool CH, bool SH, bool ROWS>
 __global__ __launch_bounds__(STATES_THREADS) void k_log2_switches(const double *__restrict__ win_log2, uint32_t n_win,
                                                                   uint32_t n_targets, PenW W, const double *__restrict__ tables,
@@ -614,6 +617,74 @@ __global__ __launch_bounds__(STATES_THREADS) void k_log2_switches(const double *
         double acc[3] = {0.0, 0.0, 0.0};
         if (own)
             post_block_switches<ROWS>(in, w0, w1, gout[b], fin[b], fexp[b], scr + (size_t)t * n_win * 3, acc);
+        // 5
+        part[b][0] = acc[0], part[b][1] = acc[1], part[b][2] = acc[2];
+        __syncthreads();
+        for (uint32_t d = STATES_THREADS / 2; d > 0; d >>= 1) {
+            if (b < d) {
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    part[b][s] = part[b][s] + part[b + d][s];
+            }
+            __syncthreads();
+        }
+        if (b < 3)
+            out[(size_t)t * 3 + b] = part[0][b];
+        __syncthreads();       // (LDS is reused by the next individual)
+    }
+}
+
+// ---- the fit's pass over a table store (ibdg_states.h) ----------------------------------------------------------
+//
+// k_log2_switch_expect: k_log2_switches<CH, SH, false> over tabs [n_tables][n_win][3] -- the same step functions in the same
+// order, so out [n_tables][3] holds the twin's bytes -- with one difference: the beta scratch belongs to the WORKGROUP, scr +
+// blockIdx.x * n_win * 3, not to the individual, so a launch over a whole store needs gridDim.x tables' worth of scratch and not a
+// second store.  Reusing it for the workgroup's next individual needs no barrier beyond the loop's own: post_block_switches
+// writes beta_w for w in [w0, w1) of the calling thread's block and its forward pass reads these rows only, in the same thread,
+// behind the writes in program order; no other thread reads or writes a row of that range, for this individual or the next
+// (w0, w1 depend on n_win and threadIdx.x alone).  What the loop's barriers order is LDS, as in its siblings.  A kernel of its
+// own, so that the others keep their code.  No atomics.
+template <bool CH, bool SH>
+__global__ __launch_bounds__(STATES_THREADS) void k_log2_switch_expect(const double *__restrict__ tabs, uint32_t n_win,
+                                                                       uint32_t n_tables, PenW W, const double *__restrict__ tables,
+                                                                       const uint32_t *__restrict__ starts_arg,
+                                                                       const int32_t *__restrict__ shift_arg,
+                                                                       double *__restrict__ scr, double *__restrict__ out)
+{
+    const uint32_t *__restrict__ starts = chains_of<CH>(starts_arg);
+    const int32_t *__restrict__ shift = steps_of<SH>(shift_arg);
+    __shared__ double mat[STATES_THREADS][9];       // 18 KB: B_b
+    __shared__ double fin[STATES_THREADS][3];       // F_b
+    __shared__ double gout[STATES_THREADS][3];      // G_b
+    __shared__ double part[STATES_THREADS][3];
+    __shared__ double T[512];                       // T1, T2
+    __shared__ int mexp[STATES_THREADS], fexp[STATES_THREADS];
+
+    const uint32_t b = threadIdx.x;
+    const Blocks B(n_win);
+    const uint32_t w0 = B.begin(b), w1 = B.end(b);
+    const bool own = b < B.nbk;
+    double *__restrict__ const beta = scr + (size_t)blockIdx.x * n_win * 3;
+
+    T[b] = tables[b], T[b + STATES_THREADS] = tables[b + STATES_THREADS];
+    __syncthreads();
+
+    for (uint32_t t = blockIdx.x; t < n_tables; t += gridDim.x) {
+        const PostIn in = {tabs + (size_t)t * n_win * 3, T, {W.a[0], W.a[1], W.a[2]}, starts, shift, {W.P[0], W.P[1], W.P[2]}};
+        // 1
+        if (own)
+            post_block_matrix(in, w0, w1, mat[b], &mexp[b]);
+        __syncthreads();
+        // 2
+        if (b == 0)
+            post_forward_walk(mat[0], mexp, B.nbk, fin[0], fexp);
+        else if (b == 64)
+            post_backward_walk(mat[0], B.nbk, gout[0]);
+        __syncthreads();
+        // 3, forward
+        double acc[3] = {0.0, 0.0, 0.0};
+        if (own)
+            post_block_switches<false>(in, w0, w1, gout[b], fin[b], fexp[b], beta, acc);
         // 5
         part[b][0] = acc[0], part[b][1] = acc[1], part[b][2] = acc[2];
         __syncthreads();
@@ -713,6 +784,22 @@ void launch_log2_switches(const double *win_log2, uint32_t n_win, uint32_t n_tar
     const PenW W{{a[0], a[1], a[2]}, {P[0], P[1], P[2]}};
     rows ? launch_switches<true>(win_log2, n_win, n_targets, W, tables, starts, shift, scr, out, st)
          : launch_switches<false>(win_log2, n_win, n_targets, W, tables, starts, shift, scr, out, st);
+}
+
+// (the grid is the caller's, who sized scr by it: switch_expect_grid)
+void launch_log2_switch_expect(const double *tabs, uint32_t n_win, uint32_t n_tables, uint32_t grid, const int64_t P[3],
+                               const double a[3], const double *tables, const uint32_t *starts, const int32_t *shift, double *scr,
+                               double *out, hipStream_t st)
+{
+    if (n_win == 0 || n_tables == 0 || grid == 0)
+        return;
+    const PenW W{{a[0], a[1], a[2]}, {P[0], P[1], P[2]}};
+    const dim3 g(grid < n_tables ? grid : n_tables), blk(STATES_THREADS);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, g, blk, 0, st, tabs, n_win, n_tables, W, tables, starts, shift, scr, out); };
+    if (shift)
+        starts ? go(k_log2_switch_expect<true, true>) : go(k_log2_switch_expect<false, true>);
+    else
+        starts ? go(k_log2_switch_expect<true, false>) : go(k_log2_switch_expect<false, false>);
 }
 
 void launch_log2_sample_records(const uint64_t *sout, uint32_t n_pairs, uint64_t *rec, hipStream_t st)

@@ -277,6 +277,68 @@ void switch_penalty_update(const double p[3], const double total[3], size_t T, c
     }
 }
 
+int switch_fit_step(const double p[3], const double total[3], size_t T, const double prior[3], const uint64_t counted[3],
+                    ibdg_fit_row *row, double next[3], int *stood)
+{
+    int64_t Pp[3], Pn[3];
+    int bad = 0;
+    if (states_penalties(p[0], p[1], p[2], Pp, &bad))
+        return 1 + bad;
+    for (int k = 0; k < 3; ++k)
+        row->p[k] = p[k], row->total[k] = total[k], row->prior[k] = prior[k], row->counted[k] = counted[k];
+    switch_penalty_update(p, total, T, prior, next);
+    (void)states_penalties(next[0], next[1], next[2], Pn, nullptr);      // (the update keeps next in [1e-300, 1])
+    *stood = 1;
+    for (int k = 0; k < 3; ++k)
+        if (Pn[k] - Pp[k] > 1 || Pp[k] - Pn[k] > 1)
+            *stood = 0;
+    return 0;
+}
+
+// The fit's loop over the cores: the arguments are checked once, the mask is made once, and every iteration is switches_core on
+// every table in order, on the NULL table for the prior, switch_counted_steps and switch_fit_step.
+int log2_fit_host(const char *fn, const double *const *tabs, size_t T, size_t n_win, const double p[3], const uint32_t *starts,
+                  size_t n_starts, const int32_t *shift, size_t max_iter, ibdg_fit_row *rows, size_t *n_rows, int *stood,
+                  double fitted[3], char *err, size_t err_len)
+{
+    int64_t P[3];
+    std::vector<uint32_t> own;
+    const uint32_t *mask;
+    static const double none[3] = {0.0, 0.0, 0.0};
+    const char *null_arg = !p ? "p" : !n_rows ? "n_rows" : !stood ? "stood" : !fitted ? "fitted" : max_iter && !rows ? "rows" :
+                           T && !tabs ? "tabs" : nullptr;
+    if (check_log_args(fn, null_arg, none, n_win, p ? p[0] : 1.0, p ? p[1] : 1.0, p ? p[2] : 1.0, "of the path", P, err, err_len) ||
+        own_mask(fn, starts, n_starts, n_win, own, &mask, err, err_len) || shift_check(fn, shift, n_win, err, err_len))
+        return 1;
+    for (size_t t = 0; t < T && n_win; ++t)
+        if (!tabs[t]) {
+            snprintf(err, err_len, "[::] ERROR in %s: NULL table of individual %zu", fn, t);
+            return 1;
+        }
+    double cur[3] = {p[0], p[1], p[2]};
+    *n_rows = 0, *stood = 0;
+    fitted[0] = cur[0], fitted[1] = cur[1], fitted[2] = cur[2];
+    if (T == 0)
+        return 0;
+    for (size_t it = 0; it < max_iter && !*stood; ++it) {
+        double total[3] = {0.0, 0.0, 0.0}, expect[3], prior[3], next[3];
+        uint64_t counted[3];
+        (void)states_penalties(cur[0], cur[1], cur[2], P, nullptr);     // (checked: p above, then the update's range)
+        for (size_t t = 0; t < T; ++t) {
+            switches_core(tabs[t], n_win, P, mask, shift, nullptr, expect);
+            for (int k = 0; k < 3; ++k)
+                total[k] = total[k] + expect[k];
+        }
+        switches_core(nullptr, n_win, P, mask, shift, nullptr, prior);
+        switch_counted_steps(n_win, P, mask, shift, counted);
+        (void)switch_fit_step(cur, total, T, prior, counted, &rows[it], next, stood);
+        *n_rows = it + 1;
+        for (int k = 0; k < 3; ++k)
+            cur[k] = fitted[k] = next[k];
+    }
+    return 0;
+}
+
 // The segment walk: one pass over the path in window order with the kernels' accumulator and summary functions (ibdg_states.h:
 // every quantity is exact and associative, so this is the kernels' result whatever their blocks).  post: the gammas [n_win][3],
 // or NULL for no support.

@@ -82,6 +82,13 @@ SYMBOLS = {
     "ibdg_window_log2_switches": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P]),
     "ibdg_window_log2_switches_prior": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P]),
     "ibdg_switch_penalty_update": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "ibdg_switch_fit_step": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
+    "ibdg_log2_fit_host": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P]),
+    "ibdg_log2_store_reserve": (C.c_int, [_P, C.c_size_t]),
+    "ibdg_log2_store_append": (C.c_int, [_P]),
+    "ibdg_log2_store_count": (C.c_size_t, [_P]),
+    "ibdg_log2_store_switches": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P]),
+    "ibdg_log2_store_fit": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P]),
     "ibdg_get_alt_counts": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
     "ibdg_last_run_ms": (C.c_int, [_P, _P]),
     "ibdg_run_ms": (C.c_int, [_P, C.c_uint, _P]),
@@ -383,6 +390,50 @@ def fit_switch_penalties_host(tables, p, iterations, starts=None, shift=None):
     return out
 
 
+# ibdg_fit_row (include/ibdgem_hip.h): 96 bytes, no padding
+FIT_ROW_DTYPE = np.dtype([("p", "<f8", (3,)), ("total", "<f8", (3,)), ("prior", "<f8", (3,)), ("counted", "<u8", (3,))])
+assert FIT_ROW_DTYPE.itemsize == 96
+
+
+def switch_fit_step(p, total, n_individuals, prior, counted):
+    """One step of the fit (ibdg_switch_fit_step): (row, a FIT_ROW_DTYPE record of the arguments; next float64 [3], the update's;
+    stood bool: no penalty's integer moved by more than one quantum)."""
+    lib = load_library()
+    p, total, prior = (np.ascontiguousarray(x, dtype=np.float64).reshape(3) for x in (p, total, prior))
+    counted = np.ascontiguousarray(counted, dtype=np.uint64).reshape(3)
+    row = np.zeros(1, dtype=FIT_ROW_DTYPE)
+    nxt = np.zeros(3, dtype=np.float64)
+    stood = C.c_int(0)
+    if lib.ibdg_switch_fit_step(p.ctypes.data, total.ctypes.data, int(n_individuals), prior.ctypes.data, counted.ctypes.data,
+                                row.ctypes.data, nxt.ctypes.data, C.addressof(stood)) != 0:
+        raise EngineError(lib.ibdg_last_error(None).decode())
+    return row[0], nxt, bool(stood.value)
+
+
+def log2_fit_host(tables, p, max_iter, starts=None, shift=None, n_win=None):
+    """The fit of the switch penalties over given window tables (a list of [n_win][3], one per individual of one site list) on
+    the host (ibdg_log2_fit_host): (rows, a FIT_ROW_DTYPE array with one record per iteration made; stood bool; fitted float64
+    [3]).  It ends behind the first iteration whose step stood, or behind max_iter.  n_win: the windows, for no tables."""
+    lib = load_library()
+    tabs = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 3) for t in tables]
+    n = tabs[0].shape[0] if tabs else int(n_win or 0)
+    if any(t.shape[0] != n for t in tabs):
+        raise ValueError("tables of different lengths")
+    ptrs = (C.c_void_p * max(len(tabs), 1))(*[t.ctypes.data for t in tabs])
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(3)
+    keep, ptr, ns = _starts(() if starts is None else starts)
+    sh = None if shift is None else _shift(shift, n)
+    rows = np.zeros(max(int(max_iter), 1), dtype=FIT_ROW_DTYPE)
+    n_rows, stood = C.c_size_t(0), C.c_int(0)
+    fitted = np.zeros(3, dtype=np.float64)
+    rc = lib.ibdg_log2_fit_host(C.addressof(ptrs) if tabs else None, len(tabs), n, p.ctypes.data, ptr, ns,
+                                None if sh is None else sh.ctypes.data, int(max_iter), rows.ctypes.data, C.addressof(n_rows),
+                                C.addressof(stood), fitted.ctypes.data)
+    if rc != 0:
+        raise EngineError(lib.ibdg_last_error(None).decode() or f"error {rc}")
+    return rows[:n_rows.value].copy(), bool(stood.value), fitted
+
+
 class Engine:
     def __init__(self, device=0, epsilon=0.02, max_cov=20, lib_path=None):
         self.lib = load_library(lib_path) if lib_path else load_library()
@@ -668,6 +719,38 @@ class Engine:
             p = switch_penalty_update(p, _total_in_order(expect), len(expect), prior)
             out[it] = p
         return out
+
+    def log2_store_reserve(self, n_individuals):
+        """An empty table store for up to n_individuals log2 window tables of the site list at hand (ibdg_log2_store_reserve).  A
+        new site list or panel empties it and takes the reserve away."""
+        self._chk(self.lib.ibdg_log2_store_reserve(self.ctx, int(n_individuals)))
+
+    def log2_store_append(self):
+        """The log2 tables of the last run's individuals onto the store's end, device to device (ibdg_log2_store_append)."""
+        self._chk(self.lib.ibdg_log2_store_append(self.ctx))
+
+    def log2_store_count(self):
+        """The individuals stored (ibdg_log2_store_count)."""
+        return int(self.lib.ibdg_log2_store_count(self.ctx))
+
+    def log2_store_switches(self, p01, p02, p12):
+        """The expected counted switches of every stored individual under the context's chains and steps, one launch over the
+        whole store (ibdg_log2_store_switches): float64 [count][3], the bytes of log2_switches_host per table.  Nothing kept from
+        earlier calls goes stale."""
+        expect = np.zeros((self.log2_store_count(), 3), dtype=np.float64)
+        self._chk(self.lib.ibdg_log2_store_switches(self.ctx, p01, p02, p12, expect.ctypes.data))
+        return expect
+
+    def log2_store_fit(self, p, max_iter):
+        """The fit over the store (ibdg_log2_store_fit): (rows FIT_ROW_DTYPE, stood bool, fitted float64 [3]), the bytes of
+        log2_fit_host over the stored tables with the context's chains and steps."""
+        p = np.ascontiguousarray(p, dtype=np.float64).reshape(3)
+        rows = np.zeros(max(int(max_iter), 1), dtype=FIT_ROW_DTYPE)
+        n_rows, stood = C.c_size_t(0), C.c_int(0)
+        fitted = np.zeros(3, dtype=np.float64)
+        self._chk(self.lib.ibdg_log2_store_fit(self.ctx, p.ctypes.data, int(max_iter), rows.ctypes.data, C.addressof(n_rows),
+                                               C.addressof(stood), fitted.ctypes.data))
+        return rows[:n_rows.value].copy(), bool(stood.value), fitted
 
     def get_log2_sample_path(self, t, k):
         """Draw k of individual t of the last window_log2_samples call, drawn again (ibdg_get_log2_sample_path): uint8 [n_win]."""

@@ -65,6 +65,8 @@ static const char *cache_fn = NULL, *dump_panel_fn = NULL;
 static int opt_stats_only = 0, has_arm = 0;
 static int opt_log_summary = 0;          /* --log-summary: the summary's likelihoods as log2, from the engine's option "log_windows" */
 static int opt_posteriors = 0;           /* --posteriors: with --log-stats --states, the forward-backward probabilities of the states beside the path */
+static long opt_fit = 0;                 /* --fit-penalties N: with --log-stats --states, the update of --switches repeated at most N times over the kept log tables of all the pileup's individuals */
+static int has_fit = 0;
 static int opt_switches = 0;             /* --switches: with --log-stats --states, the probability of a switch at every step, the expected switches and the penalties they suggest */
 static int opt_segments = 0;             /* --segments: with --log-stats --states, the path's segments with their scores and support */
 static int has_chain_gap = 0;            /* --chain-gap BP: with --log-stats --states, a window more than BP behind the end of the one before starts a chain */
@@ -95,6 +97,7 @@ static struct option longopts[] = {
     {"posteriors", no_argument, &opt_posteriors, 1},
     {"segments", no_argument, &opt_segments, 1},
     {"switches", no_argument, &opt_switches, 1},
+    {"fit-penalties", required_argument, 0, 1016},
     {"chain-gap", required_argument, 0, 1011},
     {"switch-scale", required_argument, 0, 1012},
     {"genetic-map", required_argument, 0, 1013},
@@ -247,6 +250,16 @@ static void usage(int code)
           "                            (# Prior), the steps counted, the penalties used and the penalties one multiplicative\n"
           "                            step p * total / (individuals * prior) suggests (# Next): running again with these\n"
           "                            repeats the step.  With --stats-only only the second file, on one device made there\n"
+          "  --fit-penalties N         with --log-stats --states (not with -v or -D): keep the log2 window table of every\n"
+          "                            comparison individual of the pileup's run and, after the last, repeat the step of\n"
+          "                            --switches over all of them, starting from --p01, --p02, --p12: at most N times (1 ..\n"
+          "                            1000), ending behind the first step that moves no penalty by more than 2^-16 bit (the\n"
+          "                            resolution the penalties are read at).  <out>/<pileup-name>.logibdfit.txt has a row per\n"
+          "                            iteration (the penalties used, the expected switches' totals, the prior, the steps\n"
+          "                            counted, total / (individuals * prior)), then # Individuals, # Iterations with `stood`\n"
+          "                            or `limit`, and # Fitted with 17 digits.  Every other file is made with the penalties\n"
+          "                            given.  One device keeps the tables there (24 bytes per window and individual); several\n"
+          "                            devices, or none, keep them on the host and iterate on --threads threads\n"
           "  --seed N                  with --sample-paths: the seed of the draws, 0 .. 2^64 - 1 (default 1)\n"
           "  --p01, --p02, --p12 FLOAT with --states: penalties for switching between IBD0 and IBD1, IBD0 and IBD2,\n"
           "                            IBD1 and IBD2 (defaults 1e-3, 1e-6, 1e-3, as hiddengem's)\n"
@@ -1990,6 +2003,8 @@ typedef struct {
     int tables_stay;                         /* --stats-only: no window table leaves the device */
     int dev_states;                          /* --log-stats --states --stats-only on one context: the paths are found on the device */
     int reported;                            /* a failure was reported here already (not an engine error) */
+    int fit_store;                           /* --fit-penalties on one context: every batch's log tables are kept in the engine's store, */
+    size_t fit_reserve;                      /* ... which is sized for this many individuals, all of the run */
     /* ---- the slice [a, b) of the site list at hand (shards_fill) ---- */
     const uint32_t *row;                     /* the list's panel rows as this context counts them, */
     const uint32_t *s_row;                   /* ... and as the host does, for the windows' positions */
@@ -2127,7 +2142,7 @@ static int conv_positions(dev_conv *c, size_t n_win)
  * them for every run over the list */
 static int chains_on_device(dev_conv *c)
 {
-    if (!has_chain_gap || !c->dev_states)
+    if (!has_chain_gap || !(c->dev_states || c->fit_store))
         return 0;
     const size_t n_win = ibdg_num_windows(c->eng);
     if (conv_positions(c, n_win))
@@ -2140,7 +2155,7 @@ static int chains_on_device(dev_conv *c)
 /* --switch-scale where the paths are found on the device: likewise, the step shifts of a new site list */
 static int steps_on_device(dev_conv *c)
 {
-    if (!has_switch_scale || !c->dev_states)
+    if (!has_switch_scale || !(c->dev_states || c->fit_store))
         return 0;
     const size_t n_win = ibdg_num_windows(c->eng);
     if (conv_positions(c, n_win))
@@ -2260,7 +2275,10 @@ static int conv_list(dev_conv *c)
     if (!c->list_on_device && ibdg_upload_sites(c->eng, c->row + c->a, c->nr + c->a, c->na + c->a, c->fo ? c->fo + c->a : NULL,
                                                 c->b - c->a, (unsigned)opt_window))
         return 1;
-    return chains_on_device(c) || steps_on_device(c);
+    if (chains_on_device(c) || steps_on_device(c))
+        return 1;
+    /* --fit-penalties: the store belongs to the site list, and is sized for all the run's individuals */
+    return c->fit_store && ibdg_log2_store_reserve(c->eng, c->fit_reserve);
 }
 
 /* the next batch runs while the host goes on with this one's statistics and files */
@@ -2289,6 +2307,9 @@ static int conv_batch(dev_conv *c)
     }
     c->ahead_of = NULL;
     if (device_stats(c))
+        return 1;
+    /* --fit-penalties: the batch's log tables onto the store's end, before a look-ahead replaces them */
+    if (c->fit_store && (!same_run_size(c) || ibdg_log2_store_append(c->eng)))
         return 1;
     if (!c->tables_stay && (c->next || c->n_targets > 1)) {
         /* (the library is asked in runs with per-site tables too, as it always was: the calls a context sees are pinned) */
@@ -2774,6 +2795,8 @@ typedef struct {
     ind_stats *res;                             /* the individual's lines of the run's statistics files: the twin's results go here */
     uint64_t (*smp_tot)[9];                     /* --sample-paths: the run's totals [K][9], which the individual's draws are added to */
     struct sw_prior *swp;                       /* --switches: the prior of the site list all individuals share, or NULL (each its own) */
+    struct fit_keep *fit;                       /* --fit-penalties on the host: where the job leaves a copy of its log table, or NULL */
+    size_t ti;                                  /* ... and which of the run's individuals it is */
     hg_path hgp;                                /* the slot's path arrays and text buffer (kept between individuals) */
     char *hg_buf;
     size_t hg_cap;
@@ -2787,6 +2810,20 @@ struct sw_prior {
     uint64_t counted[3];
 };
 static pthread_mutex_t g_sw_prior_lock = PTHREAD_MUTEX_INITIALIZER;
+
+/* --fit-penalties where no context holds every individual's whole table (windows spread over several devices, or no device):
+ * the run keeps a copy of every individual's gathered log table, 24 bytes per window and individual on the host (2.08 GB at
+ * 34 599 windows x 2504), left here by the output jobs, and the chain starts and step shifts of the site list they share, left
+ * by the first job that has them. */
+struct fit_keep {
+    double **tabs;                              /* [individuals]: each a job's copy, owned here */
+    size_t n_win;
+    int have_lc;
+    uint32_t *starts;
+    size_t n_starts;
+    int32_t *shift;
+};
+static pthread_mutex_t g_fit_keep_lock = PTHREAD_MUTEX_INITIALIZER;
 
 enum { OUT_SLOTS = 12, MAX_WORKERS = 64 };
 static out_job g_outs[MAX_WORKERS][OUT_SLOTS];  /* per worker (one per context with --pileup-list, else one) */
@@ -3103,6 +3140,52 @@ static int switches_individual(out_job *o, const log_chains *lc)
     return bad;
 }
 
+/* --fit-penalties on the host: a copy of the individual's log table stays with the run (the table itself goes with the job), and
+ * the list's chain starts and step shifts with the first job to come by */
+static int fit_keep_individual(out_job *o, const log_chains *lc)
+{
+    struct fit_keep *k = o->fit;
+    if (!k)
+        return 0;
+    const size_t n = o->wt.w.n_win, bytes = (n ? n : 1) * 3 * sizeof(double);
+    double *tab = malloc(bytes);
+    if (!tab) {
+        fprintf(o->err, "[::] ERROR: out of memory for the log table of %s that --fit-penalties keeps (%zu bytes: 24 per window and individual).\n",
+                o->tname, bytes);
+        return 1;
+    }
+    memcpy(tab, o->wt.log, n * 3 * sizeof(double));
+    int bad = 0;
+    pthread_mutex_lock(&g_fit_keep_lock);
+    if (!k->have_lc) {                          /* the first job to come by: the list's chain starts and step shifts, both or neither */
+        const size_t n_starts = lc->starts ? lc->n_starts : 0;
+        uint32_t *starts = n_starts ? malloc(n_starts * sizeof *starts) : NULL;
+        int32_t *shift = lc->shift ? malloc((n ? n : 1) * sizeof *shift) : NULL;
+        if ((n_starts && !starts) || (lc->shift && !shift)) {
+            fprintf(o->err, "[::] ERROR: out of memory for the %zu chain starts and %zu step shifts that --fit-penalties keeps.\n", n_starts,
+                    lc->shift ? n : (size_t)0);
+            free(starts);
+            free(shift);
+            bad = 1;
+        } else {
+            if (n_starts) memcpy(starts, lc->starts, n_starts * sizeof *starts);
+            if (shift) memcpy(shift, lc->shift, n * sizeof *shift);
+            k->n_win = n; k->starts = starts; k->n_starts = n_starts; k->shift = shift;
+            k->have_lc = 1;
+        }
+    }
+    if (!bad && k->n_win != n) {
+        fprintf(o->err, "[::] ERROR: --fit-penalties: %s has %zu windows, not the %zu of the individuals before it.\n", o->tname, n, k->n_win);
+        bad = 1;
+    }
+    pthread_mutex_unlock(&g_fit_keep_lock);
+    if (bad)
+        free(tab);
+    else
+        k->tabs[o->ti] = tab;                   /* (the individual's own slot: no other job writes it) */
+    return bad;
+}
+
 static int log_states_individual(out_job *o)
 {
     const size_t n = o->wt.w.n_win;
@@ -3143,6 +3226,7 @@ static int log_states_individual(out_job *o)
         bad = segments_individual(o, &lc) || bad;
         bad = samples_individual(o, &lc) || bad;
         bad = switches_individual(o, &lc) || bad;
+        bad = fit_keep_individual(o, &lc) || bad;
     }
     free(lc.pos);
     free(lc.starts);
@@ -3557,7 +3641,7 @@ typedef struct {
     uint32_t *row_pre_off;
 } site_list;
 
-enum { N_RUN_FILES = 5 };           /* RUN_FILES below */
+enum { N_RUN_FILES = 6 };           /* RUN_FILES below */
 
 typedef struct {
     /* ---- the pileup's run ---- */
@@ -3569,6 +3653,14 @@ typedef struct {
     size_t n_site_out;              /* entries of an individual's per-site array */
     ind_stats *res;                 /* per individual, what the run's statistics files are written from (run_end) */
     struct sw_prior sw_prior;       /* --switches: the shared site list's prior, made by the first output job */
+    /* --fit-penalties: on the device where one context holds every individual's whole table (fit_dev: its store), else over
+     * the copies the output jobs leave in fit_keep; the iterations' rows and the verdict, made by run_end before the files */
+    int fit_dev;
+    struct fit_keep fit_keep;
+    ibdg_fit_row *fit_rows;
+    size_t fit_n;
+    int fit_stood;
+    double fitted[3];
     uint64_t (*smp_tot)[9], *smp_col;   /* --sample-paths: draw k summed over the individuals so far [K][9]; scratch [K] for their columns */
     FILE *run_file[N_RUN_FILES];    /* the files of RUN_FILES, open from run_begin to run_end */
     char *run_fn[N_RUN_FILES];
@@ -3623,9 +3715,13 @@ static void run_modes(pile_run *r)
     /* ... or in the log domain (--log-stats), where one context has the whole table and finds the paths itself */
     r->dev_states = opt_stats_only && opt_states && opt_log_stats && !no_engine && r->w->n_eng == 1;
     r->tables_stay = r->tables_stay || r->dev_states;
+    /* --fit-penalties: one context holds every individual's whole table over the one site list (-v and -D are refused) and
+     * keeps them in its store; windows spread over several contexts, or no device, leave the tables to the host */
+    r->fit_dev = has_fit && !no_engine && r->w->n_eng == 1 && r->one_list;
     for (int d = 0; d < r->w->n_eng; ++d) {      /* what the conversation with each context takes from these */
         dev_conv *c = &r->w->conv[d];
         c->err = r->err; c->bg_count = g_bg_count; c->pu_id = (int)r->pj->pu_id; c->reported = 0;
+        c->fit_store = r->fit_dev; c->fit_reserve = g_targets.n;
         c->shared_list = r->batchable; c->list_on_device = r->dev_v;
         c->tables_stay = r->tables_stay; c->dev_states = r->dev_states;
     }
@@ -3768,7 +3864,33 @@ static void write_switches_file(pile_run *r, FILE *f)
     fprintf(f, "# Next\t%.6e\t%.6e\t%.6e\n", next[0], next[1], next[2]);
 }
 
-/* <out>/<pileup-name>.[log]<kind>.txt (the last four exist with --log-stats only), in the order they are opened and written.
+/* --fit-penalties: a row per iteration made (run_fit, before the files), with the penalties it used, the individuals' total, one
+ * individual's prior, the counted steps and total / (T * prior) -- nan where the update keeps p --, then the verdict and the
+ * fitted penalties with the digits that give the doubles back */
+static void write_fit_file(pile_run *r, FILE *f)
+{
+    const size_t T = g_targets.n;
+    fprintf(f, "# Iteration\tP01\tP02\tP12\tE_SW01\tE_SW02\tE_SW12\tPRIOR01\tPRIOR02\tPRIOR12\tCOUNTED01\tCOUNTED02\tCOUNTED12\tRATIO01\tRATIO02\tRATIO12\n");
+    for (size_t i = 0; i < r->fit_n; ++i) {
+        const ibdg_fit_row *w = &r->fit_rows[i];
+        fprintf(f, "%zu\t%.6e\t%.6e\t%.6e\t%.6f\t%.6f\t%.6f\t%.6f\t%.6f\t%.6f\t%llu\t%llu\t%llu", i + 1, w->p[0], w->p[1], w->p[2], w->total[0],
+                w->total[1], w->total[2], w->prior[0], w->prior[1], w->prior[2], (unsigned long long)w->counted[0],
+                (unsigned long long)w->counted[1], (unsigned long long)w->counted[2]);
+        for (int k = 0; k < 3; ++k) {
+            const int ok = isfinite(w->total[k]) && isfinite(w->prior[k]) && w->total[k] > 0.0 && w->prior[k] > 0.0;
+            if (ok)
+                fprintf(f, "\t%.6f", w->total[k] / ((double)T * w->prior[k]));
+            else
+                fputs("\tnan", f);
+        }
+        fputc('\n', f);
+    }
+    fprintf(f, "# Individuals\t%zu\n", T);
+    fprintf(f, "# Iterations\t%zu\t%s\n", r->fit_n, r->fit_stood ? "stood" : "limit");
+    fprintf(f, "# Fitted\t%.17g\t%.17g\t%.17g\n", r->fitted[0], r->fitted[1], r->fitted[2]);
+}
+
+/* <out>/<pileup-name>.[log]<kind>.txt (the last five exist with --log-stats only), in the order they are opened and written.
  * armstats.txt is not among them: it is opened where it is written, in run_end. */
 static const struct {
     const int *on;
@@ -3780,6 +3902,7 @@ static const struct {
     {&opt_segments, "ibdsegments", "IBD-state segments file", write_segments_file},
     {&has_sample_paths, "ibdsamples", "IBD-state samples file", write_samples_file},
     {&opt_switches, "ibdswitches", "IBD-state switches file", write_switches_file},
+    {&has_fit, "ibdfit", "fitted switch penalties file", write_fit_file},
 };
 
 /* the run's arrays and its statistics files */
@@ -3807,6 +3930,13 @@ static int run_begin(pile_run *r)
             SFAIL("[::] ERROR: out of memory for %lu draws.\n", opt_sample_paths);
         for (int d = 0; d < r->w->n_eng; ++d)
             r->w->conv[d].smp_tot = r->smp_tot;
+    }
+    if (has_fit) {
+        r->fit_rows = calloc((size_t)opt_fit, sizeof *r->fit_rows);
+        if (!r->fit_dev)
+            r->fit_keep.tabs = calloc(g_targets.n + 1, sizeof *r->fit_keep.tabs);
+        if (!r->fit_rows || (!r->fit_dev && !r->fit_keep.tabs))
+            SFAIL("[::] ERROR: out of memory for %ld iterations over %zu individuals.\n", opt_fit, g_targets.n);
     }
     /* opened before the run, like the individuals' files: a directory that cannot be written stops the run at once */
     for (int k = 0; k < N_RUN_FILES; ++k) {
@@ -4290,6 +4420,8 @@ static int output_start(pile_run *r)
     o->res = &r->res[r->ti];
     o->smp_tot = r->smp_tot;
     o->swp = r->one_list ? &r->sw_prior : NULL;
+    o->fit = has_fit && !r->fit_dev ? &r->fit_keep : NULL;
+    o->ti = r->ti;
     if (outputs_open(r, o))
         return 1;
     const int threads = all_threads();
@@ -4304,10 +4436,104 @@ static int output_start(pile_run *r)
     return !o->running && o->failed;
 }
 
+/* ---- --fit-penalties: the iterations, after the run's last individual ---- */
+/* the host route's share of one iteration: a thread's individuals (k, k + n, ...), each its own slot of expect */
+typedef struct {
+    const struct fit_keep *keep;
+    const double *p;
+    double *expect;                 /* [individuals][3] */
+    size_t first, step, n_ind;
+    int failed;
+    pthread_t th;
+} fit_part;
+
+static void *fit_part_run(void *arg)
+{
+    fit_part *f = arg;
+    const struct fit_keep *k = f->keep;
+    uint64_t counted[3];
+    for (size_t ti = f->first; ti < f->n_ind && !f->failed; ti += f->step)
+        f->failed = ibdg_log2_switches_host(k->tabs[ti], k->n_win, f->p[0], f->p[1], f->p[2], k->starts, k->n_starts, k->shift, NULL,
+                                            f->expect + 3 * ti, counted) != 0;
+    return NULL;
+}
+
+/* The fit over the tables the output jobs kept: per iteration every individual's expectations on --threads threads (an
+ * individual's are its own call's, whoever makes it), their sum in the order of the panel from 0.0, the prior from the table
+ * that says nothing, ibdg_switch_fit_step -- the loop of ibdg_log2_fit_host, whose bytes these are for any number of threads. */
+static int fit_on_host(pile_run *r)
+{
+    const struct fit_keep *k = &r->fit_keep;
+    const size_t T = g_targets.n;
+    const int n_th = all_threads() < 1 ? 1 : all_threads() > 64 ? 64 : all_threads();
+    double cur[3] = {opt_p01, opt_p02, opt_p12}, *expect = malloc((T ? T : 1) * 3 * sizeof *expect);
+    fit_part part[64];
+    if (!expect)
+        SFAIL("[::] ERROR: out of memory for the expectations of %zu individuals.\n", T);
+    for (size_t ti = 0; ti < T; ++ti)
+        if (!k->tabs[ti]) {
+            free(expect);
+            SFAIL("[::] ERROR: --fit-penalties: no log table was kept for %s.\n", g_ids.names[g_targets.idx[ti]]);
+        }
+    memcpy(r->fitted, cur, sizeof cur);
+    for (long it = 0; T && it < opt_fit && !r->fit_stood; ++it) {
+        double total[3] = {0.0, 0.0, 0.0}, prior[3], next[3];
+        uint64_t counted[3];
+        int bad = 0;
+        int started[64] = {0};
+        for (int t = 0; t < n_th; ++t) {
+            part[t] = (fit_part){.keep = k, .p = cur, .expect = expect, .first = (size_t)t, .step = (size_t)n_th, .n_ind = T};
+            started[t] = t < n_th - 1 && pthread_create(&part[t].th, NULL, fit_part_run, &part[t]) == 0;
+        }
+        for (int t = 0; t < n_th; ++t)
+            if (!started[t])                     /* (the last share, or no thread to be had: it runs here) */
+                fit_part_run(&part[t]);
+        for (int t = 0; t < n_th; ++t) {
+            if (started[t])
+                pthread_join(part[t].th, NULL);
+            bad |= part[t].failed;
+        }
+        for (size_t ti = 0; ti < T; ++ti)
+            for (int s = 0; s < 3; ++s)
+                total[s] += expect[3 * ti + s];
+        bad = bad || ibdg_log2_switches_host(NULL, k->n_win, cur[0], cur[1], cur[2], k->starts, k->n_starts, k->shift, NULL, prior, counted) ||
+              ibdg_switch_fit_step(cur, total, T, prior, counted, &r->fit_rows[it], next, &r->fit_stood);
+        if (bad) {
+            free(expect);
+            SFAIL("%s\n", ibdg_last_error(NULL));
+        }
+        r->fit_n = (size_t)it + 1;
+        memcpy(cur, next, sizeof cur);
+        memcpy(r->fitted, next, sizeof next);
+    }
+    free(expect);
+    return 0;
+}
+
+static int run_fit(pile_run *r)
+{
+    if (!has_fit)
+        return 0;
+    if (r->fit_dev) {
+        ibdg_ctx *eng = r->w->conv[0].eng;
+        const double p[3] = {opt_p01, opt_p02, opt_p12};
+        if (ibdg_log2_store_count(eng) != g_targets.n)
+            SFAIL("[::] ERROR: --fit-penalties: the device holds the log tables of %zu individuals, not of the run's %zu.\n",
+                  ibdg_log2_store_count(eng), g_targets.n);
+        if (ibdg_log2_store_fit(eng, p, (size_t)opt_fit, r->fit_rows, &r->fit_n, &r->fit_stood, r->fitted))
+            SFAIL("%s\n", ibdg_last_error(eng));
+    } else if (fit_on_host(r))
+        return 1;
+    phase("fit of the switch penalties (--fit-penalties)");
+    return 0;
+}
+
 /* the files the run writes once, after its last individual */
 static int run_end(pile_run *r)
 {
     const idlist_t targets = g_targets;
+    if (run_fit(r))
+        return 1;
     if (r->arm_on) {
         /* one file for the run, written here once: the lines in comparison order, as bin/chrarm-stats.py prints them */
         char *arm_fn;
@@ -4363,6 +4589,11 @@ static void run_release(pile_run *r)
     for (size_t ti = 0; r->res && ti < g_targets.n; ++ti)
         free(r->res[ti].smp_row);
     free(r->res); free(sl->row_pre); free(sl->row_pre_off); free(r->smp_tot); free(r->smp_col);
+    for (size_t ti = 0; r->fit_keep.tabs && ti < g_targets.n; ++ti)
+        free(r->fit_keep.tabs[ti]);
+    free(r->fit_keep.tabs); free(r->fit_keep.starts); free(r->fit_keep.shift); free(r->fit_rows);
+    memset(&r->fit_keep, 0, sizeof r->fit_keep);
+    r->fit_rows = NULL;
     r->res = NULL;
     r->smp_tot = NULL, r->smp_col = NULL;
     sl->row_pre = NULL;
@@ -4567,6 +4798,17 @@ int main(int argc, char **argv)
             has_seed = 1;
             break;
         }
+        case 1016: {
+            char *end = NULL;
+            errno = 0;
+            opt_fit = strtol(optarg, &end, 10);
+            if (!isdigit((unsigned char)optarg[0]) || *end || errno || opt_fit < 1 || opt_fit > 1000) {
+                fprintf(stderr, "[::] ERROR: Invalid number of iterations (--fit-penalties) '%s' (must be an integer in 1 .. 1000).\n", optarg);
+                exit(1);
+            }
+            has_fit = 1;
+            break;
+        }
         case 1006:
             if (!parse_arm_range(optarg)) {
                 fprintf(stderr, "[::] ERROR: Invalid centromeric range (--arm-stats) '%s' (must be START,END with START <= END).\n", optarg);
@@ -4620,6 +4862,9 @@ int main(int argc, char **argv)
     if (genetic_map_fn && !has_switch_scale) { fprintf(stderr, "[::] ERROR: --genetic-map needs --switch-scale X: it says in which unit X and the distances between windows are measured.\n"); exit(1); }
     if (opt_switches && opt_plan) { fprintf(stderr, "[::] ERROR: --switches writes files --plan does not make; use one of them.\n"); exit(1); }
     if (opt_switches && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --switches needs --log-stats and --states: it is the probability of a switch at every step under the weights whose best path they find, with their --p01, --p02, --p12.\n"); exit(1); }
+    if (has_fit && opt_plan) { fprintf(stderr, "[::] ERROR: --fit-penalties writes a file --plan does not make; use one of them.\n"); exit(1); }
+    if (has_fit && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --fit-penalties needs --log-stats and --states: it fits the switch penalties of the weights whose best path they find, starting from their --p01, --p02, --p12.\n"); exit(1); }
+    if (has_fit && (has_v || has_D)) { fprintf(stderr, "[::] ERROR: --fit-penalties cannot be combined with %s: every individual then has a site list of its own, and the fit is over the tables of one list.\n", has_v ? "-v" : "-D"); exit(1); }
     if (has_sample_paths && opt_plan) { fprintf(stderr, "[::] ERROR: --sample-paths writes files --plan does not make; use one of them.\n"); exit(1); }
     if (has_sample_paths && (!opt_log_stats || !opt_states)) { fprintf(stderr, "[::] ERROR: --sample-paths needs --log-stats and --states: it draws paths from the distribution over all paths of the weights whose best path they find, with their --p01, --p02, --p12.\n"); exit(1); }
     if (has_seed && !has_sample_paths) { fprintf(stderr, "[::] ERROR: --seed is the seed of --sample-paths K.\n"); exit(1); }

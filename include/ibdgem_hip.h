@@ -430,6 +430,54 @@ int ibdg_window_log2_switches_prior(ibdg_ctx *ctx, double p01, double p02, doubl
  * prior[3]: expect of ibdg_log2_switches_host on the NULL table with the same penalties, chains and shifts.  Plain fp64.  Whether
  * repeating the step converges is an observation on simulated input, not a theorem.  Errors: a NULL argument. */
 int ibdg_switch_penalty_update(const double p[3], const double total[3], size_t n_individuals, const double prior[3], double next[3]);
+
+/* ---- the fit of the switch penalties: the step above repeated over the kept tables of many individuals ---- */
+/* One iteration of the fit as it is reported: the penalties it used, the individuals' expectations added in their order from
+ * 0.0, one individual's prior and the counted steps.  96 bytes, no padding. */
+typedef struct {
+    double p[3], total[3], prior[3];
+    uint64_t counted[3];
+} ibdg_fit_row;
+/* One step of the fit, the same for every route: row = its arguments, next = ibdg_switch_penalty_update's, and *stood = 1 iff
+ * for every pair the penalty's integer, llrint(log2(.) * 65536) clamped below at -2^40 (the quanta the kernels read a penalty
+ * in), differs between next and p by at most one -- a step below what the model resolves --, else 0.  Errors: a NULL argument,
+ * a p[k] outside (0, 1] or NaN. */
+int ibdg_switch_fit_step(const double p[3], const double total[3], size_t n_individuals, const double prior[3],
+                         const uint64_t counted[3], ibdg_fit_row *row, double next[3], int *stood);
+/* The fit on the host, one thread: from p, at most max_iter times { ibdg_log2_switches_host's expect of every table tabs[t]
+ * [n_win][3], t < n_individuals, under starts and shift (as there), added in that order from 0.0; the prior and the counted steps
+ * from the NULL table; ibdg_switch_fit_step; the next iteration takes `next` }, ending after the first iteration whose step
+ * stood.  rows[max_iter]: an ibdg_fit_row per iteration made, *n_rows of them; *stood: whether the last one stood; fitted[3]: its
+ * `next`.  max_iter == 0 or n_individuals == 0: no rows, *stood = 0, fitted = p.  Needs no device.  Errors
+ * (ibdg_last_error(NULL)): a NULL argument (rows may be NULL with max_iter == 0, tabs with n_individuals == 0), a NULL table
+ * with n_win > 0, and those of ibdg_log2_switches_host. */
+int ibdg_log2_fit_host(const double *const *tabs, size_t n_individuals, size_t n_win, const double p[3], const uint32_t *starts,
+                       size_t n_starts, const int32_t *shift, size_t max_iter, ibdg_fit_row *rows, size_t *n_rows, int *stood,
+                       double fitted[3]);
+/* The table store: the log2 window tables of many runs over ONE site list kept on the device, [capacity][n_win][3] doubles, so
+ * that the fit can run over every individual of a pileup.  It belongs to the site list at hand: an upload of sites or of a panel
+ * empties it and takes the reserve away; chains, steps and runs leave it alone.
+ * ibdg_log2_store_reserve: an empty store for up to n_individuals tables (no memory yet: the buffer is allocated by the first
+ * append, when the number of windows is known; a failed allocation is an error that names the bytes asked for).  Errors: no
+ * valid site list (the store belongs to one), more than 2^31 - 1 individuals.
+ * ibdg_log2_store_append: the log2 table of every comparison individual of the last ibdg_run (or the one set by
+ * ibdg_set_window_log2) goes onto the store's end, device to device, behind the table's writers; complete when the call returns,
+ * so the next run may replace the table.  Errors: no results, a run without option log_windows, no reserve, more individuals
+ * than reserved.
+ * ibdg_log2_store_count: the individuals stored (0 for an emptied store). */
+int ibdg_log2_store_reserve(ibdg_ctx *ctx, size_t n_individuals);
+int ibdg_log2_store_append(ibdg_ctx *ctx);
+size_t ibdg_log2_store_count(ibdg_ctx *ctx);
+/* expect[count][3] of ibdg_window_log2_switches for every stored individual under the context's chains and steps, in one launch
+ * over the whole store (k_log2_switch_expect): the same bytes as ibdg_log2_switches_host per table.  Scratch of its own (a table's
+ * worth per launched workgroup): the posteriors, segment records and draws kept from earlier calls stay as they are.  24 bytes
+ * per individual leave the device.  Errors: those of ibdg_window_log2_switches, no reserve. */
+int ibdg_log2_store_switches(ibdg_ctx *ctx, double p01, double p02, double p12, double *expect);
+/* ibdg_log2_fit_host over the store: per iteration ibdg_log2_store_switches, the sum on the host in store order, the prior of
+ * ibdg_window_log2_switches_prior, ibdg_switch_fit_step.  The same bytes as ibdg_log2_fit_host over the stored tables with the
+ * context's chains and steps.  Errors: those of ibdg_log2_store_switches, a NULL argument. */
+int ibdg_log2_store_fit(ibdg_ctx *ctx, const double p[3], size_t max_iter, ibdg_fit_row *rows, size_t *n_rows, int *stood,
+                        double fitted[3]);
 /* Alt-allele count of panel rows [first_row, first_row+n): out[n] (for tests). */
 int ibdg_get_alt_counts(ibdg_ctx *ctx, size_t first_row, size_t n, uint32_t *out);
 
